@@ -5,9 +5,9 @@ A "step" is one pass of the hot path (query voxelise -> fetch_VoI -> R-POD -> Sc
 map write-back; reference OfflineMapUpdater.cpp:237-294) over one synthetic scan against a map that is
 resident in HBM.  Inputs (map and scans) are in HBM before the timed region.
 
-  python bench.py --gpus N --steps K --warmup W [--workload W] [--mode M]
+  python bench.py --gpus N --steps K --warmup W [--workload W] [--mode M] [--dump-outputs DIR]
 
---gpus N > 1 without a torchrun environment re-executes itself under
+--gpus N > 1 without a torchrun environment runs itself again, in a child process, under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, one rank per GPU
 (backend "nccl" = RCCL).  It refuses to run with fewer than N devices.
 
@@ -34,15 +34,10 @@ import time
 
 import numpy as np
 
-# (several handles in one process -- seq-per-gpu mode -- need more hardware queues than HIP's default of 4, or a handle's two query streams can
-# share one and its chains serialise: gpurun_out/r03ap.  Read when the HIP runtime starts, i.e. before torch or the library touch the device;
-# liberasor_hip.so sets the same default when it is loaded)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-PEAK_HBM_GBPS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md
+PEAK_HBM_GBPS = 8000.0  # MI355X HBM3E peak
 
 WORKLOADS = {
     # name: (params preset, R-POD override, lidar, map spacing, streets, description)
@@ -61,13 +56,16 @@ SEQS = ["00", "01", "02", "05", "07"]  # BASELINE config[2]
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (with the default --repeats 1: exactly this many)")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=7,
-                    help="the K-step timed pass is repeated this many times inside ONE invocation, the sequence simply continuing (each pass "
-                         "bracketed by barrier + device synchronisation like the contract's one pass); ms_per_step / value are the MEDIAN pass, "
-                         "ms_per_step_min / _max the spread.  One 20-step pass is a 4 ms sample on boxes that differ by +-8 %% (VERDICT r04).  "
-                         "Applies where one sequence per rank is stepped by the native node loop (the default mode); otherwise 1")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="run the K-step timed pass this many times inside ONE invocation, the sequence simply continuing (each pass "
+                         "bracketed by barrier + device synchronisation like the contract's one pass): K x repeats timed steps; ms_per_step / "
+                         "value are the MEDIAN pass, ms_per_step_min / _max the spread.  Applies where one sequence per rank is stepped by the "
+                         "native node loop (the default mode); otherwise 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all; larger arrays as a fixed, seeded sample of their rows), see dump_outputs()")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="seq05")
     ap.add_argument("--mode", choices=["replicas", "seq-per-gpu"], default="replicas")
     ap.add_argument("--large-scale-mode", choices=["off", "on"], default="off",
@@ -138,7 +136,9 @@ def respawn_under_torchrun(args):
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    # a child process, not exec: this process has already opened the GPU (device_count above)
+    import subprocess
+    raise SystemExit(subprocess.call(cmd))
 
 
 def device_source_hash():
@@ -248,25 +248,27 @@ def make_lidar(wl, args):
 _CAST = None
 
 
+def _cast_init(world, lidar, poses):
+    global _CAST
+    _CAST = (world, lidar, poses)
+
+
 def _cast_one(k):
     world, lidar, poses = _CAST
     return world.cast(poses[k], lidar, k)
 
 
 def cast_scans(world, lidar, poses):
-    """world.cast for every pose, on up to 16 host cores (fork: the children inherit the world, run numpy only and return the scan)"""
-    global _CAST
+    """world.cast for every pose, on up to 16 host cores.  The workers are fresh interpreters (spawn), not forks: this process has the
+    GPU open by now, and a fork would carry its device files into every worker.  They receive the world once, run numpy only and
+    return the scan; the scans are the same as a serial cast's (each one is seeded by its frame)."""
     n = len(poses)
     workers = min(16, os.cpu_count() or 1, n)
     if workers <= 1 or n < 8 or os.environ.get("ERASOR_BENCH_SERIAL_CAST"):
         return [world.cast(poses[k], lidar, k) for k in range(n)]
     import multiprocessing as mp
-    _CAST = (world, lidar, poses)
-    try:
-        with mp.get_context("fork").Pool(workers) as pool:
-            return pool.map(_cast_one, range(n), chunksize=max(1, n // (4 * workers)))
-    finally:
-        _CAST = None
+    with mp.get_context("spawn").Pool(workers, initializer=_cast_init, initargs=(world, lidar, poses)) as pool:
+        return pool.map(_cast_one, range(n), chunksize=max(1, n // (4 * workers)))
 
 
 class Sequence:
@@ -445,6 +447,48 @@ def verify_prefix(args, P, m, seq, gpu_results):
                       % (ns, len(gpu_results), tcpu)}
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def _rows_sample(a, max_bytes, seed):
+    """`a` itself when it fits `max_bytes`, else a fixed, seeded sample of its rows (in their order)"""
+    if a.nbytes <= max_bytes:
+        return a
+    row = max(a.nbytes // max(len(a), 1), 1)
+    idx = np.sort(np.random.default_rng(seed).choice(len(a), max_bytes // row, replace=False))
+    return a[idx]
+
+
+def dump_outputs(d, g):
+    """--dump-outputs: what a caller of the timed path receives for its last step, read back from handle `g` right after the timed
+    steps, one DIR/<name>.npy each (float32 clouds and plane normals, float64 for everything else: every counter and index below 2^53
+    is exact).  The map (~10 M points) is a seeded sample of 2 M rows, the other clouds and the indices at most 4-8 MB each: 64 MB in
+    all at most.  The field names of step_result go into the result line."""
+    import erasor_amd as ea
+    r = g.last_result()
+    names = [k for k, _ in r._fields_ if k != "reserved_"]
+    bins, normal, dist_ = g.get_planes()
+    # (query_rejected, the scan's own rejected points, is empty on every step of these workloads: not written)
+    out = {
+        "step_result": np.array([getattr(r, k) for k in names], np.float64),  # erasor_step_result, fields in the order of the result line
+        "map": _rows_sample(g.get_map(), 32 * 2**20, 1),                                   # map_arranged_ after the step (x y z intensity)
+        "map_rejected": _rows_sample(g.get_cloud(ea.CLOUD_MAP_REJECTED), 8 * 2**20, 2),    # the dynamic points removed from the map
+        "rejected_indices": _rows_sample(g.get_rejected_indices().astype(np.float64), 4 * 2**20, 3),  # ... as indices into the pre-step map
+        "query_voi": _rows_sample(g.get_cloud(ea.CLOUD_QUERY_VOI), 4 * 2**20, 5),
+        "status": g.get_status().astype(np.float64),                                          # Scan Ratio Test status per bin
+        "plane_bins": bins.astype(np.float64),                                                # R-GPF: reverted bins ...
+        "plane_normals": normal.astype(np.float32),                                           # ... their planes per iteration
+        "plane_d": dist_.astype(np.float64),
+    }
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(d, exist_ok=True)
+    for k, a in out.items():
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": d, "arrays": {k: list(a.shape) for k, a in out.items()}, "bytes": int(total), "step_result_fields": names}
+
+
 def _ref_sequence_worker(job):
     """one reference updater (oracle/_ref) on one sequence, in its own process: (steps, seconds)"""
     import ctypes as C
@@ -496,7 +540,7 @@ def main():
         os.environ.setdefault("ERASOR_HIP_QSTREAMS", "1")
         args.interleave, args.interleave_group = "threads", 2
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        respawn_under_torchrun(args)  # does not return
+        respawn_under_torchrun(args)  # does not return (exits with the run's status)
     import torch
     import erasor_amd
     from erasor_amd import synth
@@ -536,10 +580,18 @@ def main():
     m = None
     seqs = []  # the Sequence objects this rank owns (replicas: one; seq-per-gpu: its share of the five)
     if args.mode == "replicas":
-        world = synth.World(seed=20210305 + 5, length=args.street_length, n_streets=args.streets, street_gap=50.0, n_moving=10, n_peds=6)
+        # the last rank's route ends at x_end: the street (150 m beyond, the lidar's reach) and the trails of the moving objects in the map
+        # (the map's own drive is at x = 20 + frame) are made to reach past it, so that every step, however many are asked for, runs on a
+        # mapped street with moving objects, as many per metre as on the default street; runs that fit the defaults get them unchanged
+        x_end = ed.shard_frames(world_size - 1, world_size, n_frames)[0] + n_frames
+        length = max(args.street_length, x_end + 150.0)
+        per_m = length / args.street_length
+        world = synth.World(seed=20210305 + 5, length=length, n_streets=args.streets, street_gap=50.0, n_moving=int(round(10 * per_m)),
+                            n_peds=int(round(6 * per_m)))
+        trail_frames = max(320, int(x_end - 20.0) + 2)
         P = make_params(wl, args)
         # ---- the global map: rank 0 samples it, ONE RCCL broadcast over xGMI to every replica ----
-        m = world.sample_map(spacing=wl["spacing"], frames=range(0, 320, 2), step=1.0) if rank == 0 else None
+        m = world.sample_map(spacing=wl["spacing"], frames=range(0, trail_frames, 2), step=1.0) if rank == 0 else None
         if dist is not None:
             dist.barrier()
         tb = time.time()
@@ -700,6 +752,9 @@ def main():
     gpu_final = None
     if world_size == 1 and (not args.no_cpu_baseline or not args.no_pr_rr) and args.mode == "replicas" and first is not None:
         gpu_final = (first.g.get_map(), first.g.get_rejected_indices())  # (after the clock has stopped; compared with the oracle's below)
+    dumped = None
+    if args.dump_outputs and rank == 0 and first is not None:
+        dumped = dump_outputs(args.dump_outputs, first.g)  # (after the clock has stopped, before anything below steps the handle again)
     prof = first.g.profile_get() if first is not None else {}
     chain_us = first.g.chain_timing() if first is not None else (0.0, 0.0, 0, 0.0)
     if first is not None:
@@ -951,6 +1006,8 @@ def main():
         "setup_s": {"map_build_and_upload": round(t_map, 2), "rccl_broadcast": None if t_bcast is None else round(t_bcast, 4),
                     "rccl_broadcast_bytes": None if t_bcast is None else 16 * N_map},
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if union_eval is not None:
         out["union_exchange"] = union_eval
     if evals is not None:

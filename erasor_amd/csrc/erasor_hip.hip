@@ -957,22 +957,21 @@ static hipStream_t copy_stream(erasor_hip_handle *h) {
     return h->cstream ? h->cstream : h->stream;
 }
 
-// A handle runs its chains on four streams, and HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4):
+// A handle runs its chains on four streams, and HIP multiplexes a process's streams onto the process's hardware queues (GPU_MAX_HW_QUEUES):
 // with several handles in one process -- one per sequence, or the shim's updaters -- the two query streams of a handle can land on ONE
 // queue, its two chains in flight then run one after the other and the step waits for them (measured, round 3: five sequences in one
-// process 2777 scans/s with the default, 4180 with 8 or 16 queues; the C++ bench's third handle 0.22 or 0.65 ms per step depending on
-// where its streams landed).  The variable is read when the HIP runtime starts, so it is the PROCESS's business: rounds 2-3 set it from a
-// load-time constructor of this library, which changed the environment of whoever loaded it.  Now: a documented requirement
-// (include/erasor_hip.h; bench.py and the offline driver export it themselves) and ONE warning when a process creates
-// its second handle without it.
+// process 2777 scans/s with HIP's default queue count, 4180 with more queues; the C++ bench's third handle 0.22 or 0.65 ms per step
+// depending on where its streams landed).  The variable is read when the HIP runtime starts, so it is the PROCESS's business -- the
+// environment's, which may cap it: rounds 2-3 set it from a load-time constructor of this library, which changed the environment of
+// whoever loaded it.  Now: ONE warning when a process creates its second handle with few queues.
 static std::atomic<int> g_handles_created{0};
 static void warn_hw_queues_once() {
     static std::atomic<bool> warned{false};
     const char *e = getenv("GPU_MAX_HW_QUEUES");
     if ((e && atoi(e) >= 8) || warned.exchange(true)) return;
     fprintf(stderr, "[erasor_hip] several handles in one process and GPU_MAX_HW_QUEUES is %s: their streams share %s hardware queues and "
-                    "look-ahead chains of one handle may run one after the other (export GPU_MAX_HW_QUEUES=16 before the process starts HIP)\n",
-            e ? e : "unset", e ? e : "the default 4");
+                    "look-ahead chains of one handle may run one after the other\n",
+            e ? e : "unset", e ? e : "HIP's default number of");
 }
 
 int erasor_hip_create(const erasor_params *p, int device, erasor_hip_handle **out) {

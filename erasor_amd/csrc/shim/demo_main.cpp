@@ -477,8 +477,6 @@ static int bench_mode(int argc, char **argv) {
 }
 
 int main(int argc, char **argv) {
-    // an APPLICATION's decision (the library only warns): hardware queues for several updaters' streams, before HIP starts
-    setenv("GPU_MAX_HW_QUEUES", "16", 0);
     if (argc >= 2 && std::string(argv[1]) == "--bench") {
         try {
             return bench_mode(argc, argv);

@@ -52,8 +52,14 @@ def test_struct_layouts_match_the_header():
 
 
 def test_no_gpu_means_loud_failure_not_a_fallback():
-    import torch
-    if torch.cuda.is_available():
+    # (torch is asked in a process of its own: this one has loaded the library, and torch brings its own copy of the HIP runtime --
+    # initialised here it would hold the device, and every later handle of the suite's process would find none)
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"], capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    if out.stdout.strip().split("\n")[-1] == "1":
         pytest.skip("a GPU is present")
     p = erasor_amd.params_default()
     with pytest.raises(erasor_amd.ErasorError) as e:

@@ -929,7 +929,7 @@ print("ALT-PATH-OK")
                                  {"ERASOR_HIP_NO_RCCL": "1", "ERASOR_HIP_HOST_TIMING": "1", "ERASOR_HIP_SORT_STAMPS": "1", "ERASOR_HIP_DEBUG_SYNC": "1"},
                                  {"ERASOR_HIP_QSTREAMS": "3", "ERASOR_HIP_OVERLAP": "0", "ALT_CHAIN_BATCH": "1"},
                                  {"ERASOR_HIP_QSTREAMS": "1", "ERASOR_HIP_OVERLAP": "0", "ALT_EXPECT_SETS": "1"},
-                                 {"ERASOR_HIP_OVERLAP": "1", "ERASOR_HIP_CHAIN_STAMPS": "1", "ERASOR_HIP_LEAVE_ALL": "1", "GPU_MAX_HW_QUEUES": "16",
+                                 {"ERASOR_HIP_OVERLAP": "1", "ERASOR_HIP_CHAIN_STAMPS": "1", "ERASOR_HIP_LEAVE_ALL": "1", "ERASOR_HIP_QSTREAMS": "3",
                                   "ALT_CHAIN_BATCH": "3", "ALT_HOOKS_LIB": "1"},
                                  {"ERASOR_HIP_OVERLAP": ""}],
                          ids=["no_chunk_records_every_launch_profiled", "peer_copies_diagnostics", "three_query_streams_no_overlap_every_chain_on_its_own",
@@ -1098,9 +1098,7 @@ def test_full_size_other_bench_workloads(gpu_mod, tmp_path, case):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = tmp_path / "full_size_worker.py"
     script.write_text(FULL_SIZE_WORKER % dict(root=root, case=case))
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="16")
-    if case == "ouster128":
-        env["ERASOR_HIP_QSTREAMS"] = "3"
+    env = dict(os.environ, ERASOR_HIP_QSTREAMS="3")  # (three query streams, as the library picks with many hardware queues)
     out = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0 and "FULL-SIZE-OK" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
 
@@ -1203,7 +1201,7 @@ def test_a_point_on_a_sector_edge_is_counted_not_hidden(gpu_mod):
 
 @pytest.mark.parametrize("mode_args", [["--mode", "replicas"], ["--mode", "seq-per-gpu", "--placement", "queue", "--seqs", "3"]],
                          ids=["replicas_broadcast_shards", "seq_per_gpu_job_queue"])
-def test_bench_two_ranks_end_to_end_on_one_device(mode_args):
+def test_bench_two_ranks_end_to_end_on_one_device(mode_args, tmp_path):
     """`bench.py --gpus 2` -- the respawn under torch.distributed.run, init_process_group, the map broadcast, the
     per-rank shards / the job queue, the MAX-reduce, the all_gather of the per-rank counters and the JSON assembly on rank 0 -- had
     never executed end to end anywhere (no multi-GPU box; the driver's scaling run would have been its first run).  Here it does, as
@@ -1219,7 +1217,8 @@ def test_bench_two_ranks_end_to_end_on_one_device(mode_args):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--street-length", "150", "--streets", "2",
-           "--az-steps", "500", "--no-cpu-baseline", "--no-pr-rr", "--no-callback-bench", "--no-extra-workloads", "--repeats", "2"] + mode_args
+           "--az-steps", "500", "--no-cpu-baseline", "--no-pr-rr", "--no-callback-bench", "--no-extra-workloads", "--repeats", "2",
+           "--dump-outputs", str(tmp_path / "dump")] + mode_args
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.strip().split("\n") if l.startswith("{")]
@@ -1234,6 +1233,17 @@ def test_bench_two_ranks_end_to_end_on_one_device(mode_args):
         assert abs(d["value"] - 2 * 3 / (d["ms_per_step"] * 1e-3 * 3)) / d["value"] < 0.02  # whole-job rate: both ranks' scans over the slower rank's time
     else:
         assert sum(r["steps"] for r in d["per_rank"]) == 3 * 3  # three sequences handed out by the queue, three timed steps each
+    # --dump-outputs: rank 0's last step as float32 / float64 arrays, the result block as the handle reported it
+    import numpy as np
+    dumped = {f[:-4]: np.load(str(tmp_path / "dump" / f)) for f in os.listdir(str(tmp_path / "dump"))}
+    assert sorted(dumped) == sorted(d["dumped_outputs"]["arrays"]) and "map" in dumped and "step_result" in dumped
+    assert all(a.dtype in (np.float32, np.float64) for a in dumped.values())
+    assert sum(a.nbytes for a in dumped.values()) <= 64 * 2**20
+    res = dict(zip(d["dumped_outputs"]["step_result_fields"], dumped["step_result"]))
+    assert len(dumped["map"]) == min(res["n_map_out"], 2**21)  # (the whole map, or a sample of 2 M rows)
+    assert res["n_map_rejected"] == len(dumped["rejected_indices"]) == len(dumped["map_rejected"])
+    if "replicas" in mode_args:
+        assert {k: res[k] for k in d["last_step"]} == d["last_step"]
 
 
 def test_a_larger_scan_announced_behind_a_step_leaves_that_step_alone(gpu_mod):
