@@ -45,6 +45,20 @@ class StepResult(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved_"}
 
 
+class EvalResult(C.Structure):
+    """erasor_eval_result (include/erasor_hip.h): PR / RR of a cleaned map (scripts/analysis_runner.py:74-105)"""
+    _fields_ = [(k, C.c_uint64) for k in (
+        "gt_static", "gt_dynamic", "est_static", "est_dynamic", "preserved_static", "preserved_dynamic",
+        "n_tied", "n_label_out_of_range")] + [(k, C.c_double) for k in ("PR", "RR", "F1")]
+
+    def as_dict(self):
+        """evalmap.evaluate's keys plus the two diagnostics"""
+        return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
+
+
+# per-ground-truth-point codes of Erasor.evaluate(per_point=True)
+EVAL_OUT, EVAL_KEPT_STATIC, EVAL_KEPT_DYNAMIC, EVAL_CLASS_DIFFERS = 0, 1, 2, 3
+
 CLOUD_QUERY_VOI, CLOUD_MAP_VOI, CLOUD_STATIC_ESTIMATE, CLOUD_COMPLEMENT = 0, 1, 2, 3
 CLOUD_MAP_REJECTED, CLOUD_CURR_REJECTED, CLOUD_GROUND_VIZ, CLOUD_MAP = 4, 5, 6, 7
 
@@ -59,7 +73,8 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "kernels.hip.h", "revert_bins.hip.h", "exact_sort.hip.h", "exact_sort_core.h")]
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "kernels.hip.h", "evaluate.hip.h", "revert_bins.hip.h", "exact_sort.hip.h",
+                                                 "exact_sort_core.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _SRC_DIR, "-s"])
@@ -358,6 +373,40 @@ class Erasor:
         self._check(lib().erasor_hip_voxelize_preserving_labels(self._h, _p(cloud), C.c_size_t(len(cloud)), C.c_double(leaf), _p(out),
                                                                 C.c_size_t(len(out)), C.byref(n)))
         return out[: n.value].copy()
+
+    # -- PR / RR (scripts/analysis_runner.py:74-105; the same on the host: erasor_amd.evalmap) --
+    def _eval_cloud(self, cloud, kept):
+        """(pointer, point count, is_device) of a cloud argument: a host array (N x 4 float32 rows) or a (device pointer, n) pair"""
+        if isinstance(cloud, tuple):
+            ptr, n = cloud
+            return C.c_void_p(ptr), C.c_size_t(n), C.c_int(1)
+        a = _f32(cloud).reshape(-1, 4)
+        kept.append(a)
+        return _p(a), C.c_size_t(len(a)), C.c_int(0)
+
+    def evaluate(self, gt, est, voxelsize=0.2, voxel_leaf=0.0, per_point=False):
+        """PR / RR of the estimate `est` against the labelled ground truth `gt` on the device (erasor_hip_evaluate_clouds).  Each cloud is
+        a host array of XYZI rows or a (device pointer, n) pair (device_array).  voxel_leaf > 0: both voxelised at that leaf first.
+        Returns evalmap.evaluate's dict plus n_tied / n_label_out_of_range; per_point=True adds "per_point": one EVAL_* code per GT point."""
+        kept = []
+        g = self._eval_cloud(gt, kept)
+        e = self._eval_cloud(est, kept)
+        codes = np.zeros(max(g[1].value, 1), np.uint8) if per_point else None
+        r = EvalResult()
+        self._check(lib().erasor_hip_evaluate_clouds(self._h, *g, *e, C.c_double(voxel_leaf), C.c_double(voxelsize),
+                                                     _p(codes) if per_point else None, C.byref(r)))
+        out = r.as_dict()
+        if per_point:
+            out["per_point"] = codes[: g[1].value]
+        return out
+
+    def evaluate_map(self, gt, voxelsize=0.2, voxel_leaf=0.0):
+        """PR / RR of the handle's current map (the get_map view, never copied to the host) against `gt` (erasor_hip_evaluate_map)"""
+        kept = []
+        g = self._eval_cloud(gt, kept)
+        r = EvalResult()
+        self._check(lib().erasor_hip_evaluate_map(self._h, *g, C.c_double(voxel_leaf), C.c_double(voxelsize), C.byref(r)))
+        return r.as_dict()
 
     # -- mapgen (src/mapgen/mapgen.hpp) --
     def mapgen_begin(self, leafsize, is_large_scale=False):

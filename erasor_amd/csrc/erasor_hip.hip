@@ -34,6 +34,7 @@
 #define ERASOR_EARLY_GMAP 200u  // workgroups of k_assemble_early that write the map back (build options: A/B with tools/ab_dirs.sh, EXPERIMENTS r06-8)
 #endif
 #include "kernels.hip.h"
+#include "evaluate.hip.h"
 
 using namespace ek;
 
@@ -294,6 +295,13 @@ struct erasor_hip_handle {
     QSide q[NSIDE];
     int qi = 0;                      // the set the calls below work on
     DBuf<float4> curr_rejected;
+    // ---- PR / RR evaluation (erasor_hip_evaluate_*): scratch of its own, nothing a step reads ----
+    struct {
+        DBuf<float4> gt, est, map, pts;    // caller clouds on the device (or their voxelisations), the handle's map, the bucketed estimate
+        DBuf<uint32_t> bkt, cnt, pl, tops, idx;
+        DBuf<unsigned long long> ctr;
+        DBuf<uint8_t> code;
+    } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
     // ---- per-bin scratch (R-GPF / bin voxelise global paths) ----
     DBuf<uint32_t> gsK, gsV, gsL, gsR, gsK2, gsV2;
@@ -1051,6 +1059,8 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->curr_rejected);
     release(h->gsK); release(h->gsV); release(h->gsL); release(h->gsR); release(h->gsK2); release(h->gsV2); release(h->gsH); release(h->gsC);
     release(h->vox_out); release(h->d_st); release(h->d_st_get); release(h->d_ctr);
+    release(h->ev.gt); release(h->ev.est); release(h->ev.map); release(h->ev.pts); release(h->ev.bkt); release(h->ev.cnt); release(h->ev.pl);
+    release(h->ev.tops); release(h->ev.idx); release(h->ev.ctr); release(h->ev.code);
     for (int k = 0; k < NSIDE; ++k) {
         if (h->q[k].ev_keys) (void)hipEventDestroy(h->q[k].ev_keys);
         if (h->q[k].ev_done) (void)hipEventDestroy(h->q[k].ev_done);
@@ -3317,34 +3327,179 @@ int erasor_hip_get_map(erasor_hip_handle *h, float *dst, size_t cap, size_t *n) 
     if (n) *n = total;
     if (!dst) return ERASOR_OK;
     if (total > cap) return ERASOR_E_CAPACITY;
-    if (h->nC) HIPC(h, hipMemcpy(dst + ((size_t)h->nFv + h->o_valid) * 4, h->Cbuf.p, (size_t)h->nC * sizeof(float4), hipMemcpyDeviceToHost));
-    if (h->nF && h->nFv == h->nF) HIPC(h, hipMemcpy(dst, h->F[h->curF].p, (size_t)h->nF * sizeof(float4), hipMemcpyDeviceToHost));
-    else if (h->nF) {  // (round 5: the region holds reserved slots nothing filled: its points, compacted)
-        DBuf<float4> tmpF;
-        if (ensure(h, tmpF, (size_t)h->nFv + 1)) return ERASOR_E_NO_DEVICE;
-        const int rc_f = copy_F_dense(h, tmpF.p);
-        if (!rc_f && h->nFv) (void)hipMemcpy(dst, tmpF.p, (size_t)h->nFv * sizeof(float4), hipMemcpyDeviceToHost);
-        release(tmpF);
-        if (rc_f) return rc_f;
+    // (the compaction is the one erasor_hip_replicate_map and erasor_hip_evaluate_map use: the map as one dense device array)
+    DBuf<float4> dense;
+    size_t got = 0;
+    int rc = map_to_device(h, dense, &got);
+    if (!rc && got && hipMemcpy(dst, dense.p, got * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) {
+        h->err = "erasor_hip_get_map: hipMemcpy failed";
+        rc = ERASOR_E_NO_DEVICE;
     }
-    const uint32_t span = h->capO - h->o_begin;
-    if (span && h->o_valid) {
-        DBuf<uint32_t> flag, pl, tops;
-        DBuf<float4> tmp;
-        if (ensure(h, flag, span + 1) || ensure(h, pl, span + 1) || ensure(h, tops, span / 1024 + 4) || ensure(h, tmp, h->o_valid + 1))
-            return ERASOR_E_NO_DEVICE;
-        LAUNCH(h, "get_map", k_o_valid, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, h->o_begin, h->capO, flag.p);
-        scan_u32(h, flag.p, pl.p, tops.p, span, span, nullptr, nullptr, "get_map");
-        LAUNCH(h, "get_map", k_o_compact, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, (const float2 *)h->Ozi.p, h->o_begin, h->capO,
-               (const uint32_t *)flag.p, (const uint32_t *)pl.p, (const uint32_t *)tops.p, tmp.p);
-        HIPC(h, hipStreamSynchronize(h->stream));
-        HIPC(h, hipMemcpy(dst + (size_t)h->nFv * 4, tmp.p, (size_t)h->o_valid * sizeof(float4), hipMemcpyDeviceToHost));
-        release(flag);
-        release(pl);
-        release(tops);
-        release(tmp);
+    release(dense);
+    return rc;
+}
+
+static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t ns, double leaf_size, uint32_t *nq_out);
+
+// ---- PR / RR of a cleaned map against a labelled ground-truth map (scripts/analysis_runner.py:74-105; kernels: evaluate.hip.h) ----
+// Everything runs on the main stream, behind whatever a collected step launched ahead there, in the handle's own scratch (h->ev).
+static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize, uint8_t *per_gt,
+                  erasor_eval_result *res) {
+    auto &E = h->ev;
+    uint32_t nb = 1024;  // buckets: a power of two >= the estimate's size (<= 1 point per bucket on average)
+    while (nb < n_est) nb <<= 1;
+    if (ensure(h, E.ctr, EV_NCTR) || ensure(h, E.cnt, (size_t)nb + 1) || ensure(h, E.pl, (size_t)nb + 1) || ensure(h, E.tops, nb / 1024 + 4) ||
+        ensure(h, E.bkt, (size_t)n_est + 1) || ensure(h, E.pts, (size_t)n_est + 1) || ensure(h, E.idx, (size_t)n_est + 1) ||
+        (per_gt && ensure(h, E.code, (size_t)n_gt + 1)))
+        return ERASOR_E_NO_DEVICE;
+    struct KeepCur {
+        erasor_hip_handle *h;
+        hipStream_t keep;
+        ~KeepCur() { h->cur = keep; }
+    } kc{h, h->cur};
+    h->cur = h->stream;
+    HIPC(h, hipMemsetAsync(E.ctr.p, 0, EV_NCTR * sizeof(unsigned long long), h->stream));
+    const double thr = (voxelsize * sqrt(3.0)) / 2.0;  // evalmap / analysis_runner.py: voxelsize * np.sqrt(3) / 2
+    if (n_est) {
+        HIPC(h, hipMemsetAsync(E.cnt.p, 0, ((size_t)nb + 1) * sizeof(uint32_t), h->stream));
+        LAUNCH(h, "ev_index", k_ev_hist, cdiv(n_est, 256), 256, est, n_est, voxelsize, nb - 1, E.bkt.p, E.cnt.p, E.ctr.p);
+        scan_u32(h, E.cnt.p, E.pl.p, E.tops.p, nb + 1, nb + 1, nullptr, nullptr, "ev_index");
+        LAUNCH(h, "ev_index", k_ev_offsets, cdiv(nb + 1, 256), 256, (const uint32_t *)E.pl.p, (const uint32_t *)E.tops.p, nb + 1, E.cnt.p, E.pl.p);
+        LAUNCH(h, "ev_index", k_ev_scatter, cdiv(n_est, 256), 256, est, n_est, (const uint32_t *)E.bkt.p, E.pl.p, E.pts.p, E.idx.p);
+    }
+    if (n_gt)
+        LAUNCH(h, "ev_query", k_ev_query, cdiv(n_gt, 256), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p, (const uint32_t *)E.cnt.p,
+               nb - 1, n_est, voxelsize, thr, per_gt ? E.code.p : (uint8_t *)nullptr, E.ctr.p);
+    unsigned long long c[EV_NCTR];
+    HIPC(h, hipMemcpyAsync(c, E.ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (c[EV_NON_FINITE]) {
+        h->err = "erasor_hip_evaluate: non-finite coordinate (NaN / Inf) in " + std::to_string(c[EV_NON_FINITE]) + " point(s)";
+        return ERASOR_E_INVALID;
+    }
+    if (per_gt && n_gt) HIPC(h, hipMemcpy(per_gt, E.code.p, n_gt, hipMemcpyDeviceToHost));
+    erasor_eval_result r;
+    memset(&r, 0, sizeof(r));
+    r.gt_static = c[EV_GT_STATIC];
+    r.gt_dynamic = c[EV_GT_DYNAMIC];
+    r.est_static = c[EV_EST_STATIC];
+    r.est_dynamic = c[EV_EST_DYNAMIC];
+    r.preserved_static = c[EV_KEPT_STATIC];
+    r.preserved_dynamic = c[EV_KEPT_DYNAMIC];
+    r.n_tied = c[EV_TIED];
+    r.n_label_out_of_range = c[EV_LABEL_OOR];
+    // evalmap.evaluate's formulas, operation by operation (Python int / int is the correctly rounded quotient: the same as in double here)
+    const double ns = (double)r.gt_static, nd = (double)r.gt_dynamic;
+    r.PR = r.gt_static ? (double)r.preserved_static / ns * 100.0 : 0.0;
+    r.RR = r.gt_dynamic ? (double)(r.gt_dynamic - r.preserved_dynamic) / nd * 100.0 : 0.0;
+    r.F1 = (r.PR + r.RR) > 0 ? 2 * (r.PR / 100) * (r.RR / 100) / ((r.PR / 100) + (r.RR / 100)) : 0.0;
+    *res = r;
+    return ERASOR_OK;
+}
+
+// voxelize_preserving_labels of a device cloud at `leaf` (the save_static_map protocol, OMU.cpp:174-196) into dst (borrows a query side)
+static int ev_voxelize(erasor_hip_handle *h, const float4 *src, uint32_t n, double leaf, DBuf<float4> &dst, uint32_t *n_out) {
+    *n_out = 0;
+    if (!n) return ERASOR_OK;
+    uint32_t nq = 0;
+    const int rc = voxelize_device(h, src, n, leaf, &nq);
+    if (rc) return rc;
+    if (ensure(h, dst, (size_t)nq + 1)) return ERASOR_E_NO_DEVICE;  // (nq <= n: no reallocation when src is dst itself)
+    if (nq) HIPC(h, hipMemcpyAsync(dst.p, Q(h).query.p, (size_t)nq * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    *n_out = nq;
+    return ERASOR_OK;
+}
+
+static int ev_check_args(erasor_hip_handle *h, double voxel_leaf, double voxelsize, bool per_gt, erasor_eval_result *res) {
+    if (!res) {
+        h->err = "erasor_hip_evaluate: res is NULL";
+        return ERASOR_E_INVALID;
+    }
+    if (!(voxelsize > 0) || !std::isfinite(voxelsize)) {
+        h->err = "erasor_hip_evaluate: voxelsize must be a finite number > 0";
+        return ERASOR_E_INVALID;
+    }
+    if (!(voxel_leaf >= 0) || !std::isfinite(voxel_leaf)) {
+        h->err = "erasor_hip_evaluate: voxel_leaf must be 0 or a finite number > 0";
+        return ERASOR_E_INVALID;
+    }
+    if (per_gt && voxel_leaf > 0) {
+        h->err = "erasor_hip_evaluate: per_gt needs voxel_leaf == 0 (the codes would describe the voxelised ground truth)";
+        return ERASOR_E_INVALID;
     }
     return ERASOR_OK;
+}
+
+// a caller cloud on the device: its own pointer, or a copy of the host cloud in `buf`
+static int ev_input(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, DBuf<float4> &buf, const float4 **out) {
+    *out = nullptr;
+    if (!n) return ERASOR_OK;
+    if (is_device) {
+        *out = (const float4 *)xyzi;
+        return ERASOR_OK;
+    }
+    if (ensure(h, buf, n + 1)) return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemcpyAsync(buf.p, xyzi, n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    *out = buf.p;
+    return ERASOR_OK;
+}
+
+int erasor_hip_evaluate_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, const void *est_xyzi, size_t n_est,
+                               int est_is_device, double voxel_leaf, double voxelsize, uint8_t *per_gt, erasor_eval_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, per_gt != nullptr, res);
+    if (rc) return rc;
+    if ((!gt_xyzi && n_gt) || (!est_xyzi && n_est) || n_gt > 0x3FFFFFFFull || n_est > 0x3FFFFFFFull) {
+        h->err = "erasor_hip_evaluate_clouds: NULL cloud or more than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *g = nullptr, *e = nullptr;
+    if ((rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, h->ev.gt, &g)) || (rc = ev_input(h, est_xyzi, n_est, est_is_device, h->ev.est, &e))) return rc;
+    uint32_t ng = (uint32_t)n_gt, ne = (uint32_t)n_est;
+    if (voxel_leaf > 0) {
+        if ((rc = ev_voxelize(h, g, ng, voxel_leaf, h->ev.gt, &ng))) return rc;
+        if ((rc = ev_voxelize(h, e, ne, voxel_leaf, h->ev.est, &ne))) return rc;
+        g = h->ev.gt.p;
+        e = h->ev.est.p;
+    }
+    return ev_run(h, g, ng, e, ne, voxelsize, per_gt, res);
+}
+
+int erasor_hip_evaluate_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, double voxel_leaf, double voxelsize,
+                            erasor_eval_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, false, res);
+    if (rc) return rc;
+    if (!h->have_map) {
+        h->err = "erasor_hip_evaluate_map: the handle has no map (erasor_hip_set_map first)";
+        return ERASOR_E_STATE;
+    }
+    if ((!gt_xyzi && n_gt) || n_gt > 0x3FFFFFFFull) {
+        h->err = "erasor_hip_evaluate_map: NULL cloud or more than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    HIPC(h, hipSetDevice(h->device));
+    size_t n_map = 0;
+    if ((rc = map_to_device(h, h->ev.map, &n_map))) return rc;
+    if (n_map > 0x3FFFFFFFull) {
+        h->err = "erasor_hip_evaluate_map: map larger than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    const float4 *g = nullptr, *e = h->ev.map.p;
+    if ((rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, h->ev.gt, &g))) return rc;
+    uint32_t ng = (uint32_t)n_gt, ne = (uint32_t)n_map;
+    if (voxel_leaf > 0) {
+        if ((rc = ev_voxelize(h, g, ng, voxel_leaf, h->ev.gt, &ng))) return rc;
+        if ((rc = ev_voxelize(h, e, ne, voxel_leaf, h->ev.est, &ne))) return rc;
+        g = h->ev.gt.p;
+        e = h->ev.est.p;
+    }
+    return ev_run(h, g, ng, e, ne, voxelsize, nullptr, res);
 }
 
 // the last step's [selected bins theta-major | ground_viz | complement] WITHOUT tf_body2origin_ (the egocentric clouds

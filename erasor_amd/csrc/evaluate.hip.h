@@ -1,0 +1,190 @@
+// evaluate.hip.h — Preservation Rate / Rejection Rate of a cleaned map against a labelled ground-truth map, on the device.
+//
+// Replaces the reference's evaluator (scripts/analysis_runner.py:74-105, restated on the host in erasor_amd/evalmap.py): for every
+// ground-truth (GT) point the nearest estimated point (1-NN, Euclidean, what cKDTree.query(k=1) returns); the GT point is kept if that
+// distance is < voxelsize*sqrt(3)/2.  Labels: uint32(intensity) & 0xFFFF, classes 252..259 are dynamic (analysis_runner.py:14,44-47).
+//
+// The estimated map is indexed by a uniform grid of cell edge `voxelsize` hashed into a power-of-two bucket table (histogram -> exclusive
+// scan -> scatter of (point, original index)).  The threshold is 0.866 cell edges, so every estimated point within it of a GT point lies
+// in the 27 cells around that point's cell -- also when the cell coordinates of the two are a few ulps off their exact values (a margin of
+// 0.134 cell edges).  Whenever the nearest estimated point is within the threshold, the minimum over those 27 cells IS the global minimum.
+// Hash collisions only add candidates, and the order inside a bucket does not matter: the query decides by (d^2, estimated index).
+//
+// Distances are computed in float64 exactly as cKDTree does: dx = (double)gt.x - (double)est.x, d^2 = (dx*dx + dy*dy) + dz*dz, left to
+// right (the library builds with -ffp-contract=off: no fused multiply-add).  The comparison is sqrt(d^2) < thr with the correctly rounded
+// float64 square root: on gfx950 hipcc expands sqrt(double) (the llvm.sqrt.f64 lowering) into v_ldexp_f64 scaling of tiny inputs,
+// v_rsq_f64, two Newton-Raphson steps on v_fma_f64, the inverse scaling and a v_cmp_class_f64 fix-up for 0 / inf -- no v_sqrt_f64 --
+// and tests/test_gpu_hooks.py pins that device sqrt against the host's bit for bit.
+#ifndef ERASOR_EVALUATE_HIP_H
+#define ERASOR_EVALUATE_HIP_H
+
+namespace ek {
+
+// counters of one evaluation (one 64-bit atomic per wavefront and counter)
+enum : uint32_t {
+    EV_GT_STATIC = 0,
+    EV_GT_DYNAMIC,
+    EV_EST_STATIC,
+    EV_EST_DYNAMIC,
+    EV_KEPT_STATIC,
+    EV_KEPT_DYNAMIC,
+    EV_TIED,            // GT points within the threshold whose minimum d^2 is shared by candidates of both classes
+    EV_LABEL_OOR,       // intensities that are not finite or outside [0, 2^32): decoded as static
+    EV_NON_FINITE,      // points with a non-finite coordinate (the host refuses the evaluation)
+    EV_NCTR
+};
+// per GT point (optional): 0 not within the threshold, 1 kept static, 2 kept dynamic, 3 within the threshold but the class differs
+enum : uint8_t { EV_OUT = 0, EV_KEPT_S = 1, EV_KEPT_D = 2, EV_CLASS_DIFFERS = 3 };
+
+static constexpr double EV_CELL_CLAMP = 1073741824.0;  // 2^30: cell coordinates are clamped (neighbours +-1 stay in int32)
+
+// label decode of evalmap.labels: numeric cast to uint32, & 0xFFFF, dynamic = 252..259.  Values the cast is not defined for are static.
+__device__ __forceinline__ bool ev_is_dynamic(float w, uint32_t &oor) {
+    if (!(w >= 0.0f && w < 4294967296.0f)) {  // (NaN fails both)
+        oor = 1u;
+        return false;
+    }
+    const uint32_t sem = (uint32_t)w & 0xFFFFu;
+    return sem >= 252u && sem <= 259u;
+}
+
+__device__ __forceinline__ int32_t ev_cell(float v, double cell) {
+    double f = floor((double)v / cell);
+    if (!(f >= -EV_CELL_CLAMP)) f = -EV_CELL_CLAMP;  // (NaN lands here: such a point is refused by the host anyway)
+    if (f > EV_CELL_CLAMP) f = EV_CELL_CLAMP;
+    return (int32_t)f;
+}
+
+__device__ __forceinline__ uint32_t ev_bucket(int32_t cx, int32_t cy, int32_t cz, uint32_t mask) {
+    uint32_t k = ((uint32_t)cx * 73856093u) ^ ((uint32_t)cy * 19349663u) ^ ((uint32_t)cz * 83492791u);
+    k ^= k >> 16;  // (murmur3 finaliser: neighbouring cells spread over the table)
+    k *= 0x85EBCA6Bu;
+    k ^= k >> 13;
+    k *= 0xC2B2AE35u;
+    k ^= k >> 16;
+    return k & mask;
+}
+
+__device__ __forceinline__ bool ev_finite(const float4 &p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
+
+// lane 0 of each wavefront adds the wavefront's count (every lane of the wavefront must call this)
+__device__ __forceinline__ void ev_commit(unsigned long long *ctr, uint32_t which, uint32_t mine) {
+    const uint32_t s = wave_sum(mine);
+    if ((threadIdx.x & 63u) == 0 && s) atomicAdd(&ctr[which], (unsigned long long)s);
+}
+
+// (1) bucket of every estimated point + histogram of the buckets; est label counters.  cnt: [nb + 1], zeroed by the host.
+__global__ __launch_bounds__(256) void k_ev_hist(const float4 *__restrict__ est, uint32_t n, double cell, uint32_t mask,
+                                                  uint32_t *__restrict__ bucket_of, uint32_t *__restrict__ cnt, unsigned long long *__restrict__ ctr) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t dyn = 0, sta = 0, oor = 0, bad = 0;
+    if (i < n) {
+        const float4 p = est[i];
+        bad = ev_finite(p) ? 0u : 1u;
+        const uint32_t b = ev_bucket(ev_cell(p.x, cell), ev_cell(p.y, cell), ev_cell(p.z, cell), mask);
+        bucket_of[i] = b;
+        atomicAdd(&cnt[b], 1u);
+        if (ev_is_dynamic(p.w, oor)) dyn = 1; else sta = 1;
+    }
+    ev_commit(ctr, EV_EST_DYNAMIC, dyn);
+    ev_commit(ctr, EV_EST_STATIC, sta);
+    ev_commit(ctr, EV_LABEL_OOR, oor);
+    ev_commit(ctr, EV_NON_FINITE, bad);
+}
+
+// (2) after scan_u32 over cnt[0 .. nb]: off[b] = start of bucket b (off[nb] = n), cursor[b] = the same (the scatter's slot counter).
+// off may be cnt itself, cursor may be pl itself (each thread reads its own entries before it writes them).
+__global__ __launch_bounds__(256) void k_ev_offsets(const uint32_t *pl, const uint32_t *__restrict__ tops, uint32_t nb1, uint32_t *off,
+                                                     uint32_t *cursor) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nb1) return;
+    const uint32_t o = pl[b] + tops[b >> 10];
+    off[b] = o;
+    cursor[b] = o;
+}
+
+// (3) (point, original index) into its bucket's range; the order inside a bucket is whatever the atomics give
+__global__ __launch_bounds__(256) void k_ev_scatter(const float4 *__restrict__ est, uint32_t n, const uint32_t *__restrict__ bucket_of,
+                                                     uint32_t *__restrict__ cursor, float4 *__restrict__ pts, uint32_t *__restrict__ idx) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t s = atomicAdd(&cursor[bucket_of[i]], 1u);
+    pts[s] = est[i];
+    idx[s] = i;
+}
+
+// (4) one GT point per lane: the minimum (d^2, estimated index) over the 27 buckets around its cell, then the counters
+__global__ __launch_bounds__(256) void k_ev_query(const float4 *__restrict__ gt, uint32_t n_gt, const float4 *__restrict__ pts,
+                                                   const uint32_t *__restrict__ idx, const uint32_t *__restrict__ off, uint32_t mask, uint32_t n_est,
+                                                   double cell, double thr, uint8_t *__restrict__ code, unsigned long long *__restrict__ ctr) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t gs = 0, gd = 0, ks = 0, kd = 0, tied = 0, oor = 0, bad = 0;
+    if (i < n_gt) {
+        const float4 g = gt[i];
+        bad = ev_finite(g) ? 0u : 1u;
+        const bool g_dyn = ev_is_dynamic(g.w, oor);
+        gd = g_dyn ? 1u : 0u;
+        gs = 1u - gd;
+        double best = __builtin_huge_val();
+        uint32_t best_i = 0xFFFFFFFFu;
+        bool best_dyn = false, at_min_s = false, at_min_d = false;  // classes seen at the current minimum d^2
+        if (n_est) {
+            const double gx = (double)g.x, gy = (double)g.y, gz = (double)g.z;
+            const int32_t cx = ev_cell(g.x, cell), cy = ev_cell(g.y, cell), cz = ev_cell(g.z, cell);
+            for (int dz = -1; dz <= 1; ++dz)
+                for (int dy = -1; dy <= 1; ++dy)
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        const uint32_t b = ev_bucket(cx + dx, cy + dy, cz + dz, mask);
+                        const uint32_t e = off[b + 1];
+                        for (uint32_t s = off[b]; s < e; ++s) {
+                            const float4 p = pts[s];
+                            const double ex = gx - (double)p.x, ey = gy - (double)p.y, ez = gz - (double)p.z;
+                            const double d2 = (ex * ex + ey * ey) + ez * ez;
+                            if (!(d2 <= best)) continue;  // (NaN never wins)
+                            uint32_t o_ = 0;
+                            const bool e_dyn = ev_is_dynamic(p.w, o_);
+                            const uint32_t j = idx[s];
+                            if (d2 < best) {
+                                best = d2;
+                                best_i = j;
+                                best_dyn = e_dyn;
+                                at_min_s = !e_dyn;
+                                at_min_d = e_dyn;
+                            } else {  // the same d^2: the smaller index is the answer, both classes are remembered
+                                if (j < best_i) {
+                                    best_i = j;
+                                    best_dyn = e_dyn;
+                                }
+                                at_min_s = at_min_s || !e_dyn;
+                                at_min_d = at_min_d || e_dyn;
+                            }
+                        }
+                    }
+        }
+        uint8_t c = EV_OUT;
+        if (best_i != 0xFFFFFFFFu && sqrt(best) < thr) {
+            if (!g_dyn && !best_dyn) {
+                c = EV_KEPT_S;
+                ks = 1;
+            } else if (g_dyn && best_dyn) {
+                c = EV_KEPT_D;
+                kd = 1;
+            } else {
+                c = EV_CLASS_DIFFERS;
+            }
+            tied = (at_min_s && at_min_d) ? 1u : 0u;
+        }
+        if (code) code[i] = c;
+    }
+    ev_commit(ctr, EV_GT_STATIC, gs);
+    ev_commit(ctr, EV_GT_DYNAMIC, gd);
+    ev_commit(ctr, EV_KEPT_STATIC, ks);
+    ev_commit(ctr, EV_KEPT_DYNAMIC, kd);
+    ev_commit(ctr, EV_TIED, tied);
+    ev_commit(ctr, EV_LABEL_OOR, oor);
+    ev_commit(ctr, EV_NON_FINITE, bad);
+}
+
+}  // namespace ek
+
+#endif  // ERASOR_EVALUATE_HIP_H

@@ -82,11 +82,96 @@ static int erasor_class_mode(int argc, char **argv) {
     return 0;
 }
 
-// --config <rosparam.yaml> [n_frames]: the reference's own driver, main_in_your_env.cpp:61-127, without ROS:
+// ---- PR / RR (scripts/analysis_runner.py:74-105 on the device: erasor_hip_evaluate_clouds) ----
+// a cloud from a PCD (any encoding erasor_utils::load_pcd reads) or a .bin of XYZI float rows, as XYZI rows
+static bool load_cloud_xyzi(const std::string &path, std::vector<float> &xyzi) {
+    pcl::PointCloud<pcl::PointXYZI> c;
+    const bool is_bin = path.size() >= 4 && path.compare(path.size() - 4, 4, ".bin") == 0;
+    if (is_bin ? !read_bin(path, c) : erasor_utils::load_pcd(path, c) == -1) return false;
+    xyzi.resize(c.size() * 4);
+    for (size_t i = 0; i < c.size(); ++i) {
+        xyzi[4 * i] = c.points[i].x;
+        xyzi[4 * i + 1] = c.points[i].y;
+        xyzi[4 * i + 2] = c.points[i].z;
+        xyzi[4 * i + 3] = c.points[i].intensity;
+    }
+    return true;
+}
+// the row analysis_runner.py prints (tabulate, orgtbl)
+static void print_eval_row(const erasor_eval_result &r) {
+    printf("|   gt_S |   gt_D |   est_S |   est_D |   kept_S |   kept_D |     PR%% |     RR%% |     F1 |\n");
+    printf("|--------+--------+---------+---------+----------+----------+---------+---------+--------|\n");
+    printf("| %6llu | %6llu | %7llu | %7llu | %8llu | %8llu | %7.3f | %7.3f | %6.4f |\n", (unsigned long long)r.gt_static,
+           (unsigned long long)r.gt_dynamic, (unsigned long long)r.est_static, (unsigned long long)r.est_dynamic,
+           (unsigned long long)r.preserved_static, (unsigned long long)r.preserved_dynamic, r.PR, r.RR, r.F1);
+    if (r.n_tied || r.n_label_out_of_range)
+        printf("(%llu ground-truth point(s) with an equidistant nearest point of the other class, %llu label(s) out of range)\n",
+               (unsigned long long)r.n_tied, (unsigned long long)r.n_label_out_of_range);
+}
+static int evaluate_host(erasor_hip_handle *h, const std::vector<float> &gt, const std::vector<float> &est, double voxel_leaf, double voxelsize) {
+    erasor_eval_result r;
+    const int rc = erasor_hip_evaluate_clouds(h, gt.data(), gt.size() / 4, 0, est.data(), est.size() / 4, 0, voxel_leaf, voxelsize, nullptr, &r);
+    if (rc) {
+        fprintf(stderr, "evaluate: %s (rc %d)\n", erasor_hip_last_error(h), rc);
+        return 1;
+    }
+    print_eval_row(r);
+    return 0;
+}
+// --eval <gt> <est> [voxelsize = 0.2] [voxel_leaf = 0]: analysis_runner.py's evaluation of two map files, on the device
+static int eval_mode(int argc, char **argv) {
+    if (argc < 4) return 2;
+    const double voxelsize = argc > 4 ? atof(argv[4]) : 0.2, voxel_leaf = argc > 5 ? atof(argv[5]) : 0.0;
+    std::vector<float> gt, est;
+    if (!load_cloud_xyzi(argv[2], gt) || !load_cloud_xyzi(argv[3], est)) {
+        fprintf(stderr, "cannot read %s or %s\n", argv[2], argv[3]);
+        return 3;
+    }
+    printf("GT : %s\nEst: %s\n", argv[2], argv[3]);
+    erasor_params p;
+    erasor_hip_params_default(&p);
+    erasor_hip_handle *h = nullptr;
+    if (erasor_hip_create(&p, 0, &h) != ERASOR_OK) {
+        fprintf(stderr, "erasor_hip_create failed\n");
+        return 1;
+    }
+    const int rc = evaluate_host(h, gt, est, voxel_leaf, voxelsize);
+    erasor_hip_destroy(h);
+    return rc;
+}
+// PR / RR of the map save_static_map(0.2) writes (voxelize_preserving_labels of map_arranged_) against a ground-truth file
+static int evaluate_saved_map(erasor::OfflineMapUpdater &updater, const std::string &gt_path) {
+    std::vector<float> gt;
+    if (!load_cloud_xyzi(gt_path, gt)) {
+        fprintf(stderr, "cannot read %s\n", gt_path.c_str());
+        return 3;
+    }
+    pcl::PointCloud<pcl::PointXYZI> m;
+    updater.get_map(m);
+    std::vector<float> src(m.size() * 4), saved(m.size() * 4 + 4);
+    for (size_t i = 0; i < m.size(); ++i) {
+        src[4 * i] = m.points[i].x;
+        src[4 * i + 1] = m.points[i].y;
+        src[4 * i + 2] = m.points[i].z;
+        src[4 * i + 3] = m.points[i].intensity;
+    }
+    size_t n = 0;
+    erasor_hip_handle *h = updater.handle();
+    if (erasor_hip_voxelize_preserving_labels(h, src.data(), m.size(), 0.2, saved.data(), m.size() + 1, &n) != ERASOR_OK) {
+        fprintf(stderr, "voxelize_preserving_labels: %s\n", erasor_hip_last_error(h));
+        return 1;
+    }
+    saved.resize(n * 4);
+    printf("PR / RR of the saved static map against %s:\n", gt_path.c_str());
+    return evaluate_host(h, gt, saved, 0.0, 0.2);
+}
+
+// --config <rosparam.yaml> [n_frames] [gt]: the reference's own driver, main_in_your_env.cpp:61-127, without ROS:
 //   <data_dir>/poses_lidar2body.csv, <data_dir>/pcds/%06d.pcd from init_idx on, every node through
 //   OfflineMapUpdater::callback_node (pose -> eigen2geoPose -> node.odom), then save_static_map(0.2).
 // The initial map is /MapUpdater/initial_map_path, or <data_dir>/dense_global_map.pcd when that key is absent.
-static int run_config(const std::string &yaml, int max_frames, int device, bool verbose, int *nodes_done = nullptr) {
+// With a ground-truth map file `gt` (PCD or .bin), the PR / RR of the saved map are printed (analysis_runner.py's row).
+static int run_config(const std::string &yaml, int max_frames, int device, bool verbose, int *nodes_done = nullptr, const std::string &gt = "") {
     erasor::OfflineMapUpdater::Config cfg;
     erasor_hip_params_default(&cfg.params);
     cfg.params.query_voxel_size = 0.05;  // OMU.cpp:66
@@ -166,11 +251,11 @@ static int run_config(const std::string &yaml, int max_frames, int device, bool 
     if (done == 0 && !have) return 3;
     updater.save_static_map(0.2f);  // main_in_your_env.cpp:123
     if (verbose) printf("Static map building complete!\n");
-    return 0;
+    return gt.empty() ? 0 : evaluate_saved_map(updater, gt);
 }
 static int config_mode(int argc, char **argv) {
     if (argc < 3) return 2;
-    return run_config(argv[2], argc > 3 ? atoi(argv[3]) : 1 << 30, 0, true);
+    return run_config(argv[2], argc > 3 ? atoi(argv[3]) : 1 << 30, 0, true, nullptr, argc > 4 ? argv[4] : "");
 }
 
 // --queue <n_workers> <max_frames> <a.yaml> <b.yaml> ...: independent sequences (one rosparam file each) over n_workers devices
@@ -501,6 +586,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && std::string(argv[1]) == "--eval") {
+        try {
+            return eval_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--mapgen") {
         try {
             return mapgen_mode(argc, argv);
@@ -518,7 +611,10 @@ int main(int argc, char **argv) {
         }
     }
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <data_dir> <n_frames> [version] [removal_interval]\n       %s --config <rosparam.yaml> [n_frames]\n", argv[0], argv[0]);
+        fprintf(stderr,
+                "usage: %s <data_dir> <n_frames> [version] [removal_interval] [gt]\n       %s --config <rosparam.yaml> [n_frames] [gt]\n"
+                "       %s --eval <gt> <est> [voxelsize] [voxel_leaf]\n",
+                argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];
@@ -562,6 +658,7 @@ int main(int argc, char **argv) {
         erasor_utils::save_pcd_ascii(dir + "/map_final.pcd", m);
         write_bin(dir + "/map_final.bin", m);
         updater.save_static_map(0.2f);
+        if (argc > 5) return evaluate_saved_map(updater, argv[5]);
     } catch (const std::exception &e) {
         fprintf(stderr, "error: %s\n", e.what());
         return 1;

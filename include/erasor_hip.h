@@ -246,6 +246,40 @@ int erasor_hip_voxelize_preserving_labels(erasor_hip_handle *h, const float *src
                                           double leaf_size, float *dst_xyzi, size_t cap_points,
                                           size_t *n_out);
 
+/* ---- PR / RR of a cleaned map: the step AFTER the hot path (scripts/analysis_runner.py) ---------------------------------------
+ * replaces: analysis_runner.py:74-105 (evaluate), restated on the host in erasor_amd/evalmap.py.  For every ground-truth point the
+ * nearest estimated point (1-NN); the point is kept if that distance is < voxelsize*sqrt(3)/2.  Labels: uint32(intensity) & 0xFFFF,
+ * dynamic classes 252..259.  PR = preserved_static / gt_static, RR = 1 - preserved_dynamic / gt_dynamic (both in percent), F1 of
+ * PR/100 and RR/100 -- evalmap.evaluate's formulas; gt_static == 0 gives PR 0 and gt_dynamic == 0 gives RR 0. */
+typedef struct erasor_eval_result {
+    uint64_t gt_static, gt_dynamic, est_static, est_dynamic, preserved_static, preserved_dynamic;
+    uint64_t n_tied;               /* kept ground-truth points whose nearest distance is shared by estimated points of both classes: which
+                                    * one cKDTree returns is not defined (here: the smallest estimated index) */
+    uint64_t n_label_out_of_range; /* intensities (both clouds) that are not finite or outside [0, 2^32): counted as static */
+    double PR, RR, F1;             /* percent, percent, fraction */
+} erasor_eval_result;
+
+/* per-ground-truth-point codes of erasor_hip_evaluate_clouds */
+#define ERASOR_EVAL_OUT            0  /* no estimated point within the threshold */
+#define ERASOR_EVAL_KEPT_STATIC    1
+#define ERASOR_EVAL_KEPT_DYNAMIC   2
+#define ERASOR_EVAL_CLASS_DIFFERS  3  /* within the threshold, but the nearest point's class is the other one */
+
+/* replaces: analysis_runner.py:74-105 on two caller clouds (XYZI rows), each on the host or on the handle's device (_is_device).
+ * voxel_leaf > 0: both are first voxelised with voxelize_preserving_labels at that leaf on the device (the save_static_map protocol,
+ * OMU.cpp:174-196); that borrows the query side of the last step like erasor_hip_voxelize_preserving_labels does: nodes announced
+ * ahead are dropped (their steps run their own chains, results unchanged; a dropped ticket is ERASOR_E_STATE) and erasor_hip_get_cloud
+ * answers ERASOR_E_STATE until the next step.  voxel_leaf == 0: evaluated as given, in scratch of the evaluator's own -- announcements and
+ * the last step's clouds stay as they are.  per_gt (optional, n_gt bytes, ERASOR_EVAL_*) only with voxel_leaf == 0.
+ * ERASOR_E_INVALID: a non-finite coordinate, voxelsize <= 0, per_gt with voxel_leaf > 0.  ERASOR_E_STATE: a step in flight. */
+int erasor_hip_evaluate_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device,
+                               const void *est_xyzi, size_t n_est, int est_is_device,
+                               double voxel_leaf, double voxelsize, uint8_t *per_gt, erasor_eval_result *res);
+/* the same with the handle's current map as the estimate -- the erasor_hip_get_map view (large-scale mode: the submap followed by its
+ * complement), compacted on the device, never copied to the host.  ERASOR_E_STATE: no map, or a step in flight. */
+int erasor_hip_evaluate_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device,
+                            double voxel_leaf, double voxelsize, erasor_eval_result *res);
+
 /* ---- mapgen: the step BEFORE the hot path (src/mapgen/mapgen.hpp), device-resident accumulation ----
  * replaces: mapgen::setValue + constructor (mapgen.hpp:182-196): leafsize = /map/voxelsize, is_large_scale */
 int erasor_hip_mapgen_begin(erasor_hip_handle *h, double leafsize, int is_large_scale);
