@@ -56,6 +56,17 @@ class EvalResult(C.Structure):
         return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
 
 
+class OverlapResult(C.Structure):
+    """erasor_overlap_result (include/erasor_hip.h): the estimate-to-ground-truth distances of overlap_report
+    (scripts/analysis_runner.py:53-71)"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_est", "n_below_half", "n_below_one", "n_below_two")] + [(k, C.c_double) for k in (
+        "median", "p90", "p99", "max", "frac_half", "frac_one", "frac_two")]
+
+    def as_dict(self):
+        """evalmap.overlap's keys"""
+        return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
+
+
 # per-ground-truth-point codes of Erasor.evaluate(per_point=True)
 EVAL_OUT, EVAL_KEPT_STATIC, EVAL_KEPT_DYNAMIC, EVAL_CLASS_DIFFERS = 0, 1, 2, 3
 
@@ -73,8 +84,8 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "kernels.hip.h", "evaluate.hip.h", "revert_bins.hip.h", "exact_sort.hip.h",
-                                                 "exact_sort_core.h")]
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "revert_bins.hip.h",
+                                                 "exact_sort.hip.h", "exact_sort_core.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _SRC_DIR, "-s"])
@@ -406,6 +417,36 @@ class Erasor:
         g = self._eval_cloud(gt, kept)
         r = EvalResult()
         self._check(lib().erasor_hip_evaluate_map(self._h, *g, C.c_double(voxel_leaf), C.c_double(voxelsize), C.byref(r)))
+        return r.as_dict()
+
+    # -- the estimate-to-ground-truth overlap report (scripts/analysis_runner.py:53-71; the same on the host: evalmap.overlap) --
+    def overlap(self, gt, est, voxelsize=0.2, voxel_leaf=0.0, per_point=False):
+        """overlap_report's numbers for the estimate `est` against the ground truth `gt` on the device (erasor_hip_overlap_clouds): the
+        distance of every estimated point to its nearest ground-truth point, its median / p90 / p99 / max and the percentages below
+        0.5*v, v and 2*v.  Clouds as for evaluate.  per_point=True (voxel_leaf 0 only) adds "dist" (float64, one per estimated point)
+        and "nearest" (uint32: the smallest ground-truth index at that distance)."""
+        kept = []
+        g = self._eval_cloud(gt, kept)
+        e = self._eval_cloud(est, kept)
+        n_e = e[1].value
+        dist = np.zeros(max(n_e, 1), np.float64) if per_point else None
+        near = np.zeros(max(n_e, 1), np.uint32) if per_point else None
+        r = OverlapResult()
+        self._check(lib().erasor_hip_overlap_clouds(self._h, *g, *e, C.c_double(voxel_leaf), C.c_double(voxelsize),
+                                                    _p(dist) if per_point else None, _p(near) if per_point else None, C.byref(r)))
+        out = r.as_dict()
+        if per_point:
+            out["dist"] = dist[:n_e]
+            out["nearest"] = near[:n_e]
+        return out
+
+    def overlap_map(self, gt, voxelsize=0.2, voxel_leaf=0.0):
+        """overlap_report of the handle's current map (the get_map view, never copied to the host) against `gt`
+        (erasor_hip_overlap_map)"""
+        kept = []
+        g = self._eval_cloud(gt, kept)
+        r = OverlapResult()
+        self._check(lib().erasor_hip_overlap_map(self._h, *g, C.c_double(voxel_leaf), C.c_double(voxelsize), C.byref(r)))
         return r.as_dict()
 
     # -- mapgen (src/mapgen/mapgen.hpp) --

@@ -35,6 +35,7 @@
 #endif
 #include "kernels.hip.h"
 #include "evaluate.hip.h"
+#include "nearest.hip.h"
 
 using namespace ek;
 
@@ -245,7 +246,7 @@ struct erasor_hip_handle {
         bool deep = false;        // the caller had announced at least batch_lead nodes beyond this step (OvAuto samples only such steps)
     } fly;
     HostOut *pin = nullptr;         // pinned host block k_step_end reports into
-    int bank = 0;                   // scratch bank of scan/radix helpers (0: query chains, 1: map chain)
+    int bank = 0;                   // scratch bank of scan/radix helpers (0: query chains, 1: map chain, 2: the overlap report's tree)
     std::string err;
     bool have_map = false, have_step = false;
     bool poisoned = false;        // a step failed after the map store had been touched: only set_map makes the handle usable again
@@ -283,7 +284,7 @@ struct erasor_hip_handle {
     DBuf<uint32_t> voi_key, voi_src, ssrc, rejected_src, grank, glist;
     DBuf<uint8_t> gflag;
     // ---- radix ----
-    DBuf<uint32_t> rk_a, rk_b, rv_a, rv_b, hist, hist_l, hist_t, hist2, hist2_l, hist2_t, dn;
+    DBuf<uint32_t> rk_a, rk_b, rv_a, rv_b, hist, hist_l, hist_t, hist2, hist2_l, hist2_t, hist3, hist3_l, hist3_t, dn;
     // ---- bins ----
     DBuf<uint32_t> moff, mcnt, rev_idx, rev_list, vox_off, nvox, ng, out_off, ground_off, rej_off, crej_off;
     DBuf<uint32_t> out_off0, rev_before;  // the layout's R-GPF-independent part (k_srt4 -> k_assemble_map<., true>)
@@ -301,6 +302,11 @@ struct erasor_hip_handle {
         DBuf<uint32_t> bkt, cnt, pl, tops, idx;
         DBuf<unsigned long long> ctr;
         DBuf<uint8_t> code;
+        // the overlap report (erasor_hip_overlap_*): the GT tree (Morton keys and their sort, the sorted points and original indices,
+        // the node boxes), the distances' bit patterns, the nearest GT indices, the select's histograms
+        DBuf<uint32_t> nn_bb, nn_key, nn_ka, nn_kb, nn_va, nn_vb, nn_idx, nn_near, nn_hist;
+        DBuf<float4> nn_pts, nn_lo, nn_hi;
+        DBuf<unsigned long long> nn_ctr, nn_dbits;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
     // ---- per-bin scratch (R-GPF / bin voxelise global paths) ----
@@ -510,7 +516,8 @@ int radix_sort(erasor_hip_handle *h, const uint32_t *keys_in, uint32_t n_ub, con
                uint32_t *va, uint32_t *vb, const uint32_t **skeys, const uint32_t **sperm, const char *tag) {
     const uint32_t nblk = std::max(1u, cdiv(n_ub, RTILE));
     const uint32_t nhist = 256u * nblk;
-    DBuf<uint32_t> &H = h->bank ? h->hist2 : h->hist, &HL = h->bank ? h->hist2_l : h->hist_l, &HT = h->bank ? h->hist2_t : h->hist_t;
+    DBuf<uint32_t> &H = h->bank == 2 ? h->hist3 : h->bank ? h->hist2 : h->hist, &HL = h->bank == 2 ? h->hist3_l : h->bank ? h->hist2_l : h->hist_l,
+                   &HT = h->bank == 2 ? h->hist3_t : h->bank ? h->hist2_t : h->hist_t;
     if (ensure(h, H, nhist) || ensure(h, HL, nhist) || ensure(h, HT, cdiv(nhist, 1024) + 2)) return ERASOR_E_NO_DEVICE;
     const uint32_t *kin = keys_in;
     const uint32_t *vin = nullptr;
@@ -1041,7 +1048,7 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->vmask); release(h->hmask); release(h->cinfo); release(h->pvl); release(h->phl); release(h->topv); release(h->toph); release(h->topr); release(h->ometa);
     release(h->voi_ego); release(h->spts); release(h->rejected); release(h->voi_key); release(h->voi_src); release(h->ssrc);
     release(h->rejected_src); release(h->grank); release(h->glist); release(h->gflag);
-    release(h->rk_a); release(h->rk_b); release(h->rv_a); release(h->rv_b); release(h->hist); release(h->hist_l); release(h->hist_t); release(h->hist2); release(h->hist2_l); release(h->hist2_t); release(h->dn); release(h->lab_slots); release(h->mb_hist); release(h->mb_tot); release(h->mg_curr); release(h->mg_map); release(h->mg_done); release(h->mg_tmp);
+    release(h->rk_a); release(h->rk_b); release(h->rv_a); release(h->rv_b); release(h->hist); release(h->hist_l); release(h->hist_t); release(h->hist2); release(h->hist2_l); release(h->hist2_t); release(h->hist3); release(h->hist3_l); release(h->hist3_t); release(h->dn); release(h->lab_slots); release(h->mb_hist); release(h->mb_tot); release(h->mg_curr); release(h->mg_map); release(h->mg_done); release(h->mg_tmp);
     release(h->moff); release(h->mcnt); release(h->rev_idx); release(h->rev_list); release(h->vox_off);
     release(h->out_off0); release(h->rev_before); release(h->st1b);
     release(h->out_offR); release(h->gres_off);
@@ -1061,6 +1068,9 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->vox_out); release(h->d_st); release(h->d_st_get); release(h->d_ctr);
     release(h->ev.gt); release(h->ev.est); release(h->ev.map); release(h->ev.pts); release(h->ev.bkt); release(h->ev.cnt); release(h->ev.pl);
     release(h->ev.tops); release(h->ev.idx); release(h->ev.ctr); release(h->ev.code);
+    release(h->ev.nn_bb); release(h->ev.nn_key); release(h->ev.nn_ka); release(h->ev.nn_kb); release(h->ev.nn_va); release(h->ev.nn_vb);
+    release(h->ev.nn_idx); release(h->ev.nn_near); release(h->ev.nn_hist); release(h->ev.nn_pts); release(h->ev.nn_lo); release(h->ev.nn_hi);
+    release(h->ev.nn_ctr); release(h->ev.nn_dbits);
     for (int k = 0; k < NSIDE; ++k) {
         if (h->q[k].ev_keys) (void)hipEventDestroy(h->q[k].ev_keys);
         if (h->q[k].ev_done) (void)hipEventDestroy(h->q[k].ev_done);
@@ -3500,6 +3510,250 @@ int erasor_hip_evaluate_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_
         e = h->ev.est.p;
     }
     return ev_run(h, g, ng, e, ne, voxelsize, nullptr, res);
+}
+
+// ---- the estimate-to-GT overlap report (scripts/analysis_runner.py:53-71, overlap_report; kernels: nearest.hip.h) ----
+// Like ev_run: the main stream, the evaluator's scratch (h->ev), and the tree's radix sort in a histogram bank of its own (bank 2), so
+// that the query chains of nodes announced ahead (bank 0) keep theirs.
+
+// np.percentile(d, p) (method "linear") from the sorted values v(rank), operation by operation: q = p / 100, virtual index (n-1)*q,
+// previous / next index (both n-1 at or above it), gamma = index - previous, and _lerp with its t >= 0.5 branch
+static void ov_percentile_ranks(uint64_t n, double p, uint64_t *prev, uint64_t *next, double *gamma) {
+    const double q = p / 100.0;
+    const double vi = (double)(n - 1) * q;
+    double pi = floor(vi);
+    *prev = (uint64_t)pi;
+    *next = (uint64_t)pi + 1;
+    if (vi >= (double)(n - 1)) {
+        pi = -1.0;  // (numpy indexes with -1: the last value)
+        *prev = *next = n - 1;
+    }
+    *gamma = vi - pi;
+}
+static double ov_lerp(double a, double b, double t) {
+    const double diff = b - a;
+    double r = a + diff * t;
+    if (t >= 0.5) r = b - diff * (1 - t);
+    return r;
+}
+
+static int ov_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize, double *per_dist,
+                  uint32_t *per_nearest, erasor_overlap_result *res) {
+    auto &E = h->ev;
+    struct Keep {
+        erasor_hip_handle *h;
+        hipStream_t cur;
+        int bank;
+        ~Keep() {
+            h->cur = cur;
+            h->bank = bank;
+        }
+    } keep{h, h->cur, h->bank};
+    h->cur = h->stream;
+    h->bank = 2;
+    const uint32_t n_leaves = std::max(1u, cdiv(n_gt, NN_LEAF));
+    uint32_t P = 1, levels = 0;  // leaves padded to a power of two, levels below the root
+    while (P < n_leaves) {
+        P <<= 1;
+        ++levels;
+    }
+    if (levels >= NN_STACK) {
+        h->err = "erasor_hip_overlap: ground truth too large for the traversal stack";
+        return ERASOR_E_INVALID;
+    }
+    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256) ||
+        (n_est && (ensure(h, E.nn_dbits, (size_t)n_est + 1) || (per_nearest && ensure(h, E.nn_near, (size_t)n_est + 1)))))
+        return ERASOR_E_NO_DEVICE;
+    unsigned long long c[OV_NCTR];
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if (n_gt) {
+        const size_t n1 = (size_t)n_gt + 1;
+        if (ensure(h, E.nn_bb, 8) || ensure(h, E.nn_key, n1) || ensure(h, E.nn_ka, n1) || ensure(h, E.nn_kb, n1) || ensure(h, E.nn_va, n1) ||
+            ensure(h, E.nn_vb, n1) || ensure(h, E.nn_idx, n1) || ensure(h, E.nn_pts, n1) || ensure(h, E.nn_lo, 2 * (size_t)P) ||
+            ensure(h, E.nn_hi, 2 * (size_t)P))
+            return ERASOR_E_NO_DEVICE;
+        // the box: k_bbox's fkey_ord min (3 x ~0u) / max (3 x 0)
+        HIPC(h, hipMemsetAsync(E.nn_bb.p, 0xFF, 3 * sizeof(uint32_t), h->stream));
+        HIPC(h, hipMemsetAsync(E.nn_bb.p + 3, 0, 3 * sizeof(uint32_t), h->stream));
+        LAUNCH(h, "ov_tree", k_bbox, bbox_grid(n_gt), 256, gt, n_gt, E.nn_bb.p);
+        LAUNCH(h, "ov_tree", k_nn_keys, cdiv(n_gt, 256), 256, gt, n_gt, (const uint32_t *)E.nn_bb.p, E.nn_key.p, E.nn_ctr.p);
+        const uint32_t *skeys = nullptr, *sperm = nullptr;
+        if (radix_sort(h, E.nn_key.p, n_gt, nullptr, 30, E.nn_ka.p, E.nn_kb.p, E.nn_va.p, E.nn_vb.p, &skeys, &sperm, "ov_tree"))
+            return ERASOR_E_NO_DEVICE;
+        LAUNCH(h, "ov_tree", k_nn_gather, cdiv(n_gt, 256), 256, gt, n_gt, sperm, E.nn_pts.p, E.nn_idx.p);
+        LAUNCH(h, "ov_tree", k_nn_leaves, cdiv(P * NN_LEAF, 256), 256, (const float4 *)E.nn_pts.p, n_gt, P, E.nn_lo.p, E.nn_hi.p);
+        for (uint32_t first = P / 2; first >= 1; first /= 2) LAUNCH(h, "ov_tree", k_nn_level, cdiv(first, 256), 256, E.nn_lo.p, E.nn_hi.p, first);
+        HIPC(h, hipMemcpyAsync(c, E.nn_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
+        if (c[OV_NON_FINITE]) {
+            h->err = "erasor_hip_overlap: non-finite coordinate (NaN / Inf) in " + std::to_string(c[OV_NON_FINITE]) + " ground-truth point(s)";
+            return ERASOR_E_INVALID;
+        }
+    }
+    // the thresholds as overlap_report forms them: half = 0.5 * voxelsize, one = voxelsize, 2 * one
+    const double half = 0.5 * voxelsize, one = voxelsize, two = 2 * one;
+    if (n_est)
+        LAUNCH(h, "ov_query", k_nn_query, cdiv(n_est, NN_QBLOCK), NN_QBLOCK, est, n_est, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p,
+               n_gt, (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, half, one, two, E.nn_dbits.p,
+               per_nearest ? E.nn_near.p : (uint32_t *)nullptr, E.nn_ctr.p);
+    HIPC(h, hipMemcpyAsync(c, E.nn_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (c[OV_NON_FINITE]) {
+        h->err = "erasor_hip_overlap: non-finite coordinate (NaN / Inf) in " + std::to_string(c[OV_NON_FINITE]) + " estimated point(s)";
+        return ERASOR_E_INVALID;
+    }
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    erasor_overlap_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_est = n_est;
+    r.n_below_half = c[OV_BELOW_HALF];
+    r.n_below_one = c[OV_BELOW_ONE];
+    r.n_below_two = c[OV_BELOW_TWO];
+    r.median = r.p90 = r.p99 = r.max = r.frac_half = r.frac_one = r.frac_two = nan;
+    if (n_est) {
+        // target ranks: the median's one or two, the two of each percentile
+        const uint64_t n = n_est;
+        uint64_t rk[OV_SEL_MAX];
+        double g90, g99;
+        rk[0] = (n - 1) / 2;
+        rk[1] = n / 2;
+        ov_percentile_ranks(n, 90, &rk[2], &rk[3], &g90);
+        ov_percentile_ranks(n, 99, &rk[4], &rk[5], &g99);
+        // the exact radix select, from the top digit down: every target keeps its prefix and its rank inside that prefix
+        unsigned long long pref[OV_SEL_MAX] = {}, val[OV_SEL_MAX];
+        uint64_t left[OV_SEL_MAX];
+        for (uint32_t t = 0; t < OV_SEL_MAX; ++t) left[t] = rk[t];
+        std::vector<uint32_t> hist(OV_SEL_MAX * 256);
+        const uint32_t grid = std::min(cdiv(n_est, 256 * 8), 1024u);
+        for (int shift = 56; shift >= 0; shift -= 8) {
+            OvSelect s;
+            memset(&s, 0, sizeof(s));
+            s.shift = shift;
+            uint32_t slot[OV_SEL_MAX];
+            for (uint32_t t = 0; t < OV_SEL_MAX; ++t) {
+                uint32_t k = 0;
+                while (k < s.n && s.pref[k] != pref[t]) ++k;
+                if (k == s.n) s.pref[s.n++] = pref[t];
+                slot[t] = k;
+            }
+            HIPC(h, hipMemsetAsync(E.nn_hist.p, 0, (size_t)s.n * 256 * sizeof(uint32_t), h->stream));
+            LAUNCH(h, "ov_select", k_ov_select_hist, grid, 256, (const unsigned long long *)E.nn_dbits.p, n_est, s, E.nn_hist.p);
+            HIPC(h, hipMemcpyAsync(hist.data(), E.nn_hist.p, (size_t)s.n * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPC(h, hipStreamSynchronize(h->stream));
+            for (uint32_t t = 0; t < OV_SEL_MAX; ++t) {
+                const uint32_t *hh = hist.data() + (size_t)slot[t] * 256;
+                uint64_t cum = 0;
+                uint32_t d = 0;
+                while (d < 255 && left[t] >= cum + hh[d]) cum += hh[d++];
+                left[t] -= cum;
+                pref[t] = (pref[t] << 8) | d;
+            }
+        }
+        for (uint32_t t = 0; t < OV_SEL_MAX; ++t) memcpy(&val[t], &pref[t], sizeof(double));
+        double v[OV_SEL_MAX];
+        memcpy(v, val, sizeof(v));
+        // np.median: the middle value, or the mean of the two middle ones, (a + b) / 2
+        r.median = (n % 2) ? v[0] : (v[0] + v[1]) / 2.0;
+        r.p90 = ov_lerp(v[2], v[3], g90);
+        r.p99 = ov_lerp(v[4], v[5], g99);
+        double mx;
+        const unsigned long long mbits = c[OV_MAX_BITS];
+        memcpy(&mx, &mbits, sizeof(mx));
+        r.max = mx;
+        // np.mean(d < x) * 100
+        r.frac_half = (double)r.n_below_half / (double)n * 100.0;
+        r.frac_one = (double)r.n_below_one / (double)n * 100.0;
+        r.frac_two = (double)r.n_below_two / (double)n * 100.0;
+        if (per_dist) HIPC(h, hipMemcpy(per_dist, E.nn_dbits.p, (size_t)n_est * sizeof(double), hipMemcpyDeviceToHost));
+        if (per_nearest) HIPC(h, hipMemcpy(per_nearest, E.nn_near.p, (size_t)n_est * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    *res = r;
+    return ERASOR_OK;
+}
+
+static int ov_check_args(erasor_hip_handle *h, double voxel_leaf, double voxelsize, bool per_point, erasor_overlap_result *res) {
+    if (!res) {
+        h->err = "erasor_hip_overlap: res is NULL";
+        return ERASOR_E_INVALID;
+    }
+    if (!(voxelsize > 0) || !std::isfinite(voxelsize)) {
+        h->err = "erasor_hip_overlap: voxelsize must be a finite number > 0";
+        return ERASOR_E_INVALID;
+    }
+    if (!(voxel_leaf >= 0) || !std::isfinite(voxel_leaf)) {
+        h->err = "erasor_hip_overlap: voxel_leaf must be 0 or a finite number > 0";
+        return ERASOR_E_INVALID;
+    }
+    if (per_point && voxel_leaf > 0) {
+        h->err = "erasor_hip_overlap: per-point outputs need voxel_leaf == 0 (they would describe the voxelised estimate)";
+        return ERASOR_E_INVALID;
+    }
+    return ERASOR_OK;
+}
+
+int erasor_hip_overlap_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, const void *est_xyzi, size_t n_est,
+                              int est_is_device, double voxel_leaf, double voxelsize, double *per_est_dist, uint32_t *per_est_nearest,
+                              erasor_overlap_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = ov_check_args(h, voxel_leaf, voxelsize, per_est_dist || per_est_nearest, res);
+    if (rc) return rc;
+    if ((!gt_xyzi && n_gt) || (!est_xyzi && n_est) || n_gt > 0x3FFFFFFFull || n_est > 0x3FFFFFFFull) {
+        h->err = "erasor_hip_overlap_clouds: NULL cloud or more than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    if (!n_gt && n_est) {
+        h->err = "erasor_hip_overlap_clouds: empty ground truth (no nearest point to measure against)";
+        return ERASOR_E_INVALID;
+    }
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *g = nullptr, *e = nullptr;
+    if ((rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, h->ev.gt, &g)) || (rc = ev_input(h, est_xyzi, n_est, est_is_device, h->ev.est, &e))) return rc;
+    uint32_t ng = (uint32_t)n_gt, ne = (uint32_t)n_est;
+    if (voxel_leaf > 0) {
+        if ((rc = ev_voxelize(h, g, ng, voxel_leaf, h->ev.gt, &ng))) return rc;
+        if ((rc = ev_voxelize(h, e, ne, voxel_leaf, h->ev.est, &ne))) return rc;
+        g = h->ev.gt.p;
+        e = h->ev.est.p;
+    }
+    return ov_run(h, g, ng, e, ne, voxelsize, per_est_dist, per_est_nearest, res);
+}
+
+int erasor_hip_overlap_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, double voxel_leaf, double voxelsize,
+                           erasor_overlap_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = ov_check_args(h, voxel_leaf, voxelsize, false, res);
+    if (rc) return rc;
+    if (!h->have_map) {
+        h->err = "erasor_hip_overlap_map: the handle has no map (erasor_hip_set_map first)";
+        return ERASOR_E_STATE;
+    }
+    if ((!gt_xyzi && n_gt) || n_gt > 0x3FFFFFFFull) {
+        h->err = "erasor_hip_overlap_map: NULL cloud or more than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    HIPC(h, hipSetDevice(h->device));
+    size_t n_map = 0;
+    if ((rc = map_to_device(h, h->ev.map, &n_map))) return rc;
+    if (n_map > 0x3FFFFFFFull) {
+        h->err = "erasor_hip_overlap_map: map larger than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    if (!n_gt && n_map) {
+        h->err = "erasor_hip_overlap_map: empty ground truth (no nearest point to measure against)";
+        return ERASOR_E_INVALID;
+    }
+    const float4 *g = nullptr, *e = h->ev.map.p;
+    if ((rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, h->ev.gt, &g))) return rc;
+    uint32_t ng = (uint32_t)n_gt, ne = (uint32_t)n_map;
+    if (voxel_leaf > 0) {
+        if ((rc = ev_voxelize(h, g, ng, voxel_leaf, h->ev.gt, &ng))) return rc;
+        if ((rc = ev_voxelize(h, e, ne, voxel_leaf, h->ev.est, &ne))) return rc;
+        g = h->ev.gt.p;
+        e = h->ev.est.p;
+    }
+    return ov_run(h, g, ng, e, ne, voxelsize, nullptr, nullptr, res);
 }
 
 // the last step's [selected bins theta-major | ground_viz | complement] WITHOUT tf_body2origin_ (the egocentric clouds

@@ -1,0 +1,263 @@
+// nearest.hip.h — the exact nearest ground-truth point of every estimated point, however far away: analysis_runner.py's overlap_report
+// (scripts/analysis_runner.py:53-71) on the device.
+//
+// The reference fits NearestNeighbors(kd_tree) on the ground truth (GT) and queries the estimate: for every estimated point the distance
+// to its nearest GT point, then the median / p90 / p99 / max of those distances and the fractions below 0.5*v, v and 2*v.  Unlike PR / RR
+// (evaluate.hip.h: only neighbours within 0.866 cell edges matter, a 27-cell grid is exact there) the report needs the TRUE nearest
+// distance of every point -- `max` is printed, and a misaligned map puts most points more than a cell away.
+//
+// Index: a bounding-volume tree over the GT.  30-bit Morton keys (10 bits per axis over the GT's bounding box; an axis of zero extent
+// gets cell 0: planar, linear and single-point clouds) sorted stably by radix_sort, the points gathered in key order with their original
+// index, leaves of NN_LEAF consecutive sorted points with the exact float AABB of their points, and an implicit complete binary tree over
+// the leaf count padded to a power of two P (heap order: node 1 is the root, node k has children 2k and 2k+1, leaf l is node P + l).
+// Nodes without points have the empty box lo = +inf, hi = -inf.  The tree only decides the ORDER of the search, never its answer.
+//
+// Query: one estimated point per lane, depth first, nearer child first, the pending siblings on a per-lane stack in LDS (a runtime-
+// indexed per-lane array would live in scratch).  A node is pruned only when its lower bound is STRICTLY greater than the best d^2 so
+// far, so every point at the minimum d^2 is visited and ties go to the smaller GT index.  Leaf points: d^2 in float64 exactly as
+// k_ev_query / cKDTree compute it, ex = (double)q.x - (double)p.x, d^2 = (ex*ex + ey*ey) + ez*ez (the library builds with
+// -ffp-contract=off: no fused multiply-add).  d = sqrt(d^2) with the correctly rounded float64 sqrt tests/test_gpu_hooks.py pins.
+//
+// Why the pruning is exact, with no epsilon: the lower bound of a box is formed by the same operations, per axis gap = (double)lo - q if
+// q < lo, q - (double)hi if q > hi, else 0, and lb = (gx*gx + gy*gy) + gz*gz.  For a point p of the box and q < lo: p.x - q >= lo - q
+// exactly, and rounding is monotone, so fl(p.x - q) >= fl(lo - q) = gx >= 0; fl(q - p.x) = -fl(p.x - q), so ex*ex = fl(p.x - q)^2 >=
+// gx*gx (the product of non-negative values is monotone after rounding too).  The same holds for q > hi, and gx = 0 <= |ex| inside.
+// Sums of non-negative terms are monotone in each term, so lb <= d^2(p) for every p in the box: pruning on lb > best never drops a point
+// with d^2 <= best.
+//
+// Order statistics: the distances' float64 bit patterns stay on the device (every d >= +0, so unsigned order is numeric order) and an
+// exact radix select finds the ranks the median and the two percentiles need: 8 passes of 8-bit digits from the top, all target ranks in
+// the same pass; each pass is one histogram launch with 256 LDS counters per still-active prefix and one global add per non-zero bin and
+// workgroup, and only those histograms go to the host, which picks the next digit of every target.
+#ifndef ERASOR_NEAREST_HIP_H
+#define ERASOR_NEAREST_HIP_H
+
+namespace ek {
+
+// counters of one overlap report (one 64-bit atomic per wavefront and counter)
+enum : uint32_t {
+    OV_BELOW_HALF = 0,  // d < 0.5 * voxelsize
+    OV_BELOW_ONE,       // d < voxelsize
+    OV_BELOW_TWO,       // d < 2 * voxelsize
+    OV_MAX_BITS,        // the bit pattern of the largest d (atomicMax: d >= +0)
+    OV_NON_FINITE,      // points with a non-finite coordinate (the host refuses the report)
+    OV_NCTR
+};
+
+static constexpr uint32_t NN_LEAF = 32;     // sorted points per leaf
+static constexpr uint32_t NN_QBLOCK = 256;  // lanes per workgroup of k_nn_query
+static constexpr uint32_t NN_STACK = 26;    // stack entries per lane: one per level below the root, at most 2^25 leaves (2^30 points)
+static constexpr uint32_t OV_SEL_MAX = 6;   // target ranks of one select: two for the median, two for each percentile
+
+// 10 bits of v spread to every third bit
+__device__ __forceinline__ uint32_t nn_spread10(uint32_t v) {
+    v &= 0x3FFu;
+    v = (v | (v << 16)) & 0x030000FFu;
+    v = (v | (v << 8)) & 0x0300F00Fu;
+    v = (v | (v << 4)) & 0x030C30C3u;
+    v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+
+// the 10-bit cell of v on an axis of the box [lo, hi]; zero extent (and anything non-finite) gives cell 0
+__device__ __forceinline__ uint32_t nn_cell10(float v, float lo, float hi) {
+    const double ext = (double)hi - (double)lo;
+    if (!(ext > 0.0)) return 0u;
+    double t = ((double)v - (double)lo) / ext * 1024.0;
+    if (!(t >= 0.0)) t = 0.0;
+    if (t > 1023.0) t = 1023.0;
+    return (uint32_t)t;
+}
+
+// (1) Morton key of every GT point over the box k_bbox left in bb (fkey_ord order); counts the non-finite points
+__global__ __launch_bounds__(256) void k_nn_keys(const float4 *__restrict__ gt, uint32_t n, const uint32_t *__restrict__ bb,
+                                                  uint32_t *__restrict__ key, unsigned long long *__restrict__ ctr) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t bad = 0;
+    if (i < n) {
+        const float4 p = gt[i];
+        bad = ev_finite(p) ? 0u : 1u;
+        const uint32_t cx = nn_cell10(p.x, fkey_inv(bb[0]), fkey_inv(bb[3]));
+        const uint32_t cy = nn_cell10(p.y, fkey_inv(bb[1]), fkey_inv(bb[4]));
+        const uint32_t cz = nn_cell10(p.z, fkey_inv(bb[2]), fkey_inv(bb[5]));
+        key[i] = nn_spread10(cx) | (nn_spread10(cy) << 1) | (nn_spread10(cz) << 2);
+    }
+    ev_commit(ctr, OV_NON_FINITE, bad);
+}
+
+// (2) the points in key order, with their original index beside them
+__global__ __launch_bounds__(256) void k_nn_gather(const float4 *__restrict__ gt, uint32_t n, const uint32_t *__restrict__ perm,
+                                                    float4 *__restrict__ pts, uint32_t *__restrict__ idx) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = perm[i];
+    pts[i] = gt[j];
+    idx[i] = j;
+}
+
+// (3) one lane per sorted point, NN_LEAF lanes per leaf: the leaf's exact float AABB by a butterfly over the half-wavefront.  The grid
+// covers all P leaves; leaves past the last point get the empty box.  lo / hi: [2P] (node P + l is leaf l).
+__global__ __launch_bounds__(256) void k_nn_leaves(const float4 *__restrict__ pts, uint32_t n, uint32_t n_pad, float4 *__restrict__ lo,
+                                                    float4 *__restrict__ hi) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const float inf = __builtin_huge_valf();
+    float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
+    if (i < n) {
+        const float4 p = pts[i];
+        mn[0] = mx[0] = p.x;
+        mn[1] = mx[1] = p.y;
+        mn[2] = mx[2] = p.z;
+    }
+#pragma unroll
+    for (int m = NN_LEAF / 2; m >= 1; m >>= 1) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = fminf(mn[a], __shfl_xor(mn[a], m));
+            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], m));
+        }
+    }
+    const uint32_t leaf = i / NN_LEAF;
+    if ((i % NN_LEAF) == 0 && leaf < n_pad) {
+        lo[n_pad + leaf] = make_float4(mn[0], mn[1], mn[2], 0.0f);
+        hi[n_pad + leaf] = make_float4(mx[0], mx[1], mx[2], 0.0f);
+    }
+}
+
+// (4) one level of the tree, bottom-up: nodes [first, 2 * first) from their children
+__global__ __launch_bounds__(256) void k_nn_level(float4 *__restrict__ lo, float4 *__restrict__ hi, uint32_t first) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= first) return;
+    const uint32_t k = first + i;
+    const float4 a = lo[2 * k], b = lo[2 * k + 1], c = hi[2 * k], d = hi[2 * k + 1];
+    lo[k] = make_float4(fminf(a.x, b.x), fminf(a.y, b.y), fminf(a.z, b.z), 0.0f);
+    hi[k] = make_float4(fmaxf(c.x, d.x), fmaxf(c.y, d.y), fmaxf(c.z, d.z), 0.0f);
+}
+
+// the lower bound of d^2 from q to any point of the box [l, u] (exact: see the header)
+__device__ __forceinline__ double nn_lb(const float4 &l, const float4 &u, double qx, double qy, double qz) {
+    const double gx = qx < (double)l.x ? (double)l.x - qx : (qx > (double)u.x ? qx - (double)u.x : 0.0);
+    const double gy = qy < (double)l.y ? (double)l.y - qy : (qy > (double)u.y ? qy - (double)u.y : 0.0);
+    const double gz = qz < (double)l.z ? (double)l.z - qz : (qz > (double)u.z ? qz - (double)u.z : 0.0);
+    return (gx * gx + gy * gy) + gz * gz;
+}
+
+// (5) one estimated point per lane: its nearest GT point (d^2, then the smaller original index), d = sqrt(d^2) as a bit pattern in
+// dbits, the original index in nearest (optional), the three threshold counters and the maximum.  n_gt > 0.
+__global__ __launch_bounds__(NN_QBLOCK) void k_nn_query(const float4 *__restrict__ est, uint32_t n_est, const float4 *__restrict__ pts,
+                                                         const uint32_t *__restrict__ idx, uint32_t n_gt, const float4 *__restrict__ lo,
+                                                         const float4 *__restrict__ hi, uint32_t n_pad, double half, double one, double two,
+                                                         unsigned long long *__restrict__ dbits, uint32_t *__restrict__ nearest,
+                                                         unsigned long long *__restrict__ ctr) {
+    __shared__ uint32_t stack[NN_STACK * NN_QBLOCK];  // [depth][lane]: consecutive lanes in consecutive banks
+    const uint32_t t = threadIdx.x, i = blockIdx.x * NN_QBLOCK + t;
+    uint32_t bh = 0, b1 = 0, b2 = 0, bad = 0;
+    unsigned long long bits = 0ull;
+    if (i < n_est) {
+        const float4 q = est[i];
+        if (!ev_finite(q)) {
+            bad = 1;
+            dbits[i] = 0ull;
+            if (nearest) nearest[i] = 0xFFFFFFFFu;
+        } else {
+            const double qx = (double)q.x, qy = (double)q.y, qz = (double)q.z;
+            double best = __builtin_huge_val();
+            uint32_t best_i = 0xFFFFFFFFu;
+            uint32_t node = 1, sp = 0;
+            for (;;) {
+                if (node >= n_pad) {  // a leaf: its points (a leaf that is reached holds at least one)
+                    const uint32_t b = (node - n_pad) * NN_LEAF, e = b + NN_LEAF < n_gt ? b + NN_LEAF : n_gt;
+                    for (uint32_t s = b; s < e; ++s) {
+                        const float4 p = pts[s];
+                        const double ex = qx - (double)p.x, ey = qy - (double)p.y, ez = qz - (double)p.z;
+                        const double d2 = (ex * ex + ey * ey) + ez * ez;
+                        if (d2 <= best) {
+                            const uint32_t j = idx[s];
+                            if (d2 < best || j < best_i) {
+                                best = d2;
+                                best_i = j;
+                            }
+                        }
+                    }
+                } else {
+                    const uint32_t c = 2 * node;
+                    const float4 l0 = lo[c], u0 = hi[c], l1 = lo[c + 1], u1 = hi[c + 1];
+                    const double d0 = l0.x <= u0.x ? nn_lb(l0, u0, qx, qy, qz) : __builtin_huge_val();  // (empty boxes: never entered)
+                    const double d1 = l1.x <= u1.x ? nn_lb(l1, u1, qx, qy, qz) : __builtin_huge_val();
+                    const bool v0 = l0.x <= u0.x && !(d0 > best), v1 = l1.x <= u1.x && !(d1 > best);
+                    if (v0 && v1) {
+                        const uint32_t near = d1 < d0 ? c + 1 : c;
+                        stack[sp * NN_QBLOCK + t] = near ^ 1u;  // (sp < the tree's depth <= NN_STACK - 1: one entry per level above)
+                        ++sp;
+                        node = near;
+                        continue;
+                    }
+                    if (v0 || v1) {
+                        node = v0 ? c : c + 1;
+                        continue;
+                    }
+                }
+                bool more = false;  // the next pending sibling that may still hold a point at d^2 <= best
+                while (sp) {
+                    --sp;
+                    const uint32_t k = stack[sp * NN_QBLOCK + t];
+                    if (!(nn_lb(lo[k], hi[k], qx, qy, qz) > best)) {
+                        node = k;
+                        more = true;
+                        break;
+                    }
+                }
+                if (!more) break;
+            }
+            const double d = sqrt(best);
+            bh = d < half ? 1u : 0u;
+            b1 = d < one ? 1u : 0u;
+            b2 = d < two ? 1u : 0u;
+            bits = __builtin_bit_cast(unsigned long long, d);
+            dbits[i] = bits;
+            if (nearest) nearest[i] = best_i;
+        }
+    }
+    ev_commit(ctr, OV_BELOW_HALF, bh);
+    ev_commit(ctr, OV_BELOW_ONE, b1);
+    ev_commit(ctr, OV_BELOW_TWO, b2);
+    ev_commit(ctr, OV_NON_FINITE, bad);
+    // the wavefront's largest bit pattern: the high words first, then the low words of the lanes that hold the largest high word
+    const uint32_t whi = wave_minmax_u<true>((uint32_t)(bits >> 32));
+    const uint32_t wlo = wave_minmax_u<true>((uint32_t)(bits >> 32) == whi ? (uint32_t)bits : 0u);
+    const unsigned long long wmax = ((unsigned long long)whi << 32) | wlo;
+    if ((t & 63u) == 0 && wmax) atomicMax(&ctr[OV_MAX_BITS], wmax);
+}
+
+// one pass of the radix select: the values whose bits above `shift + 8` equal one of the prefixes, counted by prefix and by the 8-bit
+// digit at `shift`.  hist: [n][256], zeroed by the host.
+struct OvSelect {
+    unsigned long long pref[OV_SEL_MAX];
+    uint32_t n;
+    int shift;
+};
+__global__ __launch_bounds__(256) void k_ov_select_hist(const unsigned long long *__restrict__ v, uint32_t count, OvSelect s,
+                                                         uint32_t *__restrict__ hist) {
+    __shared__ uint32_t c[OV_SEL_MAX * 256];
+    for (uint32_t j = threadIdx.x; j < OV_SEL_MAX * 256; j += blockDim.x) c[j] = 0u;
+    __syncthreads();
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+        const unsigned long long x = v[i];
+        const unsigned long long top = s.shift >= 56 ? 0ull : x >> (s.shift + 8);
+        const uint32_t d = (uint32_t)(x >> s.shift) & 0xFFu;
+        bool done = false;
+#pragma unroll
+        for (uint32_t k = 0; k < OV_SEL_MAX; ++k) {  // (unrolled: the prefixes stay in registers, no scratch)
+            if (!done && k < s.n && top == s.pref[k]) {
+                atomicAdd(&c[k * 256 + d], 1u);
+                done = true;
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < s.n * 256; j += blockDim.x)
+        if (c[j]) atomicAdd(&hist[j], c[j]);
+}
+
+}  // namespace ek
+
+#endif  // ERASOR_NEAREST_HIP_H

@@ -139,6 +139,40 @@ static int eval_mode(int argc, char **argv) {
     erasor_hip_destroy(h);
     return rc;
 }
+// --analyze <gt> <est> [voxelsize = 0.2] [voxel_leaf = 0]: analysis_runner.py's main() on the device -- the two files, the overlap
+// report (analysis_runner.py:53-71, erasor_hip_overlap_clouds; printf's %.4f / %.2f round the binary value exactly, as Python's format
+// does) and the PR / RR row
+static int analyze_mode(int argc, char **argv) {
+    if (argc < 4) return 2;
+    const double voxelsize = argc > 4 ? atof(argv[4]) : 0.2, voxel_leaf = argc > 5 ? atof(argv[5]) : 0.0;
+    std::vector<float> gt, est;
+    if (!load_cloud_xyzi(argv[2], gt) || !load_cloud_xyzi(argv[3], est)) {
+        fprintf(stderr, "cannot read %s or %s\n", argv[2], argv[3]);
+        return 3;
+    }
+    printf("GT : %s\nEst: %s\n", argv[2], argv[3]);
+    erasor_params p;
+    erasor_hip_params_default(&p);
+    erasor_hip_handle *h = nullptr;
+    if (erasor_hip_create(&p, 0, &h) != ERASOR_OK) {
+        fprintf(stderr, "erasor_hip_create failed\n");
+        return 1;
+    }
+    erasor_overlap_result o;
+    int rc = erasor_hip_overlap_clouds(h, gt.data(), gt.size() / 4, 0, est.data(), est.size() / 4, 0, voxel_leaf, voxelsize, nullptr, nullptr, &o);
+    if (rc) {
+        fprintf(stderr, "overlap: %s (rc %d)\n", erasor_hip_last_error(h), rc);
+        erasor_hip_destroy(h);
+        return 1;
+    }
+    const double half = 0.5 * voxelsize, one = voxelsize;
+    printf("est->GT dist: median=%.4fm  p90=%.4fm  p99=%.4fm  max=%.4fm\n", o.median, o.p90, o.p99, o.max);
+    printf("  fraction <0.5*v (%.2fm): %.2f%%  <1*v (%.2fm): %.2f%%  <2*v (%.2fm): %.2f%%\n", half, o.frac_half, one, o.frac_one, 2 * one,
+           o.frac_two);
+    rc = evaluate_host(h, gt, est, voxel_leaf, voxelsize);
+    erasor_hip_destroy(h);
+    return rc;
+}
 // PR / RR of the map save_static_map(0.2) writes (voxelize_preserving_labels of map_arranged_) against a ground-truth file
 static int evaluate_saved_map(erasor::OfflineMapUpdater &updater, const std::string &gt_path) {
     std::vector<float> gt;
@@ -594,6 +628,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && std::string(argv[1]) == "--analyze") {
+        try {
+            return analyze_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--mapgen") {
         try {
             return mapgen_mode(argc, argv);
@@ -613,8 +655,8 @@ int main(int argc, char **argv) {
     if (argc < 3) {
         fprintf(stderr,
                 "usage: %s <data_dir> <n_frames> [version] [removal_interval] [gt]\n       %s --config <rosparam.yaml> [n_frames] [gt]\n"
-                "       %s --eval <gt> <est> [voxelsize] [voxel_leaf]\n",
-                argv[0], argv[0], argv[0]);
+                "       %s --eval <gt> <est> [voxelsize] [voxel_leaf]\n       %s --analyze <gt> <est> [voxelsize] [voxel_leaf]\n",
+                argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

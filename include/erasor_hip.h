@@ -280,6 +280,33 @@ int erasor_hip_evaluate_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t
 int erasor_hip_evaluate_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device,
                             double voxel_leaf, double voxelsize, erasor_eval_result *res);
 
+/* ---- the estimate-to-ground-truth overlap report: the alignment check before PR / RR (scripts/analysis_runner.py) -------------
+ * replaces: analysis_runner.py:53-71 (overlap_report).  For every estimated point the distance d to its nearest ground-truth point
+ * (exact and unbounded: float64 d^2 as cKDTree / NearestNeighbors compute it, the correctly rounded sqrt), then np.median, np.percentile
+ * (90, 99; method "linear") and the max of those distances, and np.mean(d < x) * 100 for x = 0.5 * voxelsize, voxelsize, 2 * voxelsize --
+ * each formed with numpy's operations, so the values are the reference's bit for bit.  n_est == 0: counts 0, statistics NaN. */
+typedef struct erasor_overlap_result {
+    uint64_t n_est;                                   /* distances measured (after voxel_leaf) */
+    uint64_t n_below_half, n_below_one, n_below_two;  /* d < 0.5*v, < v, < 2*v */
+    double median, p90, p99, max;                     /* metres */
+    double frac_half, frac_one, frac_two;             /* percent, np.mean(d < x) * 100 */
+} erasor_overlap_result;
+
+/* replaces: analysis_runner.py:53-71 on two caller clouds (XYZI rows; the intensity is not read), each on the host or on the handle's
+ * device (_is_device).  voxel_leaf as for erasor_hip_evaluate_clouds: > 0 voxelises both clouds first and drops nodes announced ahead;
+ * 0 works in the evaluator's own scratch and leaves announcements and the last step's clouds as they are.  per_est_dist / per_est_nearest
+ * (optional, host, n_est entries each): d of every estimated point, and the index of its nearest ground-truth point (the smallest index
+ * among points at the same d^2); only with voxel_leaf == 0.
+ * ERASOR_E_INVALID: a non-finite coordinate, voxelsize <= 0, a per-point output with voxel_leaf > 0, more than 2^30 points, or an empty
+ * ground truth with a non-empty estimate.  ERASOR_E_STATE: a step in flight. */
+int erasor_hip_overlap_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device,
+                              const void *est_xyzi, size_t n_est, int est_is_device, double voxel_leaf, double voxelsize,
+                              double *per_est_dist, uint32_t *per_est_nearest, erasor_overlap_result *res);
+/* the same with the handle's current map as the estimate (the erasor_hip_get_map view, compacted on the device, never copied to the
+ * host).  ERASOR_E_STATE: no map, or a step in flight. */
+int erasor_hip_overlap_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device,
+                           double voxel_leaf, double voxelsize, erasor_overlap_result *res);
+
 /* ---- mapgen: the step BEFORE the hot path (src/mapgen/mapgen.hpp), device-resident accumulation ----
  * replaces: mapgen::setValue + constructor (mapgen.hpp:182-196): leafsize = /map/voxelsize, is_large_scale */
 int erasor_hip_mapgen_begin(erasor_hip_handle *h, double leafsize, int is_large_scale);
