@@ -67,6 +67,22 @@ class OverlapResult(C.Structure):
         return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
 
 
+class LabelResult(C.Structure):
+    """erasor_label_result (include/erasor_hip.h): label_map of a map without labels (fill_removert_intensity.cpp:24-59)"""
+    _fields_ = [("n_src", C.c_uint64), ("n_out", C.c_uint64), ("n_tied", C.c_uint64), ("passthrough", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class ComplementResult(C.Structure):
+    """erasor_complement_result (include/erasor_hip.h): calc_complement's lost static points (compare_complement.cpp:43-75)"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_gt", "n_gt_static", "n_lost", "n_label_out_of_range")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 # per-ground-truth-point codes of Erasor.evaluate(per_point=True)
 EVAL_OUT, EVAL_KEPT_STATIC, EVAL_KEPT_DYNAMIC, EVAL_CLASS_DIFFERS = 0, 1, 2, 3
 
@@ -448,6 +464,32 @@ class Erasor:
         r = OverlapResult()
         self._check(lib().erasor_hip_overlap_map(self._h, *g, C.c_double(voxel_leaf), C.c_double(voxelsize), C.byref(r)))
         return r.as_dict()
+
+    # -- maps without labels (fill_removert_intensity.cpp:24-59, compare_complement.cpp:43-75; on the host: evalmap.label_from /
+    # evalmap.static_complement) --
+    def label_map(self, src, medium, leaf=0.2):
+        """label_map on the device (erasor_hip_label_map): `src` voxelised by VoxelGrid at `leaf`, each centroid labelled with the
+        intensity of its nearest `medium` point (float32 d^2 as KdTreeFLANN, the lowest index on ties).  Clouds as for evaluate.
+        Returns (rows, {"n_src", "n_out", "n_tied", "passthrough"})."""
+        kept = []
+        s = self._eval_cloud(src, kept)
+        m = self._eval_cloud(medium, kept)
+        out = np.empty((max(s[1].value, 1), 4), np.float32)
+        r = LabelResult()
+        self._check(lib().erasor_hip_label_map(self._h, *s, *m, C.c_double(leaf), _p(out), C.c_size_t(len(out)), C.byref(r)))
+        return out[: r.n_out].copy(), r.as_dict()
+
+    def static_complement(self, est, gt):
+        """calc_complement on the device (erasor_hip_static_complement): the static points of the labelled ground truth `gt` whose
+        nearest point of the estimate `est` has a float32 d^2 > 0.03, in ground-truth order.  Clouds as for evaluate.
+        Returns (rows, {"n_gt", "n_gt_static", "n_lost", "n_label_out_of_range"})."""
+        kept = []
+        e = self._eval_cloud(est, kept)
+        g = self._eval_cloud(gt, kept)
+        out = np.empty((max(g[1].value, 1), 4), np.float32)
+        r = ComplementResult()
+        self._check(lib().erasor_hip_static_complement(self._h, *e, *g, _p(out), C.c_size_t(len(out)), C.byref(r)))
+        return out[: r.n_lost].copy(), r.as_dict()
 
     # -- mapgen (src/mapgen/mapgen.hpp) --
     def mapgen_begin(self, leafsize, is_large_scale=False):

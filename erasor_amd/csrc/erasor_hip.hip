@@ -307,6 +307,11 @@ struct erasor_hip_handle {
         DBuf<uint32_t> nn_bb, nn_key, nn_ka, nn_kb, nn_va, nn_vb, nn_idx, nn_near, nn_hist;
         DBuf<float4> nn_pts, nn_lo, nn_hi;
         DBuf<unsigned long long> nn_ctr, nn_dbits;
+        // label_map / static_complement (erasor_hip_label_map, erasor_hip_static_complement): the same tree, then the labelled rows or the
+        // lost flags, their exclusive scan and the compacted lost points, and the counters
+        DBuf<float4> fm_out;
+        DBuf<uint32_t> fm_flag, fm_pl, fm_tops;
+        DBuf<unsigned long long> fm_ctr;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
     // ---- per-bin scratch (R-GPF / bin voxelise global paths) ----
@@ -1071,6 +1076,7 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->ev.nn_bb); release(h->ev.nn_key); release(h->ev.nn_ka); release(h->ev.nn_kb); release(h->ev.nn_va); release(h->ev.nn_vb);
     release(h->ev.nn_idx); release(h->ev.nn_near); release(h->ev.nn_hist); release(h->ev.nn_pts); release(h->ev.nn_lo); release(h->ev.nn_hi);
     release(h->ev.nn_ctr); release(h->ev.nn_dbits);
+    release(h->ev.fm_out); release(h->ev.fm_flag); release(h->ev.fm_pl); release(h->ev.fm_tops); release(h->ev.fm_ctr);
     for (int k = 0; k < NSIDE; ++k) {
         if (h->q[k].ev_keys) (void)hipEventDestroy(h->q[k].ev_keys);
         if (h->q[k].ev_done) (void)hipEventDestroy(h->q[k].ev_done);
@@ -3349,7 +3355,7 @@ int erasor_hip_get_map(erasor_hip_handle *h, float *dst, size_t cap, size_t *n) 
     return rc;
 }
 
-static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t ns, double leaf_size, uint32_t *nq_out);
+static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t ns, double leaf_size, uint32_t *nq_out, bool *passthrough = nullptr);
 
 // ---- PR / RR of a cleaned map against a labelled ground-truth map (scripts/analysis_runner.py:74-105; kernels: evaluate.hip.h) ----
 // Everything runs on the main stream, behind whatever a collected step launched ahead there, in the handle's own scratch (h->ev).
@@ -3407,12 +3413,15 @@ static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const f
     return ERASOR_OK;
 }
 
-// voxelize_preserving_labels of a device cloud at `leaf` (the save_static_map protocol, OMU.cpp:174-196) into dst (borrows a query side)
-static int ev_voxelize(erasor_hip_handle *h, const float4 *src, uint32_t n, double leaf, DBuf<float4> &dst, uint32_t *n_out) {
+// voxelize_preserving_labels of a device cloud at `leaf` (the save_static_map protocol, OMU.cpp:174-196) into dst (borrows a query side).
+// passthrough (optional): set when VoxelGrid's indices overflowed and the cloud came back unchanged.
+static int ev_voxelize(erasor_hip_handle *h, const float4 *src, uint32_t n, double leaf, DBuf<float4> &dst, uint32_t *n_out,
+                       bool *passthrough = nullptr) {
     *n_out = 0;
+    if (passthrough) *passthrough = false;
     if (!n) return ERASOR_OK;
     uint32_t nq = 0;
-    const int rc = voxelize_device(h, src, n, leaf, &nq);
+    const int rc = voxelize_device(h, src, n, leaf, &nq, passthrough);
     if (rc) return rc;
     if (ensure(h, dst, (size_t)nq + 1)) return ERASOR_E_NO_DEVICE;  // (nq <= n: no reallocation when src is dst itself)
     if (nq) HIPC(h, hipMemcpyAsync(dst.p, Q(h).query.p, (size_t)nq * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
@@ -3537,59 +3546,81 @@ static double ov_lerp(double a, double b, double t) {
     return r;
 }
 
-static int ov_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize, double *per_dist,
-                  uint32_t *per_nearest, erasor_overlap_result *res) {
-    auto &E = h->ev;
-    struct Keep {
-        erasor_hip_handle *h;
-        hipStream_t cur;
-        int bank;
-        ~Keep() {
-            h->cur = cur;
-            h->bank = bank;
-        }
-    } keep{h, h->cur, h->bank};
-    h->cur = h->stream;
-    h->bank = 2;
-    const uint32_t n_leaves = std::max(1u, cdiv(n_gt, NN_LEAF));
+// The tree calls (overlap, label_map, static_complement) run on the main stream, in the evaluator's scratch, with the tree's radix sort
+// in histogram bank 2; this restores the caller's stream and bank.
+struct NnScope {
+    erasor_hip_handle *h;
+    hipStream_t cur;
+    int bank;
+    explicit NnScope(erasor_hip_handle *hh) : h(hh), cur(hh->cur), bank(hh->bank) {
+        h->cur = h->stream;
+        h->bank = 2;
+    }
+    ~NnScope() {
+        h->cur = cur;
+        h->bank = bank;
+    }
+};
+
+// the leaf count of an n-point tree padded to a power of two (P); refused when its depth would not fit the traversal stack
+static int nn_pad(erasor_hip_handle *h, uint32_t n, uint32_t *P_out, const char *who, const char *cloud) {
+    const uint32_t n_leaves = std::max(1u, cdiv(n, NN_LEAF));
     uint32_t P = 1, levels = 0;  // leaves padded to a power of two, levels below the root
     while (P < n_leaves) {
         P <<= 1;
         ++levels;
     }
     if (levels >= NN_STACK) {
-        h->err = "erasor_hip_overlap: ground truth too large for the traversal stack";
+        h->err = std::string(who) + ": " + cloud + " too large for the traversal stack";
         return ERASOR_E_INVALID;
     }
+    *P_out = P;
+    return ERASOR_OK;
+}
+
+// the bounding-volume tree over pts[0 .. n) (n > 0; nearest.hip.h) into E.nn_pts / nn_idx / nn_lo / nn_hi, P from nn_pad.  E.nn_ctr
+// (OV_NCTR entries) is zeroed by the caller; a non-finite point refuses the call ("<who>: ... in <k> <noun>").
+static int nn_tree(erasor_hip_handle *h, const float4 *pts, uint32_t n, uint32_t P, const char *who, const char *noun) {
+    auto &E = h->ev;
+    const size_t n1 = (size_t)n + 1;
+    if (ensure(h, E.nn_bb, 8) || ensure(h, E.nn_key, n1) || ensure(h, E.nn_ka, n1) || ensure(h, E.nn_kb, n1) || ensure(h, E.nn_va, n1) ||
+        ensure(h, E.nn_vb, n1) || ensure(h, E.nn_idx, n1) || ensure(h, E.nn_pts, n1) || ensure(h, E.nn_lo, 2 * (size_t)P) ||
+        ensure(h, E.nn_hi, 2 * (size_t)P))
+        return ERASOR_E_NO_DEVICE;
+    // the box: k_bbox's fkey_ord min (3 x ~0u) / max (3 x 0)
+    HIPC(h, hipMemsetAsync(E.nn_bb.p, 0xFF, 3 * sizeof(uint32_t), h->stream));
+    HIPC(h, hipMemsetAsync(E.nn_bb.p + 3, 0, 3 * sizeof(uint32_t), h->stream));
+    LAUNCH(h, "ov_tree", k_bbox, bbox_grid(n), 256, pts, n, E.nn_bb.p);
+    LAUNCH(h, "ov_tree", k_nn_keys, cdiv(n, 256), 256, pts, n, (const uint32_t *)E.nn_bb.p, E.nn_key.p, E.nn_ctr.p);
+    const uint32_t *skeys = nullptr, *sperm = nullptr;
+    if (radix_sort(h, E.nn_key.p, n, nullptr, 30, E.nn_ka.p, E.nn_kb.p, E.nn_va.p, E.nn_vb.p, &skeys, &sperm, "ov_tree"))
+        return ERASOR_E_NO_DEVICE;
+    LAUNCH(h, "ov_tree", k_nn_gather, cdiv(n, 256), 256, pts, n, sperm, E.nn_pts.p, E.nn_idx.p);
+    LAUNCH(h, "ov_tree", k_nn_leaves, cdiv(P * NN_LEAF, 256), 256, (const float4 *)E.nn_pts.p, n, P, E.nn_lo.p, E.nn_hi.p);
+    for (uint32_t first = P / 2; first >= 1; first /= 2) LAUNCH(h, "ov_tree", k_nn_level, cdiv(first, 256), 256, E.nn_lo.p, E.nn_hi.p, first);
+    unsigned long long c[OV_NCTR];
+    HIPC(h, hipMemcpyAsync(c, E.nn_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (c[OV_NON_FINITE]) {
+        h->err = std::string(who) + ": non-finite coordinate (NaN / Inf) in " + std::to_string(c[OV_NON_FINITE]) + " " + noun;
+        return ERASOR_E_INVALID;
+    }
+    return ERASOR_OK;
+}
+
+static int ov_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize, double *per_dist,
+                  uint32_t *per_nearest, erasor_overlap_result *res) {
+    auto &E = h->ev;
+    NnScope scope(h);
+    uint32_t P = 1;
+    int rc = nn_pad(h, n_gt, &P, "erasor_hip_overlap", "ground truth");
+    if (rc) return rc;
     if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256) ||
         (n_est && (ensure(h, E.nn_dbits, (size_t)n_est + 1) || (per_nearest && ensure(h, E.nn_near, (size_t)n_est + 1)))))
         return ERASOR_E_NO_DEVICE;
     unsigned long long c[OV_NCTR];
     HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
-    if (n_gt) {
-        const size_t n1 = (size_t)n_gt + 1;
-        if (ensure(h, E.nn_bb, 8) || ensure(h, E.nn_key, n1) || ensure(h, E.nn_ka, n1) || ensure(h, E.nn_kb, n1) || ensure(h, E.nn_va, n1) ||
-            ensure(h, E.nn_vb, n1) || ensure(h, E.nn_idx, n1) || ensure(h, E.nn_pts, n1) || ensure(h, E.nn_lo, 2 * (size_t)P) ||
-            ensure(h, E.nn_hi, 2 * (size_t)P))
-            return ERASOR_E_NO_DEVICE;
-        // the box: k_bbox's fkey_ord min (3 x ~0u) / max (3 x 0)
-        HIPC(h, hipMemsetAsync(E.nn_bb.p, 0xFF, 3 * sizeof(uint32_t), h->stream));
-        HIPC(h, hipMemsetAsync(E.nn_bb.p + 3, 0, 3 * sizeof(uint32_t), h->stream));
-        LAUNCH(h, "ov_tree", k_bbox, bbox_grid(n_gt), 256, gt, n_gt, E.nn_bb.p);
-        LAUNCH(h, "ov_tree", k_nn_keys, cdiv(n_gt, 256), 256, gt, n_gt, (const uint32_t *)E.nn_bb.p, E.nn_key.p, E.nn_ctr.p);
-        const uint32_t *skeys = nullptr, *sperm = nullptr;
-        if (radix_sort(h, E.nn_key.p, n_gt, nullptr, 30, E.nn_ka.p, E.nn_kb.p, E.nn_va.p, E.nn_vb.p, &skeys, &sperm, "ov_tree"))
-            return ERASOR_E_NO_DEVICE;
-        LAUNCH(h, "ov_tree", k_nn_gather, cdiv(n_gt, 256), 256, gt, n_gt, sperm, E.nn_pts.p, E.nn_idx.p);
-        LAUNCH(h, "ov_tree", k_nn_leaves, cdiv(P * NN_LEAF, 256), 256, (const float4 *)E.nn_pts.p, n_gt, P, E.nn_lo.p, E.nn_hi.p);
-        for (uint32_t first = P / 2; first >= 1; first /= 2) LAUNCH(h, "ov_tree", k_nn_level, cdiv(first, 256), 256, E.nn_lo.p, E.nn_hi.p, first);
-        HIPC(h, hipMemcpyAsync(c, E.nn_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-        HIPC(h, hipStreamSynchronize(h->stream));
-        if (c[OV_NON_FINITE]) {
-            h->err = "erasor_hip_overlap: non-finite coordinate (NaN / Inf) in " + std::to_string(c[OV_NON_FINITE]) + " ground-truth point(s)";
-            return ERASOR_E_INVALID;
-        }
-    }
+    if (n_gt && (rc = nn_tree(h, gt, n_gt, P, "erasor_hip_overlap", "ground-truth point(s)"))) return rc;
     // the thresholds as overlap_report forms them: half = 0.5 * voxelsize, one = voxelsize, 2 * one
     const double half = 0.5 * voxelsize, one = voxelsize, two = 2 * one;
     if (n_est)
@@ -3754,6 +3785,135 @@ int erasor_hip_overlap_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_g
         e = h->ev.est.p;
     }
     return ov_run(h, g, ng, e, ne, voxelsize, nullptr, nullptr, res);
+}
+
+// ---- label_map (fill_removert_intensity.cpp:24-59, compare_map.cpp:77-110) and calc_complement (compare_complement.cpp:43-75): the
+// overlap report's tree searched in FLANN's float32 metric (kernels: nearest.hip.h).  Like ov_run: the main stream, the evaluator's
+// scratch, the tree's sort in bank 2.
+
+static int fm_check_clouds(erasor_hip_handle *h, const char *who, const void *a, size_t na, const void *b, size_t nb) {
+    if ((!a && na) || (!b && nb) || na > 0x3FFFFFFFull || nb > 0x3FFFFFFFull) {
+        h->err = std::string(who) + ": NULL cloud or more than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    return ERASOR_OK;
+}
+
+int erasor_hip_label_map(erasor_hip_handle *h, const void *src_xyzi, size_t n_src, int src_is_device, const void *medium_xyzi, size_t n_medium,
+                         int medium_is_device, double leaf, float *dst_xyzi, size_t cap_points, erasor_label_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    if (!res) {
+        h->err = "erasor_hip_label_map: res is NULL";
+        return ERASOR_E_INVALID;
+    }
+    if (!(leaf > 0) || !std::isfinite(leaf)) {
+        h->err = "erasor_hip_label_map: leaf must be a finite number > 0";
+        return ERASOR_E_INVALID;
+    }
+    int rc = fm_check_clouds(h, "erasor_hip_label_map", src_xyzi, n_src, medium_xyzi, n_medium);
+    if (rc) return rc;
+    if (n_src && !n_medium) {
+        h->err = "erasor_hip_label_map: empty medium (no labelled point to take a label from)";
+        return ERASOR_E_INVALID;
+    }
+    erasor_label_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_src = n_src;
+    if (!n_src) {
+        *res = r;
+        return ERASOR_OK;
+    }
+    HIPC(h, hipSetDevice(h->device));
+    auto &E = h->ev;
+    const float4 *s = nullptr, *m = nullptr;
+    if ((rc = ev_input(h, src_xyzi, n_src, src_is_device, E.est, &s)) || (rc = ev_input(h, medium_xyzi, n_medium, medium_is_device, E.gt, &m)))
+        return rc;
+    // 1. pcl::VoxelGrid at leaf (the centroids; their w is not read).  Index overflow: the input itself, as PCL returns it
+    uint32_t nq = 0;
+    bool passthrough = false;
+    if ((rc = ev_voxelize(h, s, (uint32_t)n_src, leaf, E.est, &nq, &passthrough))) return rc;
+    // 2. every centroid takes the intensity of its nearest medium point (KdTreeFLANN, K = 1)
+    NnScope scope(h);
+    const uint32_t nm = (uint32_t)n_medium;
+    uint32_t P = 1;
+    if ((rc = nn_pad(h, nm, &P, "erasor_hip_label_map", "medium"))) return rc;
+    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.fm_ctr, FM_NCTR) || ensure(h, E.fm_out, (size_t)nq + 1)) return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if ((rc = nn_tree(h, m, nm, P, "erasor_hip_label_map", "medium point(s)"))) return rc;
+    HIPC(h, hipMemsetAsync(E.fm_ctr.p, 0, FM_NCTR * sizeof(unsigned long long), h->stream));
+    if (nq)
+        LAUNCH(h, "lm_query", k_lm_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, (const float4 *)E.est.p, nq, (const float4 *)E.nn_pts.p,
+               (const uint32_t *)E.nn_idx.p, nm, (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, E.fm_out.p, E.fm_ctr.p);
+    unsigned long long c[FM_NCTR];
+    HIPC(h, hipMemcpyAsync(c, E.fm_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (c[FM_NON_FINITE]) {
+        h->err = "erasor_hip_label_map: non-finite coordinate (NaN / Inf) in " + std::to_string(c[FM_NON_FINITE]) + " centroid(s)";
+        return ERASOR_E_INVALID;
+    }
+    r.n_out = nq;
+    r.n_tied = c[FM_TIED];
+    r.passthrough = passthrough ? 1u : 0u;
+    *res = r;
+    if (!dst_xyzi) return ERASOR_OK;
+    if (nq > cap_points) return ERASOR_E_CAPACITY;
+    return d2h(h, dst_xyzi, E.fm_out.p, (size_t)nq * sizeof(float4));
+}
+
+int erasor_hip_static_complement(erasor_hip_handle *h, const void *est_xyzi, size_t n_est, int est_is_device, const void *gt_xyzi, size_t n_gt,
+                                 int gt_is_device, float *dst_xyzi, size_t cap_points, erasor_complement_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    if (!res) {
+        h->err = "erasor_hip_static_complement: res is NULL";
+        return ERASOR_E_INVALID;
+    }
+    int rc = fm_check_clouds(h, "erasor_hip_static_complement", est_xyzi, n_est, gt_xyzi, n_gt);
+    if (rc) return rc;
+    erasor_complement_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_gt = n_gt;
+    if (!n_gt) {
+        *res = r;
+        return ERASOR_OK;
+    }
+    HIPC(h, hipSetDevice(h->device));
+    auto &E = h->ev;
+    const float4 *e = nullptr, *g = nullptr;
+    if ((rc = ev_input(h, est_xyzi, n_est, est_is_device, E.est, &e)) || (rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, E.gt, &g))) return rc;
+    NnScope scope(h);
+    const uint32_t ne = (uint32_t)n_est, ng = (uint32_t)n_gt;
+    uint32_t P = 1;
+    if ((rc = nn_pad(h, ne, &P, "erasor_hip_static_complement", "estimate"))) return rc;
+    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.fm_ctr, FM_NCTR) || ensure(h, E.fm_flag, (size_t)ng + 1) || ensure(h, E.fm_pl, (size_t)ng + 1) ||
+        ensure(h, E.fm_tops, ng / 1024 + 4) || ensure(h, E.fm_out, (size_t)ng + 1))
+        return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if (ne && (rc = nn_tree(h, e, ne, P, "erasor_hip_static_complement", "estimated point(s)"))) return rc;
+    HIPC(h, hipMemsetAsync(E.fm_ctr.p, 0, FM_NCTR * sizeof(unsigned long long), h->stream));
+    // the lost flags, then the lost points in ground-truth order: an exclusive scan of the flags and a scatter (no atomic decides a slot)
+    LAUNCH(h, "cp_query", k_cp_query, cdiv(ng, NN_QBLOCK), NN_QBLOCK, g, ng, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, ne,
+           (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, 0.03, E.fm_flag.p, E.fm_ctr.p);
+    if (dst_xyzi) {
+        scan_u32(h, E.fm_flag.p, E.fm_pl.p, E.fm_tops.p, ng, ng, nullptr, nullptr, "cp_compact");
+        LAUNCH(h, "cp_compact", k_f_compact, cdiv(ng, 256), 256, g, ng, (const uint32_t *)E.fm_flag.p, (const uint32_t *)E.fm_pl.p,
+               (const uint32_t *)E.fm_tops.p, E.fm_out.p);
+    }
+    unsigned long long c[FM_NCTR];
+    HIPC(h, hipMemcpyAsync(c, E.fm_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (c[FM_NON_FINITE]) {
+        h->err = "erasor_hip_static_complement: non-finite coordinate (NaN / Inf) in " + std::to_string(c[FM_NON_FINITE]) + " ground-truth point(s)";
+        return ERASOR_E_INVALID;
+    }
+    r.n_gt_static = c[FM_GT_STATIC];
+    r.n_lost = c[FM_LOST];
+    r.n_label_out_of_range = c[FM_LABEL_OOR];
+    *res = r;
+    if (!dst_xyzi) return ERASOR_OK;
+    if (r.n_lost > cap_points) return ERASOR_E_CAPACITY;
+    return d2h(h, dst_xyzi, E.fm_out.p, (size_t)r.n_lost * sizeof(float4));
 }
 
 // the last step's [selected bins theta-major | ground_viz | complement] WITHOUT tf_body2origin_ (the egocentric clouds
@@ -3958,7 +4118,8 @@ int erasor_hip_get_planes(erasor_hip_handle *h, uint32_t *bin_index, float *norm
 
 // erasor_utils::voxelize_preserving_labels (utils.cpp:80-114) of a DEVICE cloud; the result is Q(h).query[0..*nq_out).
 // d_src may be any device buffer except the scan-side scratch itself.
-static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t ns, double leaf_size, uint32_t *nq_out) {
+static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t ns, double leaf_size, uint32_t *nq_out, bool *passthrough) {
+    if (passthrough) *passthrough = false;
     q_drain(h);
     // this borrows the query side of the last finished step: its QUERY_VOI / STATIC_ESTIMATE / ... read-backs are gone
     // (erasor_hip_get_cloud answers ERASOR_E_STATE until the next step instead of handing out clobbered buffers)
@@ -3983,6 +4144,7 @@ static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t n
         if (rc) return rc;
         HIPC(h, hipStreamSynchronize(h->stream));
         *nq_out = ns;
+        if (passthrough) *passthrough = true;
         return ERASOR_OK;
     }
     const uint32_t nq = nvox_host;

@@ -29,6 +29,9 @@
 // exact radix select finds the ranks the median and the two percentiles need: 8 passes of 8-bit digits from the top, all target ranks in
 // the same pass; each pass is one histogram launch with 256 LDS counters per still-active prefix and one global add per non-zero bin and
 // workgroup, and only those histograms go to the host, which picks the next digit of every target.
+//
+// label_map and calc_complement (third-party maps without labels, the static points a method lost) search the same tree in FLANN's
+// float32 metric instead: k_lm_query / k_cp_query, below k_nn_query, where the exactness argument is restated for float.
 #ifndef ERASOR_NEAREST_HIP_H
 #define ERASOR_NEAREST_HIP_H
 
@@ -226,6 +229,166 @@ __global__ __launch_bounds__(NN_QBLOCK) void k_nn_query(const float4 *__restrict
     const uint32_t wlo = wave_minmax_u<true>((uint32_t)(bits >> 32) == whi ? (uint32_t)bits : 0u);
     const unsigned long long wmax = ((unsigned long long)whi << 32) | wlo;
     if ((t & 63u) == 0 && wmax) atomicMax(&ctr[OV_MAX_BITS], wmax);
+}
+
+// ---- the same tree searched in FLANN's metric: label_map (fill_removert_intensity.cpp:24-59, compare_map.cpp:77-110) and calc_complement
+// (compare_complement.cpp:43-75) query a pcl::KdTreeFLANN, K = 1, whose distance is L2_Simple in float32: r = 0; r += dx*dx; r += dy*dy;
+// r += dz*dz with dx = q.x - p.x in float (FLANN's L2_Simple; no fused multiply-add: -ffp-contract=off), and
+// whose ties go to the lowest index.  The traversal, the LDS stack and the strict pruning are k_nn_query's; only the arithmetic differs.
+//
+// Why the pruning stays exact in float: the lower bound is formed by the same float operations on the box gaps, gx = l.x - q.x if
+// q.x < l.x, q.x - u.x if q.x > u.x, else 0, and lb = ((0 + gx*gx) + gy*gy) + gz*gz.  For a point p of the box and q.x < l.x:
+// p.x - q.x >= l.x - q.x exactly, and rounding to nearest is monotone, so fl(p.x - q.x) >= fl(l.x - q.x) = gx >= 0; fl(q.x - p.x) =
+// -fl(p.x - q.x) (rounding to nearest is symmetric), so fl(dx*dx) >= fl(gx*gx).  The same holds for q.x > u.x, and gx = 0 <= |dx|
+// inside.  Sums of non-negative floats are monotone in each term after rounding, so lb <= d^2(p) for every p of the box, and pruning on
+// lb > best never drops a point with d^2 <= best.  Nothing here relies on gradual underflow, but the answer does: a difference of
+// 1e-20 squares to a subnormal, which flushing would tie with an exact 0.  The library keeps f32 denormals (hipcc's default for
+// gfx950: the kernels' float denorm mode is "flush none"), as the host's float arithmetic does.
+//
+// Ties: the label a query takes depends on the tie rule only when the points at its minimum d^2 carry different intensity bits; those
+// queries are counted (FM_TIED), in the spirit of the evaluator's n_tied.
+
+// counters of one label_map / static_complement call (one 64-bit atomic per wavefront and counter)
+enum : uint32_t {
+    FM_TIED = 0,     // label_map: queries whose minimum d^2 is shared by medium points of different intensity bits
+    FM_GT_STATIC,    // static_complement: static ground-truth points
+    FM_LOST,         // static_complement: static ground-truth points whose nearest estimated point is farther than the threshold
+    FM_LABEL_OOR,    // static_complement: intensities that are not finite or outside [0, 2^32): decoded as static
+    FM_NON_FINITE,   // query points with a non-finite coordinate (the host refuses the call)
+    FM_NCTR
+};
+
+// the float lower bound of d^2 from q to any point of the box [l, u] (exact: see above)
+__device__ __forceinline__ float nn_lb_f32(const float4 &l, const float4 &u, float qx, float qy, float qz) {
+    const float gx = qx < l.x ? l.x - qx : (qx > u.x ? qx - u.x : 0.0f);
+    const float gy = qy < l.y ? l.y - qy : (qy > u.y ? qy - u.y : 0.0f);
+    const float gz = qz < l.z ? l.z - qz : (qz > u.z ? qz - u.z : 0.0f);
+    float r = 0.0f;
+    r += gx * gx;
+    r += gy * gy;
+    r += gz * gz;
+    return r;
+}
+
+// the exact float32 1-NN of q over the tree (n > 0, q finite): best d^2, the smallest original index at it, that point's w bits, and
+// whether the points at the minimum carry more than one w bit pattern.  stack: the workgroup's [NN_STACK][NN_QBLOCK] LDS array.
+struct NnF32 {
+    float d2;
+    uint32_t idx, w;
+    bool mixed;
+};
+__device__ __forceinline__ NnF32 nn_search_f32(float qx, float qy, float qz, const float4 *__restrict__ pts, const uint32_t *__restrict__ idx,
+                                               uint32_t n, const float4 *__restrict__ lo, const float4 *__restrict__ hi, uint32_t n_pad,
+                                               uint32_t *stack, uint32_t t) {
+    NnF32 b{__builtin_huge_valf(), 0xFFFFFFFFu, 0u, false};
+    uint32_t node = 1, sp = 0;
+    for (;;) {
+        if (node >= n_pad) {  // a leaf: its points (a leaf that is reached holds at least one)
+            const uint32_t s0 = (node - n_pad) * NN_LEAF, e = s0 + NN_LEAF < n ? s0 + NN_LEAF : n;
+            for (uint32_t s = s0; s < e; ++s) {
+                const float4 p = pts[s];
+                const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
+                float r = 0.0f;
+                r += dx * dx;
+                r += dy * dy;
+                r += dz * dz;
+                if (r <= b.d2) {
+                    const uint32_t j = idx[s], w = __float_as_uint(p.w);
+                    if (r < b.d2) {
+                        b.d2 = r;
+                        b.idx = j;
+                        b.w = w;
+                        b.mixed = false;
+                    } else {  // the same d^2: the smaller index is the answer, a second bit pattern makes the query tied
+                        if (w != b.w) b.mixed = true;
+                        if (j < b.idx) {
+                            b.idx = j;
+                            b.w = w;
+                        }
+                    }
+                }
+            }
+        } else {
+            const uint32_t c = 2 * node;
+            const float4 l0 = lo[c], u0 = hi[c], l1 = lo[c + 1], u1 = hi[c + 1];
+            const float d0 = l0.x <= u0.x ? nn_lb_f32(l0, u0, qx, qy, qz) : __builtin_huge_valf();  // (empty boxes: never entered)
+            const float d1 = l1.x <= u1.x ? nn_lb_f32(l1, u1, qx, qy, qz) : __builtin_huge_valf();
+            const bool v0 = l0.x <= u0.x && !(d0 > b.d2), v1 = l1.x <= u1.x && !(d1 > b.d2);
+            if (v0 && v1) {
+                const uint32_t near = d1 < d0 ? c + 1 : c;
+                stack[sp * NN_QBLOCK + t] = near ^ 1u;  // (sp < the tree's depth <= NN_STACK - 1: one entry per level above)
+                ++sp;
+                node = near;
+                continue;
+            }
+            if (v0 || v1) {
+                node = v0 ? c : c + 1;
+                continue;
+            }
+        }
+        bool more = false;  // the next pending sibling that may still hold a point at d^2 <= best
+        while (sp) {
+            --sp;
+            const uint32_t k = stack[sp * NN_QBLOCK + t];
+            if (!(nn_lb_f32(lo[k], hi[k], qx, qy, qz) > b.d2)) {
+                node = k;
+                more = true;
+                break;
+            }
+        }
+        if (!more) break;
+    }
+    return b;
+}
+
+// label_map: one centroid per lane; the row out[i] = (centroid x, y, z, w of its nearest medium point, copied as bits).  n_med > 0.
+__global__ __launch_bounds__(NN_QBLOCK) void k_lm_query(const float4 *__restrict__ cent, uint32_t n_q, const float4 *__restrict__ pts,
+                                                         const uint32_t *__restrict__ idx, uint32_t n_med, const float4 *__restrict__ lo,
+                                                         const float4 *__restrict__ hi, uint32_t n_pad, float4 *__restrict__ out,
+                                                         unsigned long long *__restrict__ ctr) {
+    __shared__ uint32_t stack[NN_STACK * NN_QBLOCK];
+    const uint32_t t = threadIdx.x, i = blockIdx.x * NN_QBLOCK + t;
+    uint32_t tied = 0, bad = 0;
+    if (i < n_q) {
+        const float4 q = cent[i];
+        if (!ev_finite(q)) {
+            bad = 1;
+            out[i] = q;
+        } else {
+            const NnF32 b = nn_search_f32(q.x, q.y, q.z, pts, idx, n_med, lo, hi, n_pad, stack, t);
+            out[i] = make_float4(q.x, q.y, q.z, __uint_as_float(b.w));
+            tied = b.mixed ? 1u : 0u;
+        }
+    }
+    ev_commit(ctr, FM_TIED, tied);
+    ev_commit(ctr, FM_NON_FINITE, bad);
+}
+
+// static_complement: one ground-truth point per lane; lost[i] = 1 when the point is static and its nearest estimated point's float
+// d^2, widened to double, is > thr (calc_complement's `pointNKNSquaredDistance[0] > 0.03`: a float against a double literal).  n_est == 0:
+// every static point is lost (d^2 = +inf).
+__global__ __launch_bounds__(NN_QBLOCK) void k_cp_query(const float4 *__restrict__ gt, uint32_t n_gt, const float4 *__restrict__ pts,
+                                                         const uint32_t *__restrict__ idx, uint32_t n_est, const float4 *__restrict__ lo,
+                                                         const float4 *__restrict__ hi, uint32_t n_pad, double thr, uint32_t *__restrict__ lost,
+                                                         unsigned long long *__restrict__ ctr) {
+    __shared__ uint32_t stack[NN_STACK * NN_QBLOCK];
+    const uint32_t t = threadIdx.x, i = blockIdx.x * NN_QBLOCK + t;
+    uint32_t sta = 0, ls = 0, oor = 0, bad = 0;
+    if (i < n_gt) {
+        const float4 q = gt[i];
+        if (!ev_finite(q)) {
+            bad = 1;
+        } else if (!ev_is_dynamic(q.w, oor)) {
+            sta = 1;
+            const float d2 = n_est ? nn_search_f32(q.x, q.y, q.z, pts, idx, n_est, lo, hi, n_pad, stack, t).d2 : __builtin_huge_valf();
+            ls = (double)d2 > thr ? 1u : 0u;
+        }
+        lost[i] = ls;
+    }
+    ev_commit(ctr, FM_GT_STATIC, sta);
+    ev_commit(ctr, FM_LOST, ls);
+    ev_commit(ctr, FM_LABEL_OOR, oor);
+    ev_commit(ctr, FM_NON_FINITE, bad);
 }
 
 // one pass of the radix select: the values whose bits above `shift + 8` equal one of the prefixes, counted by prefix and by the 8-bit

@@ -173,6 +173,97 @@ static int analyze_mode(int argc, char **argv) {
     erasor_hip_destroy(h);
     return rc;
 }
+static void rows_to_cloud(const std::vector<float> &rows, size_t n, pcl::PointCloud<pcl::PointXYZI> &c) {
+    c.points.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        c.points[i].x = rows[4 * i];
+        c.points[i].y = rows[4 * i + 1];
+        c.points[i].z = rows[4 * i + 2];
+        c.points[i].intensity = rows[4 * i + 3];
+    }
+    c.width = (unsigned)n;
+    c.height = 1;
+}
+// --label <map> <dense_labelled> [leaf = 0.2]: fill_removert_intensity.cpp's main() (:61-111) on the device -- label_map
+// (erasor_hip_label_map) of a map without labels (another method's output, or one cleaned with intensity = 0) from the dense labelled
+// map, saved as <map minus its 4-character extension>_w_label.pcd in ASCII; prints "n_src - > n_out" as label_map does (:38)
+static int label_mode(int argc, char **argv) {
+    if (argc < 4) return 2;
+    const double leaf = argc > 4 ? atof(argv[4]) : 0.2;
+    std::vector<float> src, medium;
+    if (!load_cloud_xyzi(argv[2], src) || !load_cloud_xyzi(argv[3], medium)) {
+        fprintf(stderr, "cannot read %s or %s\n", argv[2], argv[3]);
+        return 3;
+    }
+    erasor_params p;
+    erasor_hip_params_default(&p);
+    erasor_hip_handle *h = nullptr;
+    if (erasor_hip_create(&p, 0, &h) != ERASOR_OK) {
+        fprintf(stderr, "erasor_hip_create failed\n");
+        return 1;
+    }
+    const size_t n_src = src.size() / 4;
+    std::vector<float> rows(std::max<size_t>(n_src, 1) * 4);
+    erasor_label_result r;
+    const int rc = erasor_hip_label_map(h, src.data(), n_src, 0, medium.data(), medium.size() / 4, 0, leaf, rows.data(), n_src, &r);
+    if (rc) {
+        fprintf(stderr, "label_map: %s (rc %d)\n", erasor_hip_last_error(h), rc);
+        erasor_hip_destroy(h);
+        return 1;
+    }
+    erasor_hip_destroy(h);
+    printf("%llu - > %llu\n", (unsigned long long)r.n_src, (unsigned long long)r.n_out);
+    if (r.n_tied || r.passthrough)
+        printf("(%llu point(s) with equidistant medium points of different labels%s)\n", (unsigned long long)r.n_tied,
+               r.passthrough ? "; voxel index overflow: the map was labelled as it is" : "");
+    pcl::PointCloud<pcl::PointXYZI> out;
+    rows_to_cloud(rows, r.n_out, out);
+    std::string name = argv[2];
+    name.erase(name.size() >= 4 ? name.size() - 4 : 0);  // (the reference drops the last four characters: ".pcd")
+    const std::string save_name = name + "_w_label.pcd";
+    if (erasor_utils::save_pcd_ascii(save_name, out) != 0) {
+        fprintf(stderr, "cannot write %s\n", save_name.c_str());
+        return 1;
+    }
+    printf("saved %s\n", save_name.c_str());
+    return 0;
+}
+// --complement <est> <gt> <out.pcd>: calc_complement (compare_complement.cpp:43-75) on the device -- the static ground-truth points
+// the estimate lost (erasor_hip_static_complement), saved as <out.pcd> in ASCII
+static int complement_mode(int argc, char **argv) {
+    if (argc < 5) return 2;
+    std::vector<float> est, gt;
+    if (!load_cloud_xyzi(argv[2], est) || !load_cloud_xyzi(argv[3], gt)) {
+        fprintf(stderr, "cannot read %s or %s\n", argv[2], argv[3]);
+        return 3;
+    }
+    erasor_params p;
+    erasor_hip_params_default(&p);
+    erasor_hip_handle *h = nullptr;
+    if (erasor_hip_create(&p, 0, &h) != ERASOR_OK) {
+        fprintf(stderr, "erasor_hip_create failed\n");
+        return 1;
+    }
+    const size_t n_gt = gt.size() / 4;
+    std::vector<float> rows(std::max<size_t>(n_gt, 1) * 4);
+    erasor_complement_result r;
+    const int rc = erasor_hip_static_complement(h, est.data(), est.size() / 4, 0, gt.data(), n_gt, 0, rows.data(), n_gt, &r);
+    if (rc) {
+        fprintf(stderr, "static_complement: %s (rc %d)\n", erasor_hip_last_error(h), rc);
+        erasor_hip_destroy(h);
+        return 1;
+    }
+    erasor_hip_destroy(h);
+    printf("%llu of %llu static ground-truth point(s) lost\n", (unsigned long long)r.n_lost, (unsigned long long)r.n_gt_static);
+    pcl::PointCloud<pcl::PointXYZI> out;
+    rows_to_cloud(rows, r.n_lost, out);
+    if (erasor_utils::save_pcd_ascii(argv[4], out) != 0) {
+        fprintf(stderr, "cannot write %s\n", argv[4]);
+        return 1;
+    }
+    printf("saved %s\n", argv[4]);
+    return 0;
+}
 // PR / RR of the map save_static_map(0.2) writes (voxelize_preserving_labels of map_arranged_) against a ground-truth file
 static int evaluate_saved_map(erasor::OfflineMapUpdater &updater, const std::string &gt_path) {
     std::vector<float> gt;
@@ -636,6 +727,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && (std::string(argv[1]) == "--label" || std::string(argv[1]) == "--complement")) {
+        try {
+            return std::string(argv[1]) == "--label" ? label_mode(argc, argv) : complement_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--mapgen") {
         try {
             return mapgen_mode(argc, argv);
@@ -655,8 +754,9 @@ int main(int argc, char **argv) {
     if (argc < 3) {
         fprintf(stderr,
                 "usage: %s <data_dir> <n_frames> [version] [removal_interval] [gt]\n       %s --config <rosparam.yaml> [n_frames] [gt]\n"
-                "       %s --eval <gt> <est> [voxelsize] [voxel_leaf]\n       %s --analyze <gt> <est> [voxelsize] [voxel_leaf]\n",
-                argv[0], argv[0], argv[0], argv[0]);
+                "       %s --eval <gt> <est> [voxelsize] [voxel_leaf]\n       %s --analyze <gt> <est> [voxelsize] [voxel_leaf]\n"
+                "       %s --label <map> <dense_labelled> [leaf]\n       %s --complement <est> <gt> <out.pcd>\n",
+                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

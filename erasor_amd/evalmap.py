@@ -8,6 +8,9 @@ Pinned against the reference implementation by tests/golden/eval_golden.npz (tes
 
 overlap / overlap_lines: the estimate-to-GT distance report printed before the PR / RR row (analysis_runner.py:53-71,
 overlap_report), pinned by tests/golden/overlap_golden.npz (tests/golden/make_overlap_golden.py).
+
+nearest_f32 / label_from / static_complement: the 1-NN of pcl::KdTreeFLANN (float32 d^2, lowest index on ties) behind the
+reference's label_map (src/utils/fill_removert_intensity.cpp:24-59) and calc_complement (src/utils/compare_complement.cpp:43-75).
 """
 import numpy as np
 from scipy.spatial import cKDTree
@@ -72,3 +75,97 @@ def overlap_lines(r, voxelsize=0.2):
     return [f"est->GT dist: median={r['median']:.4f}m  p90={r['p90']:.4f}m  p99={r['p99']:.4f}m  max={r['max']:.4f}m",
             f"  fraction <0.5*v ({half:.2f}m): {r['frac_half']:.2f}%  <1*v ({one:.2f}m): {r['frac_one']:.2f}%  "
             f"<2*v ({2*one:.2f}m): {r['frac_two']:.2f}%"]
+
+
+def _l2_simple(q, p):
+    """FLANN's L2_Simple in float32, operation by operation: r = 0; r += dx*dx; r += dy*dy; r += dz*dz with dx = q.x - p.x"""
+    r = np.zeros(len(q), np.float32)
+    for a in range(3):
+        d = q[:, a] - p[:, a]
+        r += d * d
+    return r
+
+
+def nearest_f32(tree_xyz, query_xyz, tree_key=None):
+    """Exact 1-NN in FLANN's float32 metric: (index, float32 d^2, tied) per query point.  The answer is the smallest tree index
+    among the points at the minimum float32 d^2; `tied` says that those points carry more than one value of tree_key (default:
+    the index itself, i.e. more than one point at the minimum).
+
+    cKDTree is exact only in float64, whose minimum can be a different point: two float64 distances a few ulps apart can round
+    to the same float32, or swap.  So cKDTree gives the float64 minimum d2_64 first, and query_ball_point then collects every
+    point with d^2 <= d2_64 * (1 + 1e-5) + 1e-30, a superset of the float32 minimum's points: float32 rounding moves a d^2 by
+    a relative 5 * 2^-24 (about 3e-7) at most, which the relative margin covers, except where products underflow to
+    subnormals or zero, where the error is absolute (below 2^-149 per operation), which the absolute margin covers.  Among those
+    candidates the float32 d^2 is computed as FLANN does and the minimum, then the lowest index, wins.  Queries with a single
+    candidate (nearly all) need no second look: that candidate is cKDTree's answer."""
+    t = np.ascontiguousarray(np.asarray(tree_xyz, np.float32).reshape(-1, 3))
+    q = np.ascontiguousarray(np.asarray(query_xyz, np.float32).reshape(-1, 3))
+    if len(t) == 0:
+        raise ValueError("nearest_f32: empty tree")
+    if len(q) == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.float32), np.zeros(0, bool)
+    q64 = q.astype(np.float64)
+    tree = cKDTree(t.astype(np.float64))
+    d64, idx = tree.query(q64, k=1, workers=-1)
+    idx = np.asarray(idx, np.int64)
+    r = np.sqrt(d64 * d64 * (1 + 1e-5) + 1e-30)
+    cnt = tree.query_ball_point(q64, r, workers=-1, return_length=True)
+    d2 = _l2_simple(q, t[idx])
+    tied = np.zeros(len(q), bool)
+    multi = np.nonzero(cnt > 1)[0]
+    if len(multi):
+        lists = tree.query_ball_point(q64[multi], r[multi], workers=-1)
+        lens = np.array([len(c) for c in lists], np.int64)
+        cand = np.concatenate([np.asarray(c, np.int64) for c in lists])
+        owner = np.repeat(np.arange(len(multi)), lens)
+        dd = _l2_simple(q[multi][owner], t[cand])
+        starts = np.concatenate([[0], np.cumsum(lens)[:-1]])
+        m = np.minimum.reduceat(dd, starts)
+        at = dd == m[owner]
+        # the lowest index at the minimum: sort the (owner, index) pairs at the minimum and take each owner's first
+        o_at, c_at = owner[at], cand[at]
+        order = np.lexsort((c_at, o_at))
+        o_at, c_at = o_at[order], c_at[order]
+        first = np.concatenate([[True], o_at[1:] != o_at[:-1]])
+        idx[multi] = c_at[first]
+        d2[multi] = m
+        key = c_at if tree_key is None else np.asarray(tree_key)[c_at]
+        k_first = np.repeat(key[first], np.diff(np.concatenate([np.nonzero(first)[0], [len(o_at)]])))
+        differs = np.zeros(len(multi), bool)
+        np.logical_or.at(differs, o_at, key != k_first)
+        tied[multi] = differs
+    return idx, d2, tied
+
+
+def label_from(centroids, medium):
+    """label_map's second half: each row of `centroids` (XYZI; its intensity is not read) takes the intensity of its nearest
+    `medium` point, copied as bits.  Returns (rows, {"n_tied": rows whose minimum is shared by medium points of different
+    intensity bits})."""
+    c = np.asarray(centroids, np.float32).reshape(-1, 4)
+    m = np.asarray(medium, np.float32).reshape(-1, 4)
+    out = c.copy()
+    if len(c) == 0:
+        return out, {"n_tied": 0}
+    wbits = np.ascontiguousarray(m[:, 3]).view(np.uint32)
+    idx, _, tied = nearest_f32(m[:, :3], c[:, :3], wbits)
+    out.view(np.uint32)[:, 3] = wbits[idx]
+    return out, {"n_tied": int(tied.sum())}
+
+
+def static_complement(est, gt):
+    """calc_complement: the static points of the labelled ground truth `gt` (XYZI) whose nearest point of `est` has a float32
+    d^2 that, widened to double, is > 0.03 (the reference compares the float with a double literal), in ground-truth order.
+    Labels as `labels`; intensities the cast is not defined for (not finite, outside [0, 2^32)) are static and counted.  An
+    empty estimate loses every static point.  Returns (rows, {"n_gt", "n_gt_static", "n_lost", "n_label_out_of_range"})."""
+    e = np.asarray(est, np.float32).reshape(-1, 4)
+    g = np.asarray(gt, np.float32).reshape(-1, 4)
+    w = g[:, 3]
+    oor = ~((w >= 0) & (w < 4294967296.0))
+    sem = np.where(oor, 0, w).astype(np.uint32) & 0xFFFF
+    static = oor | ~np.isin(sem, DYNAMIC_CLASSES)
+    d2 = np.full(len(g), np.inf, np.float32)
+    if len(e) and static.any():
+        _, d2[static], _ = nearest_f32(e[:, :3], g[static, :3])
+    lost = static & (d2.astype(np.float64) > 0.03)
+    return g[lost].copy(), {"n_gt": int(len(g)), "n_gt_static": int(static.sum()), "n_lost": int(lost.sum()),
+                            "n_label_out_of_range": int(oor.sum())}

@@ -307,6 +307,44 @@ int erasor_hip_overlap_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t 
 int erasor_hip_overlap_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device,
                            double voxel_leaf, double voxelsize, erasor_overlap_result *res);
 
+/* ---- maps without labels: label a third-party map from a dense labelled one, and the static points a method lost ----------------
+ * Both search the overlap report's tree in FLANN's metric, as pcl::KdTreeFLANN (K = 1) does: float32 d^2 = ((0 + dx*dx) + dy*dy) + dz*dz
+ * with dx = q.x - p.x in float, exact, the lowest index on ties.  Outputs are XYZI rows in caller HOST buffers; dst == NULL asks for
+ * the counts only.  n_out <= n_src and n_lost <= n_gt, so a buffer of that many rows always suffices; a smaller one that does not hold
+ * the result gives ERASOR_E_CAPACITY (res is filled first).  ERASOR_E_INVALID: a non-finite coordinate, more than 2^30 points.
+ * ERASOR_E_STATE: a step in flight. */
+typedef struct erasor_label_result {
+    uint64_t n_src;        /* points given */
+    uint64_t n_out;        /* rows written: the VoxelGrid centroids (n_src when passthrough) */
+    uint64_t n_tied;       /* rows whose nearest distance is shared by medium points of different intensity bits (the tie rule decided) */
+    uint32_t passthrough;  /* 1: VoxelGrid's voxel index overflowed and the input was labelled as it is, as PCL returns it */
+} erasor_label_result;
+
+/* replaces: label_map (src/utils/fill_removert_intensity.cpp:24-59; the same at src/utils/compare_map.cpp:77-110).  src is voxelised by
+ * pcl::VoxelGrid at `leaf` (voxelize_preserving_labels' grid and centroids); each centroid's row is its x, y, z and the intensity of its
+ * nearest `medium` point, copied as bits.  Like erasor_hip_evaluate_clouds with voxel_leaf > 0 it drops nodes announced ahead, and
+ * erasor_hip_get_cloud answers ERASOR_E_STATE until the next step.  Where the reference is undefined: an empty src gives an empty
+ * output; an empty medium with a non-empty src is ERASOR_E_INVALID; leaf must be finite and > 0. */
+int erasor_hip_label_map(erasor_hip_handle *h, const void *src_xyzi, size_t n_src, int src_is_device,
+                         const void *medium_xyzi, size_t n_medium, int medium_is_device,
+                         double leaf, float *dst_xyzi, size_t cap_points, erasor_label_result *res);
+
+typedef struct erasor_complement_result {
+    uint64_t n_gt;                  /* ground-truth points given */
+    uint64_t n_gt_static;           /* of them static: uint32(intensity) & 0xFFFF not in 252..259 */
+    uint64_t n_lost;                /* static points whose nearest estimated point has (double)d2 > 0.03 (rows written) */
+    uint64_t n_label_out_of_range;  /* intensities not finite or outside [0, 2^32): decoded as static */
+} erasor_complement_result;
+
+/* replaces: calc_complement (src/utils/compare_complement.cpp:43-75): the static ground-truth points whose nearest estimated point has a
+ * float squared distance greater than 0.03 (compared as double, as the reference's literal is), in ground-truth order -- what the
+ * method wrongly removed.  The intensity's instance bits (>> 16) are ignored.  An empty estimate (the reference would push nothing)
+ * gives every static point: the distance is +inf.  Works in the evaluator's own scratch: announcements and the last step's clouds stay
+ * as they are. */
+int erasor_hip_static_complement(erasor_hip_handle *h, const void *est_xyzi, size_t n_est, int est_is_device,
+                                 const void *gt_xyzi, size_t n_gt, int gt_is_device,
+                                 float *dst_xyzi, size_t cap_points, erasor_complement_result *res);
+
 /* ---- mapgen: the step BEFORE the hot path (src/mapgen/mapgen.hpp), device-resident accumulation ----
  * replaces: mapgen::setValue + constructor (mapgen.hpp:182-196): leafsize = /map/voxelsize, is_large_scale */
 int erasor_hip_mapgen_begin(erasor_hip_handle *h, double leafsize, int is_large_scale);
