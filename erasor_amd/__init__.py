@@ -83,6 +83,36 @@ class ComplementResult(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class ClassRow(C.Structure):
+    """erasor_eval_class_row (include/erasor_hip.h): one row of the breakdown by class or by dynamic instance"""
+    _fields_ = [("key", C.c_uint32), ("is_dynamic", C.c_uint32)] + [(k, C.c_uint64) for k in (
+        "n_gt", "n_within", "n_preserved", "n_tied", "n_est")]
+
+
+# the rows as numpy records (ClassRow's layout); Erasor.evaluate_by_class adds PR / RR per row (CLASS_ROW_DTYPE_PR)
+CLASS_ROW_DTYPE = np.dtype([(k, np.uint32 if t is C.c_uint32 else np.uint64) for k, t in ClassRow._fields_])
+CLASS_ROW_DTYPE_PR = np.dtype(CLASS_ROW_DTYPE.descr + [("PR", np.float64), ("RR", np.float64)])
+EVAL_KEY_LABEL_OUT_OF_RANGE = 0x10000
+N_CLASS_KEYS = 0x10001  # (every class key: a class array of this many rows always fits)
+
+
+def class_rows_with_rates(rows):
+    """rows (CLASS_ROW_DTYPE) plus evalmap.evaluate's rates per row: PR = n_preserved / n_gt * 100 on static rows, RR = (n_gt -
+    n_preserved) / n_gt * 100 on dynamic rows; 0 without ground truth, NaN in the column that does not apply"""
+    out = np.zeros(len(rows), CLASS_ROW_DTYPE_PR)
+    for k in CLASS_ROW_DTYPE.names:
+        out[k] = rows[k]
+    n = rows["n_gt"].astype(np.float64)
+    kept = rows["n_preserved"].astype(np.float64)
+    dyn = rows["is_dynamic"] != 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        pr = np.where(n > 0, kept / n * 100.0, 0.0)
+        rr = np.where(n > 0, (n - kept) / n * 100.0, 0.0)
+    out["PR"] = np.where(dyn, np.nan, pr)
+    out["RR"] = np.where(dyn, rr, np.nan)
+    return out
+
+
 # per-ground-truth-point codes of Erasor.evaluate(per_point=True)
 EVAL_OUT, EVAL_KEPT_STATIC, EVAL_KEPT_DYNAMIC, EVAL_CLASS_DIFFERS = 0, 1, 2, 3
 
@@ -90,6 +120,7 @@ CLOUD_QUERY_VOI, CLOUD_MAP_VOI, CLOUD_STATIC_ESTIMATE, CLOUD_COMPLEMENT = 0, 1, 
 CLOUD_MAP_REJECTED, CLOUD_CURR_REJECTED, CLOUD_GROUND_VIZ, CLOUD_MAP = 4, 5, 6, 7
 
 E_NO_DEVICE = -2
+E_CAPACITY = -3
 
 
 class ErasorError(RuntimeError):
@@ -434,6 +465,40 @@ class Erasor:
         r = EvalResult()
         self._check(lib().erasor_hip_evaluate_map(self._h, *g, C.c_double(voxel_leaf), C.c_double(voxelsize), C.byref(r)))
         return r.as_dict()
+
+    # -- PR / RR by class and by dynamic instance (the same on the host: evalmap.evaluate_by_class) --
+    def _by_class(self, fn, args, voxel_leaf, voxelsize):
+        classes = np.zeros(N_CLASS_KEYS, CLASS_ROW_DTYPE)
+        instances = np.zeros(4096, CLASS_ROW_DTYPE)
+        nc, ni = C.c_size_t(0), C.c_size_t(0)
+        r = EvalResult()
+        for attempt in range(2):  # (a second call only when the instances did not fit: then with their exact count)
+            rc = fn(self._h, *args, C.c_double(voxel_leaf), C.c_double(voxelsize), _p(classes), C.c_size_t(len(classes)), C.byref(nc),
+                    _p(instances), C.c_size_t(len(instances)), C.byref(ni), C.byref(r))
+            if rc != E_CAPACITY or attempt:
+                break
+            instances = np.zeros(max(ni.value, 1), CLASS_ROW_DTYPE)
+        self._check(rc)
+        out = r.as_dict()
+        out["classes"] = class_rows_with_rates(classes[: nc.value])
+        out["instances"] = class_rows_with_rates(instances[: ni.value])
+        return out
+
+    def evaluate_by_class(self, gt, est, voxelsize=0.2, voxel_leaf=0.0):
+        """evaluate's dict plus its breakdown (erasor_hip_evaluate_clouds_by_class): "classes", one row per class key present in either
+        cloud, and "instances", one row per whole dynamic label; numpy records with ClassRow's fields plus PR (static rows) / RR
+        (dynamic rows).  Clouds and voxel_leaf as for evaluate."""
+        kept = []
+        g = self._eval_cloud(gt, kept)
+        e = self._eval_cloud(est, kept)
+        return self._by_class(lib().erasor_hip_evaluate_clouds_by_class, (*g, *e), voxel_leaf, voxelsize)
+
+    def evaluate_map_by_class(self, gt, voxelsize=0.2, voxel_leaf=0.0):
+        """evaluate_by_class of the handle's current map (the get_map view, never copied to the host) against `gt`
+        (erasor_hip_evaluate_map_by_class)"""
+        kept = []
+        g = self._eval_cloud(gt, kept)
+        return self._by_class(lib().erasor_hip_evaluate_map_by_class, g, voxel_leaf, voxelsize)
 
     # -- the estimate-to-ground-truth overlap report (scripts/analysis_runner.py:53-71; the same on the host: evalmap.overlap) --
     def overlap(self, gt, est, voxelsize=0.2, voxel_leaf=0.0, per_point=False):

@@ -246,7 +246,8 @@ struct erasor_hip_handle {
         bool deep = false;        // the caller had announced at least batch_lead nodes beyond this step (OvAuto samples only such steps)
     } fly;
     HostOut *pin = nullptr;         // pinned host block k_step_end reports into
-    int bank = 0;                   // scratch bank of scan/radix helpers (0: query chains, 1: map chain, 2: the overlap report's tree)
+    int bank = 0;                   // scratch bank of scan/radix helpers (0: query chains, 1: map chain, 2: the evaluators: the overlap
+                                    // report's tree, the instance rows of the breakdown by class)
     std::string err;
     bool have_map = false, have_step = false;
     bool poisoned = false;        // a step failed after the map store had been touched: only set_map makes the handle usable again
@@ -312,6 +313,9 @@ struct erasor_hip_handle {
         DBuf<float4> fm_out;
         DBuf<uint32_t> fm_flag, fm_pl, fm_tops;
         DBuf<unsigned long long> fm_ctr;
+        // the breakdown by class and instance (erasor_hip_evaluate_*_by_class): the per-key table, the dynamic points' (label, counter
+        // bits) records and their cursor, the flags / run heads with their scan, the class and instance rows (the records' sort: nn_k*, nn_v*)
+        DBuf<uint32_t> bc_tab, bc_cur, bc_ikey, bc_ival, bc_flag, bc_pl, bc_tops, bc_crows, bc_irows;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
     // ---- per-bin scratch (R-GPF / bin voxelise global paths) ----
@@ -3359,14 +3363,19 @@ static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t n
 
 // ---- PR / RR of a cleaned map against a labelled ground-truth map (scripts/analysis_runner.py:74-105; kernels: evaluate.hip.h) ----
 // Everything runs on the main stream, behind whatever a collected step launched ahead there, in the handle's own scratch (h->ev).
+// n_rec (the breakdown by class): the kernels also fill the per-key table E.bc_tab and the dynamic points' records; *n_rec = their count.
 static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize, uint8_t *per_gt,
-                  erasor_eval_result *res) {
+                  erasor_eval_result *res, uint32_t *n_rec = nullptr) {
     auto &E = h->ev;
     uint32_t nb = 1024;  // buckets: a power of two >= the estimate's size (<= 1 point per bucket on average)
     while (nb < n_est) nb <<= 1;
     if (ensure(h, E.ctr, EV_NCTR) || ensure(h, E.cnt, (size_t)nb + 1) || ensure(h, E.pl, (size_t)nb + 1) || ensure(h, E.tops, nb / 1024 + 4) ||
         ensure(h, E.bkt, (size_t)n_est + 1) || ensure(h, E.pts, (size_t)n_est + 1) || ensure(h, E.idx, (size_t)n_est + 1) ||
         (per_gt && ensure(h, E.code, (size_t)n_gt + 1)))
+        return ERASOR_E_NO_DEVICE;
+    const size_t n_all = (size_t)n_gt + n_est;  // (< 2^31: each cloud has at most 2^30 points)
+    if (n_rec && (ensure(h, E.bc_tab, (size_t)EV_NKEYS * EV_KC) || ensure(h, E.bc_cur, 4) || ensure(h, E.bc_ikey, n_all + 1) ||
+                  ensure(h, E.bc_ival, n_all + 1)))
         return ERASOR_E_NO_DEVICE;
     struct KeepCur {
         erasor_hip_handle *h;
@@ -3375,19 +3384,31 @@ static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const f
     } kc{h, h->cur};
     h->cur = h->stream;
     HIPC(h, hipMemsetAsync(E.ctr.p, 0, EV_NCTR * sizeof(unsigned long long), h->stream));
+    if (n_rec) {
+        HIPC(h, hipMemsetAsync(E.bc_tab.p, 0, (size_t)EV_NKEYS * EV_KC * sizeof(uint32_t), h->stream));
+        HIPC(h, hipMemsetAsync(E.bc_cur.p, 0, sizeof(uint32_t), h->stream));
+    }
     const double thr = (voxelsize * sqrt(3.0)) / 2.0;  // evalmap / analysis_runner.py: voxelsize * np.sqrt(3) / 2
     if (n_est) {
         HIPC(h, hipMemsetAsync(E.cnt.p, 0, ((size_t)nb + 1) * sizeof(uint32_t), h->stream));
-        LAUNCH(h, "ev_index", k_ev_hist, cdiv(n_est, 256), 256, est, n_est, voxelsize, nb - 1, E.bkt.p, E.cnt.p, E.ctr.p);
+        if (n_rec)
+            LAUNCH(h, "ev_index", k_ev_hist_keys, cdiv(n_est, 256), 256, est, n_est, voxelsize, nb - 1, E.bkt.p, E.cnt.p, E.ctr.p, E.bc_tab.p, E.bc_cur.p,
+                   E.bc_ikey.p, E.bc_ival.p);
+        else
+            LAUNCH(h, "ev_index", k_ev_hist, cdiv(n_est, 256), 256, est, n_est, voxelsize, nb - 1, E.bkt.p, E.cnt.p, E.ctr.p);
         scan_u32(h, E.cnt.p, E.pl.p, E.tops.p, nb + 1, nb + 1, nullptr, nullptr, "ev_index");
         LAUNCH(h, "ev_index", k_ev_offsets, cdiv(nb + 1, 256), 256, (const uint32_t *)E.pl.p, (const uint32_t *)E.tops.p, nb + 1, E.cnt.p, E.pl.p);
         LAUNCH(h, "ev_index", k_ev_scatter, cdiv(n_est, 256), 256, est, n_est, (const uint32_t *)E.bkt.p, E.pl.p, E.pts.p, E.idx.p);
     }
-    if (n_gt)
+    if (n_gt && n_rec)
+        LAUNCH(h, "ev_query", k_ev_query_keys, cdiv(n_gt, 256), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p,
+               (const uint32_t *)E.cnt.p, nb - 1, n_est, voxelsize, thr, E.ctr.p, E.bc_tab.p, E.bc_cur.p, E.bc_ikey.p, E.bc_ival.p);
+    else if (n_gt)
         LAUNCH(h, "ev_query", k_ev_query, cdiv(n_gt, 256), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p, (const uint32_t *)E.cnt.p,
                nb - 1, n_est, voxelsize, thr, per_gt ? E.code.p : (uint8_t *)nullptr, E.ctr.p);
     unsigned long long c[EV_NCTR];
     HIPC(h, hipMemcpyAsync(c, E.ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    if (n_rec) HIPC(h, hipMemcpyAsync(n_rec, E.bc_cur.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
     if (c[EV_NON_FINITE]) {
         h->err = "erasor_hip_evaluate: non-finite coordinate (NaN / Inf) in " + std::to_string(c[EV_NON_FINITE]) + " point(s)";
@@ -3914,6 +3935,141 @@ int erasor_hip_static_complement(erasor_hip_handle *h, const void *est_xyzi, siz
     if (!dst_xyzi) return ERASOR_OK;
     if (r.n_lost > cap_points) return ERASOR_E_CAPACITY;
     return d2h(h, dst_xyzi, E.fm_out.p, (size_t)r.n_lost * sizeof(float4));
+}
+
+// ---- PR / RR by class and by dynamic instance (kernels: evaluate.hip.h, k_ev_*_keys onwards) ----
+// ev_run in its by-key mode, then the rows on the main stream in the evaluator's scratch: the class rows by a flag per non-empty key, its
+// exclusive scan and a scatter (key order, no sort); the instance rows by a radix sort of the dynamic points' records by label (histogram
+// bank 2, like the overlap report's tree: the query chains of nodes announced ahead keep bank 0), run heads, their scan, and one atomic
+// per row and counter of a wavefront.
+static void bc_fill(const std::vector<uint32_t> &rows, size_t n, bool instances, erasor_eval_class_row *out) {
+    for (size_t r = 0; r < n; ++r) {
+        const uint32_t *v = &rows[r * EV_ROW];
+        erasor_eval_class_row &o = out[r];
+        o.key = v[0];
+        const uint32_t sem = v[0] & 0xFFFFu;
+        o.is_dynamic = (instances || (v[0] < EV_KEY_OOR && sem >= 252u && sem <= 259u)) ? 1u : 0u;
+        o.n_gt = v[1 + EV_K_GT];
+        o.n_within = v[1 + EV_K_WITHIN];
+        o.n_preserved = v[1 + EV_K_KEPT];
+        o.n_tied = v[1 + EV_K_TIED];
+        o.n_est = v[1 + EV_K_EST];
+    }
+}
+
+static int bc_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize,
+                  erasor_eval_class_row *classes, size_t cap_classes, size_t *n_classes, erasor_eval_class_row *instances, size_t cap_instances,
+                  size_t *n_instances, erasor_eval_result *res) {
+    uint32_t n_rec = 0;
+    int rc = ev_run(h, gt, n_gt, est, n_est, voxelsize, nullptr, res, &n_rec);
+    if (rc) return rc;
+    auto &E = h->ev;
+    NnScope scope(h);
+    const size_t n_scan = std::max<size_t>(EV_NKEYS, n_rec) + 1;
+    if (ensure(h, E.bc_flag, n_scan) || ensure(h, E.bc_pl, n_scan) || ensure(h, E.bc_tops, n_scan / 1024 + 4) ||
+        ensure(h, E.bc_crows, (size_t)EV_NKEYS * EV_ROW))
+        return ERASOR_E_NO_DEVICE;
+    LAUNCH(h, "ev_rows", k_ev_class_flags, cdiv(EV_NKEYS, 256), 256, (const uint32_t *)E.bc_tab.p, E.bc_flag.p);
+    scan_u32(h, E.bc_flag.p, E.bc_pl.p, E.bc_tops.p, EV_NKEYS, EV_NKEYS, nullptr, E.bc_cur.p + 1, "ev_rows");
+    LAUNCH(h, "ev_rows", k_ev_class_rows, cdiv(EV_NKEYS, 256), 256, (const uint32_t *)E.bc_tab.p, (const uint32_t *)E.bc_flag.p,
+           (const uint32_t *)E.bc_pl.p, (const uint32_t *)E.bc_tops.p, E.bc_crows.p);
+    uint32_t n_cls = 0;
+    HIPC(h, hipMemcpyAsync(&n_cls, E.bc_cur.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    uint32_t n_inst = 0;
+    if (n_rec) {
+        const size_t n1 = (size_t)n_rec + 1;
+        if (ensure(h, E.nn_ka, n1) || ensure(h, E.nn_kb, n1) || ensure(h, E.nn_va, n1) || ensure(h, E.nn_vb, n1) || ensure(h, E.bc_irows, n1 * EV_ROW))
+            return ERASOR_E_NO_DEVICE;
+        const uint32_t *skeys = nullptr, *sperm = nullptr;
+        if (radix_sort(h, E.bc_ikey.p, n_rec, nullptr, 32, E.nn_ka.p, E.nn_kb.p, E.nn_va.p, E.nn_vb.p, &skeys, &sperm, "ev_rows"))
+            return ERASOR_E_NO_DEVICE;
+        LAUNCH(h, "ev_rows", k_ev_run_heads, cdiv(n_rec, 256), 256, skeys, n_rec, E.bc_flag.p);
+        scan_u32(h, E.bc_flag.p, E.bc_pl.p, E.bc_tops.p, n_rec, n_rec, nullptr, E.bc_cur.p + 2, "ev_rows");
+        HIPC(h, hipMemsetAsync(E.bc_irows.p, 0, (size_t)n_rec * EV_ROW * sizeof(uint32_t), h->stream));
+        LAUNCH(h, "ev_rows", k_ev_inst_rows, cdiv(n_rec, 256), 256, skeys, sperm, (const uint32_t *)E.bc_ival.p, (const uint32_t *)E.bc_flag.p,
+               (const uint32_t *)E.bc_pl.p, (const uint32_t *)E.bc_tops.p, n_rec, E.bc_irows.p);
+        HIPC(h, hipMemcpyAsync(&n_inst, E.bc_cur.p + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPC(h, hipStreamSynchronize(h->stream));
+    *n_classes = n_cls;
+    *n_instances = n_inst;
+    if (n_cls > cap_classes || n_inst > cap_instances) return ERASOR_E_CAPACITY;  // (the counts and res are written: size and call again)
+    std::vector<uint32_t> rows((size_t)std::max(n_cls, n_inst) * EV_ROW);
+    if ((rc = d2h(h, rows.data(), E.bc_crows.p, (size_t)n_cls * EV_ROW * sizeof(uint32_t)))) return rc;
+    bc_fill(rows, n_cls, false, classes);
+    if ((rc = d2h(h, rows.data(), E.bc_irows.p, (size_t)n_inst * EV_ROW * sizeof(uint32_t)))) return rc;
+    bc_fill(rows, n_inst, true, instances);
+    return ERASOR_OK;
+}
+
+static int bc_check_rows(erasor_hip_handle *h, const erasor_eval_class_row *classes, size_t cap_classes, size_t *n_classes,
+                         const erasor_eval_class_row *instances, size_t cap_instances, size_t *n_instances) {
+    if (!n_classes || !n_instances || (!classes && cap_classes) || (!instances && cap_instances)) {
+        h->err = "erasor_hip_evaluate_by_class: NULL row count, or a NULL row array with a capacity > 0";
+        return ERASOR_E_INVALID;
+    }
+    *n_classes = 0;
+    *n_instances = 0;
+    return ERASOR_OK;
+}
+
+int erasor_hip_evaluate_clouds_by_class(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, const void *est_xyzi,
+                                        size_t n_est, int est_is_device, double voxel_leaf, double voxelsize, erasor_eval_class_row *classes,
+                                        size_t cap_classes, size_t *n_classes, erasor_eval_class_row *instances, size_t cap_instances,
+                                        size_t *n_instances, erasor_eval_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, false, res);
+    if (rc || (rc = bc_check_rows(h, classes, cap_classes, n_classes, instances, cap_instances, n_instances))) return rc;
+    if ((!gt_xyzi && n_gt) || (!est_xyzi && n_est) || n_gt > 0x3FFFFFFFull || n_est > 0x3FFFFFFFull) {
+        h->err = "erasor_hip_evaluate_clouds_by_class: NULL cloud or more than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *g = nullptr, *e = nullptr;
+    if ((rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, h->ev.gt, &g)) || (rc = ev_input(h, est_xyzi, n_est, est_is_device, h->ev.est, &e))) return rc;
+    uint32_t ng = (uint32_t)n_gt, ne = (uint32_t)n_est;
+    if (voxel_leaf > 0) {
+        if ((rc = ev_voxelize(h, g, ng, voxel_leaf, h->ev.gt, &ng))) return rc;
+        if ((rc = ev_voxelize(h, e, ne, voxel_leaf, h->ev.est, &ne))) return rc;
+        g = h->ev.gt.p;
+        e = h->ev.est.p;
+    }
+    return bc_run(h, g, ng, e, ne, voxelsize, classes, cap_classes, n_classes, instances, cap_instances, n_instances, res);
+}
+
+int erasor_hip_evaluate_map_by_class(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, double voxel_leaf, double voxelsize,
+                                     erasor_eval_class_row *classes, size_t cap_classes, size_t *n_classes, erasor_eval_class_row *instances,
+                                     size_t cap_instances, size_t *n_instances, erasor_eval_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, false, res);
+    if (rc || (rc = bc_check_rows(h, classes, cap_classes, n_classes, instances, cap_instances, n_instances))) return rc;
+    if (!h->have_map) {
+        h->err = "erasor_hip_evaluate_map_by_class: the handle has no map (erasor_hip_set_map first)";
+        return ERASOR_E_STATE;
+    }
+    if ((!gt_xyzi && n_gt) || n_gt > 0x3FFFFFFFull) {
+        h->err = "erasor_hip_evaluate_map_by_class: NULL cloud or more than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    HIPC(h, hipSetDevice(h->device));
+    size_t n_map = 0;
+    if ((rc = map_to_device(h, h->ev.map, &n_map))) return rc;
+    if (n_map > 0x3FFFFFFFull) {
+        h->err = "erasor_hip_evaluate_map_by_class: map larger than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    const float4 *g = nullptr, *e = h->ev.map.p;
+    if ((rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, h->ev.gt, &g))) return rc;
+    uint32_t ng = (uint32_t)n_gt, ne = (uint32_t)n_map;
+    if (voxel_leaf > 0) {
+        if ((rc = ev_voxelize(h, g, ng, voxel_leaf, h->ev.gt, &ng))) return rc;
+        if ((rc = ev_voxelize(h, e, ne, voxel_leaf, h->ev.est, &ne))) return rc;
+        g = h->ev.gt.p;
+        e = h->ev.est.p;
+    }
+    return bc_run(h, g, ng, e, ne, voxelsize, classes, cap_classes, n_classes, instances, cap_instances, n_instances, res);
 }
 
 // the last step's [selected bins theta-major | ground_viz | complement] WITHOUT tf_body2origin_ (the egocentric clouds

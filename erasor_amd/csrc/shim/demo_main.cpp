@@ -139,6 +139,85 @@ static int eval_mode(int argc, char **argv) {
     erasor_hip_destroy(h);
     return rc;
 }
+// the public SemanticKITTI label names (semantic-kitti.yaml) of a class key
+static const char *semantic_kitti_name(uint32_t key) {
+    switch (key) {
+        case 0: return "unlabeled";        case 1: return "outlier";            case 10: return "car";
+        case 11: return "bicycle";         case 13: return "bus";               case 15: return "motorcycle";
+        case 16: return "on-rails";        case 18: return "truck";             case 20: return "other-vehicle";
+        case 30: return "person";          case 31: return "bicyclist";         case 32: return "motorcyclist";
+        case 40: return "road";            case 44: return "parking";           case 48: return "sidewalk";
+        case 49: return "other-ground";    case 50: return "building";          case 51: return "fence";
+        case 52: return "other-structure"; case 60: return "lane-marking";      case 70: return "vegetation";
+        case 71: return "trunk";           case 72: return "terrain";           case 80: return "pole";
+        case 81: return "traffic-sign";    case 99: return "other-object";      case 252: return "moving-car";
+        case 253: return "moving-bicyclist"; case 254: return "moving-person";  case 255: return "moving-motorcyclist";
+        case 256: return "moving-on-rails";  case 257: return "moving-bus";     case 258: return "moving-truck";
+        case 259: return "moving-other-vehicle";
+        case ERASOR_EVAL_KEY_LABEL_OUT_OF_RANGE: return "(label out of range)";
+        default: return "-";
+    }
+}
+// --eval-classes <gt> <est> [voxelsize = 0.2] [voxel_leaf = 0]: --eval's output, then PR / RR per class and a summary of the dynamic
+// instances of the ground truth (erasor_hip_evaluate_clouds_by_class)
+static int eval_classes_mode(int argc, char **argv) {
+    if (argc < 4) return 2;
+    const double voxelsize = argc > 4 ? atof(argv[4]) : 0.2, voxel_leaf = argc > 5 ? atof(argv[5]) : 0.0;
+    std::vector<float> gt, est;
+    if (!load_cloud_xyzi(argv[2], gt) || !load_cloud_xyzi(argv[3], est)) {
+        fprintf(stderr, "cannot read %s or %s\n", argv[2], argv[3]);
+        return 3;
+    }
+    printf("GT : %s\nEst: %s\n", argv[2], argv[3]);
+    erasor_params p;
+    erasor_hip_params_default(&p);
+    erasor_hip_handle *h = nullptr;
+    if (erasor_hip_create(&p, 0, &h) != ERASOR_OK) {
+        fprintf(stderr, "erasor_hip_create failed\n");
+        return 1;
+    }
+    std::vector<erasor_eval_class_row> cls(ERASOR_EVAL_KEY_LABEL_OUT_OF_RANGE + 1), inst(4096);
+    size_t nc = 0, ni = 0;
+    erasor_eval_result r;
+    int rc = ERASOR_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {  // (again with the instances' exact count when they did not fit)
+        rc = erasor_hip_evaluate_clouds_by_class(h, gt.data(), gt.size() / 4, 0, est.data(), est.size() / 4, 0, voxel_leaf, voxelsize, cls.data(),
+                                                 cls.size(), &nc, inst.data(), inst.size(), &ni, &r);
+        if (rc != ERASOR_E_CAPACITY) break;
+        inst.resize(std::max<size_t>(ni, 1));
+    }
+    if (rc) {
+        fprintf(stderr, "evaluate: %s (rc %d)\n", erasor_hip_last_error(h), rc);
+        erasor_hip_destroy(h);
+        return 1;
+    }
+    print_eval_row(r);
+    printf("\nper class:\n");
+    printf("|    key | name                 |       gt |     kept |   PR%%/RR%% |      est |\n");
+    printf("|--------+----------------------+----------+----------+-----------+----------|\n");
+    for (size_t k = 0; k < nc; ++k) {
+        const erasor_eval_class_row &c = cls[k];
+        const double n = (double)c.n_gt, kept = (double)c.n_preserved;
+        const double rate = c.n_gt ? (c.is_dynamic ? (n - kept) / n * 100.0 : kept / n * 100.0) : 0.0;
+        printf("| %6u | %-20s | %8llu | %8llu | %s %7.3f | %8llu |\n", c.key, semantic_kitti_name(c.key), (unsigned long long)c.n_gt,
+               (unsigned long long)c.n_preserved, c.is_dynamic ? "RR" : "PR", rate, (unsigned long long)c.n_est);
+    }
+    size_t in_gt = 0, all = 0, ge90 = 0, ge50 = 0, none = 0;
+    for (size_t k = 0; k < ni; ++k) {
+        const erasor_eval_class_row &c = inst[k];
+        if (!c.n_gt) continue;
+        ++in_gt;
+        const uint64_t removed = c.n_gt - c.n_preserved;
+        all += removed == c.n_gt;
+        ge90 += removed * 10 >= c.n_gt * 9;
+        ge50 += removed * 2 >= c.n_gt;
+        none += removed == 0;
+    }
+    printf("\ndynamic instances in the ground truth: %zu; fully removed %zu, >= 90%% removed %zu, >= 50%% removed %zu, not removed %zu\n", in_gt, all,
+           ge90, ge50, none);
+    erasor_hip_destroy(h);
+    return 0;
+}
 // --analyze <gt> <est> [voxelsize = 0.2] [voxel_leaf = 0]: analysis_runner.py's main() on the device -- the two files, the overlap
 // report (analysis_runner.py:53-71, erasor_hip_overlap_clouds; printf's %.4f / %.2f round the binary value exactly, as Python's format
 // does) and the PR / RR row
@@ -719,6 +798,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && std::string(argv[1]) == "--eval-classes") {
+        try {
+            return eval_classes_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--analyze") {
         try {
             return analyze_mode(argc, argv);
@@ -754,9 +841,10 @@ int main(int argc, char **argv) {
     if (argc < 3) {
         fprintf(stderr,
                 "usage: %s <data_dir> <n_frames> [version] [removal_interval] [gt]\n       %s --config <rosparam.yaml> [n_frames] [gt]\n"
-                "       %s --eval <gt> <est> [voxelsize] [voxel_leaf]\n       %s --analyze <gt> <est> [voxelsize] [voxel_leaf]\n"
+                "       %s --eval <gt> <est> [voxelsize] [voxel_leaf]\n       %s --eval-classes <gt> <est> [voxelsize] [voxel_leaf]\n"
+                "       %s --analyze <gt> <est> [voxelsize] [voxel_leaf]\n"
                 "       %s --label <map> <dense_labelled> [leaf]\n       %s --complement <est> <gt> <out.pcd>\n",
-                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

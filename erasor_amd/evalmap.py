@@ -11,6 +11,8 @@ overlap_report), pinned by tests/golden/overlap_golden.npz (tests/golden/make_ov
 
 nearest_f32 / label_from / static_complement: the 1-NN of pcl::KdTreeFLANN (float32 d^2, lowest index on ties) behind the
 reference's label_map (src/utils/fill_removert_intensity.cpp:24-59) and calc_complement (src/utils/compare_complement.cpp:43-75).
+
+evaluate_by_class: the same decision per GT point, counted per semantic class and per dynamic instance (Erasor.evaluate_by_class).
 """
 import numpy as np
 from scipy.spatial import cKDTree
@@ -169,3 +171,104 @@ def static_complement(est, gt):
     lost = static & (d2.astype(np.float64) > 0.03)
     return g[lost].copy(), {"n_gt": int(len(g)), "n_gt_static": int(static.sum()), "n_lost": int(lost.sum()),
                             "n_label_out_of_range": int(oor.sum())}
+
+
+# the public SemanticKITTI label names (semantic-kitti.yaml), for printing
+SEMANTIC_KITTI_NAMES = {
+    0: "unlabeled", 1: "outlier", 10: "car", 11: "bicycle", 13: "bus", 15: "motorcycle", 16: "on-rails", 18: "truck",
+    20: "other-vehicle", 30: "person", 31: "bicyclist", 32: "motorcyclist", 40: "road", 44: "parking", 48: "sidewalk",
+    49: "other-ground", 50: "building", 51: "fence", 52: "other-structure", 60: "lane-marking", 70: "vegetation", 71: "trunk",
+    72: "terrain", 80: "pole", 81: "traffic-sign", 99: "other-object", 252: "moving-car", 253: "moving-bicyclist",
+    254: "moving-person", 255: "moving-motorcyclist", 256: "moving-on-rails", 257: "moving-bus", 258: "moving-truck",
+    259: "moving-other-vehicle",
+}
+KEY_LABEL_OUT_OF_RANGE = 0x10000
+ROW_FIELDS = ("key", "is_dynamic", "n_gt", "n_within", "n_preserved", "n_tied", "n_est", "PR", "RR")
+
+
+def _decode(w):
+    """(class key, whole label, is_dynamic) per intensity: uint32(w) & 0xFFFF, or KEY_LABEL_OUT_OF_RANGE (static) where the cast is not
+    defined (not finite, outside [0, 2^32))"""
+    w = np.asarray(w, np.float32)
+    inr = (w >= 0) & (w < np.float32(4294967296.0))
+    lab = np.where(inr, w, np.float32(0)).astype(np.uint32)
+    sem = lab & 0xFFFF
+    key = np.where(inr, sem, KEY_LABEL_OUT_OF_RANGE).astype(np.int64)
+    return key, lab, inr & (sem >= 252) & (sem <= 259)
+
+
+def _rows(keys, is_dyn, cnt):
+    """records of the rows: cnt[name] are arrays aligned with keys; PR / RR as evaluate forms them, per row"""
+    dt = np.dtype([("key", np.uint32), ("is_dynamic", np.uint32)] + [(k, np.uint64) for k in ROW_FIELDS[2:7]] +
+                  [("PR", np.float64), ("RR", np.float64)])
+    out = np.zeros(len(keys), dt)
+    out["key"] = keys
+    out["is_dynamic"] = is_dyn
+    for k in ROW_FIELDS[2:7]:
+        out[k] = cnt[k]
+    n, kept = out["n_gt"].astype(np.float64), out["n_preserved"].astype(np.float64)
+    has = n > 0
+    pr, rr = np.zeros(len(out)), np.zeros(len(out))
+    pr[has] = kept[has] / n[has] * 100.0
+    rr[has] = (n[has] - kept[has]) / n[has] * 100.0
+    dyn = out["is_dynamic"] != 0
+    out["PR"] = np.where(dyn, np.nan, pr)
+    out["RR"] = np.where(dyn, rr, np.nan)
+    return out
+
+
+def evaluate_by_class(gt_xyzi, est_xyzi, voxelsize=0.2):
+    """PR / RR broken down by class key and by dynamic instance (include/erasor_hip.h, erasor_eval_class_row), on the host.  The decision
+    per GT point is evaluate's: the nearest estimated point (cKDTree), within voxelsize*sqrt(3)/2, kept when both are static or both
+    dynamic; among estimated points at exactly the same float64 d^2 the smallest index answers, and a GT point whose minimum is shared
+    by points of both classes is counted as tied.  Returns evaluate's counts, n_tied, and "classes" / "instances" (records with
+    ROW_FIELDS)."""
+    gt = np.asarray(gt_xyzi, np.float32).reshape(-1, 4)
+    est = np.asarray(est_xyzi, np.float32).reshape(-1, 4)
+    g_key, g_lab, g_dyn = _decode(gt[:, 3])
+    e_key, e_lab, e_dyn = _decode(est[:, 3])
+    thr = voxelsize * np.sqrt(3) / 2
+    within = np.zeros(len(gt), bool)
+    kept = np.zeros(len(gt), bool)
+    tied = np.zeros(len(gt), bool)
+    if len(gt) and len(est):
+        e64 = est[:, :3].astype(np.float64)
+        g64 = gt[:, :3].astype(np.float64)
+        tree = cKDTree(e64)
+        k = 2 if len(est) > 1 else 1
+        d, idx = tree.query(g64, k=k, workers=-1)
+        d, idx = d.reshape(len(gt), k), idx.reshape(len(gt), k)
+        within = d[:, 0] < thr
+        best = idx[:, 0].copy()
+        # a second point as near (to 1e-9): every candidate at the exact minimum of ((dx*dx + dy*dy) + dz*dz)
+        maybe = np.nonzero(within & (d[:, -1] <= d[:, 0] * (1 + 1e-9)))[0] if k == 2 else np.zeros(0, np.int64)
+        for i in maybe:
+            cand = np.asarray(sorted(tree.query_ball_point(g64[i], d[i, 0] * (1 + 1e-9) + 1e-300)), np.int64)
+            dd = g64[i] - e64[cand]
+            d2 = (dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2]
+            at = cand[d2 == d2.min()]
+            best[i] = at[0]
+            tied[i] = e_dyn[at].any() and (~e_dyn[at]).any()
+        kept = within & (g_dyn == e_dyn[best])
+    res = {"gt_static": int((~g_dyn).sum()), "gt_dynamic": int(g_dyn.sum()), "est_static": int((~e_dyn).sum()),
+           "est_dynamic": int(e_dyn.sum()), "preserved_static": int((kept & ~g_dyn).sum()), "preserved_dynamic": int((kept & g_dyn).sum()),
+           "n_tied": int(tied.sum())}
+
+    def table(gk, ek, n):
+        c = {"n_gt": np.bincount(gk, minlength=n), "n_within": np.bincount(gk, within, minlength=n).astype(np.int64),
+             "n_preserved": np.bincount(gk, kept, minlength=n).astype(np.int64),
+             "n_tied": np.bincount(gk, tied, minlength=n).astype(np.int64), "n_est": np.bincount(ek, minlength=n)}
+        return {k: v[:n] for k, v in c.items()}
+
+    keys = np.union1d(g_key, e_key).astype(np.int64)
+    c = table(np.searchsorted(keys, g_key), np.searchsorted(keys, e_key), len(keys))
+    sem = keys & 0xFFFF
+    res["classes"] = _rows(keys, (keys < KEY_LABEL_OUT_OF_RANGE) & (sem >= 252) & (sem <= 259), c)
+    labs = np.union1d(g_lab[g_dyn], e_lab[e_dyn]).astype(np.int64)
+    gi = np.searchsorted(labs, g_lab.astype(np.int64))
+    ei = np.searchsorted(labs, e_lab.astype(np.int64))
+    ci = {k: np.bincount(gi[g_dyn], v[g_dyn] if v is not None else None, minlength=len(labs)).astype(np.int64)
+          for k, v in (("n_gt", None), ("n_within", within), ("n_preserved", kept), ("n_tied", tied))}
+    ci["n_est"] = np.bincount(ei[e_dyn], minlength=len(labs))
+    res["instances"] = _rows(labs, np.ones(len(labs), np.uint32), ci)
+    return res

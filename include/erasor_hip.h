@@ -280,6 +280,40 @@ int erasor_hip_evaluate_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t
 int erasor_hip_evaluate_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device,
                             double voxel_leaf, double voxelsize, erasor_eval_result *res);
 
+/* ---- PR / RR broken down by semantic class and by dynamic instance --------------------------------------------------------------
+ * The decision of erasor_hip_evaluate_* for every ground-truth point (its nearest estimated point, the threshold, the smallest
+ * estimated index on a tie), counted per class key and per dynamic instance.  Class key: uint32(intensity) & 0xFFFF, or
+ * ERASOR_EVAL_KEY_LABEL_OUT_OF_RANGE for an intensity that is not finite or outside [0, 2^32) (static, as in erasor_eval_result).
+ * Class rows: every key present in either cloud, in ascending order.  Instance rows: every whole label L = uint32(intensity) with a
+ * dynamic class (252..259) present in either cloud, in ascending order (n_gt may be 0: an estimate-only label).
+ * Summing the class rows gives gt_static / gt_dynamic, est_static / est_dynamic, preserved_static (static keys), preserved_dynamic
+ * (dynamic keys) and n_tied of erasor_eval_result; summing the instance rows of one dynamic class gives that class's row. */
+#define ERASOR_EVAL_KEY_LABEL_OUT_OF_RANGE 0x10000u
+typedef struct erasor_eval_class_row {
+    uint32_t key;         /* class: sem or ERASOR_EVAL_KEY_LABEL_OUT_OF_RANGE; instance: the whole uint32 label */
+    uint32_t is_dynamic;
+    uint64_t n_gt;        /* ground-truth points with this key */
+    uint64_t n_within;    /* ... whose nearest estimated point is within the threshold */
+    uint64_t n_preserved; /* ... counted in preserved_static / preserved_dynamic */
+    uint64_t n_tied;      /* ... counted in n_tied */
+    uint64_t n_est;       /* estimated points with this key */
+} erasor_eval_class_row;
+
+/* erasor_hip_evaluate_clouds / _map (arguments, errors, voxel_leaf and the map view as there; no per-point codes) with the rows.  res is
+ * what erasor_hip_evaluate_* returns on the same inputs.  *n_classes / *n_instances (required) and res are always written; the rows
+ * only when both fit their capacity, else ERASOR_E_CAPACITY: size the arrays and call again.  A NULL array with capacity 0 is allowed
+ * (a class array of 65537 rows always fits). */
+int erasor_hip_evaluate_clouds_by_class(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device,
+                                        const void *est_xyzi, size_t n_est, int est_is_device, double voxel_leaf, double voxelsize,
+                                        erasor_eval_class_row *classes, size_t cap_classes, size_t *n_classes,
+                                        erasor_eval_class_row *instances, size_t cap_instances, size_t *n_instances,
+                                        erasor_eval_result *res);
+int erasor_hip_evaluate_map_by_class(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device,
+                                     double voxel_leaf, double voxelsize,
+                                     erasor_eval_class_row *classes, size_t cap_classes, size_t *n_classes,
+                                     erasor_eval_class_row *instances, size_t cap_instances, size_t *n_instances,
+                                     erasor_eval_result *res);
+
 /* ---- the estimate-to-ground-truth overlap report: the alignment check before PR / RR (scripts/analysis_runner.py) -------------
  * replaces: analysis_runner.py:53-71 (overlap_report).  For every estimated point the distance d to its nearest ground-truth point
  * (exact and unbounded: float64 d^2 as cKDTree / NearestNeighbors compute it, the correctly rounded sqrt), then np.median, np.percentile
