@@ -67,6 +67,17 @@ class OverlapResult(C.Structure):
         return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
 
 
+class AlignRow(C.Structure):
+    """erasor_align_row (include/erasor_hip.h): one frame of align_frames"""
+    _fields_ = [("n_points", C.c_uint64), ("n_non_finite", C.c_uint64), ("r", OverlapResult)]
+
+    def as_dict(self):
+        """evalmap.align_frames' row keys"""
+        d = self.r.as_dict()
+        d.update(n_points=int(self.n_points), n_non_finite=int(self.n_non_finite))
+        return d
+
+
 class LabelResult(C.Structure):
     """erasor_label_result (include/erasor_hip.h): label_map of a map without labels (fill_removert_intensity.cpp:24-59)"""
     _fields_ = [("n_src", C.c_uint64), ("n_out", C.c_uint64), ("n_tied", C.c_uint64), ("passthrough", C.c_uint32)]
@@ -131,7 +142,7 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "revert_bins.hip.h",
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "revert_bins.hip.h",
                                                  "exact_sort.hip.h", "exact_sort_core.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
@@ -529,6 +540,41 @@ class Erasor:
         r = OverlapResult()
         self._check(lib().erasor_hip_overlap_map(self._h, *g, C.c_double(voxel_leaf), C.c_double(voxelsize), C.byref(r)))
         return r.as_dict()
+
+    # -- every frame's pose against the map before a run (the reference README's pitfalls 1, 3 and 5; on the host: evalmap.align_frames) --
+    def align_frames(self, scans, T_body2origin, T_lidar2body=None, map=None, voxelsize=0.2):
+        """overlap_report of every frame's scan, put into the map frame as the reference puts its RViz query (T_lidar2body, the identity
+        when None, then T_body2origin[f]), against `map` (a cloud as for evaluate; None: the handle's current map), all frames in one call
+        (erasor_hip_align_frames_clouds / _map).  scans: a list of (n, 4) host arrays, or the frames in one device buffer of the
+        handle's device as (device pointer, offsets), offsets[f] the first row of frame f and offsets[-1] the row count.  Returns
+        (rows, summary): per frame evalmap.overlap's keys plus n_points / n_non_finite, and the report of all frames' kept points
+        together."""
+        kept = []
+        if isinstance(scans, tuple):
+            ptr, offsets = scans
+            offs = np.ascontiguousarray(offsets, np.uint64)
+            q = (C.c_void_p(ptr), C.c_size_t(int(offs[-1]) if len(offs) else 0), 1)
+        else:
+            a = [_f32(s).reshape(-1, 4) for s in scans]
+            offs = np.zeros(len(a) + 1, np.uint64)
+            offs[1:] = np.cumsum([len(s) for s in a], dtype=np.uint64)
+            cat = _f32(np.concatenate(a) if a else np.zeros((0, 4), np.float32))
+            kept.append(cat)
+            q = (_p(cat), C.c_size_t(len(cat)), 0)
+        n_f = len(offs) - 1
+        Tb = _f32(np.asarray(T_body2origin, np.float32).reshape(n_f, 16) if n_f else np.zeros((1, 16), np.float32))
+        if T_lidar2body is not None:
+            kept.append(_f32(T_lidar2body).reshape(16))
+        Tl = None if T_lidar2body is None else _p(kept[-1])
+        rows = (AlignRow * max(n_f, 1))()
+        summ = OverlapResult()
+        tail = (q[0], q[1], _p(offs), C.c_size_t(n_f), C.c_int(q[2]), Tl, _p(Tb), C.c_double(voxelsize), rows, C.byref(summ))
+        if map is None:
+            self._check(lib().erasor_hip_align_frames_map(self._h, *tail))
+        else:
+            m = self._eval_cloud(map, kept)
+            self._check(lib().erasor_hip_align_frames_clouds(self._h, *m, *tail))
+        return [rows[f].as_dict() for f in range(n_f)], summ.as_dict()
 
     # -- maps without labels (fill_removert_intensity.cpp:24-59, compare_complement.cpp:43-75; on the host: evalmap.label_from /
     # evalmap.static_complement) --

@@ -36,6 +36,7 @@
 #include "kernels.hip.h"
 #include "evaluate.hip.h"
 #include "nearest.hip.h"
+#include "align.hip.h"
 
 using namespace ek;
 
@@ -316,6 +317,12 @@ struct erasor_hip_handle {
         // the breakdown by class and instance (erasor_hip_evaluate_*_by_class): the per-key table, the dynamic points' (label, counter
         // bits) records and their cursor, the flags / run heads with their scan, the class and instance rows (the records' sort: nn_k*, nn_v*)
         DBuf<uint32_t> bc_tab, bc_cur, bc_ikey, bc_ival, bc_flag, bc_pl, bc_tops, bc_crows, bc_irows;
+        // every frame's pose against the map (erasor_hip_align_frames_*): the map's tree and the distances are the overlap report's; the
+        // frame offsets, every query workgroup's first frame, the poses, the per-frame counters, ranks and selected values
+        DBuf<uint32_t> al_off, al_wg;
+        DBuf<Xf> al_xf;
+        DBuf<unsigned long long> al_ctr, al_val;
+        DBuf<AlRanks> al_rank;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
     // ---- per-bin scratch (R-GPF / bin voxelise global paths) ----
@@ -1081,6 +1088,7 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->ev.nn_idx); release(h->ev.nn_near); release(h->ev.nn_hist); release(h->ev.nn_pts); release(h->ev.nn_lo); release(h->ev.nn_hi);
     release(h->ev.nn_ctr); release(h->ev.nn_dbits);
     release(h->ev.fm_out); release(h->ev.fm_flag); release(h->ev.fm_pl); release(h->ev.fm_tops); release(h->ev.fm_ctr);
+    release(h->ev.al_off); release(h->ev.al_wg); release(h->ev.al_xf); release(h->ev.al_ctr); release(h->ev.al_val); release(h->ev.al_rank);
     for (int k = 0; k < NSIDE; ++k) {
         if (h->q[k].ev_keys) (void)hipEventDestroy(h->q[k].ev_keys);
         if (h->q[k].ev_done) (void)hipEventDestroy(h->q[k].ev_done);
@@ -3629,6 +3637,78 @@ static int nn_tree(erasor_hip_handle *h, const float4 *pts, uint32_t n, uint32_t
     return ERASOR_OK;
 }
 
+// the target ranks of n > 0 sorted distances: the median's one or two, the two of each percentile (and the percentiles' gammas)
+static void ov_ranks(uint64_t n, uint64_t rk[OV_SEL_MAX], double *g90, double *g99) {
+    rk[0] = (n - 1) / 2;
+    rk[1] = n / 2;
+    ov_percentile_ranks(n, 90, &rk[2], &rk[3], g90);
+    ov_percentile_ranks(n, 99, &rk[4], &rk[5], g99);
+}
+
+// the exact radix select over the bit patterns v[0 .. count), driven from the host (k_ov_select_hist): the values at the ranks rk, from the
+// top digit down; every target keeps its prefix and its rank inside that prefix.  Values above every rank (align's sentinel) never matter.
+static int ov_select(erasor_hip_handle *h, const unsigned long long *v, uint32_t count, const uint64_t rk[OV_SEL_MAX], double out[OV_SEL_MAX]) {
+    auto &E = h->ev;
+    unsigned long long pref[OV_SEL_MAX] = {};
+    uint64_t left[OV_SEL_MAX];
+    for (uint32_t t = 0; t < OV_SEL_MAX; ++t) left[t] = rk[t];
+    std::vector<uint32_t> hist(OV_SEL_MAX * 256);
+    const uint32_t grid = std::min(cdiv(count, 256 * 8), 1024u);
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        OvSelect s;
+        memset(&s, 0, sizeof(s));
+        s.shift = shift;
+        uint32_t slot[OV_SEL_MAX];
+        for (uint32_t t = 0; t < OV_SEL_MAX; ++t) {
+            uint32_t k = 0;
+            while (k < s.n && s.pref[k] != pref[t]) ++k;
+            if (k == s.n) s.pref[s.n++] = pref[t];
+            slot[t] = k;
+        }
+        HIPC(h, hipMemsetAsync(E.nn_hist.p, 0, (size_t)s.n * 256 * sizeof(uint32_t), h->stream));
+        LAUNCH(h, "ov_select", k_ov_select_hist, grid, 256, v, count, s, E.nn_hist.p);
+        HIPC(h, hipMemcpyAsync(hist.data(), E.nn_hist.p, (size_t)s.n * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
+        for (uint32_t t = 0; t < OV_SEL_MAX; ++t) {
+            const uint32_t *hh = hist.data() + (size_t)slot[t] * 256;
+            uint64_t cum = 0;
+            uint32_t d = 0;
+            while (d < 255 && left[t] >= cum + hh[d]) cum += hh[d++];
+            left[t] -= cum;
+            pref[t] = (pref[t] << 8) | d;
+        }
+    }
+    memcpy(out, pref, sizeof(pref));
+    return ERASOR_OK;
+}
+
+// one report from n distances: the counts below the thresholds, the largest distance's bits, and (n > 0) the values at ov_ranks' ranks
+static void ov_fill(uint64_t n, uint64_t below_half, uint64_t below_one, uint64_t below_two, unsigned long long max_bits, const double v[OV_SEL_MAX],
+                    double g90, double g99, erasor_overlap_result *res) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    erasor_overlap_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_est = n;
+    r.n_below_half = below_half;
+    r.n_below_one = below_one;
+    r.n_below_two = below_two;
+    r.median = r.p90 = r.p99 = r.max = r.frac_half = r.frac_one = r.frac_two = nan;
+    if (n) {
+        // np.median: the middle value, or the mean of the two middle ones, (a + b) / 2
+        r.median = (n % 2) ? v[0] : (v[0] + v[1]) / 2.0;
+        r.p90 = ov_lerp(v[2], v[3], g90);
+        r.p99 = ov_lerp(v[4], v[5], g99);
+        double mx;
+        memcpy(&mx, &max_bits, sizeof(mx));
+        r.max = mx;
+        // np.mean(d < x) * 100
+        r.frac_half = (double)r.n_below_half / (double)n * 100.0;
+        r.frac_one = (double)r.n_below_one / (double)n * 100.0;
+        r.frac_two = (double)r.n_below_two / (double)n * 100.0;
+    }
+    *res = r;
+}
+
 static int ov_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize, double *per_dist,
                   uint32_t *per_nearest, erasor_overlap_result *res) {
     auto &E = h->ev;
@@ -3654,68 +3734,16 @@ static int ov_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const f
         h->err = "erasor_hip_overlap: non-finite coordinate (NaN / Inf) in " + std::to_string(c[OV_NON_FINITE]) + " estimated point(s)";
         return ERASOR_E_INVALID;
     }
-    const double nan = std::numeric_limits<double>::quiet_NaN();
     erasor_overlap_result r;
-    memset(&r, 0, sizeof(r));
-    r.n_est = n_est;
-    r.n_below_half = c[OV_BELOW_HALF];
-    r.n_below_one = c[OV_BELOW_ONE];
-    r.n_below_two = c[OV_BELOW_TWO];
-    r.median = r.p90 = r.p99 = r.max = r.frac_half = r.frac_one = r.frac_two = nan;
+    const uint64_t n = n_est;
+    double v[OV_SEL_MAX] = {}, g90 = 0, g99 = 0;
     if (n_est) {
-        // target ranks: the median's one or two, the two of each percentile
-        const uint64_t n = n_est;
         uint64_t rk[OV_SEL_MAX];
-        double g90, g99;
-        rk[0] = (n - 1) / 2;
-        rk[1] = n / 2;
-        ov_percentile_ranks(n, 90, &rk[2], &rk[3], &g90);
-        ov_percentile_ranks(n, 99, &rk[4], &rk[5], &g99);
-        // the exact radix select, from the top digit down: every target keeps its prefix and its rank inside that prefix
-        unsigned long long pref[OV_SEL_MAX] = {}, val[OV_SEL_MAX];
-        uint64_t left[OV_SEL_MAX];
-        for (uint32_t t = 0; t < OV_SEL_MAX; ++t) left[t] = rk[t];
-        std::vector<uint32_t> hist(OV_SEL_MAX * 256);
-        const uint32_t grid = std::min(cdiv(n_est, 256 * 8), 1024u);
-        for (int shift = 56; shift >= 0; shift -= 8) {
-            OvSelect s;
-            memset(&s, 0, sizeof(s));
-            s.shift = shift;
-            uint32_t slot[OV_SEL_MAX];
-            for (uint32_t t = 0; t < OV_SEL_MAX; ++t) {
-                uint32_t k = 0;
-                while (k < s.n && s.pref[k] != pref[t]) ++k;
-                if (k == s.n) s.pref[s.n++] = pref[t];
-                slot[t] = k;
-            }
-            HIPC(h, hipMemsetAsync(E.nn_hist.p, 0, (size_t)s.n * 256 * sizeof(uint32_t), h->stream));
-            LAUNCH(h, "ov_select", k_ov_select_hist, grid, 256, (const unsigned long long *)E.nn_dbits.p, n_est, s, E.nn_hist.p);
-            HIPC(h, hipMemcpyAsync(hist.data(), E.nn_hist.p, (size_t)s.n * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-            HIPC(h, hipStreamSynchronize(h->stream));
-            for (uint32_t t = 0; t < OV_SEL_MAX; ++t) {
-                const uint32_t *hh = hist.data() + (size_t)slot[t] * 256;
-                uint64_t cum = 0;
-                uint32_t d = 0;
-                while (d < 255 && left[t] >= cum + hh[d]) cum += hh[d++];
-                left[t] -= cum;
-                pref[t] = (pref[t] << 8) | d;
-            }
-        }
-        for (uint32_t t = 0; t < OV_SEL_MAX; ++t) memcpy(&val[t], &pref[t], sizeof(double));
-        double v[OV_SEL_MAX];
-        memcpy(v, val, sizeof(v));
-        // np.median: the middle value, or the mean of the two middle ones, (a + b) / 2
-        r.median = (n % 2) ? v[0] : (v[0] + v[1]) / 2.0;
-        r.p90 = ov_lerp(v[2], v[3], g90);
-        r.p99 = ov_lerp(v[4], v[5], g99);
-        double mx;
-        const unsigned long long mbits = c[OV_MAX_BITS];
-        memcpy(&mx, &mbits, sizeof(mx));
-        r.max = mx;
-        // np.mean(d < x) * 100
-        r.frac_half = (double)r.n_below_half / (double)n * 100.0;
-        r.frac_one = (double)r.n_below_one / (double)n * 100.0;
-        r.frac_two = (double)r.n_below_two / (double)n * 100.0;
+        ov_ranks(n, rk, &g90, &g99);
+        if ((rc = ov_select(h, E.nn_dbits.p, n_est, rk, v))) return rc;
+    }
+    ov_fill(n, c[OV_BELOW_HALF], c[OV_BELOW_ONE], c[OV_BELOW_TWO], c[OV_MAX_BITS], v, g90, g99, &r);
+    if (n_est) {
         if (per_dist) HIPC(h, hipMemcpy(per_dist, E.nn_dbits.p, (size_t)n_est * sizeof(double), hipMemcpyDeviceToHost));
         if (per_nearest) HIPC(h, hipMemcpy(per_nearest, E.nn_near.p, (size_t)n_est * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
@@ -3806,6 +3834,170 @@ int erasor_hip_overlap_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_g
         e = h->ev.est.p;
     }
     return ov_run(h, g, ng, e, ne, voxelsize, nullptr, nullptr, res);
+}
+
+// ---- every frame's pose against the map, before a run (the reference README's pitfalls 1, 3 and 5; kernels: align.hip.h) ----
+// Like ov_run: the main stream, the evaluator's scratch, the map's tree sorted in bank 2.  Round trips: the per-frame counters once, the
+// per-frame values once, and the summary's host-driven select (8 passes).
+
+// the arguments both entry points check: ERASOR_E_INVALID with h->err set, else ERASOR_OK and the scans' point count in *n_scan
+static int al_check_args(erasor_hip_handle *h, const char *who, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets,
+                         size_t n_frames, const float *T_lidar2body, const float *T_body2origin, double voxelsize, erasor_align_row *rows) {
+    auto fail = [&](const char *why) {
+        h->err = std::string(who) + ": " + why;
+        return ERASOR_E_INVALID;
+    };
+    if (!(voxelsize > 0) || !std::isfinite(voxelsize)) return fail("voxelsize must be a finite number > 0");
+    if (n_frames > 65536) return fail("more than 65536 frames");
+    if (!offsets) return fail("offsets is NULL (n_frames + 1 entries)");
+    if (n_frames && (!rows || !T_body2origin)) return fail("rows or T_body2origin is NULL");
+    if (n_scan_points > 0x3FFFFFFFull) return fail("more than 2^30 scan points");
+    if (!scans_xyzi && n_scan_points) return fail("NULL scans");
+    if (offsets[0] != 0) return fail("offsets[0] must be 0");
+    for (size_t f = 0; f < n_frames; ++f)
+        if (offsets[f + 1] < offsets[f]) return fail("offsets decrease");
+    if (offsets[n_frames] != n_scan_points) return fail("the last offset is not the scans' point count");
+    if (T_lidar2body)
+        for (int k = 0; k < 16; ++k)
+            if (!std::isfinite(T_lidar2body[k])) return fail("non-finite entry in T_lidar2body");
+    for (size_t k = 0; k < n_frames * 16; ++k)
+        if (!std::isfinite(T_body2origin[k])) return fail("non-finite entry in T_body2origin");
+    return ERASOR_OK;
+}
+
+static int al_run(erasor_hip_handle *h, const char *who, const float4 *map, uint32_t n_map, const float4 *scans, uint32_t n, const uint64_t *offsets,
+                  uint32_t n_frames, const float *T_lidar2body, const float *T_body2origin, double voxelsize, erasor_align_row *rows,
+                  erasor_overlap_result *summary) {
+    auto &E = h->ev;
+    NnScope scope(h);
+    if (!n_map && n) {
+        h->err = std::string(who) + ": empty map with a non-empty frame (no nearest point to measure against)";
+        return ERASOR_E_INVALID;
+    }
+    uint32_t P = 1;
+    int rc = nn_pad(h, n_map, &P, who, "map");
+    if (rc) return rc;
+    const uint32_t grid = cdiv(n, NN_QBLOCK), nf = std::max(n_frames, 1u);
+    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256) || ensure(h, E.nn_dbits, (size_t)n + 1) ||
+        ensure(h, E.al_off, (size_t)nf + 1) || ensure(h, E.al_wg, (size_t)grid + 1) || ensure(h, E.al_xf, nf) ||
+        ensure(h, E.al_ctr, (size_t)nf * AL_NCTR) || ensure(h, E.al_rank, nf) || ensure(h, E.al_val, (size_t)nf * OV_SEL_MAX))
+        return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if (n_map && (rc = nn_tree(h, map, n_map, P, who, "map point(s)"))) return rc;
+    // the frames: offsets (< 2^30), the frame of every query workgroup's first point (the last frame after the last), the poses
+    std::vector<uint32_t> off(n_frames + 1), wg(grid + 1);
+    for (uint32_t f = 0; f <= n_frames; ++f) off[f] = (uint32_t)offsets[f];
+    for (uint32_t b = 0, f = 0; b < grid; ++b) {  // the largest f < n_frames with off[f] <= b * NN_QBLOCK
+        while (f + 1 < n_frames && off[f + 1] <= b * NN_QBLOCK) ++f;
+        wg[b] = f;
+    }
+    wg[grid] = n_frames ? n_frames - 1 : 0;
+    static const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    std::vector<Xf> xf(nf);
+    for (uint32_t f = 0; f < n_frames; ++f) xf[f] = to_xf(T_body2origin + 16 * (size_t)f);
+    HIPC(h, hipMemcpyAsync(E.al_off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(E.al_wg.p, wg.data(), wg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(E.al_xf.p, xf.data(), nf * sizeof(Xf), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemsetAsync(E.al_ctr.p, 0, (size_t)nf * AL_NCTR * sizeof(unsigned long long), h->stream));
+    // the thresholds as overlap_report forms them: half = 0.5 * voxelsize, one = voxelsize, 2 * one
+    const double half = 0.5 * voxelsize, one = voxelsize, two = 2 * one;
+    if (n)
+        LAUNCH(h, "al_query", k_al_query, grid, NN_QBLOCK, scans, n, (const uint32_t *)E.al_off.p, (const uint32_t *)E.al_wg.p,
+               to_xf(T_lidar2body ? T_lidar2body : I), (const Xf *)E.al_xf.p, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, n_map,
+               (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, half, one, two, E.nn_dbits.p, E.al_ctr.p);
+    std::vector<unsigned long long> c((size_t)nf * AL_NCTR);
+    HIPC(h, hipMemcpyAsync(c.data(), E.al_ctr.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    // every frame's ranks over its kept points, one select launch for all frames, and numpy's formulas on the six values of each
+    std::vector<AlRanks> rk(nf);
+    std::vector<double> g(2 * (size_t)nf), v((size_t)nf * OV_SEL_MAX);
+    uint64_t n_kept = 0, below[3] = {0, 0, 0};
+    unsigned long long max_bits = 0;
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const unsigned long long *cf = &c[(size_t)f * AL_NCTR];
+        memset(&rk[f], 0, sizeof(AlRanks));
+        rk[f].n = (off[f + 1] - off[f]) - cf[AL_NON_FINITE];
+        if (rk[f].n) {
+            uint64_t r6[OV_SEL_MAX];
+            ov_ranks(rk[f].n, r6, &g[2 * f], &g[2 * f + 1]);
+            for (uint32_t k = 0; k < OV_SEL_MAX; ++k) rk[f].rk[k] = r6[k];
+        }
+        n_kept += rk[f].n;
+        below[0] += cf[AL_BELOW_HALF];
+        below[1] += cf[AL_BELOW_ONE];
+        below[2] += cf[AL_BELOW_TWO];
+        max_bits = std::max(max_bits, cf[AL_MAX_BITS]);
+    }
+    if (n_kept) {
+        HIPC(h, hipMemcpyAsync(E.al_rank.p, rk.data(), n_frames * sizeof(AlRanks), hipMemcpyHostToDevice, h->stream));
+        LAUNCH(h, "al_select", k_al_select, n_frames, 256, (const unsigned long long *)E.nn_dbits.p, (const uint32_t *)E.al_off.p,
+               (const AlRanks *)E.al_rank.p, E.al_val.p);
+        HIPC(h, hipMemcpyAsync(v.data(), E.al_val.p, v.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
+    }
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const unsigned long long *cf = &c[(size_t)f * AL_NCTR];
+        rows[f].n_points = off[f + 1] - off[f];
+        rows[f].n_non_finite = cf[AL_NON_FINITE];
+        ov_fill(rk[f].n, cf[AL_BELOW_HALF], cf[AL_BELOW_ONE], cf[AL_BELOW_TWO], cf[AL_MAX_BITS], &v[(size_t)f * OV_SEL_MAX], g[2 * f], g[2 * f + 1],
+                &rows[f].r);
+    }
+    if (summary) {  // the kept points of all frames: the whole distance array, the dropped points' sentinels above every rank
+        double sv[OV_SEL_MAX] = {}, g90 = 0, g99 = 0;
+        if (n_kept) {
+            uint64_t srk[OV_SEL_MAX];
+            ov_ranks(n_kept, srk, &g90, &g99);
+            if ((rc = ov_select(h, E.nn_dbits.p, n, srk, sv))) return rc;
+        }
+        ov_fill(n_kept, below[0], below[1], below[2], max_bits, sv, g90, g99, summary);
+    }
+    return ERASOR_OK;
+}
+
+int erasor_hip_align_frames_clouds(erasor_hip_handle *h, const void *map_xyzi, size_t n_map, int map_is_device, const void *scans_xyzi,
+                                   size_t n_scan_points, const uint64_t *offsets, size_t n_frames, int scans_are_device,
+                                   const float T_lidar2body[16], const float *T_body2origin, double voxelsize, erasor_align_row *rows,
+                                   erasor_overlap_result *summary) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_align_frames_clouds";
+    int rc = al_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, voxelsize, rows);
+    if (rc) return rc;
+    if ((!map_xyzi && n_map) || n_map > 0x3FFFFFFFull) {
+        h->err = std::string(who) + ": NULL map or more than 2^30 map points";
+        return ERASOR_E_INVALID;
+    }
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr, *q = nullptr;
+    if ((rc = ev_input(h, map_xyzi, n_map, map_is_device, h->ev.gt, &m)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q)))
+        return rc;
+    return al_run(h, who, m, (uint32_t)n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, voxelsize, rows,
+                  summary);
+}
+
+int erasor_hip_align_frames_map(erasor_hip_handle *h, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                                int scans_are_device, const float T_lidar2body[16], const float *T_body2origin, double voxelsize,
+                                erasor_align_row *rows, erasor_overlap_result *summary) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_align_frames_map";
+    int rc = al_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, voxelsize, rows);
+    if (rc) return rc;
+    if (!h->have_map) {
+        h->err = std::string(who) + ": the handle has no map (erasor_hip_set_map first)";
+        return ERASOR_E_STATE;
+    }
+    HIPC(h, hipSetDevice(h->device));
+    size_t n_map = 0;
+    if ((rc = map_to_device(h, h->ev.map, &n_map))) return rc;
+    if (n_map > 0x3FFFFFFFull) {
+        h->err = std::string(who) + ": map larger than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    const float4 *q = nullptr;
+    if ((rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q))) return rc;
+    return al_run(h, who, h->ev.map.p, (uint32_t)n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin,
+                  voxelsize, rows, summary);
 }
 
 // ---- label_map (fill_removert_intensity.cpp:24-59, compare_map.cpp:77-110) and calc_complement (compare_complement.cpp:43-75): the

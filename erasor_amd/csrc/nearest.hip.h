@@ -144,6 +144,63 @@ __device__ __forceinline__ double nn_lb(const float4 &l, const float4 &u, double
     return (gx * gx + gy * gy) + gz * gz;
 }
 
+// the exact float64 1-NN of q over the tree (n_gt > 0, q finite): the best d^2, and in *best_i the smallest original index at it.
+// stack: the workgroup's [NN_STACK][NN_QBLOCK] LDS array, t: the lane's column.  k_nn_query and k_al_query (align.hip.h) share it.
+__device__ __forceinline__ double nn_search_f64(double qx, double qy, double qz, const float4 *__restrict__ pts, const uint32_t *__restrict__ idx,
+                                               uint32_t n_gt, const float4 *__restrict__ lo, const float4 *__restrict__ hi, uint32_t n_pad,
+                                               uint32_t *stack, uint32_t t, uint32_t *best_i_out) {
+    double best = __builtin_huge_val();
+    uint32_t best_i = 0xFFFFFFFFu;
+    uint32_t node = 1, sp = 0;
+    for (;;) {
+        if (node >= n_pad) {  // a leaf: its points (a leaf that is reached holds at least one)
+            const uint32_t b = (node - n_pad) * NN_LEAF, e = b + NN_LEAF < n_gt ? b + NN_LEAF : n_gt;
+            for (uint32_t s = b; s < e; ++s) {
+                const float4 p = pts[s];
+                const double ex = qx - (double)p.x, ey = qy - (double)p.y, ez = qz - (double)p.z;
+                const double d2 = (ex * ex + ey * ey) + ez * ez;
+                if (d2 <= best) {
+                    const uint32_t j = idx[s];
+                    if (d2 < best || j < best_i) {
+                        best = d2;
+                        best_i = j;
+                    }
+                }
+            }
+        } else {
+            const uint32_t c = 2 * node;
+            const float4 l0 = lo[c], u0 = hi[c], l1 = lo[c + 1], u1 = hi[c + 1];
+            const double d0 = l0.x <= u0.x ? nn_lb(l0, u0, qx, qy, qz) : __builtin_huge_val();  // (empty boxes: never entered)
+            const double d1 = l1.x <= u1.x ? nn_lb(l1, u1, qx, qy, qz) : __builtin_huge_val();
+            const bool v0 = l0.x <= u0.x && !(d0 > best), v1 = l1.x <= u1.x && !(d1 > best);
+            if (v0 && v1) {
+                const uint32_t near = d1 < d0 ? c + 1 : c;
+                stack[sp * NN_QBLOCK + t] = near ^ 1u;  // (sp < the tree's depth <= NN_STACK - 1: one entry per level above)
+                ++sp;
+                node = near;
+                continue;
+            }
+            if (v0 || v1) {
+                node = v0 ? c : c + 1;
+                continue;
+            }
+        }
+        bool more = false;  // the next pending sibling that may still hold a point at d^2 <= best
+        while (sp) {
+            --sp;
+            const uint32_t k = stack[sp * NN_QBLOCK + t];
+            if (!(nn_lb(lo[k], hi[k], qx, qy, qz) > best)) {
+                node = k;
+                more = true;
+                break;
+            }
+        }
+        if (!more) break;
+    }
+    *best_i_out = best_i;
+    return best;
+}
+
 // (5) one estimated point per lane: its nearest GT point (d^2, then the smaller original index), d = sqrt(d^2) as a bit pattern in
 // dbits, the original index in nearest (optional), the three threshold counters and the maximum.  n_gt > 0.
 __global__ __launch_bounds__(NN_QBLOCK) void k_nn_query(const float4 *__restrict__ est, uint32_t n_est, const float4 *__restrict__ pts,
@@ -162,55 +219,8 @@ __global__ __launch_bounds__(NN_QBLOCK) void k_nn_query(const float4 *__restrict
             dbits[i] = 0ull;
             if (nearest) nearest[i] = 0xFFFFFFFFu;
         } else {
-            const double qx = (double)q.x, qy = (double)q.y, qz = (double)q.z;
-            double best = __builtin_huge_val();
-            uint32_t best_i = 0xFFFFFFFFu;
-            uint32_t node = 1, sp = 0;
-            for (;;) {
-                if (node >= n_pad) {  // a leaf: its points (a leaf that is reached holds at least one)
-                    const uint32_t b = (node - n_pad) * NN_LEAF, e = b + NN_LEAF < n_gt ? b + NN_LEAF : n_gt;
-                    for (uint32_t s = b; s < e; ++s) {
-                        const float4 p = pts[s];
-                        const double ex = qx - (double)p.x, ey = qy - (double)p.y, ez = qz - (double)p.z;
-                        const double d2 = (ex * ex + ey * ey) + ez * ez;
-                        if (d2 <= best) {
-                            const uint32_t j = idx[s];
-                            if (d2 < best || j < best_i) {
-                                best = d2;
-                                best_i = j;
-                            }
-                        }
-                    }
-                } else {
-                    const uint32_t c = 2 * node;
-                    const float4 l0 = lo[c], u0 = hi[c], l1 = lo[c + 1], u1 = hi[c + 1];
-                    const double d0 = l0.x <= u0.x ? nn_lb(l0, u0, qx, qy, qz) : __builtin_huge_val();  // (empty boxes: never entered)
-                    const double d1 = l1.x <= u1.x ? nn_lb(l1, u1, qx, qy, qz) : __builtin_huge_val();
-                    const bool v0 = l0.x <= u0.x && !(d0 > best), v1 = l1.x <= u1.x && !(d1 > best);
-                    if (v0 && v1) {
-                        const uint32_t near = d1 < d0 ? c + 1 : c;
-                        stack[sp * NN_QBLOCK + t] = near ^ 1u;  // (sp < the tree's depth <= NN_STACK - 1: one entry per level above)
-                        ++sp;
-                        node = near;
-                        continue;
-                    }
-                    if (v0 || v1) {
-                        node = v0 ? c : c + 1;
-                        continue;
-                    }
-                }
-                bool more = false;  // the next pending sibling that may still hold a point at d^2 <= best
-                while (sp) {
-                    --sp;
-                    const uint32_t k = stack[sp * NN_QBLOCK + t];
-                    if (!(nn_lb(lo[k], hi[k], qx, qy, qz) > best)) {
-                        node = k;
-                        more = true;
-                        break;
-                    }
-                }
-                if (!more) break;
-            }
+            uint32_t best_i;
+            const double best = nn_search_f64((double)q.x, (double)q.y, (double)q.z, pts, idx, n_gt, lo, hi, n_pad, stack, t, &best_i);
             const double d = sqrt(best);
             bh = d < half ? 1u : 0u;
             b1 = d < one ? 1u : 0u;

@@ -462,6 +462,112 @@ static int config_mode(int argc, char **argv) {
     return run_config(argv[2], argc > 3 ? atoi(argv[3]) : 1 << 30, 0, true, nullptr, argc > 4 ? argv[4] : "");
 }
 
+// --align <rosparam.yaml> [n_frames] [voxelsize = 0.2]: the check the reference README asks for before anything else ("ERASOR in the
+// Wild", pitfalls 1, 3 and 5): does pose_i · pcds/%06d.pcd overlay the initial map?  The same files as --config (data_dir, init_idx,
+// poses_lidar2body.csv, the initial map, tf/lidar2body), and every frame's T_body2origin is the matrix run_config hands the step: the
+// CSV pose after the eigen2geoPose / geoPose2eigen round trip.  One line per frame (erasor_hip_align_frames_clouds), a frame flagged
+// when 50 % or less of its points lie within 0.5 * v ("most points should sit within 0.5 × voxel_size"), then the summary in
+// overlap_report's two lines.  When tf/lidar2body is not the identity, a second pass with the identity, and which of the README's two
+// conventions puts more of the points within v of the map: (A) poses T_map_from_lidar with an identity tf, (B) poses T_map_from_body
+// with the extrinsic in tf/lidar2body.
+static int align_mode(int argc, char **argv) {
+    if (argc < 3) return 2;
+    const int max_frames = argc > 3 ? atoi(argv[3]) : 1 << 30;
+    const double voxelsize = argc > 4 ? atof(argv[4]) : 0.2;
+    erasor::OfflineMapUpdater::Config cfg;
+    erasor_hip_params_default(&cfg.params);
+    erasor::DriverConfig drv;
+    if (!erasor::load_config_yaml(argv[2], cfg, &drv)) {
+        fprintf(stderr, "cannot read %s\n", argv[2]);
+        return 3;
+    }
+    if (cfg.initial_map_path.empty() || cfg.initial_map_path == "/") cfg.initial_map_path = drv.data_dir + "/dense_global_map.pcd";
+    std::vector<Eigen::Matrix4f> poses;
+    if (!erasor::load_all_poses(drv.data_dir + "/poses_lidar2body.csv", poses)) {
+        fprintf(stderr, "cannot read %s/poses_lidar2body.csv\n", drv.data_dir.c_str());
+        return 3;
+    }
+    std::vector<float> map, scans, Tb;
+    if (!load_cloud_xyzi(cfg.initial_map_path, map)) {
+        fprintf(stderr, "cannot read %s\n", cfg.initial_map_path.c_str());
+        return 3;
+    }
+    std::vector<uint64_t> offsets{0};
+    const int last = std::min((int)poses.size(), drv.init_idx + max_frames);
+    for (int i = drv.init_idx; i < last; ++i) {
+        char name[64];
+        snprintf(name, sizeof(name), "/pcds/%06d.pcd", i);
+        std::vector<float> scan;
+        if (!load_cloud_xyzi(drv.data_dir + name, scan)) {
+            fprintf(stderr, "cannot read %s%s\n", drv.data_dir.c_str(), name);
+            return 3;
+        }
+        scans.insert(scans.end(), scan.begin(), scan.end());
+        offsets.push_back(scans.size() / 4);
+        const Eigen::Matrix4f T = erasor_utils::geoPose2eigen(erasor_utils::eigen2geoPose(poses[i]));  // (callback_node's round trip)
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) Tb.push_back(T(r, c));
+    }
+    geometry_msgs::Pose l2b;
+    l2b.position.x = cfg.lidar2body[0];
+    l2b.position.y = cfg.lidar2body[1];
+    l2b.position.z = cfg.lidar2body[2];
+    l2b.orientation.x = cfg.lidar2body[3];
+    l2b.orientation.y = cfg.lidar2body[4];
+    l2b.orientation.z = cfg.lidar2body[5];
+    l2b.orientation.w = cfg.lidar2body[6];
+    const Eigen::Matrix4f TL = erasor_utils::geoPose2eigen(l2b);  // (OMU.cpp:100)
+    float Tl[16];
+    bool identity = true;
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+            Tl[4 * r + c] = TL(r, c);
+            identity = identity && TL(r, c) == (r == c ? 1.0f : 0.0f);
+        }
+    erasor_params p;
+    erasor_hip_params_default(&p);
+    erasor_hip_handle *h = nullptr;
+    if (erasor_hip_create(&p, 0, &h) != ERASOR_OK) {
+        fprintf(stderr, "erasor_hip_create failed\n");
+        return 1;
+    }
+    const size_t n_frames = offsets.size() - 1;
+    std::vector<erasor_align_row> rows(std::max<size_t>(n_frames, 1));
+    const double half = 0.5 * voxelsize, one = voxelsize;
+    double within_one[2] = {0, 0};
+    for (int pass = 0; pass < (identity ? 1 : 2); ++pass) {
+        erasor_overlap_result sum;
+        const int rc = erasor_hip_align_frames_clouds(h, map.data(), map.size() / 4, 0, scans.data(), scans.size() / 4, offsets.data(), n_frames, 0,
+                                                      pass ? nullptr : Tl, Tb.data(), voxelsize, rows.data(), &sum);
+        if (rc) {
+            fprintf(stderr, "align: %s (rc %d)\n", erasor_hip_last_error(h), rc);
+            erasor_hip_destroy(h);
+            return 1;
+        }
+        if (pass == 0)
+            printf("%zu frames against %s (%zu points), tf/lidar2body as configured%s:\n", n_frames, cfg.initial_map_path.c_str(), map.size() / 4,
+                   identity ? " (the identity)" : ", convention (B)");
+        else
+            printf("the same with tf/lidar2body = identity, convention (A):\n");
+        for (size_t f = 0; f < n_frames; ++f) {
+            const erasor_overlap_result &r = rows[f].r;
+            printf("%6d  n=%llu  median=%.4fm  p90=%.4fm  <0.5*v %.2f%%  <1*v %.2f%%  <2*v %.2f%%%s\n", drv.init_idx + (int)f,
+                   (unsigned long long)rows[f].n_points, r.median, r.p90, r.frac_half, r.frac_one, r.frac_two,
+                   r.frac_half > 50.0 ? "" : "  <- check this pose");
+        }
+        printf("est->GT dist: median=%.4fm  p90=%.4fm  p99=%.4fm  max=%.4fm\n", sum.median, sum.p90, sum.p99, sum.max);
+        printf("  fraction <0.5*v (%.2fm): %.2f%%  <1*v (%.2fm): %.2f%%  <2*v (%.2fm): %.2f%%\n", half, sum.frac_half, one, sum.frac_one, 2 * one,
+               sum.frac_two);
+        within_one[pass] = sum.n_est ? (double)sum.n_below_one / (double)sum.n_est * 100.0 : 0.0;
+    }
+    if (!identity)
+        printf("convention: (B) T_map_from_body with tf/lidar2body as configured puts %.2f%% of the points within v of the map, (A) "
+               "T_map_from_lidar with an identity tf/lidar2body %.2f%%: %s\n",
+               within_one[0], within_one[1], within_one[0] >= within_one[1] ? "(B) fits better" : "(A) fits better");
+    erasor_hip_destroy(h);
+    return 0;
+}
+
 // --queue <n_workers> <max_frames> <a.yaml> <b.yaml> ...: independent sequences (one rosparam file each) over n_workers devices
 // (worker w drives device w mod the visible devices): every worker is a thread with its own updater per job, and takes the NEXT sequence
 // of the list whenever it is idle (erasor::WorkQueue) -- BASELINE config 3 on a node with fewer GPUs than sequences.
@@ -806,6 +912,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && std::string(argv[1]) == "--align") {
+        try {
+            return align_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--analyze") {
         try {
             return analyze_mode(argc, argv);
@@ -842,9 +956,9 @@ int main(int argc, char **argv) {
         fprintf(stderr,
                 "usage: %s <data_dir> <n_frames> [version] [removal_interval] [gt]\n       %s --config <rosparam.yaml> [n_frames] [gt]\n"
                 "       %s --eval <gt> <est> [voxelsize] [voxel_leaf]\n       %s --eval-classes <gt> <est> [voxelsize] [voxel_leaf]\n"
-                "       %s --analyze <gt> <est> [voxelsize] [voxel_leaf]\n"
+                "       %s --analyze <gt> <est> [voxelsize] [voxel_leaf]\n       %s --align <rosparam.yaml> [n_frames] [voxelsize]\n"
                 "       %s --label <map> <dense_labelled> [leaf]\n       %s --complement <est> <gt> <out.pcd>\n",
-                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

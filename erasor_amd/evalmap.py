@@ -12,6 +12,8 @@ overlap_report), pinned by tests/golden/overlap_golden.npz (tests/golden/make_ov
 nearest_f32 / label_from / static_complement: the 1-NN of pcl::KdTreeFLANN (float32 d^2, lowest index on ties) behind the
 reference's label_map (src/utils/fill_removert_intensity.cpp:24-59) and calc_complement (src/utils/compare_complement.cpp:43-75).
 
+align_frames: overlap() of every frame's scan, put into the map frame by its pose, against the map (Erasor.align_frames).
+
 evaluate_by_class: the same decision per GT point, counted per semantic class and per dynamic instance (Erasor.evaluate_by_class).
 """
 import numpy as np
@@ -77,6 +79,35 @@ def overlap_lines(r, voxelsize=0.2):
     return [f"est->GT dist: median={r['median']:.4f}m  p90={r['p90']:.4f}m  p99={r['p99']:.4f}m  max={r['max']:.4f}m",
             f"  fraction <0.5*v ({half:.2f}m): {r['frac_half']:.2f}%  <1*v ({one:.2f}m): {r['frac_one']:.2f}%  "
             f"<2*v ({2*one:.2f}m): {r['frac_two']:.2f}%"]
+
+
+def _xform(T, xyz):
+    """pcl::transformPointCloud in float32, operation by operation: ((a*x + b*y) + c*z) + d per output coordinate"""
+    T = np.asarray(T, np.float32).reshape(4, 4)
+    x, y, z = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    return np.stack([((T[r, 0] * x + T[r, 1] * y) + T[r, 2] * z) + T[r, 3] for r in range(3)], 1)
+
+
+def align_frames(map_xyz, scans, T_body2origin, T_lidar2body=None, voxelsize=0.2):
+    """Every frame's pose checked against the map (the reference README's pitfalls 1, 3 and 5): scan f as given, put into the map frame
+    as the reference puts its RViz query, body2origin(tf_lidar2body · scan) -- T_lidar2body (the identity when None, still applied),
+    then T_body2origin[f], in float32 --, points with a non-finite coordinate afterwards dropped and counted, and overlap() of the rest
+    against the map.  Returns (rows, summary): a row per frame with overlap()'s keys plus n_points / n_non_finite, and overlap() of all
+    frames' kept points together."""
+    map_xyz = np.asarray(map_xyz, np.float32).reshape(-1, 3)
+    Tl = np.eye(4, dtype=np.float32) if T_lidar2body is None else T_lidar2body
+    rows, kept = [], []
+    for f, scan in enumerate(scans):
+        xyz = np.asarray(scan, np.float32).reshape(len(scan), 4)[:, :3]
+        with np.errstate(over="ignore", invalid="ignore"):
+            q = _xform(T_body2origin[f], _xform(Tl, xyz))
+        ok = np.isfinite(q).all(1)
+        kept.append(q[ok])
+        r = overlap(map_xyz, q[ok], voxelsize)
+        r.update(n_points=int(len(xyz)), n_non_finite=int((~ok).sum()))
+        rows.append(r)
+    allk = np.concatenate(kept) if kept else np.zeros((0, 3), np.float32)
+    return rows, overlap(map_xyz, allk, voxelsize)
 
 
 def _l2_simple(q, p):

@@ -341,6 +341,36 @@ int erasor_hip_overlap_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t 
 int erasor_hip_overlap_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device,
                            double voxel_leaf, double voxelsize, erasor_overlap_result *res);
 
+/* ---- every frame's pose against the map, before a run (the reference README's pitfalls 1, 3 and 5) ----------------------------
+ * replaces: transforming each scan on the host and running overlap_report (analysis_runner.py:53-71) on it, frame by frame.  Frame f is
+ * the scans' points [offsets[f], offsets[f + 1]) as given (no voxelisation, no range filter), put into the map frame as the reference
+ * puts its RViz query (OfflineMapUpdater.cpp:238-242): T_lidar2body, then T_body2origin[f], each in float32 with pcl::transformPointCloud's
+ * association ((a*x + b*y) + c*z) + d.  Points with a non-finite coordinate after the two transforms are dropped and counted; the row
+ * is the overlap report of the others against the map, bit for bit.  An empty frame, or one whose points were all dropped: n_est = 0,
+ * statistics NaN.  summary (optional): the overlap report of every frame's kept points together. */
+typedef struct erasor_align_row {
+    uint64_t n_points;        /* points of the frame as given */
+    uint64_t n_non_finite;    /* excluded: a non-finite coordinate after the two transforms */
+    erasor_overlap_result r;  /* overlap_report of the remaining points against the map (r.n_est = n_points - n_non_finite) */
+} erasor_align_row;
+
+/* The map (XYZI rows; the intensity is not read) and the concatenated scans, each on the host or on the handle's device (_is_device);
+ * offsets: host, n_frames + 1 entries, offsets[0] = 0 and offsets[n_frames] = n_scan_points; T_lidar2body: NULL for the identity (still
+ * applied as a transform); T_body2origin: host, n_frames row-major 4x4 matrices (the step's layout); rows: n_frames entries.  Works in
+ * the evaluator's own scratch: announced nodes, tickets and the last step's clouds stay as they are.
+ * ERASOR_E_INVALID: a non-finite pose entry or map point; offsets[0] != 0, decreasing offsets or a last offset other than n_scan_points;
+ * voxelsize <= 0; more than 2^30 scan or map points; more than 65536 frames; an empty map with a non-empty frame.
+ * ERASOR_E_STATE: a step in flight. */
+int erasor_hip_align_frames_clouds(erasor_hip_handle *h, const void *map_xyzi, size_t n_map, int map_is_device,
+                                   const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                                   int scans_are_device, const float T_lidar2body[16], const float *T_body2origin, double voxelsize,
+                                   erasor_align_row *rows, erasor_overlap_result *summary);
+/* the same against the handle's current map (the erasor_hip_get_map view, compacted on the device as erasor_hip_overlap_map does, never
+ * copied to the host).  ERASOR_E_STATE also: no map. */
+int erasor_hip_align_frames_map(erasor_hip_handle *h, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                                int scans_are_device, const float T_lidar2body[16], const float *T_body2origin, double voxelsize,
+                                erasor_align_row *rows, erasor_overlap_result *summary);
+
 /* ---- maps without labels: label a third-party map from a dense labelled one, and the static points a method lost ----------------
  * Both search the overlap report's tree in FLANN's metric, as pcl::KdTreeFLANN (K = 1) does: float32 d^2 = ((0 + dx*dx) + dy*dy) + dz*dz
  * with dx = q.x - p.x in float, exact, the lowest index on ties.  Outputs are XYZI rows in caller HOST buffers; dst == NULL asks for
