@@ -94,6 +94,39 @@ class ComplementResult(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class SweepRow(C.Structure):
+    """erasor_sweep_row (include/erasor_hip.h): one configuration of a sweep"""
+    _fields_ = [("params", Params), ("status", C.c_int32), ("n_steps", C.c_uint32), ("n_map_final", C.c_uint64), ("n_saved", C.c_uint64),
+                ("eval", EvalResult), ("run_ms", C.c_double), ("reserved_", C.c_uint32 * 8)]
+
+    def as_dict(self):
+        return {"params": params_dict(self.params), "status": int(self.status), "n_steps": int(self.n_steps),
+                "n_map_final": int(self.n_map_final), "n_saved": int(self.n_saved), "run_ms": float(self.run_ms), "eval": self.eval.as_dict()}
+
+
+def params_dict(p):
+    """the fields of a Params as a dict of field -> value (the reserved ones left out)"""
+    return {k: getattr(p, k) for k, _ in Params._fields_ if not k.startswith("reserved")}
+
+
+def param_grid(base, **axes):
+    """the Cartesian product of Params field lists, in keyword order, the last axis varying fastest: a list of copies of `base` with those
+    fields set.  param_grid(p, scan_ratio_threshold=[0.1, 0.2, 0.3], max_h=[2.8, 3.2]) gives six Params."""
+    import itertools
+    names = [f for f, _ in Params._fields_]
+    for k in axes:
+        if k not in names or k.startswith("reserved"):
+            raise ValueError("param_grid: %r is not a Params field" % k)
+    out = []
+    for combo in itertools.product(*[list(v) for v in axes.values()]):
+        p = Params()
+        C.memmove(C.byref(p), C.byref(base), C.sizeof(Params))
+        for k, v in zip(axes, combo):
+            setattr(p, k, v)
+        out.append(p)
+    return out
+
+
 class ClassRow(C.Structure):
     """erasor_eval_class_row (include/erasor_hip.h): one row of the breakdown by class or by dynamic instance"""
     _fields_ = [("key", C.c_uint32), ("is_dynamic", C.c_uint32)] + [(k, C.c_uint64) for k in (
@@ -476,6 +509,52 @@ class Erasor:
         r = EvalResult()
         self._check(lib().erasor_hip_evaluate_map(self._h, *g, C.c_double(voxel_leaf), C.c_double(voxelsize), C.byref(r)))
         return r.as_dict()
+
+    def evaluate_many(self, gt, ests, voxelsize=0.2, voxel_leaf=0.0):
+        """evaluate(gt, e, voxelsize, voxel_leaf) for every estimate e of `ests`, from one index of all of them and one query
+        (erasor_hip_evaluate_many).  Clouds as for evaluate.  Returns a list of evaluate's dicts, in the order of `ests`."""
+        kept = []
+        g = self._eval_cloud(gt, kept)
+        es = [self._eval_cloud(e, kept) for e in ests]
+        k = len(es)
+        P = (C.c_void_p * max(k, 1))(*[e[0] for e in es])
+        N = (C.c_size_t * max(k, 1))(*[e[1] for e in es])
+        D = (C.c_int * max(k, 1))(*[e[2] for e in es])
+        rows = (EvalResult * max(k, 1))()
+        self._check(lib().erasor_hip_evaluate_many(self._h, *g, P, N, D, C.c_size_t(k), C.c_double(voxel_leaf), C.c_double(voxelsize), rows))
+        return [rows[j].as_dict() for j in range(k)]
+
+    def sweep(self, configs, map, scans, T_lidar2body, T_body2origin, T_origin2body, gt, voxelsize=0.2, save_leaf=0.2, concurrency=2,
+              eval_batch=0):
+        """every Params of `configs` over one sequence, each saved map scored against `gt` (erasor_hip_sweep): the removal_interval gate,
+        the map after the last node voxelised at save_leaf, PR / RR with voxelsize.  map / gt: clouds as for evaluate; scans: a list of
+        (n, 4) host arrays, or (device pointer, offsets) as align_frames takes them; T_body2origin / T_origin2body: one 4x4 per node.
+        Returns one dict per configuration, in the order of `configs`: params (field -> value), status, n_steps, n_map_final, n_saved,
+        run_ms and eval (evaluate's dict)."""
+        kept = []
+        m = self._eval_cloud(map, kept)
+        g = self._eval_cloud(gt, kept)
+        if isinstance(scans, tuple):
+            ptr, offsets = scans
+            offs = np.ascontiguousarray(offsets, np.uint64)
+            q = (C.c_void_p(ptr), C.c_size_t(int(offs[-1]) if len(offs) else 0), 1)
+        else:
+            a = [_f32(s).reshape(-1, 4) for s in scans]
+            offs = np.zeros(len(a) + 1, np.uint64)
+            offs[1:] = np.cumsum([len(s) for s in a], dtype=np.uint64)
+            cat = _f32(np.concatenate(a) if a else np.zeros((0, 4), np.float32))
+            kept.append(cat)
+            q = (_p(cat), C.c_size_t(len(cat)), 0)
+        n = len(offs) - 1
+        Tb = _f32(np.asarray(T_body2origin, np.float32).reshape(n, 16) if n else np.zeros((1, 16), np.float32))
+        To = _f32(np.asarray(T_origin2body, np.float32).reshape(n, 16) if n else np.zeros((1, 16), np.float32))
+        Tl = _f32(T_lidar2body).reshape(16)
+        cfg = (Params * max(len(configs), 1))(*configs)
+        rows = (SweepRow * max(len(configs), 1))()
+        self._check(lib().erasor_hip_sweep(self._h, cfg, C.c_size_t(len(configs)), *m, q[0], q[1], _p(offs), C.c_size_t(n), C.c_int(q[2]),
+                                           _p(Tl), _p(Tb), _p(To), *g, C.c_double(save_leaf), C.c_double(voxelsize), C.c_int(concurrency),
+                                           C.c_int(eval_batch), rows))
+        return [rows[i].as_dict() for i in range(len(configs))]
 
     # -- PR / RR by class and by dynamic instance (the same on the host: evalmap.evaluate_by_class) --
     def _by_class(self, fn, args, voxel_leaf, voxelsize):

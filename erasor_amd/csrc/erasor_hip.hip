@@ -323,6 +323,11 @@ struct erasor_hip_handle {
         DBuf<Xf> al_xf;
         DBuf<unsigned long long> al_ctr, al_val;
         DBuf<AlRanks> al_rank;
+        // K estimates against one ground truth (erasor_hip_evaluate_many): the estimates back to back, their table, counters per estimate
+        // and one row for the ground truth (the combined bucket table and the bucketed points: cnt, pl, tops, bkt, pts, idx above)
+        DBuf<float4> em_cat;
+        DBuf<EvmEst> em_tab;
+        DBuf<unsigned long long> em_ctr;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
     // ---- per-bin scratch (R-GPF / bin voxelise global paths) ----
@@ -936,7 +941,7 @@ int erasor_hip_params_default(erasor_params *p) {
 
 static void worker_start(erasor_hip_handle *h);
 static void worker_stop(erasor_hip_handle *h);
-static bool create_sides(erasor_hip_handle *h, int prio) {
+static bool create_sides(erasor_hip_handle *h, int prio, int nqs_force) {
     // round 4: three query streams where the process has the hardware queues for them (main + 3 + copy = 5 streams; HIP's default is 4
     // queues): 233 k-point scans 0.291 -> 0.230 ms, 127 k-point scans the same either way; two otherwise
     if (const char *q = getenv("GPU_MAX_HW_QUEUES")) {
@@ -946,6 +951,7 @@ static bool create_sides(erasor_hip_handle *h, int prio) {
     // 3-8 x: main + 4 query streams 0.19 -> 0.26 ms per scan, main + early + 3: 0.34 --, so the steps that use the early stream keep their
     // chains to two of these, see enqueue_query_chain)
     if (const char *e = getenv("ERASOR_HIP_QSTREAMS")) h->nqs = std::max(1, std::min((int)erasor_hip_handle::NQS_MAX, atoi(e)));
+    if (nqs_force > 0) h->nqs = std::min((int)erasor_hip_handle::NQS_MAX, nqs_force);  // (the sweep's worker handles: one query stream)
     for (int k = 0; k < h->nqs; ++k)
         if (hipStreamCreateWithPriority(&h->qstream[k], hipStreamNonBlocking, prio) != hipSuccess) return false;
     for (int k = 0; k < NSIDE; ++k)
@@ -1005,7 +1011,8 @@ static void warn_hw_queues_once() {
             e ? e : "unset", e ? e : "HIP's default number of");
 }
 
-int erasor_hip_create(const erasor_params *p, int device, erasor_hip_handle **out) {
+// nqs_force > 0: that many query streams whatever ERASOR_HIP_QSTREAMS says (erasor_hip_sweep's worker handles)
+static int create_handle(const erasor_params *p, int device, int nqs_force, erasor_hip_handle **out) {
     if (!p || !out) return ERASOR_E_INVALID;
     *out = nullptr;
     if (p->num_rings <= 0 || p->num_sectors <= 0 || (int64_t)p->num_rings * p->num_sectors > 65000) return ERASOR_E_INVALID;
@@ -1028,7 +1035,7 @@ int erasor_hip_create(const erasor_params *p, int device, erasor_hip_handle **ou
     // one process a handle's low-priority query queues could land beside its always-busy main queue and starve (EXPERIMENTS, round 3).
     const int prio_lo = 0, prio_hi = 0;
     if (hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-        !create_sides(h, prio_lo) ||
+        !create_sides(h, prio_lo, nqs_force) ||
         hipHostMalloc((void **)&h->pin, sizeof(HostOut), hipHostMallocDefault) != hipSuccess) {
         delete h;
         return ERASOR_E_NO_DEVICE;
@@ -1044,6 +1051,8 @@ int erasor_hip_create(const erasor_params *p, int device, erasor_hip_handle **ou
     *out = h;
     return ERASOR_OK;
 }
+
+int erasor_hip_create(const erasor_params *p, int device, erasor_hip_handle **out) { return create_handle(p, device, 0, out); }
 
 void erasor_hip_destroy(erasor_hip_handle *h) {
     if (!h) return;
@@ -1089,6 +1098,7 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->ev.nn_ctr); release(h->ev.nn_dbits);
     release(h->ev.fm_out); release(h->ev.fm_flag); release(h->ev.fm_pl); release(h->ev.fm_tops); release(h->ev.fm_ctr);
     release(h->ev.al_off); release(h->ev.al_wg); release(h->ev.al_xf); release(h->ev.al_ctr); release(h->ev.al_val); release(h->ev.al_rank);
+    release(h->ev.em_cat); release(h->ev.em_tab); release(h->ev.em_ctr);
     for (int k = 0; k < NSIDE; ++k) {
         if (h->q[k].ev_keys) (void)hipEventDestroy(h->q[k].ev_keys);
         if (h->q[k].ev_done) (void)hipEventDestroy(h->q[k].ev_done);
@@ -3372,6 +3382,7 @@ static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t n
 // ---- PR / RR of a cleaned map against a labelled ground-truth map (scripts/analysis_runner.py:74-105; kernels: evaluate.hip.h) ----
 // Everything runs on the main stream, behind whatever a collected step launched ahead there, in the handle's own scratch (h->ev).
 // n_rec (the breakdown by class): the kernels also fill the per-key table E.bc_tab and the dynamic points' records; *n_rec = their count.
+static void ev_fill(const unsigned long long c[EV_NCTR], erasor_eval_result *res);
 static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize, uint8_t *per_gt,
                   erasor_eval_result *res, uint32_t *n_rec = nullptr) {
     auto &E = h->ev;
@@ -3423,6 +3434,12 @@ static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const f
         return ERASOR_E_INVALID;
     }
     if (per_gt && n_gt) HIPC(h, hipMemcpy(per_gt, E.code.p, n_gt, hipMemcpyDeviceToHost));
+    ev_fill(c, res);
+    return ERASOR_OK;
+}
+
+// erasor_eval_result from one evaluation's counters
+static void ev_fill(const unsigned long long c[EV_NCTR], erasor_eval_result *res) {
     erasor_eval_result r;
     memset(&r, 0, sizeof(r));
     r.gt_static = c[EV_GT_STATIC];
@@ -3439,7 +3456,6 @@ static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const f
     r.RR = r.gt_dynamic ? (double)(r.gt_dynamic - r.preserved_dynamic) / nd * 100.0 : 0.0;
     r.F1 = (r.PR + r.RR) > 0 ? 2 * (r.PR / 100) * (r.RR / 100) / ((r.PR / 100) + (r.RR / 100)) : 0.0;
     *res = r;
-    return ERASOR_OK;
 }
 
 // voxelize_preserving_labels of a device cloud at `leaf` (the save_static_map protocol, OMU.cpp:174-196) into dst (borrows a query side).
@@ -3548,6 +3564,155 @@ int erasor_hip_evaluate_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_
         e = h->ev.est.p;
     }
     return ev_run(h, g, ng, e, ne, voxelsize, nullptr, res);
+}
+
+// ---- K estimates against one ground truth (erasor_hip_evaluate_many; kernels: k_evm_* in evaluate.hip.h) ----
+// The callers copy the estimates back to back into E.em_cat.  Estimate j gets ev_run's bucket count for its size (a power of two >= n_j,
+// at least 1024) as its own range of one combined table: one histogram launch, one scan, one offsets launch, one scatter, one query.
+// Device memory, besides a host GT's copy (16 B a point): per estimated point the combined copy, its bucketed copy, its bucket and its
+// index (40 B); per bucket the counts and their scan (8 B, fewer than 2 buckets a point + 1024 per estimate): below 56 B per estimated
+// point + 8 KiB per estimate.  Like ev_run: the main stream, the evaluator's scratch.
+static int evm_run(erasor_hip_handle *h, const char *who, const float4 *gt, uint32_t n_gt, const uint32_t *n_est, size_t k, double voxelsize,
+                   erasor_eval_result *rows) {
+    auto &E = h->ev;
+    std::vector<EvmEst> tab(k + 1);
+    memset(tab.data(), 0, tab.size() * sizeof(EvmEst));
+    uint64_t n_all = 0, nb_all = 0, blk = 0;
+    for (size_t j = 0; j <= k; ++j) {
+        tab[j].off = (uint32_t)n_all;
+        tab[j].base = (uint32_t)nb_all;
+        tab[j].blk0 = (uint32_t)blk;
+        if (j == k) break;
+        uint32_t nb = 1024;
+        while (nb < n_est[j]) nb <<= 1;
+        tab[j].n = n_est[j];
+        tab[j].mask = nb - 1;
+        n_all += n_est[j];
+        nb_all += nb;
+        blk += cdiv(n_est[j], 256);
+    }
+    if (n_all > 0x7FFFFFFFull || nb_all > 0x7FFFFFFFull) {
+        h->err = std::string(who) + ": more than 2^31 estimated points or buckets in all";
+        return ERASOR_E_INVALID;
+    }
+    const uint32_t nb = (uint32_t)nb_all, n = (uint32_t)n_all;
+    if (ensure(h, E.em_tab, k + 1) || ensure(h, E.em_ctr, (k + 1) * EV_NCTR) || ensure(h, E.cnt, (size_t)nb + 1) || ensure(h, E.pl, (size_t)nb + 1) ||
+        ensure(h, E.tops, nb / 1024 + 4) || ensure(h, E.bkt, (size_t)n + 1) || ensure(h, E.pts, (size_t)n + 1) || ensure(h, E.idx, (size_t)n + 1))
+        return ERASOR_E_NO_DEVICE;
+    struct KeepCur {
+        erasor_hip_handle *h;
+        hipStream_t keep;
+        ~KeepCur() { h->cur = keep; }
+    } kc{h, h->cur};
+    h->cur = h->stream;
+    HIPC(h, hipMemcpyAsync(E.em_tab.p, tab.data(), (k + 1) * sizeof(EvmEst), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemsetAsync(E.em_ctr.p, 0, (k + 1) * EV_NCTR * sizeof(unsigned long long), h->stream));
+    const double thr = (voxelsize * sqrt(3.0)) / 2.0;  // (ev_run's)
+    if (n) {
+        HIPC(h, hipMemsetAsync(E.cnt.p, 0, ((size_t)nb + 1) * sizeof(uint32_t), h->stream));
+        LAUNCH(h, "evm_index", k_evm_hist, (uint32_t)blk, 256, (const float4 *)E.em_cat.p, (const EvmEst *)E.em_tab.p, (uint32_t)k, voxelsize, E.bkt.p,
+               E.cnt.p, E.em_ctr.p);
+        scan_u32(h, E.cnt.p, E.pl.p, E.tops.p, nb + 1, nb + 1, nullptr, nullptr, "evm_index");
+        LAUNCH(h, "evm_index", k_ev_offsets, cdiv(nb + 1, 256), 256, (const uint32_t *)E.pl.p, (const uint32_t *)E.tops.p, nb + 1, E.cnt.p, E.pl.p);
+        LAUNCH(h, "evm_index", k_ev_scatter, cdiv(n, 256), 256, (const float4 *)E.em_cat.p, n, (const uint32_t *)E.bkt.p, E.pl.p, E.pts.p, E.idx.p);
+    }
+    if (n_gt) {
+        // one estimate per blockIdx.y: workgroups are dispatched x fastest, so the estimates are searched one after the other, each
+        // against its own bucket table while that is cache-resident.  (All K in one lane's loop reads the GT once but walks K tables at
+        // a time: for 8 estimates of 9.8 M points against a 9.8 M-point GT that took 147 ms against 137 ms for 8 evaluate_clouds calls.)
+        const uint32_t gx = cdiv(n_gt, 256), per_y = 1, gy = (uint32_t)std::max<size_t>(k, 1);
+        LAUNCH(h, "evm_query", k_evm_query, dim3(gx, gy), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p, (const uint32_t *)E.cnt.p,
+               (const EvmEst *)E.em_tab.p, (uint32_t)k, per_y, voxelsize, thr, E.em_ctr.p);
+    }
+    std::vector<unsigned long long> c((k + 1) * EV_NCTR);
+    HIPC(h, hipMemcpyAsync(c.data(), E.em_ctr.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    const unsigned long long *cg = &c[k * EV_NCTR];
+    if (cg[EV_NON_FINITE]) {
+        h->err = std::string(who) + ": non-finite coordinate (NaN / Inf) in " + std::to_string(cg[EV_NON_FINITE]) + " point(s) of the ground truth";
+        return ERASOR_E_INVALID;
+    }
+    for (size_t j = 0; j < k; ++j)
+        if (c[j * EV_NCTR + EV_NON_FINITE]) {
+            h->err = std::string(who) + ": non-finite coordinate (NaN / Inf) in " + std::to_string(c[j * EV_NCTR + EV_NON_FINITE]) +
+                     " point(s) of estimate " + std::to_string(j);
+            return ERASOR_E_INVALID;
+        }
+    for (size_t j = 0; j < k; ++j) {
+        unsigned long long *cj = &c[j * EV_NCTR];
+        cj[EV_GT_STATIC] = cg[EV_GT_STATIC];
+        cj[EV_GT_DYNAMIC] = cg[EV_GT_DYNAMIC];
+        cj[EV_LABEL_OOR] += cg[EV_LABEL_OOR];
+        ev_fill(cj, &rows[j]);
+    }
+    return ERASOR_OK;
+}
+
+int erasor_hip_evaluate_many(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, const void *const *est_xyzi, const size_t *n_est,
+                             const int *est_is_device, size_t k, double voxel_leaf, double voxelsize, erasor_eval_result *rows) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_evaluate_many";
+    erasor_eval_result unused;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, false, k ? rows : &unused);
+    if (rc) return rc;
+    if (k && (!est_xyzi || !n_est)) {
+        h->err = std::string(who) + ": est_xyzi or n_est is NULL";
+        return ERASOR_E_INVALID;
+    }
+    if ((!gt_xyzi && n_gt) || n_gt > 0x3FFFFFFFull) {
+        h->err = std::string(who) + ": NULL ground truth or more than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    uint64_t total = 0;
+    for (size_t j = 0; j < k; ++j) {
+        if ((!est_xyzi[j] && n_est[j]) || n_est[j] > 0x3FFFFFFFull) {
+            h->err = std::string(who) + ": estimate " + std::to_string(j) + ": NULL cloud or more than 2^30 points";
+            return ERASOR_E_INVALID;
+        }
+        total += n_est[j];
+    }
+    if (total > 0x7FFFFFFFull) {
+        h->err = std::string(who) + ": more than 2^31 estimated points in all";
+        return ERASOR_E_INVALID;
+    }
+    if (!k) return ERASOR_OK;
+    HIPC(h, hipSetDevice(h->device));
+    auto &E = h->ev;
+    const float4 *g = nullptr;
+    if ((rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, E.gt, &g))) return rc;
+    uint32_t ng = (uint32_t)n_gt;
+    if (voxel_leaf > 0) {
+        if ((rc = ev_voxelize(h, g, ng, voxel_leaf, E.gt, &ng))) return rc;
+        g = E.gt.p;
+    }
+    // every estimate into the combined array (voxelised first with voxel_leaf > 0: never more points than given)
+    if (ensure(h, E.em_cat, total + 1)) return ERASOR_E_NO_DEVICE;
+    std::vector<uint32_t> ne(k, 0);
+    uint64_t off = 0;
+    for (size_t j = 0; j < k; ++j) {
+        const uint32_t n = (uint32_t)n_est[j];
+        const bool dev = est_is_device && est_is_device[j];
+        if (!n) continue;
+        if (voxel_leaf > 0) {
+            const float4 *e = nullptr;
+            uint32_t nq = 0;
+            if ((rc = ev_input(h, est_xyzi[j], n, dev, E.est, &e)) || (rc = voxelize_device(h, e, n, voxel_leaf, &nq))) {
+                h->err = std::string(who) + ": estimate " + std::to_string(j) + ": " + h->err;
+                return rc;
+            }
+            if (nq) HIPC(h, hipMemcpyAsync(E.em_cat.p + off, Q(h).query.p, (size_t)nq * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
+            HIPC(h, hipStreamSynchronize(h->stream));
+            ne[j] = nq;
+        } else {
+            HIPC(h, hipMemcpyAsync(E.em_cat.p + off, est_xyzi[j], (size_t)n * sizeof(float4), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                   h->stream));
+            ne[j] = n;
+        }
+        off += ne[j];
+    }
+    HIPC(h, hipStreamSynchronize(h->stream));
+    return evm_run(h, who, g, ng, ne.data(), k, voxelsize, rows);
 }
 
 // ---- the estimate-to-GT overlap report (scripts/analysis_runner.py:53-71, overlap_report; kernels: nearest.hip.h) ----
@@ -4946,3 +5111,270 @@ int erasor_hip_radix_sort_u32(erasor_hip_handle *h, const uint32_t *keys, size_t
 #endif  // ERASOR_HIP_TEST_HOOKS
 
 }  // extern "C"
+
+// ---- a parameter sweep: every configuration over one sequence, each one's saved map scored by PR / RR (erasor_hip_sweep) ----
+// What the shim's OfflineMapUpdater + save_static_map + evaluate_saved_map do for one configuration (demo_main.cpp --config <yaml> n
+// <gt>): node j (0-based) is stepped iff (j + 1) % removal_interval == 0 (OMU.cpp:206-209), the map after the last node is voxelised by
+// voxelize_preserving_labels at save_leaf (main_in_your_env.cpp:123), and that map is evaluated against the GT as given.  The map, the
+// scans and the GT go to the device once.  Configurations run in waves of worker handles on the caller's device, one host thread each,
+// every worker with ONE query stream (two such handles keep the device's four compute pipes busy, DESIGN "Several handles on one GPU");
+// a worker takes its map from the shared copy, steps the shared scans in place, voxelises its final map into a buffer of the sweep's and is
+// destroyed before the next wave.  Then the saved maps are scored in groups by evm_run, in the caller handle's evaluator scratch.
+namespace {
+constexpr int SWEEP_LOOKAHEAD = 6;  // nodes announced ahead by a worker (the offline driver's default)
+struct SweepIn {
+    int device = 0;
+    const float4 *map = nullptr;
+    size_t n_map = 0;
+    const float4 *scans = nullptr;
+    const uint64_t *offsets = nullptr;
+    size_t n_nodes = 0;
+    const float *Tl = nullptr, *Tb = nullptr, *To = nullptr;
+    double save_leaf = 0;
+};
+struct SweepJob {
+    erasor_params p;
+    int status = ERASOR_OK;
+    uint32_t n_steps = 0;
+    uint64_t n_map_final = 0;
+    float4 *saved = nullptr;  // the saved map (hipMalloc of the sweep's), n_saved points
+    uint32_t n_saved = 0;
+    double run_ms = 0;
+};
+
+// a worker handle's device memory for a map of n_map points and scans of at most max_scan points: per slot of alloc_map's capacity the
+// map-sized scratch, the outskirts store and both F buffers, per scan point the query sides, plus the saved map; rounded up (a handle
+// with a 9.8 M-point map took 5.49 GB after four steps of 245 k-point scans, this gives 5.6 GB)
+uint64_t sweep_need(size_t n_map, uint64_t max_scan) {
+    const uint64_t cap = (uint64_t)n_map + std::max<uint64_t>(n_map / 4, 1u << 20);
+    return cap * 420 + max_scan * 8 * 96 + (uint64_t)n_map * 24 + (64ull << 20);
+}
+
+void sweep_one(const SweepIn &in, SweepJob &J) {
+    if (hipSetDevice(in.device) != hipSuccess) {
+        J.status = ERASOR_E_NO_DEVICE;
+        return;
+    }
+    const int ri = J.p.removal_interval;
+    if (ri < 1) {  // (the shim takes stack_count % removal_interval)
+        J.status = ERASOR_E_INVALID;
+        return;
+    }
+    std::vector<const void *> ptrs;
+    std::vector<size_t> np;
+    std::vector<float> Tb, To;
+    for (size_t j = 0; j < in.n_nodes; ++j) {
+        if ((j + 1) % (size_t)ri != 0) continue;  // OMU.cpp:206-209
+        ptrs.push_back(in.scans + in.offsets[j]);
+        np.push_back((size_t)(in.offsets[j + 1] - in.offsets[j]));
+        Tb.insert(Tb.end(), in.Tb + 16 * j, in.Tb + 16 * j + 16);
+        To.insert(To.end(), in.To + 16 * j, in.To + 16 * j + 16);
+    }
+    J.n_steps = (uint32_t)ptrs.size();
+    erasor_hip_handle *h = nullptr;
+    int rc = create_handle(&J.p, in.device, 1, &h);
+    if (rc) {
+        J.status = rc;
+        return;
+    }
+    rc = erasor_hip_set_map_device(h, in.map, in.n_map);
+    if (!rc && !ptrs.empty()) {
+        size_t announced = 0;
+        const auto t0 = std::chrono::steady_clock::now();
+        rc = erasor_hip_run_nodes(h, ptrs.data(), np.data(), ptrs.size(), 1, in.Tl, Tb.data(), To.data(), 0, ptrs.size(), SWEEP_LOOKAHEAD, &announced,
+                                  nullptr);
+        J.run_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    size_t n_final = 0;
+    if (!rc) rc = map_to_device(h, h->ev.map, &n_final);
+    if (!rc && n_final > 0x3FFFFFFFull) rc = ERASOR_E_CAPACITY;
+    uint32_t nq = (uint32_t)n_final;
+    const float4 *src = h->ev.map.p;
+    if (!rc && in.save_leaf > 0 && n_final) {
+        rc = voxelize_device(h, h->ev.map.p, (uint32_t)n_final, in.save_leaf, &nq);
+        src = Q(h).query.p;
+    }
+    if (!rc) {
+        J.n_map_final = n_final;
+        if (hipMalloc((void **)&J.saved, ((size_t)nq + 1) * sizeof(float4)) != hipSuccess) {
+            J.saved = nullptr;
+            rc = ERASOR_E_NO_DEVICE;
+        } else if ((nq && hipMemcpyAsync(J.saved, src, (size_t)nq * sizeof(float4), hipMemcpyDeviceToDevice, h->stream) != hipSuccess) ||
+                   hipStreamSynchronize(h->stream) != hipSuccess) {
+            rc = ERASOR_E_NO_DEVICE;
+        }
+        J.n_saved = nq;
+    }
+    J.status = rc;
+    erasor_hip_destroy(h);
+}
+
+// hipMemGetInfo, looked up at run time in the library that provides the HIP runtime: a runtime that does not export it gets no memory
+// check (every wave is then `concurrency` wide)
+using MemInfoFn = hipError_t (*)(size_t *, size_t *);
+MemInfoFn mem_info_fn() {
+    static const MemInfoFn fn = [] {
+        Dl_info info;
+        if (!dladdr((void *)&hipGetDeviceCount, &info) || !info.dli_fname) return (MemInfoFn) nullptr;
+        void *lib = dlopen(info.dli_fname, RTLD_LAZY | RTLD_NOLOAD);
+        return lib ? (MemInfoFn)dlsym(lib, "hipMemGetInfo") : (MemInfoFn) nullptr;
+    }();
+    return fn;
+}
+
+// a sweep-owned device buffer (freed on every return)
+struct SweepBuf {
+    void *p = nullptr;
+    ~SweepBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+}  // namespace
+
+int erasor_hip_sweep(erasor_hip_handle *h, const erasor_params *configs, size_t n_configs, const void *map_xyzi, size_t n_map, int map_is_device,
+                     const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_nodes, int scans_are_device,
+                     const float T_lidar2body[16], const float *T_body2origin, const float *T_origin2body, const void *gt_xyzi, size_t n_gt,
+                     int gt_is_device, double save_leaf, double voxelsize, int concurrency, int eval_batch, erasor_sweep_row *rows) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_sweep";
+    auto fail = [&](const std::string &why) {
+        h->err = std::string(who) + ": " + why;
+        return ERASOR_E_INVALID;
+    };
+    if (n_configs > 256) return fail("more than 256 configurations");
+    if (n_configs && (!configs || !rows)) return fail("configs or rows is NULL");
+    if (concurrency < 1 || concurrency > 4) return fail("concurrency must be 1..4");
+    if (eval_batch < 0) return fail("eval_batch must be >= 0");
+    if (!(voxelsize > 0) || !std::isfinite(voxelsize)) return fail("voxelsize must be a finite number > 0");
+    if (!(save_leaf >= 0) || !std::isfinite(save_leaf)) return fail("save_leaf must be 0 or a finite number > 0");
+    if ((!map_xyzi && n_map) || n_map > 0x3FFFFFFFull) return fail("NULL map or more than 2^30 map points");
+    if ((!gt_xyzi && n_gt) || n_gt > 0x3FFFFFFFull) return fail("NULL ground truth or more than 2^30 points");
+    if (!offsets) return fail("offsets is NULL (n_nodes + 1 entries)");
+    if (n_scan_points > 0x3FFFFFFFull) return fail("more than 2^30 scan points");
+    if (!scans_xyzi && n_scan_points) return fail("NULL scans");
+    if (offsets[0] != 0) return fail("offsets[0] must be 0");
+    for (size_t f = 0; f < n_nodes; ++f)
+        if (offsets[f + 1] < offsets[f]) return fail("offsets decrease");
+    if (offsets[n_nodes] != n_scan_points) return fail("the last offset is not the scans' point count");
+    if (!T_lidar2body || (n_nodes && (!T_body2origin || !T_origin2body))) return fail("a pose array is NULL");
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(T_lidar2body[k])) return fail("non-finite entry in T_lidar2body");
+    for (size_t k = 0; k < n_nodes * 16; ++k)
+        if (!std::isfinite(T_body2origin[k]) || !std::isfinite(T_origin2body[k])) return fail("non-finite entry in T_body2origin or T_origin2body");
+    HIPC(h, hipSetDevice(h->device));
+    // the shared inputs, on the device once
+    SweepBuf b_map, b_scans, b_gt;
+    auto upload = [&](const void *src, size_t n, int is_device, SweepBuf &b, const float4 **out) -> int {
+        *out = (const float4 *)src;
+        if (is_device || !n) return ERASOR_OK;
+        HIPC(h, hipMalloc(&b.p, n * sizeof(float4)));
+        HIPC(h, hipMemcpyAsync(b.p, src, n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
+        *out = (const float4 *)b.p;
+        return ERASOR_OK;
+    };
+    SweepIn in;
+    in.device = h->device;
+    const float4 *d_gt = nullptr;
+    int rc = 0;
+    if ((rc = upload(map_xyzi, n_map, map_is_device, b_map, &in.map)) || (rc = upload(scans_xyzi, n_scan_points, scans_are_device, b_scans, &in.scans)) ||
+        (rc = upload(gt_xyzi, n_gt, gt_is_device, b_gt, &d_gt)))
+        return rc;
+    // non-finite map / GT points: the GT side of evm_run with no estimate counts them
+    for (int c = 0; c < 2; ++c) {
+        const float4 *cl = c ? d_gt : in.map;
+        const size_t n = c ? n_gt : n_map;
+        if (!n) continue;
+        if ((rc = evm_run(h, who, cl, (uint32_t)n, nullptr, 0, voxelsize, nullptr))) {
+            if (rc == ERASOR_E_INVALID) h->err = std::string(who) + ": non-finite coordinate (NaN / Inf) in the " + (c ? "ground truth" : "map");
+            return rc;
+        }
+    }
+    in.n_map = n_map;
+    in.offsets = offsets;
+    in.n_nodes = n_nodes;
+    in.Tl = T_lidar2body;
+    in.Tb = T_body2origin;
+    in.To = T_origin2body;
+    in.save_leaf = save_leaf;
+    uint64_t max_scan = 0;
+    for (size_t f = 0; f < n_nodes; ++f) max_scan = std::max<uint64_t>(max_scan, offsets[f + 1] - offsets[f]);
+    std::vector<SweepJob> jobs(n_configs);
+    for (size_t i = 0; i < n_configs; ++i) jobs[i].p = configs[i];
+    struct FreeSaved {
+        std::vector<SweepJob> &jobs;
+        ~FreeSaved() {
+            for (auto &J : jobs)
+                if (J.saved) (void)hipFree(J.saved);
+        }
+    } free_saved{jobs};
+    // waves of `concurrency` workers, as many as the free device memory takes (at least one, else that configuration fails on its own)
+    const MemInfoFn mem_info = mem_info_fn();
+    const uint64_t need = sweep_need(n_map, max_scan);
+    for (size_t next = 0; next < n_configs;) {
+        size_t free_b = ~(size_t)0, total_b = 0;
+        if (mem_info) HIPC(h, mem_info(&free_b, &total_b));
+        std::vector<size_t> wave;
+        uint64_t budget = free_b;
+        while (next < n_configs && (int)wave.size() < concurrency && need <= budget) {
+            budget -= need;
+            wave.push_back(next++);
+        }
+        if (wave.empty()) {
+            jobs[next++].status = ERASOR_E_NO_DEVICE;
+            continue;
+        }
+        std::vector<std::thread> th;
+        for (size_t i : wave) th.emplace_back(sweep_one, std::cref(in), std::ref(jobs[i]));
+        for (auto &t : th) t.join();
+    }
+    HIPC(h, hipSetDevice(h->device));
+    // the saved maps against the GT, in groups of eval_batch (0: all), each group one evm_run
+    std::vector<size_t> ok;
+    for (size_t i = 0; i < n_configs; ++i)
+        if (jobs[i].status == ERASOR_OK) ok.push_back(i);
+    std::vector<erasor_eval_result> ev(n_configs);
+    memset(ev.data(), 0, ev.size() * sizeof(erasor_eval_result));
+    auto &E = h->ev;
+    for (size_t b = 0; b < ok.size();) {
+        std::vector<size_t> grp;
+        uint64_t total = 0;
+        while (b < ok.size() && (eval_batch == 0 || (int)grp.size() < eval_batch) &&
+               (grp.empty() || total + jobs[ok[b]].n_saved <= 0x7FFFFFFFull)) {
+            total += jobs[ok[b]].n_saved;
+            grp.push_back(ok[b++]);
+        }
+        int grc = ensure(h, E.em_cat, total + 1) ? ERASOR_E_NO_DEVICE : ERASOR_OK;
+        std::vector<uint32_t> ne;
+        uint64_t off = 0;
+        for (size_t i : grp) {
+            if (!grc && jobs[i].n_saved &&
+                hipMemcpyAsync(E.em_cat.p + off, jobs[i].saved, (size_t)jobs[i].n_saved * sizeof(float4), hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
+                grc = ERASOR_E_NO_DEVICE;
+            ne.push_back(jobs[i].n_saved);
+            off += jobs[i].n_saved;
+        }
+        if (!grc && hipStreamSynchronize(h->stream) != hipSuccess) grc = ERASOR_E_NO_DEVICE;
+        std::vector<erasor_eval_result> r(grp.size());
+        if (!grc) grc = evm_run(h, who, d_gt, (uint32_t)n_gt, ne.data(), grp.size(), voxelsize, r.data());
+        for (size_t q = 0; q < grp.size(); ++q) {
+            if (grc) jobs[grp[q]].status = grc;
+            else ev[grp[q]] = r[q];
+        }
+    }
+    for (size_t i = 0; i < n_configs; ++i) {
+        erasor_sweep_row &R = rows[i];
+        memset(&R, 0, sizeof(R));
+        R.params = configs[i];
+        R.status = jobs[i].status;
+        R.n_steps = jobs[i].n_steps;
+        if (jobs[i].status == ERASOR_OK) {
+            R.n_map_final = jobs[i].n_map_final;
+            R.n_saved = jobs[i].n_saved;
+            R.eval = ev[i];
+        }
+        R.run_ms = jobs[i].run_ms;
+    }
+    return ERASOR_OK;
+}

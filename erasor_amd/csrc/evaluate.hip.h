@@ -367,6 +367,134 @@ __global__ __launch_bounds__(256) void k_ev_inst_rows(const uint32_t *__restrict
     ev_add_rows(rows + 1, EV_ROW, r, j < n, bits, 32);
 }
 
+// ---- K estimates against one ground truth in one set of launches (erasor_hip_evaluate_many) ----
+// The estimates lie back to back in one array.  Estimate j owns the bucket range [base, base + mask] of one combined table; its buckets
+// are k_ev_hist's (a power of two >= its size, at least 1024), so with the combined offsets `off + base` it is searched exactly as
+// k_ev_query searches a table of its own.  k_ev_offsets and k_ev_scatter build the combined table unchanged; the scatter stores the
+// combined index off_j + i, which orders the points of one estimate as their own index i does.
+struct EvmEst {
+    uint32_t off;   // first point of the estimate in the combined array
+    uint32_t n;     // its points
+    uint32_t base;  // first bucket of its range
+    uint32_t mask;  // its bucket count - 1
+    uint32_t blk0;  // first workgroup of k_evm_hist on it (entry k, after the last estimate: the grid)
+    uint32_t pad_[3];
+};
+
+// (1) every estimate's buckets and their histogram, one workgroup never straddling two estimates; estimate counters per estimate in
+// ctr[j * EV_NCTR ..].  cnt: [buckets + 1], zeroed by the host.
+__global__ __launch_bounds__(256) void k_evm_hist(const float4 *__restrict__ est, const EvmEst *__restrict__ tab, uint32_t k, double cell,
+                                                   uint32_t *__restrict__ bucket_of, uint32_t *__restrict__ cnt, unsigned long long *__restrict__ ctr) {
+    uint32_t lo = 0, hi = k;  // the block's estimate: the last j with blk0_j <= blockIdx.x (empty estimates share the next one's blk0)
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (tab[mid].blk0 <= blockIdx.x) lo = mid;
+        else hi = mid;
+    }
+    const EvmEst e = tab[lo];
+    const uint32_t i = (blockIdx.x - e.blk0) * blockDim.x + threadIdx.x;
+    uint32_t dyn = 0, sta = 0, oor = 0, bad = 0;
+    if (i < e.n) {
+        const float4 p = est[e.off + i];
+        bad = ev_finite(p) ? 0u : 1u;
+        const uint32_t b = e.base + ev_bucket(ev_cell(p.x, cell), ev_cell(p.y, cell), ev_cell(p.z, cell), e.mask);
+        bucket_of[e.off + i] = b;
+        atomicAdd(&cnt[b], 1u);
+        if (ev_is_dynamic(p.w, oor)) dyn = 1; else sta = 1;
+    }
+    unsigned long long *c = ctr + (size_t)lo * EV_NCTR;
+    ev_commit(c, EV_EST_DYNAMIC, dyn);
+    ev_commit(c, EV_EST_STATIC, sta);
+    ev_commit(c, EV_LABEL_OOR, oor);
+    ev_commit(c, EV_NON_FINITE, bad);
+}
+
+// ev_nearest with the GT point's cell given (computed once for all estimates)
+__device__ __forceinline__ void evm_nearest(const float4 &g, int32_t cx, int32_t cy, int32_t cz, const float4 *pts, const uint32_t *idx, const uint32_t *off,
+                                            uint32_t mask, double &best, uint32_t &best_i, bool &best_dyn, bool &at_min_s, bool &at_min_d) {
+    const double gx = (double)g.x, gy = (double)g.y, gz = (double)g.z;
+    for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) {
+                const uint32_t b = ev_bucket(cx + dx, cy + dy, cz + dz, mask);
+                const uint32_t e = off[b + 1];
+                for (uint32_t s = off[b]; s < e; ++s) {
+                    const float4 p = pts[s];
+                    const double ex = gx - (double)p.x, ey = gy - (double)p.y, ez = gz - (double)p.z;
+                    const double d2 = (ex * ex + ey * ey) + ez * ez;
+                    if (!(d2 <= best)) continue;  // (NaN never wins)
+                    uint32_t o_ = 0;
+                    const bool e_dyn = ev_is_dynamic(p.w, o_);
+                    const uint32_t j = idx[s];
+                    if (d2 < best) {
+                        best = d2;
+                        best_i = j;
+                        best_dyn = e_dyn;
+                        at_min_s = !e_dyn;
+                        at_min_d = e_dyn;
+                    } else {
+                        if (j < best_i) {
+                            best_i = j;
+                            best_dyn = e_dyn;
+                        }
+                        at_min_s = at_min_s || !e_dyn;
+                        at_min_d = at_min_d || e_dyn;
+                    }
+                }
+            }
+}
+
+// (2) one GT point per lane, read and placed in its cell once, then k_ev_query's decision against estimates
+// [blockIdx.y * per_y, + per_y) one after the other (the host launches per_y = 1, see evm_run).  Kept / tied counters in ctr[j * EV_NCTR ..]; the GT's own counters (classes,
+// labels out of range, non-finite points) once, by the blocks of blockIdx.y == 0, in row k.
+__global__ __launch_bounds__(256) void k_evm_query(const float4 *__restrict__ gt, uint32_t n_gt, const float4 *__restrict__ pts,
+                                                    const uint32_t *__restrict__ idx, const uint32_t *__restrict__ off, const EvmEst *__restrict__ tab,
+                                                    uint32_t k, uint32_t per_y, double cell, double thr, unsigned long long *__restrict__ ctr) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < n_gt;
+    uint32_t gs = 0, gd = 0, oor = 0, bad = 0;
+    bool g_dyn = false;
+    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+    int32_t cx = 0, cy = 0, cz = 0;
+    if (live) {
+        g = gt[i];
+        bad = ev_finite(g) ? 0u : 1u;
+        g_dyn = ev_is_dynamic(g.w, oor);
+        gd = g_dyn ? 1u : 0u;
+        gs = 1u - gd;
+        cx = ev_cell(g.x, cell);
+        cy = ev_cell(g.y, cell);
+        cz = ev_cell(g.z, cell);
+    }
+    if (blockIdx.y == 0) {
+        unsigned long long *c = ctr + (size_t)k * EV_NCTR;
+        ev_commit(c, EV_GT_STATIC, gs);
+        ev_commit(c, EV_GT_DYNAMIC, gd);
+        ev_commit(c, EV_LABEL_OOR, oor);
+        ev_commit(c, EV_NON_FINITE, bad);
+    }
+    const uint32_t j0 = blockIdx.y * per_y, j1 = min(k, j0 + per_y);
+    for (uint32_t j = j0; j < j1; ++j) {
+        const EvmEst e = tab[j];
+        uint32_t ks = 0, kd = 0, tied = 0;
+        if (live && e.n) {
+            double best = __builtin_huge_val();
+            uint32_t best_i = 0xFFFFFFFFu;
+            bool best_dyn = false, at_min_s = false, at_min_d = false;
+            evm_nearest(g, cx, cy, cz, pts, idx, off + e.base, e.mask, best, best_i, best_dyn, at_min_s, at_min_d);
+            if (best_i != 0xFFFFFFFFu && sqrt(best) < thr) {
+                if (!g_dyn && !best_dyn) ks = 1;
+                else if (g_dyn && best_dyn) kd = 1;
+                tied = (at_min_s && at_min_d) ? 1u : 0u;
+            }
+        }
+        unsigned long long *c = ctr + (size_t)j * EV_NCTR;
+        ev_commit(c, EV_KEPT_STATIC, ks);
+        ev_commit(c, EV_KEPT_DYNAMIC, kd);
+        ev_commit(c, EV_TIED, tied);
+    }
+}
+
 }  // namespace ek
 
 #endif  // ERASOR_EVALUATE_HIP_H

@@ -2,6 +2,7 @@
 //   <dir>/map.pcd, <dir>/pcds/%06d.pcd, <dir>/poses.csv (header line; idx,?,x,y,z,qx,qy,qz,qw per line, cols 2..8)
 // processes every node through erasor::OfflineMapUpdater and writes <dir>/<data_name>_result.pcd and map_final.pcd.
 #include <cstdlib>
+#include <algorithm>
 #include <array>
 #include <chrono>
 #include <cstdio>
@@ -343,6 +344,51 @@ static int complement_mode(int argc, char **argv) {
     printf("saved %s\n", argv[4]);
     return 0;
 }
+// --eval-many <voxelsize> <voxel_leaf> <gt> <est1> [<est2> ...]: --eval's row for every estimate against one ground truth, from ONE
+// erasor_hip_evaluate_many call (compare_map.cpp's use: several methods' maps against one GT)
+static int eval_many_mode(int argc, char **argv) {
+    if (argc < 6) return 2;
+    const double voxelsize = atof(argv[2]), voxel_leaf = atof(argv[3]);
+    std::vector<float> gt;
+    if (!load_cloud_xyzi(argv[4], gt)) {
+        fprintf(stderr, "cannot read %s\n", argv[4]);
+        return 3;
+    }
+    const int k = argc - 5;
+    std::vector<std::vector<float>> est(k);
+    std::vector<const void *> ptr(k);
+    std::vector<size_t> n(k);
+    for (int j = 0; j < k; ++j) {
+        if (!load_cloud_xyzi(argv[5 + j], est[j])) {
+            fprintf(stderr, "cannot read %s\n", argv[5 + j]);
+            return 3;
+        }
+        ptr[j] = est[j].data();
+        n[j] = est[j].size() / 4;
+    }
+    erasor_params p;
+    erasor_hip_params_default(&p);
+    erasor_hip_handle *h = nullptr;
+    if (erasor_hip_create(&p, 0, &h) != ERASOR_OK) {
+        fprintf(stderr, "erasor_hip_create failed\n");
+        return 1;
+    }
+    std::vector<erasor_eval_result> rows(k);
+    const int rc = erasor_hip_evaluate_many(h, gt.data(), gt.size() / 4, 0, ptr.data(), n.data(), nullptr, k, voxel_leaf, voxelsize, rows.data());
+    if (rc) {
+        fprintf(stderr, "evaluate_many: %s (rc %d)\n", erasor_hip_last_error(h), rc);
+        erasor_hip_destroy(h);
+        return 1;
+    }
+    printf("GT : %s\n", argv[4]);
+    for (int j = 0; j < k; ++j) {
+        printf("Est: %s\n", argv[5 + j]);
+        print_eval_row(rows[j]);
+    }
+    erasor_hip_destroy(h);
+    return 0;
+}
+
 // PR / RR of the map save_static_map(0.2) writes (voxelize_preserving_labels of map_arranged_) against a ground-truth file
 static int evaluate_saved_map(erasor::OfflineMapUpdater &updater, const std::string &gt_path) {
     std::vector<float> gt;
@@ -460,6 +506,152 @@ static int run_config(const std::string &yaml, int max_frames, int device, bool 
 static int config_mode(int argc, char **argv) {
     if (argc < 3) return 2;
     return run_config(argv[2], argc > 3 ? atoi(argv[3]) : 1 << 30, 0, true, nullptr, argc > 4 ? argv[4] : "");
+}
+
+// --sweep <rosparam.yaml> <grid.yaml> <gt> [n_frames] [voxelsize = 0.2] [concurrency = 2]: every configuration of the grid (the base
+// file with the grid's scalars and one value of every axis, erasor::expand_sweep_grid) over the sequence --config reads, each one's saved
+// map (save_static_map(0.2), main_in_your_env.cpp:123) scored against gt, from ONE erasor_hip_sweep call.  The map, the scans and the
+// poses are read as --config reads them, and the poses take callback_node's way (eigen2geoPose -> node.odom -> geoPose2eigen, and its
+// inverse), so every configuration steps with the matrices the shim steps with.  One row per configuration, the swept values in front,
+// sorted by F1 (highest first, ties in grid order), then the best configuration as rosparam lines.
+static int sweep_mode(int argc, char **argv) {
+    if (argc < 5) return 2;
+    const int max_frames = argc > 5 ? atoi(argv[5]) : 1 << 30;
+    const double voxelsize = argc > 6 ? atof(argv[6]) : 0.2;
+    const int concurrency = argc > 7 ? atoi(argv[7]) : 2;
+    erasor::SweepGrid grid;
+    erasor::DriverConfig drv;
+    std::string bad;
+    const int grc = erasor::expand_sweep_grid(argv[2], argv[3], 256, grid, &drv, &bad);
+    if (grc == -2) {
+        fprintf(stderr, "%s: key %s cannot be swept (allowed: the /erasor/* parameters, /MapUpdater/query_voxel_size, "
+                        "/MapUpdater/removal_interval, /large_scale/*)\n", argv[3], bad.c_str());
+        return 2;
+    }
+    if (grc == -3) {
+        fprintf(stderr, "%s: more than 256 configurations\n", argv[3]);
+        return 2;
+    }
+    if (grc) {
+        fprintf(stderr, "cannot read %s or %s\n", argv[2], argv[3]);
+        return 3;
+    }
+    erasor::OfflineMapUpdater::Config &cfg = grid.base;
+    if (cfg.environment != "outdoor") {  // (OfflineMapUpdater: OMU.cpp:149, 312)
+        fprintf(stderr, "env %s: only outdoor is supported\n", cfg.environment.c_str());
+        return 1;
+    }
+    if (cfg.initial_map_path.empty() || cfg.initial_map_path == "/") cfg.initial_map_path = drv.data_dir + "/dense_global_map.pcd";
+    std::vector<Eigen::Matrix4f> poses;
+    if (!erasor::load_all_poses(drv.data_dir + "/poses_lidar2body.csv", poses)) {
+        fprintf(stderr, "cannot read %s/poses_lidar2body.csv\n", drv.data_dir.c_str());
+        return 3;
+    }
+    std::vector<float> map, gt, scans, Tb, To;
+    if (!load_cloud_xyzi(cfg.initial_map_path, map) || !load_cloud_xyzi(argv[4], gt)) {
+        fprintf(stderr, "cannot read %s or %s\n", cfg.initial_map_path.c_str(), argv[4]);
+        return 3;
+    }
+    std::vector<uint64_t> offsets{0};
+    const int last = std::min((int)poses.size(), drv.init_idx + max_frames);
+    for (int i = drv.init_idx; i < last; ++i) {  // (run_config stops at the first scan it cannot read)
+        char name[64];
+        snprintf(name, sizeof(name), "/pcds/%06d.pcd", i);
+        std::vector<float> scan;
+        if (!load_cloud_xyzi(drv.data_dir + name, scan)) break;
+        scans.insert(scans.end(), scan.begin(), scan.end());
+        offsets.push_back(scans.size() / 4);
+        const Eigen::Matrix4f T = erasor_utils::geoPose2eigen(erasor_utils::eigen2geoPose(poses[i]));  // (callback_node, OMU.cpp:219)
+        const Eigen::Matrix4f Ti = erasor_utils::inverse(T);                                            // (OMU.cpp:436)
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) {
+                Tb.push_back(T(r, c));
+                To.push_back(Ti(r, c));
+            }
+    }
+    const size_t n_nodes = offsets.size() - 1;
+    if (!n_nodes) {
+        fprintf(stderr, "no scan under %s/pcds\n", drv.data_dir.c_str());
+        return 3;
+    }
+    geometry_msgs::Pose l2b;
+    l2b.position.x = cfg.lidar2body[0];
+    l2b.position.y = cfg.lidar2body[1];
+    l2b.position.z = cfg.lidar2body[2];
+    l2b.orientation.x = cfg.lidar2body[3];
+    l2b.orientation.y = cfg.lidar2body[4];
+    l2b.orientation.z = cfg.lidar2body[5];
+    l2b.orientation.w = cfg.lidar2body[6];
+    const Eigen::Matrix4f TL = erasor_utils::geoPose2eigen(l2b);  // (OMU.cpp:100)
+    float Tl[16];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) Tl[4 * r + c] = TL(r, c);
+    const size_t k = grid.configs.size();
+    std::vector<erasor_params> params(k);
+    for (size_t i = 0; i < k; ++i) {  // (what OfflineMapUpdater's constructor makes of the configuration)
+        params[i] = grid.configs[i].params;
+        params[i].is_large_scale = grid.configs[i].is_large_scale ? 1 : 0;
+        if (grid.configs[i].is_large_scale) params[i].submap_size = grid.configs[i].submap_size;
+    }
+    erasor_params p0;
+    erasor_hip_params_default(&p0);
+    erasor_hip_handle *h = nullptr;
+    if (erasor_hip_create(&p0, 0, &h) != ERASOR_OK) {
+        fprintf(stderr, "erasor_hip_create failed\n");
+        return 1;
+    }
+    std::vector<erasor_sweep_row> rows(std::max<size_t>(k, 1));
+    const double t0 = now_ms();
+    const int rc = erasor_hip_sweep(h, params.data(), k, map.data(), map.size() / 4, 0, scans.data(), scans.size() / 4, offsets.data(), n_nodes, 0, Tl,
+                                    Tb.data(), To.data(), gt.data(), gt.size() / 4, 0, 0.2, voxelsize, concurrency, 0, rows.data());
+    const double t1 = now_ms();
+    if (rc) {
+        fprintf(stderr, "sweep: %s (rc %d)\n", erasor_hip_last_error(h), rc);
+        erasor_hip_destroy(h);
+        return 1;
+    }
+    erasor_hip_destroy(h);
+    printf("%zu configurations over %zu nodes of %s, saved maps (leaf 0.2) against %s, %.1f ms in all:\n", k, n_nodes, drv.data_dir.c_str(), argv[4],
+           t1 - t0);
+    std::vector<size_t> order(k);
+    for (size_t i = 0; i < k; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+        const bool oa = rows[a].status == ERASOR_OK, ob = rows[b].status == ERASOR_OK;
+        if (oa != ob) return oa;
+        return oa && rows[a].eval.F1 > rows[b].eval.F1;
+    });
+    std::string head = "|";
+    for (const auto &a : grid.axes) head += " " + a.substr(a.rfind('/') + 1) + " |";
+    printf("%s   gt_S |   gt_D |   est_S |   est_D |   kept_S |   kept_D |     PR%% |     RR%% |     F1 |\n", head.c_str());
+    for (size_t i : order) {
+        std::string pre = "|";
+        for (size_t a = 0; a < grid.axes.size(); ++a) pre += " " + grid.values[i][a] + " |";
+        const erasor_eval_result &r = rows[i].eval;
+        if (rows[i].status != ERASOR_OK) {
+            printf("%s failed: rc %d\n", pre.c_str(), rows[i].status);
+            continue;
+        }
+        printf("%s %6llu | %6llu | %7llu | %7llu | %8llu | %8llu | %7.3f | %7.3f | %6.4f |\n", pre.c_str(), (unsigned long long)r.gt_static,
+               (unsigned long long)r.gt_dynamic, (unsigned long long)r.est_static, (unsigned long long)r.est_dynamic,
+               (unsigned long long)r.preserved_static, (unsigned long long)r.preserved_dynamic, r.PR, r.RR, r.F1);
+    }
+    if (k && rows[order[0]].status == ERASOR_OK) {
+        const size_t b = order[0];
+        printf("best configuration (F1 %.4f), as rosparam lines:\n", rows[b].eval.F1);
+        std::vector<std::pair<std::string, std::string>> kv = grid.scalars;
+        for (size_t a = 0; a < grid.axes.size(); ++a) kv.emplace_back(grid.axes[a], grid.values[b][a]);
+        std::vector<std::string> sections;
+        for (const auto &e : kv) {
+            const std::string sec = e.first.substr(1, e.first.find('/', 1) - 1);
+            if (std::find(sections.begin(), sections.end(), sec) == sections.end()) sections.push_back(sec);
+        }
+        for (const auto &sec : sections) {
+            printf("%s:\n", sec.c_str());
+            for (const auto &e : kv)
+                if (e.first.compare(1, sec.size() + 1, sec + "/") == 0) printf("  %s: %s\n", e.first.substr(sec.size() + 2).c_str(), e.second.c_str());
+        }
+    }
+    return 0;
 }
 
 // --align <rosparam.yaml> [n_frames] [voxelsize = 0.2]: the check the reference README asks for before anything else ("ERASOR in the
@@ -912,6 +1104,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && (std::string(argv[1]) == "--sweep" || std::string(argv[1]) == "--eval-many")) {
+        try {
+            return std::string(argv[1]) == "--sweep" ? sweep_mode(argc, argv) : eval_many_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--align") {
         try {
             return align_mode(argc, argv);
@@ -957,8 +1157,10 @@ int main(int argc, char **argv) {
                 "usage: %s <data_dir> <n_frames> [version] [removal_interval] [gt]\n       %s --config <rosparam.yaml> [n_frames] [gt]\n"
                 "       %s --eval <gt> <est> [voxelsize] [voxel_leaf]\n       %s --eval-classes <gt> <est> [voxelsize] [voxel_leaf]\n"
                 "       %s --analyze <gt> <est> [voxelsize] [voxel_leaf]\n       %s --align <rosparam.yaml> [n_frames] [voxelsize]\n"
-                "       %s --label <map> <dense_labelled> [leaf]\n       %s --complement <est> <gt> <out.pcd>\n",
-                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                "       %s --label <map> <dense_labelled> [leaf]\n       %s --complement <est> <gt> <out.pcd>\n"
+                "       %s --sweep <rosparam.yaml> <grid.yaml> <gt> [n_frames] [voxelsize] [concurrency]\n"
+                "       %s --eval-many <voxelsize> <voxel_leaf> <gt> <est1> [<est2> ...]\n",
+                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

@@ -14,6 +14,8 @@
 #include <fstream>
 #include <map>
 #include <sstream>
+#include <vector>
+#include <algorithm>
 
 #include "erasor_shim.h"
 
@@ -41,8 +43,9 @@ std::string unquote(const std::string &v) {
     if (v.size() >= 2 && ((v.front() == '"' && v.back() == '"') || (v.front() == '\'' && v.back() == '\''))) return v.substr(1, v.size() - 2);
     return v;
 }
-// the subset of YAML rosparam files of the reference use: nested maps by indentation, scalars, flow lists of scalars
-bool parse_yaml(const std::string &path, std::map<std::string, std::string> &kv) {
+// the subset of YAML rosparam files of the reference use: nested maps by indentation, scalars, flow lists of scalars; (key, value) in
+// file order
+bool parse_yaml_list(const std::string &path, std::vector<std::pair<std::string, std::string>> &kv) {
     std::ifstream f(path);
     if (!f) return false;
     std::vector<std::pair<int, std::string>> stack;  // (indent, key)
@@ -62,8 +65,14 @@ bool parse_yaml(const std::string &path, std::map<std::string, std::string> &kv)
         for (const auto &s : stack) full += "/" + s.second;
         full += "/" + key;
         if (val.empty()) stack.emplace_back(indent, key);
-        else kv[full] = unquote(val);
+        else kv.emplace_back(full, unquote(val));
     }
+    return true;
+}
+bool parse_yaml(const std::string &path, std::map<std::string, std::string> &kv) {
+    std::vector<std::pair<std::string, std::string>> list;
+    if (!parse_yaml_list(path, list)) return false;
+    for (const auto &e : list) kv[e.first] = e.second;  // (a key given twice: the last one)
     return true;
 }
 bool get_d(const std::map<std::string, std::string> &kv, const char *k, double &out) {
@@ -355,9 +364,7 @@ int save_pcd_binary(const std::string &pcd_name, const Cloud &src) {
 
 namespace erasor {
 
-bool load_config_yaml(const std::string &path, OfflineMapUpdater::Config &cfg, DriverConfig *drv) {
-    std::map<std::string, std::string> kv;
-    if (!parse_yaml(path, kv)) return false;
+static bool apply_config(const std::map<std::string, std::string> &kv, OfflineMapUpdater::Config &cfg, DriverConfig *drv) {
     erasor_params &p = cfg.params;
     // ERASOR's constructor (erasor.h:47-61)
     get_d(kv, "/erasor/max_range", p.max_range);
@@ -412,6 +419,80 @@ bool load_config_yaml(const std::string &path, OfflineMapUpdater::Config &cfg, D
     }
     return true;
 }
+bool load_config_yaml(const std::string &path, OfflineMapUpdater::Config &cfg, DriverConfig *drv) {
+    std::map<std::string, std::string> kv;
+    if (!parse_yaml(path, kv)) return false;
+    return apply_config(kv, cfg, drv);
+}
+
+// the keys a sweep grid may set: those apply_config reads into the step's parameters
+static bool sweep_key_allowed(const std::string &k) {
+    static const char *const keys[] = {"/erasor/max_range", "/erasor/num_rings", "/erasor/num_sectors", "/erasor/max_h", "/erasor/min_h",
+                                       "/erasor/th_bin_max_h", "/erasor/scan_ratio_threshold", "/erasor/num_lowest_pts",
+                                       "/erasor/minimum_num_pts", "/erasor/rejection_ratio", "/erasor/gf_dist_thr", "/erasor/gf_iter",
+                                       "/erasor/gf_num_lpr", "/erasor/gf_th_seeds_height", "/erasor/map_voxel_size", "/erasor/version",
+                                       "/MapUpdater/query_voxel_size", "/MapUpdater/removal_interval", "/large_scale/is_large_scale",
+                                       "/large_scale/submap_size"};
+    for (const char *a : keys)
+        if (k == a) return true;
+    return false;
+}
+static void config_defaults(OfflineMapUpdater::Config &cfg) {
+    erasor_hip_params_default(&cfg.params);
+    cfg.params.query_voxel_size = 0.05;  // OMU.cpp:66
+    cfg.params.removal_interval = 2;     // OMU.cpp:69
+}
+
+int expand_sweep_grid(const std::string &base_yaml, const std::string &grid_yaml, size_t cap, SweepGrid &out, DriverConfig *drv, std::string *bad) {
+    out = SweepGrid();
+    std::map<std::string, std::string> kv;
+    std::vector<std::pair<std::string, std::string>> grid;
+    if (!parse_yaml(base_yaml, kv) || !parse_yaml_list(grid_yaml, grid)) return -1;
+    std::vector<std::vector<std::string>> axis_vals;
+    for (const auto &e : grid) {
+        if (!sweep_key_allowed(e.first)) {
+            if (bad) *bad = e.first;
+            return -2;
+        }
+        const std::string v = trim(e.second);
+        if (v.size() >= 2 && v.front() == '[' && v.back() == ']') {  // a flow list: an axis
+            std::vector<std::string> vals;
+            std::stringstream ss(v.substr(1, v.size() - 2));
+            std::string t;
+            while (std::getline(ss, t, ','))
+                if (!trim(t).empty()) vals.push_back(unquote(trim(t)));
+            if (vals.empty()) return -1;
+            out.axes.push_back(e.first);
+            axis_vals.push_back(vals);
+        } else {
+            kv[e.first] = v;
+            out.scalars.push_back(e);
+        }
+    }
+    size_t n = 1;
+    for (const auto &a : axis_vals) {
+        if (a.size() > cap || n > cap / a.size()) return -3;
+        n *= a.size();
+    }
+    config_defaults(out.base);
+    if (!apply_config(kv, out.base, drv)) return -1;
+    for (size_t c = 0; c < n; ++c) {
+        std::map<std::string, std::string> kc = kv;
+        std::vector<std::string> vals(axis_vals.size());
+        size_t rem = c;
+        for (size_t a = axis_vals.size(); a-- > 0;) {  // the last axis varies fastest
+            vals[a] = axis_vals[a][rem % axis_vals[a].size()];
+            rem /= axis_vals[a].size();
+            kc[out.axes[a]] = vals[a];
+        }
+        OfflineMapUpdater::Config cfg;
+        config_defaults(cfg);
+        if (!apply_config(kc, cfg, nullptr)) return -1;
+        out.values.push_back(vals);
+        out.configs.push_back(cfg);
+    }
+    return 0;
+}
 
 // main_in_your_env.cpp:33-59: header line skipped; columns 2..8 = x y z qx qy qz qw, parsed with stof;
 // Eigen::Quaternionf(w, x, y, z).toRotationMatrix() in float (no normalisation)
@@ -456,16 +537,8 @@ bool load_all_poses(const std::string &txt, std::vector<Eigen::Matrix4f> &poses)
 // ---- C entry points for the (ctypes) tests of the host-side file code: no GPU involved ---------------------------
 extern "C" {
 // parses `path`; writes the values as "key=value\n" lines (fixed order) into out (capacity cap); returns bytes or -1
-int erasor_shim_dump_config(const char *path, char *out, int cap) {
-    erasor::OfflineMapUpdater::Config cfg;
-    erasor_hip_params_default(&cfg.params);
-    cfg.params.query_voxel_size = 0.05;  // OMU.cpp:66
-    cfg.params.removal_interval = 2;     // OMU.cpp:69
-    erasor::DriverConfig drv;
-    if (!erasor::load_config_yaml(path, cfg, &drv)) return -1;
+static void dump_config(const erasor::OfflineMapUpdater::Config &cfg, const erasor::DriverConfig &drv, std::ostringstream &o) {
     const erasor_params &p = cfg.params;
-    std::ostringstream o;
-    o.precision(17);
     o << "max_range=" << p.max_range << "\nnum_rings=" << p.num_rings << "\nnum_sectors=" << p.num_sectors << "\nmin_h=" << p.min_h
       << "\nmax_h=" << p.max_h << "\nth_bin_max_h=" << p.th_bin_max_h << "\nscan_ratio_threshold=" << p.scan_ratio_threshold
       << "\nnum_lowest_pts=" << p.num_lowest_pts << "\nminimum_num_pts=" << p.minimum_num_pts << "\nrejection_ratio=" << p.rejection_ratio
@@ -477,10 +550,45 @@ int erasor_shim_dump_config(const char *path, char *out, int cap) {
       << "\nvoi_max_range=" << p.voi_max_range << "\nlidar2body=";
     for (int i = 0; i < 7; ++i) o << (i ? "," : "") << cfg.lidar2body[i];
     o << "\ndata_dir=" << drv.data_dir << "\nvoxel_size=" << drv.voxel_size << "\ninit_idx=" << drv.init_idx << "\ninterval=" << drv.interval << "\n";
+}
+int erasor_shim_dump_config(const char *path, char *out, int cap) {
+    erasor::OfflineMapUpdater::Config cfg;
+    erasor_hip_params_default(&cfg.params);
+    cfg.params.query_voxel_size = 0.05;  // OMU.cpp:66
+    cfg.params.removal_interval = 2;     // OMU.cpp:69
+    erasor::DriverConfig drv;
+    if (!erasor::load_config_yaml(path, cfg, &drv)) return -1;
+    std::ostringstream o;
+    o.precision(17);
+    dump_config(cfg, drv, o);
     const std::string s = o.str();
     if ((int)s.size() + 1 > cap) return -1;
     memcpy(out, s.c_str(), s.size() + 1);
     return (int)s.size();
+}
+// the configurations of a sweep grid (erasor_offline_demo --sweep): erasor_shim_dump_config's lines per configuration, in grid order (the
+// last axis varying fastest), one empty line after each.  Returns the bytes written, or -1 (a file unreadable, out too small), -2 (a key
+// a grid may not set: out holds it), -3 (more than 256 configurations, the sweep's limit)
+int erasor_shim_expand_grid(const char *base_yaml, const char *grid_yaml, char *out, int cap) {
+    erasor::SweepGrid g;
+    erasor::DriverConfig drv;
+    std::string bad;
+    const int rc = erasor::expand_sweep_grid(base_yaml, grid_yaml, 256, g, &drv, &bad);
+    std::string s;
+    if (rc == -2) s = bad;
+    else if (rc) return rc;
+    else {
+        std::ostringstream o;
+        o.precision(17);
+        for (const auto &c : g.configs) {
+            dump_config(c, drv, o);
+            o << "\n";
+        }
+        s = o.str();
+    }
+    if ((int)s.size() + 1 > cap) return -1;
+    memcpy(out, s.c_str(), s.size() + 1);
+    return rc ? rc : (int)s.size();
 }
 // ERASOR::is_dynamic_obj_close (erasor.h:132) on an R-POD that carries only statuses (status[ring*S+sector]); no device needed
 int erasor_shim_is_dynamic_obj_close(const erasor_params *p, const double *status, int r_target, int theta_target, int r_range, int theta_range) {

@@ -215,6 +215,19 @@ struct DriverConfig {
 // Reads a rosparam YAML file in the reference's layout (config/*.yaml).  Keys that are absent keep the values already
 // in cfg (fill it with the reference's defaults first: erasor_hip_params_default + OMU.cpp:66-83).
 bool load_config_yaml(const std::string &path, OfflineMapUpdater::Config &cfg, DriverConfig *drv = nullptr);
+// a sweep grid (erasor_offline_demo --sweep): a file in the rosparam layout whose flow-list values `[a, b, ...]` are axes and whose
+// scalars override the base file; only the keys that set the step's parameters (/erasor/*, /MapUpdater/query_voxel_size,
+// /MapUpdater/removal_interval, /large_scale/*).  configs: the base file with the scalars and one value of every axis, as
+// load_config_yaml reads it, for the Cartesian product of the axes in file order (the last axis varying fastest).
+struct SweepGrid {
+    std::vector<std::string> axes;                                   // the swept keys, in file order
+    std::vector<std::pair<std::string, std::string>> scalars;        // the grid's scalar overrides, in file order
+    std::vector<std::vector<std::string>> values;                    // per configuration: the value of every axis, as written
+    std::vector<OfflineMapUpdater::Config> configs;
+    OfflineMapUpdater::Config base;                                  // the base file with the scalars applied
+};
+// 0, or -1 (a file unreadable, an empty list), -2 (a key a grid may not set: *bad), -3 (more than cap configurations)
+int expand_sweep_grid(const std::string &base_yaml, const std::string &grid_yaml, size_t cap, SweepGrid &out, DriverConfig *drv, std::string *bad);
 // main_in_your_env.cpp:33-59: poses_lidar2body.csv -> 4x4 float transforms (one per line after the header)
 bool load_all_poses(const std::string &txt, std::vector<Eigen::Matrix4f> &poses);
 }  // namespace erasor

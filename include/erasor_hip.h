@@ -280,6 +280,49 @@ int erasor_hip_evaluate_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t
 int erasor_hip_evaluate_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device,
                             double voxel_leaf, double voxelsize, erasor_eval_result *res);
 
+/* K estimates against ONE ground truth (compare_map.cpp's use: raw / OctoMap / Peopleremover / Removert / ERASOR maps against one GT):
+ * rows[j] is what erasor_hip_evaluate_clouds(h, gt, est[j], voxel_leaf, voxelsize) returns, field for field (the same decision per
+ * GT point: its nearest point of estimate j by (float64 d^2, index within estimate j), kept if sqrt(d^2) < voxelsize*sqrt(3)/2), from one
+ * index of all estimates and one query launch.  est_xyzi / n_est / est_is_device: k entries (est_is_device may be NULL: all on the host).
+ * voxel_leaf > 0: the GT is voxelised once and every estimate once, with what that borrows (see erasor_hip_evaluate_clouds); 0 works in
+ * the evaluator's own scratch.  Device memory: below 56 B per estimated point + 8 KiB per estimate, plus a host GT's copy.
+ * ERASOR_E_INVALID: those of erasor_hip_evaluate_clouds (a non-finite point in estimate j names j in erasor_hip_last_error), more than
+ * 2^31 estimated points in all.  k == 0: ERASOR_OK, no rows.  ERASOR_E_STATE: a step in flight. */
+int erasor_hip_evaluate_many(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device,
+                             const void *const *est_xyzi, const size_t *n_est, const int *est_is_device, size_t k,
+                             double voxel_leaf, double voxelsize, erasor_eval_result *rows);
+
+/* ---- a parameter sweep: ERASOR configurations over one sequence, each scored by PR / RR ----------------------------------------
+ * Per configuration, what OfflineMapUpdater + save_static_map + the saved map's evaluation do (the offline driver's --config <yaml> n
+ * <gt>): node j (0-based) is stepped iff (j + 1) % removal_interval == 0 (OMU.cpp:206-209), the map after the last node is voxelised by
+ * voxelize_preserving_labels at save_leaf (main_in_your_env.cpp:123; 0: not voxelised) and evaluated against gt as given (no
+ * voxelisation of the GT).  The map, the scans and the GT are uploaded to h's device once (device inputs are read in place).  The
+ * configurations run in waves of `concurrency` (1..4) worker handles on h's device, one host thread each, every worker with ONE query
+ * stream; the saved maps are then scored by erasor_hip_evaluate_many's kernels in groups of eval_batch (0: all at once).  Free device
+ * memory is checked before each wave.  A configuration that fails -- its parameters (version 4: ERASOR_E_UNSUPPORTED), memory, a step --
+ * carries that status in its row; the call still returns ERASOR_OK.  Only h's evaluator scratch is used: h's map, announcements and later
+ * steps stay as they were.  Scans / offsets / poses as erasor_hip_align_frames_clouds and erasor_hip_run_nodes take them: the scans back
+ * to back, offsets (n_nodes + 1, host), T_body2origin / T_origin2body n_nodes row-major 4x4 matrices each.
+ * ERASOR_E_INVALID: more than 256 configurations, bad offsets, non-finite poses / map / GT points, voxelsize <= 0, save_leaf < 0,
+ * concurrency outside 1..4.  ERASOR_E_STATE: a step of h in flight. */
+typedef struct erasor_sweep_row {
+    erasor_params params;      /* the configuration as run */
+    int32_t status;            /* ERASOR_OK, or this configuration's own error */
+    uint32_t n_steps;          /* nodes stepped after the removal_interval gate */
+    uint64_t n_map_final;      /* erasor_hip_map_size after the last node */
+    uint64_t n_saved;          /* points of the saved map */
+    erasor_eval_result eval;   /* the saved map against gt */
+    double run_ms;             /* host wall time of this configuration's node loop */
+    uint32_t reserved_[8];
+} erasor_sweep_row;
+
+int erasor_hip_sweep(erasor_hip_handle *h, const erasor_params *configs, size_t n_configs,
+                     const void *map_xyzi, size_t n_map, int map_is_device,
+                     const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_nodes, int scans_are_device,
+                     const float T_lidar2body[16], const float *T_body2origin, const float *T_origin2body,
+                     const void *gt_xyzi, size_t n_gt, int gt_is_device,
+                     double save_leaf, double voxelsize, int concurrency, int eval_batch, erasor_sweep_row *rows);
+
 /* ---- PR / RR broken down by semantic class and by dynamic instance --------------------------------------------------------------
  * The decision of erasor_hip_evaluate_* for every ground-truth point (its nearest estimated point, the threshold, the smallest
  * estimated index on a tie), counted per class key and per dynamic instance.  Class key: uint32(intensity) & 0xFFFF, or
