@@ -5,7 +5,13 @@ A "step" is one pass of the hot path (query voxelise -> fetch_VoI -> R-POD -> Sc
 map write-back; reference OfflineMapUpdater.cpp:237-294) over one synthetic scan against a map that is
 resident in HBM.  Inputs (map and scans) are in HBM before the timed region.
 
-  python bench.py --gpus N --steps K --warmup W [--workload W] [--mode M] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--workload W] [--mode M] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the result line: nothing else.  --full adds
+what the headline does not need (each --no-* option below leaves one of them out): the oracle's replay of every step the GPU ran
+and the CPU baselines, PR / RR of the final map, the timed steps again without look-ahead, the C++ drop-in path and the short
+passes over the other BASELINE configs.  Options that ask for a leg by name (--profile-all, --union-eval, --eval,
+--verify-prefix-seconds) run it with or without --full.
 
 --gpus N > 1 without a torchrun environment runs itself again, in a child process, under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, one rank per GPU
@@ -53,7 +59,7 @@ WORKLOADS = {
 SEQS = ["00", "01", "02", "05", "07"]  # BASELINE config[2]
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20, help="timed steps (with the default --repeats 1: exactly this many)")
@@ -78,7 +84,7 @@ def parse_args():
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="stop the CPU leg after this much CPU work")
     ap.add_argument("--verify-prefix-seconds", type=float, default=0.0,
                     help="with --no-cpu-baseline: replay the FIRST steps the GPU ran (warm-up first) on the oracle for this much CPU time and compare every "
-                         "erasor_step_result -- the bounded check of the extra passes of the default run (the headline and one config-4 pass replay every step)")
+                         "erasor_step_result -- the bounded check of the extra passes of the --full run (the headline and one config-4 pass replay every step)")
     ap.add_argument("--no-verify-all", dest="verify_all", action="store_false",
                     help="let --cpu-seconds also bound the oracle's replay of the GPU's steps (default: every step the GPU ran -- warm-up and all "
                          "timed passes -- is replayed and compared, then the final map: ~0.08 s per step on the 10 M-point map)")
@@ -115,13 +121,20 @@ def parse_args():
     ap.add_argument("--no-pr-rr", action="store_true", help="skip PR / RR of the final map (erasor_amd.evalmap; ~10-20 s of host time for a 10 M-point map)")
     ap.add_argument("--no-callback-bench", action="store_true", help="skip the C++ drop-in path benchmark (erasor_offline_demo --bench)")
     ap.add_argument("--no-extra-workloads", action="store_true",
-                    help="default run (1 GPU, seq05, replicas) only: do not append the short passes over BASELINE configs 4 / 2-yaml / 5")
+                    help="--full run (1 GPU, seq05, replicas) only: do not append the short passes over BASELINE configs 4 / 2-yaml / 5")
     ap.add_argument("--union-eval", type=int, default=0, metavar="N",
                     help="replicas mode: after the timed pass, SURVEY 8(e)(ii)'s result exchange -- every rank applies N scans of its shard to the "
                          "INITIAL map each (Jacobi-style), ONE all_gather of the removed initial-map indices, PR / RR of the united map next to the "
                          "sequential fold's (erasor_amd/dist.py)")
     ap.add_argument("--eval", action="store_true", help="seq-per-gpu: PR/RR of every sequence's final map (erasor_amd.evalmap)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU legs (the oracle's replay of every step, the CPU baselines), PR / RR of the final map, "
+                         "the timed steps again without look-ahead, the C++ drop-in path and the other BASELINE configs; the --no-* options "
+                         "leave single ones out.  Without it a run does only what its result line's headline needs")
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the result line
+        args.no_cpu_baseline = args.no_pr_rr = args.no_callback_bench = args.no_extra_workloads = True
+    return args
 
 
 def respawn_under_torchrun(args):
@@ -531,6 +544,16 @@ def cpu_sequence_parallel(args, seqs, maps, l2b7):
                       % (len(jobs), n_steps, cores, wall)}
 
 
+def extra_pass_cmd(wname, xargs, verified):
+    """the command line of one of --full's short passes over another workload: a --full run of its own (the oracle's replay, the
+    steps without look-ahead), without the legs that only the headline workload carries"""
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--workload", wname, "--steps", "12" if verified else "20", "--warmup",
+           "3" if verified else "5", "--no-extra-workloads", "--no-pr-rr", "--no-callback-bench", "--repeats", "1" if verified else "7"] + xargs
+    if not verified:
+        cmd += ["--no-cpu-baseline", "--verify-prefix-seconds", "4"]  # (the first steps of the pass against the oracle, 4 s of CPU)
+    return cmd
+
+
 def main():
     args = parse_args()
     if args.interleave == "pairs":
@@ -895,9 +918,9 @@ def main():
             print("  %-14s %8.3f ms/step  (%5.1f%%, %d launches)" % (name, ms / K, 100 * ms / max(tot, 1e-9), cnt // K), file=sys.stderr)
         print("  sum of kernels %.3f ms/step vs wall %.3f ms/step" % (tot / K, ms_per_step), file=sys.stderr)
 
-    # ---- the same K scans again without look-ahead (every step runs its own query chain first): what a ROS callback sees ----
+    # ---- --full: the same K scans again without look-ahead (every step runs its own query chain first): what a ROS callback sees ----
     sync_ms = None
-    if first.lookahead and world_size == 1:
+    if args.full and first.lookahead and world_size == 1:
         first.lookahead = False
         torch.cuda.synchronize()
         ts = time.perf_counter()
@@ -907,7 +930,7 @@ def main():
         sync_ms = (time.perf_counter() - ts) * 1e3 / K
         first.lookahead = True
 
-    # ---- CPU baseline: the reference's own sources (oracle/_ref) and the oracle port, one thread, bounded sample ----
+    # ---- --full: CPU baseline, the reference's own sources (oracle/_ref) and the oracle port, one thread, bounded sample ----
     cpu = cpu_refsrc = None
     parity = {"parity_checked_steps": 0, "parity": "not checked in this run (no CPU leg)"}
     if world_size == 1 and not args.no_cpu_baseline and args.mode == "replicas":
@@ -917,7 +940,7 @@ def main():
     elif world_size == 1 and args.mode == "replicas" and args.verify_prefix_seconds > 0 and step_results:
         parity = verify_prefix(args, P, m, first, step_results)
 
-    # ---- PR / RR of the map the timed pass has left (BASELINE.json: "PR/RR vs ref"): the reference's protocol (scripts/analysis_runner.py
+    # ---- --full: PR / RR of the map the timed pass has left (BASELINE.json: "PR/RR vs ref"): the reference's protocol (scripts/analysis_runner.py
     # :74-105 restated in erasor_amd/evalmap.py, pinned to the original's outputs by tests/test_evalmap.py) against the initial map as
     # labelled ground truth.  The oracle's map is bit-identical (final_map_checked), so its PR / RR are these very numbers.
     pr_rr = None
@@ -934,7 +957,7 @@ def main():
                  if parity.get("final_map_checked") else "the CPU path's map was not compared in this run",
                  "steps": int(K * len(pass_s) + W), "wall_s": round(time.time() - t_ev, 1)}
 
-    # ---- the drop-in path in C++: erasor::OfflineMapUpdater::callback_node with host pcl::PointXYZI clouds in and the
+    # ---- --full: the drop-in path in C++: erasor::OfflineMapUpdater::callback_node with host pcl::PointXYZI clouds in and the
     # rejected clouds out, timed by erasor_offline_demo --bench on an export of this very workload (no Python in its loop)
     callback = None
     demo = os.path.join(ROOT, "erasor_amd", "erasor_offline_demo")
@@ -1012,7 +1035,7 @@ def main():
         out["union_exchange"] = union_eval
     if evals is not None:
         out["pr_rr"] = [{"seq": "%02d" % e[0], "PR": e[1] / 1e2, "RR": e[2] / 1e2} for e in sorted(evals)]  # (seq-per-gpu --eval: one entry per sequence)
-    # ---- the other single-GPU BASELINE configs, measured in the same run (short passes, each its own process: a clean device state
+    # ---- --full: the other single-GPU BASELINE configs, measured in the same run (short passes, each its own process: a clean device state
     # and exactly the code path above).  config 4 is the only workload whose VoI pass streams more than the 256 MiB Infinity Cache.
     if (world_size == 1 and args.workload == "seq05" and args.mode == "replicas" and not args.no_extra_workloads and not args.no_cpu_baseline
             and not args.profile_all):
@@ -1030,10 +1053,7 @@ def main():
             ("ouster128", "config 5 shape, 1 GPU", [], {}, False),
         )
         for wname, label, xargs, xenv, verified in passes:
-            cmd = [sys.executable, os.path.abspath(__file__), "--workload", wname, "--steps", "12" if verified else "20", "--warmup",
-                   "3" if verified else "5", "--no-extra-workloads", "--no-pr-rr", "--no-callback-bench", "--repeats", "1" if verified else "7"] + xargs
-            if not verified:
-                cmd += ["--no-cpu-baseline", "--verify-prefix-seconds", "4"]  # (the first steps of the pass against the oracle, 4 s of CPU)
+            cmd = extra_pass_cmd(wname, xargs, verified)
             t_sub = time.time()
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=dict(os.environ, **xenv))

@@ -2,7 +2,7 @@
 # kernel averages (rocprofv3 --kernel-trace --stats) of the build under _ab_old/ and of the working tree on ONE box, then the bench lines
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 KERNELS=${AB_KERNELS:-"k_voi_gather k_voi_split k_late_gather k_assemble_late k_chunk_scan_one k_srt4 k_revert_bins_srt"}
-A="--no-cpu-baseline --no-extra-workloads --no-callback-bench --no-pr-rr --steps 20 --warmup 5"
+A="--full --no-cpu-baseline --no-extra-workloads --no-callback-bench --no-pr-rr --steps 20 --warmup 5"
 cd /tmp && export TMPDIR=/tmp
 for which in _ab_old . _ab_old .; do
   for wl in ${AB_WORKLOADS:-"--workload=seq05"}; do

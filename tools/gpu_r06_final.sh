@@ -10,7 +10,7 @@ timeout 1700 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; echo "
 tools/collect_profiles.sh r06 > $OUT/collect_r06.log 2>&1
 tools/collect_profiles.sh r06_ls05 --workload large_scale_05 > $OUT/collect_r06_ls05.log 2>&1
 cp gpurun_out/kernel_stats_latest*.csv gpurun_out/pmc_latest*.json gpurun_out/latest_meta*.json profiles/ 2>/dev/null
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err ) 2>&1 | tail -3
+( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err ) 2>&1 | tail -3
 B="timeout 300 python bench.py --no-cpu-baseline --no-extra-workloads --no-callback-bench --no-pr-rr --repeats 5 --steps 100"
 for m in 0 1; do echo "== steps 100, ERASOR_HIP_OVERLAP=$m"; ERASOR_HIP_OVERLAP=$m $B 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().split(chr(10))[-1]); print(d['ms_per_step'], d['ms_per_step_all'])"; done
