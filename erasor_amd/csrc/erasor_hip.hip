@@ -327,6 +327,12 @@ struct erasor_hip_handle {
         // and one row for the ground truth (the combined bucket table and the bucketed points: cnt, pl, tops, bkt, pts, idx above)
         DBuf<float4> em_cat;
         DBuf<EvmEst> em_tab;
+#ifdef ERASOR_HIP_TEST_HOOKS
+        // what the last index build left behind, for the hooks that dump it (erasor_hip_debug_nn_tree / _ev_grid / _ev_grid_many)
+        const uint32_t *dbg_skeys = nullptr;  // nn_tree: the sorted Morton keys
+        uint32_t dbg_nb = 0;                   // ev_run / evm_run: the bucket count of the table
+        std::vector<EvmEst> dbg_tab;           // evm_run: the estimates' table
+#endif
         DBuf<unsigned long long> em_ctr;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
@@ -3388,6 +3394,9 @@ static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const f
     auto &E = h->ev;
     uint32_t nb = 1024;  // buckets: a power of two >= the estimate's size (<= 1 point per bucket on average)
     while (nb < n_est) nb <<= 1;
+#ifdef ERASOR_HIP_TEST_HOOKS
+    E.dbg_nb = nb;
+#endif
     if (ensure(h, E.ctr, EV_NCTR) || ensure(h, E.cnt, (size_t)nb + 1) || ensure(h, E.pl, (size_t)nb + 1) || ensure(h, E.tops, nb / 1024 + 4) ||
         ensure(h, E.bkt, (size_t)n_est + 1) || ensure(h, E.pts, (size_t)n_est + 1) || ensure(h, E.idx, (size_t)n_est + 1) ||
         (per_gt && ensure(h, E.code, (size_t)n_gt + 1)))
@@ -3596,6 +3605,10 @@ static int evm_run(erasor_hip_handle *h, const char *who, const float4 *gt, uint
         return ERASOR_E_INVALID;
     }
     const uint32_t nb = (uint32_t)nb_all, n = (uint32_t)n_all;
+#ifdef ERASOR_HIP_TEST_HOOKS
+    E.dbg_nb = nb;
+    E.dbg_tab = tab;
+#endif
     if (ensure(h, E.em_tab, k + 1) || ensure(h, E.em_ctr, (k + 1) * EV_NCTR) || ensure(h, E.cnt, (size_t)nb + 1) || ensure(h, E.pl, (size_t)nb + 1) ||
         ensure(h, E.tops, nb / 1024 + 4) || ensure(h, E.bkt, (size_t)n + 1) || ensure(h, E.pts, (size_t)n + 1) || ensure(h, E.idx, (size_t)n + 1))
         return ERASOR_E_NO_DEVICE;
@@ -3789,6 +3802,9 @@ static int nn_tree(erasor_hip_handle *h, const float4 *pts, uint32_t n, uint32_t
     const uint32_t *skeys = nullptr, *sperm = nullptr;
     if (radix_sort(h, E.nn_key.p, n, nullptr, 30, E.nn_ka.p, E.nn_kb.p, E.nn_va.p, E.nn_vb.p, &skeys, &sperm, "ov_tree"))
         return ERASOR_E_NO_DEVICE;
+#ifdef ERASOR_HIP_TEST_HOOKS
+    E.dbg_skeys = skeys;
+#endif
     LAUNCH(h, "ov_tree", k_nn_gather, cdiv(n, 256), 256, pts, n, sperm, E.nn_pts.p, E.nn_idx.p);
     LAUNCH(h, "ov_tree", k_nn_leaves, cdiv(P * NN_LEAF, 256), 256, (const float4 *)E.nn_pts.p, n, P, E.nn_lo.p, E.nn_hi.p);
     for (uint32_t first = P / 2; first >= 1; first /= 2) LAUNCH(h, "ov_tree", k_nn_level, cdiv(first, 256), 256, E.nn_lo.p, E.nn_hi.p, first);
@@ -5107,6 +5123,128 @@ int erasor_hip_radix_sort_u32(erasor_hip_handle *h, const uint32_t *keys, size_t
         HIPC(h, hipMemcpy(perm_out, sp, (size_t)ns * 4, hipMemcpyDeviceToHost));
     }
     return ERASOR_OK;
+}
+// test hook: the bounding-volume tree of a cloud (x y z i rows, host or device) as nn_pad / nn_tree build it for overlap, align_frames,
+// label_map and static_complement: P, the points in key order with their original indices, the sorted Morton keys, the boxes of all 2P
+// nodes (node 0 is never written: its rows come back as they lie in the scratch).  cap_nodes: the rows lo / hi hold.
+int erasor_hip_debug_nn_tree(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, uint32_t *P_out, float *pts, uint32_t *idx,
+                             uint32_t *keys, float *lo, float *hi, size_t cap_nodes) {
+    NOFLY(h);
+    if (!h || !xyzi || !n || n > 0x3FFFFFFFull || !P_out || !pts || !idx || !keys || !lo || !hi) return ERASOR_E_INVALID;
+    HIPC(h, hipSetDevice(h->device));
+    auto &E = h->ev;
+    const float4 *g = nullptr;
+    int rc = ev_input(h, xyzi, n, is_device, E.gt, &g);
+    if (rc) return rc;
+    NnScope scope(h);
+    uint32_t P = 1;
+    if ((rc = nn_pad(h, (uint32_t)n, &P, "erasor_hip_debug_nn_tree", "cloud"))) return rc;
+    if (ensure(h, E.nn_ctr, OV_NCTR)) return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if ((rc = nn_tree(h, g, (uint32_t)n, P, "erasor_hip_debug_nn_tree", "point(s)"))) return rc;
+    *P_out = P;
+    if (2 * (size_t)P > cap_nodes) return ERASOR_E_CAPACITY;
+    if ((rc = d2h(h, pts, E.nn_pts.p, n * sizeof(float4))) || (rc = d2h(h, idx, E.nn_idx.p, n * sizeof(uint32_t))) ||
+        (rc = d2h(h, keys, E.dbg_skeys, n * sizeof(uint32_t))) || (rc = d2h(h, lo, E.nn_lo.p, 2 * (size_t)P * sizeof(float4))) ||
+        (rc = d2h(h, hi, E.nn_hi.p, 2 * (size_t)P * sizeof(float4))))
+        return rc;
+    return ERASOR_OK;
+}
+
+// test hook: k_nn_query (f32 == 0: overlap's float64 search) or k_lm_query (f32 != 0: label_map's float32 search) of n_q queries over
+// the tree of a cloud, built as above, with every query's effort beside the kernel's own outputs: effort[2 * i] = leaves opened,
+// effort[2 * i + 1] = leaf points tested.  f32 == 0: dist / nearest as erasor_hip_overlap_clouds returns them per point; f32 != 0:
+// rows = k_lm_query's output (x, y, z, the nearest point's w), *n_tied its FM_TIED counter.  Queries must be finite.
+int erasor_hip_debug_nn_effort(erasor_hip_handle *h, const float *tree_xyzi, size_t n, const float *query_xyzi, size_t n_q, int f32, double *dist,
+                               uint32_t *nearest, float *rows, uint64_t *n_tied, uint32_t *effort) {
+    NOFLY(h);
+    if (!h || !tree_xyzi || !n || n > 0x3FFFFFFFull || !query_xyzi || !n_q || n_q > 0x3FFFFFFFull || !effort) return ERASOR_E_INVALID;
+    if (f32 ? (!rows || !n_tied) : (!dist || !nearest)) return ERASOR_E_INVALID;
+    HIPC(h, hipSetDevice(h->device));
+    auto &E = h->ev;
+    const float4 *g = nullptr, *q = nullptr;
+    int rc;
+    if ((rc = ev_input(h, tree_xyzi, n, 0, E.gt, &g)) || (rc = ev_input(h, query_xyzi, n_q, 0, E.est, &q))) return rc;
+    NnScope scope(h);
+    const uint32_t nt = (uint32_t)n, nq = (uint32_t)n_q;
+    uint32_t P = 1;
+    if ((rc = nn_pad(h, nt, &P, "erasor_hip_debug_nn_effort", "cloud"))) return rc;
+    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.fm_ctr, FM_NCTR) || ensure(h, E.nn_dbits, n_q + 1) || ensure(h, E.nn_near, n_q + 1) ||
+        ensure(h, E.fm_out, n_q + 1))
+        return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if ((rc = nn_tree(h, g, nt, P, "erasor_hip_debug_nn_effort", "point(s)"))) return rc;
+    HIPC(h, hipMemsetAsync(E.fm_ctr.p, 0, FM_NCTR * sizeof(unsigned long long), h->stream));
+    uint32_t *d_eff = nullptr;  // (the query grid's lanes past n_q never search: 2 * n_q entries are all that is written)
+    HIPC(h, hipMalloc((void **)&d_eff, 2 * n_q * sizeof(uint32_t)));
+    (void)hipMemsetAsync(d_eff, 0xFF, 2 * n_q * sizeof(uint32_t), h->stream);
+    hipLaunchKernelGGL(k_nn_set_effort, dim3(1), dim3(1), 0, h->stream, d_eff);
+    if (f32)
+        LAUNCH(h, "lm_query", k_lm_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, q, nq, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, nt,
+               (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, E.fm_out.p, E.fm_ctr.p);
+    else
+        LAUNCH(h, "ov_query", k_nn_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, q, nq, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, nt,
+               (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, 0.5, 1.0, 2.0, E.nn_dbits.p, E.nn_near.p, E.nn_ctr.p);
+    hipLaunchKernelGGL(k_nn_set_effort, dim3(1), dim3(1), 0, h->stream, (uint32_t *)nullptr);
+    unsigned long long c[FM_NCTR], co[OV_NCTR];
+    rc = d2h(h, effort, d_eff, 2 * n_q * sizeof(uint32_t));
+    (void)hipFree(d_eff);
+    if (rc || (rc = d2h(h, c, E.fm_ctr.p, sizeof(c))) || (rc = d2h(h, co, E.nn_ctr.p, sizeof(co)))) return rc;
+    if (c[FM_NON_FINITE] || co[OV_NON_FINITE]) {
+        h->err = "erasor_hip_debug_nn_effort: non-finite query";
+        return ERASOR_E_INVALID;
+    }
+    if (f32) {
+        *n_tied = c[FM_TIED];
+        return d2h(h, rows, E.fm_out.p, n_q * sizeof(float4));
+    }
+    if ((rc = d2h(h, dist, E.nn_dbits.p, n_q * sizeof(double)))) return rc;
+    return d2h(h, nearest, E.nn_near.p, n_q * sizeof(uint32_t));
+}
+
+// what ev_run / evm_run left in the evaluator's scratch: the bucket count, the bucket offsets and the scattered points and indices
+static int dbg_ev_dump(erasor_hip_handle *h, size_t n, uint32_t *nb_out, uint32_t *off, size_t cap_off, float *pts, uint32_t *idx) {
+    auto &E = h->ev;
+    *nb_out = E.dbg_nb;
+    if ((size_t)E.dbg_nb + 1 > cap_off) return ERASOR_E_CAPACITY;
+    int rc;
+    if ((rc = d2h(h, off, E.cnt.p, ((size_t)E.dbg_nb + 1) * sizeof(uint32_t))) || (rc = d2h(h, pts, E.pts.p, n * sizeof(float4))) ||
+        (rc = d2h(h, idx, E.idx.p, n * sizeof(uint32_t))))
+        return rc;
+    return ERASOR_OK;
+}
+
+// test hook: the hashed grid of an estimate (n > 0 host rows) at a voxel size, built by erasor_hip_evaluate_clouds' own path (ev_run, an
+// empty ground truth): nb, off[nb + 1], the scattered points and their indices
+int erasor_hip_debug_ev_grid(erasor_hip_handle *h, const float *est_xyzi, size_t n, double voxelsize, uint32_t *nb_out, uint32_t *off, size_t cap_off,
+                             float *pts, uint32_t *idx) {
+    if (!h || !est_xyzi || !n || !nb_out || !off || !pts || !idx) return ERASOR_E_INVALID;
+    erasor_eval_result res;
+    const int rc = erasor_hip_evaluate_clouds(h, nullptr, 0, 0, est_xyzi, n, 0, 0.0, voxelsize, nullptr, &res);
+    if (rc) return rc;
+    return dbg_ev_dump(h, n, nb_out, off, cap_off, pts, idx);
+}
+
+// test hook: the combined table of k estimates (host rows; some may be empty, not all), built by erasor_hip_evaluate_many's own path
+// (evm_run, an empty ground truth): as above over all estimates back to back (idx: combined indices), and tab[4 * j ..] = estimate j's
+// (first point, points, first bucket, bucket mask)
+int erasor_hip_debug_ev_grid_many(erasor_hip_handle *h, const void *const *est_xyzi, const size_t *n_est, size_t k, double voxelsize, uint32_t *nb_out,
+                                  uint32_t *off, size_t cap_off, float *pts, uint32_t *idx, uint32_t *tab) {
+    if (!h || !est_xyzi || !n_est || !k || !nb_out || !off || !pts || !idx || !tab) return ERASOR_E_INVALID;
+    std::vector<erasor_eval_result> rows(k);
+    const int rc = erasor_hip_evaluate_many(h, nullptr, 0, 0, est_xyzi, n_est, nullptr, k, 0.0, voxelsize, rows.data());
+    if (rc) return rc;
+    size_t n = 0;
+    for (size_t j = 0; j < k; ++j) {
+        const EvmEst &e = h->ev.dbg_tab[j];
+        tab[4 * j] = e.off;
+        tab[4 * j + 1] = e.n;
+        tab[4 * j + 2] = e.base;
+        tab[4 * j + 3] = e.mask;
+        n += n_est[j];
+    }
+    if (!n) return ERASOR_E_INVALID;
+    return dbg_ev_dump(h, n, nb_out, off, cap_off, pts, idx);
 }
 #endif  // ERASOR_HIP_TEST_HOOKS
 

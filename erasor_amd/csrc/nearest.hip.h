@@ -136,6 +136,13 @@ __global__ __launch_bounds__(256) void k_nn_level(float4 *__restrict__ lo, float
     hi[k] = make_float4(fmaxf(c.x, d.x), fmaxf(c.y, d.y), fmaxf(c.z, d.z), 0.0f);
 }
 
+#ifdef ERASOR_HIP_TEST_HOOKS
+// test hooks only: when set, every search also writes the leaves it opened and the leaf points it tested to nn_effort[2 * i], [2 * i + 1],
+// i = blockIdx.x * NN_QBLOCK + t (the query's index in k_nn_query / k_lm_query).  The product library has none of this.
+__device__ uint32_t *nn_effort = nullptr;
+__global__ void k_nn_set_effort(uint32_t *p) { nn_effort = p; }
+#endif
+
 // the lower bound of d^2 from q to any point of the box [l, u] (exact: see the header)
 __device__ __forceinline__ double nn_lb(const float4 &l, const float4 &u, double qx, double qy, double qz) {
     const double gx = qx < (double)l.x ? (double)l.x - qx : (qx > (double)u.x ? qx - (double)u.x : 0.0);
@@ -152,9 +159,16 @@ __device__ __forceinline__ double nn_search_f64(double qx, double qy, double qz,
     double best = __builtin_huge_val();
     uint32_t best_i = 0xFFFFFFFFu;
     uint32_t node = 1, sp = 0;
+#ifdef ERASOR_HIP_TEST_HOOKS
+    uint32_t n_leaves = 0, n_points = 0;
+#endif
     for (;;) {
         if (node >= n_pad) {  // a leaf: its points (a leaf that is reached holds at least one)
             const uint32_t b = (node - n_pad) * NN_LEAF, e = b + NN_LEAF < n_gt ? b + NN_LEAF : n_gt;
+#ifdef ERASOR_HIP_TEST_HOOKS
+            ++n_leaves;
+            n_points += e - b;
+#endif
             for (uint32_t s = b; s < e; ++s) {
                 const float4 p = pts[s];
                 const double ex = qx - (double)p.x, ey = qy - (double)p.y, ez = qz - (double)p.z;
@@ -197,6 +211,12 @@ __device__ __forceinline__ double nn_search_f64(double qx, double qy, double qz,
         }
         if (!more) break;
     }
+#ifdef ERASOR_HIP_TEST_HOOKS
+    if (nn_effort) {
+        nn_effort[2 * (size_t)(blockIdx.x * NN_QBLOCK + t)] = n_leaves;
+        nn_effort[2 * (size_t)(blockIdx.x * NN_QBLOCK + t) + 1] = n_points;
+    }
+#endif
     *best_i_out = best_i;
     return best;
 }
@@ -292,9 +312,16 @@ __device__ __forceinline__ NnF32 nn_search_f32(float qx, float qy, float qz, con
                                                uint32_t *stack, uint32_t t) {
     NnF32 b{__builtin_huge_valf(), 0xFFFFFFFFu, 0u, false};
     uint32_t node = 1, sp = 0;
+#ifdef ERASOR_HIP_TEST_HOOKS
+    uint32_t n_leaves = 0, n_points = 0;
+#endif
     for (;;) {
         if (node >= n_pad) {  // a leaf: its points (a leaf that is reached holds at least one)
             const uint32_t s0 = (node - n_pad) * NN_LEAF, e = s0 + NN_LEAF < n ? s0 + NN_LEAF : n;
+#ifdef ERASOR_HIP_TEST_HOOKS
+            ++n_leaves;
+            n_points += e - s0;
+#endif
             for (uint32_t s = s0; s < e; ++s) {
                 const float4 p = pts[s];
                 const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
@@ -310,7 +337,8 @@ __device__ __forceinline__ NnF32 nn_search_f32(float qx, float qy, float qz, con
                         b.w = w;
                         b.mixed = false;
                     } else {  // the same d^2: the smaller index is the answer, a second bit pattern makes the query tied
-                        if (w != b.w) b.mixed = true;
+                        // (idx == ~0u: no candidate yet -- a first point whose d^2 overflowed to +inf equals the seed, not a point)
+                        if (b.idx != 0xFFFFFFFFu && w != b.w) b.mixed = true;
                         if (j < b.idx) {
                             b.idx = j;
                             b.w = w;
@@ -348,6 +376,12 @@ __device__ __forceinline__ NnF32 nn_search_f32(float qx, float qy, float qz, con
         }
         if (!more) break;
     }
+#ifdef ERASOR_HIP_TEST_HOOKS
+    if (nn_effort) {
+        nn_effort[2 * (size_t)(blockIdx.x * NN_QBLOCK + t)] = n_leaves;
+        nn_effort[2 * (size_t)(blockIdx.x * NN_QBLOCK + t) + 1] = n_points;
+    }
+#endif
     return b;
 }
 

@@ -113,9 +113,10 @@ def align_frames(map_xyz, scans, T_body2origin, T_lidar2body=None, voxelsize=0.2
 def _l2_simple(q, p):
     """FLANN's L2_Simple in float32, operation by operation: r = 0; r += dx*dx; r += dy*dy; r += dz*dz with dx = q.x - p.x"""
     r = np.zeros(len(q), np.float32)
-    for a in range(3):
-        d = q[:, a] - p[:, a]
-        r += d * d
+    with np.errstate(over="ignore"):  # (a difference above 1.8e19 squares to +inf, as it does in FLANN)
+        for a in range(3):
+            d = q[:, a] - p[:, a]
+            r += d * d
     return r
 
 
@@ -130,7 +131,11 @@ def nearest_f32(tree_xyz, query_xyz, tree_key=None):
     a relative 5 * 2^-24 (about 3e-7) at most, which the relative margin covers, except where products underflow to
     subnormals or zero, where the error is absolute (below 2^-149 per operation), which the absolute margin covers.  Among those
     candidates the float32 d^2 is computed as FLANN does and the minimum, then the lowest index, wins.  Queries with a single
-    candidate (nearly all) need no second look: that candidate is cKDTree's answer."""
+    candidate (nearly all) need no second look: that candidate is cKDTree's answer.
+
+    The margin argument needs finite values.  Where the float32 d^2 of cKDTree's answer overflows to +inf (a coordinate
+    difference above about 1.8e19), a relative margin around the float64 minimum says nothing about which points share that
+    +inf: those queries take ALL tree points as candidates, and the float32 minimum and its lowest index are computed outright."""
     t = np.ascontiguousarray(np.asarray(tree_xyz, np.float32).reshape(-1, 3))
     q = np.ascontiguousarray(np.asarray(query_xyz, np.float32).reshape(-1, 3))
     if len(t) == 0:
@@ -145,9 +150,12 @@ def nearest_f32(tree_xyz, query_xyz, tree_key=None):
     cnt = tree.query_ball_point(q64, r, workers=-1, return_length=True)
     d2 = _l2_simple(q, t[idx])
     tied = np.zeros(len(q), bool)
-    multi = np.nonzero(cnt > 1)[0]
+    overflowed = ~np.isfinite(d2)
+    multi = np.nonzero((cnt > 1) | (overflowed & (len(t) > 1)))[0]
     if len(multi):
         lists = tree.query_ball_point(q64[multi], r[multi], workers=-1)
+        everything = np.arange(len(t), dtype=np.int64)
+        lists = [everything if o else c for c, o in zip(lists, overflowed[multi])]
         lens = np.array([len(c) for c in lists], np.int64)
         cand = np.concatenate([np.asarray(c, np.int64) for c in lists])
         owner = np.repeat(np.arange(len(multi)), lens)

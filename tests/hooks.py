@@ -70,3 +70,60 @@ def radix_sort_u32(g, keys, bits):
 
 def debug_rebuild_outskirts(g):
     g._check(erasor_amd.lib().erasor_hip_debug_rebuild_outskirts(g._h))
+
+
+def debug_nn_tree(g, cloud):
+    """the bounding-volume tree nn_pad / nn_tree build over `cloud` (N x 4 rows): P, the points in key order, their original indices,
+    the sorted Morton keys, lo / hi of the 2P nodes (node 0 is unused)"""
+    cloud = np.ascontiguousarray(cloud, np.float32).reshape(-1, 4)
+    n = len(cloud)
+    cap = 4 * (n // 32 + 1) + 4  # (at least 2P: P < 2 * ceil(n / 32))
+    P = C.c_uint32(0)
+    pts, idx, keys = np.zeros((n, 4), np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    lo, hi = np.zeros((cap, 4), np.float32), np.zeros((cap, 4), np.float32)
+    g._check(erasor_amd.lib().erasor_hip_debug_nn_tree(g._h, _p(cloud), C.c_size_t(n), C.c_int(0), C.byref(P), _p(pts), _p(idx), _p(keys), _p(lo),
+                                                       _p(hi), C.c_size_t(cap)))
+    P = int(P.value)
+    return {"P": P, "pts": pts, "idx": idx, "keys": keys, "lo": lo[: 2 * P], "hi": hi[: 2 * P]}
+
+
+def debug_nn_effort(g, tree, queries, f32):
+    """k_nn_query (f32 False) or k_lm_query (f32 True) of `queries` over the tree of `tree`, with effort[i] = (leaves opened, leaf points
+    tested) of query i beside the kernel's outputs: "dist" / "nearest", or "rows" / "n_tied" """
+    tree = np.ascontiguousarray(tree, np.float32).reshape(-1, 4)
+    q = np.ascontiguousarray(queries, np.float32).reshape(-1, 4)
+    nq = len(q)
+    dist, near = np.zeros(nq, np.float64), np.zeros(nq, np.uint32)
+    rows, tied, effort = np.zeros((nq, 4), np.float32), C.c_uint64(0), np.zeros((nq, 2), np.uint32)
+    g._check(erasor_amd.lib().erasor_hip_debug_nn_effort(g._h, _p(tree), C.c_size_t(len(tree)), _p(q), C.c_size_t(nq), C.c_int(int(f32)), _p(dist),
+                                                         _p(near), _p(rows), C.byref(tied), _p(effort)))
+    out = {"effort": effort}
+    out.update({"rows": rows, "n_tied": int(tied.value)} if f32 else {"dist": dist, "nearest": near})
+    return out
+
+
+def debug_ev_grid(g, est, voxelsize):
+    """the evaluator's hashed grid over `est` (N x 4 rows): nb, off[nb + 1], the scattered points and their original indices"""
+    est = np.ascontiguousarray(est, np.float32).reshape(-1, 4)
+    n = len(est)
+    cap = 2 * max(n, 1024) + 2
+    nb = C.c_uint32(0)
+    off, pts, idx = np.zeros(cap, np.uint32), np.zeros((n, 4), np.float32), np.zeros(n, np.uint32)
+    g._check(erasor_amd.lib().erasor_hip_debug_ev_grid(g._h, _p(est), C.c_size_t(n), C.c_double(voxelsize), C.byref(nb), _p(off), C.c_size_t(cap),
+                                                       _p(pts), _p(idx)))
+    return {"nb": int(nb.value), "off": off[: nb.value + 1], "pts": pts, "idx": idx}
+
+
+def debug_ev_grid_many(g, ests, voxelsize):
+    """evaluate_many's combined table over `ests`: as debug_ev_grid over all estimates back to back, plus "tab": one
+    (first point, points, first bucket, bucket mask) row per estimate"""
+    ests = [np.ascontiguousarray(e, np.float32).reshape(-1, 4) for e in ests]
+    k, n = len(ests), sum(len(e) for e in ests)
+    cap = sum(2 * max(len(e), 1024) for e in ests) + 2
+    ptrs = (C.c_void_p * k)(*[_p(e) for e in ests])
+    sizes = (C.c_size_t * k)(*[len(e) for e in ests])
+    nb = C.c_uint32(0)
+    off, pts, idx, tab = np.zeros(cap, np.uint32), np.zeros((n, 4), np.float32), np.zeros(n, np.uint32), np.zeros((k, 4), np.uint32)
+    g._check(erasor_amd.lib().erasor_hip_debug_ev_grid_many(g._h, ptrs, sizes, C.c_size_t(k), C.c_double(voxelsize), C.byref(nb), _p(off),
+                                                            C.c_size_t(cap), _p(pts), _p(idx), _p(tab)))
+    return {"nb": int(nb.value), "off": off[: nb.value + 1], "pts": pts, "idx": idx, "tab": tab}

@@ -136,11 +136,36 @@ def test_exact_sort_long_segments_reach_the_final_kernel(gpu_mod):
     assert "LONG-SEGMENTS-OK" in out.stdout, out.stdout + out.stderr
 
 
-@pytest.mark.parametrize("n,B", [(0, 900), (5, 900), (12453, 900), (100000, 2160), (300001, 2160)])
+RTILE = 2048  # keys per workgroup of one radix pass (kernels.hip.h)
+
+
+def radix_keys(n, bits_, kind):
+    """keys of the widths the sort's newer callers use (30: the tree's Morton keys, 32: the instance rows' labels)"""
+    rng = np.random.default_rng(n + bits_)
+    if kind == "full":  # the whole range of the width, its two ends included
+        k = rng.integers(0, 1 << bits_, n, dtype=np.uint64)
+        k[: min(n, 2)] = [(1 << bits_) - 1, 0][: min(n, 2)]
+    elif kind == "top_byte":  # equal below the last pass's digit: only that pass orders them, every earlier one must keep the order
+        k = (rng.integers(0, 1 << (bits_ - 24), n, dtype=np.uint64) << np.uint64(24)) | np.uint64(0x5A5A5A)
+    else:  # all equal: the permutation is the identity
+        k = np.full(n, (1 << bits_) - 77, np.uint64)
+    return k.astype(np.uint32)
+
+
+WIDE = [pytest.param(n, (bits_, kind), id="%d-%dbit-%s" % (n, bits_, kind)) for bits_ in (30, 32) for kind in ("full", "top_byte", "equal")
+        for n in (1, RTILE - 1, RTILE, RTILE + 1, 300001)]
+
+
+@pytest.mark.parametrize("n,B", [(0, 900), (5, 900), (12453, 900), (100000, 2160), (300001, 2160)] + WIDE)
 def test_stable_radix_bucketing(gpu_mod, n, B):
+    """B: a bucket count (keys in [0, B], sorted at its bit width), or (bits, kind): keys of radix_keys at the width a caller uses"""
     g = gpu_mod.Erasor(gpu_mod.params_default())
-    k = np.random.default_rng(n).integers(0, B + 1, n).astype(np.uint32)
-    ko, po = hooks.radix_sort_u32(g, k, max(1, int(np.ceil(np.log2(B + 1)))))
+    if isinstance(B, tuple):
+        k, nbits = radix_keys(n, *B), B[0]
+    else:
+        k = np.random.default_rng(n).integers(0, B + 1, n).astype(np.uint32)
+        nbits = max(1, int(np.ceil(np.log2(B + 1))))
+    ko, po = hooks.radix_sort_u32(g, k, nbits)
     order = np.argsort(k, kind="stable").astype(np.uint32)
     same(ko, k[order])
     same(po, order)
