@@ -94,6 +94,88 @@ class ComplementResult(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class RenderView(C.Structure):
+    """erasor_render_view (include/erasor_hip.h): the window of a bird's-eye image"""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("res", C.c_double), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("z_lo", C.c_double), ("z_hi", C.c_double), ("background", C.c_uint32), ("reserved_", C.c_uint32)]
+
+    def as_dict(self):
+        """evalmap.render_view's keys"""
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+    @classmethod
+    def of(cls, v):
+        """from a RenderView or a dict with evalmap.render_view's keys"""
+        return v if isinstance(v, cls) else cls(**{k: v[k] for k, _ in cls._fields_ if k != "reserved_"})
+
+
+class RenderStats(C.Structure):
+    """erasor_render_stats (include/erasor_hip.h)"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_drawn", "n_outside", "n_nonfinite", "n_pixels_hit")] + [
+        ("cat_points", C.c_uint64 * 8), ("cat_pixels", C.c_uint64 * 8)]
+
+    def as_dict(self):
+        """evalmap.render's stats keys"""
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_[:5]}
+        d["cat_points"] = [int(v) for v in self.cat_points]
+        d["cat_pixels"] = [int(v) for v in self.cat_pixels]
+        return d
+
+
+RENDER_LABEL, RENDER_HEIGHT, RENDER_EVAL = 0, 1, 2
+RENDER_MODES = {"label": RENDER_LABEL, "height": RENDER_HEIGHT}
+
+
+def write_ppm(path, img):
+    """an H x W x 3 uint8 image as a binary PPM (P6, maxval 255)"""
+    img = np.ascontiguousarray(img, np.uint8)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("write_ppm: the image must be H x W x 3")
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
+        f.write(img.tobytes())
+
+
+def read_ppm(path):
+    """a binary PPM (P6, maxval 255; comments allowed in the header) as an H x W x 3 uint8 array"""
+    with open(path, "rb") as f:
+        data = f.read()
+    pos, tok = 0, []
+    while len(tok) < 4:
+        while data[pos:pos + 1].isspace():
+            pos += 1
+        if data[pos:pos + 1] == b"#":
+            pos = data.index(b"\n", pos) + 1
+            continue
+        end = pos
+        while end < len(data) and not data[end:end + 1].isspace():
+            end += 1
+        tok.append(data[pos:end])
+        pos = end
+    if tok[0] != b"P6" or int(tok[3]) != 255:
+        raise ValueError("read_ppm: not a binary PPM with maxval 255")
+    w, h = int(tok[1]), int(tok[2])
+    pos += 1  # (the single whitespace after maxval)
+    if len(data) - pos < w * h * 3:
+        raise ValueError("read_ppm: truncated file")
+    return np.frombuffer(data, np.uint8, w * h * 3, pos).reshape(h, w, 3).copy()
+
+
+def hstack_panels(imgs, gap=4, background=0):
+    """images of one height side by side, left to right, `gap` pixels of `background` (0xRRGGBB) between neighbours"""
+    imgs = [np.asarray(i, np.uint8) for i in imgs]
+    if not imgs or any(i.ndim != 3 or i.shape[2] != 3 or i.shape[0] != imgs[0].shape[0] for i in imgs):
+        raise ValueError("hstack_panels: H x W x 3 images of one height")
+    h = imgs[0].shape[0]
+    out = np.empty((h, sum(i.shape[1] for i in imgs) + gap * (len(imgs) - 1), 3), np.uint8)
+    out[:] = [(background >> 16) & 0xFF, (background >> 8) & 0xFF, background & 0xFF]
+    x = 0
+    for i in imgs:
+        out[:, x:x + i.shape[1]] = i
+        x += i.shape[1] + gap
+    return out
+
+
 class SweepRow(C.Structure):
     """erasor_sweep_row (include/erasor_hip.h): one configuration of a sweep"""
     _fields_ = [("params", Params), ("status", C.c_int32), ("n_steps", C.c_uint32), ("n_map_final", C.c_uint64), ("n_saved", C.c_uint64),
@@ -175,7 +257,7 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "revert_bins.hip.h",
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "render.hip.h", "revert_bins.hip.h",
                                                  "exact_sort.hip.h", "exact_sort_core.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
@@ -589,6 +671,79 @@ class Erasor:
         kept = []
         g = self._eval_cloud(gt, kept)
         return self._by_class(lib().erasor_hip_evaluate_map_by_class, g, voxel_leaf, voxelsize)
+
+    # -- bird's-eye images (viz_kitti_map.cpp, compare_map.cpp as image files; the same on the host: evalmap.render / render_eval) --
+    def render_fit(self, cloud=None, res=0.2, margin=2, background=0):
+        """the view that contains every finite point of `cloud` (a cloud as for evaluate; None: the handle's map), as a dict with
+        evalmap.render_view's keys (erasor_hip_render_fit / _fit_map)"""
+        v = RenderView()
+        if cloud is None:
+            self._check(lib().erasor_hip_render_fit_map(self._h, C.c_double(res), C.c_uint32(margin), C.c_uint32(background), C.byref(v)))
+        else:
+            kept = []
+            c = self._eval_cloud(cloud, kept)
+            self._check(lib().erasor_hip_render_fit(self._h, *c, C.c_double(res), C.c_uint32(margin), C.c_uint32(background), C.byref(v)))
+        return v.as_dict()
+
+    @staticmethod
+    def _render_args(view, mode, target_class, target_instance):
+        v = RenderView.of(view)
+        img = np.empty((v.height, v.width, 3), np.uint8)
+        if mode is None:
+            return v, img, (C.byref(v), _p(img), C.c_int(0))
+        if mode not in RENDER_MODES:
+            raise ValueError("render: mode must be 'label' or 'height'")
+        tc = -1 if target_class is None else int(target_class)
+        ti = -1 if target_instance is None else int(target_instance)
+        return v, img, (C.c_int(RENDER_MODES[mode]), C.c_int32(tc), C.c_int32(ti), C.byref(v), _p(img), C.c_int(0))
+
+    def render(self, cloud, view=None, res=0.2, mode="label", target_class=None, target_instance=None):
+        """`cloud` (as for evaluate) as a bird's-eye image (erasor_hip_render_clouds): (uint8 array H x W x 3, stats dict).  view: a dict
+        with evalmap.render_view's keys; None fits one at `res`.  mode "label": static / dynamic / target_class (and
+        target_instance) by label; "height": one colour, for maps without labels."""
+        if view is None:
+            view = self.render_fit(cloud, res)
+        v, img, tail = self._render_args(view, mode, target_class, target_instance)
+        kept = []
+        c = self._eval_cloud(cloud, kept)
+        st = RenderStats()
+        self._check(lib().erasor_hip_render_clouds(self._h, *c, *tail, C.byref(st)))
+        return img, st.as_dict()
+
+    def render_map(self, view=None, res=0.2, mode="label", target_class=None, target_instance=None):
+        """render of the handle's current map (the get_map view, never copied to the host; erasor_hip_render_map)"""
+        if view is None:
+            view = self.render_fit(None, res)
+        v, img, tail = self._render_args(view, mode, target_class, target_instance)
+        st = RenderStats()
+        self._check(lib().erasor_hip_render_map(self._h, *tail, C.byref(st)))
+        return img, st.as_dict()
+
+    def render_eval(self, gt, est, view=None, res=0.2, voxelsize=0.2, voxel_leaf=0.0):
+        """the error map (erasor_hip_render_eval_clouds): evaluate(gt, est, voxelsize, voxel_leaf) and the ground truth drawn by its
+        decision per point -- static kept grey, dynamic removed green, static lost blue, dynamic left red, errors on top.  Returns
+        (image, stats, evaluate's dict).  view None: fitted to `gt` at `res`."""
+        if view is None:
+            view = self.render_fit(gt, res)
+        v, img, tail = self._render_args(view, None, None, None)
+        kept = []
+        g = self._eval_cloud(gt, kept)
+        e = self._eval_cloud(est, kept)
+        st, r = RenderStats(), EvalResult()
+        self._check(lib().erasor_hip_render_eval_clouds(self._h, *g, *e, C.c_double(voxel_leaf), C.c_double(voxelsize), *tail, C.byref(st),
+                                                        C.byref(r)))
+        return img, st.as_dict(), r.as_dict()
+
+    def render_eval_map(self, gt, view=None, res=0.2, voxelsize=0.2, voxel_leaf=0.0):
+        """render_eval with the handle's current map as the estimate (erasor_hip_render_eval_map)"""
+        if view is None:
+            view = self.render_fit(gt, res)
+        v, img, tail = self._render_args(view, None, None, None)
+        kept = []
+        g = self._eval_cloud(gt, kept)
+        st, r = RenderStats(), EvalResult()
+        self._check(lib().erasor_hip_render_eval_map(self._h, *g, C.c_double(voxel_leaf), C.c_double(voxelsize), *tail, C.byref(st), C.byref(r)))
+        return img, st.as_dict(), r.as_dict()
 
     # -- the estimate-to-ground-truth overlap report (scripts/analysis_runner.py:53-71; the same on the host: evalmap.overlap) --
     def overlap(self, gt, est, voxelsize=0.2, voxel_leaf=0.0, per_point=False):

@@ -37,6 +37,7 @@
 #include "evaluate.hip.h"
 #include "nearest.hip.h"
 #include "align.hip.h"
+#include "render.hip.h"
 
 using namespace ek;
 
@@ -334,6 +335,13 @@ struct erasor_hip_handle {
         std::vector<EvmEst> dbg_tab;           // evm_run: the estimates' table
 #endif
         DBuf<unsigned long long> em_ctr;
+        // bird's-eye images (erasor_hip_render_*): the renderer's own copies of a host cloud and of the map, every point's tile and
+        // record, the tile histogram and its scan, the records sorted by tile, the counters, the heights for the fit's select and the
+        // box, and the image
+        DBuf<float4> rd_pts, rd_map;
+        DBuf<uint32_t> rd_tile, rd_cnt, rd_pl, rd_tops, rd_bb;
+        DBuf<unsigned long long> rd_rec, rd_srt, rd_ctr, rd_zb;
+        DBuf<uint8_t> rd_img;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
     // ---- per-bin scratch (R-GPF / bin voxelise global paths) ----
@@ -1105,6 +1113,8 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->ev.fm_out); release(h->ev.fm_flag); release(h->ev.fm_pl); release(h->ev.fm_tops); release(h->ev.fm_ctr);
     release(h->ev.al_off); release(h->ev.al_wg); release(h->ev.al_xf); release(h->ev.al_ctr); release(h->ev.al_val); release(h->ev.al_rank);
     release(h->ev.em_cat); release(h->ev.em_tab); release(h->ev.em_ctr);
+    release(h->ev.rd_pts); release(h->ev.rd_map); release(h->ev.rd_tile); release(h->ev.rd_cnt); release(h->ev.rd_pl); release(h->ev.rd_tops);
+    release(h->ev.rd_bb); release(h->ev.rd_rec); release(h->ev.rd_srt); release(h->ev.rd_ctr); release(h->ev.rd_zb); release(h->ev.rd_img);
     for (int k = 0; k < NSIDE; ++k) {
         if (h->q[k].ev_keys) (void)hipEventDestroy(h->q[k].ev_keys);
         if (h->q[k].ev_done) (void)hipEventDestroy(h->q[k].ev_done);
@@ -3390,8 +3400,9 @@ static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t n
 // n_rec (the breakdown by class): the kernels also fill the per-key table E.bc_tab and the dynamic points' records; *n_rec = their count.
 static void ev_fill(const unsigned long long c[EV_NCTR], erasor_eval_result *res);
 static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize, uint8_t *per_gt,
-                  erasor_eval_result *res, uint32_t *n_rec = nullptr) {
+                  erasor_eval_result *res, uint32_t *n_rec = nullptr, bool codes_on_device = false) {
     auto &E = h->ev;
+    const bool want_codes = per_gt || codes_on_device;  // (codes_on_device: E.code keeps them for the renderer, no host copy)
     uint32_t nb = 1024;  // buckets: a power of two >= the estimate's size (<= 1 point per bucket on average)
     while (nb < n_est) nb <<= 1;
 #ifdef ERASOR_HIP_TEST_HOOKS
@@ -3399,7 +3410,7 @@ static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const f
 #endif
     if (ensure(h, E.ctr, EV_NCTR) || ensure(h, E.cnt, (size_t)nb + 1) || ensure(h, E.pl, (size_t)nb + 1) || ensure(h, E.tops, nb / 1024 + 4) ||
         ensure(h, E.bkt, (size_t)n_est + 1) || ensure(h, E.pts, (size_t)n_est + 1) || ensure(h, E.idx, (size_t)n_est + 1) ||
-        (per_gt && ensure(h, E.code, (size_t)n_gt + 1)))
+        (want_codes && ensure(h, E.code, (size_t)n_gt + 1)))
         return ERASOR_E_NO_DEVICE;
     const size_t n_all = (size_t)n_gt + n_est;  // (< 2^31: each cloud has at most 2^30 points)
     if (n_rec && (ensure(h, E.bc_tab, (size_t)EV_NKEYS * EV_KC) || ensure(h, E.bc_cur, 4) || ensure(h, E.bc_ikey, n_all + 1) ||
@@ -3433,7 +3444,7 @@ static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const f
                (const uint32_t *)E.cnt.p, nb - 1, n_est, voxelsize, thr, E.ctr.p, E.bc_tab.p, E.bc_cur.p, E.bc_ikey.p, E.bc_ival.p);
     else if (n_gt)
         LAUNCH(h, "ev_query", k_ev_query, cdiv(n_gt, 256), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p, (const uint32_t *)E.cnt.p,
-               nb - 1, n_est, voxelsize, thr, per_gt ? E.code.p : (uint8_t *)nullptr, E.ctr.p);
+               nb - 1, n_est, voxelsize, thr, want_codes ? E.code.p : (uint8_t *)nullptr, E.ctr.p);
     unsigned long long c[EV_NCTR];
     HIPC(h, hipMemcpyAsync(c, E.ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
     if (n_rec) HIPC(h, hipMemcpyAsync(n_rec, E.bc_cur.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
@@ -3828,14 +3839,15 @@ static void ov_ranks(uint64_t n, uint64_t rk[OV_SEL_MAX], double *g90, double *g
 
 // the exact radix select over the bit patterns v[0 .. count), driven from the host (k_ov_select_hist): the values at the ranks rk, from the
 // top digit down; every target keeps its prefix and its rank inside that prefix.  Values above every rank (align's sentinel) never matter.
-static int ov_select(erasor_hip_handle *h, const unsigned long long *v, uint32_t count, const uint64_t rk[OV_SEL_MAX], double out[OV_SEL_MAX]) {
+static int ov_select(erasor_hip_handle *h, const unsigned long long *v, uint32_t count, const uint64_t rk[OV_SEL_MAX], double out[OV_SEL_MAX],
+                     int top_shift = 56) {  // (top_shift: the highest digit that can differ -- 24 for values below 2^32)
     auto &E = h->ev;
     unsigned long long pref[OV_SEL_MAX] = {};
     uint64_t left[OV_SEL_MAX];
     for (uint32_t t = 0; t < OV_SEL_MAX; ++t) left[t] = rk[t];
     std::vector<uint32_t> hist(OV_SEL_MAX * 256);
     const uint32_t grid = std::min(cdiv(count, 256 * 8), 1024u);
-    for (int shift = 56; shift >= 0; shift -= 8) {
+    for (int shift = top_shift; shift >= 0; shift -= 8) {
         OvSelect s;
         memset(&s, 0, sizeof(s));
         s.shift = shift;
@@ -4444,6 +4456,378 @@ int erasor_hip_evaluate_map_by_class(erasor_hip_handle *h, const void *gt_xyzi, 
     }
     return bc_run(h, g, ng, e, ne, voxelsize, classes, cap_classes, n_classes, instances, cap_instances, n_instances, res);
 }
+
+// ---- bird's-eye images (erasor_hip_render_*; kernels: render.hip.h) ----
+// Like ev_run: the main stream, behind whatever a collected step launched ahead there; scratch of the renderer's own (h->ev.rd_*).
+static constexpr uint32_t RD_MAX_EDGE = 16384u;
+static constexpr uint64_t RD_MAX_PIXELS = 1ull << 26;
+
+static int rd_check_view(erasor_hip_handle *h, const erasor_render_view *v) {
+    if (!v) {
+        h->err = "erasor_hip_render: view is NULL";
+        return ERASOR_E_INVALID;
+    }
+    if (!(v->res > 0) || !std::isfinite(v->res) || !std::isfinite(v->x0) || !std::isfinite(v->y0) || !std::isfinite(v->z_lo) || !std::isfinite(v->z_hi)) {
+        h->err = "erasor_hip_render: the view needs a finite res > 0 and finite x0, y0, z_lo, z_hi";
+        return ERASOR_E_INVALID;
+    }
+    if (v->width < 1 || v->height < 1 || v->width > RD_MAX_EDGE || v->height > RD_MAX_EDGE || (uint64_t)v->width * v->height > RD_MAX_PIXELS) {
+        h->err = "erasor_hip_render: the view needs 1 <= width, height <= 16384 and width * height <= 2^26 (got " + std::to_string(v->width) + " x " +
+                 std::to_string(v->height) + ")";
+        return ERASOR_E_INVALID;
+    }
+    return ERASOR_OK;
+}
+
+// the kernels' view and mode from the caller's
+static RdView rd_view(const erasor_render_view *view) {
+    RdView v;
+    v.x0 = view->x0;
+    v.y0 = view->y0;
+    v.res = view->res;
+    v.z_lo = view->z_lo;
+    v.z_hi = view->z_hi;
+    v.width = view->width;
+    v.height = view->height;
+    v.tiles_x = cdiv(view->width, RD_TILE);
+    v.background = view->background & 0xFFFFFFu;
+    return v;
+}
+static RdMode rd_mode(int mode, int32_t target_class, int32_t target_instance) {
+    RdMode m;
+    m.mode = (uint32_t)mode;
+    m.target_class = mode == ERASOR_RENDER_LABEL ? target_class : -1;
+    m.target_instance = target_instance;
+    for (uint32_t c = 0; c < RD_NCAT; ++c) m.palette[c] = ERASOR_RENDER_PALETTE[c];
+    return m;
+}
+static void rd_stats(const unsigned long long c[RD_NCTR], uint64_t n, erasor_render_stats *stats) {
+    erasor_render_stats s;
+    memset(&s, 0, sizeof(s));
+    s.n_points = n;
+    s.n_outside = c[RD_C_OUTSIDE];
+    s.n_nonfinite = c[RD_C_NONFINITE];
+    for (uint32_t k = 0; k < RD_NCAT; ++k) {
+        s.cat_points[k] = c[RD_C_CATPTS + k];
+        s.cat_pixels[k] = c[RD_C_CATPIX + k];
+        s.n_drawn += s.cat_points[k];
+        s.n_pixels_hit += s.cat_pixels[k];
+    }
+    *stats = s;
+}
+
+// the view fitted to pts[0 .. n) (device); see erasor_hip_render_fit
+static int rd_fit(erasor_hip_handle *h, const float4 *pts, uint32_t n, double res, uint32_t margin, uint32_t background, erasor_render_view *view) {
+    auto &E = h->ev;
+    if (!view) {
+        h->err = "erasor_hip_render_fit: view is NULL";
+        return ERASOR_E_INVALID;
+    }
+    if (!(res > 0) || !std::isfinite(res) || margin < 1 || margin > 1024) {
+        h->err = "erasor_hip_render_fit: res must be a finite number > 0 and margin_px in 1 .. 1024";
+        return ERASOR_E_INVALID;
+    }
+    if (ensure(h, E.rd_zb, (size_t)n + 1) || ensure(h, E.rd_bb, 4) || ensure(h, E.rd_ctr, RD_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256))
+        return ERASOR_E_NO_DEVICE;
+    struct KeepCur {
+        erasor_hip_handle *h;
+        hipStream_t keep;
+        ~KeepCur() { h->cur = keep; }
+    } kc{h, h->cur};
+    h->cur = h->stream;
+    HIPC(h, hipMemsetAsync(E.rd_bb.p, 0xFF, 2 * sizeof(uint32_t), h->stream));
+    HIPC(h, hipMemsetAsync(E.rd_bb.p + 2, 0, 2 * sizeof(uint32_t), h->stream));
+    HIPC(h, hipMemsetAsync(E.rd_ctr.p, 0, sizeof(unsigned long long), h->stream));
+    if (n) LAUNCH(h, "render_fit", k_rd_fit, cdiv(n, 2048), 256, pts, n, E.rd_zb.p, E.rd_bb.p, E.rd_ctr.p);
+    uint32_t bb[4];
+    unsigned long long nfin = 0;
+    HIPC(h, hipMemcpyAsync(bb, E.rd_bb.p, sizeof(bb), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipMemcpyAsync(&nfin, E.rd_ctr.p, sizeof(nfin), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (!nfin) {
+        h->err = "erasor_hip_render_fit: the cloud has no finite point";
+        return ERASOR_E_INVALID;
+    }
+    auto inv = [](uint32_t k) {  // (rd_zinv on the host)
+        const uint32_t b = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
+        float f;
+        memcpy(&f, &b, sizeof(f));
+        return (double)f;
+    };
+    const double mn[2] = {inv(bb[0]), inv(bb[1])}, mx[2] = {inv(bb[2]), inv(bb[3])};
+    double o[2], sz[2];
+    for (int a = 0; a < 2; ++a) {
+        o[a] = floor(mn[a] / res) * res - (double)margin * res;
+        sz[a] = floor((mx[a] - o[a]) / res) + 1.0 + (double)margin;
+    }
+    if (!std::isfinite(o[0]) || !std::isfinite(o[1]) || !(sz[0] <= RD_MAX_EDGE) || !(sz[1] <= RD_MAX_EDGE) || !(sz[0] * sz[1] <= (double)RD_MAX_PIXELS)) {
+        // the smallest res that fits: the sizes at res r are about span / r + 2 * margin + 2
+        const double sx = mx[0] - mn[0], sy = mx[1] - mn[1], pad = 2.0 * margin + 2.0;
+        double lo = res, hi = res;
+        auto fits = [&](double r) {
+            const double w = sx / r + pad, hh = sy / r + pad;
+            return w <= RD_MAX_EDGE && hh <= RD_MAX_EDGE && w * hh <= (double)RD_MAX_PIXELS;
+        };
+        while (!fits(hi) && hi < 1e300) hi *= 2;
+        for (int it = 0; it < 60; ++it) {
+            const double mid = 0.5 * (lo + hi);
+            (fits(mid) ? hi : lo) = mid;
+        }
+        char buf[256];
+        snprintf(buf, sizeof(buf), "erasor_hip_render_fit: at res %g the image would be %.0f x %.0f pixels (limits: 16384 per edge, 2^26 in all); "
+                 "the smallest res that fits is about %.3g", res, sz[0], sz[1], hi * 1.001);
+        h->err = buf;
+        return ERASOR_E_INVALID;
+    }
+    // z_lo / z_hi: the values at ranks floor(0.02 (n - 1)) and floor(0.98 (n - 1)) of the finite heights
+    uint64_t rk[OV_SEL_MAX];
+    rk[0] = (uint64_t)floor(0.02 * (double)(nfin - 1));
+    rk[1] = (uint64_t)floor(0.98 * (double)(nfin - 1));
+    for (uint32_t t = 2; t < OV_SEL_MAX; ++t) rk[t] = rk[0];
+    double sel[OV_SEL_MAX];
+    const int rc = ov_select(h, E.rd_zb.p, n, rk, sel, 24);
+    if (rc) return rc;
+    unsigned long long kz[2];
+    memcpy(kz, sel, sizeof(kz));
+    memset(view, 0, sizeof(*view));
+    view->x0 = o[0];
+    view->y0 = o[1];
+    view->res = res;
+    view->width = (uint32_t)sz[0];
+    view->height = (uint32_t)sz[1];
+    view->z_lo = inv((uint32_t)kz[0]);
+    view->z_hi = inv((uint32_t)kz[1]);
+    view->background = background & 0xFFFFFFu;
+    return ERASOR_OK;
+}
+
+// pts[0 .. n) (device; code: the evaluator's per-point codes for ERASOR_RENDER_EVAL) into rgb and stats
+static int rd_run(erasor_hip_handle *h, const float4 *pts, uint32_t n, const uint8_t *code, int mode, int32_t target_class, int32_t target_instance,
+                  const erasor_render_view *view, void *rgb, int rgb_is_device, erasor_render_stats *stats, hipEvent_t ev_begin = nullptr,
+                  hipEvent_t ev_end = nullptr) {  // (ev_begin / ev_end: recorded around the clears and the launches, for the hooks' timing)
+    auto &E = h->ev;
+    const int rc = rd_check_view(h, view);
+    if (rc) return rc;
+    const RdView v = rd_view(view);
+    const RdMode m = rd_mode(mode, target_class, target_instance);
+    const uint32_t ntiles = v.tiles_x * cdiv(view->height, RD_TILE);
+    const size_t bytes = (size_t)view->width * view->height * 3;
+    if (ensure(h, E.rd_ctr, RD_NCTR) || ensure(h, E.rd_cnt, (size_t)ntiles + 1) || ensure(h, E.rd_pl, (size_t)ntiles + 1) ||
+        ensure(h, E.rd_tops, ntiles / 1024 + 4) || ensure(h, E.rd_tile, (size_t)n + 1) || ensure(h, E.rd_rec, (size_t)n + 1) ||
+        ensure(h, E.rd_srt, (size_t)n + 1) || ensure(h, E.rd_img, bytes + 4))
+        return ERASOR_E_NO_DEVICE;
+    struct KeepCur {
+        erasor_hip_handle *h;
+        hipStream_t keep;
+        ~KeepCur() { h->cur = keep; }
+    } kc{h, h->cur};
+    h->cur = h->stream;
+    if (ev_begin) HIPC(h, hipEventRecord(ev_begin, h->stream));
+    HIPC(h, hipMemsetAsync(E.rd_ctr.p, 0, RD_NCTR * sizeof(unsigned long long), h->stream));
+    HIPC(h, hipMemsetAsync(E.rd_cnt.p, 0, ((size_t)ntiles + 1) * sizeof(uint32_t), h->stream));
+    if (n) LAUNCH(h, "render_bin", k_rd_bin, cdiv(n, 256), 256, pts, n, code, v, m, E.rd_tile.p, E.rd_rec.p, E.rd_cnt.p, E.rd_ctr.p);
+    scan_u32(h, E.rd_cnt.p, E.rd_pl.p, E.rd_tops.p, ntiles + 1, ntiles + 1, nullptr, nullptr, "render_scan");
+    LAUNCH(h, "render_scan", k_ev_offsets, cdiv(ntiles + 1, 256), 256, (const uint32_t *)E.rd_pl.p, (const uint32_t *)E.rd_tops.p, ntiles + 1, E.rd_cnt.p,
+           E.rd_pl.p);
+    if (n)
+        LAUNCH(h, "render_scatter", k_rd_scatter, cdiv(n, 256), 256, (const uint32_t *)E.rd_tile.p, (const unsigned long long *)E.rd_rec.p, n, E.rd_pl.p,
+               E.rd_srt.p);
+    LAUNCH(h, "render_resolve", k_rd_resolve, ntiles, 256, (const unsigned long long *)E.rd_srt.p, (const uint32_t *)E.rd_cnt.p, v, m, E.rd_img.p,
+           E.rd_ctr.p);
+    if (ev_end) HIPC(h, hipEventRecord(ev_end, h->stream));
+    unsigned long long c[RD_NCTR];
+    HIPC(h, hipMemcpyAsync(c, E.rd_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    if (rgb) HIPC(h, hipMemcpyAsync(rgb, E.rd_img.p, bytes, rgb_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (stats) rd_stats(c, n, stats);
+    return ERASOR_OK;
+}
+
+static int rd_check_cloud(erasor_hip_handle *h, const char *who, const void *xyzi, size_t n) {
+    if ((!xyzi && n) || n > 0x3FFFFFFFull) {
+        h->err = std::string(who) + ": NULL cloud or more than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    return ERASOR_OK;
+}
+// the handle's map as one dense device array in the renderer's scratch
+static int rd_map(erasor_hip_handle *h, const char *who, const float4 **pts, uint32_t *n) {
+    if (!h->have_map) {
+        h->err = std::string(who) + ": the handle has no map (erasor_hip_set_map first)";
+        return ERASOR_E_STATE;
+    }
+    size_t n_map = 0;
+    const int rc = map_to_device(h, h->ev.rd_map, &n_map);
+    if (rc) return rc;
+    if (n_map > 0x3FFFFFFFull) {
+        h->err = std::string(who) + ": map larger than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    *pts = h->ev.rd_map.p;
+    *n = (uint32_t)n_map;
+    return ERASOR_OK;
+}
+
+int erasor_hip_render_fit(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, double res, uint32_t margin_px, uint32_t background,
+                          erasor_render_view *view) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = rd_check_cloud(h, "erasor_hip_render_fit", xyzi, n);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    if ((rc = ev_input(h, xyzi, n, is_device, h->ev.rd_pts, &p))) return rc;
+    return rd_fit(h, p, (uint32_t)n, res, margin_px, background, view);
+}
+int erasor_hip_render_fit_map(erasor_hip_handle *h, double res, uint32_t margin_px, uint32_t background, erasor_render_view *view) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    uint32_t n = 0;
+    const int rc = rd_map(h, "erasor_hip_render_fit_map", &p, &n);
+    if (rc) return rc;
+    return rd_fit(h, p, n, res, margin_px, background, view);
+}
+
+static int rd_check_mode(erasor_hip_handle *h, int mode) {
+    if (mode != ERASOR_RENDER_LABEL && mode != ERASOR_RENDER_HEIGHT) {
+        h->err = "erasor_hip_render: mode must be ERASOR_RENDER_LABEL or ERASOR_RENDER_HEIGHT (the error map: erasor_hip_render_eval_*)";
+        return ERASOR_E_INVALID;
+    }
+    return ERASOR_OK;
+}
+int erasor_hip_render_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, int mode, int32_t target_class, int32_t target_instance,
+                             const erasor_render_view *view, void *rgb, int rgb_is_device, erasor_render_stats *stats) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = rd_check_mode(h, mode);
+    if (rc || (rc = rd_check_view(h, view)) || (rc = rd_check_cloud(h, "erasor_hip_render_clouds", xyzi, n))) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    if ((rc = ev_input(h, xyzi, n, is_device, h->ev.rd_pts, &p))) return rc;
+    return rd_run(h, p, (uint32_t)n, nullptr, mode, target_class, target_instance, view, rgb, rgb_is_device, stats);
+}
+int erasor_hip_render_map(erasor_hip_handle *h, int mode, int32_t target_class, int32_t target_instance, const erasor_render_view *view, void *rgb,
+                          int rgb_is_device, erasor_render_stats *stats) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = rd_check_mode(h, mode);
+    if (rc || (rc = rd_check_view(h, view))) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    uint32_t n = 0;
+    if ((rc = rd_map(h, "erasor_hip_render_map", &p, &n))) return rc;
+    return rd_run(h, p, n, nullptr, mode, target_class, target_instance, view, rgb, rgb_is_device, stats);
+}
+
+// the evaluation of (g, e) as erasor_hip_evaluate_* runs it, its codes left in h->ev.code, then the ground truth drawn by them
+static int rd_eval(erasor_hip_handle *h, const float4 *g, uint32_t ng, const float4 *e, uint32_t ne, double voxel_leaf, double voxelsize,
+                   const erasor_render_view *view, void *rgb, int rgb_is_device, erasor_render_stats *stats, erasor_eval_result *res) {
+    int rc;
+    if (voxel_leaf > 0) {
+        if ((rc = ev_voxelize(h, g, ng, voxel_leaf, h->ev.gt, &ng))) return rc;
+        if ((rc = ev_voxelize(h, e, ne, voxel_leaf, h->ev.est, &ne))) return rc;
+        g = h->ev.gt.p;
+        e = h->ev.est.p;
+    }
+    if ((rc = ev_run(h, g, ng, e, ne, voxelsize, nullptr, res, nullptr, true))) return rc;
+    return rd_run(h, g, ng, h->ev.code.p, ERASOR_RENDER_EVAL, -1, -1, view, rgb, rgb_is_device, stats);
+}
+int erasor_hip_render_eval_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, const void *est_xyzi, size_t n_est,
+                                  int est_is_device, double voxel_leaf, double voxelsize, const erasor_render_view *view, void *rgb,
+                                  int rgb_is_device, erasor_render_stats *stats, erasor_eval_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, false, res);
+    if (rc || (rc = rd_check_view(h, view))) return rc;
+    if ((rc = rd_check_cloud(h, "erasor_hip_render_eval_clouds", gt_xyzi, n_gt)) || (rc = rd_check_cloud(h, "erasor_hip_render_eval_clouds", est_xyzi, n_est)))
+        return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *g = nullptr, *e = nullptr;
+    if ((rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, h->ev.gt, &g)) || (rc = ev_input(h, est_xyzi, n_est, est_is_device, h->ev.est, &e))) return rc;
+    return rd_eval(h, g, (uint32_t)n_gt, e, (uint32_t)n_est, voxel_leaf, voxelsize, view, rgb, rgb_is_device, stats, res);
+}
+int erasor_hip_render_eval_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, double voxel_leaf, double voxelsize,
+                               const erasor_render_view *view, void *rgb, int rgb_is_device, erasor_render_stats *stats, erasor_eval_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, false, res);
+    if (rc || (rc = rd_check_view(h, view)) || (rc = rd_check_cloud(h, "erasor_hip_render_eval_map", gt_xyzi, n_gt))) return rc;
+    if (!h->have_map) {
+        h->err = "erasor_hip_render_eval_map: the handle has no map (erasor_hip_set_map first)";
+        return ERASOR_E_STATE;
+    }
+    HIPC(h, hipSetDevice(h->device));
+    size_t n_map = 0;
+    if ((rc = map_to_device(h, h->ev.map, &n_map))) return rc;
+    if (n_map > 0x3FFFFFFFull) {
+        h->err = "erasor_hip_render_eval_map: map larger than 2^30 points";
+        return ERASOR_E_INVALID;
+    }
+    const float4 *g = nullptr;
+    if ((rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, h->ev.gt, &g))) return rc;
+    return rd_eval(h, g, (uint32_t)n_gt, h->ev.map.p, (uint32_t)n_map, voxel_leaf, voxelsize, view, rgb, rgb_is_device, stats, res);
+}
+
+#ifdef ERASOR_HIP_TEST_HOOKS
+// rd_run's image and counters by the other rasteriser (one 64-bit atomic max per point on a key image in device memory): the comparison
+// of MEASUREMENTS.md.  Mode LABEL or HEIGHT; tiled != 0: the shipped kernels (rd_run) instead, timed the same way; ms (optional): device
+// time between one event before the clears and one after the last kernel -- the same bracket for both.
+int erasor_hip_debug_render_atomic(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, int mode, const erasor_render_view *view,
+                                   void *rgb, erasor_render_stats *stats, int tiled, double *ms) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = rd_check_mode(h, mode);
+    if (rc || (rc = rd_check_view(h, view)) || (rc = rd_check_cloud(h, "erasor_hip_debug_render_atomic", xyzi, n))) return rc;
+    auto &E = h->ev;
+    const float4 *p = nullptr;
+    HIPC(h, hipSetDevice(h->device));
+    if ((rc = ev_input(h, xyzi, n, is_device, E.rd_pts, &p))) return rc;
+    if (tiled) {
+        hipEvent_t a, b;
+        HIPC(h, hipEventCreate(&a));
+        HIPC(h, hipEventCreate(&b));
+        rc = rd_run(h, p, (uint32_t)n, nullptr, mode, -1, -1, view, rgb, 0, stats, a, b);
+        float t = 0.f;
+        if (!rc && hipEventElapsedTime(&t, a, b) != hipSuccess) rc = ERASOR_E_NO_DEVICE;
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+        if (ms) *ms = t;
+        return rc;
+    }
+    const RdView v = rd_view(view);
+    const RdMode m = rd_mode(mode, -1, -1);
+    const size_t npix = (size_t)view->width * view->height;
+    DBuf<unsigned long long> keyimg;
+    if (ensure(h, keyimg, npix + 1) || ensure(h, E.rd_ctr, RD_NCTR) || ensure(h, E.rd_img, npix * 3 + 4)) return ERASOR_E_NO_DEVICE;
+    hipEvent_t a, b;
+    (void)hipEventCreate(&a);
+    (void)hipEventCreate(&b);
+    (void)hipEventRecord(a, h->stream);
+    (void)hipMemsetAsync(E.rd_ctr.p, 0, RD_NCTR * sizeof(unsigned long long), h->stream);
+    (void)hipMemsetAsync(keyimg.p, 0, npix * sizeof(unsigned long long), h->stream);
+    if (n)
+        hipLaunchKernelGGL(k_rd_atomic_points, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, p, (uint32_t)n, (const uint8_t *)nullptr, v, m, keyimg.p,
+                           E.rd_ctr.p);
+    hipLaunchKernelGGL(k_rd_atomic_pixels, dim3(cdiv(npix, 256)), dim3(256), 0, h->stream, (const unsigned long long *)keyimg.p, v, m, E.rd_img.p,
+                       E.rd_ctr.p);
+    (void)hipEventRecord(b, h->stream);
+    unsigned long long c[RD_NCTR];
+    (void)hipMemcpyAsync(c, E.rd_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream);
+    if (rgb) (void)hipMemcpyAsync(rgb, E.rd_img.p, npix * 3, hipMemcpyDeviceToHost, h->stream);
+    const hipError_t e_ = hipStreamSynchronize(h->stream);
+    float t = 0.f;
+    (void)hipEventElapsedTime(&t, a, b);
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    release(keyimg);
+    if (e_ != hipSuccess) return ERASOR_E_NO_DEVICE;
+    if (ms) *ms = t;
+    if (stats) rd_stats(c, n, stats);
+    return ERASOR_OK;
+}
+#endif
 
 // the last step's [selected bins theta-major | ground_viz | complement] WITHOUT tf_body2origin_ (the egocentric clouds
 // ERASOR::get_static_estimate hands out, erasor.cpp:612-626), assembled into the retired F buffer (free until the next step)

@@ -2,6 +2,7 @@
 //   <dir>/map.pcd, <dir>/pcds/%06d.pcd, <dir>/poses.csv (header line; idx,?,x,y,z,qx,qy,qz,qw per line, cols 2..8)
 // processes every node through erasor::OfflineMapUpdater and writes <dir>/<data_name>_result.pcd and map_final.pcd.
 #include <cstdlib>
+#include <cstring>
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -139,6 +140,134 @@ static int eval_mode(int argc, char **argv) {
     const int rc = evaluate_host(h, gt, est, voxel_leaf, voxelsize);
     erasor_hip_destroy(h);
     return rc;
+}
+// ---- bird's-eye images (viz_kitti_map.cpp / compare_map.cpp as PPM files: erasor_hip_render_*) ----
+extern "C" int erasor_shim_write_ppm(const char *path, const uint8_t *rgb, uint32_t width, uint32_t height);
+static const char *const RENDER_CAT_NAMES[ERASOR_RENDER_NCAT] = {"static", "dynamic", "target", "height", "static kept", "dynamic removed",
+                                                                 "static lost", "dynamic left"};
+static void print_view_and_stats(const erasor_render_view &v, const erasor_render_stats &s) {
+    printf("view: x0 %.3f y0 %.3f res %g, %u x %u pixels, z %.3f .. %.3f\n", v.x0, v.y0, v.res, v.width, v.height, v.z_lo, v.z_hi);
+    printf("points %llu drawn %llu outside %llu non-finite %llu, pixels hit %llu\n", (unsigned long long)s.n_points, (unsigned long long)s.n_drawn,
+           (unsigned long long)s.n_outside, (unsigned long long)s.n_nonfinite, (unsigned long long)s.n_pixels_hit);
+    for (int c = 0; c < ERASOR_RENDER_NCAT; ++c)
+        if (s.cat_points[c])
+            printf("  %-16s %10llu points %10llu pixels\n", RENDER_CAT_NAMES[c], (unsigned long long)s.cat_points[c], (unsigned long long)s.cat_pixels[c]);
+}
+static int render_fail(erasor_hip_handle *h, const char *what, int rc) {
+    fprintf(stderr, "%s: %s (rc %d)\n", what, erasor_hip_last_error(h), rc);
+    erasor_hip_destroy(h);
+    return 1;
+}
+static erasor_hip_handle *render_handle() {
+    erasor_params p;
+    erasor_hip_params_default(&p);
+    erasor_hip_handle *h = nullptr;
+    if (erasor_hip_create(&p, 0, &h) != ERASOR_OK) {
+        fprintf(stderr, "erasor_hip_create failed\n");
+        return nullptr;
+    }
+    return h;
+}
+// --render <out.ppm> <map> [res = 0.2] [class_num] [instance]: viz_kitti_map's picture of one map -- static / dynamic / the chosen class
+// (and instance) among the dynamic points
+static int render_mode(int argc, char **argv) {
+    if (argc < 4) return 2;
+    const double res = argc > 4 ? atof(argv[4]) : 0.2;
+    const int32_t cls = argc > 5 ? atoi(argv[5]) : -1, inst = argc > 6 ? atoi(argv[6]) : -1;
+    std::vector<float> m;
+    if (!load_cloud_xyzi(argv[3], m)) {
+        fprintf(stderr, "cannot read %s\n", argv[3]);
+        return 3;
+    }
+    erasor_hip_handle *h = render_handle();
+    if (!h) return 1;
+    erasor_render_view v;
+    erasor_render_stats st;
+    int rc = erasor_hip_render_fit(h, m.data(), m.size() / 4, 0, res, 2, 0x000000, &v);
+    if (rc) return render_fail(h, "render_fit", rc);
+    std::vector<uint8_t> rgb((size_t)v.width * v.height * 3);
+    if ((rc = erasor_hip_render_clouds(h, m.data(), m.size() / 4, 0, ERASOR_RENDER_LABEL, cls, inst, &v, rgb.data(), 0, &st)))
+        return render_fail(h, "render", rc);
+    erasor_hip_destroy(h);
+    print_view_and_stats(v, st);
+    if (erasor_shim_write_ppm(argv[2], rgb.data(), v.width, v.height) != 0) {
+        fprintf(stderr, "cannot write %s\n", argv[2]);
+        return 3;
+    }
+    return 0;
+}
+// --render-compare <out.ppm> <res> <gt> <est1> [<est2> ...]: compare_map.cpp's side-by-side picture -- one panel per file, left to right,
+// all in the view fitted to the first, 4 background pixels between neighbours
+static int render_compare_mode(int argc, char **argv) {
+    if (argc < 5) return 2;
+    const double res = atof(argv[3]);
+    const int k = argc - 4;
+    const uint32_t gap = 4;
+    erasor_hip_handle *h = render_handle();
+    if (!h) return 1;
+    erasor_render_view v;
+    std::vector<uint8_t> out, rgb;
+    uint32_t W = 0;
+    for (int j = 0; j < k; ++j) {
+        std::vector<float> m;
+        if (!load_cloud_xyzi(argv[4 + j], m)) {
+            fprintf(stderr, "cannot read %s\n", argv[4 + j]);
+            erasor_hip_destroy(h);
+            return 3;
+        }
+        int rc;
+        if (j == 0) {
+            if ((rc = erasor_hip_render_fit(h, m.data(), m.size() / 4, 0, res, 2, 0x000000, &v))) return render_fail(h, "render_fit", rc);
+            W = v.width * k + gap * (k - 1);
+            out.assign((size_t)W * v.height * 3, 0);
+            rgb.resize((size_t)v.width * v.height * 3);
+        }
+        erasor_render_stats st;
+        if ((rc = erasor_hip_render_clouds(h, m.data(), m.size() / 4, 0, ERASOR_RENDER_LABEL, -1, -1, &v, rgb.data(), 0, &st)))
+            return render_fail(h, "render", rc);
+        printf("panel %d: %s\n", j, argv[4 + j]);
+        print_view_and_stats(v, st);
+        for (uint32_t r = 0; r < v.height; ++r)
+            memcpy(&out[((size_t)r * W + (size_t)j * (v.width + gap)) * 3], &rgb[(size_t)r * v.width * 3], (size_t)v.width * 3);
+    }
+    erasor_hip_destroy(h);
+    printf("%d panel(s), %u x %u pixels\n", k, W, v.height);
+    if (erasor_shim_write_ppm(argv[2], out.data(), W, v.height) != 0) {
+        fprintf(stderr, "cannot write %s\n", argv[2]);
+        return 3;
+    }
+    return 0;
+}
+// --render-eval <out.ppm> <gt> <est> [voxelsize = 0.2] [voxel_leaf = 0] [res = 0.2]: --eval's table, and the error map -- the ground truth
+// coloured by the evaluation's decision per point
+static int render_eval_mode(int argc, char **argv) {
+    if (argc < 5) return 2;
+    const double voxelsize = argc > 5 ? atof(argv[5]) : 0.2, voxel_leaf = argc > 6 ? atof(argv[6]) : 0.0, res = argc > 7 ? atof(argv[7]) : 0.2;
+    std::vector<float> gt, est;
+    if (!load_cloud_xyzi(argv[3], gt) || !load_cloud_xyzi(argv[4], est)) {
+        fprintf(stderr, "cannot read %s or %s\n", argv[3], argv[4]);
+        return 3;
+    }
+    printf("GT : %s\nEst: %s\n", argv[3], argv[4]);
+    erasor_hip_handle *h = render_handle();
+    if (!h) return 1;
+    erasor_render_view v;
+    erasor_render_stats st;
+    erasor_eval_result r;
+    int rc = erasor_hip_render_fit(h, gt.data(), gt.size() / 4, 0, res, 2, 0x000000, &v);
+    if (rc) return render_fail(h, "render_fit", rc);
+    std::vector<uint8_t> rgb((size_t)v.width * v.height * 3);
+    if ((rc = erasor_hip_render_eval_clouds(h, gt.data(), gt.size() / 4, 0, est.data(), est.size() / 4, 0, voxel_leaf, voxelsize, &v, rgb.data(), 0, &st,
+                                            &r)))
+        return render_fail(h, "render_eval", rc);
+    erasor_hip_destroy(h);
+    print_eval_row(r);
+    print_view_and_stats(v, st);
+    if (erasor_shim_write_ppm(argv[2], rgb.data(), v.width, v.height) != 0) {
+        fprintf(stderr, "cannot write %s\n", argv[2]);
+        return 3;
+    }
+    return 0;
 }
 // the public SemanticKITTI label names (semantic-kitti.yaml) of a class key
 static const char *semantic_kitti_name(uint32_t key) {
@@ -1091,6 +1220,15 @@ int main(int argc, char **argv) {
     if (argc >= 2 && std::string(argv[1]) == "--eval") {
         try {
             return eval_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
+    if (argc >= 2 && (std::string(argv[1]) == "--render" || std::string(argv[1]) == "--render-compare" || std::string(argv[1]) == "--render-eval")) {
+        try {
+            const std::string mode = argv[1];
+            return mode == "--render" ? render_mode(argc, argv) : mode == "--render-compare" ? render_compare_mode(argc, argv) : render_eval_mode(argc, argv);
         } catch (const std::exception &e) {
             fprintf(stderr, "error: %s\n", e.what());
             return 1;

@@ -603,6 +603,14 @@ int erasor_shim_is_dynamic_obj_close(const erasor_params *p, const double *statu
         }
     return e.is_dynamic_obj_close(pod, r_target, theta_target, r_range, theta_range) ? 1 : 0;
 }
+// a height x width x 3 RGB image as a binary PPM (P6, maxval 255); returns 0, or -1 when the file cannot be written
+int erasor_shim_write_ppm(const char *path, const uint8_t *rgb, uint32_t width, uint32_t height) {
+    FILE *f = fopen(path, "wb");
+    if (!f) return -1;
+    const size_t n = (size_t)width * height * 3;
+    const bool ok = fprintf(f, "P6\n%u %u\n255\n", width, height) > 0 && fwrite(rgb, 1, n, f) == n;
+    return (fclose(f) == 0 && ok) ? 0 : -1;
+}
 // loads a .pcd; copies up to cap points (x y z intensity rows); returns the point count or -1
 long erasor_shim_load_pcd(const char *path, float *xyzi, long cap) {
     Cloud c;

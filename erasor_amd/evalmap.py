@@ -311,3 +311,148 @@ def evaluate_by_class(gt_xyzi, est_xyzi, voxelsize=0.2):
     ci["n_est"] = np.bincount(ei[e_dyn], minlength=len(labs))
     res["instances"] = _rows(labs, np.ones(len(labs), np.uint32), ci)
     return res
+
+
+# ---- bird's-eye images (include/erasor_hip.h: erasor_hip_render_*; kernels: erasor_amd/csrc/render.hip.h), on the host -------------
+# The arithmetic of the device rasteriser spelled out in numpy, byte for byte: the pixel of a point in float64 from its float32
+# coordinates, the winner of a pixel by (priority, z in float32's total order), the colour from (category, z).
+RENDER_LABEL, RENDER_HEIGHT, RENDER_EVAL = 0, 1, 2
+RENDER_MODES = {"label": RENDER_LABEL, "height": RENDER_HEIGHT, "eval": RENDER_EVAL}
+RENDER_CATEGORIES = ("static", "dynamic", "target", "height", "static_kept", "dynamic_removed", "static_lost", "dynamic_left")
+RENDER_PALETTE = (0xC8C8C8, 0xFF5050, 0xFFE000, 0x80D0FF, 0xB4B4B4, 0x30C040, 0x3060FF, 0xFF2020)  # ERASOR_RENDER_PALETTE
+RENDER_PRIORITY = (1, 2, 3, 1, 1, 2, 3, 4)                                                          # ERASOR_RENDER_PRIORITY
+RENDER_CAT_BASE = {RENDER_LABEL: 0, RENDER_HEIGHT: 3, RENDER_EVAL: 4}  # category = base + priority - 1
+RENDER_MAX_EDGE, RENDER_MAX_PIXELS = 16384, 1 << 26
+VIEW_FIELDS = ("x0", "y0", "res", "width", "height", "z_lo", "z_hi", "background")
+
+
+def render_view(x0, y0, res, width, height, z_lo=0.0, z_hi=0.0, background=0):
+    return {"x0": float(x0), "y0": float(y0), "res": float(res), "width": int(width), "height": int(height), "z_lo": float(z_lo),
+            "z_hi": float(z_hi), "background": int(background) & 0xFFFFFF}
+
+
+def check_view(v):
+    ok = (np.isfinite([v["x0"], v["y0"], v["res"], v["z_lo"], v["z_hi"]]).all() and v["res"] > 0 and 1 <= v["width"] <= RENDER_MAX_EDGE and
+          1 <= v["height"] <= RENDER_MAX_EDGE and v["width"] * v["height"] <= RENDER_MAX_PIXELS)
+    if not ok:
+        raise ValueError("render: view outside the limits (finite, res > 0, 1 <= width, height <= 16384, width * height <= 2^26)")
+
+
+def z_order(z):
+    """float32's total order as uint32 keys: -0.0 below +0.0"""
+    b = np.ascontiguousarray(z, np.float32).view(np.uint32)
+    return np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def z_from_order(k):
+    k = np.asarray(k, np.uint32)
+    return np.where(k & np.uint32(0x80000000), k & np.uint32(0x7FFFFFFF), ~k).astype(np.uint32).view(np.float32)
+
+
+def shade(base, z, z_lo, z_hi):
+    """one channel: (uint8)floor(base * (0.35 + 0.65 * s) + 0.5), s = z_hi > z_lo ? clamp((z - z_lo) / (z_hi - z_lo), 0, 1) : 1"""
+    z = np.asarray(z, np.float32).astype(np.float64)
+    if z_hi > z_lo:
+        s = np.minimum(np.maximum((z - z_lo) / (z_hi - z_lo), 0.0), 1.0)
+    else:
+        s = np.ones_like(z)
+    return np.floor(np.asarray(base, np.float64) * (0.35 + 0.65 * s) + 0.5).astype(np.uint8)
+
+
+def render_fit(cloud, res=0.2, margin=2, background=0):
+    """erasor_hip_render_fit: the view that contains every finite point, z_lo / z_hi at ranks floor(0.02 (n - 1)) / floor(0.98 (n - 1))"""
+    c = np.asarray(cloud, np.float32).reshape(-1, 4)
+    if not (np.isfinite(res) and res > 0 and 1 <= margin <= 1024):
+        raise ValueError("render_fit: res must be finite and > 0, margin in 1 .. 1024")
+    c = c[np.isfinite(c[:, :3]).all(1)]
+    if len(c) == 0:
+        raise ValueError("render_fit: the cloud has no finite point")
+    out = {}
+    for name, size, a in (("x0", "width", 0), ("y0", "height", 1)):
+        mn, mx = float(c[:, a].min()), float(c[:, a].max())
+        o = np.floor(mn / res) * res - margin * res
+        out[name] = float(o)
+        out[size] = float(np.floor((mx - o) / res) + 1 + margin)
+    if not (out["width"] <= RENDER_MAX_EDGE and out["height"] <= RENDER_MAX_EDGE and out["width"] * out["height"] <= RENDER_MAX_PIXELS):
+        raise ValueError("render_fit: %.0f x %.0f pixels at res %g is beyond the limits" % (out["width"], out["height"], res))
+    n = len(c)
+    zs = z_from_order(np.sort(z_order(c[:, 2])))  # (ascending in the total order)
+    z_lo, z_hi = float(zs[int(np.floor(0.02 * (n - 1)))]), float(zs[int(np.floor(0.98 * (n - 1)))])
+    return render_view(out["x0"], out["y0"], res, int(out["width"]), int(out["height"]), z_lo, z_hi, background)
+
+
+def _raster(c, prio, mode, view):
+    """the image and the statistics of the points c (float32 XYZI rows) with per-point priorities (1..4) within `mode`"""
+    check_view(view)
+    W, H = view["width"], view["height"]
+    fin = np.isfinite(c[:, :3]).all(1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        cx = np.floor((c[:, 0].astype(np.float64) - view["x0"]) / view["res"])
+        cy = np.floor((c[:, 1].astype(np.float64) - view["y0"]) / view["res"])
+        inside = fin & (cx >= 0) & (cx < W) & (cy >= 0) & (cy < H)
+    key = (prio[inside].astype(np.uint64) << np.uint64(32)) | z_order(c[inside, 2]).astype(np.uint64)
+    pix = (H - 1 - cy[inside].astype(np.int64)) * W + cx[inside].astype(np.int64)
+    kimg = np.zeros(H * W, np.uint64)
+    np.maximum.at(kimg, pix, key)
+    hit = kimg != 0
+    p_img = (kimg >> np.uint64(32)).astype(np.int64)
+    z_img = np.where(hit, z_from_order((kimg & np.uint64(0xFFFFFFFF)).astype(np.uint32)), np.float32(0))  # (key 0 decodes to NaN)
+    base0 = RENDER_CAT_BASE[mode]
+    pal = np.asarray(RENDER_PALETTE, np.int64)[np.where(hit, base0 + p_img - 1, 0)]
+    img = np.empty((H * W, 3), np.uint8)
+    for ch, sh in enumerate((16, 8, 0)):
+        img[:, ch] = np.where(hit, shade((pal >> sh) & 0xFF, z_img, view["z_lo"], view["z_hi"]), (view["background"] >> sh) & 0xFF)
+    cat_points, cat_pixels = [0] * 8, [0] * 8
+    for k in range(1, 5):
+        if base0 + k - 1 < 8:
+            cat_points[base0 + k - 1] = int((prio[inside] == k).sum())
+            cat_pixels[base0 + k - 1] = int((hit & (p_img == k)).sum())
+    stats = {"n_points": int(len(c)), "n_drawn": int(inside.sum()), "n_outside": int((fin & ~inside).sum()), "n_nonfinite": int((~fin).sum()),
+             "n_pixels_hit": int(hit.sum()), "cat_points": cat_points, "cat_pixels": cat_pixels}
+    return img.reshape(H, W, 3), stats
+
+
+def render(cloud, view, mode="label", target_class=None, target_instance=None):
+    """erasor_hip_render_clouds on the host: (uint8 image H x W x 3, stats).  mode "label": static 1, dynamic 2, target 3 (a dynamic
+    point of target_class, and of target_instance when given); "height": one category."""
+    c = np.ascontiguousarray(np.asarray(cloud, np.float32).reshape(-1, 4))
+    m = RENDER_MODES[mode] if isinstance(mode, str) else mode
+    prio = np.ones(len(c), np.int64)
+    if m == RENDER_LABEL:
+        _, lab, dyn = _decode(c[:, 3])
+        prio[dyn] = 2
+        if target_class is not None and target_class >= 0:
+            t = dyn & ((lab & 0xFFFF) == target_class)
+            if target_instance is not None and target_instance >= 0:
+                t &= (lab >> 16) == target_instance
+            prio[t] = 3
+    elif m != RENDER_HEIGHT:
+        raise ValueError("render: mode must be 'label' or 'height' (the error map: render_eval)")
+    return _raster(c, prio, m, view)
+
+
+def eval_codes(gt_xyzi, est_xyzi, voxelsize=0.2):
+    """evaluate's decision per ground-truth point as ERASOR_EVAL_* codes (0 out, 1 kept static, 2 kept dynamic, 3 class differs), and
+    the ground truth's dynamic flags"""
+    gt = np.asarray(gt_xyzi, np.float32).reshape(-1, 4)
+    est = np.asarray(est_xyzi, np.float32).reshape(-1, 4)
+    g_dyn, e_dyn = _decode(gt[:, 3])[2], _decode(est[:, 3])[2]
+    code = np.zeros(len(gt), np.uint8)
+    if len(gt) and len(est):
+        dists, idx = cKDTree(est[:, :3].astype(np.float64)).query(gt[:, :3].astype(np.float64), k=1, workers=-1)
+        is_in = dists < voxelsize * np.sqrt(3) / 2
+        same = g_dyn == e_dyn[idx]
+        code[is_in & same & ~g_dyn] = 1
+        code[is_in & same & g_dyn] = 2
+        code[is_in & ~same] = 3
+    return code, g_dyn
+
+
+def render_eval(gt_xyzi, est_xyzi, view, voxelsize=0.2):
+    """erasor_hip_render_eval_clouds (voxel_leaf 0) on the host: the ground truth drawn by evaluate's decision per point -- static kept 1,
+    dynamic removed 2, static lost 3, dynamic left 4.  Returns (image, stats, evaluate_clouds' dict)."""
+    gt = np.ascontiguousarray(np.asarray(gt_xyzi, np.float32).reshape(-1, 4))
+    code, g_dyn = eval_codes(gt, est_xyzi, voxelsize)
+    prio = np.where(code == 1, 1, np.where(code == 2, 4, np.where(g_dyn, 2, 3))).astype(np.int64)
+    img, stats = _raster(gt, prio, RENDER_EVAL, view)
+    return img, stats, evaluate_clouds(gt, est_xyzi, voxelsize)

@@ -357,6 +357,84 @@ int erasor_hip_evaluate_map_by_class(erasor_hip_handle *h, const void *gt_xyzi, 
                                      erasor_eval_class_row *instances, size_t cap_instances, size_t *n_instances,
                                      erasor_eval_result *res);
 
+/* ---- bird's-eye images: looking at a map and at PR / RR's per-point decisions (kernels: render.hip.h) ---------------------------
+ * replaces: what the reference shows in RViz -- src/utils/viz_kitti_map.cpp:27-82,118-125 (one map as static / dynamic / one chosen
+ * class or instance) and src/utils/compare_map.cpp:65-96 (ground truth and several methods' maps, static and dynamic, side by side) --
+ * as an image file, plus the error map: the ground truth coloured by erasor_hip_evaluate_clouds' decision per point.
+ * A top-down orthographic raster of XYZI rows.  Pixel of a point, in float64 from its float32 coordinates, every operation on its own:
+ * cx = floor((x - x0) / res), cy = floor((y - y0) / res); drawn iff 0 <= cx < width and 0 <= cy < height (compared as doubles);
+ * column cx, image row height - 1 - cy (north up).  A point with a non-finite x, y or z is dropped and counted (n_nonfinite), a finite
+ * one off the image is counted (n_outside); neither is an error.  The winner of a pixel is the point with the largest (priority of its
+ * category, z), z compared in float32's total order (-0.0 < +0.0); the colour is a function of (category, z): the category's palette
+ * entry shaded by s = z_hi > z_lo ? clamp((z - z_lo) / (z_hi - z_lo), 0, 1) : 1, channel = (uint8)floor(base * (0.35 + 0.65 * s) + 0.5)
+ * in float64.  So the image depends on the point set, not on its order, and equals erasor_amd/evalmap.py's render byte for byte.
+ * Pixels no point hit take `background`.  Output: height x width x 3 bytes, RGB, row-major. */
+#define ERASOR_RENDER_LABEL   0  /* static / dynamic / target by label (parse_dynamic_obj, utils.cpp:57-78; viz_kitti_map.cpp:51-82) */
+#define ERASOR_RENDER_HEIGHT  1  /* one category: maps with intensity = 0 */
+#define ERASOR_RENDER_EVAL    2  /* erasor_hip_render_eval_* only: the evaluator's decision per ground-truth point */
+#define ERASOR_RENDER_NCAT    8
+#define ERASOR_RENDER_CAT_STATIC           0  /* LABEL, priority 1 */
+#define ERASOR_RENDER_CAT_DYNAMIC          1  /* LABEL, priority 2: class 252..259 */
+#define ERASOR_RENDER_CAT_TARGET           2  /* LABEL, priority 3: a dynamic point of target_class (and target_instance) */
+#define ERASOR_RENDER_CAT_HEIGHT           3  /* HEIGHT, priority 1 */
+#define ERASOR_RENDER_CAT_STATIC_KEPT      4  /* EVAL, priority 1: ERASOR_EVAL_KEPT_STATIC */
+#define ERASOR_RENDER_CAT_DYNAMIC_REMOVED  5  /* EVAL, priority 2: GT dynamic and not ERASOR_EVAL_KEPT_DYNAMIC */
+#define ERASOR_RENDER_CAT_STATIC_LOST      6  /* EVAL, priority 3: GT static and not ERASOR_EVAL_KEPT_STATIC */
+#define ERASOR_RENDER_CAT_DYNAMIC_LEFT     7  /* EVAL, priority 4: ERASOR_EVAL_KEPT_DYNAMIC -- errors on top, whatever their height */
+/* base colour 0xRRGGBB and priority per category */
+static const uint32_t ERASOR_RENDER_PALETTE[ERASOR_RENDER_NCAT] = {0xC8C8C8u, 0xFF5050u, 0xFFE000u, 0x80D0FFu,
+                                                                   0xB4B4B4u, 0x30C040u, 0x3060FFu, 0xFF2020u};
+static const uint8_t ERASOR_RENDER_PRIORITY[ERASOR_RENDER_NCAT] = {1, 2, 3, 1, 1, 2, 3, 4};
+
+typedef struct erasor_render_view {
+    double x0, y0, res;      /* world coordinates of the lower left corner, metres per pixel (finite, res > 0) */
+    uint32_t width, height;  /* 1 .. 16384 each, width * height <= 2^26 */
+    double z_lo, z_hi;       /* the shading's height range (finite) */
+    uint32_t background;     /* 0xRRGGBB */
+    uint32_t reserved_;
+} erasor_render_view;
+
+typedef struct erasor_render_stats {
+    uint64_t n_points, n_drawn, n_outside, n_nonfinite, n_pixels_hit;
+    uint64_t cat_points[ERASOR_RENDER_NCAT];  /* points drawn per category */
+    uint64_t cat_pixels[ERASOR_RENDER_NCAT];  /* pixels won per category */
+} erasor_render_stats;
+
+/* A view that contains every finite point of a cloud (host or device), or of the handle's map (erasor_hip_render_fit_map), over the
+ * finite points, in float64: x0 = floor(min_x / res) * res - margin * res, width = (uint32)floor((max_x - x0) / res) + 1 + margin (the
+ * same in y); margin_px in 1 .. 1024 pixels, at least 1 so that a last-bit rounding of floor(min_x / res) * res cannot put the lowest point off the image.
+ * z_lo / z_hi are order statistics, not interpolated: the values at ranks floor(0.02 * (n - 1)) and floor(0.98 * (n - 1)) of the
+ * ascending finite z (an exact radix select on the device), so one outlier does not flatten the shading.
+ * ERASOR_E_INVALID: res not finite or <= 0, margin_px outside 1 .. 1024, no finite point, or a size beyond the limits (erasor_hip_last_error then
+ * names a res that fits).  ERASOR_E_STATE: a step in flight; _map: no map. */
+int erasor_hip_render_fit(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, double res, uint32_t margin_px,
+                          uint32_t background, erasor_render_view *view);
+int erasor_hip_render_fit_map(erasor_hip_handle *h, double res, uint32_t margin_px, uint32_t background, erasor_render_view *view);
+
+/* One cloud (host or device) as an image, mode ERASOR_RENDER_LABEL or _HEIGHT.  target_class < 0: no target; target_instance < 0: every
+ * instance of target_class (fetch_specific_class / fetch_specific_object, viz_kitti_map.cpp:51-82: among the dynamic points).  rgb:
+ * height * width * 3 bytes on the host, or on the handle's device (rgb_is_device); may be NULL (statistics only).  Works in scratch of
+ * the renderer's own: announcements and the last step's clouds stay as they are.  An empty cloud gives the background.
+ * ERASOR_E_INVALID: a view outside the limits above, a mode other than those two, more than 2^30 points.  ERASOR_E_STATE: a step in flight. */
+int erasor_hip_render_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, int mode, int32_t target_class,
+                             int32_t target_instance, const erasor_render_view *view, void *rgb, int rgb_is_device,
+                             erasor_render_stats *stats);
+/* the same of the handle's current map: the erasor_hip_get_map view (large-scale mode: the submap followed by its complement),
+ * compacted on the device, never copied to the host.  ERASOR_E_STATE also: no map. */
+int erasor_hip_render_map(erasor_hip_handle *h, int mode, int32_t target_class, int32_t target_instance, const erasor_render_view *view,
+                          void *rgb, int rgb_is_device, erasor_render_stats *stats);
+
+/* The error map: erasor_hip_evaluate_clouds / _map (arguments, errors and voxel_leaf as there; res as there) and the ground truth drawn
+ * in mode ERASOR_RENDER_EVAL, each point by what the evaluation decided for it; the per-point codes stay on the device in between.
+ * voxel_leaf > 0: the voxelised ground truth is what is drawn.  When the view contains every ground-truth point, cat_points of the
+ * four EVAL categories equal preserved_static, gt_dynamic - preserved_dynamic, gt_static - preserved_static and preserved_dynamic. */
+int erasor_hip_render_eval_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, const void *est_xyzi, size_t n_est,
+                                  int est_is_device, double voxel_leaf, double voxelsize, const erasor_render_view *view, void *rgb,
+                                  int rgb_is_device, erasor_render_stats *stats, erasor_eval_result *res);
+int erasor_hip_render_eval_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, double voxel_leaf, double voxelsize,
+                               const erasor_render_view *view, void *rgb, int rgb_is_device, erasor_render_stats *stats,
+                               erasor_eval_result *res);
+
 /* ---- the estimate-to-ground-truth overlap report: the alignment check before PR / RR (scripts/analysis_runner.py) -------------
  * replaces: analysis_runner.py:53-71 (overlap_report).  For every estimated point the distance d to its nearest ground-truth point
  * (exact and unbounded: float64 d^2 as cKDTree / NearestNeighbors compute it, the correctly rounded sqrt), then np.median, np.percentile
