@@ -1,0 +1,1667 @@
+// The offline analyses' host code: PR / RR evaluation (one estimate, many, by class), the overlap report, the frame check, label_map and
+// static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip at its end -- one
+// translation unit, like the kernel headers -- so it sees the handle, ensure / LAUNCH / HIPC, scan_u32, radix_sort, map_to_device and
+// voxelize_device from there; nothing of the step path depends on this file.  Kernels: evaluate.hip.h, nearest.hip.h, align.hip.h,
+// render.hip.h.
+#pragma once
+
+extern "C" {
+
+// ---- what the offline analyses share: the checks of their arguments, the caller's clouds and the handle's map on the device ----
+
+// The analyses run on the main stream, behind whatever a collected step launched ahead there, in the evaluator's scratch (h->ev): LAUNCH
+// follows h->cur, which points at the main stream until the scope ends.  bank2: the call sorts (a tree's Morton keys, the instances'
+// records); its radix sort then runs in histogram bank 2, so that the query chains of nodes announced ahead (bank 0) keep theirs.
+struct MainStreamScope {
+    erasor_hip_handle *h;
+    hipStream_t cur;
+    int bank;
+    bool bank2;
+    explicit MainStreamScope(erasor_hip_handle *hh, bool bank2_ = false) : h(hh), cur(hh->cur), bank(hh->bank), bank2(bank2_) {
+        h->cur = h->stream;
+        if (bank2) h->bank = 2;
+    }
+    ~MainStreamScope() {
+        h->cur = cur;
+        if (bank2) h->bank = bank;
+    }
+};
+
+static int invalid(erasor_hip_handle *h, const std::string &who, const std::string &why) {
+    h->err = who + ": " + why;
+    return ERASOR_E_INVALID;
+}
+
+// a caller cloud has at most 2^30 points (two clouds together index in 31 bits) and a pointer when it has any: refused before anything is read
+static constexpr size_t MAX_POINTS = 0x3FFFFFFFull;
+static const char *const BAD_CLOUD = "NULL cloud or more than 2^30 points";
+static int check_cloud(erasor_hip_handle *h, const std::string &who, const char *what, const void *xyzi, size_t n) {
+    return ((!xyzi && n) || n > MAX_POINTS) ? invalid(h, who, what) : ERASOR_OK;
+}
+
+// res, voxelsize and voxel_leaf of the calls that take them; per_point: the call has a per-point output, which voxel_leaf > 0 rules out
+static int check_voxel_args(erasor_hip_handle *h, const char *prefix, double voxel_leaf, double voxelsize, bool per_point, const char *per_point_msg,
+                            const void *res) {
+    if (!res) return invalid(h, prefix, "res is NULL");
+    if (!(voxelsize > 0) || !std::isfinite(voxelsize)) return invalid(h, prefix, "voxelsize must be a finite number > 0");
+    if (!(voxel_leaf >= 0) || !std::isfinite(voxel_leaf)) return invalid(h, prefix, "voxel_leaf must be 0 or a finite number > 0");
+    if (per_point && voxel_leaf > 0) return invalid(h, prefix, per_point_msg);
+    return ERASOR_OK;
+}
+
+// the frames of one scans array (align_frames, the sweep): offsets[0 .. n] from 0, never decreasing, up to the scans' point count
+static int check_scan_offsets(erasor_hip_handle *h, const char *who, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n) {
+    if (n_scan_points > MAX_POINTS) return invalid(h, who, "more than 2^30 scan points");
+    if (!scans_xyzi && n_scan_points) return invalid(h, who, "NULL scans");
+    if (offsets[0] != 0) return invalid(h, who, "offsets[0] must be 0");
+    for (size_t f = 0; f < n; ++f)
+        if (offsets[f + 1] < offsets[f]) return invalid(h, who, "offsets decrease");
+    if (offsets[n] != n_scan_points) return invalid(h, who, "the last offset is not the scans' point count");
+    return ERASOR_OK;
+}
+static bool all_finite(const float *v, size_t n) {
+    for (size_t k = 0; k < n; ++k)
+        if (!std::isfinite(v[k])) return false;
+    return true;
+}
+
+// the handle's map as one dense device array in buf (the evaluator's h->ev.map, the renderer's h->ev.rd_map)
+static int map_on_device(erasor_hip_handle *h, const char *who, DBuf<float4> &buf, const float4 **pts, uint32_t *n) {
+    if (!h->have_map) {
+        h->err = std::string(who) + ": the handle has no map (erasor_hip_set_map first)";
+        return ERASOR_E_STATE;
+    }
+    size_t n_map = 0;
+    const int rc = map_to_device(h, buf, &n_map);
+    if (rc) return rc;
+    if (n_map > MAX_POINTS) return invalid(h, who, "map larger than 2^30 points");
+    *pts = buf.p;
+    *n = (uint32_t)n_map;
+    return ERASOR_OK;
+}
+
+// ---- PR / RR of a cleaned map against a labelled ground-truth map (scripts/analysis_runner.py:74-105; kernels: evaluate.hip.h) ----
+// Everything runs on the main stream, behind whatever a collected step launched ahead there, in the handle's own scratch (h->ev).
+// n_rec (the breakdown by class): the kernels also fill the per-key table E.bc_tab and the dynamic points' records; *n_rec = their count.
+static void ev_fill(const unsigned long long c[EV_NCTR], erasor_eval_result *res);
+static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize, uint8_t *per_gt,
+                  erasor_eval_result *res, uint32_t *n_rec = nullptr, bool codes_on_device = false) {
+    auto &E = h->ev;
+    const bool want_codes = per_gt || codes_on_device;  // (codes_on_device: E.code keeps them for the renderer, no host copy)
+    uint32_t nb = 1024;  // buckets: a power of two >= the estimate's size (<= 1 point per bucket on average)
+    while (nb < n_est) nb <<= 1;
+#ifdef ERASOR_HIP_TEST_HOOKS
+    E.dbg_nb = nb;
+#endif
+    if (ensure(h, E.ctr, EV_NCTR) || ensure(h, E.cnt, (size_t)nb + 1) || ensure(h, E.pl, (size_t)nb + 1) || ensure(h, E.tops, nb / 1024 + 4) ||
+        ensure(h, E.bkt, (size_t)n_est + 1) || ensure(h, E.pts, (size_t)n_est + 1) || ensure(h, E.idx, (size_t)n_est + 1) ||
+        (want_codes && ensure(h, E.code, (size_t)n_gt + 1)))
+        return ERASOR_E_NO_DEVICE;
+    const size_t n_all = (size_t)n_gt + n_est;  // (< 2^31: each cloud has at most 2^30 points)
+    if (n_rec && (ensure(h, E.bc_tab, (size_t)EV_NKEYS * EV_KC) || ensure(h, E.bc_cur, 4) || ensure(h, E.bc_ikey, n_all + 1) ||
+                  ensure(h, E.bc_ival, n_all + 1)))
+        return ERASOR_E_NO_DEVICE;
+    MainStreamScope scope(h);
+    HIPC(h, hipMemsetAsync(E.ctr.p, 0, EV_NCTR * sizeof(unsigned long long), h->stream));
+    if (n_rec) {
+        HIPC(h, hipMemsetAsync(E.bc_tab.p, 0, (size_t)EV_NKEYS * EV_KC * sizeof(uint32_t), h->stream));
+        HIPC(h, hipMemsetAsync(E.bc_cur.p, 0, sizeof(uint32_t), h->stream));
+    }
+    const double thr = (voxelsize * sqrt(3.0)) / 2.0;  // evalmap / analysis_runner.py: voxelsize * np.sqrt(3) / 2
+    if (n_est) {
+        HIPC(h, hipMemsetAsync(E.cnt.p, 0, ((size_t)nb + 1) * sizeof(uint32_t), h->stream));
+        if (n_rec)
+            LAUNCH(h, "ev_index", k_ev_hist_keys, cdiv(n_est, 256), 256, est, n_est, voxelsize, nb - 1, E.bkt.p, E.cnt.p, E.ctr.p, E.bc_tab.p, E.bc_cur.p,
+                   E.bc_ikey.p, E.bc_ival.p);
+        else
+            LAUNCH(h, "ev_index", k_ev_hist, cdiv(n_est, 256), 256, est, n_est, voxelsize, nb - 1, E.bkt.p, E.cnt.p, E.ctr.p);
+        scan_u32(h, E.cnt.p, E.pl.p, E.tops.p, nb + 1, nb + 1, nullptr, nullptr, "ev_index");
+        LAUNCH(h, "ev_index", k_ev_offsets, cdiv(nb + 1, 256), 256, (const uint32_t *)E.pl.p, (const uint32_t *)E.tops.p, nb + 1, E.cnt.p, E.pl.p);
+        LAUNCH(h, "ev_index", k_ev_scatter, cdiv(n_est, 256), 256, est, n_est, (const uint32_t *)E.bkt.p, E.pl.p, E.pts.p, E.idx.p);
+    }
+    if (n_gt && n_rec)
+        LAUNCH(h, "ev_query", k_ev_query_keys, cdiv(n_gt, 256), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p,
+               (const uint32_t *)E.cnt.p, nb - 1, n_est, voxelsize, thr, E.ctr.p, E.bc_tab.p, E.bc_cur.p, E.bc_ikey.p, E.bc_ival.p);
+    else if (n_gt)
+        LAUNCH(h, "ev_query", k_ev_query, cdiv(n_gt, 256), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p, (const uint32_t *)E.cnt.p,
+               nb - 1, n_est, voxelsize, thr, want_codes ? E.code.p : (uint8_t *)nullptr, E.ctr.p);
+    unsigned long long c[EV_NCTR];
+    HIPC(h, hipMemcpyAsync(c, E.ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    if (n_rec) HIPC(h, hipMemcpyAsync(n_rec, E.bc_cur.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (c[EV_NON_FINITE]) {
+        h->err = "erasor_hip_evaluate: non-finite coordinate (NaN / Inf) in " + std::to_string(c[EV_NON_FINITE]) + " point(s)";
+        return ERASOR_E_INVALID;
+    }
+    if (per_gt && n_gt) HIPC(h, hipMemcpy(per_gt, E.code.p, n_gt, hipMemcpyDeviceToHost));
+    ev_fill(c, res);
+    return ERASOR_OK;
+}
+
+// erasor_eval_result from one evaluation's counters
+static void ev_fill(const unsigned long long c[EV_NCTR], erasor_eval_result *res) {
+    erasor_eval_result r;
+    memset(&r, 0, sizeof(r));
+    r.gt_static = c[EV_GT_STATIC];
+    r.gt_dynamic = c[EV_GT_DYNAMIC];
+    r.est_static = c[EV_EST_STATIC];
+    r.est_dynamic = c[EV_EST_DYNAMIC];
+    r.preserved_static = c[EV_KEPT_STATIC];
+    r.preserved_dynamic = c[EV_KEPT_DYNAMIC];
+    r.n_tied = c[EV_TIED];
+    r.n_label_out_of_range = c[EV_LABEL_OOR];
+    // evalmap.evaluate's formulas, operation by operation (Python int / int is the correctly rounded quotient: the same as in double here)
+    const double ns = (double)r.gt_static, nd = (double)r.gt_dynamic;
+    r.PR = r.gt_static ? (double)r.preserved_static / ns * 100.0 : 0.0;
+    r.RR = r.gt_dynamic ? (double)(r.gt_dynamic - r.preserved_dynamic) / nd * 100.0 : 0.0;
+    r.F1 = (r.PR + r.RR) > 0 ? 2 * (r.PR / 100) * (r.RR / 100) / ((r.PR / 100) + (r.RR / 100)) : 0.0;
+    *res = r;
+}
+
+// voxelize_preserving_labels of a device cloud at `leaf` (the save_static_map protocol, OMU.cpp:174-196) into dst[off ..) (borrows a query
+// side).  passthrough (optional): set when VoxelGrid's indices overflowed and the cloud came back unchanged.
+static int ev_voxelize(erasor_hip_handle *h, const float4 *src, uint32_t n, double leaf, DBuf<float4> &dst, uint32_t *n_out,
+                       bool *passthrough = nullptr, size_t off = 0) {
+    *n_out = 0;
+    if (passthrough) *passthrough = false;
+    if (!n) return ERASOR_OK;
+    uint32_t nq = 0;
+    const int rc = voxelize_device(h, src, n, leaf, &nq, passthrough);
+    if (rc) return rc;
+    if (ensure(h, dst, off + nq + 1)) return ERASOR_E_NO_DEVICE;  // (nq <= n: no reallocation when src is dst itself)
+    if (nq) HIPC(h, hipMemcpyAsync(dst.p + off, Q(h).query.p, (size_t)nq * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    *n_out = nq;
+    return ERASOR_OK;
+}
+
+static int ev_check_args(erasor_hip_handle *h, double voxel_leaf, double voxelsize, bool per_gt, const void *res) {
+    return check_voxel_args(h, "erasor_hip_evaluate", voxel_leaf, voxelsize, per_gt,
+                            "per_gt needs voxel_leaf == 0 (the codes would describe the voxelised ground truth)", res);
+}
+
+// a caller cloud on the device: its own pointer, or a copy of the host cloud in `buf`
+static int ev_input(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, DBuf<float4> &buf, const float4 **out) {
+    *out = nullptr;
+    if (!n) return ERASOR_OK;
+    if (is_device) {
+        *out = (const float4 *)xyzi;
+        return ERASOR_OK;
+    }
+    if (ensure(h, buf, n + 1)) return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemcpyAsync(buf.p, xyzi, n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    *out = buf.p;
+    return ERASOR_OK;
+}
+
+// The ground truth and the estimate of one call on the device, as the *_run functions take them: the caller's clouds checked and brought
+// in through h->ev.gt / h->ev.est (ev_pair_clouds), or the handle's map in h->ev.map as the estimate (ev_pair_map); voxel_leaf > 0: both
+// voxelised at that leaf, into h->ev.gt / h->ev.est.
+struct EvPair {
+    const float4 *g = nullptr, *e = nullptr;
+    uint32_t ng = 0, ne = 0;
+};
+static int ev_pair_voxelize(erasor_hip_handle *h, double voxel_leaf, EvPair *p) {
+    if (!(voxel_leaf > 0)) return ERASOR_OK;
+    int rc;
+    if ((rc = ev_voxelize(h, p->g, p->ng, voxel_leaf, h->ev.gt, &p->ng)) || (rc = ev_voxelize(h, p->e, p->ne, voxel_leaf, h->ev.est, &p->ne))) return rc;
+    p->g = h->ev.gt.p;
+    p->e = h->ev.est.p;
+    return ERASOR_OK;
+}
+static int ev_pair_clouds(erasor_hip_handle *h, const char *who, const void *gt_xyzi, size_t n_gt, int gt_is_device, const void *est_xyzi, size_t n_est,
+                          int est_is_device, double voxel_leaf, EvPair *p) {
+    int rc;
+    if ((rc = check_cloud(h, who, BAD_CLOUD, gt_xyzi, n_gt)) || (rc = check_cloud(h, who, BAD_CLOUD, est_xyzi, n_est))) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    if ((rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, h->ev.gt, &p->g)) || (rc = ev_input(h, est_xyzi, n_est, est_is_device, h->ev.est, &p->e))) return rc;
+    p->ng = (uint32_t)n_gt;
+    p->ne = (uint32_t)n_est;
+    return ev_pair_voxelize(h, voxel_leaf, p);
+}
+static int ev_pair_map(erasor_hip_handle *h, const char *who, const void *gt_xyzi, size_t n_gt, int gt_is_device, double voxel_leaf, EvPair *p) {
+    int rc = check_cloud(h, who, BAD_CLOUD, gt_xyzi, n_gt);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    if ((rc = map_on_device(h, who, h->ev.map, &p->e, &p->ne)) || (rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, h->ev.gt, &p->g))) return rc;
+    p->ng = (uint32_t)n_gt;
+    return ev_pair_voxelize(h, voxel_leaf, p);
+}
+
+int erasor_hip_evaluate_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, const void *est_xyzi, size_t n_est,
+                               int est_is_device, double voxel_leaf, double voxelsize, uint8_t *per_gt, erasor_eval_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    EvPair p;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, per_gt != nullptr, res);
+    if (rc || (rc = ev_pair_clouds(h, "erasor_hip_evaluate_clouds", gt_xyzi, n_gt, gt_is_device, est_xyzi, n_est, est_is_device, voxel_leaf, &p))) return rc;
+    return ev_run(h, p.g, p.ng, p.e, p.ne, voxelsize, per_gt, res);
+}
+
+int erasor_hip_evaluate_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, double voxel_leaf, double voxelsize,
+                            erasor_eval_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    EvPair p;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, false, res);
+    if (rc || (rc = ev_pair_map(h, "erasor_hip_evaluate_map", gt_xyzi, n_gt, gt_is_device, voxel_leaf, &p))) return rc;
+    return ev_run(h, p.g, p.ng, p.e, p.ne, voxelsize, nullptr, res);
+}
+
+// ---- K estimates against one ground truth (erasor_hip_evaluate_many; kernels: k_evm_* in evaluate.hip.h) ----
+// The callers copy the estimates back to back into E.em_cat.  Estimate j gets ev_run's bucket count for its size (a power of two >= n_j,
+// at least 1024) as its own range of one combined table: one histogram launch, one scan, one offsets launch, one scatter, one query.
+// Device memory, besides a host GT's copy (16 B a point): per estimated point the combined copy, its bucketed copy, its bucket and its
+// index (40 B); per bucket the counts and their scan (8 B, fewer than 2 buckets a point + 1024 per estimate): below 56 B per estimated
+// point + 8 KiB per estimate.  Like ev_run: the main stream, the evaluator's scratch.
+static int evm_run(erasor_hip_handle *h, const char *who, const float4 *gt, uint32_t n_gt, const uint32_t *n_est, size_t k, double voxelsize,
+                   erasor_eval_result *rows) {
+    auto &E = h->ev;
+    std::vector<EvmEst> tab(k + 1);
+    memset(tab.data(), 0, tab.size() * sizeof(EvmEst));
+    uint64_t n_all = 0, nb_all = 0, blk = 0;
+    for (size_t j = 0; j <= k; ++j) {
+        tab[j].off = (uint32_t)n_all;
+        tab[j].base = (uint32_t)nb_all;
+        tab[j].blk0 = (uint32_t)blk;
+        if (j == k) break;
+        uint32_t nb = 1024;
+        while (nb < n_est[j]) nb <<= 1;
+        tab[j].n = n_est[j];
+        tab[j].mask = nb - 1;
+        n_all += n_est[j];
+        nb_all += nb;
+        blk += cdiv(n_est[j], 256);
+    }
+    if (n_all > 0x7FFFFFFFull || nb_all > 0x7FFFFFFFull) {
+        h->err = std::string(who) + ": more than 2^31 estimated points or buckets in all";
+        return ERASOR_E_INVALID;
+    }
+    const uint32_t nb = (uint32_t)nb_all, n = (uint32_t)n_all;
+#ifdef ERASOR_HIP_TEST_HOOKS
+    E.dbg_nb = nb;
+    E.dbg_tab = tab;
+#endif
+    if (ensure(h, E.em_tab, k + 1) || ensure(h, E.em_ctr, (k + 1) * EV_NCTR) || ensure(h, E.cnt, (size_t)nb + 1) || ensure(h, E.pl, (size_t)nb + 1) ||
+        ensure(h, E.tops, nb / 1024 + 4) || ensure(h, E.bkt, (size_t)n + 1) || ensure(h, E.pts, (size_t)n + 1) || ensure(h, E.idx, (size_t)n + 1))
+        return ERASOR_E_NO_DEVICE;
+    MainStreamScope scope(h);
+    HIPC(h, hipMemcpyAsync(E.em_tab.p, tab.data(), (k + 1) * sizeof(EvmEst), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemsetAsync(E.em_ctr.p, 0, (k + 1) * EV_NCTR * sizeof(unsigned long long), h->stream));
+    const double thr = (voxelsize * sqrt(3.0)) / 2.0;  // (ev_run's)
+    if (n) {
+        HIPC(h, hipMemsetAsync(E.cnt.p, 0, ((size_t)nb + 1) * sizeof(uint32_t), h->stream));
+        LAUNCH(h, "evm_index", k_evm_hist, (uint32_t)blk, 256, (const float4 *)E.em_cat.p, (const EvmEst *)E.em_tab.p, (uint32_t)k, voxelsize, E.bkt.p,
+               E.cnt.p, E.em_ctr.p);
+        scan_u32(h, E.cnt.p, E.pl.p, E.tops.p, nb + 1, nb + 1, nullptr, nullptr, "evm_index");
+        LAUNCH(h, "evm_index", k_ev_offsets, cdiv(nb + 1, 256), 256, (const uint32_t *)E.pl.p, (const uint32_t *)E.tops.p, nb + 1, E.cnt.p, E.pl.p);
+        LAUNCH(h, "evm_index", k_ev_scatter, cdiv(n, 256), 256, (const float4 *)E.em_cat.p, n, (const uint32_t *)E.bkt.p, E.pl.p, E.pts.p, E.idx.p);
+    }
+    if (n_gt) {
+        // one estimate per blockIdx.y: workgroups are dispatched x fastest, so the estimates are searched one after the other, each
+        // against its own bucket table while that is cache-resident.  (All K in one lane's loop reads the GT once but walks K tables at
+        // a time: for 8 estimates of 9.8 M points against a 9.8 M-point GT that took 147 ms against 137 ms for 8 evaluate_clouds calls.)
+        const uint32_t gx = cdiv(n_gt, 256), per_y = 1, gy = (uint32_t)std::max<size_t>(k, 1);
+        LAUNCH(h, "evm_query", k_evm_query, dim3(gx, gy), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p, (const uint32_t *)E.cnt.p,
+               (const EvmEst *)E.em_tab.p, (uint32_t)k, per_y, voxelsize, thr, E.em_ctr.p);
+    }
+    std::vector<unsigned long long> c((k + 1) * EV_NCTR);
+    HIPC(h, hipMemcpyAsync(c.data(), E.em_ctr.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    const unsigned long long *cg = &c[k * EV_NCTR];
+    if (cg[EV_NON_FINITE]) {
+        h->err = std::string(who) + ": non-finite coordinate (NaN / Inf) in " + std::to_string(cg[EV_NON_FINITE]) + " point(s) of the ground truth";
+        return ERASOR_E_INVALID;
+    }
+    for (size_t j = 0; j < k; ++j)
+        if (c[j * EV_NCTR + EV_NON_FINITE]) {
+            h->err = std::string(who) + ": non-finite coordinate (NaN / Inf) in " + std::to_string(c[j * EV_NCTR + EV_NON_FINITE]) +
+                     " point(s) of estimate " + std::to_string(j);
+            return ERASOR_E_INVALID;
+        }
+    for (size_t j = 0; j < k; ++j) {
+        unsigned long long *cj = &c[j * EV_NCTR];
+        cj[EV_GT_STATIC] = cg[EV_GT_STATIC];
+        cj[EV_GT_DYNAMIC] = cg[EV_GT_DYNAMIC];
+        cj[EV_LABEL_OOR] += cg[EV_LABEL_OOR];
+        ev_fill(cj, &rows[j]);
+    }
+    return ERASOR_OK;
+}
+
+int erasor_hip_evaluate_many(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, const void *const *est_xyzi, const size_t *n_est,
+                             const int *est_is_device, size_t k, double voxel_leaf, double voxelsize, erasor_eval_result *rows) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const std::string who = "erasor_hip_evaluate_many";
+    erasor_eval_result unused;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, false, k ? rows : &unused);
+    if (rc) return rc;
+    if (k && (!est_xyzi || !n_est)) return invalid(h, who, "est_xyzi or n_est is NULL");
+    if ((rc = check_cloud(h, who, "NULL ground truth or more than 2^30 points", gt_xyzi, n_gt))) return rc;
+    uint64_t total = 0;
+    for (size_t j = 0; j < k; ++j) {
+        if ((rc = check_cloud(h, who + ": estimate " + std::to_string(j), BAD_CLOUD, est_xyzi[j], n_est[j]))) return rc;
+        total += n_est[j];
+    }
+    if (total > 0x7FFFFFFFull) return invalid(h, who, "more than 2^31 estimated points in all");
+    if (!k) return ERASOR_OK;
+    HIPC(h, hipSetDevice(h->device));
+    auto &E = h->ev;
+    const float4 *g = nullptr;
+    if ((rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, E.gt, &g))) return rc;
+    uint32_t ng = (uint32_t)n_gt;
+    if (voxel_leaf > 0) {
+        if ((rc = ev_voxelize(h, g, ng, voxel_leaf, E.gt, &ng))) return rc;
+        g = E.gt.p;
+    }
+    // every estimate into the combined array (voxelised first with voxel_leaf > 0: never more points than given)
+    if (ensure(h, E.em_cat, total + 1)) return ERASOR_E_NO_DEVICE;
+    std::vector<uint32_t> ne(k, 0);
+    uint64_t off = 0;
+    for (size_t j = 0; j < k; ++j) {
+        const uint32_t n = (uint32_t)n_est[j];
+        const bool dev = est_is_device && est_is_device[j];
+        if (!n) continue;
+        if (voxel_leaf > 0) {
+            const float4 *e = nullptr;
+            if ((rc = ev_input(h, est_xyzi[j], n, dev, E.est, &e)) || (rc = ev_voxelize(h, e, n, voxel_leaf, E.em_cat, &ne[j], nullptr, off))) {
+                h->err = who + ": estimate " + std::to_string(j) + ": " + h->err;
+                return rc;
+            }
+        } else {
+            HIPC(h, hipMemcpyAsync(E.em_cat.p + off, est_xyzi[j], (size_t)n * sizeof(float4), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                   h->stream));
+            ne[j] = n;
+        }
+        off += ne[j];
+    }
+    HIPC(h, hipStreamSynchronize(h->stream));
+    return evm_run(h, who.c_str(), g, ng, ne.data(), k, voxelsize, rows);
+}
+
+// ---- the estimate-to-GT overlap report (scripts/analysis_runner.py:53-71, overlap_report; kernels: nearest.hip.h) ----
+// Like ev_run: the main stream, the evaluator's scratch (h->ev), and the tree's radix sort in a histogram bank of its own (bank 2), so
+// that the query chains of nodes announced ahead (bank 0) keep theirs.
+
+// np.percentile(d, p) (method "linear") from the sorted values v(rank), operation by operation: q = p / 100, virtual index (n-1)*q,
+// previous / next index (both n-1 at or above it), gamma = index - previous, and _lerp with its t >= 0.5 branch
+static void ov_percentile_ranks(uint64_t n, double p, uint64_t *prev, uint64_t *next, double *gamma) {
+    const double q = p / 100.0;
+    const double vi = (double)(n - 1) * q;
+    double pi = floor(vi);
+    *prev = (uint64_t)pi;
+    *next = (uint64_t)pi + 1;
+    if (vi >= (double)(n - 1)) {
+        pi = -1.0;  // (numpy indexes with -1: the last value)
+        *prev = *next = n - 1;
+    }
+    *gamma = vi - pi;
+}
+static double ov_lerp(double a, double b, double t) {
+    const double diff = b - a;
+    double r = a + diff * t;
+    if (t >= 0.5) r = b - diff * (1 - t);
+    return r;
+}
+
+// the leaf count of an n-point tree padded to a power of two (P); refused when its depth would not fit the traversal stack
+static int nn_pad(erasor_hip_handle *h, uint32_t n, uint32_t *P_out, const char *who, const char *cloud) {
+    const uint32_t n_leaves = std::max(1u, cdiv(n, NN_LEAF));
+    uint32_t P = 1, levels = 0;  // leaves padded to a power of two, levels below the root
+    while (P < n_leaves) {
+        P <<= 1;
+        ++levels;
+    }
+    if (levels >= NN_STACK) {
+        h->err = std::string(who) + ": " + cloud + " too large for the traversal stack";
+        return ERASOR_E_INVALID;
+    }
+    *P_out = P;
+    return ERASOR_OK;
+}
+
+// the bounding-volume tree over pts[0 .. n) (n > 0; nearest.hip.h) into E.nn_pts / nn_idx / nn_lo / nn_hi, P from nn_pad.  E.nn_ctr
+// (OV_NCTR entries) is zeroed by the caller; a non-finite point refuses the call ("<who>: ... in <k> <noun>").
+static int nn_tree(erasor_hip_handle *h, const float4 *pts, uint32_t n, uint32_t P, const char *who, const char *noun) {
+    auto &E = h->ev;
+    const size_t n1 = (size_t)n + 1;
+    if (ensure(h, E.nn_bb, 8) || ensure(h, E.nn_key, n1) || ensure(h, E.nn_ka, n1) || ensure(h, E.nn_kb, n1) || ensure(h, E.nn_va, n1) ||
+        ensure(h, E.nn_vb, n1) || ensure(h, E.nn_idx, n1) || ensure(h, E.nn_pts, n1) || ensure(h, E.nn_lo, 2 * (size_t)P) ||
+        ensure(h, E.nn_hi, 2 * (size_t)P))
+        return ERASOR_E_NO_DEVICE;
+    // the box: k_bbox's fkey_ord min (3 x ~0u) / max (3 x 0)
+    HIPC(h, hipMemsetAsync(E.nn_bb.p, 0xFF, 3 * sizeof(uint32_t), h->stream));
+    HIPC(h, hipMemsetAsync(E.nn_bb.p + 3, 0, 3 * sizeof(uint32_t), h->stream));
+    LAUNCH(h, "ov_tree", k_bbox, bbox_grid(n), 256, pts, n, E.nn_bb.p);
+    LAUNCH(h, "ov_tree", k_nn_keys, cdiv(n, 256), 256, pts, n, (const uint32_t *)E.nn_bb.p, E.nn_key.p, E.nn_ctr.p);
+    const uint32_t *skeys = nullptr, *sperm = nullptr;
+    if (radix_sort(h, E.nn_key.p, n, nullptr, 30, E.nn_ka.p, E.nn_kb.p, E.nn_va.p, E.nn_vb.p, &skeys, &sperm, "ov_tree"))
+        return ERASOR_E_NO_DEVICE;
+#ifdef ERASOR_HIP_TEST_HOOKS
+    E.dbg_skeys = skeys;
+#endif
+    LAUNCH(h, "ov_tree", k_nn_gather, cdiv(n, 256), 256, pts, n, sperm, E.nn_pts.p, E.nn_idx.p);
+    LAUNCH(h, "ov_tree", k_nn_leaves, cdiv(P * NN_LEAF, 256), 256, (const float4 *)E.nn_pts.p, n, P, E.nn_lo.p, E.nn_hi.p);
+    for (uint32_t first = P / 2; first >= 1; first /= 2) LAUNCH(h, "ov_tree", k_nn_level, cdiv(first, 256), 256, E.nn_lo.p, E.nn_hi.p, first);
+    unsigned long long c[OV_NCTR];
+    HIPC(h, hipMemcpyAsync(c, E.nn_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (c[OV_NON_FINITE]) {
+        h->err = std::string(who) + ": non-finite coordinate (NaN / Inf) in " + std::to_string(c[OV_NON_FINITE]) + " " + noun;
+        return ERASOR_E_INVALID;
+    }
+    return ERASOR_OK;
+}
+
+// the target ranks of n > 0 sorted distances: the median's one or two, the two of each percentile (and the percentiles' gammas)
+static void ov_ranks(uint64_t n, uint64_t rk[OV_SEL_MAX], double *g90, double *g99) {
+    rk[0] = (n - 1) / 2;
+    rk[1] = n / 2;
+    ov_percentile_ranks(n, 90, &rk[2], &rk[3], g90);
+    ov_percentile_ranks(n, 99, &rk[4], &rk[5], g99);
+}
+
+// the exact radix select over the bit patterns v[0 .. count), driven from the host (k_ov_select_hist): the values at the ranks rk, from the
+// top digit down; every target keeps its prefix and its rank inside that prefix.  Values above every rank (align's sentinel) never matter.
+static int ov_select(erasor_hip_handle *h, const unsigned long long *v, uint32_t count, const uint64_t rk[OV_SEL_MAX], double out[OV_SEL_MAX],
+                     int top_shift = 56) {  // (top_shift: the highest digit that can differ -- 24 for values below 2^32)
+    auto &E = h->ev;
+    unsigned long long pref[OV_SEL_MAX] = {};
+    uint64_t left[OV_SEL_MAX];
+    for (uint32_t t = 0; t < OV_SEL_MAX; ++t) left[t] = rk[t];
+    std::vector<uint32_t> hist(OV_SEL_MAX * 256);
+    const uint32_t grid = std::min(cdiv(count, 256 * 8), 1024u);
+    for (int shift = top_shift; shift >= 0; shift -= 8) {
+        OvSelect s;
+        memset(&s, 0, sizeof(s));
+        s.shift = shift;
+        uint32_t slot[OV_SEL_MAX];
+        for (uint32_t t = 0; t < OV_SEL_MAX; ++t) {
+            uint32_t k = 0;
+            while (k < s.n && s.pref[k] != pref[t]) ++k;
+            if (k == s.n) s.pref[s.n++] = pref[t];
+            slot[t] = k;
+        }
+        HIPC(h, hipMemsetAsync(E.nn_hist.p, 0, (size_t)s.n * 256 * sizeof(uint32_t), h->stream));
+        LAUNCH(h, "ov_select", k_ov_select_hist, grid, 256, v, count, s, E.nn_hist.p);
+        HIPC(h, hipMemcpyAsync(hist.data(), E.nn_hist.p, (size_t)s.n * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
+        for (uint32_t t = 0; t < OV_SEL_MAX; ++t) {
+            const uint32_t *hh = hist.data() + (size_t)slot[t] * 256;
+            uint64_t cum = 0;
+            uint32_t d = 0;
+            while (d < 255 && left[t] >= cum + hh[d]) cum += hh[d++];
+            left[t] -= cum;
+            pref[t] = (pref[t] << 8) | d;
+        }
+    }
+    memcpy(out, pref, sizeof(pref));
+    return ERASOR_OK;
+}
+
+// one report from n distances: the counts below the thresholds, the largest distance's bits, and (n > 0) the values at ov_ranks' ranks
+static void ov_fill(uint64_t n, uint64_t below_half, uint64_t below_one, uint64_t below_two, unsigned long long max_bits, const double v[OV_SEL_MAX],
+                    double g90, double g99, erasor_overlap_result *res) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    erasor_overlap_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_est = n;
+    r.n_below_half = below_half;
+    r.n_below_one = below_one;
+    r.n_below_two = below_two;
+    r.median = r.p90 = r.p99 = r.max = r.frac_half = r.frac_one = r.frac_two = nan;
+    if (n) {
+        // np.median: the middle value, or the mean of the two middle ones, (a + b) / 2
+        r.median = (n % 2) ? v[0] : (v[0] + v[1]) / 2.0;
+        r.p90 = ov_lerp(v[2], v[3], g90);
+        r.p99 = ov_lerp(v[4], v[5], g99);
+        double mx;
+        memcpy(&mx, &max_bits, sizeof(mx));
+        r.max = mx;
+        // np.mean(d < x) * 100
+        r.frac_half = (double)r.n_below_half / (double)n * 100.0;
+        r.frac_one = (double)r.n_below_one / (double)n * 100.0;
+        r.frac_two = (double)r.n_below_two / (double)n * 100.0;
+    }
+    *res = r;
+}
+
+static int ov_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize, double *per_dist,
+                  uint32_t *per_nearest, erasor_overlap_result *res) {
+    auto &E = h->ev;
+    MainStreamScope scope(h, true);
+    uint32_t P = 1;
+    int rc = nn_pad(h, n_gt, &P, "erasor_hip_overlap", "ground truth");
+    if (rc) return rc;
+    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256) ||
+        (n_est && (ensure(h, E.nn_dbits, (size_t)n_est + 1) || (per_nearest && ensure(h, E.nn_near, (size_t)n_est + 1)))))
+        return ERASOR_E_NO_DEVICE;
+    unsigned long long c[OV_NCTR];
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if (n_gt && (rc = nn_tree(h, gt, n_gt, P, "erasor_hip_overlap", "ground-truth point(s)"))) return rc;
+    // the thresholds as overlap_report forms them: half = 0.5 * voxelsize, one = voxelsize, 2 * one
+    const double half = 0.5 * voxelsize, one = voxelsize, two = 2 * one;
+    if (n_est)
+        LAUNCH(h, "ov_query", k_nn_query, cdiv(n_est, NN_QBLOCK), NN_QBLOCK, est, n_est, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p,
+               n_gt, (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, half, one, two, E.nn_dbits.p,
+               per_nearest ? E.nn_near.p : (uint32_t *)nullptr, E.nn_ctr.p);
+    HIPC(h, hipMemcpyAsync(c, E.nn_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (c[OV_NON_FINITE]) {
+        h->err = "erasor_hip_overlap: non-finite coordinate (NaN / Inf) in " + std::to_string(c[OV_NON_FINITE]) + " estimated point(s)";
+        return ERASOR_E_INVALID;
+    }
+    erasor_overlap_result r;
+    const uint64_t n = n_est;
+    double v[OV_SEL_MAX] = {}, g90 = 0, g99 = 0;
+    if (n_est) {
+        uint64_t rk[OV_SEL_MAX];
+        ov_ranks(n, rk, &g90, &g99);
+        if ((rc = ov_select(h, E.nn_dbits.p, n_est, rk, v))) return rc;
+    }
+    ov_fill(n, c[OV_BELOW_HALF], c[OV_BELOW_ONE], c[OV_BELOW_TWO], c[OV_MAX_BITS], v, g90, g99, &r);
+    if (n_est) {
+        if (per_dist) HIPC(h, hipMemcpy(per_dist, E.nn_dbits.p, (size_t)n_est * sizeof(double), hipMemcpyDeviceToHost));
+        if (per_nearest) HIPC(h, hipMemcpy(per_nearest, E.nn_near.p, (size_t)n_est * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    *res = r;
+    return ERASOR_OK;
+}
+
+static int ov_check_args(erasor_hip_handle *h, double voxel_leaf, double voxelsize, bool per_point, const void *res) {
+    return check_voxel_args(h, "erasor_hip_overlap", voxel_leaf, voxelsize, per_point,
+                            "per-point outputs need voxel_leaf == 0 (they would describe the voxelised estimate)", res);
+}
+static int ov_check_gt(erasor_hip_handle *h, const char *who, const EvPair &p) {
+    return (!p.ng && p.ne) ? invalid(h, who, "empty ground truth (no nearest point to measure against)") : ERASOR_OK;
+}
+
+int erasor_hip_overlap_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, const void *est_xyzi, size_t n_est,
+                              int est_is_device, double voxel_leaf, double voxelsize, double *per_est_dist, uint32_t *per_est_nearest,
+                              erasor_overlap_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_overlap_clouds";
+    EvPair p;
+    int rc = ov_check_args(h, voxel_leaf, voxelsize, per_est_dist || per_est_nearest, res);
+    if (rc || (rc = ev_pair_clouds(h, who, gt_xyzi, n_gt, gt_is_device, est_xyzi, n_est, est_is_device, voxel_leaf, &p)) || (rc = ov_check_gt(h, who, p)))
+        return rc;
+    return ov_run(h, p.g, p.ng, p.e, p.ne, voxelsize, per_est_dist, per_est_nearest, res);
+}
+
+int erasor_hip_overlap_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, double voxel_leaf, double voxelsize,
+                           erasor_overlap_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_overlap_map";
+    EvPair p;
+    int rc = ov_check_args(h, voxel_leaf, voxelsize, false, res);
+    if (rc || (rc = ev_pair_map(h, who, gt_xyzi, n_gt, gt_is_device, voxel_leaf, &p)) || (rc = ov_check_gt(h, who, p))) return rc;
+    return ov_run(h, p.g, p.ng, p.e, p.ne, voxelsize, nullptr, nullptr, res);
+}
+
+// ---- every frame's pose against the map, before a run (the reference README's pitfalls 1, 3 and 5; kernels: align.hip.h) ----
+// Like ov_run: the main stream, the evaluator's scratch, the map's tree sorted in bank 2.  Round trips: the per-frame counters once, the
+// per-frame values once, and the summary's host-driven select (8 passes).
+
+// the arguments both entry points check: ERASOR_E_INVALID with h->err set, else ERASOR_OK and the scans' point count in *n_scan
+static int al_check_args(erasor_hip_handle *h, const char *who, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets,
+                         size_t n_frames, const float *T_lidar2body, const float *T_body2origin, double voxelsize, erasor_align_row *rows) {
+    if (!(voxelsize > 0) || !std::isfinite(voxelsize)) return invalid(h, who, "voxelsize must be a finite number > 0");
+    if (n_frames > 65536) return invalid(h, who, "more than 65536 frames");
+    if (!offsets) return invalid(h, who, "offsets is NULL (n_frames + 1 entries)");
+    if (n_frames && (!rows || !T_body2origin)) return invalid(h, who, "rows or T_body2origin is NULL");
+    const int rc = check_scan_offsets(h, who, scans_xyzi, n_scan_points, offsets, n_frames);
+    if (rc) return rc;
+    if (T_lidar2body && !all_finite(T_lidar2body, 16)) return invalid(h, who, "non-finite entry in T_lidar2body");
+    if (!all_finite(T_body2origin, n_frames * 16)) return invalid(h, who, "non-finite entry in T_body2origin");
+    return ERASOR_OK;
+}
+
+static int al_run(erasor_hip_handle *h, const char *who, const float4 *map, uint32_t n_map, const float4 *scans, uint32_t n, const uint64_t *offsets,
+                  uint32_t n_frames, const float *T_lidar2body, const float *T_body2origin, double voxelsize, erasor_align_row *rows,
+                  erasor_overlap_result *summary) {
+    auto &E = h->ev;
+    MainStreamScope scope(h, true);
+    if (!n_map && n) {
+        h->err = std::string(who) + ": empty map with a non-empty frame (no nearest point to measure against)";
+        return ERASOR_E_INVALID;
+    }
+    uint32_t P = 1;
+    int rc = nn_pad(h, n_map, &P, who, "map");
+    if (rc) return rc;
+    const uint32_t grid = cdiv(n, NN_QBLOCK), nf = std::max(n_frames, 1u);
+    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256) || ensure(h, E.nn_dbits, (size_t)n + 1) ||
+        ensure(h, E.al_off, (size_t)nf + 1) || ensure(h, E.al_wg, (size_t)grid + 1) || ensure(h, E.al_xf, nf) ||
+        ensure(h, E.al_ctr, (size_t)nf * AL_NCTR) || ensure(h, E.al_rank, nf) || ensure(h, E.al_val, (size_t)nf * OV_SEL_MAX))
+        return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if (n_map && (rc = nn_tree(h, map, n_map, P, who, "map point(s)"))) return rc;
+    // the frames: offsets (< 2^30), the frame of every query workgroup's first point (the last frame after the last), the poses
+    std::vector<uint32_t> off(n_frames + 1), wg(grid + 1);
+    for (uint32_t f = 0; f <= n_frames; ++f) off[f] = (uint32_t)offsets[f];
+    for (uint32_t b = 0, f = 0; b < grid; ++b) {  // the largest f < n_frames with off[f] <= b * NN_QBLOCK
+        while (f + 1 < n_frames && off[f + 1] <= b * NN_QBLOCK) ++f;
+        wg[b] = f;
+    }
+    wg[grid] = n_frames ? n_frames - 1 : 0;
+    static const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    std::vector<Xf> xf(nf);
+    for (uint32_t f = 0; f < n_frames; ++f) xf[f] = to_xf(T_body2origin + 16 * (size_t)f);
+    HIPC(h, hipMemcpyAsync(E.al_off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(E.al_wg.p, wg.data(), wg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(E.al_xf.p, xf.data(), nf * sizeof(Xf), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemsetAsync(E.al_ctr.p, 0, (size_t)nf * AL_NCTR * sizeof(unsigned long long), h->stream));
+    // the thresholds as overlap_report forms them: half = 0.5 * voxelsize, one = voxelsize, 2 * one
+    const double half = 0.5 * voxelsize, one = voxelsize, two = 2 * one;
+    if (n)
+        LAUNCH(h, "al_query", k_al_query, grid, NN_QBLOCK, scans, n, (const uint32_t *)E.al_off.p, (const uint32_t *)E.al_wg.p,
+               to_xf(T_lidar2body ? T_lidar2body : I), (const Xf *)E.al_xf.p, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, n_map,
+               (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, half, one, two, E.nn_dbits.p, E.al_ctr.p);
+    std::vector<unsigned long long> c((size_t)nf * AL_NCTR);
+    HIPC(h, hipMemcpyAsync(c.data(), E.al_ctr.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    // every frame's ranks over its kept points, one select launch for all frames, and numpy's formulas on the six values of each
+    std::vector<AlRanks> rk(nf);
+    std::vector<double> g(2 * (size_t)nf), v((size_t)nf * OV_SEL_MAX);
+    uint64_t n_kept = 0, below[3] = {0, 0, 0};
+    unsigned long long max_bits = 0;
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const unsigned long long *cf = &c[(size_t)f * AL_NCTR];
+        memset(&rk[f], 0, sizeof(AlRanks));
+        rk[f].n = (off[f + 1] - off[f]) - cf[AL_NON_FINITE];
+        if (rk[f].n) {
+            uint64_t r6[OV_SEL_MAX];
+            ov_ranks(rk[f].n, r6, &g[2 * f], &g[2 * f + 1]);
+            for (uint32_t k = 0; k < OV_SEL_MAX; ++k) rk[f].rk[k] = r6[k];
+        }
+        n_kept += rk[f].n;
+        below[0] += cf[AL_BELOW_HALF];
+        below[1] += cf[AL_BELOW_ONE];
+        below[2] += cf[AL_BELOW_TWO];
+        max_bits = std::max(max_bits, cf[AL_MAX_BITS]);
+    }
+    if (n_kept) {
+        HIPC(h, hipMemcpyAsync(E.al_rank.p, rk.data(), n_frames * sizeof(AlRanks), hipMemcpyHostToDevice, h->stream));
+        LAUNCH(h, "al_select", k_al_select, n_frames, 256, (const unsigned long long *)E.nn_dbits.p, (const uint32_t *)E.al_off.p,
+               (const AlRanks *)E.al_rank.p, E.al_val.p);
+        HIPC(h, hipMemcpyAsync(v.data(), E.al_val.p, v.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
+    }
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const unsigned long long *cf = &c[(size_t)f * AL_NCTR];
+        rows[f].n_points = off[f + 1] - off[f];
+        rows[f].n_non_finite = cf[AL_NON_FINITE];
+        ov_fill(rk[f].n, cf[AL_BELOW_HALF], cf[AL_BELOW_ONE], cf[AL_BELOW_TWO], cf[AL_MAX_BITS], &v[(size_t)f * OV_SEL_MAX], g[2 * f], g[2 * f + 1],
+                &rows[f].r);
+    }
+    if (summary) {  // the kept points of all frames: the whole distance array, the dropped points' sentinels above every rank
+        double sv[OV_SEL_MAX] = {}, g90 = 0, g99 = 0;
+        if (n_kept) {
+            uint64_t srk[OV_SEL_MAX];
+            ov_ranks(n_kept, srk, &g90, &g99);
+            if ((rc = ov_select(h, E.nn_dbits.p, n, srk, sv))) return rc;
+        }
+        ov_fill(n_kept, below[0], below[1], below[2], max_bits, sv, g90, g99, summary);
+    }
+    return ERASOR_OK;
+}
+
+int erasor_hip_align_frames_clouds(erasor_hip_handle *h, const void *map_xyzi, size_t n_map, int map_is_device, const void *scans_xyzi,
+                                   size_t n_scan_points, const uint64_t *offsets, size_t n_frames, int scans_are_device,
+                                   const float T_lidar2body[16], const float *T_body2origin, double voxelsize, erasor_align_row *rows,
+                                   erasor_overlap_result *summary) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_align_frames_clouds";
+    int rc = al_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, voxelsize, rows);
+    if (rc || (rc = check_cloud(h, who, "NULL map or more than 2^30 map points", map_xyzi, n_map))) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr, *q = nullptr;
+    if ((rc = ev_input(h, map_xyzi, n_map, map_is_device, h->ev.gt, &m)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q)))
+        return rc;
+    return al_run(h, who, m, (uint32_t)n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, voxelsize, rows,
+                  summary);
+}
+
+int erasor_hip_align_frames_map(erasor_hip_handle *h, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                                int scans_are_device, const float T_lidar2body[16], const float *T_body2origin, double voxelsize,
+                                erasor_align_row *rows, erasor_overlap_result *summary) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_align_frames_map";
+    int rc = al_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, voxelsize, rows);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr, *q = nullptr;
+    uint32_t n_map = 0;
+    if ((rc = map_on_device(h, who, h->ev.map, &m, &n_map)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q))) return rc;
+    return al_run(h, who, m, n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, voxelsize, rows, summary);
+}
+
+// ---- label_map (fill_removert_intensity.cpp:24-59, compare_map.cpp:77-110) and calc_complement (compare_complement.cpp:43-75): the
+// overlap report's tree searched in FLANN's float32 metric (kernels: nearest.hip.h).  Like ov_run: the main stream, the evaluator's
+// scratch, the tree's sort in bank 2.
+
+int erasor_hip_label_map(erasor_hip_handle *h, const void *src_xyzi, size_t n_src, int src_is_device, const void *medium_xyzi, size_t n_medium,
+                         int medium_is_device, double leaf, float *dst_xyzi, size_t cap_points, erasor_label_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    if (!res) {
+        h->err = "erasor_hip_label_map: res is NULL";
+        return ERASOR_E_INVALID;
+    }
+    if (!(leaf > 0) || !std::isfinite(leaf)) {
+        h->err = "erasor_hip_label_map: leaf must be a finite number > 0";
+        return ERASOR_E_INVALID;
+    }
+    int rc = check_cloud(h, "erasor_hip_label_map", BAD_CLOUD, src_xyzi, n_src);
+    if (rc || (rc = check_cloud(h, "erasor_hip_label_map", BAD_CLOUD, medium_xyzi, n_medium))) return rc;
+    if (n_src && !n_medium) {
+        h->err = "erasor_hip_label_map: empty medium (no labelled point to take a label from)";
+        return ERASOR_E_INVALID;
+    }
+    erasor_label_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_src = n_src;
+    if (!n_src) {
+        *res = r;
+        return ERASOR_OK;
+    }
+    HIPC(h, hipSetDevice(h->device));
+    auto &E = h->ev;
+    const float4 *s = nullptr, *m = nullptr;
+    if ((rc = ev_input(h, src_xyzi, n_src, src_is_device, E.est, &s)) || (rc = ev_input(h, medium_xyzi, n_medium, medium_is_device, E.gt, &m)))
+        return rc;
+    // 1. pcl::VoxelGrid at leaf (the centroids; their w is not read).  Index overflow: the input itself, as PCL returns it
+    uint32_t nq = 0;
+    bool passthrough = false;
+    if ((rc = ev_voxelize(h, s, (uint32_t)n_src, leaf, E.est, &nq, &passthrough))) return rc;
+    // 2. every centroid takes the intensity of its nearest medium point (KdTreeFLANN, K = 1)
+    MainStreamScope scope(h, true);
+    const uint32_t nm = (uint32_t)n_medium;
+    uint32_t P = 1;
+    if ((rc = nn_pad(h, nm, &P, "erasor_hip_label_map", "medium"))) return rc;
+    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.fm_ctr, FM_NCTR) || ensure(h, E.fm_out, (size_t)nq + 1)) return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if ((rc = nn_tree(h, m, nm, P, "erasor_hip_label_map", "medium point(s)"))) return rc;
+    HIPC(h, hipMemsetAsync(E.fm_ctr.p, 0, FM_NCTR * sizeof(unsigned long long), h->stream));
+    if (nq)
+        LAUNCH(h, "lm_query", k_lm_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, (const float4 *)E.est.p, nq, (const float4 *)E.nn_pts.p,
+               (const uint32_t *)E.nn_idx.p, nm, (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, E.fm_out.p, E.fm_ctr.p);
+    unsigned long long c[FM_NCTR];
+    HIPC(h, hipMemcpyAsync(c, E.fm_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (c[FM_NON_FINITE]) {
+        h->err = "erasor_hip_label_map: non-finite coordinate (NaN / Inf) in " + std::to_string(c[FM_NON_FINITE]) + " centroid(s)";
+        return ERASOR_E_INVALID;
+    }
+    r.n_out = nq;
+    r.n_tied = c[FM_TIED];
+    r.passthrough = passthrough ? 1u : 0u;
+    *res = r;
+    if (!dst_xyzi) return ERASOR_OK;
+    if (nq > cap_points) return ERASOR_E_CAPACITY;
+    return d2h(h, dst_xyzi, E.fm_out.p, (size_t)nq * sizeof(float4));
+}
+
+int erasor_hip_static_complement(erasor_hip_handle *h, const void *est_xyzi, size_t n_est, int est_is_device, const void *gt_xyzi, size_t n_gt,
+                                 int gt_is_device, float *dst_xyzi, size_t cap_points, erasor_complement_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    if (!res) {
+        h->err = "erasor_hip_static_complement: res is NULL";
+        return ERASOR_E_INVALID;
+    }
+    int rc = check_cloud(h, "erasor_hip_static_complement", BAD_CLOUD, est_xyzi, n_est);
+    if (rc || (rc = check_cloud(h, "erasor_hip_static_complement", BAD_CLOUD, gt_xyzi, n_gt))) return rc;
+    erasor_complement_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_gt = n_gt;
+    if (!n_gt) {
+        *res = r;
+        return ERASOR_OK;
+    }
+    HIPC(h, hipSetDevice(h->device));
+    auto &E = h->ev;
+    const float4 *e = nullptr, *g = nullptr;
+    if ((rc = ev_input(h, est_xyzi, n_est, est_is_device, E.est, &e)) || (rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, E.gt, &g))) return rc;
+    MainStreamScope scope(h, true);
+    const uint32_t ne = (uint32_t)n_est, ng = (uint32_t)n_gt;
+    uint32_t P = 1;
+    if ((rc = nn_pad(h, ne, &P, "erasor_hip_static_complement", "estimate"))) return rc;
+    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.fm_ctr, FM_NCTR) || ensure(h, E.fm_flag, (size_t)ng + 1) || ensure(h, E.fm_pl, (size_t)ng + 1) ||
+        ensure(h, E.fm_tops, ng / 1024 + 4) || ensure(h, E.fm_out, (size_t)ng + 1))
+        return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if (ne && (rc = nn_tree(h, e, ne, P, "erasor_hip_static_complement", "estimated point(s)"))) return rc;
+    HIPC(h, hipMemsetAsync(E.fm_ctr.p, 0, FM_NCTR * sizeof(unsigned long long), h->stream));
+    // the lost flags, then the lost points in ground-truth order: an exclusive scan of the flags and a scatter (no atomic decides a slot)
+    LAUNCH(h, "cp_query", k_cp_query, cdiv(ng, NN_QBLOCK), NN_QBLOCK, g, ng, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, ne,
+           (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, 0.03, E.fm_flag.p, E.fm_ctr.p);
+    if (dst_xyzi) {
+        scan_u32(h, E.fm_flag.p, E.fm_pl.p, E.fm_tops.p, ng, ng, nullptr, nullptr, "cp_compact");
+        LAUNCH(h, "cp_compact", k_f_compact, cdiv(ng, 256), 256, g, ng, (const uint32_t *)E.fm_flag.p, (const uint32_t *)E.fm_pl.p,
+               (const uint32_t *)E.fm_tops.p, E.fm_out.p);
+    }
+    unsigned long long c[FM_NCTR];
+    HIPC(h, hipMemcpyAsync(c, E.fm_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (c[FM_NON_FINITE]) {
+        h->err = "erasor_hip_static_complement: non-finite coordinate (NaN / Inf) in " + std::to_string(c[FM_NON_FINITE]) + " ground-truth point(s)";
+        return ERASOR_E_INVALID;
+    }
+    r.n_gt_static = c[FM_GT_STATIC];
+    r.n_lost = c[FM_LOST];
+    r.n_label_out_of_range = c[FM_LABEL_OOR];
+    *res = r;
+    if (!dst_xyzi) return ERASOR_OK;
+    if (r.n_lost > cap_points) return ERASOR_E_CAPACITY;
+    return d2h(h, dst_xyzi, E.fm_out.p, (size_t)r.n_lost * sizeof(float4));
+}
+
+// ---- PR / RR by class and by dynamic instance (kernels: evaluate.hip.h, k_ev_*_keys onwards) ----
+// ev_run in its by-key mode, then the rows on the main stream in the evaluator's scratch: the class rows by a flag per non-empty key, its
+// exclusive scan and a scatter (key order, no sort); the instance rows by a radix sort of the dynamic points' records by label (histogram
+// bank 2, like the overlap report's tree: the query chains of nodes announced ahead keep bank 0), run heads, their scan, and one atomic
+// per row and counter of a wavefront.
+static void bc_fill(const std::vector<uint32_t> &rows, size_t n, bool instances, erasor_eval_class_row *out) {
+    for (size_t r = 0; r < n; ++r) {
+        const uint32_t *v = &rows[r * EV_ROW];
+        erasor_eval_class_row &o = out[r];
+        o.key = v[0];
+        const uint32_t sem = v[0] & 0xFFFFu;
+        o.is_dynamic = (instances || (v[0] < EV_KEY_OOR && sem >= 252u && sem <= 259u)) ? 1u : 0u;
+        o.n_gt = v[1 + EV_K_GT];
+        o.n_within = v[1 + EV_K_WITHIN];
+        o.n_preserved = v[1 + EV_K_KEPT];
+        o.n_tied = v[1 + EV_K_TIED];
+        o.n_est = v[1 + EV_K_EST];
+    }
+}
+
+static int bc_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize,
+                  erasor_eval_class_row *classes, size_t cap_classes, size_t *n_classes, erasor_eval_class_row *instances, size_t cap_instances,
+                  size_t *n_instances, erasor_eval_result *res) {
+    uint32_t n_rec = 0;
+    int rc = ev_run(h, gt, n_gt, est, n_est, voxelsize, nullptr, res, &n_rec);
+    if (rc) return rc;
+    auto &E = h->ev;
+    MainStreamScope scope(h, true);
+    const size_t n_scan = std::max<size_t>(EV_NKEYS, n_rec) + 1;
+    if (ensure(h, E.bc_flag, n_scan) || ensure(h, E.bc_pl, n_scan) || ensure(h, E.bc_tops, n_scan / 1024 + 4) ||
+        ensure(h, E.bc_crows, (size_t)EV_NKEYS * EV_ROW))
+        return ERASOR_E_NO_DEVICE;
+    LAUNCH(h, "ev_rows", k_ev_class_flags, cdiv(EV_NKEYS, 256), 256, (const uint32_t *)E.bc_tab.p, E.bc_flag.p);
+    scan_u32(h, E.bc_flag.p, E.bc_pl.p, E.bc_tops.p, EV_NKEYS, EV_NKEYS, nullptr, E.bc_cur.p + 1, "ev_rows");
+    LAUNCH(h, "ev_rows", k_ev_class_rows, cdiv(EV_NKEYS, 256), 256, (const uint32_t *)E.bc_tab.p, (const uint32_t *)E.bc_flag.p,
+           (const uint32_t *)E.bc_pl.p, (const uint32_t *)E.bc_tops.p, E.bc_crows.p);
+    uint32_t n_cls = 0;
+    HIPC(h, hipMemcpyAsync(&n_cls, E.bc_cur.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    uint32_t n_inst = 0;
+    if (n_rec) {
+        const size_t n1 = (size_t)n_rec + 1;
+        if (ensure(h, E.nn_ka, n1) || ensure(h, E.nn_kb, n1) || ensure(h, E.nn_va, n1) || ensure(h, E.nn_vb, n1) || ensure(h, E.bc_irows, n1 * EV_ROW))
+            return ERASOR_E_NO_DEVICE;
+        const uint32_t *skeys = nullptr, *sperm = nullptr;
+        if (radix_sort(h, E.bc_ikey.p, n_rec, nullptr, 32, E.nn_ka.p, E.nn_kb.p, E.nn_va.p, E.nn_vb.p, &skeys, &sperm, "ev_rows"))
+            return ERASOR_E_NO_DEVICE;
+        LAUNCH(h, "ev_rows", k_ev_run_heads, cdiv(n_rec, 256), 256, skeys, n_rec, E.bc_flag.p);
+        scan_u32(h, E.bc_flag.p, E.bc_pl.p, E.bc_tops.p, n_rec, n_rec, nullptr, E.bc_cur.p + 2, "ev_rows");
+        HIPC(h, hipMemsetAsync(E.bc_irows.p, 0, (size_t)n_rec * EV_ROW * sizeof(uint32_t), h->stream));
+        LAUNCH(h, "ev_rows", k_ev_inst_rows, cdiv(n_rec, 256), 256, skeys, sperm, (const uint32_t *)E.bc_ival.p, (const uint32_t *)E.bc_flag.p,
+               (const uint32_t *)E.bc_pl.p, (const uint32_t *)E.bc_tops.p, n_rec, E.bc_irows.p);
+        HIPC(h, hipMemcpyAsync(&n_inst, E.bc_cur.p + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPC(h, hipStreamSynchronize(h->stream));
+    *n_classes = n_cls;
+    *n_instances = n_inst;
+    if (n_cls > cap_classes || n_inst > cap_instances) return ERASOR_E_CAPACITY;  // (the counts and res are written: size and call again)
+    std::vector<uint32_t> rows((size_t)std::max(n_cls, n_inst) * EV_ROW);
+    if ((rc = d2h(h, rows.data(), E.bc_crows.p, (size_t)n_cls * EV_ROW * sizeof(uint32_t)))) return rc;
+    bc_fill(rows, n_cls, false, classes);
+    if ((rc = d2h(h, rows.data(), E.bc_irows.p, (size_t)n_inst * EV_ROW * sizeof(uint32_t)))) return rc;
+    bc_fill(rows, n_inst, true, instances);
+    return ERASOR_OK;
+}
+
+static int bc_check_rows(erasor_hip_handle *h, const erasor_eval_class_row *classes, size_t cap_classes, size_t *n_classes,
+                         const erasor_eval_class_row *instances, size_t cap_instances, size_t *n_instances) {
+    if (!n_classes || !n_instances || (!classes && cap_classes) || (!instances && cap_instances)) {
+        h->err = "erasor_hip_evaluate_by_class: NULL row count, or a NULL row array with a capacity > 0";
+        return ERASOR_E_INVALID;
+    }
+    *n_classes = 0;
+    *n_instances = 0;
+    return ERASOR_OK;
+}
+
+int erasor_hip_evaluate_clouds_by_class(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, const void *est_xyzi,
+                                        size_t n_est, int est_is_device, double voxel_leaf, double voxelsize, erasor_eval_class_row *classes,
+                                        size_t cap_classes, size_t *n_classes, erasor_eval_class_row *instances, size_t cap_instances,
+                                        size_t *n_instances, erasor_eval_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    EvPair p;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, false, res);
+    if (rc || (rc = bc_check_rows(h, classes, cap_classes, n_classes, instances, cap_instances, n_instances)) ||
+        (rc = ev_pair_clouds(h, "erasor_hip_evaluate_clouds_by_class", gt_xyzi, n_gt, gt_is_device, est_xyzi, n_est, est_is_device, voxel_leaf, &p)))
+        return rc;
+    return bc_run(h, p.g, p.ng, p.e, p.ne, voxelsize, classes, cap_classes, n_classes, instances, cap_instances, n_instances, res);
+}
+
+int erasor_hip_evaluate_map_by_class(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, double voxel_leaf, double voxelsize,
+                                     erasor_eval_class_row *classes, size_t cap_classes, size_t *n_classes, erasor_eval_class_row *instances,
+                                     size_t cap_instances, size_t *n_instances, erasor_eval_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    EvPair p;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, false, res);
+    if (rc || (rc = bc_check_rows(h, classes, cap_classes, n_classes, instances, cap_instances, n_instances)) ||
+        (rc = ev_pair_map(h, "erasor_hip_evaluate_map_by_class", gt_xyzi, n_gt, gt_is_device, voxel_leaf, &p)))
+        return rc;
+    return bc_run(h, p.g, p.ng, p.e, p.ne, voxelsize, classes, cap_classes, n_classes, instances, cap_instances, n_instances, res);
+}
+
+// ---- bird's-eye images (erasor_hip_render_*; kernels: render.hip.h) ----
+// Like ev_run: the main stream, behind whatever a collected step launched ahead there; scratch of the renderer's own (h->ev.rd_*).
+static constexpr uint32_t RD_MAX_EDGE = 16384u;
+static constexpr uint64_t RD_MAX_PIXELS = 1ull << 26;
+
+static int rd_check_view(erasor_hip_handle *h, const erasor_render_view *v) {
+    if (!v) {
+        h->err = "erasor_hip_render: view is NULL";
+        return ERASOR_E_INVALID;
+    }
+    if (!(v->res > 0) || !std::isfinite(v->res) || !std::isfinite(v->x0) || !std::isfinite(v->y0) || !std::isfinite(v->z_lo) || !std::isfinite(v->z_hi)) {
+        h->err = "erasor_hip_render: the view needs a finite res > 0 and finite x0, y0, z_lo, z_hi";
+        return ERASOR_E_INVALID;
+    }
+    if (v->width < 1 || v->height < 1 || v->width > RD_MAX_EDGE || v->height > RD_MAX_EDGE || (uint64_t)v->width * v->height > RD_MAX_PIXELS) {
+        h->err = "erasor_hip_render: the view needs 1 <= width, height <= 16384 and width * height <= 2^26 (got " + std::to_string(v->width) + " x " +
+                 std::to_string(v->height) + ")";
+        return ERASOR_E_INVALID;
+    }
+    return ERASOR_OK;
+}
+
+// the kernels' view and mode from the caller's
+static RdView rd_view(const erasor_render_view *view) {
+    RdView v;
+    v.x0 = view->x0;
+    v.y0 = view->y0;
+    v.res = view->res;
+    v.z_lo = view->z_lo;
+    v.z_hi = view->z_hi;
+    v.width = view->width;
+    v.height = view->height;
+    v.tiles_x = cdiv(view->width, RD_TILE);
+    v.background = view->background & 0xFFFFFFu;
+    return v;
+}
+static RdMode rd_mode(int mode, int32_t target_class, int32_t target_instance) {
+    RdMode m;
+    m.mode = (uint32_t)mode;
+    m.target_class = mode == ERASOR_RENDER_LABEL ? target_class : -1;
+    m.target_instance = target_instance;
+    for (uint32_t c = 0; c < RD_NCAT; ++c) m.palette[c] = ERASOR_RENDER_PALETTE[c];
+    return m;
+}
+static void rd_stats(const unsigned long long c[RD_NCTR], uint64_t n, erasor_render_stats *stats) {
+    erasor_render_stats s;
+    memset(&s, 0, sizeof(s));
+    s.n_points = n;
+    s.n_outside = c[RD_C_OUTSIDE];
+    s.n_nonfinite = c[RD_C_NONFINITE];
+    for (uint32_t k = 0; k < RD_NCAT; ++k) {
+        s.cat_points[k] = c[RD_C_CATPTS + k];
+        s.cat_pixels[k] = c[RD_C_CATPIX + k];
+        s.n_drawn += s.cat_points[k];
+        s.n_pixels_hit += s.cat_pixels[k];
+    }
+    *stats = s;
+}
+
+// the view fitted to pts[0 .. n) (device); see erasor_hip_render_fit
+static int rd_fit(erasor_hip_handle *h, const float4 *pts, uint32_t n, double res, uint32_t margin, uint32_t background, erasor_render_view *view) {
+    auto &E = h->ev;
+    if (!view) {
+        h->err = "erasor_hip_render_fit: view is NULL";
+        return ERASOR_E_INVALID;
+    }
+    if (!(res > 0) || !std::isfinite(res) || margin < 1 || margin > 1024) {
+        h->err = "erasor_hip_render_fit: res must be a finite number > 0 and margin_px in 1 .. 1024";
+        return ERASOR_E_INVALID;
+    }
+    if (ensure(h, E.rd_zb, (size_t)n + 1) || ensure(h, E.rd_bb, 4) || ensure(h, E.rd_ctr, RD_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256))
+        return ERASOR_E_NO_DEVICE;
+    MainStreamScope scope(h);
+    HIPC(h, hipMemsetAsync(E.rd_bb.p, 0xFF, 2 * sizeof(uint32_t), h->stream));
+    HIPC(h, hipMemsetAsync(E.rd_bb.p + 2, 0, 2 * sizeof(uint32_t), h->stream));
+    HIPC(h, hipMemsetAsync(E.rd_ctr.p, 0, sizeof(unsigned long long), h->stream));
+    if (n) LAUNCH(h, "render_fit", k_rd_fit, cdiv(n, 2048), 256, pts, n, E.rd_zb.p, E.rd_bb.p, E.rd_ctr.p);
+    uint32_t bb[4];
+    unsigned long long nfin = 0;
+    HIPC(h, hipMemcpyAsync(bb, E.rd_bb.p, sizeof(bb), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipMemcpyAsync(&nfin, E.rd_ctr.p, sizeof(nfin), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (!nfin) {
+        h->err = "erasor_hip_render_fit: the cloud has no finite point";
+        return ERASOR_E_INVALID;
+    }
+    auto inv = [](uint32_t k) {  // (rd_zinv on the host)
+        const uint32_t b = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
+        float f;
+        memcpy(&f, &b, sizeof(f));
+        return (double)f;
+    };
+    const double mn[2] = {inv(bb[0]), inv(bb[1])}, mx[2] = {inv(bb[2]), inv(bb[3])};
+    double o[2], sz[2];
+    for (int a = 0; a < 2; ++a) {
+        o[a] = floor(mn[a] / res) * res - (double)margin * res;
+        sz[a] = floor((mx[a] - o[a]) / res) + 1.0 + (double)margin;
+    }
+    if (!std::isfinite(o[0]) || !std::isfinite(o[1]) || !(sz[0] <= RD_MAX_EDGE) || !(sz[1] <= RD_MAX_EDGE) || !(sz[0] * sz[1] <= (double)RD_MAX_PIXELS)) {
+        // the smallest res that fits: the sizes at res r are about span / r + 2 * margin + 2
+        const double sx = mx[0] - mn[0], sy = mx[1] - mn[1], pad = 2.0 * margin + 2.0;
+        double lo = res, hi = res;
+        auto fits = [&](double r) {
+            const double w = sx / r + pad, hh = sy / r + pad;
+            return w <= RD_MAX_EDGE && hh <= RD_MAX_EDGE && w * hh <= (double)RD_MAX_PIXELS;
+        };
+        while (!fits(hi) && hi < 1e300) hi *= 2;
+        for (int it = 0; it < 60; ++it) {
+            const double mid = 0.5 * (lo + hi);
+            (fits(mid) ? hi : lo) = mid;
+        }
+        char buf[256];
+        snprintf(buf, sizeof(buf), "erasor_hip_render_fit: at res %g the image would be %.0f x %.0f pixels (limits: 16384 per edge, 2^26 in all); "
+                 "the smallest res that fits is about %.3g", res, sz[0], sz[1], hi * 1.001);
+        h->err = buf;
+        return ERASOR_E_INVALID;
+    }
+    // z_lo / z_hi: the values at ranks floor(0.02 (n - 1)) and floor(0.98 (n - 1)) of the finite heights
+    uint64_t rk[OV_SEL_MAX];
+    rk[0] = (uint64_t)floor(0.02 * (double)(nfin - 1));
+    rk[1] = (uint64_t)floor(0.98 * (double)(nfin - 1));
+    for (uint32_t t = 2; t < OV_SEL_MAX; ++t) rk[t] = rk[0];
+    double sel[OV_SEL_MAX];
+    const int rc = ov_select(h, E.rd_zb.p, n, rk, sel, 24);
+    if (rc) return rc;
+    unsigned long long kz[2];
+    memcpy(kz, sel, sizeof(kz));
+    memset(view, 0, sizeof(*view));
+    view->x0 = o[0];
+    view->y0 = o[1];
+    view->res = res;
+    view->width = (uint32_t)sz[0];
+    view->height = (uint32_t)sz[1];
+    view->z_lo = inv((uint32_t)kz[0]);
+    view->z_hi = inv((uint32_t)kz[1]);
+    view->background = background & 0xFFFFFFu;
+    return ERASOR_OK;
+}
+
+// pts[0 .. n) (device; code: the evaluator's per-point codes for ERASOR_RENDER_EVAL) into rgb and stats
+static int rd_run(erasor_hip_handle *h, const float4 *pts, uint32_t n, const uint8_t *code, int mode, int32_t target_class, int32_t target_instance,
+                  const erasor_render_view *view, void *rgb, int rgb_is_device, erasor_render_stats *stats, hipEvent_t ev_begin = nullptr,
+                  hipEvent_t ev_end = nullptr) {  // (ev_begin / ev_end: recorded around the clears and the launches, for the hooks' timing)
+    auto &E = h->ev;
+    const int rc = rd_check_view(h, view);
+    if (rc) return rc;
+    const RdView v = rd_view(view);
+    const RdMode m = rd_mode(mode, target_class, target_instance);
+    const uint32_t ntiles = v.tiles_x * cdiv(view->height, RD_TILE);
+    const size_t bytes = (size_t)view->width * view->height * 3;
+    if (ensure(h, E.rd_ctr, RD_NCTR) || ensure(h, E.rd_cnt, (size_t)ntiles + 1) || ensure(h, E.rd_pl, (size_t)ntiles + 1) ||
+        ensure(h, E.rd_tops, ntiles / 1024 + 4) || ensure(h, E.rd_tile, (size_t)n + 1) || ensure(h, E.rd_rec, (size_t)n + 1) ||
+        ensure(h, E.rd_srt, (size_t)n + 1) || ensure(h, E.rd_img, bytes + 4))
+        return ERASOR_E_NO_DEVICE;
+    MainStreamScope scope(h);
+    if (ev_begin) HIPC(h, hipEventRecord(ev_begin, h->stream));
+    HIPC(h, hipMemsetAsync(E.rd_ctr.p, 0, RD_NCTR * sizeof(unsigned long long), h->stream));
+    HIPC(h, hipMemsetAsync(E.rd_cnt.p, 0, ((size_t)ntiles + 1) * sizeof(uint32_t), h->stream));
+    if (n) LAUNCH(h, "render_bin", k_rd_bin, cdiv(n, 256), 256, pts, n, code, v, m, E.rd_tile.p, E.rd_rec.p, E.rd_cnt.p, E.rd_ctr.p);
+    scan_u32(h, E.rd_cnt.p, E.rd_pl.p, E.rd_tops.p, ntiles + 1, ntiles + 1, nullptr, nullptr, "render_scan");
+    LAUNCH(h, "render_scan", k_ev_offsets, cdiv(ntiles + 1, 256), 256, (const uint32_t *)E.rd_pl.p, (const uint32_t *)E.rd_tops.p, ntiles + 1, E.rd_cnt.p,
+           E.rd_pl.p);
+    if (n)
+        LAUNCH(h, "render_scatter", k_rd_scatter, cdiv(n, 256), 256, (const uint32_t *)E.rd_tile.p, (const unsigned long long *)E.rd_rec.p, n, E.rd_pl.p,
+               E.rd_srt.p);
+    LAUNCH(h, "render_resolve", k_rd_resolve, ntiles, 256, (const unsigned long long *)E.rd_srt.p, (const uint32_t *)E.rd_cnt.p, v, m, E.rd_img.p,
+           E.rd_ctr.p);
+    if (ev_end) HIPC(h, hipEventRecord(ev_end, h->stream));
+    unsigned long long c[RD_NCTR];
+    HIPC(h, hipMemcpyAsync(c, E.rd_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    if (rgb) HIPC(h, hipMemcpyAsync(rgb, E.rd_img.p, bytes, rgb_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (stats) rd_stats(c, n, stats);
+    return ERASOR_OK;
+}
+
+int erasor_hip_render_fit(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, double res, uint32_t margin_px, uint32_t background,
+                          erasor_render_view *view) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = check_cloud(h, "erasor_hip_render_fit", BAD_CLOUD, xyzi, n);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    if ((rc = ev_input(h, xyzi, n, is_device, h->ev.rd_pts, &p))) return rc;
+    return rd_fit(h, p, (uint32_t)n, res, margin_px, background, view);
+}
+int erasor_hip_render_fit_map(erasor_hip_handle *h, double res, uint32_t margin_px, uint32_t background, erasor_render_view *view) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    uint32_t n = 0;
+    const int rc = map_on_device(h, "erasor_hip_render_fit_map", h->ev.rd_map, &p, &n);
+    if (rc) return rc;
+    return rd_fit(h, p, n, res, margin_px, background, view);
+}
+
+static int rd_check_mode(erasor_hip_handle *h, int mode) {
+    if (mode != ERASOR_RENDER_LABEL && mode != ERASOR_RENDER_HEIGHT) {
+        h->err = "erasor_hip_render: mode must be ERASOR_RENDER_LABEL or ERASOR_RENDER_HEIGHT (the error map: erasor_hip_render_eval_*)";
+        return ERASOR_E_INVALID;
+    }
+    return ERASOR_OK;
+}
+int erasor_hip_render_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, int mode, int32_t target_class, int32_t target_instance,
+                             const erasor_render_view *view, void *rgb, int rgb_is_device, erasor_render_stats *stats) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = rd_check_mode(h, mode);
+    if (rc || (rc = rd_check_view(h, view)) || (rc = check_cloud(h, "erasor_hip_render_clouds", BAD_CLOUD, xyzi, n))) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    if ((rc = ev_input(h, xyzi, n, is_device, h->ev.rd_pts, &p))) return rc;
+    return rd_run(h, p, (uint32_t)n, nullptr, mode, target_class, target_instance, view, rgb, rgb_is_device, stats);
+}
+int erasor_hip_render_map(erasor_hip_handle *h, int mode, int32_t target_class, int32_t target_instance, const erasor_render_view *view, void *rgb,
+                          int rgb_is_device, erasor_render_stats *stats) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = rd_check_mode(h, mode);
+    if (rc || (rc = rd_check_view(h, view))) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    uint32_t n = 0;
+    if ((rc = map_on_device(h, "erasor_hip_render_map", h->ev.rd_map, &p, &n))) return rc;
+    return rd_run(h, p, n, nullptr, mode, target_class, target_instance, view, rgb, rgb_is_device, stats);
+}
+
+// the evaluation of a pair as erasor_hip_evaluate_* runs it, its codes left in h->ev.code, then the ground truth drawn by them
+static int rd_eval(erasor_hip_handle *h, const EvPair &p, double voxelsize, const erasor_render_view *view, void *rgb, int rgb_is_device,
+                   erasor_render_stats *stats, erasor_eval_result *res) {
+    const int rc = ev_run(h, p.g, p.ng, p.e, p.ne, voxelsize, nullptr, res, nullptr, true);
+    if (rc) return rc;
+    return rd_run(h, p.g, p.ng, h->ev.code.p, ERASOR_RENDER_EVAL, -1, -1, view, rgb, rgb_is_device, stats);
+}
+int erasor_hip_render_eval_clouds(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, const void *est_xyzi, size_t n_est,
+                                  int est_is_device, double voxel_leaf, double voxelsize, const erasor_render_view *view, void *rgb,
+                                  int rgb_is_device, erasor_render_stats *stats, erasor_eval_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    EvPair p;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, false, res);
+    if (rc || (rc = rd_check_view(h, view)) ||
+        (rc = ev_pair_clouds(h, "erasor_hip_render_eval_clouds", gt_xyzi, n_gt, gt_is_device, est_xyzi, n_est, est_is_device, voxel_leaf, &p)))
+        return rc;
+    return rd_eval(h, p, voxelsize, view, rgb, rgb_is_device, stats, res);
+}
+int erasor_hip_render_eval_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_gt, int gt_is_device, double voxel_leaf, double voxelsize,
+                               const erasor_render_view *view, void *rgb, int rgb_is_device, erasor_render_stats *stats, erasor_eval_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    EvPair p;
+    int rc = ev_check_args(h, voxel_leaf, voxelsize, false, res);
+    if (rc || (rc = rd_check_view(h, view)) || (rc = ev_pair_map(h, "erasor_hip_render_eval_map", gt_xyzi, n_gt, gt_is_device, voxel_leaf, &p))) return rc;
+    return rd_eval(h, p, voxelsize, view, rgb, rgb_is_device, stats, res);
+}
+
+#ifdef ERASOR_HIP_TEST_HOOKS
+// rd_run's image and counters by the other rasteriser (one 64-bit atomic max per point on a key image in device memory): the comparison
+// of MEASUREMENTS.md.  Mode LABEL or HEIGHT; tiled != 0: the shipped kernels (rd_run) instead, timed the same way; ms (optional): device
+// time between one event before the clears and one after the last kernel -- the same bracket for both.
+int erasor_hip_debug_render_atomic(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, int mode, const erasor_render_view *view,
+                                   void *rgb, erasor_render_stats *stats, int tiled, double *ms) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    int rc = rd_check_mode(h, mode);
+    if (rc || (rc = rd_check_view(h, view)) || (rc = check_cloud(h, "erasor_hip_debug_render_atomic", BAD_CLOUD, xyzi, n))) return rc;
+    auto &E = h->ev;
+    const float4 *p = nullptr;
+    HIPC(h, hipSetDevice(h->device));
+    if ((rc = ev_input(h, xyzi, n, is_device, E.rd_pts, &p))) return rc;
+    if (tiled) {
+        hipEvent_t a, b;
+        HIPC(h, hipEventCreate(&a));
+        HIPC(h, hipEventCreate(&b));
+        rc = rd_run(h, p, (uint32_t)n, nullptr, mode, -1, -1, view, rgb, 0, stats, a, b);
+        float t = 0.f;
+        if (!rc && hipEventElapsedTime(&t, a, b) != hipSuccess) rc = ERASOR_E_NO_DEVICE;
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+        if (ms) *ms = t;
+        return rc;
+    }
+    const RdView v = rd_view(view);
+    const RdMode m = rd_mode(mode, -1, -1);
+    const size_t npix = (size_t)view->width * view->height;
+    DBuf<unsigned long long> keyimg;
+    if (ensure(h, keyimg, npix + 1) || ensure(h, E.rd_ctr, RD_NCTR) || ensure(h, E.rd_img, npix * 3 + 4)) return ERASOR_E_NO_DEVICE;
+    hipEvent_t a, b;
+    (void)hipEventCreate(&a);
+    (void)hipEventCreate(&b);
+    (void)hipEventRecord(a, h->stream);
+    (void)hipMemsetAsync(E.rd_ctr.p, 0, RD_NCTR * sizeof(unsigned long long), h->stream);
+    (void)hipMemsetAsync(keyimg.p, 0, npix * sizeof(unsigned long long), h->stream);
+    if (n)
+        hipLaunchKernelGGL(k_rd_atomic_points, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, p, (uint32_t)n, (const uint8_t *)nullptr, v, m, keyimg.p,
+                           E.rd_ctr.p);
+    hipLaunchKernelGGL(k_rd_atomic_pixels, dim3(cdiv(npix, 256)), dim3(256), 0, h->stream, (const unsigned long long *)keyimg.p, v, m, E.rd_img.p,
+                       E.rd_ctr.p);
+    (void)hipEventRecord(b, h->stream);
+    unsigned long long c[RD_NCTR];
+    (void)hipMemcpyAsync(c, E.rd_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream);
+    if (rgb) (void)hipMemcpyAsync(rgb, E.rd_img.p, npix * 3, hipMemcpyDeviceToHost, h->stream);
+    const hipError_t e_ = hipStreamSynchronize(h->stream);
+    float t = 0.f;
+    (void)hipEventElapsedTime(&t, a, b);
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    release(keyimg);
+    if (e_ != hipSuccess) return ERASOR_E_NO_DEVICE;
+    if (ms) *ms = t;
+    if (stats) rd_stats(c, n, stats);
+    return ERASOR_OK;
+}
+#endif
+
+#ifdef ERASOR_HIP_TEST_HOOKS
+// test hook: the bounding-volume tree of a cloud (x y z i rows, host or device) as nn_pad / nn_tree build it for overlap, align_frames,
+// label_map and static_complement: P, the points in key order with their original indices, the sorted Morton keys, the boxes of all 2P
+// nodes (node 0 is never written: its rows come back as they lie in the scratch).  cap_nodes: the rows lo / hi hold.
+int erasor_hip_debug_nn_tree(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, uint32_t *P_out, float *pts, uint32_t *idx,
+                             uint32_t *keys, float *lo, float *hi, size_t cap_nodes) {
+    NOFLY(h);
+    if (!h || !xyzi || !n || n > MAX_POINTS || !P_out || !pts || !idx || !keys || !lo || !hi) return ERASOR_E_INVALID;
+    HIPC(h, hipSetDevice(h->device));
+    auto &E = h->ev;
+    const float4 *g = nullptr;
+    int rc = ev_input(h, xyzi, n, is_device, E.gt, &g);
+    if (rc) return rc;
+    MainStreamScope scope(h, true);
+    uint32_t P = 1;
+    if ((rc = nn_pad(h, (uint32_t)n, &P, "erasor_hip_debug_nn_tree", "cloud"))) return rc;
+    if (ensure(h, E.nn_ctr, OV_NCTR)) return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if ((rc = nn_tree(h, g, (uint32_t)n, P, "erasor_hip_debug_nn_tree", "point(s)"))) return rc;
+    *P_out = P;
+    if (2 * (size_t)P > cap_nodes) return ERASOR_E_CAPACITY;
+    if ((rc = d2h(h, pts, E.nn_pts.p, n * sizeof(float4))) || (rc = d2h(h, idx, E.nn_idx.p, n * sizeof(uint32_t))) ||
+        (rc = d2h(h, keys, E.dbg_skeys, n * sizeof(uint32_t))) || (rc = d2h(h, lo, E.nn_lo.p, 2 * (size_t)P * sizeof(float4))) ||
+        (rc = d2h(h, hi, E.nn_hi.p, 2 * (size_t)P * sizeof(float4))))
+        return rc;
+    return ERASOR_OK;
+}
+
+// test hook: k_nn_query (f32 == 0: overlap's float64 search) or k_lm_query (f32 != 0: label_map's float32 search) of n_q queries over
+// the tree of a cloud, built as above, with every query's effort beside the kernel's own outputs: effort[2 * i] = leaves opened,
+// effort[2 * i + 1] = leaf points tested.  f32 == 0: dist / nearest as erasor_hip_overlap_clouds returns them per point; f32 != 0:
+// rows = k_lm_query's output (x, y, z, the nearest point's w), *n_tied its FM_TIED counter.  Queries must be finite.
+int erasor_hip_debug_nn_effort(erasor_hip_handle *h, const float *tree_xyzi, size_t n, const float *query_xyzi, size_t n_q, int f32, double *dist,
+                               uint32_t *nearest, float *rows, uint64_t *n_tied, uint32_t *effort) {
+    NOFLY(h);
+    if (!h || !tree_xyzi || !n || n > MAX_POINTS || !query_xyzi || !n_q || n_q > MAX_POINTS || !effort) return ERASOR_E_INVALID;
+    if (f32 ? (!rows || !n_tied) : (!dist || !nearest)) return ERASOR_E_INVALID;
+    HIPC(h, hipSetDevice(h->device));
+    auto &E = h->ev;
+    const float4 *g = nullptr, *q = nullptr;
+    int rc;
+    if ((rc = ev_input(h, tree_xyzi, n, 0, E.gt, &g)) || (rc = ev_input(h, query_xyzi, n_q, 0, E.est, &q))) return rc;
+    MainStreamScope scope(h, true);
+    const uint32_t nt = (uint32_t)n, nq = (uint32_t)n_q;
+    uint32_t P = 1;
+    if ((rc = nn_pad(h, nt, &P, "erasor_hip_debug_nn_effort", "cloud"))) return rc;
+    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.fm_ctr, FM_NCTR) || ensure(h, E.nn_dbits, n_q + 1) || ensure(h, E.nn_near, n_q + 1) ||
+        ensure(h, E.fm_out, n_q + 1))
+        return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if ((rc = nn_tree(h, g, nt, P, "erasor_hip_debug_nn_effort", "point(s)"))) return rc;
+    HIPC(h, hipMemsetAsync(E.fm_ctr.p, 0, FM_NCTR * sizeof(unsigned long long), h->stream));
+    uint32_t *d_eff = nullptr;  // (the query grid's lanes past n_q never search: 2 * n_q entries are all that is written)
+    HIPC(h, hipMalloc((void **)&d_eff, 2 * n_q * sizeof(uint32_t)));
+    (void)hipMemsetAsync(d_eff, 0xFF, 2 * n_q * sizeof(uint32_t), h->stream);
+    hipLaunchKernelGGL(k_nn_set_effort, dim3(1), dim3(1), 0, h->stream, d_eff);
+    if (f32)
+        LAUNCH(h, "lm_query", k_lm_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, q, nq, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, nt,
+               (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, E.fm_out.p, E.fm_ctr.p);
+    else
+        LAUNCH(h, "ov_query", k_nn_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, q, nq, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, nt,
+               (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, 0.5, 1.0, 2.0, E.nn_dbits.p, E.nn_near.p, E.nn_ctr.p);
+    hipLaunchKernelGGL(k_nn_set_effort, dim3(1), dim3(1), 0, h->stream, (uint32_t *)nullptr);
+    unsigned long long c[FM_NCTR], co[OV_NCTR];
+    rc = d2h(h, effort, d_eff, 2 * n_q * sizeof(uint32_t));
+    (void)hipFree(d_eff);
+    if (rc || (rc = d2h(h, c, E.fm_ctr.p, sizeof(c))) || (rc = d2h(h, co, E.nn_ctr.p, sizeof(co)))) return rc;
+    if (c[FM_NON_FINITE] || co[OV_NON_FINITE]) {
+        h->err = "erasor_hip_debug_nn_effort: non-finite query";
+        return ERASOR_E_INVALID;
+    }
+    if (f32) {
+        *n_tied = c[FM_TIED];
+        return d2h(h, rows, E.fm_out.p, n_q * sizeof(float4));
+    }
+    if ((rc = d2h(h, dist, E.nn_dbits.p, n_q * sizeof(double)))) return rc;
+    return d2h(h, nearest, E.nn_near.p, n_q * sizeof(uint32_t));
+}
+
+// what ev_run / evm_run left in the evaluator's scratch: the bucket count, the bucket offsets and the scattered points and indices
+static int dbg_ev_dump(erasor_hip_handle *h, size_t n, uint32_t *nb_out, uint32_t *off, size_t cap_off, float *pts, uint32_t *idx) {
+    auto &E = h->ev;
+    *nb_out = E.dbg_nb;
+    if ((size_t)E.dbg_nb + 1 > cap_off) return ERASOR_E_CAPACITY;
+    int rc;
+    if ((rc = d2h(h, off, E.cnt.p, ((size_t)E.dbg_nb + 1) * sizeof(uint32_t))) || (rc = d2h(h, pts, E.pts.p, n * sizeof(float4))) ||
+        (rc = d2h(h, idx, E.idx.p, n * sizeof(uint32_t))))
+        return rc;
+    return ERASOR_OK;
+}
+
+// test hook: the hashed grid of an estimate (n > 0 host rows) at a voxel size, built by erasor_hip_evaluate_clouds' own path (ev_run, an
+// empty ground truth): nb, off[nb + 1], the scattered points and their indices
+int erasor_hip_debug_ev_grid(erasor_hip_handle *h, const float *est_xyzi, size_t n, double voxelsize, uint32_t *nb_out, uint32_t *off, size_t cap_off,
+                             float *pts, uint32_t *idx) {
+    if (!h || !est_xyzi || !n || !nb_out || !off || !pts || !idx) return ERASOR_E_INVALID;
+    erasor_eval_result res;
+    const int rc = erasor_hip_evaluate_clouds(h, nullptr, 0, 0, est_xyzi, n, 0, 0.0, voxelsize, nullptr, &res);
+    if (rc) return rc;
+    return dbg_ev_dump(h, n, nb_out, off, cap_off, pts, idx);
+}
+
+// test hook: the combined table of k estimates (host rows; some may be empty, not all), built by erasor_hip_evaluate_many's own path
+// (evm_run, an empty ground truth): as above over all estimates back to back (idx: combined indices), and tab[4 * j ..] = estimate j's
+// (first point, points, first bucket, bucket mask)
+int erasor_hip_debug_ev_grid_many(erasor_hip_handle *h, const void *const *est_xyzi, const size_t *n_est, size_t k, double voxelsize, uint32_t *nb_out,
+                                  uint32_t *off, size_t cap_off, float *pts, uint32_t *idx, uint32_t *tab) {
+    if (!h || !est_xyzi || !n_est || !k || !nb_out || !off || !pts || !idx || !tab) return ERASOR_E_INVALID;
+    std::vector<erasor_eval_result> rows(k);
+    const int rc = erasor_hip_evaluate_many(h, nullptr, 0, 0, est_xyzi, n_est, nullptr, k, 0.0, voxelsize, rows.data());
+    if (rc) return rc;
+    size_t n = 0;
+    for (size_t j = 0; j < k; ++j) {
+        const EvmEst &e = h->ev.dbg_tab[j];
+        tab[4 * j] = e.off;
+        tab[4 * j + 1] = e.n;
+        tab[4 * j + 2] = e.base;
+        tab[4 * j + 3] = e.mask;
+        n += n_est[j];
+    }
+    if (!n) return ERASOR_E_INVALID;
+    return dbg_ev_dump(h, n, nb_out, off, cap_off, pts, idx);
+}
+#endif  // ERASOR_HIP_TEST_HOOKS
+
+}  // extern "C"
+
+// ---- a parameter sweep: every configuration over one sequence, each one's saved map scored by PR / RR (erasor_hip_sweep) ----
+// What the shim's OfflineMapUpdater + save_static_map + evaluate_saved_map do for one configuration (demo_main.cpp --config <yaml> n
+// <gt>): node j (0-based) is stepped iff (j + 1) % removal_interval == 0 (OMU.cpp:206-209), the map after the last node is voxelised by
+// voxelize_preserving_labels at save_leaf (main_in_your_env.cpp:123), and that map is evaluated against the GT as given.  The map, the
+// scans and the GT go to the device once.  Configurations run in waves of worker handles on the caller's device, one host thread each,
+// every worker with ONE query stream (two such handles keep the device's four compute pipes busy, DESIGN "Several handles on one GPU");
+// a worker takes its map from the shared copy, steps the shared scans in place, voxelises its final map into a buffer of the sweep's and is
+// destroyed before the next wave.  Then the saved maps are scored in groups by evm_run, in the caller handle's evaluator scratch.
+namespace {
+constexpr int SWEEP_LOOKAHEAD = 6;  // nodes announced ahead by a worker (the offline driver's default)
+struct SweepIn {
+    int device = 0;
+    const float4 *map = nullptr;
+    size_t n_map = 0;
+    const float4 *scans = nullptr;
+    const uint64_t *offsets = nullptr;
+    size_t n_nodes = 0;
+    const float *Tl = nullptr, *Tb = nullptr, *To = nullptr;
+    double save_leaf = 0;
+};
+struct SweepJob {
+    erasor_params p;
+    int status = ERASOR_OK;
+    uint32_t n_steps = 0;
+    uint64_t n_map_final = 0;
+    float4 *saved = nullptr;  // the saved map (hipMalloc of the sweep's), n_saved points
+    uint32_t n_saved = 0;
+    double run_ms = 0;
+};
+
+// a worker handle's device memory for a map of n_map points and scans of at most max_scan points: per slot of alloc_map's capacity the
+// map-sized scratch, the outskirts store and both F buffers, per scan point the query sides, plus the saved map; rounded up (a handle
+// with a 9.8 M-point map took 5.49 GB after four steps of 245 k-point scans, this gives 5.6 GB)
+uint64_t sweep_need(size_t n_map, uint64_t max_scan) {
+    const uint64_t cap = (uint64_t)n_map + std::max<uint64_t>(n_map / 4, 1u << 20);
+    return cap * 420 + max_scan * 8 * 96 + (uint64_t)n_map * 24 + (64ull << 20);
+}
+
+void sweep_one(const SweepIn &in, SweepJob &J) {
+    if (hipSetDevice(in.device) != hipSuccess) {
+        J.status = ERASOR_E_NO_DEVICE;
+        return;
+    }
+    const int ri = J.p.removal_interval;
+    if (ri < 1) {  // (the shim takes stack_count % removal_interval)
+        J.status = ERASOR_E_INVALID;
+        return;
+    }
+    std::vector<const void *> ptrs;
+    std::vector<size_t> np;
+    std::vector<float> Tb, To;
+    for (size_t j = 0; j < in.n_nodes; ++j) {
+        if ((j + 1) % (size_t)ri != 0) continue;  // OMU.cpp:206-209
+        ptrs.push_back(in.scans + in.offsets[j]);
+        np.push_back((size_t)(in.offsets[j + 1] - in.offsets[j]));
+        Tb.insert(Tb.end(), in.Tb + 16 * j, in.Tb + 16 * j + 16);
+        To.insert(To.end(), in.To + 16 * j, in.To + 16 * j + 16);
+    }
+    J.n_steps = (uint32_t)ptrs.size();
+    erasor_hip_handle *h = nullptr;
+    int rc = create_handle(&J.p, in.device, 1, &h);
+    if (rc) {
+        J.status = rc;
+        return;
+    }
+    rc = erasor_hip_set_map_device(h, in.map, in.n_map);
+    if (!rc && !ptrs.empty()) {
+        size_t announced = 0;
+        const auto t0 = std::chrono::steady_clock::now();
+        rc = erasor_hip_run_nodes(h, ptrs.data(), np.data(), ptrs.size(), 1, in.Tl, Tb.data(), To.data(), 0, ptrs.size(), SWEEP_LOOKAHEAD, &announced,
+                                  nullptr);
+        J.run_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    size_t n_final = 0;
+    if (!rc) rc = map_to_device(h, h->ev.map, &n_final);
+    if (!rc && n_final > MAX_POINTS) rc = ERASOR_E_CAPACITY;
+    uint32_t nq = (uint32_t)n_final;
+    const float4 *src = h->ev.map.p;
+    if (!rc && in.save_leaf > 0 && n_final) {
+        rc = voxelize_device(h, h->ev.map.p, (uint32_t)n_final, in.save_leaf, &nq);
+        src = Q(h).query.p;
+    }
+    if (!rc) {
+        J.n_map_final = n_final;
+        if (hipMalloc((void **)&J.saved, ((size_t)nq + 1) * sizeof(float4)) != hipSuccess) {
+            J.saved = nullptr;
+            rc = ERASOR_E_NO_DEVICE;
+        } else if ((nq && hipMemcpyAsync(J.saved, src, (size_t)nq * sizeof(float4), hipMemcpyDeviceToDevice, h->stream) != hipSuccess) ||
+                   hipStreamSynchronize(h->stream) != hipSuccess) {
+            rc = ERASOR_E_NO_DEVICE;
+        }
+        J.n_saved = nq;
+    }
+    J.status = rc;
+    erasor_hip_destroy(h);
+}
+
+// hipMemGetInfo, looked up at run time in the library that provides the HIP runtime: a runtime that does not export it gets no memory
+// check (every wave is then `concurrency` wide)
+using MemInfoFn = hipError_t (*)(size_t *, size_t *);
+MemInfoFn mem_info_fn() {
+    static const MemInfoFn fn = [] {
+        Dl_info info;
+        if (!dladdr((void *)&hipGetDeviceCount, &info) || !info.dli_fname) return (MemInfoFn) nullptr;
+        void *lib = dlopen(info.dli_fname, RTLD_LAZY | RTLD_NOLOAD);
+        return lib ? (MemInfoFn)dlsym(lib, "hipMemGetInfo") : (MemInfoFn) nullptr;
+    }();
+    return fn;
+}
+
+// a sweep-owned device buffer (freed on every return)
+struct SweepBuf {
+    void *p = nullptr;
+    ~SweepBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+}  // namespace
+
+int erasor_hip_sweep(erasor_hip_handle *h, const erasor_params *configs, size_t n_configs, const void *map_xyzi, size_t n_map, int map_is_device,
+                     const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_nodes, int scans_are_device,
+                     const float T_lidar2body[16], const float *T_body2origin, const float *T_origin2body, const void *gt_xyzi, size_t n_gt,
+                     int gt_is_device, double save_leaf, double voxelsize, int concurrency, int eval_batch, erasor_sweep_row *rows) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_sweep";
+    auto fail = [&](const char *why) { return invalid(h, who, why); };
+    if (n_configs > 256) return fail("more than 256 configurations");
+    if (n_configs && (!configs || !rows)) return fail("configs or rows is NULL");
+    if (concurrency < 1 || concurrency > 4) return fail("concurrency must be 1..4");
+    if (eval_batch < 0) return fail("eval_batch must be >= 0");
+    if (!(voxelsize > 0) || !std::isfinite(voxelsize)) return fail("voxelsize must be a finite number > 0");
+    if (!(save_leaf >= 0) || !std::isfinite(save_leaf)) return fail("save_leaf must be 0 or a finite number > 0");
+    int rc = check_cloud(h, who, "NULL map or more than 2^30 map points", map_xyzi, n_map);
+    if (rc || (rc = check_cloud(h, who, "NULL ground truth or more than 2^30 points", gt_xyzi, n_gt))) return rc;
+    if (!offsets) return fail("offsets is NULL (n_nodes + 1 entries)");
+    if ((rc = check_scan_offsets(h, who, scans_xyzi, n_scan_points, offsets, n_nodes))) return rc;
+    if (!T_lidar2body || (n_nodes && (!T_body2origin || !T_origin2body))) return fail("a pose array is NULL");
+    if (!all_finite(T_lidar2body, 16)) return fail("non-finite entry in T_lidar2body");
+    if (!all_finite(T_body2origin, n_nodes * 16) || !all_finite(T_origin2body, n_nodes * 16))
+        return fail("non-finite entry in T_body2origin or T_origin2body");
+    HIPC(h, hipSetDevice(h->device));
+    // the shared inputs, on the device once
+    SweepBuf b_map, b_scans, b_gt;
+    auto upload = [&](const void *src, size_t n, int is_device, SweepBuf &b, const float4 **out) -> int {
+        *out = (const float4 *)src;
+        if (is_device || !n) return ERASOR_OK;
+        HIPC(h, hipMalloc(&b.p, n * sizeof(float4)));
+        HIPC(h, hipMemcpyAsync(b.p, src, n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
+        *out = (const float4 *)b.p;
+        return ERASOR_OK;
+    };
+    SweepIn in;
+    in.device = h->device;
+    const float4 *d_gt = nullptr;
+    if ((rc = upload(map_xyzi, n_map, map_is_device, b_map, &in.map)) || (rc = upload(scans_xyzi, n_scan_points, scans_are_device, b_scans, &in.scans)) ||
+        (rc = upload(gt_xyzi, n_gt, gt_is_device, b_gt, &d_gt)))
+        return rc;
+    // non-finite map / GT points: the GT side of evm_run with no estimate counts them
+    for (int c = 0; c < 2; ++c) {
+        const float4 *cl = c ? d_gt : in.map;
+        const size_t n = c ? n_gt : n_map;
+        if (!n) continue;
+        if ((rc = evm_run(h, who, cl, (uint32_t)n, nullptr, 0, voxelsize, nullptr))) {
+            if (rc == ERASOR_E_INVALID) h->err = std::string(who) + ": non-finite coordinate (NaN / Inf) in the " + (c ? "ground truth" : "map");
+            return rc;
+        }
+    }
+    in.n_map = n_map;
+    in.offsets = offsets;
+    in.n_nodes = n_nodes;
+    in.Tl = T_lidar2body;
+    in.Tb = T_body2origin;
+    in.To = T_origin2body;
+    in.save_leaf = save_leaf;
+    uint64_t max_scan = 0;
+    for (size_t f = 0; f < n_nodes; ++f) max_scan = std::max<uint64_t>(max_scan, offsets[f + 1] - offsets[f]);
+    std::vector<SweepJob> jobs(n_configs);
+    for (size_t i = 0; i < n_configs; ++i) jobs[i].p = configs[i];
+    struct FreeSaved {
+        std::vector<SweepJob> &jobs;
+        ~FreeSaved() {
+            for (auto &J : jobs)
+                if (J.saved) (void)hipFree(J.saved);
+        }
+    } free_saved{jobs};
+    // waves of `concurrency` workers, as many as the free device memory takes (at least one, else that configuration fails on its own)
+    const MemInfoFn mem_info = mem_info_fn();
+    const uint64_t need = sweep_need(n_map, max_scan);
+    for (size_t next = 0; next < n_configs;) {
+        size_t free_b = ~(size_t)0, total_b = 0;
+        if (mem_info) HIPC(h, mem_info(&free_b, &total_b));
+        std::vector<size_t> wave;
+        uint64_t budget = free_b;
+        while (next < n_configs && (int)wave.size() < concurrency && need <= budget) {
+            budget -= need;
+            wave.push_back(next++);
+        }
+        if (wave.empty()) {
+            jobs[next++].status = ERASOR_E_NO_DEVICE;
+            continue;
+        }
+        std::vector<std::thread> th;
+        for (size_t i : wave) th.emplace_back(sweep_one, std::cref(in), std::ref(jobs[i]));
+        for (auto &t : th) t.join();
+    }
+    HIPC(h, hipSetDevice(h->device));
+    // the saved maps against the GT, in groups of eval_batch (0: all), each group one evm_run
+    std::vector<size_t> ok;
+    for (size_t i = 0; i < n_configs; ++i)
+        if (jobs[i].status == ERASOR_OK) ok.push_back(i);
+    std::vector<erasor_eval_result> ev(n_configs);
+    memset(ev.data(), 0, ev.size() * sizeof(erasor_eval_result));
+    auto &E = h->ev;
+    for (size_t b = 0; b < ok.size();) {
+        std::vector<size_t> grp;
+        uint64_t total = 0;
+        while (b < ok.size() && (eval_batch == 0 || (int)grp.size() < eval_batch) &&
+               (grp.empty() || total + jobs[ok[b]].n_saved <= 0x7FFFFFFFull)) {
+            total += jobs[ok[b]].n_saved;
+            grp.push_back(ok[b++]);
+        }
+        int grc = ensure(h, E.em_cat, total + 1) ? ERASOR_E_NO_DEVICE : ERASOR_OK;
+        std::vector<uint32_t> ne;
+        uint64_t off = 0;
+        for (size_t i : grp) {
+            if (!grc && jobs[i].n_saved &&
+                hipMemcpyAsync(E.em_cat.p + off, jobs[i].saved, (size_t)jobs[i].n_saved * sizeof(float4), hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
+                grc = ERASOR_E_NO_DEVICE;
+            ne.push_back(jobs[i].n_saved);
+            off += jobs[i].n_saved;
+        }
+        if (!grc && hipStreamSynchronize(h->stream) != hipSuccess) grc = ERASOR_E_NO_DEVICE;
+        std::vector<erasor_eval_result> r(grp.size());
+        if (!grc) grc = evm_run(h, who, d_gt, (uint32_t)n_gt, ne.data(), grp.size(), voxelsize, r.data());
+        for (size_t q = 0; q < grp.size(); ++q) {
+            if (grc) jobs[grp[q]].status = grc;
+            else ev[grp[q]] = r[q];
+        }
+    }
+    for (size_t i = 0; i < n_configs; ++i) {
+        erasor_sweep_row &R = rows[i];
+        memset(&R, 0, sizeof(R));
+        R.params = configs[i];
+        R.status = jobs[i].status;
+        R.n_steps = jobs[i].n_steps;
+        if (jobs[i].status == ERASOR_OK) {
+            R.n_map_final = jobs[i].n_map_final;
+            R.n_saved = jobs[i].n_saved;
+            R.eval = ev[i];
+        }
+        R.run_ms = jobs[i].run_ms;
+    }
+    return ERASOR_OK;
+}

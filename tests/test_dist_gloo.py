@@ -5,6 +5,8 @@ import subprocess
 import sys
 import textwrap
 
+import simt
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 WORKER = textwrap.dedent('''
@@ -109,12 +111,8 @@ def test_two_ranks_run_real_steps_and_exchange_the_union_of_their_removals(tmp_p
     """SURVEY 8(e)(ii) on two gloo ranks: rank 0's map is broadcast, each rank runs REAL steps (the device code on the CPU
     stand-in) on its shard of one sequence's scans -- every scan against the initial map (Jacobi-style, see erasor_amd/dist.py) --,
     ONE all_gather exchanges the removed initial-map indices, and the union equals a single-process oracle computation."""
-    lib = str(tmp_path / "liberasor_hip_simt.so")
-    subprocess.check_call(["g++", "-x", "c++", "-O1", "-std=c++20", "-pthread", "-ffp-contract=off", "-fPIC", "-shared",
-                           "-I" + os.path.join(ROOT, "tests", "cpp", "simt_emu"), "-o", lib, os.path.join(ROOT, "erasor_amd", "csrc", "erasor_hip.hip")])
-    sys.path.insert(0, ROOT)
-    from oracle import orc
-    orc.build()
+    lib = simt.build_simt_lib(tmp_path, hooks=False)
+    simt.build_oracle()
     script = tmp_path / "union_worker.py"
     script.write_text(UNION_WORKER)
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", ERASOR_TEST_SIMT_LIB=lib)

@@ -1,37 +1,21 @@
-"""The device evaluator of PR / RR (evaluate.hip.h and its host code in erasor_hip.hip), compiled UNMODIFIED against the CPU stand-in of
+"""The device evaluator of PR / RR (evaluate.hip.h and its host code in analysis_host.hip.h), compiled UNMODIFIED against the CPU stand-in of
 the HIP runtime (tests/cpp/simt_emu, as in tests/test_full_step_on_cpu.py) and checked by tests/test_gpu_evaluate.py itself: the
 reference's golden vectors (host and device inputs), the per-point decisions against cKDTree, the errors and the struct layout, and
 the handle's map after two steps.  No GPU needed."""
-import os
-import subprocess
-import sys
-
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+import simt
+
 pytestmark = pytest.mark.timeout(3600)
 
 
 @pytest.fixture(scope="module")
 def simt_lib(tmp_path_factory):
-    lib = str(tmp_path_factory.mktemp("simt_eval") / "liberasor_hip_simt.so")
-    subprocess.check_call(["g++", "-x", "c++", "-O1", "-std=c++20", "-pthread", "-ffp-contract=off", "-fPIC", "-shared", "-DERASOR_HIP_TEST_HOOKS",
-                           "-I" + os.path.join(HERE, "cpp", "simt_emu"), "-o", lib, os.path.join(ROOT, "erasor_amd", "csrc", "erasor_hip.hip")])
-    sys.path.insert(0, ROOT)
-    from oracle import orc
-    orc.build()
-    return lib
+    simt.build_oracle()
+    return simt.build_simt_lib(tmp_path_factory.mktemp("simt_eval"))
 
 
 def test_the_evaluator_passes_its_gpu_tests_on_the_cpu_stand_in(simt_lib):
     expr = ("golden or per_point or threshold or device_inputs or tied or out_of_range or errors_and_struct_layout or "
             "(end_to_end_protocol and False-2)")
-    env = dict(os.environ, ERASOR_TEST_SIMT_LIB=simt_lib)
-    out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(HERE, "test_gpu_evaluate.py"), "-m", "gpu", "-q", "-x", "-k", expr,
-                          "-p", "no:cacheprovider"], capture_output=True, text=True, timeout=3000, cwd=ROOT, env=env)
-    tail = out.stdout[-1500:]
-    sys.stdout.write(tail)
-    assert out.returncode == 0 and " passed" in tail and "failed" not in tail, out.stdout[-4000:] + out.stderr[-2000:]
-    n_passed = int(tail.split(" passed")[0].split()[-1])
-    assert n_passed >= 16, tail  # 2 golden + 8 per-point + threshold + device + tied + labels + errors + the handle's map
+    simt.run_gpu_tests_on_stand_in(simt_lib, "test_gpu_evaluate.py", expr, 16)  # 2 golden + 8 per-point + threshold + device + tied + labels + errors + the handle's map

@@ -20,6 +20,8 @@ import sys
 
 import pytest
 
+import simt
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 pytestmark = pytest.mark.timeout(7200)  # (pytest.ini's 300 s is for the device; the extended modes here take minutes to an hour)
@@ -27,13 +29,8 @@ pytestmark = pytest.mark.timeout(7200)  # (pytest.ini's 300 s is for the device;
 
 @pytest.fixture(scope="module")
 def simt_lib(tmp_path_factory):
-    lib = str(tmp_path_factory.mktemp("simt") / "liberasor_hip_simt.so")
-    subprocess.check_call(["g++", "-x", "c++", "-O1", "-std=c++20", "-pthread", "-ffp-contract=off", "-fPIC", "-shared", "-DERASOR_HIP_TEST_HOOKS",
-                           "-I" + os.path.join(HERE, "cpp", "simt_emu"), "-o", lib, os.path.join(ROOT, "erasor_amd", "csrc", "erasor_hip.hip")])
-    sys.path.insert(0, ROOT)
-    from oracle import orc
-    orc.build()
-    return lib
+    simt.build_oracle()
+    return simt.build_simt_lib(tmp_path_factory.mktemp("simt"))
 
 
 def test_two_steps_of_the_real_host_code_and_kernels_match_the_oracle(simt_lib):
@@ -51,15 +48,8 @@ def test_part_of_the_gpu_parity_suite_passes_on_the_cpu_stand_in(simt_lib):
     expr = " or ".join(keys)
     if os.environ.get("ERASOR_SIMT_ALL"):  # everything but the full-size cases: 49 tests, ~40 minutes on 8 cores
         expr = "not (full_size or config4 or whole_map or long_segments or map_grows)"
-    env = dict(os.environ, ERASOR_TEST_SIMT_LIB=simt_lib)
-    out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(HERE, "test_gpu_parity.py"), os.path.join(HERE, "test_gpu_hooks.py"), "-m", "gpu",
-                          "-q", "-x", "-k", expr,
-                          "-p", "no:cacheprovider"], capture_output=True, text=True, timeout=7200 if os.environ.get("ERASOR_SIMT_ALL") else 2400, cwd=ROOT, env=env)
-    tail = out.stdout[-1500:]
-    sys.stdout.write(tail)
-    assert out.returncode == 0 and " passed" in tail and "failed" not in tail, out.stdout[-4000:] + out.stderr[-2000:]
-    n_passed = int(tail.split(" passed")[0].split()[-1])
-    assert n_passed >= 9, tail  # 1 + 1 + 5 + 1 + 1
+    # 1 + 1 + 5 + 1 + 1
+    simt.run_gpu_tests_on_stand_in(simt_lib, ["test_gpu_parity.py", "test_gpu_hooks.py"], expr, 9, timeout=7200 if os.environ.get("ERASOR_SIMT_ALL") else 2400)
 
 
 def test_the_references_own_vectors_are_reproduced_on_the_cpu_stand_in(simt_lib):
@@ -67,12 +57,7 @@ def test_the_references_own_vectors_are_reproduced_on_the_cpu_stand_in(simt_lib)
     tests/test_golden.py replays them through the C ABI with nothing but the committed data (-m gpu).  The same test, against
     the device code on the CPU stand-in: one vector by default, all seven golden files with ERASOR_SIMT_MORE=1."""
     expr = "hip_reproduces" if os.environ.get("ERASOR_SIMT_MORE") or os.environ.get("ERASOR_SIMT_ALL") else "reference_vectors and ref_seq05_v3"
-    env = dict(os.environ, ERASOR_TEST_SIMT_LIB=simt_lib)
-    out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(HERE, "test_golden.py"), "-m", "gpu", "-q", "-x", "-k", expr, "-p", "no:cacheprovider"],
-                         capture_output=True, text=True, timeout=2400, cwd=ROOT, env=env)
-    tail = out.stdout[-1500:]
-    sys.stdout.write(tail)
-    assert out.returncode == 0 and " passed" in tail and "failed" not in tail, out.stdout[-4000:] + out.stderr[-2000:]
+    simt.run_gpu_tests_on_stand_in(simt_lib, "test_golden.py", expr, 1, timeout=2400)
 
 
 @pytest.mark.skipif(not (os.environ.get("ERASOR_SIMT_MORE") or os.environ.get("ERASOR_SIMT_ALL")), reason="~8 minutes: ERASOR_SIMT_MORE=1")
