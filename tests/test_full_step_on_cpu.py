@@ -8,7 +8,8 @@ driven through the C ABI and compared with the oracle.
   * a part of the GPU parity suite itself (tests/test_gpu_parity.py, `-m gpu`) re-run against that library: the one-bin
     known answers, the edge cases (empty / one-point / ragged inputs), the stable bucketing, the exact sort's heapsort
     fallback, the API's error behaviour.  ERASOR_SIMT_MORE=1 adds the standalone voxelisation, the exact-sort sweep, the
-    VoxelGrid index-overflow pass-through and the NaN refusal (~5 more minutes); ERASOR_SIMT_ALL=1 runs the whole file except
+    VoxelGrid index-overflow pass-through and the NaN refusal (~5 more minutes), and the size classes of a reverted bin
+    (tests/test_gpu_bin_sizes.py: its 83 cases of at most 4097 map points, the four-bin launch left out); ERASOR_SIMT_ALL=1 runs the whole file except
     the full-size cases (49 tests: every synthetic sequence, v2 / v3, submap mode, look-ahead, mapgen, PR / RR; ~40 minutes).
 
 This is a checker, not a product: the library is built into the test's temporary directory, loaded by helper processes only
@@ -43,13 +44,17 @@ def test_part_of_the_gpu_parity_suite_passes_on_the_cpu_stand_in(simt_lib):
     # (round 5: `api_error_two_handles...` -- five look-ahead steps of two handles, 4 minutes here since steps overlap -- runs with
     # ERASOR_SIMT_MORE / _ALL and on the GPU)
     keys = ["one_bin_known", "edge_cases", "stable_radix", "heapsort_fallback", "api_error_behaviour"]
+    files, n_min = ["test_gpu_parity.py", "test_gpu_hooks.py"], 9  # 1 + 1 + 5 + 1 + 1
     if os.environ.get("ERASOR_SIMT_MORE"):
         keys += ["voxelize_preserving_labels_standalone", "exact_std_sort", "voxelgrid_index_overflow", "non_finite", "device_libm", "api_error_two_handles"]
+        # the per-bin launch at every size class of a reverted bin: the cases whose ids say `standin` (M <= 4097, one bin)
+        keys += ["standin"]
+        files, n_min = files + ["test_gpu_bin_sizes.py"], n_min + 83
     expr = " or ".join(keys)
     if os.environ.get("ERASOR_SIMT_ALL"):  # everything but the full-size cases: 49 tests, ~40 minutes on 8 cores
         expr = "not (full_size or config4 or whole_map or long_segments or map_grows)"
-    # 1 + 1 + 5 + 1 + 1
-    simt.run_gpu_tests_on_stand_in(simt_lib, ["test_gpu_parity.py", "test_gpu_hooks.py"], expr, 9, timeout=7200 if os.environ.get("ERASOR_SIMT_ALL") else 2400)
+        files, n_min = ["test_gpu_parity.py", "test_gpu_hooks.py"], 9
+    simt.run_gpu_tests_on_stand_in(simt_lib, files, expr, n_min, timeout=7200 if os.environ.get("ERASOR_SIMT_ALL") else 2400)
 
 
 def test_the_references_own_vectors_are_reproduced_on_the_cpu_stand_in(simt_lib):
