@@ -163,6 +163,7 @@ struct erasor_hip_handle {
         bool scan = false;               // the chunk scan was launched ahead as well (buffers below)
         const void *pvl = nullptr, *phl = nullptr;
         uint32_t scan_cap = 0;
+        int scan_levels = 0;             // 1: k_chunk_scan_one, 2: k_chunk_scan_local + k_chunk_scan_top
         unsigned long long seq = 0;      // h->step_seq when it was launched
         unsigned long long epoch = 0;    // h->store_epoch then
         int curF = 0;                    // the F buffer it read
@@ -179,11 +180,18 @@ struct erasor_hip_handle {
         double x = 0, y = 0;
         float To[16] = {0};
         uint32_t cap_chunks = 0, cap_voi = 0, nbk = 0;
+        int scan_levels = 0;      // as spec.scan_levels
         bool stats_done = false;  // ... and the stable scatter + bin statistics + first Scan Ratio Test pass (the query chain was through)
         const void *vmask = nullptr, *hmask = nullptr, *lmask = nullptr, *cinfo = nullptr, *pvl = nullptr, *phl = nullptr, *voi_ego = nullptr,
                    *mb_hist = nullptr;
     } ov;
     unsigned long long n_ov_launched = 0, n_ov_used = 0;
+    // the chunk scan: one workgroup (k_chunk_scan_one) scans up to SCAN_ONE_MAX chunk counts, stores with more chunks take the two-level scan.
+    // Every place that decides between the two, or sizes what the one-launch scan may read, asks scan_one_max (the hooks build can lower it:
+    // erasor_hip_debug_set_scan_one_max; never above SCAN_ONE_MAX, the kernel's own clamp).
+    static constexpr uint32_t SCAN_ONE_MAX = 16384;
+    uint32_t scan_one_max = SCAN_ONE_MAX;
+    int last_scan_path = 0;  // the last enqueued step's chunk scan: levels (1 / 2) + 0 run by the step itself, + 2 launched ahead, + 4 overlapped
     bool ov_mode = false;  // the last step used the reserved layout / the early stream: query chains keep to TWO streams then
     // round 5: a step is ~45 launches, ~30 of them the query chain of a scan announced ahead -- with the steps overlapped the HOST had
     // become the bound (180 us of launch calls per step against a 120 us chain on the device).  The chain's launches go to a worker
@@ -1932,7 +1940,7 @@ static void launch_split_ahead(erasor_hip_handle *h, double nx, double ny, uint3
     // round 4: ... and the next step's chunk scan behind it: the stream goes on while the host is still collecting this step's results
     // and comes back with the next one (its turnaround, ~10 us, used to be idle time between the split and the scan)
     const bool mb_count = h->B + 1 <= QB_NB_MAX;
-    const uint32_t scan_cap = (uint32_t)std::min<size_t>(std::min(std::min(h->pvl.cap, h->phl.cap), h->cinfo.cap) - 8, 16384);  // (k_chunk_scan_one reads cinfo up to here)
+    const uint32_t scan_cap = (uint32_t)std::min<size_t>(std::min(std::min(h->pvl.cap, h->phl.cap), h->cinfo.cap) - 8, h->scan_one_max);  // (k_chunk_scan_one reads cinfo up to here)
     if (nchunks_hint + 64u <= scan_cap && h->topv.cap >= 24 && h->toph.cap >= 24 && h->prof != 1) {
         hipStream_t keep = h->cur;
         h->cur = h->stream;
@@ -1943,11 +1951,12 @@ static void launch_split_ahead(erasor_hip_handle *h, double nx, double ny, uint3
                h->use_ometa ? h->ometa.p : (OMeta *)nullptr, h->capO / CHUNK, scan_cap, (const DevState *)h->d_st.p, 0xFFFFFFFFu);
         h->cur = keep;
         h->spec.scan = true;
+        h->spec.scan_levels = 1;
         h->spec.scan_cap = scan_cap;
         h->spec.pvl = h->pvl.p;
         h->spec.phl = h->phl.p;
     } else if (h->prof != 1) {
-        // maps beyond k_chunk_scan_one's 16384 chunks (config 4: 38 k): the two-level scan ahead, its grid an upper bound
+        // maps beyond k_chunk_scan_one's scan_one_max chunks (16384; config 4: 38 k): the two-level scan ahead, its grid an upper bound
         const size_t room = std::min(h->pvl.cap, h->phl.cap);
         const uint32_t grid = (uint32_t)cdiv(nchunks_hint + 64u, 1024);
         const size_t top_cap = std::min(std::min(h->topv.cap, h->toph.cap), h->topr.cap);
@@ -1962,6 +1971,7 @@ static void launch_split_ahead(erasor_hip_handle *h, double nx, double ny, uint3
                    (const uint32_t *)h->topr.p, h->use_ometa ? h->ometa.p : (OMeta *)nullptr, h->capO / CHUNK, cap2, (const DevState *)h->d_st.p, 0xFFFFFFFFu);
             h->cur = keep;
             h->spec.scan = true;
+            h->spec.scan_levels = 2;
             h->spec.scan_cap = cap2;
             h->spec.pvl = h->pvl.p;
             h->spec.phl = h->phl.p;
@@ -2223,6 +2233,7 @@ static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_sca
                 h->spec.valid = false;
                 nbk = h->ov.nbk;
                 bits = key_bits(nbk);
+                h->last_scan_path = 4 + h->ov.scan_levels;
             }
         }
         if (!use_ov) {   // VoI split (OMU.cpp:254 fetch_VoI membership)
@@ -2242,11 +2253,14 @@ static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_sca
             const uint32_t ntop = std::max(1u, cdiv(nchunks, 1024));
             if (scan_done) {
                 // (launched ahead behind the split, see launch_split_ahead)
-            } else if (nchunks <= 16384) {
+                h->last_scan_path = 2 + h->spec.scan_levels;
+            } else if (nchunks <= h->scan_one_max) {
+                h->last_scan_path = 1;
                 LAUNCH(h, "chunk_scan", k_chunk_scan_one, 1, 1024, (const uint32_t *)h->cinfo.p, nchunks, h->pvl.p, h->phl.p, h->topv.p, h->toph.p, ntop,
                        nFchunks, ds, dc, h->st, h->lab_slots.p, mb_count ? h->mb_tot.p : (uint32_t *)nullptr, mb_count ? B + 2 : 0u,
                        h->use_ometa ? h->ometa.p : (OMeta *)nullptr, 0u, 0u, (const DevState *)nullptr, 0u);
             } else {
+                h->last_scan_path = 2;
                 LAUNCH(h, "chunk_scan", k_chunk_scan_local, ntop, 256, (const uint32_t *)h->cinfo.p, nchunks, h->pvl.p, h->phl.p, h->topv.p, h->toph.p,
                        h->topr.p, (const DevState *)nullptr, 0u, 0u, 0u);
                 LAUNCH(h, "chunk_scan", k_chunk_scan_top, 1, 1024, h->topv.p, h->toph.p, ntop, (const uint32_t *)h->pvl.p, (const uint32_t *)h->phl.p,
@@ -2430,12 +2444,13 @@ static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_sca
             // (its extents come from *ds: the region this step writes and the outskirts as its gather has left them)
             launch_voi_split(h, (const float4 *)Fnew, 0u, 0u, 0u, 0u, 0u, nchunks + 64 + cdiv((uint64_t)ns + 4096, CHUNK), nx, ny, P.voi_r2,
                              (const DevState *)nullptr, (uint32_t)cap_chunks, (const StepEnd *)nullptr, &ovs);
-            const uint32_t scan_cap1 = (uint32_t)std::min<size_t>(std::min(h->pvl.cap, h->phl.cap) - 8, 16384);
+            const uint32_t scan_cap1 = (uint32_t)std::min<size_t>(std::min(h->pvl.cap, h->phl.cap) - 8, h->scan_one_max);
             // (the next region's extent is not known here: it keeps this step's reserved places -- up to 4 x the VoI + 2 x the scan, see
-            // alloc_step --, and the outskirts grow by what leaves; one workgroup scans up to 16384 chunk counts, beyond that two levels
+            // alloc_step --, and the outskirts grow by what leaves; one workgroup scans up to scan_one_max chunk counts, beyond that two levels
             // over everything the buffers hold.  What the scan ahead can take is recorded: a step with more chunks runs its own passes)
             const uint32_t hint = nchunks + 64 + cdiv(4 * (uint64_t)std::max(h->last_n_voi, 1u << 16) + 2 * (uint64_t)ns + 4096, CHUNK);
             uint32_t scan_cap_used = 0;
+            h->ov.scan_levels = hint <= scan_cap1 ? 1 : 2;
             if (hint <= scan_cap1) {
                 scan_cap_used = std::min<uint32_t>(scan_cap1, (uint32_t)cap_chunks);
                 LAUNCH(h, "chunk_scan", k_chunk_scan_one, 1, 1024, (const uint32_t *)h->cinfo.p, 0u, h->pvl.p, h->phl.p, h->topv.p, h->toph.p, 16u, 0u,
@@ -4051,6 +4066,50 @@ int erasor_hip_debug_rebuild_outskirts(erasor_hip_handle *h) {
     if (!h->have_map) return ERASOR_E_STATE;
     HIPC(h, hipSetDevice(h->device));
     return rebuild_outskirts(h, h->nF + CHUNK);
+}
+
+// test hook: the map store between steps, read-only.  out[0..11] = nF, nFv, o_begin, capO, o_valid, then the last step's n_o_read, n_leaving,
+// o_new_begin and chunk-scan path (handle::last_scan_path), the records in use (0: ERASOR_HIP_NO_OMETA), scan_one_max, CHUNK; rec (may be null):
+// the OMeta records of the chunks [o_begin / CHUNK, capO / CHUNK), at most rec_cap of them, 8 words each; *n_rec: how many there are
+int erasor_hip_debug_store_state(erasor_hip_handle *h, uint64_t *out, uint32_t *rec, size_t rec_cap, size_t *n_rec) {
+    NOFLY(h);
+    if (!h || !out) return ERASOR_E_INVALID;
+    if (!h->have_map) return ERASOR_E_STATE;
+    HIPC(h, hipSetDevice(h->device));
+    if (h->bstream) HIPC(h, hipStreamSynchronize(h->bstream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    out[0] = h->nF;
+    out[1] = h->nFv;
+    out[2] = h->o_begin;
+    out[3] = h->capO;
+    out[4] = h->o_valid;
+    out[5] = h->have_step ? h->st.n_o_read : 0;
+    out[6] = h->have_step ? h->st.n_leaving : 0;
+    out[7] = h->have_step ? h->st.o_new_begin : h->o_begin;
+    out[8] = h->have_step ? (uint64_t)h->last_scan_path : 0;
+    out[9] = h->use_ometa ? 1 : 0;
+    out[10] = h->scan_one_max;
+    out[11] = CHUNK;
+    const size_t c0 = h->o_begin / CHUNK, n = h->capO / CHUNK - c0;
+    if (n_rec) *n_rec = h->use_ometa ? n : 0;
+    if (rec && h->use_ometa && n) {
+        static_assert(sizeof(OMeta) == 32, "a record is 8 words");
+        HIPC(h, hipMemcpy(rec, h->ometa.p + c0, std::min(n, rec_cap) * sizeof(OMeta), hipMemcpyDeviceToHost));
+    }
+    return ERASOR_OK;
+}
+
+// test hook: the largest store (in chunks) that takes the one-launch chunk scan; 0 restores the default.  Passes launched ahead under the
+// old limit are not taken (store_epoch)
+int erasor_hip_debug_set_scan_one_max(erasor_hip_handle *h, uint32_t n) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    HIPC(h, hipSetDevice(h->device));
+    if (h->bstream) HIPC(h, hipStreamSynchronize(h->bstream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    ++h->store_epoch;
+    h->scan_one_max = n ? std::min(n, erasor_hip_handle::SCAN_ONE_MAX) : erasor_hip_handle::SCAN_ONE_MAX;
+    return ERASOR_OK;
 }
 
 // test hook: the stable LSD radix sort used for R-POD bucketing

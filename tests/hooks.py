@@ -72,6 +72,29 @@ def debug_rebuild_outskirts(g):
     g._check(erasor_amd.lib().erasor_hip_debug_rebuild_outskirts(g._h))
 
 
+def debug_store_state(g, records=True):
+    """the map store between steps (read-only): nF, nFv, o_begin, capO, o_valid; the last step's n_o_read, n_leaving, o_new_begin and
+    scan_path (1 / 2: one-launch / two-level chunk scan run by the step, 3 / 4: launched ahead, 5 / 6: overlapped); scan_one_max, chunk;
+    "rec": the OMeta records of the chunks [o_begin / chunk, capO / chunk) as (xmin, xmax, ymin, ymax), valid, known (None without records)"""
+    out = np.zeros(12, np.uint64)
+    n = C.c_size_t(0)
+    g._check(erasor_amd.lib().erasor_hip_debug_store_state(g._h, _p(out), C.c_void_p(None), C.c_size_t(0), C.byref(n)))
+    names = ("nF", "nFv", "o_begin", "capO", "o_valid", "n_o_read", "n_leaving", "o_new_begin", "scan_path", "use_ometa", "scan_one_max", "chunk")
+    st = {k: int(v) for k, v in zip(names, out)}
+    st["rec"] = None
+    if records and st["use_ometa"]:
+        rec = np.zeros((max(n.value, 1), 8), np.uint32)
+        g._check(erasor_amd.lib().erasor_hip_debug_store_state(g._h, _p(out), _p(rec), C.c_size_t(len(rec)), C.byref(n)))
+        rec = rec[: n.value]
+        st["rec"] = {"box": rec[:, :4].copy().view(np.float32), "valid": rec[:, 4].copy(), "known": rec[:, 5].copy()}
+    return st
+
+
+def debug_set_scan_one_max(g, n):
+    """stores of more than n chunks take the two-level chunk scan (0: the default, 16384)"""
+    g._check(erasor_amd.lib().erasor_hip_debug_set_scan_one_max(g._h, C.c_uint32(n)))
+
+
 def debug_nn_tree(g, cloud):
     """the bounding-volume tree nn_pad / nn_tree build over `cloud` (N x 4 rows): P, the points in key order, their original indices,
     the sorted Morton keys, lo / hi of the 2P nodes (node 0 is unused)"""
