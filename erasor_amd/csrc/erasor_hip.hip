@@ -61,6 +61,49 @@ struct DBuf {
 
 }  // namespace
 
+// What consecutive steps must not share (round 5: an overlapped step's early passes run while the step in flight still reads its own):
+// VoI-order arrays, the bucketed VoI, bin offsets and statistics, state, counters, label tallies.  The handle owns two: `cset` is the
+// CURRENT step's, `oset` the other one, where the passes launched ahead write; they change places when a step is enqueued (swap_sides)
+struct StepSet {
+    DBuf<float4> voi_ego, spts;
+    DBuf<uint32_t> voi_key, voi_src, moff, ssrc, rk_a, mcnt;
+    DBuf<float> mmin, mmax;
+    DBuf<uint8_t> st1b;  // (first-pass status | 0x80 written by k_bin_stats_srt)
+    DBuf<DevState> d_st;
+    DBuf<Counters> d_ctr;
+    DBuf<unsigned long long> lab_slots;  // [16][8] label tallies of the assemble kernels (one cache line per slot)
+};
+
+// What launch_chunk_scan did: levels (0: nothing, 1: k_chunk_scan_one, 2: k_chunk_scan_local + k_chunk_scan_top), how many chunks it
+// can take when it was launched ahead, the buffers it wrote
+struct ScanDone {
+    int levels = 0;
+    uint32_t cap = 0;
+    const void *pvl = nullptr, *phl = nullptr;
+};
+// Passes of the NEXT step that were launched ahead of it, and what they assumed: the step that follows takes them only if it is exactly
+// that step (ahead_mismatch).  One type for the split behind a step (erasor_hip_handle::spec) and for an overlapped step's passes (::ov);
+// spec leaves what it does not launch at its default and the step tests only the AH_* conditions that apply.
+enum : unsigned {
+    AH_SEQ = 1u << 0, AH_EPOCH = 1u << 1, AH_CURF = 1u << 2, AH_QSIDE = 1u << 3, AH_POSE = 1u << 4, AH_TO = 1u << 5, AH_CHUNKS = 1u << 6,
+    AH_VOI = 1u << 7, AH_VMASK = 1u << 8, AH_HMASK = 1u << 9, AH_LMASK = 1u << 10, AH_CINFO = 1u << 11, AH_PVL = 1u << 12, AH_PHL = 1u << 13,
+    AH_VOI_EGO = 1u << 14, AH_MB_HIST = 1u << 15, AH_SCAN_CAP = 1u << 16,
+    AH_SPLIT = AH_SEQ | AH_EPOCH | AH_CURF | AH_POSE | AH_CHUNKS | AH_VMASK | AH_HMASK | AH_CINFO,  // spec: the split ...
+    AH_SCAN = AH_SCAN_CAP | AH_PVL | AH_PHL,                                                         // ... and the chunk scan behind it
+    AH_OVERLAP = AH_SPLIT | AH_QSIDE | AH_TO | AH_VOI | AH_LMASK | AH_PVL | AH_PHL | AH_VOI_EGO | AH_MB_HIST,
+};
+struct Ahead {
+    bool valid = false;
+    unsigned long long seq = 0, epoch = 0;  // h->step_seq of the step it is for, h->store_epoch when it was launched
+    int curF = 0, qside = -1;               // the F buffer it read, the query side of the node
+    double x = 0, y = 0;                    // the node's pose ...
+    float To[16] = {0};                     // ... and T_origin2body (the gather ahead)
+    uint32_t cap_chunks = 0, cap_voi = 0, nbk = 0;
+    ScanDone scan;                          // the chunk scan (spec: levels == 0 when only the split went ahead)
+    bool stats_done = false;  // ... and the stable scatter + bin statistics + first Scan Ratio Test pass (the query chain was through)
+    const void *vmask = nullptr, *hmask = nullptr, *lmask = nullptr, *cinfo = nullptr, *voi_ego = nullptr, *mb_hist = nullptr;
+};
+
 // The query side of a step (see erasor_hip_handle::q)
 // layout of a HOST scan's records: float x, y, z at byte 0, float intensity at byte `ioff`, one record every `stride` bytes
 // (the library's own XYZI rows: 16 / 12; pcl::PointXYZI, what OMU.cpp:237 pcl::fromROSMsg leaves: 32 / 16)
@@ -156,35 +199,12 @@ struct erasor_hip_handle {
     int last_ann_side = -1;  // the side of the most recent announcement (erasor_hip_announce_origin2body attaches to it)
     int step_side = -1;      // the side of the step in flight / of the last step collected: its arrays are read by that step's launches and by the getters
     uint64_t next_ticket = 1;
-    // the NEXT step's VoI split, launched ahead (behind this step's k_step_end) when the next scan was announced with its pose
-    struct {
-        bool valid = false;
-        double x = 0, y = 0;
-        bool scan = false;               // the chunk scan was launched ahead as well (buffers below)
-        const void *pvl = nullptr, *phl = nullptr;
-        uint32_t scan_cap = 0;
-        int scan_levels = 0;             // 1: k_chunk_scan_one, 2: k_chunk_scan_local + k_chunk_scan_top
-        unsigned long long seq = 0;      // h->step_seq when it was launched
-        unsigned long long epoch = 0;    // h->store_epoch then
-        int curF = 0;                    // the F buffer it read
-        uint32_t cap_chunks = 0;
-        const void *vmask = nullptr, *hmask = nullptr, *cinfo = nullptr;
-    } spec;
+    // the NEXT step's VoI split (and chunk scan), launched ahead behind this step's k_step_end when the next scan was announced with its pose
+    Ahead spec;
     // round 5: what was launched for the NEXT step beside this step's per-bin launch (OVERLAPPED steps): split, chunk scan and gather
     // without the late table's slots on bstream, then -- behind the per-bin launch -- k_late_gather (which also ends the step in
     // flight), the bucket histogram and its column scan.  The step that follows takes all of it if it is exactly the step assumed here.
-    struct {
-        bool valid = false;
-        unsigned long long seq = 0, epoch = 0;
-        int curF = 0, qside = -1;
-        double x = 0, y = 0;
-        float To[16] = {0};
-        uint32_t cap_chunks = 0, cap_voi = 0, nbk = 0;
-        int scan_levels = 0;      // as spec.scan_levels
-        bool stats_done = false;  // ... and the stable scatter + bin statistics + first Scan Ratio Test pass (the query chain was through)
-        const void *vmask = nullptr, *hmask = nullptr, *lmask = nullptr, *cinfo = nullptr, *pvl = nullptr, *phl = nullptr, *voi_ego = nullptr,
-                   *mb_hist = nullptr;
-    } ov;
+    Ahead ov;
     unsigned long long n_ov_launched = 0, n_ov_used = 0;
     // the chunk scan: one workgroup (k_chunk_scan_one) scans up to SCAN_ONE_MAX chunk counts, stores with more chunks take the two-level scan.
     // Every place that decides between the two, or sizes what the one-launch scan may read, asks scan_one_max (the hooks build can lower it:
@@ -216,7 +236,6 @@ struct erasor_hip_handle {
     bool mg_large = false, mg_initial = true, mg_active = false;
     uint64_t mg_cnt_voxel = 0, mg_accum = 0;
     DBuf<uint32_t> mb_hist, mb_tot;   // the map's bucketing as a counting sort: [tiles][B + 1] table, [B + 1] totals
-    DBuf<unsigned long long> lab_slots;  // [16][8] label tallies of the assemble kernels (one cache line per slot)
     double tm_span = 0, tm_gap = 0, tm_period = 0;  // erasor_hip_chain_timing: sums in microseconds
     unsigned long long tm_last_open = 0;
     uint64_t tm_n = 0, tm_ngap = 0, tm_nper = 0;
@@ -291,17 +310,17 @@ struct erasor_hip_handle {
     DBuf<OMeta> ometa;  // one record per outskirts chunk (bounding box, valid count): chunks outside the VoI circle are not read
     bool use_ometa = true;
     // ---- VoI-order arrays ----
-    DBuf<float4> voi_ego, spts, rejected;
-    DBuf<uint32_t> voi_key, voi_src, ssrc, rejected_src, grank, glist;
+    DBuf<float4> rejected;
+    DBuf<uint32_t> rejected_src, grank, glist;
     DBuf<uint8_t> gflag;
     // ---- radix ----
-    DBuf<uint32_t> rk_a, rk_b, rv_a, rv_b, hist, hist_l, hist_t, hist2, hist2_l, hist2_t, hist3, hist3_l, hist3_t, dn;
+    DBuf<uint32_t> rk_b, rv_a, rv_b, hist, hist_l, hist_t, hist2, hist2_l, hist2_t, hist3, hist3_l, hist3_t, dn;
     // ---- bins ----
-    DBuf<uint32_t> moff, mcnt, rev_idx, rev_list, vox_off, nvox, ng, out_off, ground_off, rej_off, crej_off;
+    DBuf<uint32_t> rev_idx, rev_list, vox_off, nvox, ng, out_off, ground_off, rej_off, crej_off;
     DBuf<uint32_t> out_off0, rev_before;  // the layout's R-GPF-independent part (k_srt4 -> k_assemble_map<., true>)
-    DBuf<float> mmin, mmax, plane_n;
+    DBuf<float> plane_n;
     DBuf<double> plane_d;
-    DBuf<uint8_t> st1, st1b, status, action;  // (st1b: first-pass status | 0x80 written by k_bin_stats_srt)
+    DBuf<uint8_t> st1, status, action;
     // ---- query side: everything the voxelisation / bucketing of ONE scan owns.  Two sets, so that the query chain of the
     // next scan (erasor_hip_prefetch_scan) can run while the current step is in its map-side stages ----
     QSide q[NSIDE];
@@ -356,21 +375,9 @@ struct erasor_hip_handle {
     DBuf<uint32_t> gsK, gsV, gsL, gsR, gsK2, gsV2;
     DBuf<uint32_t> gsH;
     DBuf<float4> gsC, vox_out;
-    // ---- round 5: what consecutive steps must not share (an overlapped step's early passes run while the step in flight still reads its
-    // own): VoI-order arrays, bin offsets, state, counters, label tallies.  The names above / below are the CURRENT step's set; `alt` is
-    // the other one, where the passes launched ahead write; the two change places when a step is enqueued (swap_sides)
-    struct {
-        DBuf<float4> voi_ego, spts;
-        DBuf<uint32_t> voi_key, voi_src, moff, ssrc, rk_a, mcnt;
-        DBuf<float> mmin, mmax;
-        DBuf<uint8_t> st1b;
-        DBuf<DevState> d_st;
-        DBuf<Counters> d_ctr;
-        DBuf<unsigned long long> lab_slots;
-    } alt;
+    StepSet cset, oset;  // the per-step arrays of the current step and of the passes launched ahead of the next (see StepSet)
     // ---- state ----
-    DBuf<DevState> d_st, d_st_get;  // (d_st_get: a copy of the last finished step's state for the getters, see assemble_egocentric)
-    DBuf<Counters> d_ctr;
+    DBuf<DevState> d_st_get;  // (a copy of the last finished step's state for the getters, see assemble_egocentric)
     DevState st;
     Counters ctr;
     Xf Tl2b, Tb2o, To2b;
@@ -597,19 +604,29 @@ int alloc_bins(erasor_hip_handle *h) {
         rc |= ensure(h, Q(h).d_nvox, 4) | ensure(h, Q(h).d_qctr, 1);
     }
     h->qi = keep;
-    rc |= ensure(h, h->moff, B + 4) | ensure(h, h->alt.moff, B + 4) | ensure(h, h->mcnt, B) | ensure(h, h->alt.mcnt, B);
-    rc |= ensure(h, h->alt.mmin, B) | ensure(h, h->alt.mmax, B) | ensure(h, h->alt.st1b, B + 8);
-    rc |= ensure(h, h->mmin, B) | ensure(h, h->mmax, B);
+    for (StepSet *s : {&h->cset, &h->oset}) {
+        rc |= ensure(h, s->moff, B + 4) | ensure(h, s->mcnt, B) | ensure(h, s->mmin, B) | ensure(h, s->mmax, B) | ensure(h, s->st1b, B + 8);
+        rc |= ensure(h, s->d_st, 1) | ensure(h, s->d_ctr, 1) | ensure(h, s->lab_slots, 128);
+    }
     rc |= ensure(h, h->st1, B) | ensure(h, h->status, B) | ensure(h, h->action, B) | ensure(h, h->rev_idx, B) | ensure(h, h->rev_list, B);
-    rc |= ensure(h, h->out_off0, B + 2) | ensure(h, h->rev_before, B + 2) | ensure(h, h->st1b, B + 8);
+    rc |= ensure(h, h->out_off0, B + 2) | ensure(h, h->rev_before, B + 2);
     rc |= ensure(h, h->out_offR, B + 2) | ensure(h, h->gres_off, B + 2);
     for (int k = 0; k < 2; ++k) rc |= ensure(h, h->late[k], 2 * B + 4) | ensure(h, h->late_holes[k], 2 * B + 4);
     rc |= ensure(h, h->vox_off, B) | ensure(h, h->nvox, B) | ensure(h, h->ng, B) | ensure(h, h->out_off, B) | ensure(h, h->ground_off, B);
     rc |= ensure(h, h->rej_off, B) | ensure(h, h->crej_off, B);
     rc |= ensure(h, h->plane_n, B * (size_t)std::max(h->P.gf_iter, 1) * 3) | ensure(h, h->plane_d, B * (size_t)std::max(h->P.gf_iter, 1));
-    rc |= ensure(h, h->d_st, 1) | ensure(h, h->d_ctr, 1) | ensure(h, h->dn, 16) | ensure(h, h->lab_slots, 128) | ensure(h, h->mb_tot, B + 4);
-    rc |= ensure(h, h->alt.d_st, 1) | ensure(h, h->alt.d_ctr, 1) | ensure(h, h->alt.lab_slots, 128);
+    rc |= ensure(h, h->dn, 16) | ensure(h, h->mb_tot, B + 4);
     return rc ? ERASOR_E_NO_DEVICE : 0;
+}
+
+// the scratch arrays with one entry per map point (both sets of per-step arrays among them)
+int ensure_map_sized(erasor_hip_handle *h, uint32_t V) {
+    int rc = 0;
+    for (StepSet *s : {&h->cset, &h->oset})
+        rc |= ensure(h, s->voi_ego, V) | ensure(h, s->spts, V) | ensure(h, s->voi_key, V) | ensure(h, s->voi_src, V) | ensure(h, s->ssrc, V) | ensure(h, s->rk_a, V);
+    rc |= ensure(h, h->rejected, V) | ensure(h, h->rejected_src, V) | ensure(h, h->grank, V) | ensure(h, h->glist, V) | ensure(h, h->gflag, V);
+    rc |= ensure(h, h->rk_b, V) | ensure(h, h->rv_a, V) | ensure(h, h->rv_b, V);
+    return rc;
 }
 
 // capacity-sized buffers that depend on the map size
@@ -628,11 +645,7 @@ int alloc_map(erasor_hip_handle *h, uint32_t n) {
     int rc = 0;
     rc |= ensure(h, h->Oxy, h->capO) | ensure(h, h->Ozi, h->capO);
     const uint32_t V = h->capV;
-    rc |= ensure(h, h->voi_ego, V) | ensure(h, h->spts, V) | ensure(h, h->voi_key, V) | ensure(h, h->voi_src, V) | ensure(h, h->ssrc, V);
-    rc |= ensure(h, h->alt.voi_ego, V) | ensure(h, h->alt.voi_key, V) | ensure(h, h->alt.voi_src, V);
-    rc |= ensure(h, h->alt.spts, V) | ensure(h, h->alt.ssrc, V) | ensure(h, h->alt.rk_a, V);
-    rc |= ensure(h, h->rejected, V) | ensure(h, h->rejected_src, V) | ensure(h, h->grank, V) | ensure(h, h->glist, V) | ensure(h, h->gflag, V);
-    rc |= ensure(h, h->rk_a, V) | ensure(h, h->rk_b, V) | ensure(h, h->rv_a, V) | ensure(h, h->rv_b, V);
+    rc |= ensure_map_sized(h, V);
     return rc ? ERASOR_E_NO_DEVICE : 0;
 }
 
@@ -650,11 +663,7 @@ int grow_map_scratch(erasor_hip_handle *h, uint64_t need) {
     h->capV = h->capMap;
     const uint32_t V = h->capV;
     int rc = 0;
-    rc |= ensure(h, h->voi_ego, V) | ensure(h, h->spts, V) | ensure(h, h->voi_key, V) | ensure(h, h->voi_src, V) | ensure(h, h->ssrc, V);
-    rc |= ensure(h, h->alt.voi_ego, V) | ensure(h, h->alt.voi_key, V) | ensure(h, h->alt.voi_src, V);
-    rc |= ensure(h, h->alt.spts, V) | ensure(h, h->alt.ssrc, V) | ensure(h, h->alt.rk_a, V);
-    rc |= ensure(h, h->rejected, V) | ensure(h, h->rejected_src, V) | ensure(h, h->grank, V) | ensure(h, h->glist, V) | ensure(h, h->gflag, V);
-    rc |= ensure(h, h->rk_a, V) | ensure(h, h->rk_b, V) | ensure(h, h->rv_a, V) | ensure(h, h->rv_b, V);
+    rc |= ensure_map_sized(h, V);
     h->have_step = false;  // the previous step's read-back clouds lived in these arrays
     return rc ? ERASOR_E_NO_DEVICE : 0;
 }
@@ -873,11 +882,11 @@ int split_submap(erasor_hip_handle *h, double x, double y) {
     int rc = push_state(h);
     if (rc) return rc;
     if (n_sub) {
-        DevState *ds = h->d_st.p;
+        DevState *ds = h->cset.d_st.p;
         LAUNCH(h, "submap", k_count_labels_zi, std::min<uint32_t>(cdiv(n_sub, 256), 1024), 256, (const float2 *)(h->Ozi.p + dst0), n_sub,
                &ds->O_static, &ds->O_dynamic);
     }
-    HIPC(h, hipMemcpyAsync(&h->st, h->d_st.p, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipMemcpyAsync(&h->st, h->cset.d_st.p, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
     release(h->Cbuf);
     h->Cbuf = newC;
@@ -923,8 +932,17 @@ int push_state(erasor_hip_handle *h) {
     h->st.nF = h->nF;
     h->st.nF_valid = h->nFv;
     h->st.o_begin = h->o_begin;
-    HIPC(h, hipMemcpyAsync(h->d_st.p, &h->st, sizeof(DevState), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(h->cset.d_st.p, &h->st, sizeof(DevState), hipMemcpyHostToDevice, h->stream));
     return 0;
+}
+
+// the 19 pointers SrtArgs (k_revert_bins_srt) and EarlyArgs (k_assemble_early) share: what srt4_body reads and writes
+template <class Args>
+void fill_srt_args(Args &a, erasor_hip_handle *h, const StepSet &s, const QSide &q) {
+    a.mcnt = s.mcnt.p, a.mmin = s.mmin.p, a.mmax = s.mmax.p, a.ccnt = q.ccnt.p, a.cmin = q.cmin.p, a.cmax = q.cmax.p;
+    a.st1 = h->st1.p, a.status = h->status.p, a.action = h->action.p, a.rev_idx = h->rev_idx.p, a.rev_list = h->rev_list.p, a.vox_off = h->vox_off.p;
+    a.st = s.d_st.p, a.out_off0 = h->out_off0.p, a.rev_before = h->rev_before.p, a.crej_off = h->crej_off.p;
+    a.st1_in = s.st1b.p, a.moff = s.moff.p, a.qoff = q.qoff.p;
 }
 
 }  // namespace
@@ -1093,26 +1111,27 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     h->qi = 0;
     release(h->Cbuf); release(h->F[0]); release(h->F[1]); release(h->Oxy); release(h->Ozi);
     release(h->vmask); release(h->hmask); release(h->cinfo); release(h->pvl); release(h->phl); release(h->topv); release(h->toph); release(h->topr); release(h->ometa);
-    release(h->voi_ego); release(h->spts); release(h->rejected); release(h->voi_key); release(h->voi_src); release(h->ssrc);
+    release(h->rejected);
     release(h->rejected_src); release(h->grank); release(h->glist); release(h->gflag);
-    release(h->rk_a); release(h->rk_b); release(h->rv_a); release(h->rv_b); release(h->hist); release(h->hist_l); release(h->hist_t); release(h->hist2); release(h->hist2_l); release(h->hist2_t); release(h->hist3); release(h->hist3_l); release(h->hist3_t); release(h->dn); release(h->lab_slots); release(h->mb_hist); release(h->mb_tot); release(h->mg_curr); release(h->mg_map); release(h->mg_done); release(h->mg_tmp);
-    release(h->moff); release(h->mcnt); release(h->rev_idx); release(h->rev_list); release(h->vox_off);
-    release(h->out_off0); release(h->rev_before); release(h->st1b);
+    release(h->rk_b); release(h->rv_a); release(h->rv_b); release(h->hist); release(h->hist_l); release(h->hist_t); release(h->hist2); release(h->hist2_l); release(h->hist2_t); release(h->hist3); release(h->hist3_l); release(h->hist3_t); release(h->dn); release(h->mb_hist); release(h->mb_tot); release(h->mg_curr); release(h->mg_map); release(h->mg_done); release(h->mg_tmp);
+    release(h->rev_idx); release(h->rev_list); release(h->vox_off);
+    release(h->out_off0); release(h->rev_before);
     release(h->out_offR); release(h->gres_off);
     for (int k = 0; k < 2; ++k) { release(h->late[k]); release(h->late_holes[k]); }
     release(h->lmask);
-    release(h->alt.voi_ego); release(h->alt.voi_key); release(h->alt.voi_src); release(h->alt.moff); release(h->alt.d_st); release(h->alt.d_ctr);
-    release(h->alt.spts); release(h->alt.ssrc); release(h->alt.rk_a); release(h->alt.mcnt); release(h->alt.mmin); release(h->alt.mmax); release(h->alt.st1b);
-    release(h->alt.lab_slots);
+    for (StepSet *s : {&h->cset, &h->oset}) {
+        release(s->voi_ego); release(s->spts); release(s->voi_key); release(s->voi_src); release(s->moff); release(s->ssrc); release(s->rk_a);
+        release(s->mcnt); release(s->mmin); release(s->mmax); release(s->st1b); release(s->d_st); release(s->d_ctr); release(s->lab_slots);
+    }
     for (hipEvent_t e : {h->ev_stats, h->ev_srt4, h->ev_asm, h->ev_early, h->ev_scan})
         if (e) (void)hipEventDestroy(e);
     if (h->bstream && h->bstream_own) (void)hipStreamDestroy(h->bstream);
     release(h->nvox); release(h->ng); release(h->out_off); release(h->ground_off); release(h->rej_off); release(h->crej_off);
-    release(h->mmin); release(h->mmax); release(h->plane_n); release(h->plane_d);
+    release(h->plane_n); release(h->plane_d);
     release(h->st1); release(h->status); release(h->action);
     release(h->curr_rejected);
     release(h->gsK); release(h->gsV); release(h->gsL); release(h->gsR); release(h->gsK2); release(h->gsV2); release(h->gsH); release(h->gsC);
-    release(h->vox_out); release(h->d_st); release(h->d_st_get); release(h->d_ctr);
+    release(h->vox_out); release(h->d_st_get);
     release(h->ev.gt); release(h->ev.est); release(h->ev.map); release(h->ev.pts); release(h->ev.bkt); release(h->ev.cnt); release(h->ev.pl);
     release(h->ev.tops); release(h->ev.idx); release(h->ev.ctr); release(h->ev.code);
     release(h->ev.nn_bb); release(h->ev.nn_key); release(h->ev.nn_ka); release(h->ev.nn_kb); release(h->ev.nn_va); release(h->ev.nn_vb);
@@ -1152,7 +1171,7 @@ static int set_map_common(erasor_hip_handle *h, const void *src, size_t n, bool 
     if (rc) return rc;
     // stage the AoS cloud in voi_ego (capV >= n), then split into the outskirts layout at the END of the O buffer
     if (n) {
-        HIPC(h, hipMemcpyAsync(h->voi_ego.p, src, n * sizeof(float4), src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+        HIPC(h, hipMemcpyAsync(h->cset.voi_ego.p, src, n * sizeof(float4), src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     }
     h->nF = 0;
     h->nFv = 0;
@@ -1162,7 +1181,7 @@ static int set_map_common(erasor_hip_handle *h, const void *src, size_t n, bool 
     h->o_valid = n;
     h->nC = 0;
     h->submap_not_initialized = true;
-    if (n) LAUNCH(h, "set_map", k_store_outskirts, cdiv(n, 256), 256, (const float4 *)h->voi_ego.p, (uint32_t)n, h->Oxy.p, h->Ozi.p, h->o_begin);
+    if (n) LAUNCH(h, "set_map", k_store_outskirts, cdiv(n, 256), 256, (const float4 *)h->cset.voi_ego.p, (uint32_t)n, h->Oxy.p, h->Ozi.p, h->o_begin);
     rc = ometa_reset(h);
     if (rc) return rc;
     memset(&h->st, 0, sizeof(h->st));
@@ -1170,11 +1189,11 @@ static int set_map_common(erasor_hip_handle *h, const void *src, size_t n, bool 
     if (rc) return rc;
     // initial label counters of the outskirts (parse_dynamic_obj, utils.cpp:57-78)
     if (n) {
-        DevState *ds = h->d_st.p;
-        LAUNCH(h, "set_map", k_count_labels4, std::min<uint32_t>(cdiv(n, 256), 2048), 256, (const float4 *)h->voi_ego.p, (uint32_t)n,
+        DevState *ds = h->cset.d_st.p;
+        LAUNCH(h, "set_map", k_count_labels4, std::min<uint32_t>(cdiv(n, 256), 2048), 256, (const float4 *)h->cset.voi_ego.p, (uint32_t)n,
                (const uint32_t *)nullptr, &ds->O_static, &ds->O_dynamic);
     }
-    HIPC(h, hipMemcpyAsync(&h->st, h->d_st.p, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipMemcpyAsync(&h->st, h->cset.d_st.p, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
     h->have_map = true;
     h->poisoned = false;
@@ -1864,14 +1883,30 @@ static void q_drain(erasor_hip_handle *h) {
 }
 
 
-// The VoI split on the main stream.  dev == nullptr: a step's own pass (extents from the host mirror).  dev != nullptr: the
-// pass of the NEXT step, launched ahead; the kernel takes the extents the step in flight commits on the device.
-static void launch_voi_split(erasor_hip_handle *h, const float4 *F, uint32_t nF, uint32_t nFchunks, uint32_t o_begin, uint32_t o_chunk0,
-                             uint32_t nOchunks, uint32_t nchunks_grid, double xc, double yc, double voi_r2, const DevState *dev, uint32_t cap_chunks,
-                             const StepEnd *step_end = nullptr, const OvSplit *ovs = nullptr) {
+// Where a pass over the map store takes the store's extents from.  HOST: a step's own pass, from the host mirror (the fields below).
+// A pass of the NEXT step, launched ahead, reads them from the state of the step in flight (dev; the host fields stay 0) -- COMMITTED:
+// behind that step, what its end commits; BEING_WRITTEN: beside its per-bin launch, on the early stream, with its late table
+struct Extents {
+    enum From { HOST, COMMITTED, BEING_WRITTEN } from = HOST;
+    uint32_t nF = 0, nFchunks = 0, o_begin = 0, o_chunk0 = 0, nOchunks = 0, nchunks = 0;
+    const DevState *dev = nullptr;
+};
+// LAUNCH() targets h->cur: the launchers below take their stream and leave h->cur as they found it
+struct OnStream {
+    erasor_hip_handle *h;
+    hipStream_t keep;
+    OnStream(erasor_hip_handle *h_, hipStream_t s) : h(h_), keep(h_->cur) { h->cur = s; }
+    ~OnStream() { h->cur = keep; }
+};
+static inline OMeta *ometa_or_null(const erasor_hip_handle *h) { return h->use_ometa ? h->ometa.p : (OMeta *)nullptr; }
+
+// The VoI split (OMU.cpp:254 fetch_VoI membership).  ext.from == HOST: a step's own pass, on the main stream.  COMMITTED: the pass of the
+// NEXT step launched ahead on the main stream (`step_end`: its last workgroup also ends the step in flight -- round 4, see StepEnd in
+// kernels.hip.h).  BEING_WRITTEN (`ovs`): an overlapped step's pass, on the early stream beside the per-bin launch of the step in flight.
+static void launch_voi_split(erasor_hip_handle *h, const float4 *F, const Extents &ext, uint32_t nchunks_grid, double xc, double yc, double voi_r2,
+                             uint32_t cap_chunks, const StepEnd *step_end = nullptr, const OvSplit *ovs = nullptr) {
     // one chunk per wave while that needs <= 16 workgroups per CU: the hardware back-fills workgroups as they finish,
     // which balances better than a grid-stride tail (measured, tools/bw_probe.hip)
-    // (step_end: the launch's LAST workgroup ends the step in flight -- round 4, see StepEnd in kernels.hip.h)
     StepEnd se;
     memset(&se, 0, sizeof(se));
     if (step_end) se = *step_end;
@@ -1879,125 +1914,165 @@ static void launch_voi_split(erasor_hip_handle *h, const float4 *F, uint32_t nF,
     if (ovs) ov = *ovs;
     const uint32_t grid = std::max(1u, std::min<uint32_t>(cdiv(nchunks_grid, 4), 256 * 16)) + (step_end ? 1u : 0u);
     const uint32_t capO_chunks = h->capO / CHUNK;
-    // (prof 3: the same on every FOURTH launch -- the bracket costs the step it observes ~9 us (gpurun_out/r03k: 0.276 vs 0.267 ms
-    // per scan with / without), a sample of the timed region's launches costs a quarter of that)
-    if (ovs && (h->prof == 2 || (h->prof == 3 && (h->n_split_launch++ & 3u) == 0))) {
-        // (the roofline measurement of an overlapped step's pass: start / stop events on the early stream, see below)
+    const DevState *dev = ovs ? (const DevState *)nullptr : ext.dev;  // (an overlapped step's pass takes the extents from ovs->prev)
+    hipStream_t s = ovs ? h->bstream : h->stream;
+    // roofline measurement (prof 2; prof 3: every FOURTH launch -- the bracket costs the step it observes ~9 us (round 3: 0.276 vs
+    // 0.267 ms per scan with / without), a sample of the timed region's launches costs a quarter of that): the launch carries its own
+    // start / stop events (hipExtLaunchKernelGGL: they stamp the kernel's execution window itself, the figure rocprofv3 reports too).
+    // A record / record bracket around the launch costs two extra barrier packets on a 17 us kernel and slows the step it observes.
+    if (h->prof == 2 || (h->prof == 3 && (h->n_split_launch++ & 3u) == 0)) {
         PendingEvt ke;
         ke.name_id = prof_id(h, "voi_split");
         ke.a = get_evt(h);
         ke.b = get_evt(h);
-        hipExtLaunchKernelGGL(k_voi_split, dim3(grid), dim3(256), 0, h->bstream, ke.a, ke.b, 0, F, nF, nFchunks, (const float2 *)h->Oxy.p, o_begin, o_chunk0,
-                              nOchunks, xc, yc, voi_r2, h->vmask.p, h->hmask.p, h->cinfo.p, dev, capO_chunks, cap_chunks,
-                              h->use_ometa ? h->ometa.p : (OMeta *)nullptr, se, ov);
-        h->pending.push_back(ke);
-    } else if (ovs) {  // (an overlapped step's pass: on the early stream, beside the per-bin launch of the step in flight)
-        hipStream_t keep = h->cur;
-        h->cur = h->bstream;
-        LAUNCH(h, "voi_split", k_voi_split, grid, 256, F, nF, nFchunks, (const float2 *)h->Oxy.p, o_begin, o_chunk0, nOchunks, xc, yc, voi_r2, h->vmask.p,
-               h->hmask.p, h->cinfo.p, dev, capO_chunks, cap_chunks, h->use_ometa ? h->ometa.p : (OMeta *)nullptr, se, ov);
-        h->cur = keep;
-    } else if (h->prof == 2 || (h->prof == 3 && (h->n_split_launch++ & 3u) == 0)) {
-        // roofline measurement: the launch carries its own start / stop events (hipExtLaunchKernelGGL: they stamp the
-        // kernel's execution window itself, the figure rocprofv3 reports too).  A record / record bracket around the
-        // launch costs two extra barrier packets on a 17 us kernel and slows the step it is supposed to observe.
-        PendingEvt ke;
-        ke.name_id = prof_id(h, "voi_split");
-        ke.a = get_evt(h);
-        ke.b = get_evt(h);
-        hipExtLaunchKernelGGL(k_voi_split, dim3(grid), dim3(256), 0, h->stream, ke.a, ke.b, 0, F, nF, nFchunks, (const float2 *)h->Oxy.p, o_begin,
-                              o_chunk0, nOchunks, xc, yc, voi_r2, h->vmask.p, h->hmask.p, h->cinfo.p, dev, capO_chunks, cap_chunks,
-                              h->use_ometa ? h->ometa.p : (OMeta *)nullptr, se, ov);
+        hipExtLaunchKernelGGL(k_voi_split, dim3(grid), dim3(256), 0, s, ke.a, ke.b, 0, F, ext.nF, ext.nFchunks, (const float2 *)h->Oxy.p, ext.o_begin,
+                              ext.o_chunk0, ext.nOchunks, xc, yc, voi_r2, h->vmask.p, h->hmask.p, h->cinfo.p, dev, capO_chunks, cap_chunks, ometa_or_null(h), se, ov);
         h->pending.push_back(ke);
     } else {
-        hipStream_t keep = h->cur;
-        h->cur = h->stream;
-        LAUNCH(h, "voi_split", k_voi_split, grid, 256, F, nF, nFchunks, (const float2 *)h->Oxy.p, o_begin, o_chunk0, nOchunks, xc, yc, voi_r2,
-               h->vmask.p, h->hmask.p, h->cinfo.p, dev, capO_chunks, cap_chunks, h->use_ometa ? h->ometa.p : (OMeta *)nullptr, se, ov);
-        h->cur = keep;
+        OnStream on(h, s);
+        LAUNCH(h, "voi_split", k_voi_split, grid, 256, F, ext.nF, ext.nFchunks, (const float2 *)h->Oxy.p, ext.o_begin, ext.o_chunk0, ext.nOchunks, xc, yc, voi_r2,
+               h->vmask.p, h->hmask.p, h->cinfo.p, dev, capO_chunks, cap_chunks, ometa_or_null(h), se, ov);
     }
 }
 
+// The chunk scan behind a split, on stream s; the step's state, counters and label tallies start in `to`.  One workgroup
+// (k_chunk_scan_one) scans up to scan_one_max chunk counts, more take two levels.  A step's own scan knows its chunk count (ext.nchunks).
+// A scan launched ahead does not: `hint` bounds it -- behind the step (COMMITTED) the two-level grid comes from the hint, and nothing is
+// launched (levels == 0) when the buffers cannot take it; beside the per-bin launch (BEING_WRITTEN) two levels go over everything the
+// buffers hold, at most cap_chunks.  What the scan can take is in the record: a step with more chunks runs its own passes.
+static ScanDone launch_chunk_scan(erasor_hip_handle *h, StepSet &to, hipStream_t s, const Extents &ext, uint32_t hint, uint32_t cap_chunks, uint32_t cap_voi) {
+    ScanDone d;
+    uint32_t grid = 0;  // two levels: workgroups of the first; one level of a step's own scan: the kernel's ntop argument
+    const size_t room = std::min(h->pvl.cap, h->phl.cap);
+    const auto top_cap = [h] { return std::min(std::min(h->topv.cap, h->toph.cap), h->topr.cap); };
+    if (ext.from == Extents::HOST) {
+        d.levels = ext.nchunks <= h->scan_one_max ? 1 : 2;
+        grid = std::max(1u, cdiv(ext.nchunks, 1024));
+    } else if (ext.from == Extents::COMMITTED) {
+        const uint32_t one_cap = (uint32_t)std::min<size_t>(std::min(room, h->cinfo.cap) - 8, h->scan_one_max);  // (k_chunk_scan_one reads cinfo up to here)
+        grid = cdiv(hint, 1024);  // (maps beyond scan_one_max chunks -- 16384; config 4: 38 k --: the grid is an upper bound)
+        if (hint <= one_cap && h->topv.cap >= 24 && h->toph.cap >= 24) {
+            d.levels = 1;
+            d.cap = one_cap;
+        } else if (room >= 8 && (size_t)grid * 1024 + 8 <= room && grid + 1 <= top_cap()) {
+            d.levels = 2;
+            d.cap = grid * 1024u;
+        } else
+            return d;
+    } else {
+        const uint32_t one_cap = (uint32_t)std::min<size_t>(room - 8, h->scan_one_max);
+        if (hint <= one_cap) {
+            d.levels = 1;
+            d.cap = std::min<uint32_t>(one_cap, cap_chunks);
+        } else {
+            grid = (uint32_t)std::min<size_t>(cdiv(std::min<size_t>(cap_chunks, room - 8), 1024), top_cap() - 2);
+            d.levels = 2;
+            d.cap = std::min<uint32_t>(grid * 1024u, cap_chunks);
+        }
+    }
+    d.pvl = h->pvl.p;
+    d.phl = h->phl.p;
+    const bool ahead = ext.from != Extents::HOST;
+    const bool mb_count = h->B + 1 <= QB_NB_MAX;
+    uint32_t *mb_tot = mb_count ? h->mb_tot.p : (uint32_t *)nullptr;
+    const uint32_t mb_n = mb_count ? h->B + 2 : 0u, capO_chunks = ahead ? h->capO / CHUNK : 0u;
+    OnStream on(h, s);
+    if (d.levels == 1) {
+        LAUNCH(h, "chunk_scan", k_chunk_scan_one, 1, 1024, (const uint32_t *)h->cinfo.p, ext.nchunks, h->pvl.p, h->phl.p, h->topv.p, h->toph.p, ahead ? 16u : grid,
+               ext.nFchunks, to.d_st.p, to.d_ctr.p, h->st, to.lab_slots.p, mb_tot, mb_n, ometa_or_null(h), capO_chunks, d.cap, ext.dev, cap_voi);
+    } else {
+        LAUNCH(h, "chunk_scan", k_chunk_scan_local, grid, 256, (const uint32_t *)h->cinfo.p, ext.nchunks, h->pvl.p, h->phl.p, h->topv.p, h->toph.p, h->topr.p,
+               ext.dev, capO_chunks, d.cap, ahead ? 1u : 0u);
+        LAUNCH(h, "chunk_scan", k_chunk_scan_top, 1, 1024, h->topv.p, h->toph.p, grid, (const uint32_t *)h->pvl.p, (const uint32_t *)h->phl.p, ext.nchunks,
+               ext.nFchunks, to.d_st.p, to.d_ctr.p, h->st, to.lab_slots.p, mb_tot, mb_n, (const uint32_t *)h->topr.p, ometa_or_null(h), capO_chunks, d.cap,
+               ext.dev, cap_voi);
+    }
+    return d;
+}
+
+// VoI gather + egocentric transform + R-POD key (OMU.cpp:435-437; erasor.cpp:124-139) of region F into `to`, on stream s.  One wavefront
+// per work item (`items`: GATHER_SUB pieces per chunk of the VoI-resident region, one per outskirts chunk).  lmask: the gather ahead of an
+// overlapped step leaves the late table's slots alone
+static void launch_voi_gather(erasor_hip_handle *h, StepSet &to, hipStream_t s, const float4 *F, const Extents &ext, uint32_t items, const Xf &To,
+                              const QSide &q, const unsigned long long *lmask) {
+    OnStream on(h, s);
+    LAUNCH(h, "voi_gather", k_voi_gather, std::max(1u, std::min<uint32_t>(cdiv(items, 4), 256 * 16)), 256, F, ext.nF, ext.nFchunks, h->Oxy.p, h->Ozi.p,
+           ext.o_chunk0, ext.nOchunks, (const unsigned long long *)h->vmask.p, (const unsigned long long *)h->hmask.p, (const uint32_t *)h->cinfo.p,
+           (const uint32_t *)h->pvl.p, (const uint32_t *)h->phl.p, (const uint32_t *)h->topv.p, (const uint32_t *)h->toph.p, To, h->dp, to.d_st.p, to.d_ctr.p,
+           (const Counters *)q.d_qctr.p, to.voi_ego.p, to.voi_key.p, to.voi_src.p, ometa_or_null(h), lmask, lmask ? h->capO / CHUNK : 0u);
+}
+
+// The map's bucketing as a one-digit counting sort.  The table is sized for the whole map (n_voi is an upper bound), the GRIDS for 1.5 x
+// the previous step's VoI: the kernels walk the tiles with a grid stride, so an under-estimate only costs a second round
+static uint32_t bucket_tiles(const erasor_hip_handle *h, uint32_t n_voi) {
+    const uint32_t ntile_tab = std::max(1u, cdiv(n_voi, MB_TILE));
+    return h->last_n_voi ? std::min(ntile_tab, std::max(64u, cdiv((uint64_t)h->last_n_voi * 3 / 2, MB_TILE))) : ntile_tab;
+}
+// ... the histogram and its column scan (the bins' offsets into to.moff)
+static void launch_bucket_table(erasor_hip_handle *h, StepSet &to, hipStream_t s, uint32_t n_voi, uint32_t nbk) {
+    const uint32_t *nvoi_dev = &to.d_st.p->voi_total;
+    OnStream on(h, s);
+    LAUNCH(h, "voi_bucket", k_mb_hist, bucket_tiles(h, n_voi), 1024, (const uint32_t *)to.voi_key.p, n_voi, nvoi_dev, nbk, h->mb_hist.p, h->mb_tot.p);
+    LAUNCH(h, "voi_bucket", k_mb_colscan, cdiv(nbk, MB_PAD), 256, h->mb_hist.p, n_voi, nvoi_dev, nbk, (const uint32_t *)h->mb_tot.p, to.moff.p);
+}
+// ... the stable scatter into to.spts / ssrc / rk_a
+static void launch_bucket_scatter(erasor_hip_handle *h, StepSet &to, hipStream_t s, uint32_t n_voi, uint32_t nbk, int bits) {
+    const uint32_t *nvoi_dev = &to.d_st.p->voi_total;
+    const uint32_t ntile_ub = bucket_tiles(h, n_voi);
+    OnStream on(h, s);
+    if (nbk <= MBW_NB_SMALL)
+        LAUNCH(h, "voi_bucket", k_mb_scatter_w<MBW_NB_SMALL>, ntile_ub, 1024, (const uint32_t *)to.voi_key.p, (const float4 *)to.voi_ego.p,
+               (const uint32_t *)to.voi_src.p, n_voi, nvoi_dev, nbk, bits, (const uint32_t *)h->mb_hist.p, to.spts.p, to.ssrc.p, to.rk_a.p, h->dbg_stamps.p);
+    else if (nbk <= MBW_NB_MAX)
+        LAUNCH(h, "voi_bucket", k_mb_scatter_w<MBW_NB_MAX>, ntile_ub, 1024, (const uint32_t *)to.voi_key.p, (const float4 *)to.voi_ego.p,
+               (const uint32_t *)to.voi_src.p, n_voi, nvoi_dev, nbk, bits, (const uint32_t *)h->mb_hist.p, to.spts.p, to.ssrc.p, to.rk_a.p, h->dbg_stamps.p);
+    else
+        LAUNCH(h, "voi_bucket", k_mb_scatter, ntile_ub, 1024, (const uint32_t *)to.voi_key.p, (const float4 *)to.voi_ego.p, (const uint32_t *)to.voi_src.p,
+               n_voi, nvoi_dev, nbk, bits, (const uint32_t *)h->mb_hist.p, to.spts.p, to.ssrc.p, to.rk_a.p);
+}
+// The bins' statistics of the bucketed map.  with_srt (v3): the Scan Ratio Test's first pass rides along, bin by bin -- the query's
+// statistics are needed: the stream joins q's chain in front of the launch (with nodes announced ahead it finished long ago)
+static void launch_bin_stats(erasor_hip_handle *h, StepSet &to, hipStream_t s, const QSide &q, bool with_srt) {
+    const uint32_t B = h->B;
+    OnStream on(h, s);
+    if (with_srt) {
+        (void)hipStreamWaitEvent(s, q.ev_done, 0);
+        LAUNCH(h, "bin_stats", k_bin_stats_srt, cdiv((uint64_t)B * 64, 256), 256, h->dp, (const float4 *)to.spts.p, (const uint32_t *)to.moff.p, B, to.mcnt.p,
+               to.mmin.p, to.mmax.p, (const uint32_t *)q.ccnt.p, (const float *)q.cmin.p, (const float *)q.cmax.p, to.st1b.p);
+    } else
+        LAUNCH(h, "bin_stats", k_bin_stats, cdiv((uint64_t)B * 64, 256), 256, (const float4 *)to.spts.p, (const uint32_t *)to.moff.p, B, to.mcnt.p, to.mmin.p,
+               to.mmax.p);
+}
+// what every pass launched ahead assumes of the step that may take it: its number, the node's pose, the store, the split's buffers
+static void ahead_assumes(erasor_hip_handle *h, Ahead &a, unsigned long long seq, double x, double y, uint32_t cap_chunks) {
+    a.valid = true;
+    a.seq = seq, a.epoch = h->store_epoch, a.curF = h->curF ^ 1;
+    a.x = x, a.y = y, a.cap_chunks = cap_chunks;
+    a.vmask = h->vmask.p, a.hmask = h->hmask.p, a.cinfo = h->cinfo.p;
+}
 // The NEXT step's VoI split behind the step in flight (its pose is known: erasor_hip_prefetch_node): reads the store that step writes
 // and the extents its end commits; `step_end`: the launch also ends the step in flight (see StepEnd).
 static void launch_split_ahead(erasor_hip_handle *h, double nx, double ny, uint32_t nchunks_hint, const StepEnd *step_end) {
     const size_t cap_chunks = std::min(std::min(h->vmask.cap, h->hmask.cap) / CHUNK_TILES, h->cinfo.cap) - 8;
-    launch_voi_split(h, (const float4 *)h->F[h->curF ^ 1].p, 0u, 0u, 0u, 0u, 0u, nchunks_hint + 64, nx, ny, h->dp.voi_r2, (const DevState *)h->d_st.p,
-                     (uint32_t)cap_chunks, step_end);
-    h->spec.valid = true;
-    h->spec.x = nx;
-    h->spec.y = ny;
-    h->spec.seq = h->step_seq;
-    h->spec.epoch = h->store_epoch;
-    h->spec.curF = h->curF ^ 1;
-    h->spec.cap_chunks = (uint32_t)cap_chunks;
-    h->spec.vmask = h->vmask.p;
-    h->spec.hmask = h->hmask.p;
-    h->spec.cinfo = h->cinfo.p;
-    h->spec.scan = false;
+    Extents ext;
+    ext.from = Extents::COMMITTED;
+    ext.dev = (const DevState *)h->cset.d_st.p;
+    launch_voi_split(h, (const float4 *)h->F[h->curF ^ 1].p, ext, nchunks_hint + 64, nx, ny, h->dp.voi_r2, (uint32_t)cap_chunks, step_end);
+    Ahead &a = h->spec;
+    ahead_assumes(h, a, h->step_seq, nx, ny, (uint32_t)cap_chunks);
+    a.scan = ScanDone();
     h->fly.spec_launched = true;
     ++h->n_spec_launched;
     // round 4: ... and the next step's chunk scan behind it: the stream goes on while the host is still collecting this step's results
     // and comes back with the next one (its turnaround, ~10 us, used to be idle time between the split and the scan)
-    const bool mb_count = h->B + 1 <= QB_NB_MAX;
-    const uint32_t scan_cap = (uint32_t)std::min<size_t>(std::min(std::min(h->pvl.cap, h->phl.cap), h->cinfo.cap) - 8, h->scan_one_max);  // (k_chunk_scan_one reads cinfo up to here)
-    if (nchunks_hint + 64u <= scan_cap && h->topv.cap >= 24 && h->toph.cap >= 24 && h->prof != 1) {
-        hipStream_t keep = h->cur;
-        h->cur = h->stream;
-        // (round 5: the next step's state, counters and tallies live in the OTHER set, see erasor_hip_handle::alt; it starts from what the
-        // step in flight has committed)
-        LAUNCH(h, "chunk_scan", k_chunk_scan_one, 1, 1024, (const uint32_t *)h->cinfo.p, 0u, h->pvl.p, h->phl.p, h->topv.p, h->toph.p, 16u, 0u, h->alt.d_st.p,
-               h->alt.d_ctr.p, h->st, h->alt.lab_slots.p, mb_count ? h->mb_tot.p : (uint32_t *)nullptr, mb_count ? h->B + 2 : 0u,
-               h->use_ometa ? h->ometa.p : (OMeta *)nullptr, h->capO / CHUNK, scan_cap, (const DevState *)h->d_st.p, 0xFFFFFFFFu);
-        h->cur = keep;
-        h->spec.scan = true;
-        h->spec.scan_levels = 1;
-        h->spec.scan_cap = scan_cap;
-        h->spec.pvl = h->pvl.p;
-        h->spec.phl = h->phl.p;
-    } else if (h->prof != 1) {
-        // maps beyond k_chunk_scan_one's scan_one_max chunks (16384; config 4: 38 k): the two-level scan ahead, its grid an upper bound
-        const size_t room = std::min(h->pvl.cap, h->phl.cap);
-        const uint32_t grid = (uint32_t)cdiv(nchunks_hint + 64u, 1024);
-        const size_t top_cap = std::min(std::min(h->topv.cap, h->toph.cap), h->topr.cap);
-        if (room >= 8 && (size_t)grid * 1024 + 8 <= room && grid + 1 <= top_cap) {
-            const uint32_t cap2 = grid * 1024u;
-            hipStream_t keep = h->cur;
-            h->cur = h->stream;
-            LAUNCH(h, "chunk_scan", k_chunk_scan_local, grid, 256, (const uint32_t *)h->cinfo.p, 0u, h->pvl.p, h->phl.p, h->topv.p, h->toph.p, h->topr.p,
-                   (const DevState *)h->d_st.p, h->capO / CHUNK, cap2, 1u);
-            LAUNCH(h, "chunk_scan", k_chunk_scan_top, 1, 1024, h->topv.p, h->toph.p, grid, (const uint32_t *)h->pvl.p, (const uint32_t *)h->phl.p, 0u, 0u,
-                   h->alt.d_st.p, h->alt.d_ctr.p, h->st, h->alt.lab_slots.p, mb_count ? h->mb_tot.p : (uint32_t *)nullptr, mb_count ? h->B + 2 : 0u,
-                   (const uint32_t *)h->topr.p, h->use_ometa ? h->ometa.p : (OMeta *)nullptr, h->capO / CHUNK, cap2, (const DevState *)h->d_st.p, 0xFFFFFFFFu);
-            h->cur = keep;
-            h->spec.scan = true;
-            h->spec.scan_levels = 2;
-            h->spec.scan_cap = cap2;
-            h->spec.pvl = h->pvl.p;
-            h->spec.phl = h->phl.p;
-        }
-    }
+    // (round 5: the next step's state, counters and tallies live in the OTHER set, see StepSet; it starts from what the step in flight
+    // has committed)
+    if (h->prof != 1) a.scan = launch_chunk_scan(h, h->oset, h->stream, ext, nchunks_hint + 64u, 0u, 0xFFFFFFFFu);
 }
 
-// round 5: the two sets of per-step arrays change places (see erasor_hip_handle::alt): what the passes launched ahead wrote becomes the
-// current step's, the finished step's becomes scratch for the passes launched ahead of the next
-static void swap_sides(erasor_hip_handle *h) {
-    std::swap(h->voi_ego, h->alt.voi_ego);
-    std::swap(h->voi_key, h->alt.voi_key);
-    std::swap(h->voi_src, h->alt.voi_src);
-    std::swap(h->moff, h->alt.moff);
-    std::swap(h->d_st, h->alt.d_st);
-    std::swap(h->d_ctr, h->alt.d_ctr);
-    std::swap(h->lab_slots, h->alt.lab_slots);
-    // (the bucketed VoI and the bins' statistics too: an overlapped step's scatter and first Scan Ratio Test pass are launched ahead)
-    std::swap(h->spts, h->alt.spts);
-    std::swap(h->ssrc, h->alt.ssrc);
-    std::swap(h->rk_a, h->alt.rk_a);
-    std::swap(h->mcnt, h->alt.mcnt);
-    std::swap(h->mmin, h->alt.mmin);
-    std::swap(h->mmax, h->alt.mmax);
-    std::swap(h->st1b, h->alt.st1b);
-}
+// round 5: the two sets of per-step arrays change places (see StepSet): what the passes launched ahead wrote becomes the current step's,
+// the finished step's becomes scratch for the passes launched ahead of the next
+static void swap_sides(erasor_hip_handle *h) { std::swap(h->cset, h->oset); }
 
 static inline void cpu_relax() {
 #if defined(__x86_64__) || defined(__i386__)
@@ -2009,13 +2084,95 @@ static inline void cpu_relax() {
 // ERASOR_HIP_OVERLAP unset: does overlapping consecutive steps pay on this handle's workload?  See the definition of OvAuto.
 static void overlap_auto_sample(erasor_hip_handle *h, double period_us);
 static int step_collect(erasor_hip_handle *h, erasor_step_result *res);
-// First half of a step: everything is ENQUEUED (this scan's query chain unless it is in flight already, the map chain, Scan Ratio
-// Test .. write-back, k_step_end, the next step's VoI split and the next announced scan's query chain); nothing is waited for.
-// ticket != 0: the scan is the OLDEST announced one and must carry that ticket (erasor_hip_step_ticket): nothing is compared, the
-// caller's buffer is not read again; scan_src / n_scan / T_l2b are ignored.
-static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_scan, bool src_is_device, const float T_l2b[16],
-                        const float T_b2o[16], const float T_o2b[16], int flags = 0, RowFmt fmt = RowFmt(), uint64_t ticket = 0) {
-    if (!h) return ERASOR_E_INVALID;
+
+// ERASOR_HIP_HOST_TIMING: the host's time stamps along step_enqueue (carried in the plan)
+struct HostMarks {
+    bool on = false;
+    std::chrono::steady_clock::time_point t0;
+    std::vector<std::pair<const char *, double>> marks;
+    double us() const { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
+    void operator()(const char *what) {
+        if (on) marks.emplace_back(what, us());
+    }
+};
+
+// Everything step_enqueue's stages share: the call's arguments, the sizes and every path decision.  step_admit fills the arguments,
+// step_plan_reserve the sizes and decisions.  Only two groups are written after that, each by the stage named: the map chain decides
+// use_ov / stats_ahead / nbk / bits (and leaves its result, sm_keys); step_next_overlap decides ov_next / nxt_side before the early stream.
+struct StepPlan {
+    // ---- the call (a ticket: resolved to the announced scan by step_admit)
+    const void *scan_src;
+    size_t n_scan;
+    bool src_is_device;
+    const float *T_l2b, *T_b2o, *T_o2b;
+    int flags;
+    RowFmt fmt;
+    uint64_t ticket;
+    float Tl_ticket[16];
+    uint32_t ns = 0;      // points of the scan
+    bool prevox = false;  // STEP_QUERY_PREVOXELIZED
+    HostMarks MARK;
+    // ---- sizes
+    double xc = 0, yc = 0;  // the pose, OMU.cpp:246-247
+    DevState *ds = nullptr;  // the current set's state and counters
+    Counters *dc = nullptr;
+    uint32_t B = 0;
+    uint64_t n_map_in = 0, n_voi_room = 0;  // (n_voi_room: entries of the VoI-order arrays: reserved slots keep places too, round 5)
+    double voi_r2 = 0;
+    Extents ext;              // the store's extents, from the host mirror
+    uint32_t n_voi = 0, nq = 0;  // upper bounds: the kernels read the actual counts (st->voi_total, st->q_nvox) from device memory
+    // ---- decisions
+    bool mb_count = false;  // the map's bucketing as a one-digit counting sort (else: LSD radix passes)
+    bool st1_ahead = false;  // v3: the Scan Ratio Test's first pass rides along with the map's bin statistics (k_bin_stats_srt)
+    // up to 4096 bins the output layout has no launch of its own: k_srt4 prepares what does not depend on R-GPF, every workgroup of
+    // the write-back finishes it (beyond that, and under per-launch profiling: k_layout4 / k_layout)
+    bool fold = false;
+    // round 4: v3's second pass is the LAST WORKGROUP of the per-bin launch (k_revert_bins_srt): the revert decision is local to a bin, so
+    // the per-bin workgroups find their bins themselves and nothing on the chain waits for k_srt4
+    bool srt_in_revert = false;
+    // round 5: the RESERVED layout (srt4_body): the write-back of everything but the reverted bins does not wait for the per-bin launch.
+    // ERASOR_HIP_OVERLAP: 1 = always, 0 = never, unset = the handle decides (overlap_wanted).
+    // (decided BEFORE the map chain: a step that does not write the reserved layout must not take passes launched ahead on the assumption
+    // that it would -- their VoI-order source indices count reserved slots, which only the reserved write-back converts; ADVICE r05)
+    bool reserved = false;
+    bool have_pose = false;  // the NEXT node's pose, if it was announced with it (erasor_hip_prefetch_node)
+    double nx = 0, ny = 0;
+    // reserved: a reverted bin whose points may lie outside the NEXT VoI circle reserves places in the outskirts' order as well (beyond
+    // this distance from the pose; -1: without the next pose, every bin does)
+    double leave_lim = -1.0;
+    float4 *Fnew = nullptr;   // the region this step writes, and its late table
+    LateEnt *late_out = nullptr;
+    // ---- written by enqueue_map_chain
+    bool use_ov = false;       // this step's split .. bucket table were launched ahead of it and are taken (round 5, OVERLAPPED steps)
+    bool stats_ahead = false;  // ... its scatter and bin statistics too
+    uint32_t nbk = 0;          // buckets of the map's counting sort: the bins + the complement (+ the dead bucket of an overlapped step)
+    int bits = 0;
+    const uint32_t *sm_keys = nullptr;  // the sorted VoI keys
+    // ---- written by step_next_overlap
+    // round 5, OVERLAPPED steps: with the next node announced together with BOTH its transforms (erasor_hip_prefetch_node +
+    // erasor_hip_announce_origin2body) its split, chunk scan and gather run beside this step's per-bin launch, on the early stream
+    bool ov_next = false;
+    int nxt_side = -1;
+};
+
+// "Is this the announced scan?", the cheap half: pointer, size, T_lidar2body, record layout.  (For a host scan the hash of every record of
+// the caller's buffer against the hash of the copy that was staged comes on top: only taken when this has passed, see step_admit)
+struct ScanId {
+    const void *src;
+    size_t n;
+    bool dev;
+    const float *Tl;
+    RowFmt fmt;
+};
+static bool same_scan(const ScanId &a, const ScanId &b) {
+    return a.src == b.src && a.n == b.n && a.dev == b.dev && memcmp(a.Tl, b.Tl, 16 * sizeof(float)) == 0 && a.fmt.stride == b.fmt.stride &&
+           a.fmt.ioff == b.fmt.ioff;
+}
+static ScanId scan_id(const QSide &c) { return ScanId{c.src, c.src_n, c.src_dev, c.Tl, c.fmt}; }
+
+// Stage 1, admit: argument checks, the ticket, this scan's query chain -- already in flight (erasor_hip_prefetch_scan), or enqueued now:
+// first, it is the long one --, the query side of the step
+static int step_admit(erasor_hip_handle *h, StepPlan &pl) {
     if (h->fly.active) {
         h->err = "erasor_hip_step_async: the previous step has not been collected (erasor_hip_step_wait)";
         return ERASOR_E_STATE;
@@ -2025,12 +2182,14 @@ static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_sca
                              : "erasor_hip_step before erasor_hip_set_map";
         return ERASOR_E_STATE;
     }
-    if (!ticket && (!T_l2b || (!scan_src && n_scan) || n_scan > 0x3FFFFFFFull)) return ERASOR_E_INVALID;
-    if (!T_b2o || !T_o2b || (src_is_device && (fmt.stride != 16 || fmt.ioff != 12)) || fmt.stride < 16 || fmt.ioff < 12 || fmt.ioff + 4 > fmt.stride)
+    const uint64_t ticket = pl.ticket;
+    const int flags = pl.flags;
+    if (!ticket && (!pl.T_l2b || (!pl.scan_src && pl.n_scan) || pl.n_scan > 0x3FFFFFFFull)) return ERASOR_E_INVALID;
+    if (!pl.T_b2o || !pl.T_o2b || (pl.src_is_device && (pl.fmt.stride != 16 || pl.fmt.ioff != 12)) || pl.fmt.stride < 16 || pl.fmt.ioff < 12 ||
+        pl.fmt.ioff + 4 > pl.fmt.stride)
         return ERASOR_E_INVALID;
     HIPC(h, hipSetDevice(h->device));
     prof_collect(h);
-    float Tl_ticket[16];
     if (ticket) {
         // the announced scan, by ticket: still only announced (the first node of a sequence) -> its chain starts now
         if (h->npend == 0 && h->ann.valid && h->ann.ticket == ticket) {
@@ -2042,87 +2201,85 @@ static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_sca
             return ERASOR_E_STATE;
         }
         const QSide &c = h->q[h->pend[0]];
-        memcpy(Tl_ticket, c.Tl, sizeof(Tl_ticket));
-        T_l2b = Tl_ticket;
-        n_scan = c.src_n;
-        src_is_device = c.src_dev;
+        memcpy(pl.Tl_ticket, c.Tl, sizeof(pl.Tl_ticket));
+        pl.T_l2b = pl.Tl_ticket;
+        pl.n_scan = c.src_n;
+        pl.src_is_device = c.src_dev;
         // (a host scan lives on in the side's pinned staging copy: that is what a step that has to run again reads)
-        scan_src = c.src_dev ? c.src : (const void *)c.stage;
-        fmt = RowFmt();
+        pl.scan_src = c.src_dev ? c.src : (const void *)c.stage;
+        pl.fmt = RowFmt();
     }
-    const auto t_host0 = std::chrono::steady_clock::now();
     static const bool host_timing = getenv("ERASOR_HIP_HOST_TIMING") != nullptr;
-    std::vector<std::pair<const char *, double>> marks;
-    auto MARK = [&](const char *what) {
-        if (host_timing) marks.emplace_back(what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_host0).count());
-    };
-    const uint32_t ns = (uint32_t)n_scan;
-    const bool prevox = (flags & STEP_QUERY_PREVOXELIZED) != 0;
+    pl.MARK.t0 = std::chrono::steady_clock::now();
+    pl.MARK.on = host_timing;
+    pl.ns = (uint32_t)pl.n_scan;
+    pl.prevox = (flags & STEP_QUERY_PREVOXELIZED) != 0;
+    const bool dev = pl.src_is_device;
     int rc = 0;
-    // ---- this scan's query chain: already in flight (erasor_hip_prefetch_scan), or enqueued now -- first, it is the long one ----
-    {
-        int side = -1;
-        // (recognition WITHOUT a ticket: pointer, size, T_lidar2body -- and, for a host scan, the hash of every record of the caller's
-        // buffer against the hash of the copy that was staged: only taken when the cheap tests have passed)
-        const bool ann_cand = !ticket && !(flags & STEP_RETRIED) && h->npend == 0 && h->ann.valid && !prevox && h->ann.src == scan_src && h->ann.n == n_scan &&
-                              h->ann.is_device == src_is_device && memcmp(h->ann.Tl, T_l2b, sizeof(h->ann.Tl)) == 0 &&
-                              h->ann.fmt.stride == fmt.stride && h->ann.fmt.ioff == fmt.ioff;
-        const bool pend_cand = !ticket && !(flags & STEP_RETRIED) && h->npend > 0 && !prevox && h->q[h->pend[0]].src == scan_src && h->q[h->pend[0]].src_n == n_scan &&
-                               h->q[h->pend[0]].src_dev == src_is_device && memcmp(h->q[h->pend[0]].Tl, T_l2b, sizeof(h->q[0].Tl)) == 0 &&
-                               h->q[h->pend[0]].fmt.stride == fmt.stride && h->q[h->pend[0]].fmt.ioff == fmt.ioff;
-        const uint64_t fp_now = (!src_is_device && (ann_cand || pend_cand)) ? scan_fingerprint(scan_src, n_scan, fmt) : 0ull;
-        if (ann_cand && !src_is_device && !h->ann.fp_valid) {  // (the announced copy is hashed now that somebody asks)
-            h->ann.fp = staged_fingerprint(h->q[h->ann.side], h->ann.n);
-            h->ann.fp_valid = true;
-        }
-        if (ann_cand && (src_is_device || h->ann.fp == fp_now)) {
-            rc = flush_announced(h);  // announced, not yet started (first scan of a sequence): start it now, it is ours
-            if (rc) return rc;
-        }
-        if (flags & STEP_RETRIED) {
-            // the step runs again in the other VoxelGrid mode (step_collect): the nodes announced behind it are NOT this scan and are not
-            // dropped -- a ticket has no caller buffer to come back with --; their chains (which ran in the old mode) go again below
-        } else if (h->npend > 0) {
-            QSide &c = h->q[h->pend[0]];
-            if (ticket || (!prevox && c.src == scan_src && c.src_n == n_scan && c.src_dev == src_is_device &&
-                           (src_is_device || (pend_cand && staged_fingerprint(c, c.src_n) == fp_now)) &&
-                           memcmp(c.Tl, T_l2b, sizeof(c.Tl)) == 0 && c.fmt.stride == fmt.stride && c.fmt.ioff == fmt.ioff)) {
-                side = h->pend[0];
-                for (int j = 1; j < h->npend; ++j) h->pend[j - 1] = h->pend[j];
-                --h->npend;
-            } else {
-                // not the scan that was announced: the prefetched chains are dropped.  Let them run out before going on, so
-                // that a device-resident scan they read in place may be released once this call has returned
-                q_drain(h);
-            }
-        }
-        if (side < 0) {
-            // (an announcement that is not this scan is the NEXT scan: it keeps the side it was staged into)
-            side = pick_side(h);
-            rc = enqueue_query_chain(h, side, scan_src, ns, src_is_device, T_l2b, prevox, 0, h->q_passthrough && !prevox, fmt);
-            if (rc) return rc;
-        }
-        if (flags & STEP_RETRIED)
-            for (int j = 0; j < h->npend; ++j) {  // (in announcement order, behind this step's own chain; a host scan still lies in q.scan)
-                QSide &c = h->q[h->pend[j]];
-                rc = enqueue_query_chain(h, h->pend[j], c.src, (uint32_t)c.src_n, c.src_dev, c.Tl, false, 2, h->q_passthrough, c.fmt);
-                if (rc) return rc;
-            }
-        h->qi = side;
-        h->step_side = side;
-        rc = chain_wait(h, side);  // (the chain's events are waited for below: they must have been recorded)
+    int side = -1;
+    // recognition WITHOUT a ticket: same_scan -- and, for a host scan, the fingerprints: only taken when the cheap tests have passed
+    const bool by_value = !ticket && !(flags & STEP_RETRIED) && !pl.prevox;
+    const ScanId me{pl.scan_src, pl.n_scan, dev, pl.T_l2b, pl.fmt};
+    const bool ann_cand = by_value && h->npend == 0 && h->ann.valid && same_scan(ScanId{h->ann.src, h->ann.n, h->ann.is_device, h->ann.Tl, h->ann.fmt}, me);
+    const bool pend_cand = by_value && h->npend > 0 && same_scan(scan_id(h->q[h->pend[0]]), me);
+    const uint64_t fp_now = (!dev && (ann_cand || pend_cand)) ? scan_fingerprint(pl.scan_src, pl.n_scan, pl.fmt) : 0ull;
+    if (ann_cand && !dev && !h->ann.fp_valid) {  // (the announced copy is hashed now that somebody asks)
+        h->ann.fp = staged_fingerprint(h->q[h->ann.side], h->ann.n);
+        h->ann.fp_valid = true;
+    }
+    if (ann_cand && (dev || h->ann.fp == fp_now)) {
+        rc = flush_announced(h);  // announced, not yet started (first scan of a sequence): start it now, it is ours
         if (rc) return rc;
     }
-    MARK("query chain");
-    h->Tl2b = to_xf(T_l2b);
-    h->Tb2o = to_xf(T_b2o);
-    h->To2b = to_xf(T_o2b);
-    const double xc = (double)T_b2o[3], yc = (double)T_b2o[7];  // OMU.cpp:246-247
+    if (flags & STEP_RETRIED) {
+        // the step runs again in the other VoxelGrid mode (step_collect): the nodes announced behind it are NOT this scan and are not
+        // dropped -- a ticket has no caller buffer to come back with --; their chains (which ran in the old mode) go again below
+    } else if (h->npend > 0) {
+        QSide &c = h->q[h->pend[0]];
+        if (ticket || (by_value && same_scan(scan_id(c), me) && (dev || (pend_cand && staged_fingerprint(c, c.src_n) == fp_now)))) {
+            side = h->pend[0];
+            for (int j = 1; j < h->npend; ++j) h->pend[j - 1] = h->pend[j];
+            --h->npend;
+        } else {
+            // not the scan that was announced: the prefetched chains are dropped.  Let them run out before going on, so
+            // that a device-resident scan they read in place may be released once this call has returned
+            q_drain(h);
+        }
+    }
+    if (side < 0) {
+        // (an announcement that is not this scan is the NEXT scan: it keeps the side it was staged into)
+        side = pick_side(h);
+        rc = enqueue_query_chain(h, side, pl.scan_src, pl.ns, dev, pl.T_l2b, pl.prevox, 0, h->q_passthrough && !pl.prevox, pl.fmt);
+        if (rc) return rc;
+    }
+    if (flags & STEP_RETRIED)
+        for (int j = 0; j < h->npend; ++j) {  // (in announcement order, behind this step's own chain; a host scan still lies in q.scan)
+            QSide &c = h->q[h->pend[j]];
+            rc = enqueue_query_chain(h, h->pend[j], c.src, (uint32_t)c.src_n, c.src_dev, c.Tl, false, 2, h->q_passthrough, c.fmt);
+            if (rc) return rc;
+        }
+    h->qi = side;
+    h->step_side = side;
+    rc = chain_wait(h, side);  // (the chain's events are waited for below: they must have been recorded)
+    if (rc) return rc;
+    pl.MARK("query chain");
+    return ERASOR_OK;
+}
+
+// Stage 2, plan and reserve: the sets change places, the store makes room, then the sizes, the scratch and every path decision
+static int step_plan_reserve(erasor_hip_handle *h, StepPlan &pl) {
+    const int flags = pl.flags;
+    const uint32_t ns = pl.ns;
+    int rc = 0;
+    h->Tl2b = to_xf(pl.T_l2b);
+    h->Tb2o = to_xf(pl.T_b2o);
+    h->To2b = to_xf(pl.T_o2b);
+    const double xc = pl.xc = (double)pl.T_b2o[3], yc = pl.yc = (double)pl.T_b2o[7];  // OMU.cpp:246-247
     swap_sides(h);  // (whatever was launched ahead of this step wrote into the other set: it is this step's now)
-    DevState *ds = h->d_st.p;
-    Counters *dc = h->d_ctr.p;
+    pl.ds = h->cset.d_st.p;
+    pl.dc = h->cset.d_ctr.p;
     const DP &P = h->dp;
-    const uint32_t B = h->B;
+    const uint32_t B = pl.B = h->B;
 
     if (h->P.is_large_scale) {  // OMU.cpp:249-251
         rc = reassign_submap(h, xc, yc);
@@ -2133,8 +2290,8 @@ static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_sca
         rc = rebuild_outskirts(h, h->nF + CHUNK);
         if (rc) return rc;
     }
-    const uint64_t n_map_in = (uint64_t)h->nFv + h->o_valid;
-    const uint64_t n_voi_room = (uint64_t)h->nF + h->o_valid;  // entries of the VoI-order arrays: reserved slots keep places too (round 5)
+    pl.n_map_in = (uint64_t)h->nFv + h->o_valid;
+    const uint64_t n_voi_room = pl.n_voi_room = (uint64_t)h->nF + h->o_valid;
     if (n_voi_room + ns + 64 > h->capV) {
         // the reference's map_arranged_ simply grows (scan points enter every reverted bin, erasor.cpp:512; v2 merges whole
         // query bins, erasor.cpp:296-307): enlarge the map-sized scratch between steps (it carries no state across steps)
@@ -2144,20 +2301,23 @@ static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_sca
     h->st.nF = h->nF;  // the host's mirror of the device state rides along as a kernel argument of k_chunk_scan_top
     h->st.nF_valid = h->nFv;
     h->st.o_begin = h->o_begin;
-    const bool mb_count = B + 1 <= QB_NB_MAX;  // the map's bucketing as a one-digit counting sort (else: LSD radix passes)
+    pl.mb_count = B + 1 <= QB_NB_MAX;
     // (state push, counters and tallies are reset by k_chunk_scan_top, the first launch of the step that needs them)
 
-    MARK("prologue");
+    pl.MARK("prologue");
     // ---- sizes, scratch ----
-    const double voi_r2 = (flags & STEP_VOI_EVERYTHING) ? HUGE_VAL : P.voi_r2;
-    const uint32_t nFchunks = cdiv(h->nF, CHUNK);
-    const uint32_t o_chunk0 = h->o_begin / CHUNK;
-    const uint32_t nOchunks = h->capO / CHUNK - o_chunk0;
-    const uint32_t nchunks = nFchunks + nOchunks;
+    pl.voi_r2 = (flags & STEP_VOI_EVERYTHING) ? HUGE_VAL : P.voi_r2;
+    Extents &e = pl.ext;
+    e.nF = h->nF;
+    e.nFchunks = cdiv(h->nF, CHUNK);
+    e.o_begin = h->o_begin;
+    e.o_chunk0 = h->o_begin / CHUNK;
+    e.nOchunks = h->capO / CHUNK - e.o_chunk0;
+    e.nchunks = e.nFchunks + e.nOchunks;
     // (the masks and chunk counts also hold the NEXT step's split when it is launched ahead: its F region may be longer by
     // this step's VoI + scan, its outskirts region may begin up to nF entries earlier)
     // (round 5: in the reserved layout the next region may be as long as 4 x this step's VoI + 2 x its scan)
-    const size_t chunks_room = (size_t)nchunks + cdiv(4 * n_voi_room + 2 * (uint64_t)ns + 64, CHUNK) + cdiv(h->nF, CHUNK) + 8;
+    const size_t chunks_room = (size_t)e.nchunks + cdiv(4 * n_voi_room + 2 * (uint64_t)ns + 64, CHUNK) + cdiv(h->nF, CHUNK) + 8;
     if (chunks_room * CHUNK_TILES + 8 > h->vmask.cap || chunks_room * CHUNK_TILES + 8 > h->hmask.cap || chunks_room + 8 > h->cinfo.cap)
         h->spec.valid = false;  // (re-allocated below: a pass launched ahead wrote into the old buffers)
     if (ensure(h, h->lmask, chunks_room * CHUNK_TILES + 8)) return ERASOR_E_NO_DEVICE;
@@ -2167,9 +2327,9 @@ static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_sca
         return ERASOR_E_NO_DEVICE;
     // No mid-step read-back: everything is launched on upper-bound grids and reads the actual counts
     // (st->voi_total, st->q_nvox) from device memory.  n_voi <= logical map size, nq <= n_scan.
-    const uint32_t n_voi = (uint32_t)std::min<uint64_t>(n_voi_room, 0xFFFFFFF0ull), nq = ns;  // upper bounds from here on
-    const uint32_t *nvoi_dev = &ds->voi_total;
-    rc = alloc_step(h, n_voi, nq);
+    const uint32_t n_voi = pl.n_voi = (uint32_t)std::min<uint64_t>(n_voi_room, 0xFFFFFFF0ull);
+    pl.nq = ns;
+    rc = alloc_step(h, n_voi, pl.nq);
     if (rc) return rc;
     if (B + 1 <= QB_NB_MAX) {  // [tiles][B + 1] table of the map's counting sort (round 5: B + 2 with the dead bucket of an overlapped step)
         // (rows for every tile the VoI-order arrays can hold: the NEXT step's table is filled ahead, and its VoI order keeps places for
@@ -2179,414 +2339,293 @@ static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_sca
         const uint32_t nb_m = 256u * std::max(1u, cdiv(n_voi, RTILE));
         if (ensure(h, h->hist2, nb_m) || ensure(h, h->hist2_l, nb_m) || ensure(h, h->hist2_t, cdiv(nb_m, 1024) + 2)) return ERASOR_E_NO_DEVICE;
     }
-    const uint32_t *sm_keys = nullptr, *sm_perm = nullptr;
-    // v3: the Scan Ratio Test's first pass rides along with the map's bin statistics (k_bin_stats_srt)
-    const bool st1_ahead = P.version == 3 && B <= 1024 * SRT_KPT;
-    // up to 4096 bins the output layout has no launch of its own: k_srt4 prepares what does not depend on R-GPF, every workgroup of
-    // the write-back finishes it (beyond that, and under per-launch profiling: k_layout4 / k_layout)
-    const bool fold = B <= 1024 * SRT_KPT && n_voi > 0;
-    // round 4: v3's second pass is the LAST WORKGROUP of the per-bin launch (k_revert_bins_srt): the revert decision is local to a bin, so
-    // the per-bin workgroups find their bins themselves and nothing on the chain waits for k_srt4
-    const bool srt_in_revert = st1_ahead && h->prof != 1;
-    // round 5: the RESERVED layout (srt4_body): the write-back of everything but the reverted bins does not wait for the per-bin launch.
-    // ERASOR_HIP_OVERLAP: 1 = always, 0 = never, unset = the handle decides (overlap_pays).
+    pl.st1_ahead = P.version == 3 && B <= 1024 * SRT_KPT;
+    pl.fold = B <= 1024 * SRT_KPT && n_voi > 0;
+    pl.srt_in_revert = pl.st1_ahead && h->prof != 1;
     const int announced_beyond = h->npend + (h->ann.valid ? 1 : 0);  // nodes announced behind this step's own
     const bool overlap_pays = overlap_wanted(h, announced_beyond);
     h->fly.deep = announced_beyond >= h->batch_lead;
-    // (decided BEFORE the map chain: a step that does not write the reserved layout must not take passes launched ahead on the assumption
-    // that it would -- their VoI-order source indices count reserved slots, which only the reserved write-back converts; ADVICE r05)
-    const bool reserved = srt_in_revert && fold && mb_count && !flags && overlap_pays && early_stream(h);
-    bool use_ov = false;   // this step's split .. bucket table were launched ahead of it and are taken (round 5, OVERLAPPED steps)
-    bool stats_ahead = false;  // ... its scatter and bin statistics too
-    uint32_t nbk = B + 1;  // buckets of the map's counting sort: the bins + the complement (+ the dead bucket of an overlapped step)
-    int bits = key_bits(B + 1);
-
-    // ---- map chain (the query chains run on their own streams; the two only meet at the Scan Ratio Test) ----
-    auto enqueue_map_chain = [&]() {
-        MARK("  mapchain_begin");
-        // With the query chains on streams of their own, the map chain simply opens the step on the main stream
-        // (no fork / join events, one hardware queue less).
-        h->cur = h->stream;
-        h->bank = 1;
-        {   // round 5: split, chunk scan, gather and the bucket table may all be there already -- launched beside the previous step's per-bin
-            // launch (h->ov) -- if this step is exactly the step that was assumed then: node, pose, transform, store, buffers, room
-            const bool ov_launched = h->ov.valid;
-            use_ov = ov_launched && reserved && !flags && mb_count && h->ov.seq == h->step_seq && h->ov.epoch == h->store_epoch && h->ov.curF == h->curF &&
-                     h->ov.qside == h->qi && h->ov.x == xc && h->ov.y == yc && memcmp(h->ov.To, T_o2b, sizeof(h->ov.To)) == 0 &&
-                     nchunks <= h->ov.cap_chunks && n_voi_room + 64 <= h->ov.cap_voi && h->ov.vmask == (const void *)h->vmask.p &&
-                     h->ov.hmask == (const void *)h->hmask.p && h->ov.lmask == (const void *)h->lmask.p && h->ov.cinfo == (const void *)h->cinfo.p &&
-                     h->ov.pvl == (const void *)h->pvl.p && h->ov.phl == (const void *)h->phl.p && h->ov.voi_ego == (const void *)h->voi_ego.p &&
-                     h->ov.mb_hist == (const void *)h->mb_hist.p;
-            if (ov_launched && !use_ov && getenv("ERASOR_HIP_CHAIN_STAMPS"))
-                fprintf(stderr, "[overlap passes not taken] flags %d seq %d epoch %d curF %d qside %d pose %d To %d chunks %u/%u voi %llu/%u ptrs %d%d%d%d%d%d%d%d\n", flags,
-                        (int)(h->ov.seq == h->step_seq), (int)(h->ov.epoch == h->store_epoch), (int)(h->ov.curF == h->curF), (int)(h->ov.qside == h->qi),
-                        (int)(h->ov.x == xc && h->ov.y == yc), (int)(memcmp(h->ov.To, T_o2b, sizeof(h->ov.To)) == 0), nchunks, h->ov.cap_chunks,
-                        (unsigned long long)n_voi_room + 64, h->ov.cap_voi, (int)(h->ov.vmask == (const void *)h->vmask.p), (int)(h->ov.hmask == (const void *)h->hmask.p),
-                        (int)(h->ov.lmask == (const void *)h->lmask.p), (int)(h->ov.cinfo == (const void *)h->cinfo.p), (int)(h->ov.pvl == (const void *)h->pvl.p),
-                        (int)(h->ov.phl == (const void *)h->phl.p), (int)(h->ov.voi_ego == (const void *)h->voi_ego.p), (int)(h->ov.mb_hist == (const void *)h->mb_hist.p));
-            h->ov.valid = false;
-            stats_ahead = use_ov && h->ov.stats_done && st1_ahead;
-            if (ov_launched && !use_ov) (void)hipStreamWaitEvent(h->stream, h->ev_early, 0);  // (those passes write what this step's own will)
-            if (use_ov) {
-                ++h->n_ov_used;
-                ++h->n_spec_used;
-                h->spec.valid = false;
-                nbk = h->ov.nbk;
-                bits = key_bits(nbk);
-                h->last_scan_path = 4 + h->ov.scan_levels;
-            }
-        }
-        if (!use_ov) {   // VoI split (OMU.cpp:254 fetch_VoI membership)
-            // ... unless it is already there: launched ahead by the previous step for exactly this pose and this store
-            const bool use_spec = h->spec.valid && !flags && h->spec.seq == h->step_seq && h->spec.epoch == h->store_epoch &&
-                                  h->spec.curF == h->curF && h->spec.x == xc && h->spec.y == yc && nchunks <= h->spec.cap_chunks &&
-                                  h->spec.vmask == (const void *)h->vmask.p && h->spec.hmask == (const void *)h->hmask.p &&
-                                  h->spec.cinfo == (const void *)h->cinfo.p;
-            const bool scan_done = use_spec && h->spec.scan && nchunks <= h->spec.scan_cap && h->spec.pvl == (const void *)h->pvl.p &&
-                                   h->spec.phl == (const void *)h->phl.p;
-            h->spec.valid = false;
-            h->spec.scan = false;
-            if (use_spec) ++h->n_spec_used;
-            else
-                launch_voi_split(h, (const float4 *)h->F[h->curF].p, h->nF, nFchunks, h->o_begin, o_chunk0, nOchunks, nchunks, xc, yc, voi_r2,
-                                 (const DevState *)nullptr, 0u);
-            const uint32_t ntop = std::max(1u, cdiv(nchunks, 1024));
-            if (scan_done) {
-                // (launched ahead behind the split, see launch_split_ahead)
-                h->last_scan_path = 2 + h->spec.scan_levels;
-            } else if (nchunks <= h->scan_one_max) {
-                h->last_scan_path = 1;
-                LAUNCH(h, "chunk_scan", k_chunk_scan_one, 1, 1024, (const uint32_t *)h->cinfo.p, nchunks, h->pvl.p, h->phl.p, h->topv.p, h->toph.p, ntop,
-                       nFchunks, ds, dc, h->st, h->lab_slots.p, mb_count ? h->mb_tot.p : (uint32_t *)nullptr, mb_count ? B + 2 : 0u,
-                       h->use_ometa ? h->ometa.p : (OMeta *)nullptr, 0u, 0u, (const DevState *)nullptr, 0u);
-            } else {
-                h->last_scan_path = 2;
-                LAUNCH(h, "chunk_scan", k_chunk_scan_local, ntop, 256, (const uint32_t *)h->cinfo.p, nchunks, h->pvl.p, h->phl.p, h->topv.p, h->toph.p,
-                       h->topr.p, (const DevState *)nullptr, 0u, 0u, 0u);
-                LAUNCH(h, "chunk_scan", k_chunk_scan_top, 1, 1024, h->topv.p, h->toph.p, ntop, (const uint32_t *)h->pvl.p, (const uint32_t *)h->phl.p,
-                       nchunks, nFchunks, ds, dc, h->st, h->lab_slots.p, mb_count ? h->mb_tot.p : (uint32_t *)nullptr, mb_count ? B + 2 : 0u,
-                       (const uint32_t *)h->topr.p, h->use_ometa ? h->ometa.p : (OMeta *)nullptr, 0u, 0u, (const DevState *)nullptr, 0u);
-            }
-        }
-        if (!use_ov) (void)hipStreamWaitEvent(h->stream, Q(h).ev_keys, 0);  // k_voi_gather must see the query side's error flag
-        if (!use_ov) {   // VoI gather + egocentric transform + R-POD key (OMU.cpp:435-437; erasor.cpp:124-139)
-            // one wavefront per work item: GATHER_SUB pieces per chunk of the VoI-resident region, one per outskirts chunk
-            const uint32_t grid = std::max(1u, std::min<uint32_t>(cdiv(nFchunks * GATHER_SUB + nOchunks, 4), 256 * 16));
-            LAUNCH(h, "voi_gather", k_voi_gather, grid, 256, (const float4 *)h->F[h->curF].p, h->nF, nFchunks, h->Oxy.p, h->Ozi.p, o_chunk0,
-                   nOchunks, (const unsigned long long *)h->vmask.p, (const unsigned long long *)h->hmask.p, (const uint32_t *)h->cinfo.p,
-                   (const uint32_t *)h->pvl.p, (const uint32_t *)h->phl.p, (const uint32_t *)h->topv.p, (const uint32_t *)h->toph.p, h->To2b, P, ds,
-                   dc, (const Counters *)Q(h).d_qctr.p, h->voi_ego.p, h->voi_key.p, h->voi_src.p, h->use_ometa ? h->ometa.p : (OMeta *)nullptr,
-                   (const unsigned long long *)nullptr, 0u);
-        }
-        if (mb_count) {
-            // the table is sized for the whole map (n_voi is an upper bound), the GRIDS for 1.5 x the previous step's VoI: the
-            // kernels walk the tiles with a grid stride, so an under-estimate only costs a second round
-            const uint32_t ntile_tab = std::max(1u, cdiv(n_voi, MB_TILE));
-            const uint32_t ntile_ub = h->last_n_voi ? std::min(ntile_tab, std::max(64u, cdiv((uint64_t)h->last_n_voi * 3 / 2, MB_TILE))) : ntile_tab;
-            if (!use_ov) {  // (an overlapped step: both launched ahead, behind k_late_gather)
-                LAUNCH(h, "voi_bucket", k_mb_hist, ntile_ub, 1024, (const uint32_t *)h->voi_key.p, n_voi, nvoi_dev, nbk, h->mb_hist.p, h->mb_tot.p);
-                LAUNCH(h, "voi_bucket", k_mb_colscan, cdiv(nbk, MB_PAD), 256, h->mb_hist.p, n_voi, nvoi_dev, nbk, (const uint32_t *)h->mb_tot.p, h->moff.p);
-            }
-            if (use_ov && stats_ahead) {
-                // (scatter, statistics and first Scan Ratio Test pass were launched ahead as well)
-            } else if (nbk <= MBW_NB_SMALL)
-                LAUNCH(h, "voi_bucket", k_mb_scatter_w<MBW_NB_SMALL>, ntile_ub, 1024, (const uint32_t *)h->voi_key.p, (const float4 *)h->voi_ego.p,
-                       (const uint32_t *)h->voi_src.p, n_voi, nvoi_dev, nbk, bits, (const uint32_t *)h->mb_hist.p, h->spts.p, h->ssrc.p, h->rk_a.p,
-                       h->dbg_stamps.p);
-            else if (nbk <= MBW_NB_MAX)
-                LAUNCH(h, "voi_bucket", k_mb_scatter_w<MBW_NB_MAX>, ntile_ub, 1024, (const uint32_t *)h->voi_key.p, (const float4 *)h->voi_ego.p,
-                       (const uint32_t *)h->voi_src.p, n_voi, nvoi_dev, nbk, bits, (const uint32_t *)h->mb_hist.p, h->spts.p, h->ssrc.p, h->rk_a.p,
-                       h->dbg_stamps.p);
-            else
-                LAUNCH(h, "voi_bucket", k_mb_scatter, ntile_ub, 1024, (const uint32_t *)h->voi_key.p, (const float4 *)h->voi_ego.p,
-                       (const uint32_t *)h->voi_src.p, n_voi, nvoi_dev, nbk, bits, (const uint32_t *)h->mb_hist.p, h->spts.p, h->ssrc.p, h->rk_a.p);
-            sm_keys = h->rk_a.p;
-        } else {
-            radix_sort(h, h->voi_key.p, n_voi, nvoi_dev, bits, h->rk_a.p, h->rk_b.p, h->rv_a.p, h->rv_b.p, &sm_keys, &sm_perm, "voi_bucket");
-            if (n_voi) LAUNCH(h, "voi_bucket", k_gather, cdiv(n_voi, 256), 256, (const float4 *)h->voi_ego.p, (const uint32_t *)h->voi_src.p, sm_perm,
-                              n_voi, nvoi_dev, h->spts.p, h->ssrc.p);
-            LAUNCH(h, "voi_bucket", k_bin_offsets, cdiv((uint64_t)std::max(n_voi, B + 2) + 1, 256), 256, sm_keys, n_voi, nvoi_dev, B + 1, h->moff.p);
-        }
-        // v3: the Scan Ratio Test's first pass rides along, bin by bin (the query's statistics are needed: the join with its chain
-        // comes before this launch instead of after it; with nodes announced ahead the chain finished long ago)
-        if (use_ov && stats_ahead) {
-            // (done)
-        } else if (st1_ahead) {
-            (void)hipStreamWaitEvent(h->stream, Q(h).ev_done, 0);
-            LAUNCH(h, "bin_stats", k_bin_stats_srt, cdiv((uint64_t)B * 64, 256), 256, P, (const float4 *)h->spts.p, (const uint32_t *)h->moff.p, B, h->mcnt.p,
-                   h->mmin.p, h->mmax.p, (const uint32_t *)Q(h).ccnt.p, (const float *)Q(h).cmin.p, (const float *)Q(h).cmax.p, h->st1b.p);
-        } else
-        LAUNCH(h, "bin_stats", k_bin_stats, cdiv((uint64_t)B * 64, 256), 256, (const float4 *)h->spts.p, (const uint32_t *)h->moff.p, B, h->mcnt.p,
-               h->mmin.p, h->mmax.p);
-        if (use_ov) {
-            // the entering outskirts entries are erased NOW that the step is certain (k_voi_gather left them: a getter could still ask
-            // for the store as the previous step left it); on the early stream, in front of the next pass over the store (enqueued
-            // behind the launches the main stream was waiting for)
-            h->cur = h->bstream;
-            LAUNCH(h, "voi_gather", k_o_commit, std::max(1u, std::min<uint32_t>(cdiv(nOchunks, 4), 2048)), 256, h->Oxy.p,
-                   (const unsigned long long *)h->vmask.p, (const uint32_t *)h->cinfo.p, (const DevState *)ds, h->capO / CHUNK,
-                   h->use_ometa ? h->ometa.p : (OMeta *)nullptr, (const Counters *)dc, (const Counters *)Q(h).d_qctr.p);
-        }
-        MARK("  mapchain_end");
-        h->cur = h->stream;
-        h->bank = 0;
-    };
-
-    enqueue_map_chain();
-    MARK("map chain");
-    HIPC(h, hipStreamWaitEvent(h->stream, Q(h).ev_done, 0));  // join: the query's bins are ready
-
-    // ---- Scan Ratio Test, R-GPF, per-bin voxelisation (erasor.cpp:332-571) ----
-    h->ov_mode = reserved;
-    bool have_pose = false;  // the NEXT node's pose, if it was announced with it (erasor_hip_prefetch_node)
-    double nx = 0, ny = 0;
+    pl.reserved = pl.srt_in_revert && pl.fold && pl.mb_count && !flags && overlap_pays && early_stream(h);
+    pl.nbk = B + 1;
+    pl.bits = key_bits(B + 1);
+    // the NEXT node, as announced so far (nothing is announced or started between here and step_next_overlap)
     if (h->npend > 0) {
         const QSide &nq_ = h->q[h->pend[0]];
-        have_pose = nq_.pose_valid;
-        nx = nq_.pose_x;
-        ny = nq_.pose_y;
+        pl.have_pose = nq_.pose_valid;
+        pl.nx = nq_.pose_x;
+        pl.ny = nq_.pose_y;
     } else if (h->ann.valid) {
-        have_pose = h->ann.pose_valid;
-        nx = h->ann.pose_x;
-        ny = h->ann.pose_y;
+        pl.have_pose = h->ann.pose_valid;
+        pl.nx = h->ann.pose_x;
+        pl.ny = h->ann.pose_y;
     }
-    float4 *Fnew = h->F[h->curF ^ 1].p;
-    LateEnt *late_out = h->late[h->late_idx ^ 1].p;
-    // round 5, OVERLAPPED steps: with the next node announced together with BOTH its transforms (erasor_hip_prefetch_node +
-    // erasor_hip_announce_origin2body) its split, chunk scan and gather run beside this step's per-bin launch, on the early stream
-    bool ov_next = false;
-    int nxt_side = -1;
-    if (reserved && have_pose && h->prof != 1 && !submap_would_move(h, nx, ny)) {
+    pl.Fnew = h->F[h->curF ^ 1].p;
+    pl.late_out = h->late[h->late_idx ^ 1].p;
+    if (pl.reserved) {
+#ifdef ERASOR_HIP_TEST_HOOKS
+        static const bool leave_all = getenv("ERASOR_HIP_LEAVE_ALL") != nullptr;  // (test hook: every reverted bin reserves places in the outskirts' order)
+#else
+        constexpr bool leave_all = false;
+#endif
+        pl.leave_lim = (pl.have_pose && !leave_all) ? sqrt(P.voi_r2) - hypot(pl.nx - xc, pl.ny - yc) - 0.05 : -1.0;
+    }
+    return ERASOR_OK;
+}
+
+// Which of the conditions under which passes launched ahead may be taken do NOT hold for this step (AH_* bits; every one is evaluated:
+// the step masks the ones that apply, the ERASOR_HIP_CHAIN_STAMPS diagnostic prints them)
+static unsigned ahead_mismatch(const erasor_hip_handle *h, const Ahead &a, const StepPlan &pl) {
+    unsigned m = 0;
+    m |= a.seq == h->step_seq ? 0u : AH_SEQ;
+    m |= a.epoch == h->store_epoch ? 0u : AH_EPOCH;
+    m |= a.curF == h->curF ? 0u : AH_CURF;
+    m |= a.qside == h->qi ? 0u : AH_QSIDE;
+    m |= a.x == pl.xc && a.y == pl.yc ? 0u : AH_POSE;
+    m |= memcmp(a.To, pl.T_o2b, sizeof(a.To)) == 0 ? 0u : AH_TO;
+    m |= pl.ext.nchunks <= a.cap_chunks ? 0u : AH_CHUNKS;
+    m |= pl.ext.nchunks <= a.scan.cap ? 0u : AH_SCAN_CAP;
+    m |= pl.n_voi_room + 64 <= a.cap_voi ? 0u : AH_VOI;
+    m |= a.vmask == (const void *)h->vmask.p ? 0u : AH_VMASK;
+    m |= a.hmask == (const void *)h->hmask.p ? 0u : AH_HMASK;
+    m |= a.lmask == (const void *)h->lmask.p ? 0u : AH_LMASK;
+    m |= a.cinfo == (const void *)h->cinfo.p ? 0u : AH_CINFO;
+    m |= a.scan.pvl == (const void *)h->pvl.p ? 0u : AH_PVL;
+    m |= a.scan.phl == (const void *)h->phl.p ? 0u : AH_PHL;
+    m |= a.voi_ego == (const void *)h->cset.voi_ego.p ? 0u : AH_VOI_EGO;
+    m |= a.mb_hist == (const void *)h->mb_hist.p ? 0u : AH_MB_HIST;
+    return m;
+}
+
+// Stage 3, the map chain: split, chunk scan, gather, bucketing, bin statistics (the query chains run on their own streams; the two only
+// meet at the Scan Ratio Test).  Decides use_ov / stats_ahead / nbk / bits; leaves sm_keys
+static void enqueue_map_chain(erasor_hip_handle *h, StepPlan &pl) {
+    const int flags = pl.flags;
+    const Extents &e = pl.ext;
+    const uint32_t B = pl.B, n_voi = pl.n_voi;
+    StepSet &cs = h->cset;
+    pl.MARK("  mapchain_begin");
+    // With the query chains on streams of their own, the map chain simply opens the step on the main stream
+    // (no fork / join events, one hardware queue less).
+    h->cur = h->stream;
+    h->bank = 1;
+    {   // round 5: split, chunk scan, gather and the bucket table may all be there already -- launched beside the previous step's per-bin
+        // launch (h->ov) -- if this step is exactly the step that was assumed then: node, pose, transform, store, buffers, room
+        const bool ov_launched = h->ov.valid;
+        const unsigned m = ahead_mismatch(h, h->ov, pl);
+        pl.use_ov = ov_launched && pl.reserved && !flags && pl.mb_count && !(m & AH_OVERLAP);
+        if (ov_launched && !pl.use_ov && getenv("ERASOR_HIP_CHAIN_STAMPS"))
+            fprintf(stderr, "[overlap passes not taken] flags %d seq %d epoch %d curF %d qside %d pose %d To %d chunks %u/%u voi %llu/%u ptrs %d%d%d%d%d%d%d%d\n", flags,
+                    !(m & AH_SEQ), !(m & AH_EPOCH), !(m & AH_CURF), !(m & AH_QSIDE), !(m & AH_POSE), !(m & AH_TO), e.nchunks, h->ov.cap_chunks,
+                    (unsigned long long)pl.n_voi_room + 64, h->ov.cap_voi, !(m & AH_VMASK), !(m & AH_HMASK), !(m & AH_LMASK), !(m & AH_CINFO), !(m & AH_PVL),
+                    !(m & AH_PHL), !(m & AH_VOI_EGO), !(m & AH_MB_HIST));
+        h->ov.valid = false;
+        pl.stats_ahead = pl.use_ov && h->ov.stats_done && pl.st1_ahead;
+        if (ov_launched && !pl.use_ov) (void)hipStreamWaitEvent(h->stream, h->ev_early, 0);  // (those passes write what this step's own will)
+        if (pl.use_ov) {
+            ++h->n_ov_used;
+            ++h->n_spec_used;
+            h->spec.valid = false;
+            pl.nbk = h->ov.nbk;
+            pl.bits = key_bits(pl.nbk);
+            h->last_scan_path = 4 + h->ov.scan.levels;
+        }
+    }
+    if (!pl.use_ov) {
+        // the split ... unless it is already there: launched ahead by the previous step for exactly this pose and this store
+        const unsigned m = ahead_mismatch(h, h->spec, pl);
+        const bool use_spec = h->spec.valid && !flags && !(m & AH_SPLIT);
+        const bool scan_done = use_spec && h->spec.scan.levels && !(m & AH_SCAN);  // (launched ahead behind the split, see launch_split_ahead)
+        h->spec.valid = false;
+        if (use_spec) ++h->n_spec_used;
+        else
+            launch_voi_split(h, (const float4 *)h->F[h->curF].p, e, e.nchunks, pl.xc, pl.yc, pl.voi_r2, 0u);
+        if (scan_done) h->last_scan_path = 2 + h->spec.scan.levels;
+        else
+            h->last_scan_path = launch_chunk_scan(h, cs, h->stream, e, 0u, 0u, 0u).levels;
+        h->spec.scan = ScanDone();
+        (void)hipStreamWaitEvent(h->stream, Q(h).ev_keys, 0);  // k_voi_gather must see the query side's error flag
+        launch_voi_gather(h, cs, h->stream, (const float4 *)h->F[h->curF].p, e, e.nFchunks * GATHER_SUB + e.nOchunks, h->To2b, Q(h), nullptr);
+    }
+    if (pl.mb_count) {
+        if (!pl.use_ov) launch_bucket_table(h, cs, h->stream, n_voi, pl.nbk);  // (an overlapped step: launched ahead, behind k_late_gather)
+        // (... and with stats_ahead the scatter, the statistics and the first Scan Ratio Test pass as well)
+        if (!pl.stats_ahead) launch_bucket_scatter(h, cs, h->stream, n_voi, pl.nbk, pl.bits);
+        pl.sm_keys = cs.rk_a.p;
+    } else {
+        const uint32_t *nvoi_dev = &pl.ds->voi_total, *sm_perm = nullptr;
+        radix_sort(h, cs.voi_key.p, n_voi, nvoi_dev, pl.bits, cs.rk_a.p, h->rk_b.p, h->rv_a.p, h->rv_b.p, &pl.sm_keys, &sm_perm, "voi_bucket");
+        if (n_voi) LAUNCH(h, "voi_bucket", k_gather, cdiv(n_voi, 256), 256, (const float4 *)cs.voi_ego.p, (const uint32_t *)cs.voi_src.p, sm_perm,
+                          n_voi, nvoi_dev, cs.spts.p, cs.ssrc.p);
+        LAUNCH(h, "voi_bucket", k_bin_offsets, cdiv((uint64_t)std::max(n_voi, B + 2) + 1, 256), 256, pl.sm_keys, n_voi, nvoi_dev, B + 1, cs.moff.p);
+    }
+    if (!pl.stats_ahead) launch_bin_stats(h, cs, h->stream, Q(h), pl.st1_ahead);
+    if (pl.use_ov) {
+        // the entering outskirts entries are erased NOW that the step is certain (k_voi_gather left them: a getter could still ask
+        // for the store as the previous step left it); on the early stream, in front of the next pass over the store (enqueued
+        // behind the launches the main stream was waiting for)
+        h->cur = h->bstream;
+        LAUNCH(h, "voi_gather", k_o_commit, std::max(1u, std::min<uint32_t>(cdiv(e.nOchunks, 4), 2048)), 256, h->Oxy.p,
+               (const unsigned long long *)h->vmask.p, (const uint32_t *)h->cinfo.p, (const DevState *)pl.ds, h->capO / CHUNK, ometa_or_null(h),
+               (const Counters *)pl.dc, (const Counters *)Q(h).d_qctr.p);
+    }
+    pl.MARK("  mapchain_end");
+    h->cur = h->stream;
+    h->bank = 0;
+}
+
+// Decides ov_next / nxt_side: may the next node's passes run beside this step's per-bin launch?  (Its chain goes into its queue NOW if it
+// was only just announced -- the gather ahead waits for the chain's error flag)
+static int step_next_overlap(erasor_hip_handle *h, StepPlan &pl) {
+    if (pl.reserved && pl.have_pose && h->prof != 1 && !submap_would_move(h, pl.nx, pl.ny)) {
         if (h->npend == 0 && h->ann.valid && h->ann.to_valid) {
-            // (only just announced: its chain goes into its queue NOW -- the gather ahead waits for the chain's error flag)
             const int keep_side = h->qi;
             const int rc_f = flush_announced(h);
             h->qi = keep_side;
             if (rc_f) return rc_f;
         }
         if (h->npend > 0 && h->q[h->pend[0]].pose_valid && h->q[h->pend[0]].to_valid) {
-            ov_next = true;
-            nxt_side = h->pend[0];
-            const int rc_w = chain_wait(h, nxt_side);  // (its ev_keys is waited for on the early stream)
+            pl.ov_next = true;
+            pl.nxt_side = h->pend[0];
+            const int rc_w = chain_wait(h, pl.nxt_side);  // (its ev_keys is waited for on the early stream)
             if (rc_w) return rc_w;
         }
     }
-    std::function<void()> enqueue_early;
-    if (getenv("ERASOR_HIP_CHAIN_STAMPS") && !ov_next)
+    if (getenv("ERASOR_HIP_CHAIN_STAMPS") && !pl.ov_next)
         fprintf(stderr, "[no overlap for the next step] reserved %d (srt_in_revert %d fold %d mb_count %d flags %d) have_pose %d prof %d npend %d ann %d/%d/%d pend0 %d/%d\n",
-                (int)reserved, (int)srt_in_revert, (int)fold, (int)mb_count, flags, (int)have_pose, h->prof, h->npend, (int)h->ann.valid, (int)h->ann.pose_valid,
-                (int)h->ann.to_valid, h->npend ? (int)h->q[h->pend[0]].pose_valid : -1, h->npend ? (int)h->q[h->pend[0]].to_valid : -1);
-    if (reserved) {
-        // a reverted bin whose points may lie outside the NEXT VoI circle reserves places in the outskirts' order as well: without the
-        // next pose, every bin does
-#ifdef ERASOR_HIP_TEST_HOOKS
-        static const bool leave_all = getenv("ERASOR_HIP_LEAVE_ALL") != nullptr;  // (test hook: every reverted bin reserves places in the outskirts' order)
-#else
-        constexpr bool leave_all = false;
-#endif
-        const double leave_lim = (have_pose && !leave_all) ? sqrt(P.voi_r2) - hypot(nx - xc, ny - yc) - 0.05 : -1.0;
-        // (enqueued BEHIND the per-bin launch, which the main stream is waiting for: see enqueue_early() below)
-        enqueue_early = [&, leave_lim]() {
-        MARK("srt: begin");
-        (void)hipStreamWaitEvent(h->bstream, h->ev_stats, 0);
-        MARK("  ev_stats record + wait");
-        h->cur = h->bstream;  // ---- the early stream: beside the per-bin launch
-        // (round 6: ONE launch -- every workgroup of the early write-back derives the reserved offsets it needs from the status bytes itself,
-        // the launch's last workgroup is k_srt4 for everything behind it: see k_assemble_early)
-        {
-            EarlyArgs ea;
-            ea.mcnt = h->mcnt.p;
-            ea.mmin = h->mmin.p;
-            ea.mmax = h->mmax.p;
-            ea.ccnt = Q(h).ccnt.p;
-            ea.cmin = Q(h).cmin.p;
-            ea.cmax = Q(h).cmax.p;
-            ea.st1 = h->st1.p;
-            ea.status = h->status.p;
-            ea.action = h->action.p;
-            ea.rev_idx = h->rev_idx.p;
-            ea.rev_list = h->rev_list.p;
-            ea.vox_off = h->vox_off.p;
-            ea.st = ds;
-            ea.out_off0 = h->out_off0.p;
-            ea.rev_before = h->rev_before.p;
-            ea.crej_off = h->crej_off.p;
-            ea.st1_in = h->st1b.p;
-            ea.moff = h->moff.p;
-            ea.qoff = Q(h).qoff.p;
-            ea.out_offR = h->out_offR.p;
-            ea.gres_off = h->gres_off.p;
-            ea.late = late_out;
-            ea.leave_lim = leave_lim;
-            ea.skeys = sm_keys;
-            ea.spts = h->spts.p;
-            ea.Fnew = Fnew;
-            ea.cnt = h->lab_slots.p;
-            // (one round of workgroups: a 1024-thread workgroup of this kernel has a compute unit to itself, and the per-bin launch and the query
-            // chains hold some of the 256)
-            LAUNCH(h, "srt+assemble", k_assemble_early, std::min<uint32_t>(cdiv(n_voi, 1024), ERASOR_EARLY_GMAP) + 1u, 1024, P, h->Tb2o, ea);
-        }
-        MARK("  k_srt4 + assemble early");
-        // (an overlapped step's late write-back joins at ev_scan, further down this stream and long there when the per-bin launch ends)
-        if (!ov_next) (void)hipEventRecord(h->ev_srt4, h->bstream);
-        MARK("  ev_srt4 record");
-        MARK("  assemble early");
-        if (!ov_next) (void)hipEventRecord(h->ev_asm, h->bstream);  // (an overlapped step joins at ev_early: one packet less on the early chain)
-        MARK("  ev_asm record");
-        if (ov_next) {
-            const QSide &nq_ = h->q[nxt_side];
-            const size_t cap_chunks = std::min(std::min(std::min(h->vmask.cap, h->hmask.cap), h->lmask.cap) / CHUNK_TILES, h->cinfo.cap) - 8;
-            const uint32_t cap_voi = h->capV - 64u;
-            OvSplit ovs;
-            ovs.late = late_out;
-            ovs.prev = ds;
-            ovs.lmask = h->lmask.p;
-            // (its extents come from *ds: the region this step writes and the outskirts as its gather has left them)
-            launch_voi_split(h, (const float4 *)Fnew, 0u, 0u, 0u, 0u, 0u, nchunks + 64 + cdiv((uint64_t)ns + 4096, CHUNK), nx, ny, P.voi_r2,
-                             (const DevState *)nullptr, (uint32_t)cap_chunks, (const StepEnd *)nullptr, &ovs);
-            const uint32_t scan_cap1 = (uint32_t)std::min<size_t>(std::min(h->pvl.cap, h->phl.cap) - 8, h->scan_one_max);
-            // (the next region's extent is not known here: it keeps this step's reserved places -- up to 4 x the VoI + 2 x the scan, see
-            // alloc_step --, and the outskirts grow by what leaves; one workgroup scans up to scan_one_max chunk counts, beyond that two levels
-            // over everything the buffers hold.  What the scan ahead can take is recorded: a step with more chunks runs its own passes)
-            const uint32_t hint = nchunks + 64 + cdiv(4 * (uint64_t)std::max(h->last_n_voi, 1u << 16) + 2 * (uint64_t)ns + 4096, CHUNK);
-            uint32_t scan_cap_used = 0;
-            h->ov.scan_levels = hint <= scan_cap1 ? 1 : 2;
-            if (hint <= scan_cap1) {
-                scan_cap_used = std::min<uint32_t>(scan_cap1, (uint32_t)cap_chunks);
-                LAUNCH(h, "chunk_scan", k_chunk_scan_one, 1, 1024, (const uint32_t *)h->cinfo.p, 0u, h->pvl.p, h->phl.p, h->topv.p, h->toph.p, 16u, 0u,
-                       h->alt.d_st.p, h->alt.d_ctr.p, h->st, h->alt.lab_slots.p, h->mb_tot.p, B + 2, h->use_ometa ? h->ometa.p : (OMeta *)nullptr,
-                       h->capO / CHUNK, std::min<uint32_t>(scan_cap1, (uint32_t)cap_chunks), (const DevState *)ds, cap_voi);
-            } else {
-                const size_t top_cap = std::min(std::min(h->topv.cap, h->toph.cap), h->topr.cap);
-                const uint32_t grid2 = (uint32_t)std::min<size_t>(cdiv(std::min<size_t>(cap_chunks, std::min(h->pvl.cap, h->phl.cap) - 8), 1024), top_cap - 2);
-                const uint32_t cap2 = std::min<uint32_t>(grid2 * 1024u, (uint32_t)cap_chunks);
-                scan_cap_used = cap2;
-                LAUNCH(h, "chunk_scan", k_chunk_scan_local, grid2, 256, (const uint32_t *)h->cinfo.p, 0u, h->pvl.p, h->phl.p, h->topv.p, h->toph.p, h->topr.p,
-                       (const DevState *)ds, h->capO / CHUNK, cap2, 1u);
-                LAUNCH(h, "chunk_scan", k_chunk_scan_top, 1, 1024, h->topv.p, h->toph.p, grid2, (const uint32_t *)h->pvl.p, (const uint32_t *)h->phl.p, 0u, 0u,
-                       h->alt.d_st.p, h->alt.d_ctr.p, h->st, h->alt.lab_slots.p, h->mb_tot.p, B + 2, (const uint32_t *)h->topr.p,
-                       h->use_ometa ? h->ometa.p : (OMeta *)nullptr, h->capO / CHUNK, cap2, (const DevState *)ds, cap_voi);
-            }
-            MARK("  split + scan ahead");
-            // (round 6: the late gather needs the masks and the chunk prefix, not the gather: it joins HERE and runs beside the gather ahead)
-            (void)hipEventRecord(h->ev_scan, h->bstream);
-            (void)hipStreamWaitEvent(h->bstream, nq_.ev_keys, 0);  // k_voi_gather must see that query side's error flag
-            MARK("  ev_keys wait");
-            {
-                const uint32_t grid = std::max(1u, std::min<uint32_t>(cdiv((nFchunks + 64) * GATHER_SUB + nOchunks + 64, 4), 256 * 16));
-                LAUNCH(h, "voi_gather", k_voi_gather, grid, 256, (const float4 *)Fnew, 0u, 0u, h->Oxy.p, h->Ozi.p, 0u, 0u, (const unsigned long long *)h->vmask.p,
-                       (const unsigned long long *)h->hmask.p, (const uint32_t *)h->cinfo.p, (const uint32_t *)h->pvl.p, (const uint32_t *)h->phl.p,
-                       (const uint32_t *)h->topv.p, (const uint32_t *)h->toph.p, to_xf(nq_.To), P, h->alt.d_st.p, h->alt.d_ctr.p,
-                       (const Counters *)nq_.d_qctr.p, h->alt.voi_ego.p, h->alt.voi_key.p, h->alt.voi_src.p, h->use_ometa ? h->ometa.p : (OMeta *)nullptr,
-                       (const unsigned long long *)h->lmask.p, h->capO / CHUNK);
-            }
-            MARK("  gather ahead");
-            (void)hipEventRecord(h->ev_early, h->bstream);
-            MARK("  ev_early record");
-            h->ov.valid = true;
-            h->ov.seq = h->step_seq + 1;  // (this step's number: checked by the step that follows before it takes a number of its own)
-            h->ov.epoch = h->store_epoch;
-            h->ov.curF = h->curF ^ 1;
-            h->ov.qside = nxt_side;
-            h->ov.x = nx;
-            h->ov.y = ny;
-            memcpy(h->ov.To, nq_.To, sizeof(h->ov.To));
-            h->ov.cap_chunks = std::min<uint32_t>((uint32_t)cap_chunks, scan_cap_used);
-            h->ov.cap_voi = cap_voi;
-            h->ov.nbk = B + 2;
-            h->ov.vmask = h->vmask.p;
-            h->ov.hmask = h->hmask.p;
-            h->ov.lmask = h->lmask.p;
-            h->ov.cinfo = h->cinfo.p;
-            h->ov.pvl = h->pvl.p;
-            h->ov.phl = h->phl.p;
-            h->ov.voi_ego = h->alt.voi_ego.p;
-            h->ov.mb_hist = h->mb_hist.p;
-            ++h->n_ov_launched;
-            ++h->n_spec_launched;  // (it is the split ahead of this node, with company)
-            h->fly.spec_launched = true;
-        }
-        h->cur = h->stream;  // ---- back on the main stream
-        };
-    } else if (srt_in_revert) {
-        // (no launch)
+                (int)pl.reserved, (int)pl.srt_in_revert, (int)pl.fold, (int)pl.mb_count, pl.flags, (int)pl.have_pose, h->prof, h->npend, (int)h->ann.valid,
+                (int)h->ann.pose_valid, (int)h->ann.to_valid, h->npend ? (int)h->q[h->pend[0]].pose_valid : -1, h->npend ? (int)h->q[h->pend[0]].to_valid : -1);
+    return ERASOR_OK;
+}
+
+// The early stream of a step that writes the reserved layout, beside its per-bin launch (enqueued BEHIND that launch, which the main
+// stream is waiting for): k_srt4 + the early write-back in one launch, then -- ov_next -- the next step's split, chunk scan and gather
+static void enqueue_early(erasor_hip_handle *h, StepPlan &pl) {
+    const uint32_t B = pl.B;
+    const DP &P = h->dp;
+    pl.MARK("srt: begin");
+    (void)hipStreamWaitEvent(h->bstream, h->ev_stats, 0);
+    pl.MARK("  ev_stats record + wait");
+    h->cur = h->bstream;  // ---- the early stream: beside the per-bin launch
+    // (round 6: ONE launch -- every workgroup of the early write-back derives the reserved offsets it needs from the status bytes itself,
+    // the launch's last workgroup is k_srt4 for everything behind it: see k_assemble_early)
+    {
+        EarlyArgs ea;
+        fill_srt_args(ea, h, h->cset, Q(h));
+        ea.out_offR = h->out_offR.p;
+        ea.gres_off = h->gres_off.p;
+        ea.late = pl.late_out;
+        ea.leave_lim = pl.leave_lim;
+        ea.skeys = pl.sm_keys;
+        ea.spts = h->cset.spts.p;
+        ea.Fnew = pl.Fnew;
+        ea.cnt = h->cset.lab_slots.p;
+        // (one round of workgroups: a 1024-thread workgroup of this kernel has a compute unit to itself, and the per-bin launch and the query
+        // chains hold some of the 256)
+        LAUNCH(h, "srt+assemble", k_assemble_early, std::min<uint32_t>(cdiv(pl.n_voi, 1024), ERASOR_EARLY_GMAP) + 1u, 1024, P, h->Tb2o, ea);
+    }
+    pl.MARK("  k_srt4 + assemble early");
+    // (an overlapped step's late write-back joins at ev_scan, further down this stream and long there when the per-bin launch ends)
+    if (!pl.ov_next) (void)hipEventRecord(h->ev_srt4, h->bstream);
+    pl.MARK("  ev_srt4 record");
+    pl.MARK("  assemble early");
+    if (!pl.ov_next) (void)hipEventRecord(h->ev_asm, h->bstream);  // (an overlapped step joins at ev_early: one packet less on the early chain)
+    pl.MARK("  ev_asm record");
+    if (pl.ov_next) {
+        const QSide &nq_ = h->q[pl.nxt_side];
+        const uint32_t nchunks = pl.ext.nchunks, ns = pl.ns;
+        const size_t cap_chunks = std::min(std::min(std::min(h->vmask.cap, h->hmask.cap), h->lmask.cap) / CHUNK_TILES, h->cinfo.cap) - 8;
+        const uint32_t cap_voi = h->capV - 64u;
+        OvSplit ovs;
+        ovs.late = pl.late_out;
+        ovs.prev = pl.ds;
+        ovs.lmask = h->lmask.p;
+        // (its extents come from *ds: the region this step writes and the outskirts as its gather has left them)
+        Extents next;
+        next.from = Extents::BEING_WRITTEN;
+        next.dev = (const DevState *)pl.ds;
+        launch_voi_split(h, (const float4 *)pl.Fnew, next, nchunks + 64 + cdiv((uint64_t)ns + 4096, CHUNK), pl.nx, pl.ny, P.voi_r2, (uint32_t)cap_chunks,
+                         (const StepEnd *)nullptr, &ovs);
+        // (the next region's extent is not known here: it keeps this step's reserved places -- up to 4 x the VoI + 2 x the scan, see
+        // alloc_step --, and the outskirts grow by what leaves)
+        const uint32_t hint = nchunks + 64 + cdiv(4 * (uint64_t)std::max(h->last_n_voi, 1u << 16) + 2 * (uint64_t)ns + 4096, CHUNK);
+        Ahead &a = h->ov;
+        a.scan = launch_chunk_scan(h, h->oset, h->bstream, next, hint, (uint32_t)cap_chunks, cap_voi);
+        pl.MARK("  split + scan ahead");
+        // (round 6: the late gather needs the masks and the chunk prefix, not the gather: it joins HERE and runs beside the gather ahead)
+        (void)hipEventRecord(h->ev_scan, h->bstream);
+        (void)hipStreamWaitEvent(h->bstream, nq_.ev_keys, 0);  // k_voi_gather must see that query side's error flag
+        pl.MARK("  ev_keys wait");
+        launch_voi_gather(h, h->oset, h->bstream, (const float4 *)pl.Fnew, next, (pl.ext.nFchunks + 64) * GATHER_SUB + pl.ext.nOchunks + 64, to_xf(nq_.To), nq_,
+                          (const unsigned long long *)h->lmask.p);
+        pl.MARK("  gather ahead");
+        (void)hipEventRecord(h->ev_early, h->bstream);
+        pl.MARK("  ev_early record");
+        // (seq: this step's number: checked by the step that follows before it takes a number of its own)
+        ahead_assumes(h, a, h->step_seq + 1, pl.nx, pl.ny, std::min<uint32_t>((uint32_t)cap_chunks, a.scan.cap));
+        a.qside = pl.nxt_side;
+        memcpy(a.To, nq_.To, sizeof(a.To));
+        a.cap_voi = cap_voi;
+        a.nbk = B + 2;
+        a.lmask = h->lmask.p, a.voi_ego = h->oset.voi_ego.p, a.mb_hist = h->mb_hist.p;
+        ++h->n_ov_launched;
+        ++h->n_spec_launched;  // (it is the split ahead of this node, with company)
+        h->fly.spec_launched = true;
+    }
+    h->cur = h->stream;  // ---- back on the main stream
+}
+
+// Stage 4: Scan Ratio Test, R-GPF, per-bin voxelisation (erasor.cpp:332-571), with the early stream beside the per-bin launch and the late
+// write-back of a step in the reserved layout, and the output layout where it has a launch of its own
+static void step_srt_and_bins(erasor_hip_handle *h, StepPlan &pl) {
+    const DP &P = h->dp;
+    const uint32_t B = pl.B, n_voi = pl.n_voi;
+    const bool reserved = pl.reserved, fold = pl.fold;
+    StepSet &cs = h->cset;
+    DevState *ds = pl.ds;
+    if (reserved || pl.srt_in_revert) {
+        // (no launch: k_assemble_early / the per-bin launch's last workgroup)
     } else if (B <= 1024 * SRT_KPT)
-        LAUNCH(h, "srt", k_srt4, 1, 1024, P, (const uint32_t *)h->mcnt.p, (const float *)h->mmin.p, (const float *)h->mmax.p, (const uint32_t *)Q(h).ccnt.p,
+        LAUNCH(h, "srt", k_srt4, 1, 1024, P, (const uint32_t *)cs.mcnt.p, (const float *)cs.mmin.p, (const float *)cs.mmax.p, (const uint32_t *)Q(h).ccnt.p,
            (const float *)Q(h).cmin.p, (const float *)Q(h).cmax.p, h->st1.p, h->status.p, h->action.p, h->rev_idx.p, h->rev_list.p, h->vox_off.p, ds,
            fold ? h->out_off0.p : (uint32_t *)nullptr, fold ? h->rev_before.p : (uint32_t *)nullptr, fold ? h->crej_off.p : (uint32_t *)nullptr,
-           st1_ahead ? (const uint8_t *)h->st1b.p : (const uint8_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+           pl.st1_ahead ? (const uint8_t *)cs.st1b.p : (const uint8_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
            (uint32_t *)nullptr, (LateEnt *)nullptr, -1.0);
     else
-        LAUNCH(h, "srt", k_srt, 1, 1024, P, (const uint32_t *)h->mcnt.p, (const float *)h->mmin.p, (const float *)h->mmax.p, (const uint32_t *)Q(h).ccnt.p,
+        LAUNCH(h, "srt", k_srt, 1, 1024, P, (const uint32_t *)cs.mcnt.p, (const float *)cs.mmin.p, (const float *)cs.mmax.p, (const uint32_t *)Q(h).ccnt.p,
            (const float *)Q(h).cmin.p, (const float *)Q(h).cmax.p, h->st1.p, h->status.p, h->action.p, h->rev_idx.p, h->rev_list.p, h->vox_off.p, ds);
     // R-GPF and the per-bin voxelisation walk the reverted-bin LIST on a small fixed grid (n_rev is on the device)
     const uint32_t rev_grid = ERASOR_REV_GRID;
     // v3: R-GPF and the per-bin voxelisation of a reverted bin in ONE launch (k_revert_bins); ERASOR_HIP_NO_FUSE=1: two launches (A/B)
     RevArgs ra;
-    ra.moff = h->moff.p;
-    ra.spts = h->spts.p;
-    ra.qoff = Q(h).qoff.p;
-    ra.sq = Q(h).sq.p;
-    ra.gsK = h->gsK.p;
-    ra.gsV = h->gsV.p;
-    ra.gsL = h->gsL.p;
-    ra.gsR = h->gsR.p;
-    ra.gsH = h->gsH.p;
-    ra.gsK2 = h->gsK2.p;
-    ra.gsV2 = h->gsV2.p;
-    ra.gsC = h->gsC.p;
-    ra.gflag = h->gflag.p;
-    ra.grank = h->grank.p;
-    ra.glist = h->glist.p;
-    ra.ng_arr = h->ng.p;
-    ra.plane_n = h->plane_n.p;
-    ra.plane_d = h->plane_d.p;
-    ra.vox_out = h->vox_out.p;
-    ra.nvox_out = h->nvox.p;
-    ra.ctr = dc;
-    ra.dbg = h->dbg_stamps.p;
+    ra.moff = cs.moff.p, ra.spts = cs.spts.p, ra.qoff = Q(h).qoff.p, ra.sq = Q(h).sq.p;
+    ra.gsK = h->gsK.p, ra.gsV = h->gsV.p, ra.gsL = h->gsL.p, ra.gsR = h->gsR.p, ra.gsH = h->gsH.p, ra.gsK2 = h->gsK2.p, ra.gsV2 = h->gsV2.p, ra.gsC = h->gsC.p;
+    ra.gflag = h->gflag.p, ra.grank = h->grank.p, ra.glist = h->glist.p, ra.ng_arr = h->ng.p, ra.plane_n = h->plane_n.p, ra.plane_d = h->plane_d.p;
+    ra.vox_out = h->vox_out.p, ra.nvox_out = h->nvox.p, ra.ctr = pl.dc, ra.dbg = h->dbg_stamps.p;
     // (fused launch: the voxelisation's global-memory path works in the upper half of the shared scratch arrays)
-    ra.vox_base = (uint32_t)((size_t)n_voi + nq + 8);
-    ra.h_base = (uint32_t)(((size_t)n_voi + nq + 8) / 32 + 2 * (size_t)B + 16);
-    if (srt_in_revert) {
+    ra.vox_base = (uint32_t)((size_t)n_voi + pl.nq + 8);
+    ra.h_base = (uint32_t)(((size_t)n_voi + pl.nq + 8) / 32 + 2 * (size_t)B + 16);
+    if (pl.srt_in_revert) {
         SrtArgs sa;
-        sa.mcnt = h->mcnt.p;
-        sa.mmin = h->mmin.p;
-        sa.mmax = h->mmax.p;
-        sa.ccnt = Q(h).ccnt.p;
-        sa.cmin = Q(h).cmin.p;
-        sa.cmax = Q(h).cmax.p;
-        sa.st1 = h->st1.p;
-        sa.status = h->status.p;
-        sa.action = h->action.p;
-        sa.rev_idx = h->rev_idx.p;
-        sa.rev_list = h->rev_list.p;
-        sa.vox_off = h->vox_off.p;
-        sa.st = ds;
-        sa.out_off0 = fold ? h->out_off0.p : (uint32_t *)nullptr;
-        sa.rev_before = fold ? h->rev_before.p : (uint32_t *)nullptr;
-        sa.crej_off = fold ? h->crej_off.p : (uint32_t *)nullptr;
-        sa.st1_in = h->st1b.p;
-        sa.moff = h->moff.p;
-        sa.qoff = Q(h).qoff.p;
+        fill_srt_args(sa, h, cs, Q(h));
+        if (!fold) sa.out_off0 = sa.rev_before = sa.crej_off = nullptr;
         if (reserved) sa.status = nullptr;  // (k_srt4 is the first workgroup of k_assemble_early, on the early stream: no extra workgroup here)
         if (reserved) (void)hipEventRecord(h->ev_stats, h->stream);  // (the bin statistics are there: the early stream may start)
         LAUNCH(h, "rgpf+bin_voxelize", k_revert_bins_srt, std::min<uint32_t>(rev_grid, B) + (reserved ? 0u : 1u), 1024, P, sa, ra);
-        MARK("per-bin launch");
-        if (reserved) enqueue_early();
+        pl.MARK("per-bin launch");
+        if (reserved) enqueue_early(h, pl);
         // (the reverted list, the reserved offsets, the late table; ev_scan: also the next step's masks and chunk prefix, for the late gather)
-        if (reserved) (void)hipStreamWaitEvent(h->stream, ov_next ? h->ev_scan : h->ev_srt4, 0);
-        MARK("  ev_srt4 wait");
+        if (reserved) (void)hipStreamWaitEvent(h->stream, pl.ov_next ? h->ev_scan : h->ev_srt4, 0);
+        pl.MARK("  ev_srt4 wait");
         if (reserved)
-            LAUNCH(h, "assemble", k_assemble_late, std::min<uint32_t>(rev_grid, B) + 1u, 256, P, h->Tb2o, (const uint32_t *)h->rev_list.p, (const float4 *)h->spts.p,
-                   (const uint32_t *)h->ssrc.p, (const uint32_t *)h->moff.p, (const uint32_t *)Q(h).qoff.p, (const uint8_t *)h->gflag.p,
+            LAUNCH(h, "assemble", k_assemble_late, std::min<uint32_t>(rev_grid, B) + 1u, 256, P, h->Tb2o, (const uint32_t *)h->rev_list.p, (const float4 *)cs.spts.p,
+                   (const uint32_t *)cs.ssrc.p, (const uint32_t *)cs.moff.p, (const uint32_t *)Q(h).qoff.p, (const uint8_t *)h->gflag.p,
                    (const uint32_t *)h->grank.p, (const uint32_t *)h->ng.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->vox_off.p,
                    (const float4 *)h->vox_out.p, (const uint32_t *)h->out_offR.p, (const uint32_t *)h->gres_off.p, (const uint32_t *)h->out_off0.p,
-                   (const uint32_t *)h->rev_before.p, late_out, h->late_holes[h->late_idx ^ 1].p, h->out_off.p, h->ground_off.p, h->rej_off.p, ds, Fnew,
-                   h->rejected.p, h->rejected_src.p, h->lab_slots.p,
+                   (const uint32_t *)h->rev_before.p, pl.late_out, h->late_holes[h->late_idx ^ 1].p, h->out_off.p, h->ground_off.p, h->rej_off.p, ds, pl.Fnew,
+                   h->rejected.p, h->rejected_src.p, cs.lab_slots.p,
                    // (an overlapped step read a region with reserved slots as if they were entries: its source indices count them)
-                   use_ov ? (const LateEnt *)h->late[h->late_idx].p : (const LateEnt *)nullptr,
-                   use_ov ? (const uint32_t *)h->late_holes[h->late_idx].p : (const uint32_t *)nullptr, use_ov ? h->n_late_F : 0u);
+                   pl.use_ov ? (const LateEnt *)h->late[h->late_idx].p : (const LateEnt *)nullptr,
+                   pl.use_ov ? (const uint32_t *)h->late_holes[h->late_idx].p : (const uint32_t *)nullptr, pl.use_ov ? h->n_late_F : 0u);
     } else if (P.version == 3 && h->prof != 1) {
         LAUNCH(h, "rgpf+bin_voxelize", k_revert_bins, std::min<uint32_t>(rev_grid, B), 1024, P, (const uint32_t *)h->rev_list.p, (const DevState *)ds,
                (const uint32_t *)h->vox_off.p, ra);
@@ -2602,133 +2641,153 @@ static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_sca
     if (fold) {
         // (no launch)
     } else if (B <= 1024 * SRT_KPT)
-        LAUNCH(h, "layout", k_layout4, 1, 1024, P, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p, (const uint32_t *)h->mcnt.p,
-           (const uint32_t *)Q(h).ccnt.p, (const uint32_t *)h->moff.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->ng.p, h->out_off.p,
+        LAUNCH(h, "layout", k_layout4, 1, 1024, P, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p, (const uint32_t *)cs.mcnt.p,
+           (const uint32_t *)Q(h).ccnt.p, (const uint32_t *)cs.moff.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->ng.p, h->out_off.p,
            h->ground_off.p, h->rej_off.p, h->crej_off.p, ds);
     else
-        LAUNCH(h, "layout", k_layout, 1, 1024, P, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p, (const uint32_t *)h->mcnt.p,
-           (const uint32_t *)Q(h).ccnt.p, (const uint32_t *)h->moff.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->ng.p, h->out_off.p,
+        LAUNCH(h, "layout", k_layout, 1, 1024, P, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p, (const uint32_t *)cs.mcnt.p,
+           (const uint32_t *)Q(h).ccnt.p, (const uint32_t *)cs.moff.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->ng.p, h->out_off.p,
            h->ground_off.p, h->rej_off.p, h->crej_off.p, ds);
+}
 
-    // ---- map write-back (OMU.cpp:281-290) ----
-    if (!reserved) {
-        // v3: the voxelised reverted bins are written by `tail` extra workgroups of the same launch (from the reverted list)
-        const uint32_t tail = (P.version == 3 && n_voi) ? 32u : 0u;
+// Stage 5, map write-back (OMU.cpp:281-290) of a step that does not write the reserved layout (that one's is k_assemble_early / _late)
+static void step_write_back(erasor_hip_handle *h, StepPlan &pl) {
+    if (pl.reserved) return;
+    const DP &P = h->dp;
+    const uint32_t B = pl.B, n_voi = pl.n_voi;
+    StepSet &cs = h->cset;
+    // v3: the voxelised reverted bins are written by `tail` extra workgroups of the same launch (from the reverted list)
+    const uint32_t tail = (P.version == 3 && n_voi) ? 32u : 0u;
 #define ASM_ARGS(FOLDPTR)                                                                                                                   \
-    P, h->Tb2o, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p, sm_keys, (const float4 *)h->spts.p, (const uint32_t *)h->ssrc.p, \
-        (const uint32_t *)h->moff.p, (const uint32_t *)Q(h).ccnt.p, (const uint8_t *)h->gflag.p, (const uint32_t *)h->grank.p, h->out_off.p,   \
-        h->ground_off.p, h->rej_off.p, ds, Fnew, h->rejected.p, h->rejected_src.p, h->lab_slots.p, tail, (const uint32_t *)h->rev_list.p,      \
+    P, h->Tb2o, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p, pl.sm_keys, (const float4 *)cs.spts.p, (const uint32_t *)cs.ssrc.p, \
+        (const uint32_t *)cs.moff.p, (const uint32_t *)Q(h).ccnt.p, (const uint8_t *)h->gflag.p, (const uint32_t *)h->grank.p, h->out_off.p,   \
+        h->ground_off.p, h->rej_off.p, pl.ds, pl.Fnew, h->rejected.p, h->rejected_src.p, cs.lab_slots.p, tail, (const uint32_t *)h->rev_list.p,      \
         (const uint32_t *)Q(h).qoff.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->vox_off.p, (const float4 *)h->vox_out.p,              \
         (const uint32_t *)(FOLDPTR ? h->out_off0.p : nullptr), (const uint32_t *)(FOLDPTR ? h->rev_before.p : nullptr), (const uint32_t *)h->ng.p
-        const uint32_t asm_grid = std::min<uint32_t>(cdiv(n_voi, 256), 2048) + tail;
-        if (n_voi && fold) LAUNCH(h, "assemble", (k_assemble_map<true, true>), asm_grid, 256, ASM_ARGS(true));
-        else if (n_voi) LAUNCH(h, "assemble", (k_assemble_map<true, false>), asm_grid, 256, ASM_ARGS(false));
+    const uint32_t asm_grid = std::min<uint32_t>(cdiv(n_voi, 256), 2048) + tail;
+    if (n_voi && pl.fold) LAUNCH(h, "assemble", (k_assemble_map<true, true>), asm_grid, 256, ASM_ARGS(true));
+    else if (n_voi) LAUNCH(h, "assemble", (k_assemble_map<true, false>), asm_grid, 256, ASM_ARGS(false));
 #undef ASM_ARGS
-        if (!tail)
-            LAUNCH(h, "assemble", k_assemble_bins<true>, B, 256, P, h->Tb2o, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p,
-                   (const uint32_t *)Q(h).qoff.p, (const float4 *)Q(h).sq.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->vox_off.p,
-                   (const float4 *)h->vox_out.p, (const uint32_t *)h->out_off.p, (const uint32_t *)h->crej_off.p, Fnew, h->curr_rejected.p, h->lab_slots.p);
-    }
+    if (!tail)
+        LAUNCH(h, "assemble", k_assemble_bins<true>, B, 256, P, h->Tb2o, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p,
+               (const uint32_t *)Q(h).qoff.p, (const float4 *)Q(h).sq.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->vox_off.p,
+               (const float4 *)h->vox_out.p, (const uint32_t *)h->out_off.p, (const uint32_t *)h->crej_off.p, pl.Fnew, h->curr_rejected.p, cs.lab_slots.p);
     // (label counters of the new VoI-resident region are accumulated by the two assemble kernels)
-    const unsigned long long step_seq = ++h->step_seq;
-    {   // the NEXT step's VoI split goes right behind the step when its pose is known (erasor_hip_prefetch_node): the main
-        // stream runs it while the host collects this step's results and the caller comes back with the next scan -- the pass
-        // reads the store this step has just written and the extents the step's end commits; a step that finds anything else than
-        // what was assumed here (pose, store, buffers) simply runs its own pass.
-        // Round 4: that launch also ENDS this step (its last workgroup does k_step_end's work)
-        // (large-scale mode, round 4: ahead as well, unless the next node's pose moves the submap)
-        const bool spec = have_pose && !flags && !submap_would_move(h, nx, ny);
-        StepEnd se;
-        se.st = ds;
-        se.ctr = dc;
-        se.out = h->pin;
-        se.lab_slots = (const unsigned long long *)h->lab_slots.p;
-        se.qctr = (const Counters *)Q(h).d_qctr.p;
-        se.q_nvox = (const uint32_t *)Q(h).d_nvox.p;
-        se.seq = step_seq;
-        const bool end_in_split = spec && h->prof != 1 && !ov_next;
-        h->fly.nchunks = nchunks;
-        h->fly.spec_launched = ov_next;
-        if (ov_next) {
-            // round 5: behind the per-bin launch and the late write-back, the late half of the NEXT step's gather -- its last workgroup ends
-            // THIS step --, then that step's bucket histogram and column scan: the stream works through the host's turnaround
-            const QSide &nq_ = h->q[nxt_side];
-            MARK("assemble late");
-            // round 6: the late gather joins the early stream behind the next step's split and chunk scan (ev_scan) -- it fills the late
-            // table's places in VoI order, which the gather ahead leaves alone, and reads nothing that gather writes -- and runs BESIDE that
-            // gather; what needs both, the bucket histogram, joins at ev_early.  On the 9.8 M-point map the early stream's passes are the
-            // longer branch in three steps of four: the late gather (8 us + a boundary) no longer follows them (measured, one box, medians of
-            // seven passes twice: 0.1903 / 0.1876 -> 0.1885 / 0.1848 ms per scan; 39 M-point map 0.326 / 0.330 -> 0.3155 / 0.3197)
-            // (joined at ev_scan in front of the late write-back already)
-            MARK("  ev_scan wait");
-            LAUNCH(h, "voi_gather", k_late_gather, std::min<uint32_t>(2 * B, 128u) + 1u, 256, (const float4 *)Fnew, (const LateEnt *)late_out, (const DevState *)ds,
-                   h->Oxy.p, h->Ozi.p, (const unsigned long long *)h->vmask.p, (const unsigned long long *)h->hmask.p, (const uint32_t *)h->pvl.p,
-                   (const uint32_t *)h->phl.p, (const uint32_t *)h->topv.p, (const uint32_t *)h->toph.p, nx, ny, P.voi_r2, to_xf(nq_.To), P, h->alt.d_st.p,
-                   h->alt.d_ctr.p, (const Counters *)nq_.d_qctr.p, h->alt.voi_ego.p, h->alt.voi_key.p, h->alt.voi_src.p, se);
-            const uint32_t ntile_tab = std::max(1u, cdiv(n_voi, MB_TILE));
-            const uint32_t ntile_ub = h->last_n_voi ? std::min(ntile_tab, std::max(64u, cdiv((uint64_t)h->last_n_voi * 3 / 2, MB_TILE))) : ntile_tab;
-            const uint32_t *nvoi_next = &h->alt.d_st.p->voi_total;
-            (void)hipStreamWaitEvent(h->stream, h->ev_early, 0);  // (the gather ahead)
-            LAUNCH(h, "voi_bucket", k_mb_hist, ntile_ub, 1024, (const uint32_t *)h->alt.voi_key.p, n_voi, nvoi_next, B + 2, h->mb_hist.p, h->mb_tot.p);
-            LAUNCH(h, "voi_bucket", k_mb_colscan, cdiv(B + 2, MB_PAD), 256, h->mb_hist.p, n_voi, nvoi_next, B + 2, (const uint32_t *)h->mb_tot.p,
-                   h->alt.moff.p);
-            // ... and the stable scatter, the bins' statistics and the Scan Ratio Test's first pass (into the OTHER set of arrays: a getter may
-            // still ask for this step's): what is left for the next step's call is its per-bin launch -- the host's turnaround is off the chain
-            h->ov.stats_done = false;
-            if (B + 2 <= MBW_NB_MAX) {
-                const int bits2 = key_bits(B + 2);
-                if (B + 2 <= MBW_NB_SMALL)
-                    LAUNCH(h, "voi_bucket", k_mb_scatter_w<MBW_NB_SMALL>, ntile_ub, 1024, (const uint32_t *)h->alt.voi_key.p, (const float4 *)h->alt.voi_ego.p,
-                           (const uint32_t *)h->alt.voi_src.p, n_voi, nvoi_next, B + 2, bits2, (const uint32_t *)h->mb_hist.p, h->alt.spts.p, h->alt.ssrc.p,
-                           h->alt.rk_a.p, h->dbg_stamps.p);
-                else
-                    LAUNCH(h, "voi_bucket", k_mb_scatter_w<MBW_NB_MAX>, ntile_ub, 1024, (const uint32_t *)h->alt.voi_key.p, (const float4 *)h->alt.voi_ego.p,
-                           (const uint32_t *)h->alt.voi_src.p, n_voi, nvoi_next, B + 2, bits2, (const uint32_t *)h->mb_hist.p, h->alt.spts.p, h->alt.ssrc.p,
-                           h->alt.rk_a.p, h->dbg_stamps.p);
-                (void)hipStreamWaitEvent(h->stream, nq_.ev_done, 0);  // (the query's bins: its chain was enqueued steps ago)
-                LAUNCH(h, "bin_stats", k_bin_stats_srt, cdiv((uint64_t)B * 64, 256), 256, P, (const float4 *)h->alt.spts.p, (const uint32_t *)h->alt.moff.p, B,
-                       h->alt.mcnt.p, h->alt.mmin.p, h->alt.mmax.p, (const uint32_t *)nq_.ccnt.p, (const float *)nq_.cmin.p, (const float *)nq_.cmax.p,
-                       h->alt.st1b.p);
-                h->ov.stats_done = true;
-            }
-        } else {
-            if (reserved) (void)hipStreamWaitEvent(h->stream, h->ev_asm, 0);  // (the early half of the write-back, its label tallies)
-            if (!end_in_split)
-                LAUNCH(h, "step_end", k_step_end, 1, 1, se.st, se.ctr, se.out, se.lab_slots, se.qctr, se.q_nvox, se.seq);
-            if (spec) launch_split_ahead(h, nx, ny, nchunks, end_in_split ? &se : (const StepEnd *)nullptr);
+}
+
+// Stage 6: the step's end, together with what is launched for the NEXT step behind it, and the next announced scan's query chain.
+// The NEXT step's VoI split goes right behind the step when its pose is known (erasor_hip_prefetch_node): the main stream runs it while
+// the host collects this step's results and the caller comes back with the next scan -- the pass reads the store this step has just
+// written and the extents the step's end commits; a step that finds anything else than what was assumed here (pose, store, buffers)
+// simply runs its own pass.  Round 4: that launch also ENDS this step (its last workgroup does k_step_end's work)
+// (large-scale mode, round 4: ahead as well, unless the next node's pose moves the submap)
+static int step_end_and_ahead(erasor_hip_handle *h, StepPlan &pl) {
+    const uint32_t B = pl.B, n_voi = pl.n_voi;
+    const DP &P = h->dp;
+    ++h->step_seq;  // this step's number
+    const bool spec = pl.have_pose && !pl.flags && !submap_would_move(h, pl.nx, pl.ny);
+    StepEnd se;
+    se.st = pl.ds;
+    se.ctr = pl.dc;
+    se.out = h->pin;
+    se.lab_slots = (const unsigned long long *)h->cset.lab_slots.p;
+    se.qctr = (const Counters *)Q(h).d_qctr.p;
+    se.q_nvox = (const uint32_t *)Q(h).d_nvox.p;
+    se.seq = h->step_seq;
+    const bool end_in_split = spec && h->prof != 1 && !pl.ov_next;
+    h->fly.nchunks = pl.ext.nchunks;
+    h->fly.spec_launched = pl.ov_next;
+    if (pl.ov_next) {
+        // round 5: behind the per-bin launch and the late write-back, the late half of the NEXT step's gather -- its last workgroup ends
+        // THIS step --, then that step's bucket histogram and column scan: the stream works through the host's turnaround
+        const QSide &nq_ = h->q[pl.nxt_side];
+        StepSet &os = h->oset;
+        pl.MARK("assemble late");
+        // round 6: the late gather joins the early stream behind the next step's split and chunk scan (ev_scan) -- it fills the late
+        // table's places in VoI order, which the gather ahead leaves alone, and reads nothing that gather writes -- and runs BESIDE that
+        // gather; what needs both, the bucket histogram, joins at ev_early.  On the 9.8 M-point map the early stream's passes are the
+        // longer branch in three steps of four: the late gather (8 us + a boundary) no longer follows them (measured, one box, medians of
+        // seven passes twice: 0.1903 / 0.1876 -> 0.1885 / 0.1848 ms per scan; 39 M-point map 0.326 / 0.330 -> 0.3155 / 0.3197)
+        // (joined at ev_scan in front of the late write-back already)
+        pl.MARK("  ev_scan wait");
+        LAUNCH(h, "voi_gather", k_late_gather, std::min<uint32_t>(2 * B, 128u) + 1u, 256, (const float4 *)pl.Fnew, (const LateEnt *)pl.late_out,
+               (const DevState *)pl.ds, h->Oxy.p, h->Ozi.p, (const unsigned long long *)h->vmask.p, (const unsigned long long *)h->hmask.p,
+               (const uint32_t *)h->pvl.p, (const uint32_t *)h->phl.p, (const uint32_t *)h->topv.p, (const uint32_t *)h->toph.p, pl.nx, pl.ny, P.voi_r2,
+               to_xf(nq_.To), P, os.d_st.p, os.d_ctr.p, (const Counters *)nq_.d_qctr.p, os.voi_ego.p, os.voi_key.p, os.voi_src.p, se);
+        (void)hipStreamWaitEvent(h->stream, h->ev_early, 0);  // (the gather ahead)
+        launch_bucket_table(h, os, h->stream, n_voi, B + 2);
+        // ... and the stable scatter, the bins' statistics and the Scan Ratio Test's first pass (into the OTHER set of arrays: a getter may
+        // still ask for this step's): what is left for the next step's call is its per-bin launch -- the host's turnaround is off the chain
+        h->ov.stats_done = false;
+        if (B + 2 <= MBW_NB_MAX) {
+            launch_bucket_scatter(h, os, h->stream, n_voi, B + 2, key_bits(B + 2));
+            launch_bin_stats(h, os, h->stream, nq_, true);  // (the query's bins: its chain was enqueued steps ago)
+            h->ov.stats_done = true;
         }
+    } else {
+        if (pl.reserved) (void)hipStreamWaitEvent(h->stream, h->ev_asm, 0);  // (the early half of the write-back, its label tallies)
+        if (!end_in_split)
+            LAUNCH(h, "step_end", k_step_end, 1, 1, se.st, se.ctr, se.out, se.lab_slots, se.qctr, se.q_nvox, se.seq);
+        if (spec) launch_split_ahead(h, pl.nx, pl.ny, pl.ext.nchunks, end_in_split ? &se : (const StepEnd *)nullptr);
     }
-    MARK("late gather + table ahead / end");
-    {   // the NEXT scan's query chain goes into its queue now, behind this step's own launches; it runs while we wait
-        const int keep_side = h->qi;
-        int rc_next = flush_announced(h);
-        if (!rc_next) rc_next = flush_held_if_due(h);  // (a chain held back for a shared set of launches whose own step is near)
-        h->qi = keep_side;
-        if (rc_next) {
-            (void)hipStreamSynchronize(h->stream);
-            h->spec.valid = false;
-            return rc_next;
-        }
+    pl.MARK("late gather + table ahead / end");
+    // the NEXT scan's query chain goes into its queue now, behind this step's own launches; it runs while we wait
+    const int keep_side = h->qi;
+    int rc_next = flush_announced(h);
+    if (!rc_next) rc_next = flush_held_if_due(h);  // (a chain held back for a shared set of launches whose own step is near)
+    h->qi = keep_side;
+    if (rc_next) {
+        (void)hipStreamSynchronize(h->stream);
+        h->spec.valid = false;
     }
+    return rc_next;
+}
+
+// Stage 7, publish: the step is in flight
+static void step_publish(erasor_hip_handle *h, StepPlan &pl) {
     h->fly.active = true;
-    h->fly.reserved = reserved;
-    h->fly.seq = step_seq;
-    h->fly.n_map_in = n_map_in;
-    h->fly.ns = ns;
-    h->fly.sm_keys = sm_keys;
-    h->fly.flags = flags;
+    h->fly.reserved = pl.reserved;
+    h->fly.seq = h->step_seq;
+    h->fly.n_map_in = pl.n_map_in;
+    h->fly.ns = pl.ns;
+    h->fly.sm_keys = pl.sm_keys;
+    h->fly.flags = pl.flags;
     // (what a step that has to run again reads: a host scan's staged copy -- float4 rows in the side's pinned buffer --, never the
     // caller's buffer, which is the caller's again once this call has returned)
-    h->fly.scan_src = (src_is_device || !n_scan) ? scan_src : (const void *)Q(h).stage;
-    h->fly.n_scan = n_scan;
-    h->fly.src_is_device = src_is_device;
-    memcpy(h->fly.Tl, T_l2b, sizeof(h->fly.Tl));
-    memcpy(h->fly.Tb, T_b2o, sizeof(h->fly.Tb));
-    memcpy(h->fly.To, T_o2b, sizeof(h->fly.To));
-    if (host_timing) {
-        for (auto &m : marks) fprintf(stderr, "   %-20s %.1f us\n", m.first, m.second);
-        fprintf(stderr, "[step host] enqueue %.1f us\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_host0).count());
+    h->fly.scan_src = (pl.src_is_device || !pl.n_scan) ? pl.scan_src : (const void *)Q(h).stage;
+    h->fly.n_scan = pl.n_scan;
+    h->fly.src_is_device = pl.src_is_device;
+    memcpy(h->fly.Tl, pl.T_l2b, sizeof(h->fly.Tl));
+    memcpy(h->fly.Tb, pl.T_b2o, sizeof(h->fly.Tb));
+    memcpy(h->fly.To, pl.T_o2b, sizeof(h->fly.To));
+    if (pl.MARK.on) {
+        for (auto &m : pl.MARK.marks) fprintf(stderr, "   %-20s %.1f us\n", m.first, m.second);
+        fprintf(stderr, "[step host] enqueue %.1f us\n", pl.MARK.us());
     }
+}
+
+// First half of a step: everything is ENQUEUED (this scan's query chain unless it is in flight already, the map chain, Scan Ratio
+// Test .. write-back, k_step_end, the next step's VoI split and the next announced scan's query chain); nothing is waited for.
+// ticket != 0: the scan is the OLDEST announced one and must carry that ticket (erasor_hip_step_ticket): nothing is compared, the
+// caller's buffer is not read again; scan_src / n_scan / T_l2b are ignored.
+static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_scan, bool src_is_device, const float T_l2b[16],
+                        const float T_b2o[16], const float T_o2b[16], int flags = 0, RowFmt fmt = RowFmt(), uint64_t ticket = 0) {
+    if (!h) return ERASOR_E_INVALID;
+    StepPlan pl{scan_src, n_scan, src_is_device, T_l2b, T_b2o, T_o2b, flags, fmt, ticket};
+    int rc = step_admit(h, pl);
+    if (!rc) rc = step_plan_reserve(h, pl);
+    if (rc) return rc;
+    enqueue_map_chain(h, pl);
+    pl.MARK("map chain");
+    HIPC(h, hipStreamWaitEvent(h->stream, Q(h).ev_done, 0));  // join: the query's bins are ready
+    h->ov_mode = pl.reserved;
+    rc = step_next_overlap(h, pl);
+    if (rc) return rc;
+    step_srt_and_bins(h, pl);
+    step_write_back(h, pl);
+    rc = step_end_and_ahead(h, pl);
+    if (rc) return rc;
+    step_publish(h, pl);
     return ERASOR_OK;
 }
 
@@ -3424,8 +3483,8 @@ static int assemble_egocentric(erasor_hip_handle *h, float4 **out) {
     const uint32_t B = h->B, n_voi = h->last_n_voi;
     if (n_voi)
         LAUNCH(h, "get_cloud", (k_assemble_map<false, false>), std::min<uint32_t>(cdiv(n_voi, 256), 2048), 256, P, h->Tb2o, (const uint8_t *)h->action.p,
-               (const uint32_t *)h->rev_idx.p, h->last_skeys, (const float4 *)h->spts.p, (const uint32_t *)h->ssrc.p,
-               (const uint32_t *)h->moff.p, (const uint32_t *)Q(h).ccnt.p, (const uint8_t *)h->gflag.p, (const uint32_t *)h->grank.p,
+               (const uint32_t *)h->rev_idx.p, h->last_skeys, (const float4 *)h->cset.spts.p, (const uint32_t *)h->cset.ssrc.p,
+               (const uint32_t *)h->cset.moff.p, (const uint32_t *)Q(h).ccnt.p, (const uint8_t *)h->gflag.p, (const uint32_t *)h->grank.p,
                h->out_off.p, h->ground_off.p, h->rej_off.p,
                h->d_st_get.p, tmp, (float4 *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr, 0u, (const uint32_t *)nullptr,
                (const uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, (const float4 *)nullptr, (const uint32_t *)nullptr,
@@ -3452,7 +3511,7 @@ int erasor_hip_get_cloud(erasor_hip_handle *h, int which, float *dst, size_t cap
     switch (which) {
         case ERASOR_CLOUD_QUERY_VOI: return out_cloud(h, Q(h).query.p, h->last_nq, dst, cap, n);
         case ERASOR_CLOUD_MAP_VOI: {
-            if (!s.n_voi_dead) return out_cloud(h, h->voi_ego.p, h->last_n_voi, dst, cap, n);
+            if (!s.n_voi_dead) return out_cloud(h, h->cset.voi_ego.p, h->last_n_voi, dst, cap, n);
             // (round 5: an overlapped step's VoI-order array keeps places no point came to, key B + 1: the VoI is what is left)
             if (n) *n = h->last_n_voi;
             if (!dst) return ERASOR_OK;
@@ -3464,9 +3523,9 @@ int erasor_hip_get_cloud(erasor_hip_handle *h, int which, float *dst, size_t cap
                 return ERASOR_E_NO_DEVICE;
             hipStream_t keep = h->cur;
             h->cur = h->stream;
-            LAUNCH(h, "get_cloud", k_voi_live, cdiv(tot, 256), 256, (const uint32_t *)h->voi_key.p, tot, h->B, flag.p);
+            LAUNCH(h, "get_cloud", k_voi_live, cdiv(tot, 256), 256, (const uint32_t *)h->cset.voi_key.p, tot, h->B, flag.p);
             scan_u32(h, flag.p, pl.p, tops.p, tot, tot, nullptr, nullptr, "get_cloud");
-            LAUNCH(h, "get_cloud", k_f_compact, cdiv(tot, 256), 256, (const float4 *)h->voi_ego.p, tot, (const uint32_t *)flag.p, (const uint32_t *)pl.p,
+            LAUNCH(h, "get_cloud", k_f_compact, cdiv(tot, 256), 256, (const float4 *)h->cset.voi_ego.p, tot, (const uint32_t *)flag.p, (const uint32_t *)pl.p,
                    (const uint32_t *)tops.p, tmp.p);
             h->cur = keep;
             const int rc_c = d2h(h, dst, tmp.p, (size_t)h->last_n_voi * sizeof(float4));
@@ -3518,9 +3577,9 @@ int erasor_hip_get_bins(erasor_hip_handle *h, int which, uint32_t *count, double
     const uint32_t B = h->B, R = h->P.num_rings, S = h->P.num_sectors;
     std::vector<uint32_t> c(B);
     std::vector<float> mn(B), mx(B);
-    HIPC(h, hipMemcpy(c.data(), which ? Q(h).ccnt.p : h->mcnt.p, B * 4, hipMemcpyDeviceToHost));
-    HIPC(h, hipMemcpy(mn.data(), which ? Q(h).cmin.p : h->mmin.p, B * 4, hipMemcpyDeviceToHost));
-    HIPC(h, hipMemcpy(mx.data(), which ? Q(h).cmax.p : h->mmax.p, B * 4, hipMemcpyDeviceToHost));
+    HIPC(h, hipMemcpy(c.data(), which ? Q(h).ccnt.p : h->cset.mcnt.p, B * 4, hipMemcpyDeviceToHost));
+    HIPC(h, hipMemcpy(mn.data(), which ? Q(h).cmin.p : h->cset.mmin.p, B * 4, hipMemcpyDeviceToHost));
+    HIPC(h, hipMemcpy(mx.data(), which ? Q(h).cmax.p : h->cset.mmax.p, B * 4, hipMemcpyDeviceToHost));
     for (uint32_t key = 0; key < B; ++key) {  // device key = sector*R + ring -> API index = ring*S + sector
         const uint32_t ring = key % R, sector = key / R;
         const uint32_t o = ring * S + sector;
@@ -3558,8 +3617,8 @@ int erasor_hip_get_rpod(erasor_hip_handle *h, int which, float *xyzi, size_t cap
     const float4 *src = nullptr;
     size_t total = 0;
     if (which == 0) {
-        HIPC(h, hipMemcpy(off.data(), h->moff.p, (size_t)(B + 1) * 4, hipMemcpyDeviceToHost));
-        src = h->spts.p;
+        HIPC(h, hipMemcpy(off.data(), h->cset.moff.p, (size_t)(B + 1) * 4, hipMemcpyDeviceToHost));
+        src = h->cset.spts.p;
         total = off[B];
     } else if (which == 1) {
         HIPC(h, hipMemcpy(off.data(), Q(h).qoff.p, (size_t)(B + 1) * 4, hipMemcpyDeviceToHost));

@@ -567,22 +567,37 @@ inline hipError_t hipDeviceCanAccessPeer(int *can, int, int) {
     return hipSuccess;
 }
 inline hipError_t hipDeviceEnablePeerAccess(int, unsigned) { return hipSuccess; }
+// SIMT_EMU_TRACE: one line per launch (with its duration), event record, stream wait and synchronise.  Streams and events are numbered in
+// creation order from 1 (0: the null stream / no event), so that two builds' traces can be compared stream by stream (tools/simt_trace_diff.py)
+inline bool simt_trace_on() {
+    static const bool on = getenv("SIMT_EMU_TRACE") != nullptr;
+    return on;
+}
+inline int simt_next_id(bool event) {
+    static std::atomic<int> n[2] = {{0}, {0}};
+    return ++n[event];
+}
+inline int simt_id(hipStream_t s_) { return s_ ? s_->id : 0; }
+inline int simt_id(hipEvent_t e) { return e ? e->id : 0; }
 inline hipError_t hipStreamCreateWithPriority(hipStream_t *s_, unsigned, int) {
-    *s_ = new simt_stream_t{0};
+    *s_ = new simt_stream_t{simt_next_id(false)};
     return hipSuccess;
 }
-inline hipError_t hipStreamCreateWithFlags(hipStream_t *s_, unsigned) {
-    *s_ = new simt_stream_t{0};
-    return hipSuccess;
-}
+inline hipError_t hipStreamCreateWithFlags(hipStream_t *s_, unsigned) { return hipStreamCreateWithPriority(s_, 0, 0); }
 inline hipError_t hipStreamDestroy(hipStream_t s_) {
     delete s_;
     return hipSuccess;
 }
-inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
+inline hipError_t hipStreamSynchronize(hipStream_t s_) {
+    if (simt_trace_on()) fprintf(stderr, "[simt_emu] sync stream %d\n", simt_id(s_));
+    return hipSuccess;
+}
+inline hipError_t hipStreamWaitEvent(hipStream_t s_, hipEvent_t e, unsigned) {
+    if (simt_trace_on()) fprintf(stderr, "[simt_emu] wait stream %d event %d\n", simt_id(s_), simt_id(e));
+    return hipSuccess;
+}
 inline hipError_t hipEventCreate(hipEvent_t *e) {
-    *e = new simt_event_t{0};
+    *e = new simt_event_t{simt_next_id(true)};
     return hipSuccess;
 }
 inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
@@ -590,25 +605,27 @@ inline hipError_t hipEventDestroy(hipEvent_t e) {
     delete e;
     return hipSuccess;
 }
-inline hipError_t hipEventRecord(hipEvent_t, hipStream_t = nullptr) { return hipSuccess; }
-inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
+inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s_ = nullptr) {
+    if (simt_trace_on()) fprintf(stderr, "[simt_emu] record event %d stream %d\n", simt_id(e), simt_id(s_));
+    return hipSuccess;
+}
+inline hipError_t hipEventSynchronize(hipEvent_t e) {
+    if (simt_trace_on()) fprintf(stderr, "[simt_emu] sync event %d\n", simt_id(e));
+    return hipSuccess;
+}
 inline hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
 inline hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) {
     *ms = 0.001f;
     return hipSuccess;
 }
-inline bool simt_trace_on() {
-    static const bool on = getenv("SIMT_EMU_TRACE") != nullptr;  // one line per launch, with its duration
-    return on;
-}
-#define SIMT_LAUNCH(kern, grid, block, ...)                                                                                    \
+#define SIMT_LAUNCH(kern, grid, block, stream, ...)                                                                            \
     do {                                                                                                                       \
         const auto t0_ = std::chrono::steady_clock::now();                                                                     \
         simt::run_grid(dim3(grid).x, dim3(block).x, [&] { kern(__VA_ARGS__); }, dim3(grid).y);                                               \
         if (simt_trace_on())                                                                                                   \
-            fprintf(stderr, "[simt_emu] %s <<<%u, %u>>> %.0f ms\n", #kern, dim3(grid).x, dim3(block).x,                        \
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0_).count());               \
+            fprintf(stderr, "[simt_emu] %s <<<%u x %u, %u>>> stream %d %.0f ms\n", #kern, dim3(grid).x, dim3(grid).y, dim3(block).x, \
+                    simt_id(stream), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0_).count()); \
     } while (0)
-#define hipLaunchKernelGGL(kern, grid, block, shmem, stream, ...) SIMT_LAUNCH(kern, grid, block, __VA_ARGS__)
-#define hipExtLaunchKernelGGL(kern, grid, block, shmem, stream, ev0, ev1, flags, ...) SIMT_LAUNCH(kern, grid, block, __VA_ARGS__)
+#define hipLaunchKernelGGL(kern, grid, block, shmem, stream, ...) SIMT_LAUNCH(kern, grid, block, stream, __VA_ARGS__)
+#define hipExtLaunchKernelGGL(kern, grid, block, shmem, stream, ev0, ev1, flags, ...) SIMT_LAUNCH(kern, grid, block, stream, __VA_ARGS__)
 #endif
