@@ -371,6 +371,10 @@ struct erasor_hip_handle {
         DBuf<uint8_t> rd_img;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
+#ifdef ERASOR_HIP_TEST_HOOKS
+    // what the last run_exact_sort launched, for erasor_hip_debug_sort_queues: keys, wide levels, level-queue launches, k_esort_mid run, final grid
+    uint32_t dbg_sort[5] = {0, 0, 0, 0, 0};
+#endif
     // ---- per-bin scratch (R-GPF / bin voxelise global paths) ----
     DBuf<uint32_t> gsK, gsV, gsL, gsR, gsK2, gsV2;
     DBuf<uint32_t> gsH;
@@ -1251,6 +1255,15 @@ static void run_exact_sort(erasor_hip_handle *h, uint32_t n, bool queues_open = 
     // a scan leaves ~120 segments for the finisher: 128 workgroups of 1024 threads take them in one round and leave the compute units
     // to the chains running beside this one (2048 measured 1.5 % slower per scan, gpurun_out/r03o); a whole map keeps the wide grid
     const uint32_t final_grid = n <= (1u << 20) ? 128u : 2048u;
+#ifdef ERASOR_HIP_TEST_HOOKS
+    {
+        const bool wide = n >= WIDE_MIN && (n - 1 + WTILE - 1) / WTILE <= WTILES_MAX;
+        const int cap = getenv("ERASOR_HIP_SORT_LEVEL_CAP") ? atoi(getenv("ERASOR_HIP_SORT_LEVEL_CAP")) : 1 << 20;
+        const uint32_t rec[5] = {n, wide ? (uint32_t)std::min(std::min(esort::lg2_floor(n / WIDE_MIN) + ESORT_WIDE_SLACK, 16), cap) : 0u, (uint32_t)nlev,
+                                 mid_done ? 1u : 0u, final_grid};
+        memcpy(h->dbg_sort, rec, sizeof(rec));
+    }
+#endif
     LAUNCH(h, "q_esort_final", k_esort_final, final_grid, 1024, Q(h).qk_a.p, Q(h).qv_a.p, Q(h).qposL.p, Q(h).qposR.p, Q(h).qhead.p, Q(h).qk_b.p, Q(h).qv_b.p,
            (const esort::Seg *)Q(h).essmall.p, (const esort::Seg *)qs3[bigcur], Q(h).esqs.p, bigcur, dc, h->dbg_stamps.p);
 }
@@ -4114,6 +4127,39 @@ int erasor_hip_exact_sort_u32(erasor_hip_handle *h, uint32_t *keys, uint32_t *va
     if (ns) {
         HIPC(h, hipMemcpy(keys, Q(h).qk_b.p, (size_t)ns * 4, hipMemcpyDeviceToHost));
         HIPC(h, hipMemcpy(vals, Q(h).qv_b.p, (size_t)ns * 4, hipMemcpyDeviceToHost));
+    }
+    return ERASOR_OK;
+}
+
+// test hook: what the last exact sort of the handle's query side (erasor_hip_exact_sort_u32, or the sort inside a voxelisation) left in its
+// queues, read-only.  state[0..17] = EsQueues (cnt[0..2], small_cnt), WideState (nseg[0..1], ntiles[0..1]), then what run_exact_sort launched
+// (keys, wide levels, k_esort_level launches, k_esort_mid run, k_esort_final's grid), then the chain's counters n_sort_fallback,
+// n_voxel_overflow, sort_qoverflow, err, and the run detection's tile count.  smallq / q0 / q1 / q2 (may be null): the (first, last, depth)
+// records of the finisher's queue and of the three level queues, up to their counts and at most `cap` records each.  k_esort_mid only reads
+// queue 0, so after a sort that ran it queue 0 still holds what it was given.
+int erasor_hip_debug_sort_queues(erasor_hip_handle *h, uint32_t *state, int32_t *smallq, int32_t *q0, int32_t *q1, int32_t *q2, size_t cap) {
+    NOFLY(h);
+    if (!h || !state) return ERASOR_E_INVALID;
+    if (!Q(h).esqs.p || !Q(h).wstate.p) return ERASOR_E_STATE;
+    HIPC(h, hipSetDevice(h->device));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    EsQueues qs;
+    WideState ws;
+    Counters c;
+    HIPC(h, hipMemcpy(&qs, Q(h).esqs.p, sizeof(qs), hipMemcpyDeviceToHost));
+    HIPC(h, hipMemcpy(&ws, Q(h).wstate.p, sizeof(ws), hipMemcpyDeviceToHost));
+    HIPC(h, hipMemcpy(&c, Q(h).d_qctr.p, sizeof(c), hipMemcpyDeviceToHost));
+    static_assert(sizeof(esort::Seg) == 12, "a record is three words");
+    const uint32_t st[18] = {qs.cnt[0], qs.cnt[1], qs.cnt[2], qs.small_cnt, ws.nseg[0], ws.nseg[1], ws.ntiles[0], ws.ntiles[1], h->dbg_sort[0],
+                             h->dbg_sort[1], h->dbg_sort[2], h->dbg_sort[3], h->dbg_sort[4], c.n_sort_fallback, c.n_voxel_overflow, c.sort_qoverflow,
+                             c.err, std::max(1u, cdiv(h->dbg_sort[0], 1024))};
+    memcpy(state, st, sizeof(st));
+    const esort::Seg *src[4] = {Q(h).essmall.p, Q(h).esq0.p, Q(h).esq1.p, Q(h).esq2.p};
+    int32_t *dst[4] = {smallq, q0, q1, q2};
+    const uint32_t cnt[4] = {qs.small_cnt, qs.cnt[0], qs.cnt[1], qs.cnt[2]};
+    for (int i = 0; i < 4; ++i) {
+        const size_t k = std::min<size_t>(std::min<size_t>(cnt[i], cap), 65536);  // (the queues' capacity: a count beyond it is an overflow, flagged)
+        if (dst[i] && src[i] && k) HIPC(h, hipMemcpy(dst[i], src[i], k * sizeof(esort::Seg), hipMemcpyDeviceToHost));
     }
     return ERASOR_OK;
 }

@@ -150,3 +150,24 @@ def debug_ev_grid_many(g, ests, voxelsize):
     g._check(erasor_amd.lib().erasor_hip_debug_ev_grid_many(g._h, ptrs, sizes, C.c_size_t(k), C.c_double(voxelsize), C.byref(nb), _p(off),
                                                             C.c_size_t(cap), _p(pts), _p(idx), _p(tab)))
     return {"nb": int(nb.value), "off": off[: nb.value + 1], "pts": pts, "idx": idx, "tab": tab}
+
+
+SORT_STATE = ("cnt0", "cnt1", "cnt2", "small_cnt", "nseg0", "nseg1", "ntiles0", "ntiles1", "n", "wide_levels", "level_launches", "mid_run",
+              "final_grid", "n_sort_fallback", "n_voxel_overflow", "sort_qoverflow", "err", "run_tiles")
+
+
+def debug_sort_queues(g):
+    """what the last exact sort of the handle's query side -- exact_sort_u32, or the sort inside a voxelisation -- left behind (read-only):
+    EsQueues and WideState, what run_exact_sort launched (keys, wide levels, k_esort_level launches, whether k_esort_mid ran,
+    k_esort_final's grid), the chain's counters, and the (first, last, depth) records of the finisher's queue ("small") and of the three
+    level queues ("q0", "q1", "q2") up to their counts.  After a sort that ran k_esort_mid, q0 is what that kernel was given."""
+    st = np.zeros(len(SORT_STATE), np.uint32)
+    g._check(erasor_amd.lib().erasor_hip_debug_sort_queues(g._h, _p(st), C.c_void_p(None), C.c_void_p(None), C.c_void_p(None), C.c_void_p(None),
+                                                           C.c_size_t(0)))
+    out = {k: int(v) for k, v in zip(SORT_STATE, st)}
+    cap = max(1, min(65536, max(out["cnt0"], out["cnt1"], out["cnt2"], out["small_cnt"])))
+    rec = [np.zeros((cap, 3), np.int32) for _ in range(4)]
+    g._check(erasor_amd.lib().erasor_hip_debug_sort_queues(g._h, _p(st), _p(rec[0]), _p(rec[1]), _p(rec[2]), _p(rec[3]), C.c_size_t(cap)))
+    for name, r, k in zip(("small", "q0", "q1", "q2"), rec, ("small_cnt", "cnt0", "cnt1", "cnt2")):
+        out[name] = r[: min(out[k], cap)].astype(np.int64)
+    return out
