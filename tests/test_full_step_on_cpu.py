@@ -11,7 +11,9 @@ driven through the C ABI and compared with the oracle.
     VoxelGrid index-overflow pass-through and the NaN refusal (~5 more minutes), and the size classes of a reverted bin
     (tests/test_gpu_bin_sizes.py: its 83 cases of at most 4097 map points, the four-bin launch left out), and the map store at every chunk
     boundary (tests/test_gpu_map_store.py: its 93 cases of at most ~70 k store entries, ~4 more minutes), and the voxelisation chain on every
-    route of its sort and label search (tests/test_gpu_voxelize.py: its 257 cases of at most ~8200 points, ~6 more minutes); ERASOR_SIMT_ALL=1 runs the whole file except
+    route of its sort and label search (tests/test_gpu_voxelize.py: its 257 cases of at most ~8200 points, ~6 more minutes), and the Scan Ratio
+    Test and the reverted-bin list on designed grids (tests/test_gpu_scan_ratio.py: its 171 cases on the small grids and, on 64 x 64 bins,
+    of at most 129 reverted bins, ~9 more minutes); ERASOR_SIMT_ALL=1 runs the whole file except
     the full-size cases (49 tests: every synthetic sequence, v2 / v3, submap mode, look-ahead, mapgen, PR / RR; ~40 minutes).
 
 This is a checker, not a product: the library is built into the test's temporary directory, loaded by helper processes only
@@ -56,6 +58,8 @@ def test_part_of_the_gpu_parity_suite_passes_on_the_cpu_stand_in(simt_lib):
         files, n_min = files + ["test_gpu_map_store.py"], n_min + 93
         # the voxelisation chain on every route of its sort and label search: the cases of at most ~8200 points (the same key)
         files, n_min = files + ["test_gpu_voxelize.py"], n_min + 257
+        # the Scan Ratio Test and the reverted-bin list on designed grids: the small grids, and lists of at most 129 bins (the same key)
+        files, n_min = files + ["test_gpu_scan_ratio.py"], n_min + 171
     expr = " or ".join(keys)
     if os.environ.get("ERASOR_SIMT_ALL"):  # everything but the full-size cases: 49 tests, ~40 minutes on 8 cores
         expr = "not (full_size or config4 or whole_map or long_segments or map_grows)"
