@@ -13,7 +13,9 @@ driven through the C ABI and compared with the oracle.
     boundary (tests/test_gpu_map_store.py: its 93 cases of at most ~70 k store entries, ~4 more minutes), and the voxelisation chain on every
     route of its sort and label search (tests/test_gpu_voxelize.py: its 257 cases of at most ~8200 points, ~6 more minutes), and the Scan Ratio
     Test and the reverted-bin list on designed grids (tests/test_gpu_scan_ratio.py: its 171 cases on the small grids and, on 64 x 64 bins,
-    of at most 129 reverted bins, ~9 more minutes); ERASOR_SIMT_ALL=1 runs the whole file except
+    of at most 129 reverted bins, ~9 more minutes), and the stable bucketing and the bin statistics on designed key sequences
+    (tests/test_gpu_bucketing.py: its 202 cases of at most three map tiles, most of them on grids of at most 2176 bins,
+    ~11 more minutes); ERASOR_SIMT_ALL=1 runs the whole file except
     the full-size cases (49 tests: every synthetic sequence, v2 / v3, submap mode, look-ahead, mapgen, PR / RR; ~40 minutes).
 
 This is a checker, not a product: the library is built into the test's temporary directory, loaded by helper processes only
@@ -60,11 +62,13 @@ def test_part_of_the_gpu_parity_suite_passes_on_the_cpu_stand_in(simt_lib):
         files, n_min = files + ["test_gpu_voxelize.py"], n_min + 257
         # the Scan Ratio Test and the reverted-bin list on designed grids: the small grids, and lists of at most 129 bins (the same key)
         files, n_min = files + ["test_gpu_scan_ratio.py"], n_min + 171
+        # the stable bucketing and the bin statistics on designed key sequences: at most three map tiles, ~4100 bins (the same key)
+        files, n_min = files + ["test_gpu_bucketing.py"], n_min + 202
     expr = " or ".join(keys)
     if os.environ.get("ERASOR_SIMT_ALL"):  # everything but the full-size cases: 49 tests, ~40 minutes on 8 cores
         expr = "not (full_size or config4 or whole_map or long_segments or map_grows)"
         files, n_min = ["test_gpu_parity.py", "test_gpu_hooks.py"], 9
-    simt.run_gpu_tests_on_stand_in(simt_lib, files, expr, n_min, timeout=7200 if os.environ.get("ERASOR_SIMT_ALL") else 2400)
+    simt.run_gpu_tests_on_stand_in(simt_lib, files, expr, n_min, timeout=7200 if os.environ.get("ERASOR_SIMT_ALL") else (4800 if os.environ.get("ERASOR_SIMT_MORE") else 2400))
 
 
 def test_the_references_own_vectors_are_reproduced_on_the_cpu_stand_in(simt_lib):
