@@ -9,23 +9,9 @@ extern "C" {
 
 // ---- what the offline analyses share: the checks of their arguments, the caller's clouds and the handle's map on the device ----
 
-// The analyses run on the main stream, behind whatever a collected step launched ahead there, in the evaluator's scratch (h->ev): LAUNCH
-// follows h->cur, which points at the main stream until the scope ends.  bank2: the call sorts (a tree's Morton keys, the instances'
-// records); its radix sort then runs in histogram bank 2, so that the query chains of nodes announced ahead (bank 0) keep theirs.
-struct MainStreamScope {
-    erasor_hip_handle *h;
-    hipStream_t cur;
-    int bank;
-    bool bank2;
-    explicit MainStreamScope(erasor_hip_handle *hh, bool bank2_ = false) : h(hh), cur(hh->cur), bank(hh->bank), bank2(bank2_) {
-        h->cur = h->stream;
-        if (bank2) h->bank = 2;
-    }
-    ~MainStreamScope() {
-        h->cur = cur;
-        if (bank2) h->bank = bank;
-    }
-};
+// The analyses run on the main stream (every launch names h->stream), behind whatever a collected step launched ahead there, in the
+// evaluator's scratch (h->ev).  Where one sorts (a tree's Morton keys, the instances' records) its radix sort runs in histogram bank 2, so
+// that the query chains of nodes announced ahead (bank 0) keep theirs.
 
 static int invalid(erasor_hip_handle *h, const std::string &who, const std::string &why) {
     h->err = who + ": " + why;
@@ -101,7 +87,6 @@ static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const f
     if (n_rec && (ensure(h, E.bc_tab, (size_t)EV_NKEYS * EV_KC) || ensure(h, E.bc_cur, 4) || ensure(h, E.bc_ikey, n_all + 1) ||
                   ensure(h, E.bc_ival, n_all + 1)))
         return ERASOR_E_NO_DEVICE;
-    MainStreamScope scope(h);
     HIPC(h, hipMemsetAsync(E.ctr.p, 0, EV_NCTR * sizeof(unsigned long long), h->stream));
     if (n_rec) {
         HIPC(h, hipMemsetAsync(E.bc_tab.p, 0, (size_t)EV_NKEYS * EV_KC * sizeof(uint32_t), h->stream));
@@ -111,19 +96,19 @@ static int ev_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const f
     if (n_est) {
         HIPC(h, hipMemsetAsync(E.cnt.p, 0, ((size_t)nb + 1) * sizeof(uint32_t), h->stream));
         if (n_rec)
-            LAUNCH(h, "ev_index", k_ev_hist_keys, cdiv(n_est, 256), 256, est, n_est, voxelsize, nb - 1, E.bkt.p, E.cnt.p, E.ctr.p, E.bc_tab.p, E.bc_cur.p,
+            LAUNCH(h, h->stream, "ev_index", k_ev_hist_keys, cdiv(n_est, 256), 256, est, n_est, voxelsize, nb - 1, E.bkt.p, E.cnt.p, E.ctr.p, E.bc_tab.p, E.bc_cur.p,
                    E.bc_ikey.p, E.bc_ival.p);
         else
-            LAUNCH(h, "ev_index", k_ev_hist, cdiv(n_est, 256), 256, est, n_est, voxelsize, nb - 1, E.bkt.p, E.cnt.p, E.ctr.p);
-        scan_u32(h, E.cnt.p, E.pl.p, E.tops.p, nb + 1, nb + 1, nullptr, nullptr, "ev_index");
-        LAUNCH(h, "ev_index", k_ev_offsets, cdiv(nb + 1, 256), 256, (const uint32_t *)E.pl.p, (const uint32_t *)E.tops.p, nb + 1, E.cnt.p, E.pl.p);
-        LAUNCH(h, "ev_index", k_ev_scatter, cdiv(n_est, 256), 256, est, n_est, (const uint32_t *)E.bkt.p, E.pl.p, E.pts.p, E.idx.p);
+            LAUNCH(h, h->stream, "ev_index", k_ev_hist, cdiv(n_est, 256), 256, est, n_est, voxelsize, nb - 1, E.bkt.p, E.cnt.p, E.ctr.p);
+        scan_u32(h, h->stream, E.cnt.p, E.pl.p, E.tops.p, nb + 1, nb + 1, nullptr, nullptr, "ev_index");
+        LAUNCH(h, h->stream, "ev_index", k_ev_offsets, cdiv(nb + 1, 256), 256, (const uint32_t *)E.pl.p, (const uint32_t *)E.tops.p, nb + 1, E.cnt.p, E.pl.p);
+        LAUNCH(h, h->stream, "ev_index", k_ev_scatter, cdiv(n_est, 256), 256, est, n_est, (const uint32_t *)E.bkt.p, E.pl.p, E.pts.p, E.idx.p);
     }
     if (n_gt && n_rec)
-        LAUNCH(h, "ev_query", k_ev_query_keys, cdiv(n_gt, 256), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p,
+        LAUNCH(h, h->stream, "ev_query", k_ev_query_keys, cdiv(n_gt, 256), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p,
                (const uint32_t *)E.cnt.p, nb - 1, n_est, voxelsize, thr, E.ctr.p, E.bc_tab.p, E.bc_cur.p, E.bc_ikey.p, E.bc_ival.p);
     else if (n_gt)
-        LAUNCH(h, "ev_query", k_ev_query, cdiv(n_gt, 256), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p, (const uint32_t *)E.cnt.p,
+        LAUNCH(h, h->stream, "ev_query", k_ev_query, cdiv(n_gt, 256), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p, (const uint32_t *)E.cnt.p,
                nb - 1, n_est, voxelsize, thr, want_codes ? E.code.p : (uint8_t *)nullptr, E.ctr.p);
     unsigned long long c[EV_NCTR];
     HIPC(h, hipMemcpyAsync(c, E.ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
@@ -169,7 +154,7 @@ static int ev_voxelize(erasor_hip_handle *h, const float4 *src, uint32_t n, doub
     const int rc = voxelize_device(h, src, n, leaf, &nq, passthrough);
     if (rc) return rc;
     if (ensure(h, dst, off + nq + 1)) return ERASOR_E_NO_DEVICE;  // (nq <= n: no reallocation when src is dst itself)
-    if (nq) HIPC(h, hipMemcpyAsync(dst.p + off, Q(h).query.p, (size_t)nq * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
+    if (nq) HIPC(h, hipMemcpyAsync(dst.p + off, h->q[h->qi].query.p, (size_t)nq * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
     *n_out = nq;
     return ERASOR_OK;
@@ -286,24 +271,23 @@ static int evm_run(erasor_hip_handle *h, const char *who, const float4 *gt, uint
     if (ensure(h, E.em_tab, k + 1) || ensure(h, E.em_ctr, (k + 1) * EV_NCTR) || ensure(h, E.cnt, (size_t)nb + 1) || ensure(h, E.pl, (size_t)nb + 1) ||
         ensure(h, E.tops, nb / 1024 + 4) || ensure(h, E.bkt, (size_t)n + 1) || ensure(h, E.pts, (size_t)n + 1) || ensure(h, E.idx, (size_t)n + 1))
         return ERASOR_E_NO_DEVICE;
-    MainStreamScope scope(h);
     HIPC(h, hipMemcpyAsync(E.em_tab.p, tab.data(), (k + 1) * sizeof(EvmEst), hipMemcpyHostToDevice, h->stream));
     HIPC(h, hipMemsetAsync(E.em_ctr.p, 0, (k + 1) * EV_NCTR * sizeof(unsigned long long), h->stream));
     const double thr = (voxelsize * sqrt(3.0)) / 2.0;  // (ev_run's)
     if (n) {
         HIPC(h, hipMemsetAsync(E.cnt.p, 0, ((size_t)nb + 1) * sizeof(uint32_t), h->stream));
-        LAUNCH(h, "evm_index", k_evm_hist, (uint32_t)blk, 256, (const float4 *)E.em_cat.p, (const EvmEst *)E.em_tab.p, (uint32_t)k, voxelsize, E.bkt.p,
+        LAUNCH(h, h->stream, "evm_index", k_evm_hist, (uint32_t)blk, 256, (const float4 *)E.em_cat.p, (const EvmEst *)E.em_tab.p, (uint32_t)k, voxelsize, E.bkt.p,
                E.cnt.p, E.em_ctr.p);
-        scan_u32(h, E.cnt.p, E.pl.p, E.tops.p, nb + 1, nb + 1, nullptr, nullptr, "evm_index");
-        LAUNCH(h, "evm_index", k_ev_offsets, cdiv(nb + 1, 256), 256, (const uint32_t *)E.pl.p, (const uint32_t *)E.tops.p, nb + 1, E.cnt.p, E.pl.p);
-        LAUNCH(h, "evm_index", k_ev_scatter, cdiv(n, 256), 256, (const float4 *)E.em_cat.p, n, (const uint32_t *)E.bkt.p, E.pl.p, E.pts.p, E.idx.p);
+        scan_u32(h, h->stream, E.cnt.p, E.pl.p, E.tops.p, nb + 1, nb + 1, nullptr, nullptr, "evm_index");
+        LAUNCH(h, h->stream, "evm_index", k_ev_offsets, cdiv(nb + 1, 256), 256, (const uint32_t *)E.pl.p, (const uint32_t *)E.tops.p, nb + 1, E.cnt.p, E.pl.p);
+        LAUNCH(h, h->stream, "evm_index", k_ev_scatter, cdiv(n, 256), 256, (const float4 *)E.em_cat.p, n, (const uint32_t *)E.bkt.p, E.pl.p, E.pts.p, E.idx.p);
     }
     if (n_gt) {
         // one estimate per blockIdx.y: workgroups are dispatched x fastest, so the estimates are searched one after the other, each
         // against its own bucket table while that is cache-resident.  (All K in one lane's loop reads the GT once but walks K tables at
         // a time: for 8 estimates of 9.8 M points against a 9.8 M-point GT that took 147 ms against 137 ms for 8 evaluate_clouds calls.)
         const uint32_t gx = cdiv(n_gt, 256), per_y = 1, gy = (uint32_t)std::max<size_t>(k, 1);
-        LAUNCH(h, "evm_query", k_evm_query, dim3(gx, gy), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p, (const uint32_t *)E.cnt.p,
+        LAUNCH(h, h->stream, "evm_query", k_evm_query, dim3(gx, gy), 256, gt, n_gt, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p, (const uint32_t *)E.cnt.p,
                (const EvmEst *)E.em_tab.p, (uint32_t)k, per_y, voxelsize, thr, E.em_ctr.p);
     }
     std::vector<unsigned long long> c((k + 1) * EV_NCTR);
@@ -434,17 +418,17 @@ static int nn_tree(erasor_hip_handle *h, const float4 *pts, uint32_t n, uint32_t
     // the box: k_bbox's fkey_ord min (3 x ~0u) / max (3 x 0)
     HIPC(h, hipMemsetAsync(E.nn_bb.p, 0xFF, 3 * sizeof(uint32_t), h->stream));
     HIPC(h, hipMemsetAsync(E.nn_bb.p + 3, 0, 3 * sizeof(uint32_t), h->stream));
-    LAUNCH(h, "ov_tree", k_bbox, bbox_grid(n), 256, pts, n, E.nn_bb.p);
-    LAUNCH(h, "ov_tree", k_nn_keys, cdiv(n, 256), 256, pts, n, (const uint32_t *)E.nn_bb.p, E.nn_key.p, E.nn_ctr.p);
+    LAUNCH(h, h->stream, "ov_tree", k_bbox, bbox_grid(n), 256, pts, n, E.nn_bb.p);
+    LAUNCH(h, h->stream, "ov_tree", k_nn_keys, cdiv(n, 256), 256, pts, n, (const uint32_t *)E.nn_bb.p, E.nn_key.p, E.nn_ctr.p);
     const uint32_t *skeys = nullptr, *sperm = nullptr;
-    if (radix_sort(h, E.nn_key.p, n, nullptr, 30, E.nn_ka.p, E.nn_kb.p, E.nn_va.p, E.nn_vb.p, &skeys, &sperm, "ov_tree"))
+    if (radix_sort(h, h->stream, 2, E.nn_key.p, n, nullptr, 30, E.nn_ka.p, E.nn_kb.p, E.nn_va.p, E.nn_vb.p, &skeys, &sperm, "ov_tree"))
         return ERASOR_E_NO_DEVICE;
 #ifdef ERASOR_HIP_TEST_HOOKS
     E.dbg_skeys = skeys;
 #endif
-    LAUNCH(h, "ov_tree", k_nn_gather, cdiv(n, 256), 256, pts, n, sperm, E.nn_pts.p, E.nn_idx.p);
-    LAUNCH(h, "ov_tree", k_nn_leaves, cdiv(P * NN_LEAF, 256), 256, (const float4 *)E.nn_pts.p, n, P, E.nn_lo.p, E.nn_hi.p);
-    for (uint32_t first = P / 2; first >= 1; first /= 2) LAUNCH(h, "ov_tree", k_nn_level, cdiv(first, 256), 256, E.nn_lo.p, E.nn_hi.p, first);
+    LAUNCH(h, h->stream, "ov_tree", k_nn_gather, cdiv(n, 256), 256, pts, n, sperm, E.nn_pts.p, E.nn_idx.p);
+    LAUNCH(h, h->stream, "ov_tree", k_nn_leaves, cdiv(P * NN_LEAF, 256), 256, (const float4 *)E.nn_pts.p, n, P, E.nn_lo.p, E.nn_hi.p);
+    for (uint32_t first = P / 2; first >= 1; first /= 2) LAUNCH(h, h->stream, "ov_tree", k_nn_level, cdiv(first, 256), 256, E.nn_lo.p, E.nn_hi.p, first);
     unsigned long long c[OV_NCTR];
     HIPC(h, hipMemcpyAsync(c, E.nn_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
@@ -485,7 +469,7 @@ static int ov_select(erasor_hip_handle *h, const unsigned long long *v, uint32_t
             slot[t] = k;
         }
         HIPC(h, hipMemsetAsync(E.nn_hist.p, 0, (size_t)s.n * 256 * sizeof(uint32_t), h->stream));
-        LAUNCH(h, "ov_select", k_ov_select_hist, grid, 256, v, count, s, E.nn_hist.p);
+        LAUNCH(h, h->stream, "ov_select", k_ov_select_hist, grid, 256, v, count, s, E.nn_hist.p);
         HIPC(h, hipMemcpyAsync(hist.data(), E.nn_hist.p, (size_t)s.n * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
         for (uint32_t t = 0; t < OV_SEL_MAX; ++t) {
@@ -531,7 +515,6 @@ static void ov_fill(uint64_t n, uint64_t below_half, uint64_t below_one, uint64_
 static int ov_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize, double *per_dist,
                   uint32_t *per_nearest, erasor_overlap_result *res) {
     auto &E = h->ev;
-    MainStreamScope scope(h, true);
     uint32_t P = 1;
     int rc = nn_pad(h, n_gt, &P, "erasor_hip_overlap", "ground truth");
     if (rc) return rc;
@@ -544,7 +527,7 @@ static int ov_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const f
     // the thresholds as overlap_report forms them: half = 0.5 * voxelsize, one = voxelsize, 2 * one
     const double half = 0.5 * voxelsize, one = voxelsize, two = 2 * one;
     if (n_est)
-        LAUNCH(h, "ov_query", k_nn_query, cdiv(n_est, NN_QBLOCK), NN_QBLOCK, est, n_est, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p,
+        LAUNCH(h, h->stream, "ov_query", k_nn_query, cdiv(n_est, NN_QBLOCK), NN_QBLOCK, est, n_est, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p,
                n_gt, (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, half, one, two, E.nn_dbits.p,
                per_nearest ? E.nn_near.p : (uint32_t *)nullptr, E.nn_ctr.p);
     HIPC(h, hipMemcpyAsync(c, E.nn_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
@@ -624,7 +607,6 @@ static int al_run(erasor_hip_handle *h, const char *who, const float4 *map, uint
                   uint32_t n_frames, const float *T_lidar2body, const float *T_body2origin, double voxelsize, erasor_align_row *rows,
                   erasor_overlap_result *summary) {
     auto &E = h->ev;
-    MainStreamScope scope(h, true);
     if (!n_map && n) {
         h->err = std::string(who) + ": empty map with a non-empty frame (no nearest point to measure against)";
         return ERASOR_E_INVALID;
@@ -657,7 +639,7 @@ static int al_run(erasor_hip_handle *h, const char *who, const float4 *map, uint
     // the thresholds as overlap_report forms them: half = 0.5 * voxelsize, one = voxelsize, 2 * one
     const double half = 0.5 * voxelsize, one = voxelsize, two = 2 * one;
     if (n)
-        LAUNCH(h, "al_query", k_al_query, grid, NN_QBLOCK, scans, n, (const uint32_t *)E.al_off.p, (const uint32_t *)E.al_wg.p,
+        LAUNCH(h, h->stream, "al_query", k_al_query, grid, NN_QBLOCK, scans, n, (const uint32_t *)E.al_off.p, (const uint32_t *)E.al_wg.p,
                to_xf(T_lidar2body ? T_lidar2body : I), (const Xf *)E.al_xf.p, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, n_map,
                (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, half, one, two, E.nn_dbits.p, E.al_ctr.p);
     std::vector<unsigned long long> c((size_t)nf * AL_NCTR);
@@ -685,7 +667,7 @@ static int al_run(erasor_hip_handle *h, const char *who, const float4 *map, uint
     }
     if (n_kept) {
         HIPC(h, hipMemcpyAsync(E.al_rank.p, rk.data(), n_frames * sizeof(AlRanks), hipMemcpyHostToDevice, h->stream));
-        LAUNCH(h, "al_select", k_al_select, n_frames, 256, (const unsigned long long *)E.nn_dbits.p, (const uint32_t *)E.al_off.p,
+        LAUNCH(h, h->stream, "al_select", k_al_select, n_frames, 256, (const unsigned long long *)E.nn_dbits.p, (const uint32_t *)E.al_off.p,
                (const AlRanks *)E.al_rank.p, E.al_val.p);
         HIPC(h, hipMemcpyAsync(v.data(), E.al_val.p, v.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
@@ -780,7 +762,6 @@ int erasor_hip_label_map(erasor_hip_handle *h, const void *src_xyzi, size_t n_sr
     bool passthrough = false;
     if ((rc = ev_voxelize(h, s, (uint32_t)n_src, leaf, E.est, &nq, &passthrough))) return rc;
     // 2. every centroid takes the intensity of its nearest medium point (KdTreeFLANN, K = 1)
-    MainStreamScope scope(h, true);
     const uint32_t nm = (uint32_t)n_medium;
     uint32_t P = 1;
     if ((rc = nn_pad(h, nm, &P, "erasor_hip_label_map", "medium"))) return rc;
@@ -789,7 +770,7 @@ int erasor_hip_label_map(erasor_hip_handle *h, const void *src_xyzi, size_t n_sr
     if ((rc = nn_tree(h, m, nm, P, "erasor_hip_label_map", "medium point(s)"))) return rc;
     HIPC(h, hipMemsetAsync(E.fm_ctr.p, 0, FM_NCTR * sizeof(unsigned long long), h->stream));
     if (nq)
-        LAUNCH(h, "lm_query", k_lm_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, (const float4 *)E.est.p, nq, (const float4 *)E.nn_pts.p,
+        LAUNCH(h, h->stream, "lm_query", k_lm_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, (const float4 *)E.est.p, nq, (const float4 *)E.nn_pts.p,
                (const uint32_t *)E.nn_idx.p, nm, (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, E.fm_out.p, E.fm_ctr.p);
     unsigned long long c[FM_NCTR];
     HIPC(h, hipMemcpyAsync(c, E.fm_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
@@ -828,7 +809,6 @@ int erasor_hip_static_complement(erasor_hip_handle *h, const void *est_xyzi, siz
     auto &E = h->ev;
     const float4 *e = nullptr, *g = nullptr;
     if ((rc = ev_input(h, est_xyzi, n_est, est_is_device, E.est, &e)) || (rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, E.gt, &g))) return rc;
-    MainStreamScope scope(h, true);
     const uint32_t ne = (uint32_t)n_est, ng = (uint32_t)n_gt;
     uint32_t P = 1;
     if ((rc = nn_pad(h, ne, &P, "erasor_hip_static_complement", "estimate"))) return rc;
@@ -839,11 +819,11 @@ int erasor_hip_static_complement(erasor_hip_handle *h, const void *est_xyzi, siz
     if (ne && (rc = nn_tree(h, e, ne, P, "erasor_hip_static_complement", "estimated point(s)"))) return rc;
     HIPC(h, hipMemsetAsync(E.fm_ctr.p, 0, FM_NCTR * sizeof(unsigned long long), h->stream));
     // the lost flags, then the lost points in ground-truth order: an exclusive scan of the flags and a scatter (no atomic decides a slot)
-    LAUNCH(h, "cp_query", k_cp_query, cdiv(ng, NN_QBLOCK), NN_QBLOCK, g, ng, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, ne,
+    LAUNCH(h, h->stream, "cp_query", k_cp_query, cdiv(ng, NN_QBLOCK), NN_QBLOCK, g, ng, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, ne,
            (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, 0.03, E.fm_flag.p, E.fm_ctr.p);
     if (dst_xyzi) {
-        scan_u32(h, E.fm_flag.p, E.fm_pl.p, E.fm_tops.p, ng, ng, nullptr, nullptr, "cp_compact");
-        LAUNCH(h, "cp_compact", k_f_compact, cdiv(ng, 256), 256, g, ng, (const uint32_t *)E.fm_flag.p, (const uint32_t *)E.fm_pl.p,
+        scan_u32(h, h->stream, E.fm_flag.p, E.fm_pl.p, E.fm_tops.p, ng, ng, nullptr, nullptr, "cp_compact");
+        LAUNCH(h, h->stream, "cp_compact", k_f_compact, cdiv(ng, 256), 256, g, ng, (const uint32_t *)E.fm_flag.p, (const uint32_t *)E.fm_pl.p,
                (const uint32_t *)E.fm_tops.p, E.fm_out.p);
     }
     unsigned long long c[FM_NCTR];
@@ -889,14 +869,13 @@ static int bc_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const f
     int rc = ev_run(h, gt, n_gt, est, n_est, voxelsize, nullptr, res, &n_rec);
     if (rc) return rc;
     auto &E = h->ev;
-    MainStreamScope scope(h, true);
     const size_t n_scan = std::max<size_t>(EV_NKEYS, n_rec) + 1;
     if (ensure(h, E.bc_flag, n_scan) || ensure(h, E.bc_pl, n_scan) || ensure(h, E.bc_tops, n_scan / 1024 + 4) ||
         ensure(h, E.bc_crows, (size_t)EV_NKEYS * EV_ROW))
         return ERASOR_E_NO_DEVICE;
-    LAUNCH(h, "ev_rows", k_ev_class_flags, cdiv(EV_NKEYS, 256), 256, (const uint32_t *)E.bc_tab.p, E.bc_flag.p);
-    scan_u32(h, E.bc_flag.p, E.bc_pl.p, E.bc_tops.p, EV_NKEYS, EV_NKEYS, nullptr, E.bc_cur.p + 1, "ev_rows");
-    LAUNCH(h, "ev_rows", k_ev_class_rows, cdiv(EV_NKEYS, 256), 256, (const uint32_t *)E.bc_tab.p, (const uint32_t *)E.bc_flag.p,
+    LAUNCH(h, h->stream, "ev_rows", k_ev_class_flags, cdiv(EV_NKEYS, 256), 256, (const uint32_t *)E.bc_tab.p, E.bc_flag.p);
+    scan_u32(h, h->stream, E.bc_flag.p, E.bc_pl.p, E.bc_tops.p, EV_NKEYS, EV_NKEYS, nullptr, E.bc_cur.p + 1, "ev_rows");
+    LAUNCH(h, h->stream, "ev_rows", k_ev_class_rows, cdiv(EV_NKEYS, 256), 256, (const uint32_t *)E.bc_tab.p, (const uint32_t *)E.bc_flag.p,
            (const uint32_t *)E.bc_pl.p, (const uint32_t *)E.bc_tops.p, E.bc_crows.p);
     uint32_t n_cls = 0;
     HIPC(h, hipMemcpyAsync(&n_cls, E.bc_cur.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
@@ -906,12 +885,12 @@ static int bc_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const f
         if (ensure(h, E.nn_ka, n1) || ensure(h, E.nn_kb, n1) || ensure(h, E.nn_va, n1) || ensure(h, E.nn_vb, n1) || ensure(h, E.bc_irows, n1 * EV_ROW))
             return ERASOR_E_NO_DEVICE;
         const uint32_t *skeys = nullptr, *sperm = nullptr;
-        if (radix_sort(h, E.bc_ikey.p, n_rec, nullptr, 32, E.nn_ka.p, E.nn_kb.p, E.nn_va.p, E.nn_vb.p, &skeys, &sperm, "ev_rows"))
+        if (radix_sort(h, h->stream, 2, E.bc_ikey.p, n_rec, nullptr, 32, E.nn_ka.p, E.nn_kb.p, E.nn_va.p, E.nn_vb.p, &skeys, &sperm, "ev_rows"))
             return ERASOR_E_NO_DEVICE;
-        LAUNCH(h, "ev_rows", k_ev_run_heads, cdiv(n_rec, 256), 256, skeys, n_rec, E.bc_flag.p);
-        scan_u32(h, E.bc_flag.p, E.bc_pl.p, E.bc_tops.p, n_rec, n_rec, nullptr, E.bc_cur.p + 2, "ev_rows");
+        LAUNCH(h, h->stream, "ev_rows", k_ev_run_heads, cdiv(n_rec, 256), 256, skeys, n_rec, E.bc_flag.p);
+        scan_u32(h, h->stream, E.bc_flag.p, E.bc_pl.p, E.bc_tops.p, n_rec, n_rec, nullptr, E.bc_cur.p + 2, "ev_rows");
         HIPC(h, hipMemsetAsync(E.bc_irows.p, 0, (size_t)n_rec * EV_ROW * sizeof(uint32_t), h->stream));
-        LAUNCH(h, "ev_rows", k_ev_inst_rows, cdiv(n_rec, 256), 256, skeys, sperm, (const uint32_t *)E.bc_ival.p, (const uint32_t *)E.bc_flag.p,
+        LAUNCH(h, h->stream, "ev_rows", k_ev_inst_rows, cdiv(n_rec, 256), 256, skeys, sperm, (const uint32_t *)E.bc_ival.p, (const uint32_t *)E.bc_flag.p,
                (const uint32_t *)E.bc_pl.p, (const uint32_t *)E.bc_tops.p, n_rec, E.bc_irows.p);
         HIPC(h, hipMemcpyAsync(&n_inst, E.bc_cur.p + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     }
@@ -1037,11 +1016,10 @@ static int rd_fit(erasor_hip_handle *h, const float4 *pts, uint32_t n, double re
     }
     if (ensure(h, E.rd_zb, (size_t)n + 1) || ensure(h, E.rd_bb, 4) || ensure(h, E.rd_ctr, RD_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256))
         return ERASOR_E_NO_DEVICE;
-    MainStreamScope scope(h);
     HIPC(h, hipMemsetAsync(E.rd_bb.p, 0xFF, 2 * sizeof(uint32_t), h->stream));
     HIPC(h, hipMemsetAsync(E.rd_bb.p + 2, 0, 2 * sizeof(uint32_t), h->stream));
     HIPC(h, hipMemsetAsync(E.rd_ctr.p, 0, sizeof(unsigned long long), h->stream));
-    if (n) LAUNCH(h, "render_fit", k_rd_fit, cdiv(n, 2048), 256, pts, n, E.rd_zb.p, E.rd_bb.p, E.rd_ctr.p);
+    if (n) LAUNCH(h, h->stream, "render_fit", k_rd_fit, cdiv(n, 2048), 256, pts, n, E.rd_zb.p, E.rd_bb.p, E.rd_ctr.p);
     uint32_t bb[4];
     unsigned long long nfin = 0;
     HIPC(h, hipMemcpyAsync(bb, E.rd_bb.p, sizeof(bb), hipMemcpyDeviceToHost, h->stream));
@@ -1119,18 +1097,17 @@ static int rd_run(erasor_hip_handle *h, const float4 *pts, uint32_t n, const uin
         ensure(h, E.rd_tops, ntiles / 1024 + 4) || ensure(h, E.rd_tile, (size_t)n + 1) || ensure(h, E.rd_rec, (size_t)n + 1) ||
         ensure(h, E.rd_srt, (size_t)n + 1) || ensure(h, E.rd_img, bytes + 4))
         return ERASOR_E_NO_DEVICE;
-    MainStreamScope scope(h);
     if (ev_begin) HIPC(h, hipEventRecord(ev_begin, h->stream));
     HIPC(h, hipMemsetAsync(E.rd_ctr.p, 0, RD_NCTR * sizeof(unsigned long long), h->stream));
     HIPC(h, hipMemsetAsync(E.rd_cnt.p, 0, ((size_t)ntiles + 1) * sizeof(uint32_t), h->stream));
-    if (n) LAUNCH(h, "render_bin", k_rd_bin, cdiv(n, 256), 256, pts, n, code, v, m, E.rd_tile.p, E.rd_rec.p, E.rd_cnt.p, E.rd_ctr.p);
-    scan_u32(h, E.rd_cnt.p, E.rd_pl.p, E.rd_tops.p, ntiles + 1, ntiles + 1, nullptr, nullptr, "render_scan");
-    LAUNCH(h, "render_scan", k_ev_offsets, cdiv(ntiles + 1, 256), 256, (const uint32_t *)E.rd_pl.p, (const uint32_t *)E.rd_tops.p, ntiles + 1, E.rd_cnt.p,
+    if (n) LAUNCH(h, h->stream, "render_bin", k_rd_bin, cdiv(n, 256), 256, pts, n, code, v, m, E.rd_tile.p, E.rd_rec.p, E.rd_cnt.p, E.rd_ctr.p);
+    scan_u32(h, h->stream, E.rd_cnt.p, E.rd_pl.p, E.rd_tops.p, ntiles + 1, ntiles + 1, nullptr, nullptr, "render_scan");
+    LAUNCH(h, h->stream, "render_scan", k_ev_offsets, cdiv(ntiles + 1, 256), 256, (const uint32_t *)E.rd_pl.p, (const uint32_t *)E.rd_tops.p, ntiles + 1, E.rd_cnt.p,
            E.rd_pl.p);
     if (n)
-        LAUNCH(h, "render_scatter", k_rd_scatter, cdiv(n, 256), 256, (const uint32_t *)E.rd_tile.p, (const unsigned long long *)E.rd_rec.p, n, E.rd_pl.p,
+        LAUNCH(h, h->stream, "render_scatter", k_rd_scatter, cdiv(n, 256), 256, (const uint32_t *)E.rd_tile.p, (const unsigned long long *)E.rd_rec.p, n, E.rd_pl.p,
                E.rd_srt.p);
-    LAUNCH(h, "render_resolve", k_rd_resolve, ntiles, 256, (const unsigned long long *)E.rd_srt.p, (const uint32_t *)E.rd_cnt.p, v, m, E.rd_img.p,
+    LAUNCH(h, h->stream, "render_resolve", k_rd_resolve, ntiles, 256, (const unsigned long long *)E.rd_srt.p, (const uint32_t *)E.rd_cnt.p, v, m, E.rd_img.p,
            E.rd_ctr.p);
     if (ev_end) HIPC(h, hipEventRecord(ev_end, h->stream));
     unsigned long long c[RD_NCTR];
@@ -1295,7 +1272,6 @@ int erasor_hip_debug_nn_tree(erasor_hip_handle *h, const void *xyzi, size_t n, i
     const float4 *g = nullptr;
     int rc = ev_input(h, xyzi, n, is_device, E.gt, &g);
     if (rc) return rc;
-    MainStreamScope scope(h, true);
     uint32_t P = 1;
     if ((rc = nn_pad(h, (uint32_t)n, &P, "erasor_hip_debug_nn_tree", "cloud"))) return rc;
     if (ensure(h, E.nn_ctr, OV_NCTR)) return ERASOR_E_NO_DEVICE;
@@ -1324,7 +1300,6 @@ int erasor_hip_debug_nn_effort(erasor_hip_handle *h, const float *tree_xyzi, siz
     const float4 *g = nullptr, *q = nullptr;
     int rc;
     if ((rc = ev_input(h, tree_xyzi, n, 0, E.gt, &g)) || (rc = ev_input(h, query_xyzi, n_q, 0, E.est, &q))) return rc;
-    MainStreamScope scope(h, true);
     const uint32_t nt = (uint32_t)n, nq = (uint32_t)n_q;
     uint32_t P = 1;
     if ((rc = nn_pad(h, nt, &P, "erasor_hip_debug_nn_effort", "cloud"))) return rc;
@@ -1339,10 +1314,10 @@ int erasor_hip_debug_nn_effort(erasor_hip_handle *h, const float *tree_xyzi, siz
     (void)hipMemsetAsync(d_eff, 0xFF, 2 * n_q * sizeof(uint32_t), h->stream);
     hipLaunchKernelGGL(k_nn_set_effort, dim3(1), dim3(1), 0, h->stream, d_eff);
     if (f32)
-        LAUNCH(h, "lm_query", k_lm_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, q, nq, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, nt,
+        LAUNCH(h, h->stream, "lm_query", k_lm_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, q, nq, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, nt,
                (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, E.fm_out.p, E.fm_ctr.p);
     else
-        LAUNCH(h, "ov_query", k_nn_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, q, nq, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, nt,
+        LAUNCH(h, h->stream, "ov_query", k_nn_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, q, nq, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, nt,
                (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, 0.5, 1.0, 2.0, E.nn_dbits.p, E.nn_near.p, E.nn_ctr.p);
     hipLaunchKernelGGL(k_nn_set_effort, dim3(1), dim3(1), 0, h->stream, (uint32_t *)nullptr);
     unsigned long long c[FM_NCTR], co[OV_NCTR];
@@ -1489,7 +1464,7 @@ void sweep_one(const SweepIn &in, SweepJob &J) {
     const float4 *src = h->ev.map.p;
     if (!rc && in.save_leaf > 0 && n_final) {
         rc = voxelize_device(h, h->ev.map.p, (uint32_t)n_final, in.save_leaf, &nq);
-        src = Q(h).query.p;
+        src = h->q[h->qi].query.p;
     }
     if (!rc) {
         J.n_map_final = n_final;

@@ -177,7 +177,6 @@ struct erasor_hip_handle {
     // `batch_lead` chains are in their queues in front of them (then latency matters more than queue time)
     int batch_n = 2, batch_lead = 3;
     unsigned long long n_batches = 0, n_batched_chains = 0;
-    hipStream_t cur = nullptr;      // stream LAUNCH() currently targets
     int pend[MAX_AHEAD] = {0};  // query sides with a prefetched chain in flight (or held back for a shared set of launches), oldest first
     int npend = 0;
     // a scan announced by erasor_hip_prefetch_scan whose chain is not enqueued yet (the step in flight goes first)
@@ -197,7 +196,7 @@ struct erasor_hip_handle {
         float To[16] = {0};
     } ann;
     int last_ann_side = -1;  // the side of the most recent announcement (erasor_hip_announce_origin2body attaches to it)
-    int step_side = -1;      // the side of the step in flight / of the last step collected: its arrays are read by that step's launches and by the getters
+    int step_side = -1;      // qi once a step has been admitted, -1 before: the side alloc_scan must leave alone (the step's launches and the getters read its arrays)
     uint64_t next_ticket = 1;
     // the NEXT step's VoI split (and chunk scan), launched ahead behind this step's k_step_end when the next scan was announced with its pose
     Ahead spec;
@@ -275,8 +274,6 @@ struct erasor_hip_handle {
         bool deep = false;        // the caller had announced at least batch_lead nodes beyond this step (OvAuto samples only such steps)
     } fly;
     HostOut *pin = nullptr;         // pinned host block k_step_end reports into
-    int bank = 0;                   // scratch bank of scan/radix helpers (0: query chains, 1: map chain, 2: the evaluators: the overlap
-                                    // report's tree, the instance rows of the breakdown by class)
     std::string err;
     bool have_map = false, have_step = false;
     bool poisoned = false;        // a step failed after the map store had been touched: only set_map makes the handle usable again
@@ -324,7 +321,8 @@ struct erasor_hip_handle {
     // ---- query side: everything the voxelisation / bucketing of ONE scan owns.  Two sets, so that the query chain of the
     // next scan (erasor_hip_prefetch_scan) can run while the current step is in its map-side stages ----
     QSide q[NSIDE];
-    int qi = 0;                      // the set the calls below work on
+    int qi = 0;  // the side of the step being enqueued or last collected: the getters and assemble_egocentric read it, the standalone entry
+                 // points (voxelize, mapgen, sort hooks) use it as scratch.  Written by step_admit alone; 0 on a handle that has not stepped yet
     DBuf<float4> curr_rejected;
     // ---- PR / RR evaluation (erasor_hip_evaluate_*): scratch of its own, nothing a step reads ----
     struct {
@@ -397,16 +395,6 @@ struct erasor_hip_handle {
     std::vector<hipEvent_t> evt_pool;
 };
 
-// (round 5: the worker thread launches a query chain with its OWN target stream and query side -- the caller's thread goes on using
-// the handle's --: LAUNCH() and Q() look here first)
-struct TlCtx {
-    const erasor_hip_handle *h = nullptr;
-    hipStream_t cur = nullptr;
-    int qi = 0;
-};
-static thread_local TlCtx g_tl;
-#define Q(h) ((h)->q[g_tl.h == (h) ? g_tl.qi : (h)->qi])
-#define CUR(h) (g_tl.h == (h) ? g_tl.cur : (h)->cur)
 // between erasor_hip_step_async and erasor_hip_step_wait the handle takes no other call: the step's scratch, query side and
 // host mirror are in use
 #define NOFLY(h)                                                                                              \
@@ -493,8 +481,8 @@ void prof_collect(erasor_hip_handle *h, bool force = false) {
     h->pending.swap(keep);
 }
 
-// kernel launch with optional event bracketing on the handle's stream
-#define LAUNCH(h, name, kern, grid, block, ...)                                   \
+// kernel launch on `stream`, with optional event bracketing
+#define LAUNCH(h, stream, name, kern, grid, block, ...)                           \
     do {                                                                          \
         PendingEvt pe_;                                                           \
         const bool prof_ = (h)->prof == 1 || ((h)->prof == 2 && strncmp(name, "voi_split", 9) == 0); \
@@ -502,16 +490,16 @@ void prof_collect(erasor_hip_handle *h, bool force = false) {
             pe_.name_id = prof_id((h), name);                                     \
             pe_.a = get_evt(h);                                                   \
             pe_.b = get_evt(h);                                                   \
-            (void)hipEventRecord(pe_.a, CUR(h));                                  \
+            (void)hipEventRecord(pe_.a, stream);                                  \
         }                                                                         \
         if (g_debug_sync) fprintf(stderr, "[erasor_hip] launch %s grid=%u\n", name, (unsigned)dim3(grid).x); \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, CUR(h), __VA_ARGS__);   \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, stream, __VA_ARGS__); \
         if (g_debug_sync) {                                                       \
-            hipError_t e2_ = hipStreamSynchronize(CUR(h));                        \
+            hipError_t e2_ = hipStreamSynchronize(stream);                        \
             if (e2_ != hipSuccess) fprintf(stderr, "[erasor_hip]   -> %s\n", hipGetErrorString(e2_)); \
         }                                                                         \
         if (prof_) {                                                              \
-            (void)hipEventRecord(pe_.b, CUR(h));                                  \
+            (void)hipEventRecord(pe_.b, stream);                                  \
             (h)->pending.push_back(pe_);                                          \
         }                                                                         \
     } while (0)
@@ -556,31 +544,32 @@ void fill_dp(erasor_hip_handle *h) {
 // were 17 us of atomics around 2 MB of loads.  Eight points per thread, at most 512 workgroups.
 static inline uint32_t bbox_grid(uint32_t n) { return std::max(1u, std::min<uint32_t>(cdiv(n, 2048), 512)); }
 
-int scan_u32(erasor_hip_handle *h, const uint32_t *in, uint32_t *out_local, uint32_t *tops, uint32_t n_host_max, uint32_t n_host,
+int scan_u32(erasor_hip_handle *h, hipStream_t s, const uint32_t *in, uint32_t *out_local, uint32_t *tops, uint32_t n_host_max, uint32_t n_host,
              const uint32_t *n_dev, uint32_t *total_out, const char *tag) {
     const uint32_t nb = std::max(1u, cdiv(n_host_max, 1024));
-    LAUNCH(h, tag, k_scan_local, nb, 256, in, out_local, tops, n_host, n_dev);
-    LAUNCH(h, tag, k_scan_top, 1, 1024, tops, n_host, n_dev, total_out);
+    LAUNCH(h, s, tag, k_scan_local, nb, 256, in, out_local, tops, n_host, n_dev);
+    LAUNCH(h, s, tag, k_scan_top, 1, 1024, tops, n_host, n_dev, total_out);
     return 0;
 }
 
 // stable LSD radix sort of keys[0..n): n = *n_dev when given (n_ub is then only an upper bound that sizes grids and
-// scratch), else n_ub itself.  Returns pointers to the sorted keys / permutation.
-int radix_sort(erasor_hip_handle *h, const uint32_t *keys_in, uint32_t n_ub, const uint32_t *n_dev, int bits, uint32_t *ka, uint32_t *kb,
+// scratch), else n_ub itself.  Returns pointers to the sorted keys / permutation.  bank: the histogram scratch -- 0: query chains (which
+// share it: one stream for all of them, next_chain_stream), 1: the map chain, 2: the analyses (a tree's Morton keys, the instance rows)
+int radix_sort(erasor_hip_handle *h, hipStream_t s, int bank, const uint32_t *keys_in, uint32_t n_ub, const uint32_t *n_dev, int bits, uint32_t *ka, uint32_t *kb,
                uint32_t *va, uint32_t *vb, const uint32_t **skeys, const uint32_t **sperm, const char *tag) {
     const uint32_t nblk = std::max(1u, cdiv(n_ub, RTILE));
     const uint32_t nhist = 256u * nblk;
-    DBuf<uint32_t> &H = h->bank == 2 ? h->hist3 : h->bank ? h->hist2 : h->hist, &HL = h->bank == 2 ? h->hist3_l : h->bank ? h->hist2_l : h->hist_l,
-                   &HT = h->bank == 2 ? h->hist3_t : h->bank ? h->hist2_t : h->hist_t;
+    DBuf<uint32_t> &H = bank == 2 ? h->hist3 : bank ? h->hist2 : h->hist, &HL = bank == 2 ? h->hist3_l : bank ? h->hist2_l : h->hist_l,
+                   &HT = bank == 2 ? h->hist3_t : bank ? h->hist2_t : h->hist_t;
     if (ensure(h, H, nhist) || ensure(h, HL, nhist) || ensure(h, HT, cdiv(nhist, 1024) + 2)) return ERASOR_E_NO_DEVICE;
     const uint32_t *kin = keys_in;
     const uint32_t *vin = nullptr;
     uint32_t *kout = ka, *vout = va;
-    uint32_t *nhist_dev = h->dn.p + 8 + h->bank;
+    uint32_t *nhist_dev = h->dn.p + 8 + bank;
     for (int shift = 0; shift < bits; shift += 8) {
-        LAUNCH(h, tag, k_radix_hist, nblk, 256, kin, n_ub, n_dev, shift, H.p, nhist_dev);
-        scan_u32(h, H.p, HL.p, HT.p, nhist, nhist, n_dev ? (const uint32_t *)nhist_dev : nullptr, nullptr, tag);
-        LAUNCH(h, tag, k_radix_scatter, nblk, 256, kin, vin, n_ub, n_dev, shift, (const uint32_t *)HL.p, (const uint32_t *)HT.p,
+        LAUNCH(h, s, tag, k_radix_hist, nblk, 256, kin, n_ub, n_dev, shift, H.p, nhist_dev);
+        scan_u32(h, s, H.p, HL.p, HT.p, nhist, nhist, n_dev ? (const uint32_t *)nhist_dev : nullptr, nullptr, tag);
+        LAUNCH(h, s, tag, k_radix_scatter, nblk, 256, kin, vin, n_ub, n_dev, shift, (const uint32_t *)HL.p, (const uint32_t *)HT.p,
                kout, vout);
         kin = kout;
         vin = vout;
@@ -601,13 +590,11 @@ int key_bits(uint32_t nbuckets) {
 int alloc_bins(erasor_hip_handle *h) {
     const size_t B = h->B;
     int rc = 0;
-    const int keep = h->qi;
-    for (h->qi = 0; h->qi < NSIDE; ++h->qi) {
-        rc |= ensure(h, Q(h).qoff, B + 2) | ensure(h, Q(h).ccnt, B) | ensure(h, Q(h).cmin, B) | ensure(h, Q(h).cmax, B);
-        rc |= ensure(h, Q(h).bb, 8) | ensure(h, Q(h).qgrid, 1) | ensure(h, Q(h).esqs, 1) | ensure(h, Q(h).qb_tot, B + 2);
-        rc |= ensure(h, Q(h).d_nvox, 4) | ensure(h, Q(h).d_qctr, 1);
+    for (QSide &q : h->q) {
+        rc |= ensure(h, q.qoff, B + 2) | ensure(h, q.ccnt, B) | ensure(h, q.cmin, B) | ensure(h, q.cmax, B);
+        rc |= ensure(h, q.bb, 8) | ensure(h, q.qgrid, 1) | ensure(h, q.esqs, 1) | ensure(h, q.qb_tot, B + 2);
+        rc |= ensure(h, q.d_nvox, 4) | ensure(h, q.d_qctr, 1);
     }
-    h->qi = keep;
     for (StepSet *s : {&h->cset, &h->oset}) {
         rc |= ensure(h, s->moff, B + 4) | ensure(h, s->mcnt, B) | ensure(h, s->mmin, B) | ensure(h, s->mmax, B) | ensure(h, s->st1b, B + 8);
         rc |= ensure(h, s->d_st, 1) | ensure(h, s->d_ctr, 1) | ensure(h, s->lab_slots, 128);
@@ -672,43 +659,39 @@ int grow_map_scratch(erasor_hip_handle *h, uint64_t need) {
     return rc ? ERASOR_E_NO_DEVICE : 0;
 }
 
-static int alloc_scan_side(erasor_hip_handle *h, uint32_t ns) {
-    if (ns <= Q(h).capS && Q(h).capS) return 0;
+static int alloc_scan_side(erasor_hip_handle *h, QSide &q, uint32_t ns) {
+    if (ns <= q.capS && q.capS) return 0;
     const uint32_t S = ns + ns / 4 + 1024;
-    Q(h).capS = S;
+    q.capS = S;
     int rc = 0;
-    rc |= ensure(h, Q(h).scan, S) | ensure(h, Q(h).cent, S) | ensure(h, Q(h).query, S) | ensure(h, Q(h).sq, S) | ensure(h, h->curr_rejected, S, /*keep: the last step's CURR_REJECTED*/ true);
-    rc |= ensure(h, Q(h).qk_a, S) | ensure(h, Q(h).qk_b, S) | ensure(h, Q(h).qv_a, S) | ensure(h, Q(h).qv_b, S) | ensure(h, Q(h).qposL, S) | ensure(h, Q(h).qposR, S);
-    rc |= ensure(h, Q(h).qflag, S) | ensure(h, Q(h).qpl, S) | ensure(h, Q(h).qtops, S / 1024 + 4) | ensure(h, Q(h).run_begin, S + 1) | ensure(h, Q(h).ukeys, S);
-    rc |= ensure(h, Q(h).qkey, S) | ensure(h, Q(h).qhead, S / 32 + 8);
-    Q(h).hbits = 10;  // voxel hash table: >= 2 slots per possible voxel
-    while ((1ull << Q(h).hbits) < 2ull * S) ++Q(h).hbits;
-    rc |= ensure(h, Q(h).hkey, (size_t)1 << Q(h).hbits) | ensure(h, Q(h).hval, (size_t)1 << Q(h).hbits);
+    rc |= ensure(h, q.scan, S) | ensure(h, q.cent, S) | ensure(h, q.query, S) | ensure(h, q.sq, S) | ensure(h, h->curr_rejected, S, /*keep: the last step's CURR_REJECTED*/ true);
+    rc |= ensure(h, q.qk_a, S) | ensure(h, q.qk_b, S) | ensure(h, q.qv_a, S) | ensure(h, q.qv_b, S) | ensure(h, q.qposL, S) | ensure(h, q.qposR, S);
+    rc |= ensure(h, q.qflag, S) | ensure(h, q.qpl, S) | ensure(h, q.qtops, S / 1024 + 4) | ensure(h, q.run_begin, S + 1) | ensure(h, q.ukeys, S);
+    rc |= ensure(h, q.qkey, S) | ensure(h, q.qhead, S / 32 + 8);
+    q.hbits = 10;  // voxel hash table: >= 2 slots per possible voxel
+    while ((1ull << q.hbits) < 2ull * S) ++q.hbits;
+    rc |= ensure(h, q.hkey, (size_t)1 << q.hbits) | ensure(h, q.hval, (size_t)1 << q.hbits);
     if (getenv("ERASOR_HIP_SORT_STAMPS")) rc |= ensure(h, h->dbg_stamps, 96);
-    rc |= ensure(h, Q(h).wseg0, WSEG_MAX) | ensure(h, Q(h).wseg1, WSEG_MAX) | ensure(h, Q(h).wstate, 1) | ensure(h, Q(h).wtileL, WTILES_MAX) | ensure(h, Q(h).wtileR, WTILES_MAX);
-    rc |= ensure(h, Q(h).esq0, 65536) | ensure(h, Q(h).esq1, 65536) | ensure(h, Q(h).esq2, 65536) | ensure(h, Q(h).essmall, 65536);
+    rc |= ensure(h, q.wseg0, WSEG_MAX) | ensure(h, q.wseg1, WSEG_MAX) | ensure(h, q.wstate, 1) | ensure(h, q.wtileL, WTILES_MAX) | ensure(h, q.wtileR, WTILES_MAX);
+    rc |= ensure(h, q.esq0, 65536) | ensure(h, q.esq1, 65536) | ensure(h, q.esq2, 65536) | ensure(h, q.essmall, 65536);
     return rc ? ERASOR_E_NO_DEVICE : 0;
 }
 
-// The query side in use gets room for a scan of ns points -- and, round 6, every IDLE side with it: eight sides take turns, and a side's
+// Query side `me` gets room for a scan of ns points -- and, round 6, every IDLE side with it: eight sides take turns, and a side's
 // first scan used to pay for ~40 device allocations (and a pinned staging buffer) in the middle of a sequence, 5-7 ms once per side: a
 // visible share of a 20-node pass (erasor_offline_demo --bench: 0.35 or 0.70 ms per callback depending on where the first uses fell).
-int alloc_scan(erasor_hip_handle *h, uint32_t ns) {
-    int rc = alloc_scan_side(h, ns);
-    if (rc || g_tl.h == h) return rc;  // (the worker thread never allocates)
-    const int me = h->qi;
+int alloc_scan(erasor_hip_handle *h, QSide &me, uint32_t ns) {
+    int rc = alloc_scan_side(h, me, ns);
     for (int k = 0; k < NSIDE && !rc; ++k) {
         QSide &q = h->q[k];
         // (NOT the side of the step in flight or last collected: the Scan Ratio Test, the per-bin launch, the write-back and the getters read its
         // bucketed scan -- a side whose chain has run out is not an idle side; found by the 240-walk soak, not by the suite's four walks)
-        if (k == me || k == h->step_side || (q.capS && ns <= q.capS) || q.held || (h->ann.valid && h->ann.side == k)) continue;
+        if (&q == &me || k == h->step_side || (q.capS && ns <= q.capS) || q.held || (h->ann.valid && h->ann.side == k)) continue;
         bool busy = h->worker && h->worker->busy[k].load(std::memory_order_acquire) > 0;
         for (int j = 0; j < h->npend; ++j) busy = busy || h->pend[j] == k;
         if (busy || (q.used && hipEventQuery(q.ev_done) != hipSuccess)) continue;  // (a dropped chain may still be running on it)
-        h->qi = k;
-        rc = alloc_scan_side(h, ns);
+        rc = alloc_scan_side(h, q, ns);
     }
-    h->qi = me;
     return rc;
 }
 
@@ -750,13 +733,10 @@ int copy_F_dense(erasor_hip_handle *h, float4 *dst) {
     }
     DBuf<uint32_t> flag, pl, tops;
     if (ensure(h, flag, (size_t)h->nF + 1) || ensure(h, pl, (size_t)h->nF + 1) || ensure(h, tops, h->nF / 1024 + 4)) return ERASOR_E_NO_DEVICE;
-    hipStream_t keep = h->cur;
-    h->cur = h->stream;
-    LAUNCH(h, "f_dense", k_f_valid, cdiv(h->nF, 256), 256, (const float4 *)h->F[h->curF].p, h->nF, flag.p);
-    scan_u32(h, flag.p, pl.p, tops.p, h->nF, h->nF, nullptr, nullptr, "f_dense");
-    LAUNCH(h, "f_dense", k_f_compact, cdiv(h->nF, 256), 256, (const float4 *)h->F[h->curF].p, h->nF, (const uint32_t *)flag.p, (const uint32_t *)pl.p,
+    LAUNCH(h, h->stream, "f_dense", k_f_valid, cdiv(h->nF, 256), 256, (const float4 *)h->F[h->curF].p, h->nF, flag.p);
+    scan_u32(h, h->stream, flag.p, pl.p, tops.p, h->nF, h->nF, nullptr, nullptr, "f_dense");
+    LAUNCH(h, h->stream, "f_dense", k_f_compact, cdiv(h->nF, 256), 256, (const float4 *)h->F[h->curF].p, h->nF, (const uint32_t *)flag.p, (const uint32_t *)pl.p,
            (const uint32_t *)tops.p, dst);
-    h->cur = keep;
     const hipError_t e = hipStreamSynchronize(h->stream);
     release(flag);
     release(pl);
@@ -782,13 +762,13 @@ int rebuild_outskirts(erasor_hip_handle *h, uint32_t min_front_room) {
     if (ensure(h, flag, span + 1) || ensure(h, pl, span + 1) || ensure(h, tops, span / 1024 + 4)) return ERASOR_E_NO_DEVICE;
     uint32_t nvalid = 0;
     if (span) {
-        LAUNCH(h, "o_rebuild", k_o_valid, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, h->o_begin, h->capO, flag.p);
-        scan_u32(h, flag.p, pl.p, tops.p, span, span, nullptr, h->dn.p, "o_rebuild");
+        LAUNCH(h, h->stream, "o_rebuild", k_o_valid, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, h->o_begin, h->capO, flag.p);
+        scan_u32(h, h->stream, flag.p, pl.p, tops.p, span, span, nullptr, h->dn.p, "o_rebuild");
         HIPC(h, hipMemcpyAsync(&nvalid, h->dn.p, 4, hipMemcpyDeviceToHost, h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
     }
     if (ensure(h, tmp, (size_t)nvalid + 1)) return ERASOR_E_NO_DEVICE;
-    if (span) LAUNCH(h, "o_rebuild", k_o_compact, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, (const float2 *)h->Ozi.p, h->o_begin,
+    if (span) LAUNCH(h, h->stream, "o_rebuild", k_o_compact, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, (const float2 *)h->Ozi.p, h->o_begin,
                      h->capO, (const uint32_t *)flag.p, (const uint32_t *)pl.p, (const uint32_t *)tops.p, tmp.p);
     uint32_t need = rup((uint64_t)nvalid + min_front_room + CHUNK, CHUNK);
     if (need > h->capO) {
@@ -800,7 +780,7 @@ int rebuild_outskirts(erasor_hip_handle *h, uint32_t min_front_room) {
         h->capO = ncap;
     }
     h->o_begin = h->capO - nvalid;
-    if (nvalid) LAUNCH(h, "o_rebuild", k_store_outskirts, cdiv(nvalid, 256), 256, (const float4 *)tmp.p, nvalid, h->Oxy.p, h->Ozi.p, h->o_begin);
+    if (nvalid) LAUNCH(h, h->stream, "o_rebuild", k_store_outskirts, cdiv(nvalid, 256), 256, (const float4 *)tmp.p, nvalid, h->Oxy.p, h->Ozi.p, h->o_begin);
     {
         const int rc_m = ometa_reset(h);
         if (rc_m) return rc_m;
@@ -842,9 +822,9 @@ int split_submap(erasor_hip_handle *h, double x, double y) {
     if (span && h->o_valid) {
         DBuf<uint32_t> f2, p2, t2;
         if (ensure(h, f2, span + 1) || ensure(h, p2, span + 1) || ensure(h, t2, span / 1024 + 4)) return ERASOR_E_NO_DEVICE;
-        LAUNCH(h, "submap", k_o_valid, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, h->o_begin, h->capO, f2.p);
-        scan_u32(h, f2.p, p2.p, t2.p, span, span, nullptr, nullptr, "submap");
-        LAUNCH(h, "submap", k_o_compact, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, (const float2 *)h->Ozi.p, h->o_begin, h->capO,
+        LAUNCH(h, h->stream, "submap", k_o_valid, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, h->o_begin, h->capO, f2.p);
+        scan_u32(h, h->stream, f2.p, p2.p, t2.p, span, span, nullptr, nullptr, "submap");
+        LAUNCH(h, h->stream, "submap", k_o_compact, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, (const float2 *)h->Ozi.p, h->o_begin, h->capO,
                (const uint32_t *)f2.p, (const uint32_t *)p2.p, (const uint32_t *)t2.p, G.p + h->nFv);
         HIPC(h, hipStreamSynchronize(h->stream));
         release(f2);
@@ -854,8 +834,8 @@ int split_submap(erasor_hip_handle *h, double x, double y) {
     if (h->nC) HIPC(h, hipMemcpyAsync(G.p + h->nFv + h->o_valid, h->Cbuf.p, (size_t)h->nC * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
     uint32_t n_sub = 0;
     if (total) {
-        LAUNCH(h, "submap", k_box_flag, cdiv(total, 256), 256, (const float4 *)G.p, total, x, y, h->P.submap_size, flag.p);
-        scan_u32(h, flag.p, pl.p, tops.p, total, total, nullptr, h->dn.p, "submap");
+        LAUNCH(h, h->stream, "submap", k_box_flag, cdiv(total, 256), 256, (const float4 *)G.p, total, x, y, h->P.submap_size, flag.p);
+        scan_u32(h, h->stream, flag.p, pl.p, tops.p, total, total, nullptr, h->dn.p, "submap");
         HIPC(h, hipMemcpyAsync(&n_sub, h->dn.p, 4, hipMemcpyDeviceToHost, h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
     }
@@ -871,7 +851,7 @@ int split_submap(erasor_hip_handle *h, double x, double y) {
     if (ensure(h, newC, (size_t)n_cmp + 1)) return ERASOR_E_NO_DEVICE;
     const uint32_t dst0 = h->capO - n_sub;
     if (total)
-        LAUNCH(h, "submap", k_box_partition, cdiv(total, 256), 256, (const float4 *)G.p, total, (const uint32_t *)flag.p, (const uint32_t *)pl.p,
+        LAUNCH(h, h->stream, "submap", k_box_partition, cdiv(total, 256), 256, (const float4 *)G.p, total, (const uint32_t *)flag.p, (const uint32_t *)pl.p,
                (const uint32_t *)tops.p, h->Oxy.p, h->Ozi.p, dst0, newC.p);
     {
         const int rc_m = ometa_reset(h);
@@ -887,7 +867,7 @@ int split_submap(erasor_hip_handle *h, double x, double y) {
     if (rc) return rc;
     if (n_sub) {
         DevState *ds = h->cset.d_st.p;
-        LAUNCH(h, "submap", k_count_labels_zi, std::min<uint32_t>(cdiv(n_sub, 256), 1024), 256, (const float2 *)(h->Ozi.p + dst0), n_sub,
+        LAUNCH(h, h->stream, "submap", k_count_labels_zi, std::min<uint32_t>(cdiv(n_sub, 256), 1024), 256, (const float2 *)(h->Ozi.p + dst0), n_sub,
                &ds->O_static, &ds->O_dynamic);
     }
     HIPC(h, hipMemcpyAsync(&h->st, h->cset.d_st.p, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
@@ -1085,7 +1065,6 @@ static int create_handle(const erasor_params *p, int device, int nqs_force, eras
         return ERASOR_E_NO_DEVICE;
     }
     memset(h->pin, 0, sizeof(HostOut));
-    h->cur = h->stream;
     if (alloc_bins(h)) {
         erasor_hip_destroy(h);
         return ERASOR_E_NO_DEVICE;
@@ -1109,10 +1088,9 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     prof_collect(h, true);
     for (auto e : h->evt_pool) (void)hipEventDestroy(e);
-    for (h->qi = 0; h->qi < NSIDE; ++h->qi) {  // every query side
-        release(Q(h).d_nvox); release(Q(h).d_qctr); release(Q(h).qb_hist); release(Q(h).qb_tot); release(Q(h).hkey); release(Q(h).hval); release(Q(h).qoff); release(Q(h).ccnt); release(Q(h).cmin); release(Q(h).cmax); release(Q(h).scan); release(Q(h).cent); release(Q(h).query); release(Q(h).sq); release(Q(h).bb); release(Q(h).qk_a); release(Q(h).qk_b); release(Q(h).qv_a); release(Q(h).qv_b); release(Q(h).qposL); release(Q(h).qposR); release(Q(h).qflag); release(Q(h).qpl); release(Q(h).qtops); release(Q(h).run_begin); release(Q(h).ukeys); release(Q(h).qkey); release(Q(h).qhead); release(Q(h).wseg0); release(Q(h).wseg1); release(Q(h).wstate); release(Q(h).wtileL); release(Q(h).wtileR); release(Q(h).esq0); release(Q(h).esq1); release(Q(h).esq2); release(Q(h).essmall); release(Q(h).esqs); release(Q(h).qgrid);
+    for (QSide &q : h->q) {
+        release(q.d_nvox); release(q.d_qctr); release(q.qb_hist); release(q.qb_tot); release(q.hkey); release(q.hval); release(q.qoff); release(q.ccnt); release(q.cmin); release(q.cmax); release(q.scan); release(q.cent); release(q.query); release(q.sq); release(q.bb); release(q.qk_a); release(q.qk_b); release(q.qv_a); release(q.qv_b); release(q.qposL); release(q.qposR); release(q.qflag); release(q.qpl); release(q.qtops); release(q.run_begin); release(q.ukeys); release(q.qkey); release(q.qhead); release(q.wseg0); release(q.wseg1); release(q.wstate); release(q.wtileL); release(q.wtileR); release(q.esq0); release(q.esq1); release(q.esq2); release(q.essmall); release(q.esqs); release(q.qgrid);
     }
-    h->qi = 0;
     release(h->Cbuf); release(h->F[0]); release(h->F[1]); release(h->Oxy); release(h->Ozi);
     release(h->vmask); release(h->hmask); release(h->cinfo); release(h->pvl); release(h->phl); release(h->topv); release(h->toph); release(h->topr); release(h->ometa);
     release(h->rejected);
@@ -1185,7 +1163,7 @@ static int set_map_common(erasor_hip_handle *h, const void *src, size_t n, bool 
     h->o_valid = n;
     h->nC = 0;
     h->submap_not_initialized = true;
-    if (n) LAUNCH(h, "set_map", k_store_outskirts, cdiv(n, 256), 256, (const float4 *)h->cset.voi_ego.p, (uint32_t)n, h->Oxy.p, h->Ozi.p, h->o_begin);
+    if (n) LAUNCH(h, h->stream, "set_map", k_store_outskirts, cdiv(n, 256), 256, (const float4 *)h->cset.voi_ego.p, (uint32_t)n, h->Oxy.p, h->Ozi.p, h->o_begin);
     rc = ometa_reset(h);
     if (rc) return rc;
     memset(&h->st, 0, sizeof(h->st));
@@ -1194,7 +1172,7 @@ static int set_map_common(erasor_hip_handle *h, const void *src, size_t n, bool 
     // initial label counters of the outskirts (parse_dynamic_obj, utils.cpp:57-78)
     if (n) {
         DevState *ds = h->cset.d_st.p;
-        LAUNCH(h, "set_map", k_count_labels4, std::min<uint32_t>(cdiv(n, 256), 2048), 256, (const float4 *)h->cset.voi_ego.p, (uint32_t)n,
+        LAUNCH(h, h->stream, "set_map", k_count_labels4, std::min<uint32_t>(cdiv(n, 256), 2048), 256, (const float4 *)h->cset.voi_ego.p, (uint32_t)n,
                (const uint32_t *)nullptr, &ds->O_static, &ds->O_dynamic);
     }
     HIPC(h, hipMemcpyAsync(&h->st, h->cset.d_st.p, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
@@ -1212,10 +1190,10 @@ int erasor_hip_set_map_device(erasor_hip_handle *h, const void *d_xyzi, size_t n
 // launch), then every remaining segment is completed inside LDS by one workgroup.
 // (levels beyond lg(n / WIDE_MIN): 4 measured best -- fewer leave k_esort_mid / k_esort_final more than the levels save, EXPERIMENTS r05-5)
 #define ESORT_WIDE_SLACK 4
-static void run_exact_sort(erasor_hip_handle *h, uint32_t n, bool queues_open = false) {
-    Counters *dc = Q(h).d_qctr.p;
+static void run_exact_sort(erasor_hip_handle *h, hipStream_t s, QSide &q, uint32_t n, bool queues_open = false) {
+    Counters *dc = q.d_qctr.p;
     if (!queues_open)  // (the scan's voxelisation opens them in its key kernel: k_voxel_keys_es)
-        LAUNCH(h, "q_esort", k_esort_init, 1, 1, Q(h).qk_a.p, Q(h).qv_a.p, Q(h).esq0.p, Q(h).essmall.p, Q(h).esqs.p, Q(h).wseg0.p, Q(h).wstate.p, n);
+        LAUNCH(h, s, "q_esort", k_esort_init, 1, 1, q.qk_a.p, q.qv_a.p, q.esq0.p, q.essmall.p, q.esqs.p, q.wseg0.p, q.wstate.p, n);
     int nlev = 0;
     if (n >= WIDE_MIN && (n - 1 + WTILE - 1) / WTILE <= WTILES_MAX) {
         // wide levels: segments >= WIDE_MIN keys, many workgroups each.  A segment halves (roughly) per level, so
@@ -1226,19 +1204,19 @@ static void run_exact_sort(erasor_hip_handle *h, uint32_t n, bool queues_open = 
         for (int l = 0; l < wl; ++l) {
             const int cur = l & 1;
             // two launches per level (round 2: three -- the children's routing and median move had a kernel of their own)
-            LAUNCH(h, "q_esort_wide", k_esort_wide_mark, 256, 256, (const uint32_t *)Q(h).qk_a.p, (const uint32_t *)Q(h).qv_a.p, Q(h).qposL.p, Q(h).qposR.p,
-                   cur ? Q(h).wseg1.p : Q(h).wseg0.p, Q(h).wstate.p, cur, Q(h).wtileL.p, Q(h).wtileR.p);
-            LAUNCH(h, "q_esort_wide", k_esort_wide_swap, 256, 256, Q(h).qk_a.p, Q(h).qv_a.p, (const uint32_t *)Q(h).qposL.p, (const uint32_t *)Q(h).qposR.p,
-                   cur ? Q(h).wseg1.p : Q(h).wseg0.p, cur ? Q(h).wseg0.p : Q(h).wseg1.p, Q(h).wstate.p, cur, (const uint32_t *)Q(h).wtileL.p,
-                   (const uint32_t *)Q(h).wtileR.p, Q(h).esq0.p, Q(h).essmall.p, Q(h).esqs.p, 65536u, l == wl - 1 ? 1 : 0, dc);
+            LAUNCH(h, s, "q_esort_wide", k_esort_wide_mark, 256, 256, (const uint32_t *)q.qk_a.p, (const uint32_t *)q.qv_a.p, q.qposL.p, q.qposR.p,
+                   cur ? q.wseg1.p : q.wseg0.p, q.wstate.p, cur, q.wtileL.p, q.wtileR.p);
+            LAUNCH(h, s, "q_esort_wide", k_esort_wide_swap, 256, 256, q.qk_a.p, q.qv_a.p, (const uint32_t *)q.qposL.p, (const uint32_t *)q.qposR.p,
+                   cur ? q.wseg1.p : q.wseg0.p, cur ? q.wseg0.p : q.wseg1.p, q.wstate.p, cur, (const uint32_t *)q.wtileL.p,
+                   (const uint32_t *)q.wtileR.p, q.esq0.p, q.essmall.p, q.esqs.p, 65536u, l == wl - 1 ? 1 : 0, dc);
         }
     }
     bool mid_done = false;
     if (n >= WIDE_MIN && (n - 1 + WTILE - 1) / WTILE <= WTILES_MAX && !getenv("ERASOR_HIP_SORT_LEVEL_CAP")) {
         // whatever is still longer than the finisher's LDS capacity after the wide levels (a few unbalanced subtrees):
         // one workgroup per segment cuts it down, all of its partitions in this one launch
-        LAUNCH(h, "q_esort", k_esort_mid, 256, 1024, Q(h).qk_a.p, Q(h).qv_a.p, Q(h).qposL.p, Q(h).qposR.p, (const esort::Seg *)Q(h).esq0.p, Q(h).essmall.p,
-               Q(h).esqs.p, 0, 65536u, dc);
+        LAUNCH(h, s, "q_esort", k_esort_mid, 256, 1024, q.qk_a.p, q.qv_a.p, q.qposL.p, q.qposR.p, (const esort::Seg *)q.esq0.p, q.essmall.p,
+               q.esqs.p, 0, 65536u, dc);
         mid_done = true;
     }
     if (n > ES_LMAX && !mid_done) {
@@ -1247,11 +1225,11 @@ static void run_exact_sort(erasor_hip_handle *h, uint32_t n, bool queues_open = 
         static const int level_cap2 = getenv("ERASOR_HIP_SORT_LEVEL_CAP") ? atoi(getenv("ERASOR_HIP_SORT_LEVEL_CAP")) : 1 << 20;
         nlev = std::min(std::min(2 * esort::lg2_floor(n), n >= WIDE_MIN ? (n > (1u << 21) ? 12 : 2) : 12), level_cap2);
         for (int l = 0; l < nlev; ++l)
-            LAUNCH(h, "q_esort", k_esort_level, 48, 1024, Q(h).qk_a.p, Q(h).qv_a.p, Q(h).qposL.p, Q(h).qposR.p, Q(h).esq0.p, Q(h).esq1.p, Q(h).esq2.p,
-                   Q(h).essmall.p, Q(h).esqs.p, l, 65536u, dc);
+            LAUNCH(h, s, "q_esort", k_esort_level, 48, 1024, q.qk_a.p, q.qv_a.p, q.qposL.p, q.qposR.p, q.esq0.p, q.esq1.p, q.esq2.p,
+                   q.essmall.p, q.esqs.p, l, 65536u, dc);
     }
     const int bigcur = mid_done ? 1 : nlev % 3;  // after k_esort_mid queue 0 is spent: hand the (empty) queue 1 to the final kernel
-    esort::Seg *qs3[3] = {Q(h).esq0.p, Q(h).esq1.p, Q(h).esq2.p};
+    esort::Seg *qs3[3] = {q.esq0.p, q.esq1.p, q.esq2.p};
     // a scan leaves ~120 segments for the finisher: 128 workgroups of 1024 threads take them in one round and leave the compute units
     // to the chains running beside this one (2048 measured 1.5 % slower per scan, gpurun_out/r03o); a whole map keeps the wide grid
     const uint32_t final_grid = n <= (1u << 20) ? 128u : 2048u;
@@ -1264,40 +1242,40 @@ static void run_exact_sort(erasor_hip_handle *h, uint32_t n, bool queues_open = 
         memcpy(h->dbg_sort, rec, sizeof(rec));
     }
 #endif
-    LAUNCH(h, "q_esort_final", k_esort_final, final_grid, 1024, Q(h).qk_a.p, Q(h).qv_a.p, Q(h).qposL.p, Q(h).qposR.p, Q(h).qhead.p, Q(h).qk_b.p, Q(h).qv_b.p,
-           (const esort::Seg *)Q(h).essmall.p, (const esort::Seg *)qs3[bigcur], Q(h).esqs.p, bigcur, dc, h->dbg_stamps.p);
+    LAUNCH(h, s, "q_esort_final", k_esort_final, final_grid, 1024, q.qk_a.p, q.qv_a.p, q.qposL.p, q.qposR.p, q.qhead.p, q.qk_b.p, q.qv_b.p,
+           (const esort::Seg *)q.essmall.p, (const esort::Seg *)qs3[bigcur], q.esqs.p, bigcur, dc, h->dbg_stamps.p);
 }
 
-// ---- exact voxelisation of the cloud in Q(h).scan[0..n): fills run_begin / cent / ukeys, d_st->q_nvox -------------------
-static int voxelize_query_part1(erasor_hip_handle *h, uint32_t n, float leaf, const std::function<void()> &after_keys) {
-    Counters *dc = Q(h).d_qctr.p;
+// ---- exact voxelisation of the cloud in q.scan_in[0..n) on stream s: fills run_begin / cent / ukeys, d_st->q_nvox -------------------
+static int voxelize_query_part1(erasor_hip_handle *h, hipStream_t s, QSide &q, uint32_t n, float leaf, const std::function<void()> &after_keys) {
+    Counters *dc = q.d_qctr.p;
     // (the bounding box was reset by k_query_begin)
-    if (n) LAUNCH(h, "q_bbox", k_bbox, bbox_grid(n), 256, Q(h).scan_in, n, Q(h).bb.p);
+    if (n) LAUNCH(h, s, "q_bbox", k_bbox, bbox_grid(n), 256, q.scan_in, n, q.bb.p);
     {
         EsInit es;
-        es.q0 = Q(h).esq0.p;
-        es.smallq = Q(h).essmall.p;
-        es.qs = Q(h).esqs.p;
-        es.w0 = Q(h).wseg0.p;
-        es.ws = Q(h).wstate.p;
-        LAUNCH(h, "q_keys", k_voxel_keys_es, std::max(1u, cdiv(n, 256)), 256, Q(h).scan_in, n, (const uint32_t *)Q(h).bb.p, leaf, Q(h).qk_a.p,
-               Q(h).qv_a.p, Q(h).qgrid.p, dc, Q(h).hkey.p, 1u << Q(h).hbits, es);
+        es.q0 = q.esq0.p;
+        es.smallq = q.essmall.p;
+        es.qs = q.esqs.p;
+        es.w0 = q.wseg0.p;
+        es.ws = q.wstate.p;
+        LAUNCH(h, s, "q_keys", k_voxel_keys_es, std::max(1u, cdiv(n, 256)), 256, q.scan_in, n, (const uint32_t *)q.bb.p, leaf, q.qk_a.p,
+               q.qv_a.p, q.qgrid.p, dc, q.hkey.p, 1u << q.hbits, es);
     }
     after_keys();  // ctr->err (VoxelGrid overflow) is final from here on: the caller may fork work that depends on it
     // exact std::sort: a few global levels (one workgroup per big segment), then per-segment completion in LDS
-    run_exact_sort(h, n, true);
+    run_exact_sort(h, s, q, n, true);
     // runs
     const uint32_t ntile = std::max(1u, cdiv(n, 1024));
     if (ntile <= 1024) {  // (a scan: ~120 tiles) two launches: tile totals, then heads -> run_begin with the tile's offset summed in place
-        LAUNCH(h, "q_runs", k_run_count, ntile, 256, (const uint32_t *)Q(h).qk_b.p, n, Q(h).qtops.p);
-        LAUNCH(h, "q_runs", k_run_emit, ntile, 256, (const uint32_t *)Q(h).qk_b.p, n, (const uint32_t *)Q(h).qtops.p, ntile, Q(h).run_begin.p,
-               Q(h).d_nvox.p);
+        LAUNCH(h, s, "q_runs", k_run_count, ntile, 256, (const uint32_t *)q.qk_b.p, n, q.qtops.p);
+        LAUNCH(h, s, "q_runs", k_run_emit, ntile, 256, (const uint32_t *)q.qk_b.p, n, (const uint32_t *)q.qtops.p, ntile, q.run_begin.p,
+               q.d_nvox.p);
         return 0;
     }
-    if (n) LAUNCH(h, "q_runs", k_run_heads, cdiv(n, 256), 256, (const uint32_t *)Q(h).qk_b.p, n, Q(h).qflag.p);
-    scan_u32(h, Q(h).qflag.p, Q(h).qpl.p, Q(h).qtops.p, n, n, nullptr, nullptr, "q_runs");
-    LAUNCH(h, "q_runs", k_run_begin, cdiv((uint64_t)n + 1, 256), 256, (const uint32_t *)Q(h).qflag.p, (const uint32_t *)Q(h).qpl.p,
-           (const uint32_t *)Q(h).qtops.p, n, Q(h).run_begin.p, Q(h).d_nvox.p);
+    if (n) LAUNCH(h, s, "q_runs", k_run_heads, cdiv(n, 256), 256, (const uint32_t *)q.qk_b.p, n, q.qflag.p);
+    scan_u32(h, s, q.qflag.p, q.qpl.p, q.qtops.p, n, n, nullptr, nullptr, "q_runs");
+    LAUNCH(h, s, "q_runs", k_run_begin, cdiv((uint64_t)n + 1, 256), 256, (const uint32_t *)q.qflag.p, (const uint32_t *)q.qpl.p,
+           (const uint32_t *)q.qtops.p, n, q.run_begin.p, q.d_nvox.p);
     return 0;
 }
 
@@ -1344,11 +1322,10 @@ static uint64_t staged_fingerprint(QSide &q, size_t n) {
     return q.fp;
 }
 
-// A HOST scan on its way into query side Q(h): REPACKED into the side's pinned staging buffer NOW -- one pass that also hashes every
+// A HOST scan on its way into query side q: REPACKED into the side's pinned staging buffer NOW -- one pass that also hashes every
 // record (the caller's buffer is free again when this returns) --, from there asynchronously into q.scan on `stream`.  The side's
 // previous chain must be through with q.scan and the staging buffer (the caller has waited for q.ev_done).
-static int stage_host_scan(erasor_hip_handle *h, const void *scan_src, uint32_t ns, hipStream_t stream, RowFmt fmt, uint64_t *fp_out) {
-    QSide &q = Q(h);
+static int stage_host_scan(erasor_hip_handle *h, QSide &q, const void *scan_src, uint32_t ns, hipStream_t stream, RowFmt fmt, uint64_t *fp_out) {
     if (q.h2d_pending) HIPC(h, hipEventSynchronize(q.ev_h2d));  // (an announcement that was dropped: its copy may still read the staging buffer)
     if (scan_src != (const void *)q.stage && q.stage_cap < ns) {
         if (q.stage) (void)hipHostFree(q.stage);
@@ -1485,51 +1462,37 @@ static int pick_side(const erasor_hip_handle *h) {
     return fallback;
 }
 
-// restores the handle's active query side / target stream when a helper that switched them returns (also on errors)
-struct SideGuard {
-    erasor_hip_handle *h;
-    int qi;
-    hipStream_t cur;
-    explicit SideGuard(erasor_hip_handle *hh) : h(hh), qi(hh->qi), cur(hh->cur) {}
-    ~SideGuard() {
-        h->qi = qi;
-        h->cur = cur;
-    }
-};
-
 // The QUERY CHAIN of one scan, enqueued on the stream of query side `side`: voxelize_preserving_labels (OMU.cpp:238),
 // lidar->body + R-POD key (OMU.cpp:240; erasor.cpp:100-115), bucketing and per-bin statistics of the query.  It depends
 // on the scan and the lidar->body transform only -- not on the map -- which is what lets erasor_hip_prefetch_scan run
 // it for scan k+1 while step k is still in its map-side stages.
 // A host scan is copied to the device when it is announced (erasor_hip_prefetch_scan).  The step that claims the prefetched
-// chain recognises "the same scan" by (pointer, size, T_lidar2body) -- and by this fingerprint of the contents, so that a
+// chain recognises "the same scan" by its ticket, or by (pointer, size, T_lidar2body) and the hash of every record (RowHash), so that a
 // buffer that was refilled (or freed and re-used at the same address) in between is not mistaken for the announced one.
-// FNV-1a over at most 256 evenly spaced points plus the first and the last: microseconds, not a checksum of 2 MB.
 
 // VoxelGrid pass-through (see k_dup_label_passthrough): out[0..ns) = T * (point with the label of its first exact duplicate),
-// on the current stream.  Scratch: the current query side's sort buffers.
-static int enqueue_passthrough(erasor_hip_handle *h, const float4 *d_src, uint32_t ns, const float T[16], float4 *out, uint32_t *qkey) {
+// on stream s.  Scratch: side q's sort buffers and histogram bank 0.
+static int enqueue_passthrough(erasor_hip_handle *h, hipStream_t s, QSide &q, const float4 *d_src, uint32_t ns, const float T[16], float4 *out, uint32_t *qkey) {
     if (!ns) return ERASOR_OK;
     int bits = 8;
     while ((1u << bits) < 2u * ns && bits < 24) ++bits;
-    QSide &q = Q(h);
-    LAUNCH(h, "q_passthrough", k_xyz_hash_keys, cdiv(ns, 256), 256, d_src, ns, bits, q.ukeys.p);
+    LAUNCH(h, s, "q_passthrough", k_xyz_hash_keys, cdiv(ns, 256), 256, d_src, ns, bits, q.ukeys.p);
     const uint32_t *sk = nullptr, *sp = nullptr;
-    const int rc = radix_sort(h, q.ukeys.p, ns, nullptr, bits, q.qk_a.p, q.qposL.p, q.qv_a.p, q.qposR.p, &sk, &sp, "q_passthrough");
+    const int rc = radix_sort(h, s, 0, q.ukeys.p, ns, nullptr, bits, q.qk_a.p, q.qposL.p, q.qv_a.p, q.qposR.p, &sk, &sp, "q_passthrough");
     if (rc) return rc;
     const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    LAUNCH(h, "q_passthrough", k_dup_label_passthrough, cdiv(ns, 256), 256, d_src, ns, sk, sp, bits, to_xf(T ? T : I), T ? 1 : 0, h->dp, q.d_qctr.p, out,
+    LAUNCH(h, s, "q_passthrough", k_dup_label_passthrough, cdiv(ns, 256), 256, d_src, ns, sk, sp, bits, to_xf(T ? T : I), T ? 1 : 0, h->dp, q.d_qctr.p, out,
            qkey);
     return ERASOR_OK;
 }
 
-// ---- the launches of ONE scan's chain on `qstream` (the caller's thread or the handle's worker: TlCtx) ----
+// ---- the launches of ONE scan's chain on `qstream` (from the caller's thread or the handle's worker) ----
 struct ChainJob {
     erasor_hip_handle *h;
     int side;
     hipStream_t qstream;
     uint32_t ns;
-    bool prevox, passthrough, to_worker;
+    bool prevox, passthrough;
     float Tl[16];
 };
 static int chain_launches(const ChainJob &j) {
@@ -1544,73 +1507,47 @@ static int chain_launches(const ChainJob &j) {
     const uint32_t *nq_dev = q.d_nvox.p;
     const float *T_l2b = j.Tl;
     int rc = 0;
-    // (LAUNCH() and Q() look at the thread's context first: the chain's own stream and side, on the worker thread and on the caller's
-    // alike; on the caller's thread the handle's own fields say the same -- the tests' CPU stand-in evaluates a launch's arguments on
-    // its wavefront threads, which have no context of their own)
-    TlCtx keep_tl = g_tl;
-    g_tl.h = h;
-    g_tl.cur = qstream;
-    g_tl.qi = j.side;
-    struct HandleCtx {
-        erasor_hip_handle *h;
-        int qi;
-        hipStream_t cur;
-        ~HandleCtx() {
-            if (h) {
-                h->qi = qi;
-                h->cur = cur;
-            }
-        }
-    } handle_ctx{j.to_worker ? nullptr : h, h->qi, h->cur};
-    if (!j.to_worker) {
-        h->qi = j.side;
-        h->cur = qstream;
-    }
-    struct TlRestore {
-        TlCtx k;
-        ~TlRestore() { g_tl = k; }
-    } tl_restore{keep_tl};
-    LAUNCH(h, "q_begin", k_query_begin, 1, 256, qc, q.bb.p, B + 1 <= QB_NB_MAX ? q.qb_tot.p : (uint32_t *)nullptr, B + 1 <= QB_NB_MAX ? B + 1 : 0u,
+    LAUNCH(h, qstream, "q_begin", k_query_begin, 1, 256, qc, q.bb.p, B + 1 <= QB_NB_MAX ? q.qb_tot.p : (uint32_t *)nullptr, B + 1 <= QB_NB_MAX ? B + 1 : 0u,
            q.d_nvox.p, (prevox || passthrough) ? ns : 0u);
     // ---- part 1: bounding box, voxel keys, exact std::sort, runs ----
     if (passthrough && !prevox) {
         // PCL's VoxelGrid refuses this cloud (index overflow) and hands it back unchanged (utils.cpp:88-91): the chain verifies
         // that on the device (err 4 if not) and produces the un-voxelised query with the label search's answers
-        if (ns) LAUNCH(h, "q_bbox", k_bbox, bbox_grid(ns), 256, q.scan_in, ns, q.bb.p);
-        LAUNCH(h, "q_passthrough", k_passthrough_check, 1, 64, (const uint32_t *)q.bb.p, ns, P.leaf_query, q.qgrid.p, qc);
+        if (ns) LAUNCH(h, qstream, "q_bbox", k_bbox, bbox_grid(ns), 256, q.scan_in, ns, q.bb.p);
+        LAUNCH(h, qstream, "q_passthrough", k_passthrough_check, 1, 64, (const uint32_t *)q.bb.p, ns, P.leaf_query, q.qgrid.p, qc);
         (void)hipEventRecord(q.ev_keys, qstream);
-        rc = enqueue_passthrough(h, q.scan_in, ns, T_l2b, q.query.p, q.qkey.p);
+        rc = enqueue_passthrough(h, qstream, q, q.scan_in, ns, T_l2b, q.query.p, q.qkey.p);
         if (rc) return rc;
     } else if (!prevox) {
-        voxelize_query_part1(h, ns, P.leaf_query, [&] { (void)hipEventRecord(q.ev_keys, qstream); });
+        voxelize_query_part1(h, qstream, q, ns, P.leaf_query, [&] { (void)hipEventRecord(q.ev_keys, qstream); });
     } else
         (void)hipEventRecord(q.ev_keys, qstream);
     // ---- part 2: centroids, label NN, lidar->body, R-POD key ----
     const uint32_t *sq_keys = nullptr, *sq_perm = nullptr;
     if (prevox) {
-        if (nq) LAUNCH(h, "q_direct", k_query_direct, cdiv(nq, 256), 256, q.scan_in, nq, P, qc, q.query.p, q.qkey.p);
+        if (nq) LAUNCH(h, qstream, "q_direct", k_query_direct, cdiv(nq, 256), 256, q.scan_in, nq, P, qc, q.query.p, q.qkey.p);
     } else if (passthrough) {
         // (query and keys are already there)
     } else if (nq) {
-        LAUNCH(h, "q_centroids", k_centroids, cdiv((uint64_t)nq * 8, 256), 256, q.scan_in, (const uint32_t *)q.qk_b.p, (const uint32_t *)q.qv_b.p,
+        LAUNCH(h, qstream, "q_centroids", k_centroids, cdiv((uint64_t)nq * 8, 256), 256, q.scan_in, (const uint32_t *)q.qk_b.p, (const uint32_t *)q.qv_b.p,
                (const uint32_t *)q.run_begin.p, nq_dev, q.cent.p, q.ukeys.p, q.hkey.p, q.hval.p, q.hbits);
-        LAUNCH(h, "q_nn", k_query_nn, cdiv((uint64_t)nq * NN_SUB, 256), 256, q.scan_in, (const uint32_t *)q.qv_b.p, (const uint32_t *)q.run_begin.p,
+        LAUNCH(h, qstream, "q_nn", k_query_nn, cdiv((uint64_t)nq * NN_SUB, 256), 256, q.scan_in, (const uint32_t *)q.qv_b.p, (const uint32_t *)q.run_begin.p,
                (const uint32_t *)q.ukeys.p, (const float4 *)q.cent.p, nq_dev, (const VoxGrid *)q.qgrid.p, to_xf(T_l2b), P, qc, q.query.p, q.qkey.p,
                (const uint32_t *)q.hkey.p, (const uint32_t *)q.hval.p, q.hbits);
     }
     if (B + 1 <= QB_NB_MAX) {  // one-digit stable counting sort with the gather and the bucket offsets folded in
         const uint32_t ntile_ub = std::max(1u, cdiv(nq, QB_TILE));
-        LAUNCH(h, "q_bucket", k_qb_hist, ntile_ub, 1024, (const uint32_t *)q.qkey.p, nq, nq_dev, B + 1, q.qb_hist.p, q.qb_tot.p);
-        LAUNCH(h, "q_bucket", k_qb_scan, 1, 1024, (const uint32_t *)q.qb_tot.p, B + 1, q.qoff.p);
-        LAUNCH(h, "q_bucket", k_qb_scatter, ntile_ub, 1024, (const uint32_t *)q.qkey.p, (const float4 *)q.query.p, nq, nq_dev, B + 1, bits,
+        LAUNCH(h, qstream, "q_bucket", k_qb_hist, ntile_ub, 1024, (const uint32_t *)q.qkey.p, nq, nq_dev, B + 1, q.qb_hist.p, q.qb_tot.p);
+        LAUNCH(h, qstream, "q_bucket", k_qb_scan, 1, 1024, (const uint32_t *)q.qb_tot.p, B + 1, q.qoff.p);
+        LAUNCH(h, qstream, "q_bucket", k_qb_scatter, ntile_ub, 1024, (const uint32_t *)q.qkey.p, (const float4 *)q.query.p, nq, nq_dev, B + 1, bits,
                (const uint32_t *)q.qb_hist.p, (const uint32_t *)q.qoff.p, q.sq.p);
     } else {  // very fine R-POD grids: LSD radix passes
-        radix_sort(h, q.qkey.p, nq, nq_dev, bits, q.qk_a.p, q.qposL.p, q.qv_a.p, q.qposR.p, &sq_keys, &sq_perm, "q_bucket");
-        if (nq) LAUNCH(h, "q_bucket", k_gather, cdiv(nq, 256), 256, (const float4 *)q.query.p, (const uint32_t *)nullptr, sq_perm, nq, nq_dev, q.sq.p,
+        radix_sort(h, qstream, 0, q.qkey.p, nq, nq_dev, bits, q.qk_a.p, q.qposL.p, q.qv_a.p, q.qposR.p, &sq_keys, &sq_perm, "q_bucket");
+        if (nq) LAUNCH(h, qstream, "q_bucket", k_gather, cdiv(nq, 256), 256, (const float4 *)q.query.p, (const uint32_t *)nullptr, sq_perm, nq, nq_dev, q.sq.p,
                        (uint32_t *)nullptr);
-        LAUNCH(h, "q_bucket", k_bin_offsets, cdiv((uint64_t)std::max(nq, B + 2) + 1, 256), 256, sq_keys, nq, nq_dev, B + 1, q.qoff.p);
+        LAUNCH(h, qstream, "q_bucket", k_bin_offsets, cdiv((uint64_t)std::max(nq, B + 2) + 1, 256), 256, sq_keys, nq, nq_dev, B + 1, q.qoff.p);
     }
-    LAUNCH(h, "bin_stats", k_bin_stats, cdiv((uint64_t)B * 64, 256), 256, (const float4 *)q.sq.p, (const uint32_t *)q.qoff.p, B, q.ccnt.p, q.cmin.p,
+    LAUNCH(h, qstream, "bin_stats", k_bin_stats, cdiv((uint64_t)B * 64, 256), 256, (const float4 *)q.sq.p, (const uint32_t *)q.qoff.p, B, q.ccnt.p, q.cmin.p,
            q.cmax.p);
     (void)hipEventRecord(q.ev_done, qstream);
     return rc;
@@ -1641,7 +1578,6 @@ struct BatchJob {
     int nb;
     hipStream_t qstream;
     QBatch qb;
-    bool to_worker;
 };
 static int batch_launches(const BatchJob &j) {
     erasor_hip_handle *h = j.h;
@@ -1652,16 +1588,8 @@ static int batch_launches(const BatchJob &j) {
     hipStream_t qstream = j.qstream;
     uint32_t nmax = 0;
     for (int k = 0; k < j.nb; ++k) nmax = std::max(nmax, j.qb.s[k].n);
-    TlCtx keep_tl = g_tl;
-    g_tl.h = h;
-    g_tl.cur = qstream;
-    g_tl.qi = j.sides[0];
-    struct TlRestore {
-        TlCtx k;
-        ~TlRestore() { g_tl = k; }
-    } tl_restore{keep_tl};
     const QBatch &qb = j.qb;
-#define LAUNCH_B(name, kern, gx, block, ...) LAUNCH(h, name, kern, dim3((gx), nb), block, qb, ##__VA_ARGS__)
+#define LAUNCH_B(name, kern, gx, block, ...) LAUNCH(h, qstream, name, kern, dim3((gx), nb), block, qb, ##__VA_ARGS__)
     LAUNCH_B("q_begin", k_query_begin_b, 1, 256, B + 1);
     LAUNCH_B("q_bbox", k_bbox_b, bbox_grid(nmax), 256);
     LAUNCH_B("q_keys", k_voxel_keys_es_b, std::max(1u, cdiv(nmax, 256)), 256, P.leaf_query);
@@ -1742,7 +1670,7 @@ static int flush_held(erasor_hip_handle *h) {
         if (nb == 1) {
             QSide &q = h->q[sides[i0]];
             chain_stream_waits(h, q, qstream);
-            ChainJob cj{h, sides[i0], qstream, q.ns, false, false, to_worker, {0}};
+            ChainJob cj{h, sides[i0], qstream, q.ns, false, false, {0}};
             memcpy(cj.Tl, q.Tl, sizeof(cj.Tl));
             const int rc = dispatch_chain(h, to_worker, &sides[i0], 1, [cj]() { return chain_launches(cj); });
             if (rc) return rc;
@@ -1751,7 +1679,6 @@ static int flush_held(erasor_hip_handle *h) {
             bj.h = h;
             bj.nb = nb;
             bj.qstream = qstream;
-            bj.to_worker = to_worker;
             memset(&bj.qb, 0, sizeof(bj.qb));
             for (int k = 0; k < nb; ++k) {
                 QSide &q = h->q[sides[i0 + k]];
@@ -1778,18 +1705,16 @@ static int enqueue_query_chain(erasor_hip_handle *h, int side, const void *scan_
         const int rc_w = chain_wait(h, side);  // (the side's previous chain: its events are waited for below)
         if (rc_w) return rc_w;
     }
-    SideGuard guard(h);
-    h->qi = side;
-    int rc = alloc_scan(h, std::max(ns, 1u));
+    QSide &q = h->q[side];
+    int rc = alloc_scan(h, q, std::max(ns, 1u));
     if (rc) return rc;
     const uint32_t B = h->B, nq = ns;
     if (B + 1 <= QB_NB_MAX) {
-        if (ensure(h, Q(h).qb_hist, (size_t)(B + 1) * std::max(1u, cdiv(nq, QB_TILE)) + 8)) return ERASOR_E_NO_DEVICE;
+        if (ensure(h, q.qb_hist, (size_t)(B + 1) * std::max(1u, cdiv(nq, QB_TILE)) + 8)) return ERASOR_E_NO_DEVICE;
     } else {
         const uint32_t nb_q = 256u * std::max(1u, cdiv(nq, RTILE));
         if (ensure(h, h->hist, nb_q) || ensure(h, h->hist_l, nb_q) || ensure(h, h->hist_t, cdiv(nb_q, 1024) + 2)) return ERASOR_E_NO_DEVICE;
     }
-    QSide &q = Q(h);
     // the common chain (voxelising, counting-sort bucketing, nothing profiled launch by launch) may go to the worker thread and may share
     // its launches with other scans' chains
     const bool common = !passthrough && !prevox && B + 1 <= QB_NB_MAX && h->prof != 1 && !g_debug_sync;
@@ -1801,7 +1726,7 @@ static int enqueue_query_chain(erasor_hip_handle *h, int side, const void *scan_
         // the side may still be executing a chain that was dropped (a prefetch that no step claimed): its kernels read
         // q.scan, and a scan that changes between the bounding-box pass and the voxel keys sends them astray
         if (q.used) HIPC(h, hipEventSynchronize(q.ev_done));
-        rc = stage_host_scan(h, scan_src, ns, qstream, fmt, nullptr);  // (on the chain's own stream: ordered before its first kernel)
+        rc = stage_host_scan(h, q, scan_src, ns, qstream, fmt, nullptr);  // (on the chain's own stream: ordered before its first kernel)
         if (rc) return rc;
         q.h2d_pending = false;
         q.fp = 0ull;
@@ -1817,7 +1742,7 @@ static int enqueue_query_chain(erasor_hip_handle *h, int side, const void *scan_
         // (round 6: a chain the step needs AT ONCE -- its own scan, not announced ahead -- is launched right here: handing it to the worker
         // only to wait for the worker's event records puts a thread wake-up in front of the step)
         const bool to_worker = h->worker && common && staged != 0;
-        ChainJob cj{h, side, qstream, ns, prevox, passthrough, to_worker, {0}};
+        ChainJob cj{h, side, qstream, ns, prevox, passthrough, {0}};
         memcpy(cj.Tl, T_l2b, sizeof(cj.Tl));
         if (to_worker) rc = dispatch_chain(h, true, &side, 1, [cj]() { return chain_launches(cj); });
         else rc = chain_launches(cj);
@@ -1876,7 +1801,7 @@ static int flush_held_if_due(erasor_hip_handle *h) {
     return ERASOR_OK;
 }
 
-// standalone entry points (voxelize, mapgen, sort hooks, ERASOR-class runs) use the active query side as scratch:
+// standalone entry points (voxelize, mapgen, sort hooks, ERASOR-class runs) use query side h->qi as scratch:
 // forget prefetched chains and let the query streams run dry first
 static void q_drain(erasor_hip_handle *h) {
     h->npend = 0;
@@ -1903,13 +1828,6 @@ struct Extents {
     enum From { HOST, COMMITTED, BEING_WRITTEN } from = HOST;
     uint32_t nF = 0, nFchunks = 0, o_begin = 0, o_chunk0 = 0, nOchunks = 0, nchunks = 0;
     const DevState *dev = nullptr;
-};
-// LAUNCH() targets h->cur: the launchers below take their stream and leave h->cur as they found it
-struct OnStream {
-    erasor_hip_handle *h;
-    hipStream_t keep;
-    OnStream(erasor_hip_handle *h_, hipStream_t s) : h(h_), keep(h_->cur) { h->cur = s; }
-    ~OnStream() { h->cur = keep; }
 };
 static inline OMeta *ometa_or_null(const erasor_hip_handle *h) { return h->use_ometa ? h->ometa.p : (OMeta *)nullptr; }
 
@@ -1942,8 +1860,7 @@ static void launch_voi_split(erasor_hip_handle *h, const float4 *F, const Extent
                               ext.o_chunk0, ext.nOchunks, xc, yc, voi_r2, h->vmask.p, h->hmask.p, h->cinfo.p, dev, capO_chunks, cap_chunks, ometa_or_null(h), se, ov);
         h->pending.push_back(ke);
     } else {
-        OnStream on(h, s);
-        LAUNCH(h, "voi_split", k_voi_split, grid, 256, F, ext.nF, ext.nFchunks, (const float2 *)h->Oxy.p, ext.o_begin, ext.o_chunk0, ext.nOchunks, xc, yc, voi_r2,
+        LAUNCH(h, s, "voi_split", k_voi_split, grid, 256, F, ext.nF, ext.nFchunks, (const float2 *)h->Oxy.p, ext.o_begin, ext.o_chunk0, ext.nOchunks, xc, yc, voi_r2,
                h->vmask.p, h->hmask.p, h->cinfo.p, dev, capO_chunks, cap_chunks, ometa_or_null(h), se, ov);
     }
 }
@@ -1989,14 +1906,13 @@ static ScanDone launch_chunk_scan(erasor_hip_handle *h, StepSet &to, hipStream_t
     const bool mb_count = h->B + 1 <= QB_NB_MAX;
     uint32_t *mb_tot = mb_count ? h->mb_tot.p : (uint32_t *)nullptr;
     const uint32_t mb_n = mb_count ? h->B + 2 : 0u, capO_chunks = ahead ? h->capO / CHUNK : 0u;
-    OnStream on(h, s);
     if (d.levels == 1) {
-        LAUNCH(h, "chunk_scan", k_chunk_scan_one, 1, 1024, (const uint32_t *)h->cinfo.p, ext.nchunks, h->pvl.p, h->phl.p, h->topv.p, h->toph.p, ahead ? 16u : grid,
+        LAUNCH(h, s, "chunk_scan", k_chunk_scan_one, 1, 1024, (const uint32_t *)h->cinfo.p, ext.nchunks, h->pvl.p, h->phl.p, h->topv.p, h->toph.p, ahead ? 16u : grid,
                ext.nFchunks, to.d_st.p, to.d_ctr.p, h->st, to.lab_slots.p, mb_tot, mb_n, ometa_or_null(h), capO_chunks, d.cap, ext.dev, cap_voi);
     } else {
-        LAUNCH(h, "chunk_scan", k_chunk_scan_local, grid, 256, (const uint32_t *)h->cinfo.p, ext.nchunks, h->pvl.p, h->phl.p, h->topv.p, h->toph.p, h->topr.p,
+        LAUNCH(h, s, "chunk_scan", k_chunk_scan_local, grid, 256, (const uint32_t *)h->cinfo.p, ext.nchunks, h->pvl.p, h->phl.p, h->topv.p, h->toph.p, h->topr.p,
                ext.dev, capO_chunks, d.cap, ahead ? 1u : 0u);
-        LAUNCH(h, "chunk_scan", k_chunk_scan_top, 1, 1024, h->topv.p, h->toph.p, grid, (const uint32_t *)h->pvl.p, (const uint32_t *)h->phl.p, ext.nchunks,
+        LAUNCH(h, s, "chunk_scan", k_chunk_scan_top, 1, 1024, h->topv.p, h->toph.p, grid, (const uint32_t *)h->pvl.p, (const uint32_t *)h->phl.p, ext.nchunks,
                ext.nFchunks, to.d_st.p, to.d_ctr.p, h->st, to.lab_slots.p, mb_tot, mb_n, (const uint32_t *)h->topr.p, ometa_or_null(h), capO_chunks, d.cap,
                ext.dev, cap_voi);
     }
@@ -2008,8 +1924,7 @@ static ScanDone launch_chunk_scan(erasor_hip_handle *h, StepSet &to, hipStream_t
 // overlapped step leaves the late table's slots alone
 static void launch_voi_gather(erasor_hip_handle *h, StepSet &to, hipStream_t s, const float4 *F, const Extents &ext, uint32_t items, const Xf &To,
                               const QSide &q, const unsigned long long *lmask) {
-    OnStream on(h, s);
-    LAUNCH(h, "voi_gather", k_voi_gather, std::max(1u, std::min<uint32_t>(cdiv(items, 4), 256 * 16)), 256, F, ext.nF, ext.nFchunks, h->Oxy.p, h->Ozi.p,
+    LAUNCH(h, s, "voi_gather", k_voi_gather, std::max(1u, std::min<uint32_t>(cdiv(items, 4), 256 * 16)), 256, F, ext.nF, ext.nFchunks, h->Oxy.p, h->Ozi.p,
            ext.o_chunk0, ext.nOchunks, (const unsigned long long *)h->vmask.p, (const unsigned long long *)h->hmask.p, (const uint32_t *)h->cinfo.p,
            (const uint32_t *)h->pvl.p, (const uint32_t *)h->phl.p, (const uint32_t *)h->topv.p, (const uint32_t *)h->toph.p, To, h->dp, to.d_st.p, to.d_ctr.p,
            (const Counters *)q.d_qctr.p, to.voi_ego.p, to.voi_key.p, to.voi_src.p, ometa_or_null(h), lmask, lmask ? h->capO / CHUNK : 0u);
@@ -2024,36 +1939,33 @@ static uint32_t bucket_tiles(const erasor_hip_handle *h, uint32_t n_voi) {
 // ... the histogram and its column scan (the bins' offsets into to.moff)
 static void launch_bucket_table(erasor_hip_handle *h, StepSet &to, hipStream_t s, uint32_t n_voi, uint32_t nbk) {
     const uint32_t *nvoi_dev = &to.d_st.p->voi_total;
-    OnStream on(h, s);
-    LAUNCH(h, "voi_bucket", k_mb_hist, bucket_tiles(h, n_voi), 1024, (const uint32_t *)to.voi_key.p, n_voi, nvoi_dev, nbk, h->mb_hist.p, h->mb_tot.p);
-    LAUNCH(h, "voi_bucket", k_mb_colscan, cdiv(nbk, MB_PAD), 256, h->mb_hist.p, n_voi, nvoi_dev, nbk, (const uint32_t *)h->mb_tot.p, to.moff.p);
+    LAUNCH(h, s, "voi_bucket", k_mb_hist, bucket_tiles(h, n_voi), 1024, (const uint32_t *)to.voi_key.p, n_voi, nvoi_dev, nbk, h->mb_hist.p, h->mb_tot.p);
+    LAUNCH(h, s, "voi_bucket", k_mb_colscan, cdiv(nbk, MB_PAD), 256, h->mb_hist.p, n_voi, nvoi_dev, nbk, (const uint32_t *)h->mb_tot.p, to.moff.p);
 }
 // ... the stable scatter into to.spts / ssrc / rk_a
 static void launch_bucket_scatter(erasor_hip_handle *h, StepSet &to, hipStream_t s, uint32_t n_voi, uint32_t nbk, int bits) {
     const uint32_t *nvoi_dev = &to.d_st.p->voi_total;
     const uint32_t ntile_ub = bucket_tiles(h, n_voi);
-    OnStream on(h, s);
     if (nbk <= MBW_NB_SMALL)
-        LAUNCH(h, "voi_bucket", k_mb_scatter_w<MBW_NB_SMALL>, ntile_ub, 1024, (const uint32_t *)to.voi_key.p, (const float4 *)to.voi_ego.p,
+        LAUNCH(h, s, "voi_bucket", k_mb_scatter_w<MBW_NB_SMALL>, ntile_ub, 1024, (const uint32_t *)to.voi_key.p, (const float4 *)to.voi_ego.p,
                (const uint32_t *)to.voi_src.p, n_voi, nvoi_dev, nbk, bits, (const uint32_t *)h->mb_hist.p, to.spts.p, to.ssrc.p, to.rk_a.p, h->dbg_stamps.p);
     else if (nbk <= MBW_NB_MAX)
-        LAUNCH(h, "voi_bucket", k_mb_scatter_w<MBW_NB_MAX>, ntile_ub, 1024, (const uint32_t *)to.voi_key.p, (const float4 *)to.voi_ego.p,
+        LAUNCH(h, s, "voi_bucket", k_mb_scatter_w<MBW_NB_MAX>, ntile_ub, 1024, (const uint32_t *)to.voi_key.p, (const float4 *)to.voi_ego.p,
                (const uint32_t *)to.voi_src.p, n_voi, nvoi_dev, nbk, bits, (const uint32_t *)h->mb_hist.p, to.spts.p, to.ssrc.p, to.rk_a.p, h->dbg_stamps.p);
     else
-        LAUNCH(h, "voi_bucket", k_mb_scatter, ntile_ub, 1024, (const uint32_t *)to.voi_key.p, (const float4 *)to.voi_ego.p, (const uint32_t *)to.voi_src.p,
+        LAUNCH(h, s, "voi_bucket", k_mb_scatter, ntile_ub, 1024, (const uint32_t *)to.voi_key.p, (const float4 *)to.voi_ego.p, (const uint32_t *)to.voi_src.p,
                n_voi, nvoi_dev, nbk, bits, (const uint32_t *)h->mb_hist.p, to.spts.p, to.ssrc.p, to.rk_a.p);
 }
 // The bins' statistics of the bucketed map.  with_srt (v3): the Scan Ratio Test's first pass rides along, bin by bin -- the query's
 // statistics are needed: the stream joins q's chain in front of the launch (with nodes announced ahead it finished long ago)
 static void launch_bin_stats(erasor_hip_handle *h, StepSet &to, hipStream_t s, const QSide &q, bool with_srt) {
     const uint32_t B = h->B;
-    OnStream on(h, s);
     if (with_srt) {
         (void)hipStreamWaitEvent(s, q.ev_done, 0);
-        LAUNCH(h, "bin_stats", k_bin_stats_srt, cdiv((uint64_t)B * 64, 256), 256, h->dp, (const float4 *)to.spts.p, (const uint32_t *)to.moff.p, B, to.mcnt.p,
+        LAUNCH(h, s, "bin_stats", k_bin_stats_srt, cdiv((uint64_t)B * 64, 256), 256, h->dp, (const float4 *)to.spts.p, (const uint32_t *)to.moff.p, B, to.mcnt.p,
                to.mmin.p, to.mmax.p, (const uint32_t *)q.ccnt.p, (const float *)q.cmin.p, (const float *)q.cmax.p, to.st1b.p);
     } else
-        LAUNCH(h, "bin_stats", k_bin_stats, cdiv((uint64_t)B * 64, 256), 256, (const float4 *)to.spts.p, (const uint32_t *)to.moff.p, B, to.mcnt.p, to.mmin.p,
+        LAUNCH(h, s, "bin_stats", k_bin_stats, cdiv((uint64_t)B * 64, 256), 256, (const float4 *)to.spts.p, (const uint32_t *)to.moff.p, B, to.mcnt.p, to.mmin.p,
                to.mmax.p);
 }
 // what every pass launched ahead assumes of the step that may take it: its number, the node's pose, the store, the split's buffers
@@ -2124,6 +2036,7 @@ struct StepPlan {
     float Tl_ticket[16];
     uint32_t ns = 0;      // points of the scan
     bool prevox = false;  // STEP_QUERY_PREVOXELIZED
+    QSide *q = nullptr;   // the step's query side (h->q[h->qi]: every stage's launches name its buffers)
     HostMarks MARK;
     // ---- sizes
     double xc = 0, yc = 0;  // the pose, OMU.cpp:246-247
@@ -2273,6 +2186,7 @@ static int step_admit(erasor_hip_handle *h, StepPlan &pl) {
         }
     h->qi = side;
     h->step_side = side;
+    pl.q = &h->q[side];
     rc = chain_wait(h, side);  // (the chain's events are waited for below: they must have been recorded)
     if (rc) return rc;
     pl.MARK("query chain");
@@ -2416,11 +2330,10 @@ static void enqueue_map_chain(erasor_hip_handle *h, StepPlan &pl) {
     const Extents &e = pl.ext;
     const uint32_t B = pl.B, n_voi = pl.n_voi;
     StepSet &cs = h->cset;
+    QSide &q = *pl.q;
     pl.MARK("  mapchain_begin");
     // With the query chains on streams of their own, the map chain simply opens the step on the main stream
     // (no fork / join events, one hardware queue less).
-    h->cur = h->stream;
-    h->bank = 1;
     {   // round 5: split, chunk scan, gather and the bucket table may all be there already -- launched beside the previous step's per-bin
         // launch (h->ov) -- if this step is exactly the step that was assumed then: node, pose, transform, store, buffers, room
         const bool ov_launched = h->ov.valid;
@@ -2456,8 +2369,8 @@ static void enqueue_map_chain(erasor_hip_handle *h, StepPlan &pl) {
         else
             h->last_scan_path = launch_chunk_scan(h, cs, h->stream, e, 0u, 0u, 0u).levels;
         h->spec.scan = ScanDone();
-        (void)hipStreamWaitEvent(h->stream, Q(h).ev_keys, 0);  // k_voi_gather must see the query side's error flag
-        launch_voi_gather(h, cs, h->stream, (const float4 *)h->F[h->curF].p, e, e.nFchunks * GATHER_SUB + e.nOchunks, h->To2b, Q(h), nullptr);
+        (void)hipStreamWaitEvent(h->stream, q.ev_keys, 0);  // k_voi_gather must see the query side's error flag
+        launch_voi_gather(h, cs, h->stream, (const float4 *)h->F[h->curF].p, e, e.nFchunks * GATHER_SUB + e.nOchunks, h->To2b, q, nullptr);
     }
     if (pl.mb_count) {
         if (!pl.use_ov) launch_bucket_table(h, cs, h->stream, n_voi, pl.nbk);  // (an overlapped step: launched ahead, behind k_late_gather)
@@ -2466,24 +2379,21 @@ static void enqueue_map_chain(erasor_hip_handle *h, StepPlan &pl) {
         pl.sm_keys = cs.rk_a.p;
     } else {
         const uint32_t *nvoi_dev = &pl.ds->voi_total, *sm_perm = nullptr;
-        radix_sort(h, cs.voi_key.p, n_voi, nvoi_dev, pl.bits, cs.rk_a.p, h->rk_b.p, h->rv_a.p, h->rv_b.p, &pl.sm_keys, &sm_perm, "voi_bucket");
-        if (n_voi) LAUNCH(h, "voi_bucket", k_gather, cdiv(n_voi, 256), 256, (const float4 *)cs.voi_ego.p, (const uint32_t *)cs.voi_src.p, sm_perm,
+        radix_sort(h, h->stream, 1, cs.voi_key.p, n_voi, nvoi_dev, pl.bits, cs.rk_a.p, h->rk_b.p, h->rv_a.p, h->rv_b.p, &pl.sm_keys, &sm_perm, "voi_bucket");
+        if (n_voi) LAUNCH(h, h->stream, "voi_bucket", k_gather, cdiv(n_voi, 256), 256, (const float4 *)cs.voi_ego.p, (const uint32_t *)cs.voi_src.p, sm_perm,
                           n_voi, nvoi_dev, cs.spts.p, cs.ssrc.p);
-        LAUNCH(h, "voi_bucket", k_bin_offsets, cdiv((uint64_t)std::max(n_voi, B + 2) + 1, 256), 256, pl.sm_keys, n_voi, nvoi_dev, B + 1, cs.moff.p);
+        LAUNCH(h, h->stream, "voi_bucket", k_bin_offsets, cdiv((uint64_t)std::max(n_voi, B + 2) + 1, 256), 256, pl.sm_keys, n_voi, nvoi_dev, B + 1, cs.moff.p);
     }
-    if (!pl.stats_ahead) launch_bin_stats(h, cs, h->stream, Q(h), pl.st1_ahead);
+    if (!pl.stats_ahead) launch_bin_stats(h, cs, h->stream, q, pl.st1_ahead);
     if (pl.use_ov) {
         // the entering outskirts entries are erased NOW that the step is certain (k_voi_gather left them: a getter could still ask
         // for the store as the previous step left it); on the early stream, in front of the next pass over the store (enqueued
         // behind the launches the main stream was waiting for)
-        h->cur = h->bstream;
-        LAUNCH(h, "voi_gather", k_o_commit, std::max(1u, std::min<uint32_t>(cdiv(e.nOchunks, 4), 2048)), 256, h->Oxy.p,
+        LAUNCH(h, h->bstream, "voi_gather", k_o_commit, std::max(1u, std::min<uint32_t>(cdiv(e.nOchunks, 4), 2048)), 256, h->Oxy.p,
                (const unsigned long long *)h->vmask.p, (const uint32_t *)h->cinfo.p, (const DevState *)pl.ds, h->capO / CHUNK, ometa_or_null(h),
-               (const Counters *)pl.dc, (const Counters *)Q(h).d_qctr.p);
+               (const Counters *)pl.dc, (const Counters *)q.d_qctr.p);
     }
     pl.MARK("  mapchain_end");
-    h->cur = h->stream;
-    h->bank = 0;
 }
 
 // Decides ov_next / nxt_side: may the next node's passes run beside this step's per-bin launch?  (Its chain goes into its queue NOW if it
@@ -2491,9 +2401,7 @@ static void enqueue_map_chain(erasor_hip_handle *h, StepPlan &pl) {
 static int step_next_overlap(erasor_hip_handle *h, StepPlan &pl) {
     if (pl.reserved && pl.have_pose && h->prof != 1 && !submap_would_move(h, pl.nx, pl.ny)) {
         if (h->npend == 0 && h->ann.valid && h->ann.to_valid) {
-            const int keep_side = h->qi;
             const int rc_f = flush_announced(h);
-            h->qi = keep_side;
             if (rc_f) return rc_f;
         }
         if (h->npend > 0 && h->q[h->pend[0]].pose_valid && h->q[h->pend[0]].to_valid) {
@@ -2518,12 +2426,11 @@ static void enqueue_early(erasor_hip_handle *h, StepPlan &pl) {
     pl.MARK("srt: begin");
     (void)hipStreamWaitEvent(h->bstream, h->ev_stats, 0);
     pl.MARK("  ev_stats record + wait");
-    h->cur = h->bstream;  // ---- the early stream: beside the per-bin launch
     // (round 6: ONE launch -- every workgroup of the early write-back derives the reserved offsets it needs from the status bytes itself,
     // the launch's last workgroup is k_srt4 for everything behind it: see k_assemble_early)
     {
         EarlyArgs ea;
-        fill_srt_args(ea, h, h->cset, Q(h));
+        fill_srt_args(ea, h, h->cset, *pl.q);
         ea.out_offR = h->out_offR.p;
         ea.gres_off = h->gres_off.p;
         ea.late = pl.late_out;
@@ -2534,7 +2441,7 @@ static void enqueue_early(erasor_hip_handle *h, StepPlan &pl) {
         ea.cnt = h->cset.lab_slots.p;
         // (one round of workgroups: a 1024-thread workgroup of this kernel has a compute unit to itself, and the per-bin launch and the query
         // chains hold some of the 256)
-        LAUNCH(h, "srt+assemble", k_assemble_early, std::min<uint32_t>(cdiv(pl.n_voi, 1024), ERASOR_EARLY_GMAP) + 1u, 1024, P, h->Tb2o, ea);
+        LAUNCH(h, h->bstream, "srt+assemble", k_assemble_early, std::min<uint32_t>(cdiv(pl.n_voi, 1024), ERASOR_EARLY_GMAP) + 1u, 1024, P, h->Tb2o, ea);
     }
     pl.MARK("  k_srt4 + assemble early");
     // (an overlapped step's late write-back joins at ev_scan, further down this stream and long there when the per-bin launch ends)
@@ -2584,7 +2491,6 @@ static void enqueue_early(erasor_hip_handle *h, StepPlan &pl) {
         ++h->n_spec_launched;  // (it is the split ahead of this node, with company)
         h->fly.spec_launched = true;
     }
-    h->cur = h->stream;  // ---- back on the main stream
 }
 
 // Stage 4: Scan Ratio Test, R-GPF, per-bin voxelisation (erasor.cpp:332-571), with the early stream beside the per-bin launch and the late
@@ -2594,23 +2500,24 @@ static void step_srt_and_bins(erasor_hip_handle *h, StepPlan &pl) {
     const uint32_t B = pl.B, n_voi = pl.n_voi;
     const bool reserved = pl.reserved, fold = pl.fold;
     StepSet &cs = h->cset;
+    const QSide &q = *pl.q;
     DevState *ds = pl.ds;
     if (reserved || pl.srt_in_revert) {
         // (no launch: k_assemble_early / the per-bin launch's last workgroup)
     } else if (B <= 1024 * SRT_KPT)
-        LAUNCH(h, "srt", k_srt4, 1, 1024, P, (const uint32_t *)cs.mcnt.p, (const float *)cs.mmin.p, (const float *)cs.mmax.p, (const uint32_t *)Q(h).ccnt.p,
-           (const float *)Q(h).cmin.p, (const float *)Q(h).cmax.p, h->st1.p, h->status.p, h->action.p, h->rev_idx.p, h->rev_list.p, h->vox_off.p, ds,
+        LAUNCH(h, h->stream, "srt", k_srt4, 1, 1024, P, (const uint32_t *)cs.mcnt.p, (const float *)cs.mmin.p, (const float *)cs.mmax.p, (const uint32_t *)q.ccnt.p,
+           (const float *)q.cmin.p, (const float *)q.cmax.p, h->st1.p, h->status.p, h->action.p, h->rev_idx.p, h->rev_list.p, h->vox_off.p, ds,
            fold ? h->out_off0.p : (uint32_t *)nullptr, fold ? h->rev_before.p : (uint32_t *)nullptr, fold ? h->crej_off.p : (uint32_t *)nullptr,
            pl.st1_ahead ? (const uint8_t *)cs.st1b.p : (const uint8_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
            (uint32_t *)nullptr, (LateEnt *)nullptr, -1.0);
     else
-        LAUNCH(h, "srt", k_srt, 1, 1024, P, (const uint32_t *)cs.mcnt.p, (const float *)cs.mmin.p, (const float *)cs.mmax.p, (const uint32_t *)Q(h).ccnt.p,
-           (const float *)Q(h).cmin.p, (const float *)Q(h).cmax.p, h->st1.p, h->status.p, h->action.p, h->rev_idx.p, h->rev_list.p, h->vox_off.p, ds);
+        LAUNCH(h, h->stream, "srt", k_srt, 1, 1024, P, (const uint32_t *)cs.mcnt.p, (const float *)cs.mmin.p, (const float *)cs.mmax.p, (const uint32_t *)q.ccnt.p,
+           (const float *)q.cmin.p, (const float *)q.cmax.p, h->st1.p, h->status.p, h->action.p, h->rev_idx.p, h->rev_list.p, h->vox_off.p, ds);
     // R-GPF and the per-bin voxelisation walk the reverted-bin LIST on a small fixed grid (n_rev is on the device)
     const uint32_t rev_grid = ERASOR_REV_GRID;
-    // v3: R-GPF and the per-bin voxelisation of a reverted bin in ONE launch (k_revert_bins); ERASOR_HIP_NO_FUSE=1: two launches (A/B)
+    // v3: R-GPF and the per-bin voxelisation of a reverted bin in ONE launch (k_revert_bins); two when every launch is profiled
     RevArgs ra;
-    ra.moff = cs.moff.p, ra.spts = cs.spts.p, ra.qoff = Q(h).qoff.p, ra.sq = Q(h).sq.p;
+    ra.moff = cs.moff.p, ra.spts = cs.spts.p, ra.qoff = q.qoff.p, ra.sq = q.sq.p;
     ra.gsK = h->gsK.p, ra.gsV = h->gsV.p, ra.gsL = h->gsL.p, ra.gsR = h->gsR.p, ra.gsH = h->gsH.p, ra.gsK2 = h->gsK2.p, ra.gsV2 = h->gsV2.p, ra.gsC = h->gsC.p;
     ra.gflag = h->gflag.p, ra.grank = h->grank.p, ra.glist = h->glist.p, ra.ng_arr = h->ng.p, ra.plane_n = h->plane_n.p, ra.plane_d = h->plane_d.p;
     ra.vox_out = h->vox_out.p, ra.nvox_out = h->nvox.p, ra.ctr = pl.dc, ra.dbg = h->dbg_stamps.p;
@@ -2619,19 +2526,19 @@ static void step_srt_and_bins(erasor_hip_handle *h, StepPlan &pl) {
     ra.h_base = (uint32_t)(((size_t)n_voi + pl.nq + 8) / 32 + 2 * (size_t)B + 16);
     if (pl.srt_in_revert) {
         SrtArgs sa;
-        fill_srt_args(sa, h, cs, Q(h));
+        fill_srt_args(sa, h, cs, q);
         if (!fold) sa.out_off0 = sa.rev_before = sa.crej_off = nullptr;
         if (reserved) sa.status = nullptr;  // (k_srt4 is the first workgroup of k_assemble_early, on the early stream: no extra workgroup here)
         if (reserved) (void)hipEventRecord(h->ev_stats, h->stream);  // (the bin statistics are there: the early stream may start)
-        LAUNCH(h, "rgpf+bin_voxelize", k_revert_bins_srt, std::min<uint32_t>(rev_grid, B) + (reserved ? 0u : 1u), 1024, P, sa, ra);
+        LAUNCH(h, h->stream, "rgpf+bin_voxelize", k_revert_bins_srt, std::min<uint32_t>(rev_grid, B) + (reserved ? 0u : 1u), 1024, P, sa, ra);
         pl.MARK("per-bin launch");
         if (reserved) enqueue_early(h, pl);
         // (the reverted list, the reserved offsets, the late table; ev_scan: also the next step's masks and chunk prefix, for the late gather)
         if (reserved) (void)hipStreamWaitEvent(h->stream, pl.ov_next ? h->ev_scan : h->ev_srt4, 0);
         pl.MARK("  ev_srt4 wait");
         if (reserved)
-            LAUNCH(h, "assemble", k_assemble_late, std::min<uint32_t>(rev_grid, B) + 1u, 256, P, h->Tb2o, (const uint32_t *)h->rev_list.p, (const float4 *)cs.spts.p,
-                   (const uint32_t *)cs.ssrc.p, (const uint32_t *)cs.moff.p, (const uint32_t *)Q(h).qoff.p, (const uint8_t *)h->gflag.p,
+            LAUNCH(h, h->stream, "assemble", k_assemble_late, std::min<uint32_t>(rev_grid, B) + 1u, 256, P, h->Tb2o, (const uint32_t *)h->rev_list.p, (const float4 *)cs.spts.p,
+                   (const uint32_t *)cs.ssrc.p, (const uint32_t *)cs.moff.p, (const uint32_t *)q.qoff.p, (const uint8_t *)h->gflag.p,
                    (const uint32_t *)h->grank.p, (const uint32_t *)h->ng.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->vox_off.p,
                    (const float4 *)h->vox_out.p, (const uint32_t *)h->out_offR.p, (const uint32_t *)h->gres_off.p, (const uint32_t *)h->out_off0.p,
                    (const uint32_t *)h->rev_before.p, pl.late_out, h->late_holes[h->late_idx ^ 1].p, h->out_off.p, h->ground_off.p, h->rej_off.p, ds, pl.Fnew,
@@ -2640,26 +2547,26 @@ static void step_srt_and_bins(erasor_hip_handle *h, StepPlan &pl) {
                    pl.use_ov ? (const LateEnt *)h->late[h->late_idx].p : (const LateEnt *)nullptr,
                    pl.use_ov ? (const uint32_t *)h->late_holes[h->late_idx].p : (const uint32_t *)nullptr, pl.use_ov ? h->n_late_F : 0u);
     } else if (P.version == 3 && h->prof != 1) {
-        LAUNCH(h, "rgpf+bin_voxelize", k_revert_bins, std::min<uint32_t>(rev_grid, B), 1024, P, (const uint32_t *)h->rev_list.p, (const DevState *)ds,
+        LAUNCH(h, h->stream, "rgpf+bin_voxelize", k_revert_bins, std::min<uint32_t>(rev_grid, B), 1024, P, (const uint32_t *)h->rev_list.p, (const DevState *)ds,
                (const uint32_t *)h->vox_off.p, ra);
     } else {
         // (two launches: the stages' global-memory paths do not overlap in time and share the scratch arrays from their start)
         ra.vox_base = 0u;
         ra.h_base = 0u;
-        LAUNCH(h, "rgpf", k_rgpf2, std::min<uint32_t>(rev_grid, B), 1024, P, (const uint32_t *)h->rev_list.p, (const DevState *)ds, ra);
+        LAUNCH(h, h->stream, "rgpf", k_rgpf2, std::min<uint32_t>(rev_grid, B), 1024, P, (const uint32_t *)h->rev_list.p, (const DevState *)ds, ra);
         if (P.version == 3)
-            LAUNCH(h, "bin_voxelize", k_binvox2, std::min<uint32_t>(rev_grid, B), 1024, P, (const uint32_t *)h->rev_list.p, (const DevState *)ds,
+            LAUNCH(h, h->stream, "bin_voxelize", k_binvox2, std::min<uint32_t>(rev_grid, B), 1024, P, (const uint32_t *)h->rev_list.p, (const DevState *)ds,
                    (const uint32_t *)h->vox_off.p, ra);
     }
     if (fold) {
         // (no launch)
     } else if (B <= 1024 * SRT_KPT)
-        LAUNCH(h, "layout", k_layout4, 1, 1024, P, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p, (const uint32_t *)cs.mcnt.p,
-           (const uint32_t *)Q(h).ccnt.p, (const uint32_t *)cs.moff.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->ng.p, h->out_off.p,
+        LAUNCH(h, h->stream, "layout", k_layout4, 1, 1024, P, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p, (const uint32_t *)cs.mcnt.p,
+           (const uint32_t *)q.ccnt.p, (const uint32_t *)cs.moff.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->ng.p, h->out_off.p,
            h->ground_off.p, h->rej_off.p, h->crej_off.p, ds);
     else
-        LAUNCH(h, "layout", k_layout, 1, 1024, P, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p, (const uint32_t *)cs.mcnt.p,
-           (const uint32_t *)Q(h).ccnt.p, (const uint32_t *)cs.moff.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->ng.p, h->out_off.p,
+        LAUNCH(h, h->stream, "layout", k_layout, 1, 1024, P, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p, (const uint32_t *)cs.mcnt.p,
+           (const uint32_t *)q.ccnt.p, (const uint32_t *)cs.moff.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->ng.p, h->out_off.p,
            h->ground_off.p, h->rej_off.p, h->crej_off.p, ds);
 }
 
@@ -2669,21 +2576,22 @@ static void step_write_back(erasor_hip_handle *h, StepPlan &pl) {
     const DP &P = h->dp;
     const uint32_t B = pl.B, n_voi = pl.n_voi;
     StepSet &cs = h->cset;
+    const QSide &q = *pl.q;
     // v3: the voxelised reverted bins are written by `tail` extra workgroups of the same launch (from the reverted list)
     const uint32_t tail = (P.version == 3 && n_voi) ? 32u : 0u;
 #define ASM_ARGS(FOLDPTR)                                                                                                                   \
     P, h->Tb2o, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p, pl.sm_keys, (const float4 *)cs.spts.p, (const uint32_t *)cs.ssrc.p, \
-        (const uint32_t *)cs.moff.p, (const uint32_t *)Q(h).ccnt.p, (const uint8_t *)h->gflag.p, (const uint32_t *)h->grank.p, h->out_off.p,   \
+        (const uint32_t *)cs.moff.p, (const uint32_t *)q.ccnt.p, (const uint8_t *)h->gflag.p, (const uint32_t *)h->grank.p, h->out_off.p,   \
         h->ground_off.p, h->rej_off.p, pl.ds, pl.Fnew, h->rejected.p, h->rejected_src.p, cs.lab_slots.p, tail, (const uint32_t *)h->rev_list.p,      \
-        (const uint32_t *)Q(h).qoff.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->vox_off.p, (const float4 *)h->vox_out.p,              \
+        (const uint32_t *)q.qoff.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->vox_off.p, (const float4 *)h->vox_out.p,              \
         (const uint32_t *)(FOLDPTR ? h->out_off0.p : nullptr), (const uint32_t *)(FOLDPTR ? h->rev_before.p : nullptr), (const uint32_t *)h->ng.p
     const uint32_t asm_grid = std::min<uint32_t>(cdiv(n_voi, 256), 2048) + tail;
-    if (n_voi && pl.fold) LAUNCH(h, "assemble", (k_assemble_map<true, true>), asm_grid, 256, ASM_ARGS(true));
-    else if (n_voi) LAUNCH(h, "assemble", (k_assemble_map<true, false>), asm_grid, 256, ASM_ARGS(false));
+    if (n_voi && pl.fold) LAUNCH(h, h->stream, "assemble", (k_assemble_map<true, true>), asm_grid, 256, ASM_ARGS(true));
+    else if (n_voi) LAUNCH(h, h->stream, "assemble", (k_assemble_map<true, false>), asm_grid, 256, ASM_ARGS(false));
 #undef ASM_ARGS
     if (!tail)
-        LAUNCH(h, "assemble", k_assemble_bins<true>, B, 256, P, h->Tb2o, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p,
-               (const uint32_t *)Q(h).qoff.p, (const float4 *)Q(h).sq.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->vox_off.p,
+        LAUNCH(h, h->stream, "assemble", k_assemble_bins<true>, B, 256, P, h->Tb2o, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p,
+               (const uint32_t *)q.qoff.p, (const float4 *)q.sq.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->vox_off.p,
                (const float4 *)h->vox_out.p, (const uint32_t *)h->out_off.p, (const uint32_t *)h->crej_off.p, pl.Fnew, h->curr_rejected.p, cs.lab_slots.p);
     // (label counters of the new VoI-resident region are accumulated by the two assemble kernels)
 }
@@ -2704,8 +2612,8 @@ static int step_end_and_ahead(erasor_hip_handle *h, StepPlan &pl) {
     se.ctr = pl.dc;
     se.out = h->pin;
     se.lab_slots = (const unsigned long long *)h->cset.lab_slots.p;
-    se.qctr = (const Counters *)Q(h).d_qctr.p;
-    se.q_nvox = (const uint32_t *)Q(h).d_nvox.p;
+    se.qctr = (const Counters *)pl.q->d_qctr.p;
+    se.q_nvox = (const uint32_t *)pl.q->d_nvox.p;
     se.seq = h->step_seq;
     const bool end_in_split = spec && h->prof != 1 && !pl.ov_next;
     h->fly.nchunks = pl.ext.nchunks;
@@ -2723,7 +2631,7 @@ static int step_end_and_ahead(erasor_hip_handle *h, StepPlan &pl) {
         // seven passes twice: 0.1903 / 0.1876 -> 0.1885 / 0.1848 ms per scan; 39 M-point map 0.326 / 0.330 -> 0.3155 / 0.3197)
         // (joined at ev_scan in front of the late write-back already)
         pl.MARK("  ev_scan wait");
-        LAUNCH(h, "voi_gather", k_late_gather, std::min<uint32_t>(2 * B, 128u) + 1u, 256, (const float4 *)pl.Fnew, (const LateEnt *)pl.late_out,
+        LAUNCH(h, h->stream, "voi_gather", k_late_gather, std::min<uint32_t>(2 * B, 128u) + 1u, 256, (const float4 *)pl.Fnew, (const LateEnt *)pl.late_out,
                (const DevState *)pl.ds, h->Oxy.p, h->Ozi.p, (const unsigned long long *)h->vmask.p, (const unsigned long long *)h->hmask.p,
                (const uint32_t *)h->pvl.p, (const uint32_t *)h->phl.p, (const uint32_t *)h->topv.p, (const uint32_t *)h->toph.p, pl.nx, pl.ny, P.voi_r2,
                to_xf(nq_.To), P, os.d_st.p, os.d_ctr.p, (const Counters *)nq_.d_qctr.p, os.voi_ego.p, os.voi_key.p, os.voi_src.p, se);
@@ -2740,15 +2648,13 @@ static int step_end_and_ahead(erasor_hip_handle *h, StepPlan &pl) {
     } else {
         if (pl.reserved) (void)hipStreamWaitEvent(h->stream, h->ev_asm, 0);  // (the early half of the write-back, its label tallies)
         if (!end_in_split)
-            LAUNCH(h, "step_end", k_step_end, 1, 1, se.st, se.ctr, se.out, se.lab_slots, se.qctr, se.q_nvox, se.seq);
+            LAUNCH(h, h->stream, "step_end", k_step_end, 1, 1, se.st, se.ctr, se.out, se.lab_slots, se.qctr, se.q_nvox, se.seq);
         if (spec) launch_split_ahead(h, pl.nx, pl.ny, pl.ext.nchunks, end_in_split ? &se : (const StepEnd *)nullptr);
     }
     pl.MARK("late gather + table ahead / end");
     // the NEXT scan's query chain goes into its queue now, behind this step's own launches; it runs while we wait
-    const int keep_side = h->qi;
     int rc_next = flush_announced(h);
     if (!rc_next) rc_next = flush_held_if_due(h);  // (a chain held back for a shared set of launches whose own step is near)
-    h->qi = keep_side;
     if (rc_next) {
         (void)hipStreamSynchronize(h->stream);
         h->spec.valid = false;
@@ -2767,7 +2673,7 @@ static void step_publish(erasor_hip_handle *h, StepPlan &pl) {
     h->fly.flags = pl.flags;
     // (what a step that has to run again reads: a host scan's staged copy -- float4 rows in the side's pinned buffer --, never the
     // caller's buffer, which is the caller's again once this call has returned)
-    h->fly.scan_src = (pl.src_is_device || !pl.n_scan) ? pl.scan_src : (const void *)Q(h).stage;
+    h->fly.scan_src = (pl.src_is_device || !pl.n_scan) ? pl.scan_src : (const void *)pl.q->stage;
     h->fly.n_scan = pl.n_scan;
     h->fly.src_is_device = pl.src_is_device;
     memcpy(h->fly.Tl, pl.T_l2b, sizeof(h->fly.Tl));
@@ -2792,7 +2698,7 @@ static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_sca
     if (rc) return rc;
     enqueue_map_chain(h, pl);
     pl.MARK("map chain");
-    HIPC(h, hipStreamWaitEvent(h->stream, Q(h).ev_done, 0));  // join: the query's bins are ready
+    HIPC(h, hipStreamWaitEvent(h->stream, pl.q->ev_done, 0));  // join: the query's bins are ready
     h->ov_mode = pl.reserved;
     rc = step_next_overlap(h, pl);
     if (rc) return rc;
@@ -3102,20 +3008,19 @@ static int prefetch_common(erasor_hip_handle *h, const void *scan_xyzi, size_t n
         return ERASOR_E_STATE;
     }
     if (n && !src_is_device) {  // a host scan is taken over at once
-        SideGuard guard(h);
-        h->qi = side;
-        rc = alloc_scan(h, (uint32_t)n);
+        QSide &q = h->q[side];
+        rc = alloc_scan(h, q, (uint32_t)n);
         if (rc) return rc;
         rc = chain_wait(h, side);
         if (rc) return rc;
-        if (Q(h).used) HIPC(h, hipEventSynchronize(Q(h).ev_done));  // (a dropped chain may still be reading this side's scan)
-        rc = stage_host_scan(h, scan_xyzi, (uint32_t)n, copy_stream(h), fmt, nullptr);
+        if (q.used) HIPC(h, hipEventSynchronize(q.ev_done));  // (a dropped chain may still be reading this side's scan)
+        rc = stage_host_scan(h, q, scan_xyzi, (uint32_t)n, copy_stream(h), fmt, nullptr);
         if (rc) return rc;
         h->ann.fp = 0ull;
         h->ann.fp_valid = false;
-        Q(h).fp_valid = false;  // (the side's buffer holds a new copy)
-        HIPC(h, hipEventRecord(Q(h).ev_h2d, copy_stream(h)));
-        Q(h).h2d_pending = true;
+        q.fp_valid = false;  // (the side's buffer holds a new copy)
+        HIPC(h, hipEventRecord(q.ev_h2d, copy_stream(h)));
+        q.h2d_pending = true;
     } else {
         h->ann.fp = 0ull;
         h->ann.fp_valid = false;
@@ -3143,12 +3048,8 @@ static int prefetch_common(erasor_hip_handle *h, const void *scan_xyzi, size_t n
         rc = flush_announced(h);
         if (!rc) rc = flush_held_if_due(h);
         if (rc) return rc;
-        if (next_in_line && pose && !h->fly.flags && !h->fly.spec_launched && !h->ov.valid && !submap_would_move(h, nx, ny)) {
-            hipStream_t keep = h->cur;
-            h->cur = h->stream;
+        if (next_in_line && pose && !h->fly.flags && !h->fly.spec_launched && !h->ov.valid && !submap_would_move(h, nx, ny))
             launch_split_ahead(h, nx, ny, h->fly.nchunks, nullptr);
-            h->cur = keep;
-        }
     }
     return ERASOR_OK;
 }
@@ -3287,19 +3188,15 @@ int map_to_device(erasor_hip_handle *h, DBuf<float4> &dense, size_t *n_out) {
     const size_t total = (size_t)h->nFv + (size_t)h->o_valid + (size_t)h->nC;
     *n_out = total;
     if (ensure(h, dense, total + 8)) return ERASOR_E_NO_DEVICE;
-    struct Restore {  // (also on the error returns below: the stream LAUNCH() targets, the temporaries)
-        erasor_hip_handle *h;
-        hipStream_t keep;
+    struct Restore {  // (the temporaries go on the error returns below as well)
         DBuf<uint32_t> flag, pl, tops;
         ~Restore() {
             release(flag);
             release(pl);
             release(tops);
-            h->cur = keep;
         }
-    } rs{h, h->cur, {}, {}, {}};
+    } rs;
     DBuf<uint32_t> &flag = rs.flag, &pl = rs.pl, &tops = rs.tops;
-    h->cur = h->stream;
     {
         const int rc_f = copy_F_dense(h, dense.p);
         if (rc_f) return rc_f;
@@ -3307,9 +3204,9 @@ int map_to_device(erasor_hip_handle *h, DBuf<float4> &dense, size_t *n_out) {
     const uint32_t span = h->capO - h->o_begin;
     if (span && h->o_valid) {
         if (ensure(h, flag, span + 1) || ensure(h, pl, span + 1) || ensure(h, tops, span / 1024 + 4)) return ERASOR_E_NO_DEVICE;
-        LAUNCH(h, "replicate", k_o_valid, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, h->o_begin, h->capO, flag.p);
-        scan_u32(h, flag.p, pl.p, tops.p, span, span, nullptr, nullptr, "replicate");
-        LAUNCH(h, "replicate", k_o_compact, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, (const float2 *)h->Ozi.p, h->o_begin, h->capO,
+        LAUNCH(h, h->stream, "replicate", k_o_valid, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, h->o_begin, h->capO, flag.p);
+        scan_u32(h, h->stream, flag.p, pl.p, tops.p, span, span, nullptr, nullptr, "replicate");
+        LAUNCH(h, h->stream, "replicate", k_o_compact, cdiv(span, 256), 256, (const float2 *)h->Oxy.p, (const float2 *)h->Ozi.p, h->o_begin, h->capO,
                (const uint32_t *)flag.p, (const uint32_t *)pl.p, (const uint32_t *)tops.p, dense.p + h->nFv);
         HIPC(h, hipStreamSynchronize(h->stream));
     }
@@ -3486,6 +3383,7 @@ static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t n
 // ERASOR::get_static_estimate hands out, erasor.cpp:612-626), assembled into the retired F buffer (free until the next step)
 static int assemble_egocentric(erasor_hip_handle *h, float4 **out) {
     const DevState &s = h->st;
+    const QSide &q = h->q[h->qi];
     if (ensure(h, h->F[h->curF ^ 1], (size_t)s.nF_new + 8)) return ERASOR_E_NO_DEVICE;
     // the kernel reads the LAST step's state (sizes of its VoI and of its output): from a copy of the host mirror, not from the live
     // device state -- the next step's chunk scan may have opened that already (launched ahead, round 4)
@@ -3495,15 +3393,15 @@ static int assemble_egocentric(erasor_hip_handle *h, float4 **out) {
     const DP &P = h->dp;
     const uint32_t B = h->B, n_voi = h->last_n_voi;
     if (n_voi)
-        LAUNCH(h, "get_cloud", (k_assemble_map<false, false>), std::min<uint32_t>(cdiv(n_voi, 256), 2048), 256, P, h->Tb2o, (const uint8_t *)h->action.p,
+        LAUNCH(h, h->stream, "get_cloud", (k_assemble_map<false, false>), std::min<uint32_t>(cdiv(n_voi, 256), 2048), 256, P, h->Tb2o, (const uint8_t *)h->action.p,
                (const uint32_t *)h->rev_idx.p, h->last_skeys, (const float4 *)h->cset.spts.p, (const uint32_t *)h->cset.ssrc.p,
-               (const uint32_t *)h->cset.moff.p, (const uint32_t *)Q(h).ccnt.p, (const uint8_t *)h->gflag.p, (const uint32_t *)h->grank.p,
+               (const uint32_t *)h->cset.moff.p, (const uint32_t *)q.ccnt.p, (const uint8_t *)h->gflag.p, (const uint32_t *)h->grank.p,
                h->out_off.p, h->ground_off.p, h->rej_off.p,
                h->d_st_get.p, tmp, (float4 *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr, 0u, (const uint32_t *)nullptr,
                (const uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, (const float4 *)nullptr, (const uint32_t *)nullptr,
                (const uint32_t *)nullptr, (const uint32_t *)nullptr);
-    LAUNCH(h, "get_cloud", k_assemble_bins<false>, B, 256, P, h->Tb2o, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p,
-           (const uint32_t *)Q(h).qoff.p, (const float4 *)Q(h).sq.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->vox_off.p,
+    LAUNCH(h, h->stream, "get_cloud", k_assemble_bins<false>, B, 256, P, h->Tb2o, (const uint8_t *)h->action.p, (const uint32_t *)h->rev_idx.p,
+           (const uint32_t *)q.qoff.p, (const float4 *)q.sq.p, (const uint32_t *)h->nvox.p, (const uint32_t *)h->vox_off.p,
            (const float4 *)h->vox_out.p, (const uint32_t *)h->out_off.p, (const uint32_t *)h->crej_off.p, tmp, (float4 *)nullptr, (unsigned long long *)nullptr);
     HIPC(h, hipStreamSynchronize(h->stream));
     *out = tmp;
@@ -3522,7 +3420,7 @@ int erasor_hip_get_cloud(erasor_hip_handle *h, int which, float *dst, size_t cap
     if (which == ERASOR_CLOUD_CURR_REJECTED) return out_cloud_collected(h, h->curr_rejected.p, s.n_curr_rejected, dst, cap, n);
     HIPC(h, hipStreamSynchronize(h->stream));
     switch (which) {
-        case ERASOR_CLOUD_QUERY_VOI: return out_cloud(h, Q(h).query.p, h->last_nq, dst, cap, n);
+        case ERASOR_CLOUD_QUERY_VOI: return out_cloud(h, h->q[h->qi].query.p, h->last_nq, dst, cap, n);
         case ERASOR_CLOUD_MAP_VOI: {
             if (!s.n_voi_dead) return out_cloud(h, h->cset.voi_ego.p, h->last_n_voi, dst, cap, n);
             // (round 5: an overlapped step's VoI-order array keeps places no point came to, key B + 1: the VoI is what is left)
@@ -3534,13 +3432,10 @@ int erasor_hip_get_cloud(erasor_hip_handle *h, int which, float *dst, size_t cap
             DBuf<float4> tmp;
             if (ensure(h, flag, (size_t)tot + 1) || ensure(h, pl, (size_t)tot + 1) || ensure(h, tops, tot / 1024 + 4) || ensure(h, tmp, (size_t)h->last_n_voi + 1))
                 return ERASOR_E_NO_DEVICE;
-            hipStream_t keep = h->cur;
-            h->cur = h->stream;
-            LAUNCH(h, "get_cloud", k_voi_live, cdiv(tot, 256), 256, (const uint32_t *)h->cset.voi_key.p, tot, h->B, flag.p);
-            scan_u32(h, flag.p, pl.p, tops.p, tot, tot, nullptr, nullptr, "get_cloud");
-            LAUNCH(h, "get_cloud", k_f_compact, cdiv(tot, 256), 256, (const float4 *)h->cset.voi_ego.p, tot, (const uint32_t *)flag.p, (const uint32_t *)pl.p,
+            LAUNCH(h, h->stream, "get_cloud", k_voi_live, cdiv(tot, 256), 256, (const uint32_t *)h->cset.voi_key.p, tot, h->B, flag.p);
+            scan_u32(h, h->stream, flag.p, pl.p, tops.p, tot, tot, nullptr, nullptr, "get_cloud");
+            LAUNCH(h, h->stream, "get_cloud", k_f_compact, cdiv(tot, 256), 256, (const float4 *)h->cset.voi_ego.p, tot, (const uint32_t *)flag.p, (const uint32_t *)pl.p,
                    (const uint32_t *)tops.p, tmp.p);
-            h->cur = keep;
             const int rc_c = d2h(h, dst, tmp.p, (size_t)h->last_n_voi * sizeof(float4));
             release(flag);
             release(pl);
@@ -3590,9 +3485,10 @@ int erasor_hip_get_bins(erasor_hip_handle *h, int which, uint32_t *count, double
     const uint32_t B = h->B, R = h->P.num_rings, S = h->P.num_sectors;
     std::vector<uint32_t> c(B);
     std::vector<float> mn(B), mx(B);
-    HIPC(h, hipMemcpy(c.data(), which ? Q(h).ccnt.p : h->cset.mcnt.p, B * 4, hipMemcpyDeviceToHost));
-    HIPC(h, hipMemcpy(mn.data(), which ? Q(h).cmin.p : h->cset.mmin.p, B * 4, hipMemcpyDeviceToHost));
-    HIPC(h, hipMemcpy(mx.data(), which ? Q(h).cmax.p : h->cset.mmax.p, B * 4, hipMemcpyDeviceToHost));
+    const QSide &q = h->q[h->qi];
+    HIPC(h, hipMemcpy(c.data(), which ? q.ccnt.p : h->cset.mcnt.p, B * 4, hipMemcpyDeviceToHost));
+    HIPC(h, hipMemcpy(mn.data(), which ? q.cmin.p : h->cset.mmin.p, B * 4, hipMemcpyDeviceToHost));
+    HIPC(h, hipMemcpy(mx.data(), which ? q.cmax.p : h->cset.mmax.p, B * 4, hipMemcpyDeviceToHost));
     for (uint32_t key = 0; key < B; ++key) {  // device key = sector*R + ring -> API index = ring*S + sector
         const uint32_t ring = key % R, sector = key / R;
         const uint32_t o = ring * S + sector;
@@ -3634,8 +3530,9 @@ int erasor_hip_get_rpod(erasor_hip_handle *h, int which, float *xyzi, size_t cap
         src = h->cset.spts.p;
         total = off[B];
     } else if (which == 1) {
-        HIPC(h, hipMemcpy(off.data(), Q(h).qoff.p, (size_t)(B + 1) * 4, hipMemcpyDeviceToHost));
-        src = Q(h).sq.p;
+        const QSide &q = h->q[h->qi];
+        HIPC(h, hipMemcpy(off.data(), q.qoff.p, (size_t)(B + 1) * 4, hipMemcpyDeviceToHost));
+        src = q.sq.p;
         total = off[B];
     } else {
         HIPC(h, hipMemcpy(off.data(), h->out_off.p, (size_t)B * 4, hipMemcpyDeviceToHost));
@@ -3682,7 +3579,7 @@ int erasor_hip_get_planes(erasor_hip_handle *h, uint32_t *bin_index, float *norm
     return ERASOR_OK;
 }
 
-// erasor_utils::voxelize_preserving_labels (utils.cpp:80-114) of a DEVICE cloud; the result is Q(h).query[0..*nq_out).
+// erasor_utils::voxelize_preserving_labels (utils.cpp:80-114) of a DEVICE cloud; the result is h->q[h->qi].query[0..*nq_out).
 // d_src may be any device buffer except the scan-side scratch itself.
 static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t ns, double leaf_size, uint32_t *nq_out, bool *passthrough) {
     if (passthrough) *passthrough = false;
@@ -3690,15 +3587,16 @@ static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t n
     // this borrows the query side of the last finished step: its QUERY_VOI / STATIC_ESTIMATE / ... read-backs are gone
     // (erasor_hip_get_cloud answers ERASOR_E_STATE until the next step instead of handing out clobbered buffers)
     h->have_step = false;
-    int rc = alloc_scan(h, std::max(ns, 1u));
+    QSide &q = h->q[h->qi];
+    int rc = alloc_scan(h, q, std::max(ns, 1u));
     if (rc) return rc;
-    Q(h).scan_in = d_src;
-    LAUNCH(h, "q_begin", k_query_begin, 1, 256, Q(h).d_qctr.p, Q(h).bb.p, (uint32_t *)nullptr, 0u, Q(h).d_nvox.p, 0u);
-    voxelize_query_part1(h, ns, (float)leaf_size, [] {});
+    q.scan_in = d_src;
+    LAUNCH(h, h->stream, "q_begin", k_query_begin, 1, 256, q.d_qctr.p, q.bb.p, (uint32_t *)nullptr, 0u, q.d_nvox.p, 0u);
+    voxelize_query_part1(h, h->stream, q, ns, (float)leaf_size, [] {});
     uint32_t nvox_host = 0;
     VoxGrid g;
-    HIPC(h, hipMemcpyAsync(&nvox_host, Q(h).d_nvox.p, sizeof(nvox_host), hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipMemcpyAsync(&g, Q(h).qgrid.p, sizeof(g), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipMemcpyAsync(&nvox_host, q.d_nvox.p, sizeof(nvox_host), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipMemcpyAsync(&g, q.qgrid.p, sizeof(g), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
     if (ns && g.overflow) {
         if (g.overflow == 2) {
@@ -3706,7 +3604,7 @@ static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t n
             return ERASOR_E_INVALID;
         }
         // PCL returns the input unchanged (utils.cpp:88-91); the label search then answers with the point itself or its first duplicate
-        rc = enqueue_passthrough(h, d_src, ns, nullptr, Q(h).query.p, nullptr);
+        rc = enqueue_passthrough(h, h->stream, q, d_src, ns, nullptr, q.query.p, nullptr);
         if (rc) return rc;
         HIPC(h, hipStreamSynchronize(h->stream));
         *nq_out = ns;
@@ -3719,15 +3617,15 @@ static int voxelize_device(erasor_hip_handle *h, const float4 *d_src, uint32_t n
         // identity lidar->body; the R-POD key output is ignored
         const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
         // x*1 + y*0 + z*0 + 0 reproduces x exactly (0*finite = 0, x+0 = x; -0.0 would become +0.0, irrelevant for a centroid)
-        LAUNCH(h, "q_centroids", k_centroids, cdiv((uint64_t)nq * 8, 256), 256, Q(h).scan_in, (const uint32_t *)Q(h).qk_b.p, (const uint32_t *)Q(h).qv_b.p,
-               (const uint32_t *)Q(h).run_begin.p, (const uint32_t *)Q(h).d_nvox.p, Q(h).cent.p, Q(h).ukeys.p, Q(h).hkey.p, Q(h).hval.p, Q(h).hbits);
-        LAUNCH(h, "q_nn", k_query_nn, cdiv((uint64_t)nq * NN_SUB, 256), 256, Q(h).scan_in, (const uint32_t *)Q(h).qv_b.p, (const uint32_t *)Q(h).run_begin.p,
-               (const uint32_t *)Q(h).ukeys.p, (const float4 *)Q(h).cent.p, (const uint32_t *)Q(h).d_nvox.p, (const VoxGrid *)Q(h).qgrid.p, to_xf(I),
-               h->dp, Q(h).d_qctr.p, Q(h).query.p, Q(h).qkey.p, (const uint32_t *)Q(h).hkey.p, (const uint32_t *)Q(h).hval.p, Q(h).hbits);
+        LAUNCH(h, h->stream, "q_centroids", k_centroids, cdiv((uint64_t)nq * 8, 256), 256, q.scan_in, (const uint32_t *)q.qk_b.p, (const uint32_t *)q.qv_b.p,
+               (const uint32_t *)q.run_begin.p, (const uint32_t *)q.d_nvox.p, q.cent.p, q.ukeys.p, q.hkey.p, q.hval.p, q.hbits);
+        LAUNCH(h, h->stream, "q_nn", k_query_nn, cdiv((uint64_t)nq * NN_SUB, 256), 256, q.scan_in, (const uint32_t *)q.qv_b.p, (const uint32_t *)q.run_begin.p,
+               (const uint32_t *)q.ukeys.p, (const float4 *)q.cent.p, (const uint32_t *)q.d_nvox.p, (const VoxGrid *)q.qgrid.p, to_xf(I),
+               h->dp, q.d_qctr.p, q.query.p, q.qkey.p, (const uint32_t *)q.hkey.p, (const uint32_t *)q.hval.p, q.hbits);
         HIPC(h, hipStreamSynchronize(h->stream));
     }
     Counters c;
-    HIPC(h, hipMemcpy(&c, Q(h).d_qctr.p, sizeof(c), hipMemcpyDeviceToHost));
+    HIPC(h, hipMemcpy(&c, q.d_qctr.p, sizeof(c), hipMemcpyDeviceToHost));
     if (c.sort_qoverflow) {
         h->err = "exact-sort segment queue overflow (site " + std::to_string(c.sort_qoverflow) + ")";
         return ERASOR_E_INTERNAL;
@@ -3743,16 +3641,17 @@ int erasor_hip_voxelize_preserving_labels(erasor_hip_handle *h, const float *src
     prof_collect(h);
     const uint32_t ns = (uint32_t)n;
     q_drain(h);
-    int rc = alloc_scan(h, std::max(ns, 1u));
+    QSide &q = h->q[h->qi];
+    int rc = alloc_scan(h, q, std::max(ns, 1u));
     if (rc) return rc;
-    if (ns) HIPC(h, hipMemcpyAsync(Q(h).scan.p, src, (size_t)ns * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+    if (ns) HIPC(h, hipMemcpyAsync(q.scan.p, src, (size_t)ns * sizeof(float4), hipMemcpyHostToDevice, h->stream));
     uint32_t nq = 0;
-    rc = voxelize_device(h, (const float4 *)Q(h).scan.p, ns, leaf_size, &nq);
+    rc = voxelize_device(h, (const float4 *)q.scan.p, ns, leaf_size, &nq);
     if (rc) return rc;
     if (n_out) *n_out = nq;
     if (!dst) return ERASOR_OK;
     if (nq > cap) return ERASOR_E_CAPACITY;
-    if (nq) HIPC(h, hipMemcpy(dst, Q(h).query.p, (size_t)nq * sizeof(float4), hipMemcpyDeviceToHost));
+    if (nq) HIPC(h, hipMemcpy(dst, q.query.p, (size_t)nq * sizeof(float4), hipMemcpyDeviceToHost));
     return ERASOR_OK;
 }
 
@@ -3802,18 +3701,19 @@ int erasor_hip_mapgen_accum(erasor_hip_handle *h, const float *scan_xyzi, size_t
     prof_collect(h);
     const uint32_t ns = (uint32_t)n;
     q_drain(h);
-    int rc = alloc_scan(h, std::max(ns, 1u));
+    QSide &q = h->q[h->qi];
+    int rc = alloc_scan(h, q, std::max(ns, 1u));
     if (rc) return rc;
     if (ensure(h, h->mg_tmp, (size_t)ns + 8)) return ERASOR_E_NO_DEVICE;
     static const float L2O[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 1.73f, 0, 0, 0, 1};  // mapgen.hpp:212-215
     uint32_t n_kept = 0;
     if (ns) {
-        HIPC(h, hipMemcpyAsync(Q(h).scan.p, scan_xyzi, (size_t)ns * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+        HIPC(h, hipMemcpyAsync(q.scan.p, scan_xyzi, (size_t)ns * sizeof(float4), hipMemcpyHostToDevice, h->stream));
         const float max_dist_square = (float)pow(2.7, 2);  // CAR_BODY_SIZE, mapgen.hpp:8,221
-        LAUNCH(h, "mapgen", k_mapgen_flag, cdiv(ns, 256), 256, (const float4 *)Q(h).scan.p, ns, max_dist_square, Q(h).qflag.p);
-        scan_u32(h, Q(h).qflag.p, Q(h).qpl.p, Q(h).qtops.p, ns, ns, nullptr, h->dn.p, "mapgen");
-        LAUNCH(h, "mapgen", k_mapgen_scatter, cdiv(ns, 256), 256, (const float4 *)Q(h).scan.p, ns, (const uint32_t *)Q(h).qflag.p,
-               (const uint32_t *)Q(h).qpl.p, (const uint32_t *)Q(h).qtops.p, to_xf(T_lidar2origin ? T_lidar2origin : L2O), to_xf(T_pose), h->mg_tmp.p);
+        LAUNCH(h, h->stream, "mapgen", k_mapgen_flag, cdiv(ns, 256), 256, (const float4 *)q.scan.p, ns, max_dist_square, q.qflag.p);
+        scan_u32(h, h->stream, q.qflag.p, q.qpl.p, q.qtops.p, ns, ns, nullptr, h->dn.p, "mapgen");
+        LAUNCH(h, h->stream, "mapgen", k_mapgen_scatter, cdiv(ns, 256), 256, (const float4 *)q.scan.p, ns, (const uint32_t *)q.qflag.p,
+               (const uint32_t *)q.qpl.p, (const uint32_t *)q.qtops.p, to_xf(T_lidar2origin ? T_lidar2origin : L2O), to_xf(T_pose), h->mg_tmp.p);
         HIPC(h, hipMemcpyAsync(&n_kept, h->dn.p, 4, hipMemcpyDeviceToHost, h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
     }
@@ -3821,22 +3721,22 @@ int erasor_hip_mapgen_accum(erasor_hip_handle *h, const float *scan_xyzi, size_t
     rc = voxelize_device(h, (const float4 *)h->mg_tmp.p, n_kept, 0.2, &nq);  // cloud_curr (mapgen.hpp:239: fixed 0.2 m leaf)
     if (rc) return rc;
     h->mg_ncurr = 0;
-    rc = mg_append(h, h->mg_curr, h->mg_ncurr, (const float4 *)Q(h).query.p, nq);
+    rc = mg_append(h, h->mg_curr, h->mg_ncurr, (const float4 *)q.query.p, nq);
     if (rc) return rc;
     if (h->mg_initial) {  // :241-243
         h->mg_nmap = 0;
-        rc = mg_append(h, h->mg_map, h->mg_nmap, (const float4 *)Q(h).query.p, nq);
+        rc = mg_append(h, h->mg_map, h->mg_nmap, (const float4 *)q.query.p, nq);
         if (rc) return rc;
         h->mg_initial = false;
     } else {  // :244-256
-        rc = mg_append(h, h->mg_map, h->mg_nmap, (const float4 *)Q(h).query.p, nq);
+        rc = mg_append(h, h->mg_map, h->mg_nmap, (const float4 *)q.query.p, nq);
         if (rc) return rc;
         if (h->mg_large && (h->mg_cnt_voxel++ % 500 == 0)) {
             HIPC(h, hipStreamSynchronize(h->stream));
             uint32_t nv = 0;
             rc = voxelize_device(h, (const float4 *)h->mg_map.p, (uint32_t)h->mg_nmap, h->mg_leaf, &nv);
             if (rc) return rc;
-            rc = mg_append(h, h->mg_done, h->mg_ndone, (const float4 *)Q(h).query.p, nv);  // cloud_maps.push_back
+            rc = mg_append(h, h->mg_done, h->mg_ndone, (const float4 *)q.query.p, nv);  // cloud_maps.push_back
             if (rc) return rc;
             h->mg_nmap = 0;  // cloud_map.clear()
         }
@@ -3887,7 +3787,7 @@ int erasor_hip_mapgen_save(erasor_hip_handle *h, float *dst, size_t cap, size_t 
         if (n_out) *n_out = nq;
         if (dst) {
             if (nq > cap) rc = ERASOR_E_CAPACITY;
-            else if (nq && hipMemcpy(dst, Q(h).query.p, (size_t)nq * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) rc = ERASOR_E_NO_DEVICE;
+            else if (nq && hipMemcpy(dst, h->q[h->qi].query.p, (size_t)nq * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) rc = ERASOR_E_NO_DEVICE;
         }
     }
     (void)hipStreamSynchronize(h->stream);
@@ -4096,15 +3996,16 @@ int erasor_hip_exact_sort_u32(erasor_hip_handle *h, uint32_t *keys, uint32_t *va
     h->have_step = false;  // borrows the last step's query side
     const uint32_t ns = (uint32_t)n;
     q_drain(h);
-    int rc = alloc_scan(h, std::max(ns, 1u));
+    QSide &q = h->q[h->qi];
+    int rc = alloc_scan(h, q, std::max(ns, 1u));
     if (rc) return rc;
-    LAUNCH(h, "q_begin", k_query_begin, 1, 256, Q(h).d_qctr.p, Q(h).bb.p, (uint32_t *)nullptr, 0u, Q(h).d_nvox.p, 0u);
+    LAUNCH(h, h->stream, "q_begin", k_query_begin, 1, 256, q.d_qctr.p, q.bb.p, (uint32_t *)nullptr, 0u, q.d_nvox.p, 0u);
     if (ns) {
-        HIPC(h, hipMemcpyAsync(Q(h).qk_a.p, keys, (size_t)ns * 4, hipMemcpyHostToDevice, h->stream));
-        HIPC(h, hipMemcpyAsync(Q(h).qv_a.p, vals, (size_t)ns * 4, hipMemcpyHostToDevice, h->stream));
+        HIPC(h, hipMemcpyAsync(q.qk_a.p, keys, (size_t)ns * 4, hipMemcpyHostToDevice, h->stream));
+        HIPC(h, hipMemcpyAsync(q.qv_a.p, vals, (size_t)ns * 4, hipMemcpyHostToDevice, h->stream));
     }
-    Counters *dc = Q(h).d_qctr.p;
-    run_exact_sort(h, ns);
+    Counters *dc = q.d_qctr.p;
+    run_exact_sort(h, h->stream, q, ns);
     HIPC(h, hipStreamSynchronize(h->stream));
     Counters c;
     HIPC(h, hipMemcpy(&c, dc, sizeof(c), hipMemcpyDeviceToHost));
@@ -4125,8 +4026,8 @@ int erasor_hip_exact_sort_u32(erasor_hip_handle *h, uint32_t *keys, uint32_t *va
         (void)hipMemcpy(h->dbg_stamps.p, t, sizeof(t), hipMemcpyHostToDevice);
     }
     if (ns) {
-        HIPC(h, hipMemcpy(keys, Q(h).qk_b.p, (size_t)ns * 4, hipMemcpyDeviceToHost));
-        HIPC(h, hipMemcpy(vals, Q(h).qv_b.p, (size_t)ns * 4, hipMemcpyDeviceToHost));
+        HIPC(h, hipMemcpy(keys, q.qk_b.p, (size_t)ns * 4, hipMemcpyDeviceToHost));
+        HIPC(h, hipMemcpy(vals, q.qv_b.p, (size_t)ns * 4, hipMemcpyDeviceToHost));
     }
     return ERASOR_OK;
 }
@@ -4140,21 +4041,22 @@ int erasor_hip_exact_sort_u32(erasor_hip_handle *h, uint32_t *keys, uint32_t *va
 int erasor_hip_debug_sort_queues(erasor_hip_handle *h, uint32_t *state, int32_t *smallq, int32_t *q0, int32_t *q1, int32_t *q2, size_t cap) {
     NOFLY(h);
     if (!h || !state) return ERASOR_E_INVALID;
-    if (!Q(h).esqs.p || !Q(h).wstate.p) return ERASOR_E_STATE;
+    const QSide &q = h->q[h->qi];
+    if (!q.esqs.p || !q.wstate.p) return ERASOR_E_STATE;
     HIPC(h, hipSetDevice(h->device));
     HIPC(h, hipStreamSynchronize(h->stream));
     EsQueues qs;
     WideState ws;
     Counters c;
-    HIPC(h, hipMemcpy(&qs, Q(h).esqs.p, sizeof(qs), hipMemcpyDeviceToHost));
-    HIPC(h, hipMemcpy(&ws, Q(h).wstate.p, sizeof(ws), hipMemcpyDeviceToHost));
-    HIPC(h, hipMemcpy(&c, Q(h).d_qctr.p, sizeof(c), hipMemcpyDeviceToHost));
+    HIPC(h, hipMemcpy(&qs, q.esqs.p, sizeof(qs), hipMemcpyDeviceToHost));
+    HIPC(h, hipMemcpy(&ws, q.wstate.p, sizeof(ws), hipMemcpyDeviceToHost));
+    HIPC(h, hipMemcpy(&c, q.d_qctr.p, sizeof(c), hipMemcpyDeviceToHost));
     static_assert(sizeof(esort::Seg) == 12, "a record is three words");
     const uint32_t st[18] = {qs.cnt[0], qs.cnt[1], qs.cnt[2], qs.small_cnt, ws.nseg[0], ws.nseg[1], ws.ntiles[0], ws.ntiles[1], h->dbg_sort[0],
                              h->dbg_sort[1], h->dbg_sort[2], h->dbg_sort[3], h->dbg_sort[4], c.n_sort_fallback, c.n_voxel_overflow, c.sort_qoverflow,
                              c.err, std::max(1u, cdiv(h->dbg_sort[0], 1024))};
     memcpy(state, st, sizeof(st));
-    const esort::Seg *src[4] = {Q(h).essmall.p, Q(h).esq0.p, Q(h).esq1.p, Q(h).esq2.p};
+    const esort::Seg *src[4] = {q.essmall.p, q.esq0.p, q.esq1.p, q.esq2.p};
     int32_t *dst[4] = {smallq, q0, q1, q2};
     const uint32_t cnt[4] = {qs.small_cnt, qs.cnt[0], qs.cnt[1], qs.cnt[2]};
     for (int i = 0; i < 4; ++i) {
@@ -4225,11 +4127,12 @@ int erasor_hip_radix_sort_u32(erasor_hip_handle *h, const uint32_t *keys, size_t
     h->have_step = false;  // borrows the last step's query side
     const uint32_t ns = (uint32_t)n;
     q_drain(h);
-    int rc = alloc_scan(h, std::max(ns, 1u));
+    QSide &q = h->q[h->qi];
+    int rc = alloc_scan(h, q, std::max(ns, 1u));
     if (rc) return rc;
-    if (ns) HIPC(h, hipMemcpyAsync(Q(h).qkey.p, keys, (size_t)ns * 4, hipMemcpyHostToDevice, h->stream));
+    if (ns) HIPC(h, hipMemcpyAsync(q.qkey.p, keys, (size_t)ns * 4, hipMemcpyHostToDevice, h->stream));
     const uint32_t *sk = nullptr, *sp = nullptr;
-    rc = radix_sort(h, Q(h).qkey.p, ns, nullptr, bits, Q(h).qk_a.p, Q(h).qposL.p, Q(h).qv_a.p, Q(h).qposR.p, &sk, &sp, "radix_test");
+    rc = radix_sort(h, h->stream, 0, q.qkey.p, ns, nullptr, bits, q.qk_a.p, q.qposL.p, q.qv_a.p, q.qposR.p, &sk, &sp, "radix_test");
     if (rc) return rc;
     HIPC(h, hipStreamSynchronize(h->stream));
     if (ns) {

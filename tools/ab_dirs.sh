@@ -1,6 +1,6 @@
 #!/bin/bash
 # several builds side by side on ONE box (each a directory with bench.py + erasor_amd/ like _ab_old/): the driver's statistic and 100-step
-# passes, the directories in rotation, twice.   tools/ab_dirs.sh <dir> <dir> ...   (AB_WORKLOADS as in tools/ab_old_new.sh)
+# passes, the directories in rotation, AB_REPS times (default 2).   tools/ab_dirs.sh <dir> <dir> ...   (AB_WORKLOADS as in tools/ab_old_new.sh)
 # A run that fails or runs out of time ends the whole call: nothing more is started on a device that may have faulted.
 set -o pipefail
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -11,6 +11,6 @@ import json,sys; d=json.loads(sys.stdin.read().strip().split(chr(10))[-1]); prin
 for wl in ${AB_WORKLOADS:-"--workload=seq05" "--workload=large_scale_05"}; do
   for cfg in "--steps 20 --warmup 5 --repeats 7" "--steps 100 --warmup 5 --repeats 5"; do
     echo "== $wl $cfg"
-    for rep in 1 2; do for d in "$@"; do run $d "$wl $cfg" || { echo "run failed ($d $wl $cfg): stopping"; exit 1; }; done; done
+    for rep in $(seq ${AB_REPS:-2}); do for d in "$@"; do run $d "$wl $cfg" || { echo "run failed ($d $wl $cfg): stopping"; exit 1; }; done; done
   done
 done
