@@ -78,6 +78,16 @@ class AlignRow(C.Structure):
         return d
 
 
+class ScanLabelRow(C.Structure):
+    """erasor_scan_label_row (include/erasor_hip.h): one frame of label_scans, or their sum"""
+    _fields_ = [("n_points", C.c_uint64), ("n_non_finite", C.c_uint64), ("n_label_out_of_range", C.c_uint64), ("n", (C.c_uint64 * 3) * 2)]
+
+    def as_dict(self):
+        """evalmap.label_scans' row keys"""
+        return {"n_points": int(self.n_points), "n_non_finite": int(self.n_non_finite), "n_label_out_of_range": int(self.n_label_out_of_range),
+                "n": [[int(self.n[g][k]) for k in range(3)] for g in range(2)]}
+
+
 class LabelResult(C.Structure):
     """erasor_label_result (include/erasor_hip.h): label_map of a map without labels (fill_removert_intensity.cpp:24-59)"""
     _fields_ = [("n_src", C.c_uint64), ("n_out", C.c_uint64), ("n_tied", C.c_uint64), ("passthrough", C.c_uint32)]
@@ -257,7 +267,7 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "render.hip.h", "revert_bins.hip.h",
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "label_scans.hip.h", "render.hip.h", "revert_bins.hip.h",
                                                  "exact_sort.hip.h", "exact_sort_core.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
@@ -809,6 +819,53 @@ class Erasor:
             m = self._eval_cloud(map, kept)
             self._check(lib().erasor_hip_align_frames_clouds(self._h, *m, *tail))
         return [rows[f].as_dict() for f in range(n_f)], summ.as_dict()
+
+    # -- every scan's points labelled static or moving from a cleaned map (on the host: evalmap.label_scans) --
+    def label_scans(self, scans, T_body2origin, T_lidar2body=None, static_map=None, raw_map=None, tau=None, voxelsize=0.2, split=None):
+        """Every point of every scan classified against the cleaned map `static_map` (a cloud as for evaluate; None: the handle's current
+        map) and, optionally, the raw map `raw_map`, all frames in one call (erasor_hip_label_scans_clouds / _map): 0 static (a static-map
+        point within tau), 1 dynamic, 2 unknown (a raw map was given and has no point within tau either), 255 dropped.  scans and poses as
+        for align_frames; tau: voxelsize * np.sqrt(3) / 2 when None.  Returns (codes, rows, summary) as evalmap.label_scans does; with
+        split = 0, 1 or 2 also the rows of that code, as given, one (k, 4) array per frame."""
+        from . import evalmap
+        kept = []
+        if isinstance(scans, tuple):
+            ptr, offsets = scans
+            offs = np.ascontiguousarray(offsets, np.uint64)
+            q = (C.c_void_p(ptr), C.c_size_t(int(offs[-1]) if len(offs) else 0), 1)
+        else:
+            a = [_f32(s).reshape(-1, 4) for s in scans]
+            offs = np.zeros(len(a) + 1, np.uint64)
+            offs[1:] = np.cumsum([len(s) for s in a], dtype=np.uint64)
+            cat = _f32(np.concatenate(a) if a else np.zeros((0, 4), np.float32))
+            kept.append(cat)
+            q = (_p(cat), C.c_size_t(len(cat)), 0)
+        n_f, n_pts = len(offs) - 1, int(q[1].value)
+        Tb = _f32(np.asarray(T_body2origin, np.float32).reshape(n_f, 16) if n_f else np.zeros((1, 16), np.float32))
+        if T_lidar2body is not None:
+            kept.append(_f32(T_lidar2body).reshape(16))
+        Tl = None if T_lidar2body is None else _p(kept[-1])
+        tau = evalmap.label_tau(voxelsize) if tau is None else float(tau)
+        raw = (None, C.c_size_t(0), 0) if raw_map is None else self._eval_cloud(raw_map, kept)
+        codes = np.zeros(max(n_pts, 1), np.uint8)
+        out = np.empty((max(n_pts, 1), 4), np.float32) if split is not None else None
+        out_offs = np.zeros(n_f + 1, np.uint64)
+        rows = (ScanLabelRow * max(n_f, 1))()
+        summ = ScanLabelRow()
+        tail = (*raw, C.c_int(int(raw_map is not None)), q[0], q[1], _p(offs), C.c_size_t(n_f), C.c_int(q[2]), Tl, _p(Tb), C.c_double(tau), _p(codes),
+                C.c_int(0 if split is None else int(split)), None if split is None else _p(out), C.c_size_t(0 if split is None else len(out)),
+                None if split is None else _p(out_offs), rows, C.byref(summ))
+        if static_map is None:
+            self._check(lib().erasor_hip_label_scans_map(self._h, *tail))
+        else:
+            m = self._eval_cloud(static_map, kept)
+            self._check(lib().erasor_hip_label_scans_clouds(self._h, *m, *tail))
+        o = offs.astype(np.int64)
+        res = ([codes[o[f]:o[f + 1]].copy() for f in range(n_f)], [rows[f].as_dict() for f in range(n_f)], summ.as_dict())
+        if split is None:
+            return res
+        oo = out_offs.astype(np.int64)
+        return res + ([out[oo[f]:oo[f + 1]].copy() for f in range(n_f)],)
 
     # -- maps without labels (fill_removert_intensity.cpp:24-59, compare_complement.cpp:43-75; on the host: evalmap.label_from /
     # evalmap.static_complement) --

@@ -1,8 +1,8 @@
-// The offline analyses' host code: PR / RR evaluation (one estimate, many, by class), the overlap report, the frame check, label_map and
-// static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip at its end -- one
-// translation unit, like the kernel headers -- so it sees the handle, ensure / LAUNCH / HIPC, scan_u32, radix_sort, map_to_device and
-// voxelize_device from there; nothing of the step path depends on this file.  Kernels: evaluate.hip.h, nearest.hip.h, align.hip.h,
-// render.hip.h.
+// The offline analyses' host code: PR / RR evaluation (one estimate, many, by class), the overlap report, the frame check, the scans'
+// labels, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
+// at its end -- one translation unit, like the kernel headers -- so it sees the handle, ensure / LAUNCH / HIPC, scan_u32, radix_sort,
+// map_to_device and voxelize_device from there; nothing of the step path depends on this file.  Kernels: evaluate.hip.h, nearest.hip.h,
+// align.hip.h, label_scans.hip.h, render.hip.h.
 #pragma once
 
 extern "C" {
@@ -591,7 +591,7 @@ int erasor_hip_overlap_map(erasor_hip_handle *h, const void *gt_xyzi, size_t n_g
 
 // the arguments both entry points check: ERASOR_E_INVALID with h->err set, else ERASOR_OK and the scans' point count in *n_scan
 static int al_check_args(erasor_hip_handle *h, const char *who, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets,
-                         size_t n_frames, const float *T_lidar2body, const float *T_body2origin, double voxelsize, erasor_align_row *rows) {
+                         size_t n_frames, const float *T_lidar2body, const float *T_body2origin, double voxelsize, const void *rows) {
     if (!(voxelsize > 0) || !std::isfinite(voxelsize)) return invalid(h, who, "voxelsize must be a finite number > 0");
     if (n_frames > 65536) return invalid(h, who, "more than 65536 frames");
     if (!offsets) return invalid(h, who, "offsets is NULL (n_frames + 1 entries)");
@@ -602,6 +602,34 @@ static int al_check_args(erasor_hip_handle *h, const char *who, const void *scan
     if (!all_finite(T_body2origin, n_frames * 16)) return invalid(h, who, "non-finite entry in T_body2origin");
     return ERASOR_OK;
 }
+
+// the frames of one call on the device (align_frames, label_scans), for k_al_query's frame lookup: the offsets (< 2^30) in E.al_off, the
+// frame of every query workgroup's first point (the last frame after the last) in E.al_wg, the poses in E.al_xf.  The host copies live in
+// the caller's AlFrames until its next synchronisation.
+struct AlFrames {
+    std::vector<uint32_t> off, wg;
+    std::vector<Xf> xf;
+};
+static int al_put_frames(erasor_hip_handle *h, uint32_t n, const uint64_t *offsets, uint32_t n_frames, const float *T_body2origin, AlFrames &F) {
+    auto &E = h->ev;
+    const uint32_t grid = cdiv(n, NN_QBLOCK), nf = std::max(n_frames, 1u);
+    if (ensure(h, E.al_off, (size_t)nf + 1) || ensure(h, E.al_wg, (size_t)grid + 1) || ensure(h, E.al_xf, nf)) return ERASOR_E_NO_DEVICE;
+    F.off.resize(n_frames + 1);
+    F.wg.resize(grid + 1);
+    F.xf.resize(nf);
+    for (uint32_t f = 0; f <= n_frames; ++f) F.off[f] = (uint32_t)offsets[f];
+    for (uint32_t b = 0, f = 0; b < grid; ++b) {  // the largest f < n_frames with off[f] <= b * NN_QBLOCK
+        while (f + 1 < n_frames && F.off[f + 1] <= b * NN_QBLOCK) ++f;
+        F.wg[b] = f;
+    }
+    F.wg[grid] = n_frames ? n_frames - 1 : 0;
+    for (uint32_t f = 0; f < n_frames; ++f) F.xf[f] = to_xf(T_body2origin + 16 * (size_t)f);
+    HIPC(h, hipMemcpyAsync(E.al_off.p, F.off.data(), F.off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(E.al_wg.p, F.wg.data(), F.wg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(E.al_xf.p, F.xf.data(), nf * sizeof(Xf), hipMemcpyHostToDevice, h->stream));
+    return ERASOR_OK;
+}
+static const float AL_IDENTITY[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
 static int al_run(erasor_hip_handle *h, const char *who, const float4 *map, uint32_t n_map, const float4 *scans, uint32_t n, const uint64_t *offsets,
                   uint32_t n_frames, const float *T_lidar2body, const float *T_body2origin, double voxelsize, erasor_align_row *rows,
@@ -616,31 +644,19 @@ static int al_run(erasor_hip_handle *h, const char *who, const float4 *map, uint
     if (rc) return rc;
     const uint32_t grid = cdiv(n, NN_QBLOCK), nf = std::max(n_frames, 1u);
     if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256) || ensure(h, E.nn_dbits, (size_t)n + 1) ||
-        ensure(h, E.al_off, (size_t)nf + 1) || ensure(h, E.al_wg, (size_t)grid + 1) || ensure(h, E.al_xf, nf) ||
         ensure(h, E.al_ctr, (size_t)nf * AL_NCTR) || ensure(h, E.al_rank, nf) || ensure(h, E.al_val, (size_t)nf * OV_SEL_MAX))
         return ERASOR_E_NO_DEVICE;
     HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
     if (n_map && (rc = nn_tree(h, map, n_map, P, who, "map point(s)"))) return rc;
-    // the frames: offsets (< 2^30), the frame of every query workgroup's first point (the last frame after the last), the poses
-    std::vector<uint32_t> off(n_frames + 1), wg(grid + 1);
-    for (uint32_t f = 0; f <= n_frames; ++f) off[f] = (uint32_t)offsets[f];
-    for (uint32_t b = 0, f = 0; b < grid; ++b) {  // the largest f < n_frames with off[f] <= b * NN_QBLOCK
-        while (f + 1 < n_frames && off[f + 1] <= b * NN_QBLOCK) ++f;
-        wg[b] = f;
-    }
-    wg[grid] = n_frames ? n_frames - 1 : 0;
-    static const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    std::vector<Xf> xf(nf);
-    for (uint32_t f = 0; f < n_frames; ++f) xf[f] = to_xf(T_body2origin + 16 * (size_t)f);
-    HIPC(h, hipMemcpyAsync(E.al_off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIPC(h, hipMemcpyAsync(E.al_wg.p, wg.data(), wg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIPC(h, hipMemcpyAsync(E.al_xf.p, xf.data(), nf * sizeof(Xf), hipMemcpyHostToDevice, h->stream));
+    AlFrames F;
+    if ((rc = al_put_frames(h, n, offsets, n_frames, T_body2origin, F))) return rc;
+    const std::vector<uint32_t> &off = F.off;
     HIPC(h, hipMemsetAsync(E.al_ctr.p, 0, (size_t)nf * AL_NCTR * sizeof(unsigned long long), h->stream));
     // the thresholds as overlap_report forms them: half = 0.5 * voxelsize, one = voxelsize, 2 * one
     const double half = 0.5 * voxelsize, one = voxelsize, two = 2 * one;
     if (n)
         LAUNCH(h, h->stream, "al_query", k_al_query, grid, NN_QBLOCK, scans, n, (const uint32_t *)E.al_off.p, (const uint32_t *)E.al_wg.p,
-               to_xf(T_lidar2body ? T_lidar2body : I), (const Xf *)E.al_xf.p, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, n_map,
+               to_xf(T_lidar2body ? T_lidar2body : AL_IDENTITY), (const Xf *)E.al_xf.p, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, n_map,
                (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, half, one, two, E.nn_dbits.p, E.al_ctr.p);
     std::vector<unsigned long long> c((size_t)nf * AL_NCTR);
     HIPC(h, hipMemcpyAsync(c.data(), E.al_ctr.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
@@ -721,6 +737,184 @@ int erasor_hip_align_frames_map(erasor_hip_handle *h, const void *scans_xyzi, si
     uint32_t n_map = 0;
     if ((rc = map_on_device(h, who, h->ev.map, &m, &n_map)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q))) return rc;
     return al_run(h, who, m, n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, voxelsize, rows, summary);
+}
+
+// ---- every scan's points labelled static / dynamic / unknown from a cleaned map (kernels: label_scans.hip.h) ----
+// Like al_run: the main stream, the evaluator's scratch, the trees' sorts in bank 2.  One tree is resident at a time: the static map's,
+// then -- for the points the static pass left -- the raw map's in the same scratch; a host raw map is brought in only then, into the
+// buffer the static map's copy no longer needs (the tree holds its own sorted copy).  Round trips: the counters after each pass.
+
+// T2: the largest double whose correctly rounded sqrt is < tau (tau finite, > 0), by steps of one ulp from tau * tau
+static double ls_bound(double tau) {
+    const double inf = std::numeric_limits<double>::infinity();
+    double x = tau * tau;
+    while (x > 0 && !(sqrt(x) < tau)) x = std::nextafter(x, 0.0);
+    for (;;) {
+        const double y = std::nextafter(x, inf);
+        if (!(y < inf) || !(sqrt(y) < tau)) break;
+        x = y;
+    }
+    return x;
+}
+
+// what a call's split arguments ask for
+struct LsSplit {
+    int code = 0;
+    float *xyzi = nullptr;
+    size_t cap = 0;
+    uint64_t *offsets = nullptr;
+    bool wanted() const { return xyzi || offsets; }
+};
+
+static int ls_check_args(erasor_hip_handle *h, const char *who, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                         const float *T_lidar2body, const float *T_body2origin, double tau, const void *raw_xyzi, size_t n_raw, int have_raw,
+                         const LsSplit &sp, const erasor_scan_label_row *rows) {
+    if (!(tau > 0) || !std::isfinite(tau)) return invalid(h, who, "tau must be a finite number > 0");
+    if (sp.wanted() && (sp.code < 0 || sp.code > 2)) return invalid(h, who, "split_code must be 0 (static), 1 (dynamic) or 2 (unknown)");
+    if (sp.wanted() && sp.code == 2 && !have_raw) return invalid(h, who, "split_code 2 (unknown) needs a raw map");
+    int rc = al_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, 1.0, rows);
+    if (rc) return rc;
+    return have_raw ? check_cloud(h, who, "NULL raw map or more than 2^30 raw map points", raw_xyzi, n_raw) : ERASOR_OK;
+}
+
+// the launch of one pass (list == nullptr: all n points; else the n_list left points)
+static int ls_pass(erasor_hip_handle *h, const float4 *scans, uint32_t n, const uint32_t *list, uint32_t n_list, uint32_t n_frames, const Xf &Tl,
+                   uint32_t n_map, uint32_t P, double T2, uint32_t code_hit, uint32_t code_miss, uint32_t count_miss, uint32_t *left) {
+    auto &E = h->ev;
+    const uint32_t m = list ? n_list : n;
+    if (!m) return ERASOR_OK;
+    LAUNCH(h, h->stream, "ls_query", k_ls_query, cdiv(m, NN_QBLOCK), NN_QBLOCK, scans, n, list, n_list, (const uint32_t *)E.al_off.p, n_frames,
+           (const uint32_t *)E.al_wg.p, Tl, (const Xf *)E.al_xf.p, (const float4 *)E.nn_pts.p, n_map, (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P,
+           T2, code_hit, code_miss, count_miss, E.code.p, left, E.al_ctr.p);
+    return ERASOR_OK;
+}
+
+static int ls_run(erasor_hip_handle *h, const char *who, const float4 *smap, uint32_t n_smap, const void *raw_xyzi, uint32_t n_raw, int raw_is_device,
+                  int have_raw, const float4 *scans, uint32_t n, const uint64_t *offsets, uint32_t n_frames, const float *T_lidar2body,
+                  const float *T_body2origin, double tau, uint8_t *codes, const LsSplit &sp, erasor_scan_label_row *rows,
+                  erasor_scan_label_row *summary) {
+    auto &E = h->ev;
+    const double T2 = ls_bound(tau);
+    uint32_t P = 1;
+    int rc = nn_pad(h, n_smap, &P, who, "static map");
+    if (rc) return rc;
+    const uint32_t nf = std::max(n_frames, 1u);
+    const bool scan = have_raw || sp.wanted();
+    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.al_ctr, (size_t)nf * LS_NCTR) || ensure(h, E.code, (size_t)n + 1) ||
+        (scan && (ensure(h, E.fm_flag, (size_t)n + 1) || ensure(h, E.fm_pl, (size_t)n + 1) || ensure(h, E.fm_tops, n / 1024 + 4))) ||
+        (have_raw && ensure(h, E.nn_near, (size_t)n + 1)) || (sp.xyzi && ensure(h, E.fm_out, (size_t)n + 1)))
+        return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if (n_smap && (rc = nn_tree(h, smap, n_smap, P, who, "static map point(s)"))) return rc;
+    AlFrames F;
+    if ((rc = al_put_frames(h, n, offsets, n_frames, T_body2origin, F))) return rc;
+    const std::vector<uint32_t> &off = F.off;
+    const Xf Tl = to_xf(T_lidar2body ? T_lidar2body : AL_IDENTITY);
+    HIPC(h, hipMemsetAsync(E.al_ctr.p, 0, (size_t)nf * LS_NCTR * sizeof(unsigned long long), h->stream));
+    // the static pass: code 0, or 1 for now
+    if ((rc = ls_pass(h, scans, n, nullptr, 0, n_frames, Tl, n_smap, P, T2, LS_STATIC, LS_DYNAMIC, have_raw ? 0u : 1u,
+                      have_raw ? E.fm_flag.p : (uint32_t *)nullptr)))
+        return rc;
+    std::vector<unsigned long long> c((size_t)nf * LS_NCTR, 0ull);
+    if (have_raw) {
+        // the points it left (kept and not static: nothing counted them yet), as an ascending list of their indices; then the raw map's
+        // tree where the static map's was (built even when nothing is left: a bad raw map is refused whatever the scans hold), and the
+        // raw pass over the list: code 1 stays, or 2
+        HIPC(h, hipMemcpyAsync(c.data(), E.al_ctr.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
+        uint64_t decided = 0;
+        for (uint32_t f = 0; f < n_frames; ++f)
+            decided += c[(size_t)f * LS_NCTR + LS_STATIC] + c[(size_t)f * LS_NCTR + 3 + LS_STATIC] + c[(size_t)f * LS_NCTR + LS_NON_FINITE];
+        const uint32_t n_left = n - (uint32_t)decided;
+        if (n_left) {
+            scan_u32(h, h->stream, E.fm_flag.p, E.fm_pl.p, E.fm_tops.p, n, n, nullptr, nullptr, "ls_left");
+            LAUNCH(h, h->stream, "ls_left", k_ls_list, cdiv(n, 256), 256, n, (const uint32_t *)E.fm_flag.p, (const uint32_t *)E.fm_pl.p,
+                   (const uint32_t *)E.fm_tops.p, E.nn_near.p);
+        }
+        const float4 *rmap = nullptr;
+        uint32_t Pr = 1;
+        if ((rc = ev_input(h, raw_xyzi, n_raw, raw_is_device, E.gt, &rmap)) || (rc = nn_pad(h, n_raw, &Pr, who, "raw map"))) return rc;
+        HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+        if (n_raw && (rc = nn_tree(h, rmap, n_raw, Pr, who, "raw map point(s)"))) return rc;
+        if ((rc = ls_pass(h, scans, n, E.nn_near.p, n_left, n_frames, Tl, n_raw, Pr, T2, LS_DYNAMIC, LS_UNKNOWN, 1u, nullptr))) return rc;
+    }
+    HIPC(h, hipMemcpyAsync(c.data(), E.al_ctr.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    erasor_scan_label_row sum;
+    memset(&sum, 0, sizeof(sum));
+    uint64_t out_n = 0;
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const unsigned long long *cf = &c[(size_t)f * LS_NCTR];
+        erasor_scan_label_row r;
+        memset(&r, 0, sizeof(r));
+        r.n_points = off[f + 1] - off[f];
+        r.n_non_finite = cf[LS_NON_FINITE];
+        r.n_label_out_of_range = cf[LS_LABEL_OOR];
+        for (int g = 0; g < 2; ++g)
+            for (int k = 0; k < 3; ++k) {
+                r.n[g][k] = cf[g * 3 + k];
+                sum.n[g][k] += r.n[g][k];
+            }
+        sum.n_points += r.n_points;
+        sum.n_non_finite += r.n_non_finite;
+        sum.n_label_out_of_range += r.n_label_out_of_range;
+        rows[f] = r;
+        if (sp.wanted()) {
+            if (sp.offsets) sp.offsets[f] = out_n;
+            out_n += r.n[0][sp.code] + r.n[1][sp.code];
+        }
+    }
+    if (sp.offsets) sp.offsets[n_frames] = out_n;
+    if (summary) *summary = sum;
+    if (codes && n) HIPC(h, hipMemcpy(codes, E.code.p, n, hipMemcpyDeviceToHost));
+    if (!sp.xyzi) return ERASOR_OK;
+    if (out_n > sp.cap) return ERASOR_E_CAPACITY;
+    if (!out_n) return ERASOR_OK;
+    // the rows of the chosen code, as given: a stable compaction over the concatenated scans (frames are consecutive ranges)
+    LAUNCH(h, h->stream, "ls_split", k_ls_flag, cdiv(n, 256), 256, (const uint8_t *)E.code.p, n, (uint32_t)sp.code, E.fm_flag.p);
+    scan_u32(h, h->stream, E.fm_flag.p, E.fm_pl.p, E.fm_tops.p, n, n, nullptr, nullptr, "ls_split");
+    LAUNCH(h, h->stream, "ls_split", k_f_compact, cdiv(n, 256), 256, scans, n, (const uint32_t *)E.fm_flag.p, (const uint32_t *)E.fm_pl.p,
+           (const uint32_t *)E.fm_tops.p, E.fm_out.p);
+    return d2h(h, sp.xyzi, E.fm_out.p, (size_t)out_n * sizeof(float4));
+}
+
+int erasor_hip_label_scans_clouds(erasor_hip_handle *h, const void *static_xyzi, size_t n_static, int static_is_device, const void *raw_xyzi, size_t n_raw,
+                                  int raw_is_device, int have_raw, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                                  int scans_are_device, const float T_lidar2body[16], const float *T_body2origin, double tau, uint8_t *codes,
+                                  int split_code, float *split_xyzi, size_t split_cap, uint64_t *split_offsets, erasor_scan_label_row *rows,
+                                  erasor_scan_label_row *summary) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_label_scans_clouds";
+    LsSplit sp;
+    sp.code = split_code, sp.xyzi = split_xyzi, sp.cap = split_cap, sp.offsets = split_offsets;
+    int rc = ls_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, tau, raw_xyzi, n_raw, have_raw, sp, rows);
+    if (rc || (rc = check_cloud(h, who, "NULL static map or more than 2^30 static map points", static_xyzi, n_static))) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr, *q = nullptr;
+    if ((rc = ev_input(h, static_xyzi, n_static, static_is_device, h->ev.gt, &m)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q)))
+        return rc;
+    return ls_run(h, who, m, (uint32_t)n_static, raw_xyzi, (uint32_t)n_raw, raw_is_device, have_raw, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames,
+                  T_lidar2body, T_body2origin, tau, codes, sp, rows, summary);
+}
+
+int erasor_hip_label_scans_map(erasor_hip_handle *h, const void *raw_xyzi, size_t n_raw, int raw_is_device, int have_raw, const void *scans_xyzi,
+                               size_t n_scan_points, const uint64_t *offsets, size_t n_frames, int scans_are_device, const float T_lidar2body[16],
+                               const float *T_body2origin, double tau, uint8_t *codes, int split_code, float *split_xyzi, size_t split_cap,
+                               uint64_t *split_offsets, erasor_scan_label_row *rows, erasor_scan_label_row *summary) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_label_scans_map";
+    LsSplit sp;
+    sp.code = split_code, sp.xyzi = split_xyzi, sp.cap = split_cap, sp.offsets = split_offsets;
+    int rc = ls_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, tau, raw_xyzi, n_raw, have_raw, sp, rows);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr, *q = nullptr;
+    uint32_t n_map = 0;
+    if ((rc = map_on_device(h, who, h->ev.map, &m, &n_map)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q))) return rc;
+    return ls_run(h, who, m, n_map, raw_xyzi, (uint32_t)n_raw, raw_is_device, have_raw, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body,
+                  T_body2origin, tau, codes, sp, rows, summary);
 }
 
 // ---- label_map (fill_removert_intensity.cpp:24-59, compare_map.cpp:77-110) and calc_complement (compare_complement.cpp:43-75): the
@@ -1334,6 +1528,50 @@ int erasor_hip_debug_nn_effort(erasor_hip_handle *h, const float *tree_xyzi, siz
     }
     if ((rc = d2h(h, dist, E.nn_dbits.p, n_q * sizeof(double)))) return rc;
     return d2h(h, nearest, E.nn_near.p, n_q * sizeof(uint32_t));
+}
+
+// test hook: the labelling's bounded search (k_ls_query's static pass: one frame, identity transforms) of n_q finite queries over the
+// tree of a cloud, built as above: codes[i] = 0 when a tree point lies within tau of query i, else 1, and the search's effort beside it,
+// effort[2 * i] = leaves opened, effort[2 * i + 1] = leaf points tested -- to set against erasor_hip_debug_nn_effort's on the same input.
+int erasor_hip_debug_ls_effort(erasor_hip_handle *h, const float *tree_xyzi, size_t n, const float *query_xyzi, size_t n_q, double tau, uint8_t *codes,
+                               uint32_t *effort) {
+    NOFLY(h);
+    if (!h || !tree_xyzi || !n || n > MAX_POINTS || !query_xyzi || !n_q || n_q > MAX_POINTS || !codes || !effort || !(tau > 0) || !std::isfinite(tau))
+        return ERASOR_E_INVALID;
+    HIPC(h, hipSetDevice(h->device));
+    auto &E = h->ev;
+    const float4 *g = nullptr, *q = nullptr;
+    int rc;
+    if ((rc = ev_input(h, tree_xyzi, n, 0, E.gt, &g)) || (rc = ev_input(h, query_xyzi, n_q, 0, E.est, &q))) return rc;
+    const uint32_t nt = (uint32_t)n, nq = (uint32_t)n_q, grid = cdiv(nq, NN_QBLOCK);
+    uint32_t P = 1;
+    if ((rc = nn_pad(h, nt, &P, "erasor_hip_debug_ls_effort", "cloud"))) return rc;
+    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.al_off, 2) || ensure(h, E.al_wg, (size_t)grid + 1) || ensure(h, E.al_xf, 1) ||
+        ensure(h, E.al_ctr, LS_NCTR) || ensure(h, E.code, n_q + 1))
+        return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if ((rc = nn_tree(h, g, nt, P, "erasor_hip_debug_ls_effort", "point(s)"))) return rc;
+    const uint32_t off[2] = {0, nq};
+    const Xf one = to_xf(AL_IDENTITY);
+    HIPC(h, hipMemcpyAsync(E.al_off.p, off, sizeof(off), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemsetAsync(E.al_wg.p, 0, ((size_t)grid + 1) * sizeof(uint32_t), h->stream));
+    HIPC(h, hipMemcpyAsync(E.al_xf.p, &one, sizeof(Xf), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemsetAsync(E.al_ctr.p, 0, LS_NCTR * sizeof(unsigned long long), h->stream));
+    uint32_t *d_eff = nullptr;
+    HIPC(h, hipMalloc((void **)&d_eff, 2 * n_q * sizeof(uint32_t)));
+    (void)hipMemsetAsync(d_eff, 0xFF, 2 * n_q * sizeof(uint32_t), h->stream);
+    hipLaunchKernelGGL(k_nn_set_effort, dim3(1), dim3(1), 0, h->stream, d_eff);
+    rc = ls_pass(h, q, nq, nullptr, 0, 1, one, nt, P, ls_bound(tau), LS_STATIC, LS_DYNAMIC, 1u, nullptr);
+    hipLaunchKernelGGL(k_nn_set_effort, dim3(1), dim3(1), 0, h->stream, (uint32_t *)nullptr);
+    if (!rc) rc = d2h(h, effort, d_eff, 2 * n_q * sizeof(uint32_t));
+    (void)hipFree(d_eff);
+    unsigned long long c[LS_NCTR];
+    if (rc || (rc = d2h(h, c, E.al_ctr.p, sizeof(c)))) return rc;
+    if (c[LS_NON_FINITE]) {
+        h->err = "erasor_hip_debug_ls_effort: non-finite query";
+        return ERASOR_E_INVALID;
+    }
+    return d2h(h, codes, E.code.p, n_q);
 }
 
 // what ev_run / evm_run left in the evaluator's scratch: the bucket count, the bucket offsets and the scattered points and indices

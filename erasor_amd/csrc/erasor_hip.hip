@@ -37,6 +37,7 @@
 #include "evaluate.hip.h"
 #include "nearest.hip.h"
 #include "align.hip.h"
+#include "label_scans.hip.h"
 #include "render.hip.h"
 
 using namespace ek;

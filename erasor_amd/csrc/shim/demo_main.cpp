@@ -6,9 +6,11 @@
 #include <algorithm>
 #include <array>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <deque>
 #include <fstream>
+#include <limits>
 #include <memory>
 #include <sstream>
 #include <thread>
@@ -889,6 +891,132 @@ static int align_mode(int argc, char **argv) {
     return 0;
 }
 
+// --label-scans <rosparam.yaml> <static.pcd> <raw.pcd|-> <out_dir> [n_frames] [tau]: a cleaned map carried back to the scans
+// (erasor_hip_label_scans_clouds).  The same files and poses as --align (data_dir, init_idx, poses_lidar2body.csv after callback_node's
+// round trip, tf/lidar2body); every scan point is static (a point of <static.pcd> within tau), dynamic, or -- with a raw map -- unknown
+// (neither map has a point within tau).  tau: 0.2 * sqrt(3) / 2, --eval's threshold at its default voxel size.  One line per frame
+// and the summary with the moving-object IoU / precision / recall against the scans' own labels (classes 252..259 moving).  Writes
+// <out_dir>/%06d.label, one little-endian uint32 per point in scan order: static 9, moving 251, unknown and dropped 0 -- the ids
+// SemanticKITTI's moving-object-segmentation benchmark uses for "static", "moving" and "unlabeled", quoted from memory: check them
+// against the benchmark's semantic-kitti-mos.yaml before training on these files --, and <out_dir>/%06d.pcd (binary: every float
+// keeps its bits) with the frame's static points, as given.
+static double ratio_or_nan(uint64_t a, uint64_t b) { return b ? (double)a / (double)b : std::numeric_limits<double>::quiet_NaN(); }
+static int label_scans_mode(int argc, char **argv) {
+    if (argc < 6) return 2;
+    const std::string static_path = argv[3], raw_path = argv[4], out_dir = argv[5];
+    const int max_frames = argc > 6 ? atoi(argv[6]) : 1 << 30;
+    const double tau = argc > 7 ? atof(argv[7]) : (0.2 * std::sqrt(3.0)) / 2.0;
+    const bool have_raw = raw_path != "-";
+    erasor::OfflineMapUpdater::Config cfg;
+    erasor_hip_params_default(&cfg.params);
+    erasor::DriverConfig drv;
+    if (!erasor::load_config_yaml(argv[2], cfg, &drv)) {
+        fprintf(stderr, "cannot read %s\n", argv[2]);
+        return 3;
+    }
+    std::vector<Eigen::Matrix4f> poses;
+    if (!erasor::load_all_poses(drv.data_dir + "/poses_lidar2body.csv", poses)) {
+        fprintf(stderr, "cannot read %s/poses_lidar2body.csv\n", drv.data_dir.c_str());
+        return 3;
+    }
+    std::vector<float> smap, rmap, scans, Tb;
+    if (!load_cloud_xyzi(static_path, smap) || (have_raw && !load_cloud_xyzi(raw_path, rmap))) {
+        fprintf(stderr, "cannot read %s or %s\n", static_path.c_str(), raw_path.c_str());
+        return 3;
+    }
+    std::vector<uint64_t> offsets{0};
+    const int last = std::min((int)poses.size(), drv.init_idx + max_frames);
+    for (int i = drv.init_idx; i < last; ++i) {
+        char name[64];
+        snprintf(name, sizeof(name), "/pcds/%06d.pcd", i);
+        std::vector<float> scan;
+        if (!load_cloud_xyzi(drv.data_dir + name, scan)) {
+            fprintf(stderr, "cannot read %s%s\n", drv.data_dir.c_str(), name);
+            return 3;
+        }
+        scans.insert(scans.end(), scan.begin(), scan.end());
+        offsets.push_back(scans.size() / 4);
+        const Eigen::Matrix4f T = erasor_utils::geoPose2eigen(erasor_utils::eigen2geoPose(poses[i]));  // (callback_node's round trip)
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) Tb.push_back(T(r, c));
+    }
+    geometry_msgs::Pose l2b;
+    l2b.position.x = cfg.lidar2body[0];
+    l2b.position.y = cfg.lidar2body[1];
+    l2b.position.z = cfg.lidar2body[2];
+    l2b.orientation.x = cfg.lidar2body[3];
+    l2b.orientation.y = cfg.lidar2body[4];
+    l2b.orientation.z = cfg.lidar2body[5];
+    l2b.orientation.w = cfg.lidar2body[6];
+    const Eigen::Matrix4f TL = erasor_utils::geoPose2eigen(l2b);  // (OMU.cpp:100)
+    float Tl[16];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) Tl[4 * r + c] = TL(r, c);
+    erasor_params p;
+    erasor_hip_params_default(&p);
+    erasor_hip_handle *h = nullptr;
+    if (erasor_hip_create(&p, 0, &h) != ERASOR_OK) {
+        fprintf(stderr, "erasor_hip_create failed\n");
+        return 1;
+    }
+    const size_t n_frames = offsets.size() - 1, n_pts = scans.size() / 4;
+    std::vector<erasor_scan_label_row> rows(std::max<size_t>(n_frames, 1));
+    std::vector<uint8_t> codes(std::max<size_t>(n_pts, 1));
+    std::vector<float> kept(std::max<size_t>(n_pts, 1) * 4);
+    std::vector<uint64_t> kept_off(n_frames + 1);
+    erasor_scan_label_row sum;
+    const int rc = erasor_hip_label_scans_clouds(h, smap.data(), smap.size() / 4, 0, have_raw ? rmap.data() : nullptr, rmap.size() / 4, 0, have_raw ? 1 : 0,
+                                                 scans.data(), n_pts, offsets.data(), n_frames, 0, Tl, Tb.data(), tau, codes.data(), 0, kept.data(), n_pts,
+                                                 kept_off.data(), rows.data(), &sum);
+    if (rc) {
+        fprintf(stderr, "label_scans: %s (rc %d)\n", erasor_hip_last_error(h), rc);
+        erasor_hip_destroy(h);
+        return 1;
+    }
+    erasor_hip_destroy(h);
+    printf("%zu frames against %s (%zu points)%s%s, tau %.6f m:\n", n_frames, static_path.c_str(), smap.size() / 4, have_raw ? " and " : "",
+           have_raw ? raw_path.c_str() : "", tau);
+    for (size_t f = 0; f < n_frames; ++f) {
+        const erasor_scan_label_row &r = rows[f];
+        printf("%6d  n=%llu  static=%llu  dynamic=%llu  unknown=%llu  dropped=%llu  moving IoU=%.4f\n", drv.init_idx + (int)f,
+               (unsigned long long)r.n_points, (unsigned long long)(r.n[0][0] + r.n[1][0]), (unsigned long long)(r.n[0][1] + r.n[1][1]),
+               (unsigned long long)(r.n[0][2] + r.n[1][2]), (unsigned long long)r.n_non_finite,
+               ratio_or_nan(r.n[1][1], r.n[1][1] + r.n[0][1] + r.n[1][0] + r.n[1][2]));
+        char name[64];
+        snprintf(name, sizeof(name), "/%06d.label", drv.init_idx + (int)f);
+        FILE *fp = fopen((out_dir + name).c_str(), "wb");
+        if (!fp) {
+            fprintf(stderr, "cannot write %s%s\n", out_dir.c_str(), name);
+            return 1;
+        }
+        for (uint64_t i = offsets[f]; i < offsets[f + 1]; ++i) {
+            const uint32_t id = codes[i] == 0 ? 9u : codes[i] == 1 ? 251u : 0u;
+            const unsigned char le[4] = {(unsigned char)(id & 0xFF), (unsigned char)((id >> 8) & 0xFF), (unsigned char)((id >> 16) & 0xFF),
+                                         (unsigned char)(id >> 24)};
+            fwrite(le, 1, 4, fp);
+        }
+        if (fclose(fp) != 0) return 1;
+        pcl::PointCloud<pcl::PointXYZI> out;
+        const std::vector<float> frame_rows(kept.begin() + 4 * kept_off[f], kept.begin() + 4 * kept_off[f + 1]);
+        rows_to_cloud(frame_rows, kept_off[f + 1] - kept_off[f], out);
+        snprintf(name, sizeof(name), "/%06d.pcd", drv.init_idx + (int)f);
+        if (erasor_utils::save_pcd_binary(out_dir + name, out) != 0) {
+            fprintf(stderr, "cannot write %s%s\n", out_dir.c_str(), name);
+            return 1;
+        }
+    }
+    const uint64_t TP = sum.n[1][1], FP = sum.n[0][1], FN = sum.n[1][0] + sum.n[1][2];
+    printf("summary: n=%llu  dropped=%llu  labels out of range=%llu\n", (unsigned long long)sum.n_points, (unsigned long long)sum.n_non_finite,
+           (unsigned long long)sum.n_label_out_of_range);
+    printf("  own label static: static=%llu dynamic=%llu unknown=%llu\n", (unsigned long long)sum.n[0][0], (unsigned long long)sum.n[0][1],
+           (unsigned long long)sum.n[0][2]);
+    printf("  own label moving: static=%llu dynamic=%llu unknown=%llu\n", (unsigned long long)sum.n[1][0], (unsigned long long)sum.n[1][1],
+           (unsigned long long)sum.n[1][2]);
+    printf("  moving: TP=%llu FP=%llu FN=%llu  IoU=%.6f  precision=%.6f  recall=%.6f\n", (unsigned long long)TP, (unsigned long long)FP,
+           (unsigned long long)FN, ratio_or_nan(TP, TP + FP + FN), ratio_or_nan(TP, TP + FP), ratio_or_nan(TP, TP + FN));
+    return 0;
+}
+
 // --queue <n_workers> <max_frames> <a.yaml> <b.yaml> ...: independent sequences (one rosparam file each) over n_workers devices
 // (worker w drives device w mod the visible devices): every worker is a thread with its own updater per job, and takes the NEXT sequence
 // of the list whenever it is idle (erasor::WorkQueue) -- BASELINE config 3 on a node with fewer GPUs than sequences.
@@ -1258,6 +1386,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && std::string(argv[1]) == "--label-scans") {
+        try {
+            return label_scans_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--analyze") {
         try {
             return analyze_mode(argc, argv);
@@ -1297,8 +1433,9 @@ int main(int argc, char **argv) {
                 "       %s --analyze <gt> <est> [voxelsize] [voxel_leaf]\n       %s --align <rosparam.yaml> [n_frames] [voxelsize]\n"
                 "       %s --label <map> <dense_labelled> [leaf]\n       %s --complement <est> <gt> <out.pcd>\n"
                 "       %s --sweep <rosparam.yaml> <grid.yaml> <gt> [n_frames] [voxelsize] [concurrency]\n"
-                "       %s --eval-many <voxelsize> <voxel_leaf> <gt> <est1> [<est2> ...]\n",
-                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                "       %s --eval-many <voxelsize> <voxel_leaf> <gt> <est1> [<est2> ...]\n"
+                "       %s --label-scans <rosparam.yaml> <static.pcd> <raw.pcd|-> <out_dir> [n_frames] [tau]\n",
+                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

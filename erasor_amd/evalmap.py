@@ -14,6 +14,9 @@ reference's label_map (src/utils/fill_removert_intensity.cpp:24-59) and calc_com
 
 align_frames: overlap() of every frame's scan, put into the map frame by its pose, against the map (Erasor.align_frames).
 
+label_scans / moving_iou: every scan's points labelled static / dynamic / unknown from a cleaned map, against the scan's own labels
+(Erasor.label_scans).
+
 evaluate_by_class: the same decision per GT point, counted per semantic class and per dynamic instance (Erasor.evaluate_by_class).
 """
 import numpy as np
@@ -108,6 +111,97 @@ def align_frames(map_xyz, scans, T_body2origin, T_lidar2body=None, voxelsize=0.2
         rows.append(r)
     allk = np.concatenate(kept) if kept else np.zeros((0, 3), np.float32)
     return rows, overlap(map_xyz, allk, voxelsize)
+
+
+LABEL_STATIC, LABEL_DYNAMIC, LABEL_UNKNOWN, LABEL_DROPPED = 0, 1, 2, 255
+
+
+def label_tau(voxelsize=0.2):
+    """label_scans' default threshold: evaluate's, voxelsize * np.sqrt(3) / 2, formed as evaluate forms it"""
+    return float(voxelsize * np.sqrt(3) / 2)
+
+
+def label_bound(tau):
+    """the largest float64 whose sqrt is < tau: d < tau <=> d^2 <= label_bound(tau) for d = sqrt(d^2) (what the device tests)"""
+    tau = np.float64(tau)
+    with np.errstate(over="ignore", under="ignore"):
+        x = tau * tau
+    while x > 0 and not np.sqrt(x) < tau:
+        x = np.nextafter(x, 0.0)
+    while True:
+        y = np.nextafter(x, np.inf)
+        if not y < np.inf or not np.sqrt(y) < tau:
+            return float(x)
+        x = y
+
+
+def _nearest_dist(map_xyz, q):
+    """the float64 distance of every row of q to its nearest map point, as cKDTree returns it (+inf against an empty map)"""
+    if len(map_xyz) == 0 or len(q) == 0:
+        return np.full(len(q), np.inf)
+    d, _ = cKDTree(map_xyz.astype(np.float64)).query(q.astype(np.float64), k=1, workers=-1)
+    return d.reshape(-1)
+
+
+def label_scans(static_xyz, scans, T_body2origin, T_lidar2body=None, raw_xyz=None, tau=None, voxelsize=0.2, split=None):
+    """Every point of every scan classified against a cleaned (static) map and, optionally, the raw map.  Scan f is put into the map
+    frame as align_frames puts it.  Per point: 255 dropped (a non-finite coordinate after the transforms); else 0 static when its distance
+    to the nearest static-map point is < tau; else 1 dynamic when no raw map was given or its distance to the nearest raw-map point is
+    < tau; else 2 unknown.  tau: voxelsize * np.sqrt(3) / 2 when None.  The scan's own label: moving when labels(intensity) is in
+    DYNAMIC_CLASSES; intensities outside [0, 2^32) (or not finite) count as static and are counted, over the kept points.
+    Returns (codes, rows, summary): a uint8 array per frame; per frame {"n_points", "n_non_finite", "n_label_out_of_range", "n"} with
+    n[gt moving][code] a 2 x 3 list; and the sum of the rows.  split (0, 1 or 2): also the rows of that code, as given, per frame."""
+    static_xyz = np.asarray(static_xyz, np.float32).reshape(-1, 3)
+    raw = None if raw_xyz is None else np.asarray(raw_xyz, np.float32).reshape(-1, 3)
+    tau = label_tau(voxelsize) if tau is None else float(tau)
+    if not (tau > 0 and np.isfinite(tau)):
+        raise ValueError("tau must be a finite number > 0")
+    if split is not None and (split not in (0, 1, 2) or (split == 2 and raw is None)):
+        raise ValueError("split must be 0, 1 or 2 (2 only with a raw map)")
+    Tl = np.eye(4, dtype=np.float32) if T_lidar2body is None else T_lidar2body
+    codes, rows, clouds = [], [], []
+    total = {"n_points": 0, "n_non_finite": 0, "n_label_out_of_range": 0, "n": [[0, 0, 0], [0, 0, 0]]}
+    for f, scan in enumerate(scans):
+        s = np.ascontiguousarray(scan, np.float32).reshape(len(scan), 4)
+        with np.errstate(over="ignore", invalid="ignore"):
+            q = _xform(T_body2origin[f], _xform(Tl, s[:, :3]))
+        ok = np.isfinite(q).all(1)
+        code = np.full(len(s), LABEL_DROPPED, np.uint8)
+        c = np.full(int(ok.sum()), LABEL_DYNAMIC, np.uint8)
+        not_static = ~(_nearest_dist(static_xyz, q[ok]) < tau)
+        c[~not_static] = LABEL_STATIC
+        if raw is not None:
+            far = ~(_nearest_dist(raw, q[ok][not_static]) < tau)
+            c[np.flatnonzero(not_static)[far]] = LABEL_UNKNOWN
+        code[ok] = c
+        w = s[ok, 3]
+        in_range = (w >= 0) & (w < 4294967296.0)  # (NaN fails both)
+        moving = np.zeros(len(w), bool)
+        moving[in_range] = np.isin(labels(w[in_range]), DYNAMIC_CLASSES)
+        r = {"n_points": int(len(s)), "n_non_finite": int((~ok).sum()), "n_label_out_of_range": int((~in_range).sum()),
+             "n": [[int(np.sum((moving == bool(g)) & (c == k))) for k in range(3)] for g in range(2)]}
+        for k in ("n_points", "n_non_finite", "n_label_out_of_range"):
+            total[k] += r[k]
+        for g in range(2):
+            for k in range(3):
+                total["n"][g][k] += r["n"][g][k]
+        codes.append(code)
+        rows.append(r)
+        if split is not None:
+            clouds.append(s[code == split].copy())
+    return (codes, rows, total) if split is None else (codes, rows, total, clouds)
+
+
+def moving_iou(summary):
+    """moving-object segmentation scores of a label_scans summary (or row), in float64: TP = n[1][1], FP = n[0][1], FN = n[1][0] + n[1][2];
+    IoU = TP / (TP + FP + FN), precision = TP / (TP + FP), recall = TP / (TP + FN); NaN where a denominator is 0"""
+    n = summary["n"]
+    tp, fp, fn = int(n[1][1]), int(n[0][1]), int(n[1][0]) + int(n[1][2])
+
+    def ratio(a, b):
+        return float(a) / float(b) if b else float("nan")
+
+    return {"TP": tp, "FP": fp, "FN": fn, "IoU": ratio(tp, tp + fp + fn), "precision": ratio(tp, tp + fp), "recall": ratio(tp, tp + fn)}
 
 
 def _l2_simple(q, p):

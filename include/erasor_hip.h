@@ -492,6 +492,51 @@ int erasor_hip_align_frames_map(erasor_hip_handle *h, const void *scans_xyzi, si
                                 int scans_are_device, const float T_lidar2body[16], const float *T_body2origin, double voxelsize,
                                 erasor_align_row *rows, erasor_overlap_result *summary);
 
+/* ---- every scan's points labelled static or moving from a cleaned map ---------------------------------------------------------
+ * replaces: what users of a cleaned map do on the host afterwards -- a KD-tree over the cleaned map, a radius test per scan point, the
+ * scan's moving points dropped (automatic moving-object-segmentation labels, cleaned scans for re-mapping); the reference itself stops
+ * at the map.  Frame f is the scans' points [offsets[f], offsets[f + 1]) as given, put into the map frame exactly as
+ * erasor_hip_align_frames_clouds puts them (T_lidar2body, NULL for the identity and still applied, then T_body2origin[f], in float32).
+ * With d_s / d_r the float64 distances from a point to its nearest static-map / raw-map point (as cKDTree returns them) its code is
+ *   0   static:  d_s < tau
+ *   1   dynamic: not static, and no raw map was given or d_r < tau
+ *   2   unknown: a raw map was given, not static, and d_r >= tau (structure neither map holds)
+ *   255 dropped: a non-finite coordinate after the two transforms.
+ * An empty static map: nothing is static.  An empty raw map that is given (have_raw != 0, n_raw == 0): everything else is unknown.  The
+ * answer is exact: the search is bounded by tau and stops at the first map point within it, and decides as the distances would.
+ * The scan's own label: moving when uint32(intensity) & 0xFFFF is in 252..259; an intensity that is not finite or outside [0, 2^32)
+ * counts as static and is counted. */
+typedef struct erasor_scan_label_row {
+    uint64_t n_points;              /* points of the frame as given */
+    uint64_t n_non_finite;          /* dropped (code 255) */
+    uint64_t n_label_out_of_range;  /* kept points whose intensity is not finite or outside [0, 2^32): decoded as static */
+    uint64_t n[2][3];               /* [the scan's own label: 0 static, 1 moving][code 0, 1, 2] */
+} erasor_scan_label_row;
+
+/* The static map, the optional raw map (have_raw) and the concatenated scans, each on the host or on the handle's device (_is_device);
+ * offsets / T_lidar2body / T_body2origin as erasor_hip_align_frames_clouds takes them; rows: n_frames entries; summary (optional): the
+ * sum of the rows.  codes (optional, host): one byte per scan point.  The split (optional): the rows of the points with code split_code,
+ * as given (sensor frame, all four floats copied as bits), frame by frame in scan order, into split_xyzi (host, split_cap rows), and
+ * split_offsets (host, n_frames + 1 entries: frame f's rows are [split_offsets[f], split_offsets[f + 1])); either may be NULL, both
+ * NULL: no split.  n_scan_points rows always suffice; a smaller buffer that does not hold the result gives ERASOR_E_CAPACITY (rows,
+ * summary, codes and split_offsets are filled first).  Works in the evaluator's own scratch: announced nodes, tickets and the last
+ * step's clouds stay as they are.
+ * ERASOR_E_INVALID: as erasor_hip_align_frames_clouds (poses, offsets, 2^30 points, 65536 frames, a non-finite map point); tau not a
+ * finite number > 0; a split with split_code outside 0..2, or 2 without a raw map.  ERASOR_E_STATE: a step in flight. */
+int erasor_hip_label_scans_clouds(erasor_hip_handle *h, const void *static_xyzi, size_t n_static, int static_is_device,
+                                  const void *raw_xyzi, size_t n_raw, int raw_is_device, int have_raw,
+                                  const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                                  int scans_are_device, const float T_lidar2body[16], const float *T_body2origin, double tau,
+                                  uint8_t *codes, int split_code, float *split_xyzi, size_t split_cap, uint64_t *split_offsets,
+                                  erasor_scan_label_row *rows, erasor_scan_label_row *summary);
+/* the same with the handle's current map as the static map (the erasor_hip_get_map view, compacted on the device as
+ * erasor_hip_overlap_map does, never copied to the host).  ERASOR_E_STATE also: no map. */
+int erasor_hip_label_scans_map(erasor_hip_handle *h, const void *raw_xyzi, size_t n_raw, int raw_is_device, int have_raw,
+                               const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                               int scans_are_device, const float T_lidar2body[16], const float *T_body2origin, double tau,
+                               uint8_t *codes, int split_code, float *split_xyzi, size_t split_cap, uint64_t *split_offsets,
+                               erasor_scan_label_row *rows, erasor_scan_label_row *summary);
+
 /* ---- maps without labels: label a third-party map from a dense labelled one, and the static points a method lost ----------------
  * Both search the overlap report's tree in FLANN's metric, as pcl::KdTreeFLANN (K = 1) does: float32 d^2 = ((0 + dx*dx) + dy*dy) + dz*dz
  * with dx = q.x - p.x in float, exact, the lowest index on ties.  Outputs are XYZI rows in caller HOST buffers; dst == NULL asks for
