@@ -88,6 +88,27 @@ class ScanLabelRow(C.Structure):
                 "n": [[int(self.n[g][k]) for k in range(3)] for g in range(2)]}
 
 
+class ClusterRow(C.Structure):
+    """erasor_cluster_row (include/erasor_hip.h): one listed cluster"""
+    _fields_ = [(k, C.c_uint32) for k in ("first", "n_points", "n_dynamic", "n_label_out_of_range")] + [
+        ("min_xyz", C.c_float * 3), ("max_xyz", C.c_float * 3)]
+
+
+# the rows as numpy records (ClusterRow's layout; evalmap.CLUSTER_ROW_DTYPE)
+CLUSTER_ROW_DTYPE = np.dtype([(k, np.uint32) for k in ("first", "n_points", "n_dynamic", "n_label_out_of_range")] + [
+    ("min_xyz", np.float32, 3), ("max_xyz", np.float32, 3)])
+CLUSTER_NONE = 0xFFFFFFFF  # ids of points whose cluster is not listed
+
+
+class ClusterResult(C.Structure):
+    """erasor_cluster_result (include/erasor_hip.h)"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_clusters", "n_listed", "n_points_listed", "n_singletons", "largest")]
+
+    def as_dict(self):
+        """evalmap.cluster's result keys"""
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class LabelResult(C.Structure):
     """erasor_label_result (include/erasor_hip.h): label_map of a map without labels (fill_removert_intensity.cpp:24-59)"""
     _fields_ = [("n_src", C.c_uint64), ("n_out", C.c_uint64), ("n_tied", C.c_uint64), ("passthrough", C.c_uint32)]
@@ -267,7 +288,7 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "label_scans.hip.h", "render.hip.h", "revert_bins.hip.h",
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "label_scans.hip.h", "cluster.hip.h", "render.hip.h", "revert_bins.hip.h",
                                                  "exact_sort.hip.h", "exact_sort_core.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
@@ -866,6 +887,54 @@ class Erasor:
             return res
         oo = out_offs.astype(np.int64)
         return res + ([out[oo[f]:oo[f + 1]].copy() for f in range(n_f)],)
+
+    # -- a cloud as connected objects: Euclidean clustering (on the host: evalmap.cluster) --
+    def _cluster(self, fn, head, n, tol, min_size, max_size, ids, keep):
+        r = ClusterResult()
+        tail = (C.c_double(tol), C.c_size_t(int(min_size)), C.c_size_t(int(max_size)))
+        id_buf = np.empty(max(n, 1), np.uint32) if ids else None
+        rows = np.zeros(max(min(n, 1 << 16), 1), CLUSTER_ROW_DTYPE)
+        kept = np.empty((max(n, 1), 4), np.float32) if keep else None
+        for attempt in range(2):  # (a second call only when the rows did not fit: then with their exact count; the ids came with the first)
+            rc = fn(self._h, *head, *tail, _p(id_buf) if ids and not attempt else None, _p(rows), C.c_size_t(len(rows)), _p(kept) if keep else None,
+                    C.c_size_t(len(kept) if keep else 0), C.byref(r))
+            if rc != E_CAPACITY or attempt:
+                break
+            rows = np.zeros(max(int(r.n_listed), 1), CLUSTER_ROW_DTYPE)
+        self._check(rc)
+        return (rows[: r.n_listed], id_buf[:n] if ids else None, kept[: r.n_points_listed] if keep else None, r.as_dict())
+
+    def cluster(self, cloud, tol, min_size=1, max_size=0, ids=True, keep=False):
+        """Euclidean clustering of `cloud` (as for evaluate) on the device (erasor_hip_cluster_clouds): the connected components of
+        "within tol" (float64 distances), a cluster listed when min_size <= n_points and (max_size == 0 or n_points <= max_size).
+        Returns (rows, ids, kept, result) as evalmap.cluster does: CLUSTER_ROW_DTYPE records in increasing `first`; per point the index
+        of its cluster among the rows or CLUSTER_NONE (None unless ids); the rows of the points of listed clusters in the order given
+        (None unless keep: the residue filter); and the result's counts as a dict."""
+        kept = []
+        c = self._eval_cloud(cloud, kept)
+        return self._cluster(lib().erasor_hip_cluster_clouds, c, c[1].value, tol, min_size, max_size, ids, keep)
+
+    def cluster_map(self, tol, min_size=1, max_size=0, ids=True, keep=False):
+        """cluster of the handle's current map (the get_map view, never copied to the host; erasor_hip_cluster_map)"""
+        n = C.c_size_t(0)
+        if lib().erasor_hip_map_size(self._h, C.byref(n)) != 0:  # (no map, a step in flight: the call itself says so)
+            n = C.c_size_t(0)
+        return self._cluster(lib().erasor_hip_cluster_map, (), n.value, tol, min_size, max_size, ids, keep)
+
+    def residue(self, gt, est, tol=0.5, voxelsize=0.2, voxel_leaf=0.0, min_size=1):
+        """The ghost objects a method left: the dynamic points of the labelled ground truth `gt` that evaluate(gt, est, voxelsize) found
+        kept (EVAL_KEPT_DYNAMIC), clustered at `tol` -- boxes and sizes, no instance labels needed.  Host clouds; voxel_leaf > 0: both
+        voxelised at that leaf first.  Returns (rows, ids, points, result): cluster's rows, ids and result over `points`, the kept
+        dynamic ground-truth rows in ground-truth order."""
+        g = _f32(gt).reshape(-1, 4)
+        e = _f32(est).reshape(-1, 4)
+        if voxel_leaf > 0:
+            g = self.voxelize_preserving_labels(g, voxel_leaf)
+            e = self.voxelize_preserving_labels(e, voxel_leaf)
+        codes = self.evaluate(g, e, voxelsize, 0.0, per_point=True)["per_point"]
+        pts = np.ascontiguousarray(g[codes == EVAL_KEPT_DYNAMIC])
+        rows, ids, _, res = self.cluster(pts, tol, min_size)
+        return rows, ids, pts, res
 
     # -- maps without labels (fill_removert_intensity.cpp:24-59, compare_complement.cpp:43-75; on the host: evalmap.label_from /
     # evalmap.static_complement) --

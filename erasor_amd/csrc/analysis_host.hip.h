@@ -1,8 +1,8 @@
 // The offline analyses' host code: PR / RR evaluation (one estimate, many, by class), the overlap report, the frame check, the scans'
-// labels, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
+// labels, the clustering, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
 // at its end -- one translation unit, like the kernel headers -- so it sees the handle, ensure / LAUNCH / HIPC, scan_u32, radix_sort,
 // map_to_device and voxelize_device from there; nothing of the step path depends on this file.  Kernels: evaluate.hip.h, nearest.hip.h,
-// align.hip.h, label_scans.hip.h, render.hip.h.
+// align.hip.h, label_scans.hip.h, cluster.hip.h, render.hip.h.
 #pragma once
 
 extern "C" {
@@ -915,6 +915,118 @@ int erasor_hip_label_scans_map(erasor_hip_handle *h, const void *raw_xyzi, size_
     if ((rc = map_on_device(h, who, h->ev.map, &m, &n_map)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q))) return rc;
     return ls_run(h, who, m, n_map, raw_xyzi, (uint32_t)n_raw, raw_is_device, have_raw, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body,
                   T_body2origin, tau, codes, sp, rows, summary);
+}
+
+// ---- a cloud as connected objects: Euclidean clustering, listed and filtered by size (kernels: cluster.hip.h) ----
+// Like ev_run: the main stream, the evaluator's scratch; the grid is the evaluator's, at a cell edge a little above tol.  One round trip
+// for the counters (they size the rows), then the rows, the ids and the kept cloud.
+static int cl_check_args(erasor_hip_handle *h, const char *who, double tol, const void *res) {
+    if (!res) return invalid(h, who, "res is NULL");
+    if (!(tol > 0) || !std::isfinite(tol)) return invalid(h, who, "tol must be a finite number > 0");
+    return ERASOR_OK;
+}
+
+static int cl_run(erasor_hip_handle *h, const char *who, const float4 *pts, uint32_t n, double tol, size_t min_size, size_t max_size, uint32_t *ids,
+                  erasor_cluster_row *rows, size_t cap_rows, float *kept_xyzi, size_t cap_points, erasor_cluster_result *res) {
+    static_assert(sizeof(erasor_cluster_row) == CL_ROW * sizeof(uint32_t), "the device writes erasor_cluster_row word by word");
+    auto &E = h->ev;
+    erasor_cluster_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_points = n;
+    if (!n) {
+        *res = r;
+        return ERASOR_OK;
+    }
+    const uint32_t mn = (uint32_t)std::min<size_t>(std::max<size_t>(min_size, 1), 0xFFFFFFFFull);
+    const uint32_t mx = (uint32_t)std::min<size_t>(max_size, 0xFFFFFFFFull);  // (0: no upper limit)
+    uint32_t nb = 1024;  // buckets: ev_run's (a power of two >= the cloud's size)
+    while (nb < n) nb <<= 1;
+    const size_t n1 = (size_t)n + 1;
+    if (ensure(h, E.ctr, EV_NCTR) || ensure(h, E.cl_ctr, CL_NCTR) || ensure(h, E.cnt, (size_t)nb + 1) || ensure(h, E.pl, (size_t)nb + 1) ||
+        ensure(h, E.tops, nb / 1024 + 4) || ensure(h, E.bkt, n1) || ensure(h, E.pts, n1) || ensure(h, E.idx, n1) || ensure(h, E.cl_parent, n1) ||
+        ensure(h, E.cl_root, n1) || ensure(h, E.cl_tab, n1 * CL_TROW) || ensure(h, E.cl_rank, n1) || ensure(h, E.cl_ids, n1) || ensure(h, E.fm_flag, n1) ||
+        ensure(h, E.fm_pl, n1) || ensure(h, E.fm_tops, n / 1024 + 4))
+        return ERASOR_E_NO_DEVICE;
+    const double cell = tol * CL_CELL_MARGIN, tol2 = tol * tol;
+    const uint32_t g = cdiv(n, 256);
+    HIPC(h, hipMemsetAsync(E.ctr.p, 0, EV_NCTR * sizeof(unsigned long long), h->stream));
+    HIPC(h, hipMemsetAsync(E.cl_ctr.p, 0, CL_NCTR * sizeof(unsigned long long), h->stream));
+    HIPC(h, hipMemsetAsync(E.cnt.p, 0, ((size_t)nb + 1) * sizeof(uint32_t), h->stream));
+    LAUNCH(h, h->stream, "cl_index", k_ev_hist, g, 256, pts, n, cell, nb - 1, E.bkt.p, E.cnt.p, E.ctr.p);
+    scan_u32(h, h->stream, E.cnt.p, E.pl.p, E.tops.p, nb + 1, nb + 1, nullptr, nullptr, "cl_index");
+    LAUNCH(h, h->stream, "cl_index", k_ev_offsets, cdiv(nb + 1, 256), 256, (const uint32_t *)E.pl.p, (const uint32_t *)E.tops.p, nb + 1, E.cnt.p, E.pl.p);
+    LAUNCH(h, h->stream, "cl_index", k_ev_scatter, g, 256, pts, n, (const uint32_t *)E.bkt.p, E.pl.p, E.pts.p, E.idx.p);
+    LAUNCH(h, h->stream, "cl_index", k_cl_init, g, 256, n, E.cl_parent.p, E.cl_tab.p);
+    LAUNCH(h, h->stream, "cl_unite", k_cl_unite, g, 256, pts, n, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p, (const uint32_t *)E.cnt.p, nb - 1, cell, tol2,
+           E.cl_parent.p);
+    LAUNCH(h, h->stream, "cl_table", k_cl_table, g, 256, pts, n, (const uint32_t *)E.cl_parent.p, E.cl_root.p, E.cl_tab.p);
+    LAUNCH(h, h->stream, "cl_list", k_cl_flags, g, 256, n, (const uint32_t *)E.cl_root.p, (const uint32_t *)E.cl_tab.p, mn, mx, E.fm_flag.p, E.cl_ctr.p);
+    unsigned long long c[EV_NCTR], cc[CL_NCTR];
+    HIPC(h, hipMemcpyAsync(c, E.ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipMemcpyAsync(cc, E.cl_ctr.p, sizeof(cc), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (c[EV_NON_FINITE])
+        return invalid(h, who, "non-finite coordinate (NaN / Inf) in " + std::to_string(c[EV_NON_FINITE]) + " point(s)");
+    r.n_clusters = cc[CL_C_CLUSTERS];
+    r.n_listed = cc[CL_C_LISTED];
+    r.n_points_listed = cc[CL_C_POINTS_LISTED];
+    r.n_singletons = cc[CL_C_SINGLETONS];
+    r.largest = cc[CL_C_LARGEST];
+    *res = r;
+    if (!ids && !rows && !kept_xyzi) return ERASOR_OK;
+    // the listed roots ranked in index order (= `first` order), their rows, every point's row
+    if (ensure(h, E.cl_rows, (size_t)r.n_listed * CL_ROW + 1)) return ERASOR_E_NO_DEVICE;
+    scan_u32(h, h->stream, E.fm_flag.p, E.fm_pl.p, E.fm_tops.p, n, n, nullptr, nullptr, "cl_list");
+    LAUNCH(h, h->stream, "cl_list", k_cl_rows, g, 256, n, (const uint32_t *)E.fm_flag.p, (const uint32_t *)E.fm_pl.p, (const uint32_t *)E.fm_tops.p,
+           (const uint32_t *)E.cl_tab.p, E.cl_rows.p, E.cl_rank.p);
+    if (ids || kept_xyzi)
+        LAUNCH(h, h->stream, "cl_list", k_cl_ids, g, 256, n, (const uint32_t *)E.cl_root.p, (const uint32_t *)E.cl_rank.p, E.cl_ids.p, E.fm_flag.p);
+    int rc;
+    if (ids && (rc = d2h(h, ids, E.cl_ids.p, (size_t)n * sizeof(uint32_t)))) return rc;
+    if ((rows && r.n_listed > cap_rows) || (kept_xyzi && r.n_points_listed > cap_points)) {
+        HIPC(h, hipStreamSynchronize(h->stream));
+        return ERASOR_E_CAPACITY;
+    }
+    if (rows && (rc = d2h(h, rows, E.cl_rows.p, (size_t)r.n_listed * sizeof(erasor_cluster_row)))) return rc;
+    if (kept_xyzi && r.n_points_listed) {
+        // the rows of the listed clusters' points, as given: the stable compaction over the keep flags
+        if (ensure(h, E.fm_out, n1)) return ERASOR_E_NO_DEVICE;
+        scan_u32(h, h->stream, E.fm_flag.p, E.fm_pl.p, E.fm_tops.p, n, n, nullptr, nullptr, "cl_keep");
+        LAUNCH(h, h->stream, "cl_keep", k_f_compact, g, 256, pts, n, (const uint32_t *)E.fm_flag.p, (const uint32_t *)E.fm_pl.p, (const uint32_t *)E.fm_tops.p,
+               E.fm_out.p);
+        return d2h(h, kept_xyzi, E.fm_out.p, (size_t)r.n_points_listed * sizeof(float4));
+    }
+    HIPC(h, hipStreamSynchronize(h->stream));
+    return ERASOR_OK;
+}
+
+int erasor_hip_cluster_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, double tol, size_t min_size, size_t max_size, uint32_t *ids,
+                              erasor_cluster_row *rows, size_t cap_rows, float *kept_xyzi, size_t cap_points, erasor_cluster_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_cluster_clouds";
+    int rc = cl_check_args(h, who, tol, res);
+    if (rc || (rc = check_cloud(h, who, BAD_CLOUD, xyzi, n))) return rc;
+    const float4 *p = nullptr;
+    if (n) {
+        HIPC(h, hipSetDevice(h->device));
+        if ((rc = ev_input(h, xyzi, n, is_device, h->ev.gt, &p))) return rc;
+    }
+    return cl_run(h, who, p, (uint32_t)n, tol, min_size, max_size, ids, rows, cap_rows, kept_xyzi, cap_points, res);
+}
+
+int erasor_hip_cluster_map(erasor_hip_handle *h, double tol, size_t min_size, size_t max_size, uint32_t *ids, erasor_cluster_row *rows, size_t cap_rows,
+                           float *kept_xyzi, size_t cap_points, erasor_cluster_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_cluster_map";
+    int rc = cl_check_args(h, who, tol, res);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    uint32_t n = 0;
+    if ((rc = map_on_device(h, who, h->ev.map, &p, &n))) return rc;
+    return cl_run(h, who, p, n, tol, min_size, max_size, ids, rows, cap_rows, kept_xyzi, cap_points, res);
 }
 
 // ---- label_map (fill_removert_intensity.cpp:24-59, compare_map.cpp:77-110) and calc_complement (compare_complement.cpp:43-75): the

@@ -38,6 +38,7 @@
 #include "nearest.hip.h"
 #include "align.hip.h"
 #include "label_scans.hip.h"
+#include "cluster.hip.h"
 #include "render.hip.h"
 
 using namespace ek;
@@ -368,6 +369,10 @@ struct erasor_hip_handle {
         DBuf<uint32_t> rd_tile, rd_cnt, rd_pl, rd_tops, rd_bb;
         DBuf<unsigned long long> rd_rec, rd_srt, rd_ctr, rd_zb;
         DBuf<uint8_t> rd_img;
+        // Euclidean clustering (erasor_hip_cluster_*): the union-find forest, every point's root, the table per root, the listed
+        // roots' ranks, the rows, the ids and the counters (the grid: cnt, pl, tops, bkt, pts, idx above; flags and kept cloud: fm_*)
+        DBuf<uint32_t> cl_parent, cl_root, cl_tab, cl_rank, cl_rows, cl_ids;
+        DBuf<unsigned long long> cl_ctr;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
 #ifdef ERASOR_HIP_TEST_HOOKS
@@ -1125,6 +1130,8 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->ev.em_cat); release(h->ev.em_tab); release(h->ev.em_ctr);
     release(h->ev.rd_pts); release(h->ev.rd_map); release(h->ev.rd_tile); release(h->ev.rd_cnt); release(h->ev.rd_pl); release(h->ev.rd_tops);
     release(h->ev.rd_bb); release(h->ev.rd_rec); release(h->ev.rd_srt); release(h->ev.rd_ctr); release(h->ev.rd_zb); release(h->ev.rd_img);
+    release(h->ev.cl_parent); release(h->ev.cl_root); release(h->ev.cl_tab); release(h->ev.cl_rank); release(h->ev.cl_rows); release(h->ev.cl_ids);
+    release(h->ev.cl_ctr);
     for (int k = 0; k < NSIDE; ++k) {
         if (h->q[k].ev_keys) (void)hipEventDestroy(h->q[k].ev_keys);
         if (h->q[k].ev_done) (void)hipEventDestroy(h->q[k].ev_done);

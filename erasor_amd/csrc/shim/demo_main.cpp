@@ -475,6 +475,121 @@ static int complement_mode(int argc, char **argv) {
     printf("saved %s\n", argv[4]);
     return 0;
 }
+// ---- a cloud as connected objects (erasor_hip_cluster_clouds) ----
+// a number argument read whole: false on anything else
+static bool parse_number(const char *a, double *v) {
+    char *end = nullptr;
+    *v = strtod(a, &end);
+    return end != a && *end == '\0' && std::isfinite(*v);
+}
+static bool parse_count(const char *a, size_t *v) {
+    double d = 0;
+    if (!parse_number(a, &d) || d < 0 || d != floor(d) || d > 4294967295.0) return false;
+    *v = (size_t)d;
+    return true;
+}
+// the result line and the twenty largest listed clusters (ties: the lower `first`): size, dynamic share, box
+static void print_clusters(const erasor_cluster_result &r, std::vector<erasor_cluster_row> rows) {
+    printf("clusters: n=%llu  clusters=%llu  listed=%llu  points listed=%llu  singletons=%llu  largest=%llu\n", (unsigned long long)r.n_points,
+           (unsigned long long)r.n_clusters, (unsigned long long)r.n_listed, (unsigned long long)r.n_points_listed, (unsigned long long)r.n_singletons,
+           (unsigned long long)r.largest);
+    std::stable_sort(rows.begin(), rows.end(), [](const erasor_cluster_row &a, const erasor_cluster_row &b) { return a.n_points > b.n_points; });
+    for (size_t k = 0; k < rows.size() && k < 20; ++k) {
+        const erasor_cluster_row &c = rows[k];
+        printf("  first=%u  n=%u  dynamic=%u (%.1f%%)  box=[%.3f %.3f %.3f]..[%.3f %.3f %.3f]\n", c.first, c.n_points, c.n_dynamic,
+               100.0 * (double)c.n_dynamic / (double)c.n_points, c.min_xyz[0], c.min_xyz[1], c.min_xyz[2], c.max_xyz[0], c.max_xyz[1], c.max_xyz[2]);
+    }
+}
+// the clustering of a host cloud: the rows (all of them), optionally the kept cloud; 0, or 1 after printing the error
+static int cluster_host(erasor_hip_handle *h, const std::vector<float> &cloud, double tol, size_t min_size, size_t max_size, erasor_cluster_result *r,
+                        std::vector<erasor_cluster_row> *rows, std::vector<float> *kept) {
+    const size_t n = cloud.size() / 4;
+    rows->assign(std::max<size_t>(n, 1), erasor_cluster_row());
+    if (kept) kept->assign(std::max<size_t>(n, 1) * 4, 0.f);
+    const int rc = erasor_hip_cluster_clouds(h, cloud.data(), n, 0, tol, min_size, max_size, nullptr, rows->data(), rows->size(), kept ? kept->data() : nullptr,
+                                             kept ? n : 0, r);
+    if (rc) {
+        fprintf(stderr, "cluster: %s (rc %d)\n", erasor_hip_last_error(h), rc);
+        return 1;
+    }
+    rows->resize(r->n_listed);
+    if (kept) kept->resize(r->n_points_listed * 4);
+    return 0;
+}
+// --clusters <cloud.pcd> <tol> [min_size = 1] [max_size = 0] [kept_out.pcd]: Euclidean clustering of one cloud -- the result line, the
+// twenty largest clusters, and optionally the points of the listed clusters saved as a binary PCD (the residue filter)
+static int clusters_mode(int argc, char **argv) {
+    if (argc < 4 || argc > 7) return 2;
+    double tol = 0;
+    size_t min_size = 1, max_size = 0;
+    if (!parse_number(argv[3], &tol) || !(tol > 0)) return 2;
+    if ((argc > 4 && !parse_count(argv[4], &min_size)) || (argc > 5 && !parse_count(argv[5], &max_size))) return 2;
+    std::vector<float> cloud;
+    if (!load_cloud_xyzi(argv[2], cloud)) {
+        fprintf(stderr, "cannot read %s\n", argv[2]);
+        return 3;
+    }
+    erasor_hip_handle *h = render_handle();
+    if (!h) return 1;
+    erasor_cluster_result r;
+    std::vector<erasor_cluster_row> rows;
+    std::vector<float> kept;
+    const int rc = cluster_host(h, cloud, tol, min_size, max_size, &r, &rows, argc > 6 ? &kept : nullptr);
+    erasor_hip_destroy(h);
+    if (rc) return rc;
+    print_clusters(r, rows);
+    if (argc > 6) {
+        pcl::PointCloud<pcl::PointXYZI> out;
+        rows_to_cloud(kept, r.n_points_listed, out);
+        if (erasor_utils::save_pcd_binary(argv[6], out) != 0) {
+            fprintf(stderr, "cannot write %s\n", argv[6]);
+            return 1;
+        }
+        printf("saved %s\n", argv[6]);
+    }
+    return 0;
+}
+// --residue <gt> <est> [tol = 0.5] [voxelsize = 0.2] [voxel_leaf = 0]: the ghost objects a method left -- the ground truth's dynamic points
+// that --eval counts as kept, clustered (no instance labels needed)
+static int residue_mode(int argc, char **argv) {
+    if (argc < 4 || argc > 7) return 2;
+    double tol = 0.5, voxelsize = 0.2, voxel_leaf = 0.0;
+    if ((argc > 4 && (!parse_number(argv[4], &tol) || !(tol > 0))) || (argc > 5 && (!parse_number(argv[5], &voxelsize) || !(voxelsize > 0))) ||
+        (argc > 6 && (!parse_number(argv[6], &voxel_leaf) || voxel_leaf < 0)))
+        return 2;
+    std::vector<float> gt, est;
+    if (!load_cloud_xyzi(argv[2], gt) || !load_cloud_xyzi(argv[3], est)) {
+        fprintf(stderr, "cannot read %s or %s\n", argv[2], argv[3]);
+        return 3;
+    }
+    erasor_hip_handle *h = render_handle();
+    if (!h) return 1;
+    if (voxel_leaf > 0)
+        for (std::vector<float> *c : {&gt, &est}) {
+            std::vector<float> out(std::max<size_t>(c->size(), 4));
+            size_t n_out = 0;
+            const int rc = erasor_hip_voxelize_preserving_labels(h, c->data(), c->size() / 4, voxel_leaf, out.data(), out.size() / 4, &n_out);
+            if (rc) return render_fail(h, "voxelize", rc);
+            out.resize(n_out * 4);
+            c->swap(out);
+        }
+    const size_t n_gt = gt.size() / 4;
+    std::vector<uint8_t> code(std::max<size_t>(n_gt, 1));
+    erasor_eval_result e;
+    int rc = erasor_hip_evaluate_clouds(h, gt.data(), n_gt, 0, est.data(), est.size() / 4, 0, 0.0, voxelsize, code.data(), &e);
+    if (rc) return render_fail(h, "evaluate", rc);
+    std::vector<float> left;
+    for (size_t i = 0; i < n_gt; ++i)
+        if (code[i] == ERASOR_EVAL_KEPT_DYNAMIC) left.insert(left.end(), gt.begin() + 4 * i, gt.begin() + 4 * i + 4);
+    erasor_cluster_result r;
+    std::vector<erasor_cluster_row> rows;
+    rc = cluster_host(h, left, tol, 1, 0, &r, &rows, nullptr);
+    erasor_hip_destroy(h);
+    if (rc) return rc;
+    printf("residue: %llu of %llu dynamic ground-truth point(s) left\n", (unsigned long long)e.preserved_dynamic, (unsigned long long)e.gt_dynamic);
+    print_clusters(r, rows);
+    return 0;
+}
 // --eval-many <voxelsize> <voxel_leaf> <gt> <est1> [<est2> ...]: --eval's row for every estimate against one ground truth, from ONE
 // erasor_hip_evaluate_many call (compare_map.cpp's use: several methods' maps against one GT)
 static int eval_many_mode(int argc, char **argv) {
@@ -1394,6 +1509,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && (std::string(argv[1]) == "--clusters" || std::string(argv[1]) == "--residue")) {
+        try {
+            return std::string(argv[1]) == "--clusters" ? clusters_mode(argc, argv) : residue_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--analyze") {
         try {
             return analyze_mode(argc, argv);
@@ -1434,8 +1557,10 @@ int main(int argc, char **argv) {
                 "       %s --label <map> <dense_labelled> [leaf]\n       %s --complement <est> <gt> <out.pcd>\n"
                 "       %s --sweep <rosparam.yaml> <grid.yaml> <gt> [n_frames] [voxelsize] [concurrency]\n"
                 "       %s --eval-many <voxelsize> <voxel_leaf> <gt> <est1> [<est2> ...]\n"
-                "       %s --label-scans <rosparam.yaml> <static.pcd> <raw.pcd|-> <out_dir> [n_frames] [tau]\n",
-                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                "       %s --label-scans <rosparam.yaml> <static.pcd> <raw.pcd|-> <out_dir> [n_frames] [tau]\n"
+                "       %s --clusters <cloud.pcd> <tol> [min_size] [max_size] [kept_out.pcd]\n"
+                "       %s --residue <gt> <est> [tol] [voxelsize] [voxel_leaf]\n",
+                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

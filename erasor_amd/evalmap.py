@@ -18,6 +18,9 @@ label_scans / moving_iou: every scan's points labelled static / dynamic / unknow
 (Erasor.label_scans).
 
 evaluate_by_class: the same decision per GT point, counted per semantic class and per dynamic instance (Erasor.evaluate_by_class).
+
+cluster / cluster_brute: Euclidean clustering of a cloud, the host restatement of Erasor.cluster (include/erasor_hip.h,
+erasor_cluster_row): connected components of "within tol", listed and filtered by size, with counts and boxes.
 """
 import numpy as np
 from scipy.spatial import cKDTree
@@ -550,3 +553,108 @@ def render_eval(gt_xyzi, est_xyzi, view, voxelsize=0.2):
     prio = np.where(code == 1, 1, np.where(code == 2, 4, np.where(g_dyn, 2, 3))).astype(np.int64)
     img, stats = _raster(gt, prio, RENDER_EVAL, view)
     return img, stats, evaluate_clouds(gt, est_xyzi, voxelsize)
+
+
+# ---- Euclidean clustering (include/erasor_hip.h: erasor_hip_cluster_*; kernels: erasor_amd/csrc/cluster.hip.h), on the host ---------
+# The host restatement of the device's contract: points i and j are adjacent iff ((dx*dx + dy*dy) + dz*dz) <= tol*tol in float64 (dx =
+# float64(x_i) - float64(x_j)), a cluster is a connected component named by its lowest point index, a cluster is listed when min_size <=
+# n_points and (max_size == 0 or n_points <= max_size), rows in increasing `first`, the box in z_order's total order.
+CLUSTER_ROW_DTYPE = np.dtype([("first", np.uint32), ("n_points", np.uint32), ("n_dynamic", np.uint32), ("n_label_out_of_range", np.uint32),
+                              ("min_xyz", np.float32, 3), ("max_xyz", np.float32, 3)])
+CLUSTER_NONE = 0xFFFFFFFF
+CLUSTER_RESULT_FIELDS = ("n_points", "n_clusters", "n_listed", "n_points_listed", "n_singletons", "largest")
+
+
+def cluster_adjacent(a, b, tol):
+    """the predicate, row by row: a, b float32 (k, 3) arrays"""
+    d = np.asarray(a, np.float32).astype(np.float64) - np.asarray(b, np.float32).astype(np.float64)
+    return (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2] <= np.float64(tol) * np.float64(tol)
+
+
+def _cluster_args(cloud, tol, min_size, max_size):
+    c = np.ascontiguousarray(np.asarray(cloud, np.float32).reshape(-1, 4))
+    if not (np.isfinite(tol) and tol > 0):
+        raise ValueError("cluster: tol must be a finite number > 0")
+    if len(c) > 1 << 30:
+        raise ValueError("cluster: more than 2^30 points")
+    if not np.isfinite(c[:, :3]).all():
+        raise ValueError("cluster: non-finite coordinate")
+    if min_size < 0 or max_size < 0:
+        raise ValueError("cluster: negative size limit")
+    return c, float(tol), max(int(min_size), 1), int(max_size)
+
+
+def _cluster_finish(c, comp_any, min_size, max_size):
+    """rows, ids, kept cloud and result from any labelling of the components (comp_any[i]: an integer per component)"""
+    n = len(c)
+    if n == 0:
+        return (np.zeros(0, CLUSTER_ROW_DTYPE), np.zeros(0, np.uint32), c.copy(),
+                dict.fromkeys(CLUSTER_RESULT_FIELDS, 0))
+    # canonical form: the clusters numbered in the order of their lowest point index
+    _, first, inv, counts = np.unique(comp_any, return_index=True, return_inverse=True, return_counts=True)
+    by_first = np.argsort(first)
+    number = np.empty(len(first), np.int64)
+    number[by_first] = np.arange(len(first))
+    comp = number[inv.reshape(-1)]
+    first, counts = first[by_first], counts[by_first]
+    k = len(first)
+    key, _, dyn = _decode(c[:, 3])
+    order = np.argsort(comp, kind="stable")
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    rows_all = np.zeros(k, CLUSTER_ROW_DTYPE)
+    rows_all["first"] = first
+    rows_all["n_points"] = counts
+    rows_all["n_dynamic"] = np.bincount(comp, dyn, minlength=k).astype(np.uint32)
+    rows_all["n_label_out_of_range"] = np.bincount(comp, key == KEY_LABEL_OUT_OF_RANGE, minlength=k).astype(np.uint32)
+    for a in range(3):
+        keys = z_order(c[:, a])[order]
+        rows_all["min_xyz"][:, a] = z_from_order(np.minimum.reduceat(keys, starts))
+        rows_all["max_xyz"][:, a] = z_from_order(np.maximum.reduceat(keys, starts))
+    listed = (counts >= min_size) & ((max_size == 0) | (counts <= max_size))
+    lrank = np.full(k, CLUSTER_NONE, np.uint32)
+    lrank[listed] = np.arange(int(listed.sum()), dtype=np.uint32)
+    ids = lrank[comp]
+    res = {"n_points": int(n), "n_clusters": int(k), "n_listed": int(listed.sum()), "n_points_listed": int(counts[listed].sum()),
+           "n_singletons": int((counts == 1).sum()), "largest": int(counts.max())}
+    return rows_all[listed].copy(), ids, c[ids != CLUSTER_NONE].copy(), res
+
+
+def _components(n, i, j):
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    g = coo_matrix((np.ones(len(i), np.uint8), (i, j)), shape=(n, n))
+    return connected_components(g, directed=False)[1]
+
+
+def cluster(cloud, tol, min_size=1, max_size=0):
+    """Euclidean clustering of `cloud` (XYZI rows) at the tolerance tol.  cKDTree.query_pairs with a radius a hair above tol only
+    proposes the pairs; the float64 predicate decides.  Returns (rows, ids, kept, result): CLUSTER_ROW_DTYPE records of the listed
+    clusters in increasing `first`; per point the index of its cluster among the rows, or CLUSTER_NONE; the rows of the points of listed
+    clusters in the order given; and a dict with CLUSTER_RESULT_FIELDS."""
+    c, tol, min_size, max_size = _cluster_args(cloud, tol, min_size, max_size)
+    n = len(c)
+    if n == 0:
+        return _cluster_finish(c, None, min_size, max_size)
+    c64 = c[:, :3].astype(np.float64)
+    # (the tree's own float64 distances are a few ulps off the predicate's: 1e-9 relative is far above that, far below a float32 step)
+    pairs = cKDTree(c64).query_pairs(tol * (1 + 1e-9), output_type="ndarray")
+    ok = cluster_adjacent(c[pairs[:, 0], :3], c[pairs[:, 1], :3], tol)
+    return _cluster_finish(c, _components(n, pairs[ok, 0], pairs[ok, 1]), min_size, max_size)
+
+
+def cluster_brute(cloud, tol, min_size=1, max_size=0):
+    """cluster() with every pair tested by the predicate in numpy (no tree): for a few thousand points"""
+    c, tol, min_size, max_size = _cluster_args(cloud, tol, min_size, max_size)
+    n = len(c)
+    if n == 0:
+        return _cluster_finish(c, None, min_size, max_size)
+    c64 = c[:, :3].astype(np.float64)
+    t2 = np.float64(tol) * np.float64(tol)
+    ii, jj = [], []
+    for lo in range(0, n, 512):  # (row blocks: 512 x n distances at a time)
+        d = c64[lo:lo + 512, None, :] - c64[None, :, :]
+        adj = (d[:, :, 0] * d[:, :, 0] + d[:, :, 1] * d[:, :, 1]) + d[:, :, 2] * d[:, :, 2] <= t2
+        a, b = np.nonzero(adj)
+        ii.append(a + lo)
+        jj.append(b)
+    return _cluster_finish(c, _components(n, np.concatenate(ii), np.concatenate(jj)), min_size, max_size)

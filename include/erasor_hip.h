@@ -537,6 +537,54 @@ int erasor_hip_label_scans_map(erasor_hip_handle *h, const void *raw_xyzi, size_
                                uint8_t *codes, int split_code, float *split_xyzi, size_t split_cap, uint64_t *split_offsets,
                                erasor_scan_label_row *rows, erasor_scan_label_row *summary);
 
+/* ---- a cloud as connected objects: Euclidean clustering, listed and filtered by size --------------------------------------------
+ * replaces: what users of a cleaned map do on the host afterwards -- pcl::EuclideanClusterExtraction (a KD-tree and a region-growing
+ * loop) over the removed points, the left-over dynamic points or the whole map, then "drop every cluster smaller than n points"; the
+ * reference itself stops at the map.  The contract, restated on the host by erasor_amd/evalmap.py (cluster, cluster_brute), which the
+ * device equals byte for byte:
+ *   - points i and j are adjacent iff ((dx*dx + dy*dy) + dz*dz) <= tol*tol, dx = (double)x_i - (double)x_j and likewise dy, dz, all
+ *     in float64, left to right, no fused multiply-add (symmetric bit for bit);
+ *   - a cluster is a connected component of that graph; its name is `first`, the lowest point index it contains;
+ *   - a cluster is listed when min_size <= n_points and (max_size == 0 or n_points <= max_size) -- the size limits of
+ *     pcl::EuclideanClusterExtraction; min_size 0 is taken as 1;
+ *   - one row per listed cluster, in increasing `first`.
+ * There is no centroid: a float sum depends on the order of its terms, a box and a count do not, and nothing in the result depends
+ * on how the device scheduled its work.  Up to the metric at the very edge d == tol this is the partition PCL's region growing
+ * produces; PCL measures in float32, is not a dependency of this project, and the contract is not pinned against it. */
+typedef struct erasor_cluster_row {
+    uint32_t first;                 /* the lowest point index of the cluster */
+    uint32_t n_points;
+    uint32_t n_dynamic;             /* points whose uint32(intensity) & 0xFFFF is in 252..259 */
+    uint32_t n_label_out_of_range;  /* points whose intensity is not finite or outside [0, 2^32): decoded as static */
+    float min_xyz[3], max_xyz[3];   /* the box, per coordinate in float32's total order (-0.0 below +0.0), copied as bits */
+} erasor_cluster_row;
+
+typedef struct erasor_cluster_result {
+    uint64_t n_points;         /* points given */
+    uint64_t n_clusters;       /* all clusters, listed or not */
+    uint64_t n_listed;         /* rows */
+    uint64_t n_points_listed;  /* points of listed clusters: the kept cloud's rows */
+    uint64_t n_singletons;     /* clusters of one point */
+    uint64_t largest;          /* the largest n_points of any cluster */
+} erasor_cluster_result;
+
+/* The cloud (XYZI rows, on the host or on the handle's device: is_device) clustered at the tolerance tol.  All outputs are host
+ * buffers and optional.  ids (n entries): the index of point i's cluster among the rows, or 0xFFFFFFFF when its cluster is not listed.
+ * rows (cap_rows entries) and kept_xyzi (cap_points rows): the listed clusters, and the rows of all points of listed clusters in the
+ * order given, all four floats copied as bits (the residue filter); NULL asks for the counts only.  n rows always suffice for either;
+ * a buffer that does not hold the result gives ERASOR_E_CAPACITY, with res, and ids if asked for, filled first.  n == 0: zero clusters,
+ * ERASOR_OK.  Works in the evaluator's own scratch: announced nodes, tickets and the last step's clouds stay as they are.
+ * ERASOR_E_INVALID: a non-finite coordinate, tol not a finite number > 0, more than 2^30 points, res NULL.  ERASOR_E_STATE: a step in
+ * flight. */
+int erasor_hip_cluster_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, double tol, size_t min_size,
+                              size_t max_size, uint32_t *ids, erasor_cluster_row *rows, size_t cap_rows, float *kept_xyzi,
+                              size_t cap_points, erasor_cluster_result *res);
+/* the same over the handle's current map (the erasor_hip_get_map view, compacted on the device as erasor_hip_overlap_map does, never
+ * copied to the host).  ERASOR_E_STATE also: no map. */
+int erasor_hip_cluster_map(erasor_hip_handle *h, double tol, size_t min_size, size_t max_size, uint32_t *ids,
+                           erasor_cluster_row *rows, size_t cap_rows, float *kept_xyzi, size_t cap_points,
+                           erasor_cluster_result *res);
+
 /* ---- maps without labels: label a third-party map from a dense labelled one, and the static points a method lost ----------------
  * Both search the overlap report's tree in FLANN's metric, as pcl::KdTreeFLANN (K = 1) does: float32 d^2 = ((0 + dx*dx) + dy*dy) + dz*dz
  * with dx = q.x - p.x in float, exact, the lowest index on ties.  Outputs are XYZI rows in caller HOST buffers; dst == NULL asks for
