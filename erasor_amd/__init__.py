@@ -109,6 +109,41 @@ class ClusterResult(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class ScoreStats(C.Structure):
+    """erasor_score_stats (include/erasor_hip.h): a score's statistics over the points where it is finite"""
+    _fields_ = [("n_scored", C.c_uint64)] + [(k, C.c_double) for k in ("min", "median", "p90", "p99", "max")]
+
+    def as_dict(self):
+        """evalmap.score_stats' keys"""
+        return {"n_scored": int(self.n_scored), **{k: float(getattr(self, k)) for k in ("min", "median", "p90", "p99", "max")}}
+
+
+class KnnResult(C.Structure):
+    """erasor_knn_result (include/erasor_hip.h)"""
+    _fields_ = [("n_points", C.c_uint64), ("n_short", C.c_uint64), ("kth", ScoreStats), ("mean", ScoreStats)]
+
+
+class DensityFilter(C.Structure):
+    """erasor_density_filter (include/erasor_hip.h)"""
+    _fields_ = [("score", C.c_int32), ("rule", C.c_int32), ("k", C.c_uint32), ("min_neighbors", C.c_uint32), ("radius", C.c_double),
+                ("thr", C.c_double), ("mul", C.c_double)]
+
+
+class DensityResult(C.Structure):
+    """erasor_density_result (include/erasor_hip.h)"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_kept", "n_removed", "n_removed_dynamic", "n_removed_static", "n_short", "n_scored")] + [
+        (k, C.c_double) for k in ("m", "mad", "thr", "min", "median", "p90", "p99", "max")]
+
+    def as_dict(self):
+        """evalmap.density_filter's result keys"""
+        return {k: (int if t is C.c_uint64 else float)(getattr(self, k)) for k, t in self._fields_}
+
+
+DENSITY_SCORES = {"kth": 0, "mean": 1, "count": 2}  # ERASOR_DENSITY_KTH / _MEAN / _COUNT
+DENSITY_RULES = {"abs": 0, "mad": 1}                # ERASOR_DENSITY_ABS / _MAD
+KNN_NONE = 0xFFFFFFFF  # the padding of a neighbour list
+
+
 class LabelResult(C.Structure):
     """erasor_label_result (include/erasor_hip.h): label_map of a map without labels (fill_removert_intensity.cpp:24-59)"""
     _fields_ = [("n_src", C.c_uint64), ("n_out", C.c_uint64), ("n_tied", C.c_uint64), ("passthrough", C.c_uint32)]
@@ -288,7 +323,7 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "label_scans.hip.h", "cluster.hip.h", "render.hip.h", "revert_bins.hip.h",
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "render.hip.h", "revert_bins.hip.h",
                                                  "exact_sort.hip.h", "exact_sort_core.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
@@ -935,6 +970,86 @@ class Erasor:
         pts = np.ascontiguousarray(g[codes == EVAL_KEPT_DYNAMIC])
         rows, ids, _, res = self.cluster(pts, tol, min_size)
         return rows, ids, pts, res
+
+    # -- how dense the cloud is around each point: k nearest neighbours, radius counts, the outlier filters (on the host: evalmap.knn /
+    # radius_count / density_filter) --
+    def _map_n(self):
+        n = C.c_size_t(0)
+        if lib().erasor_hip_map_size(self._h, C.byref(n)) != 0:  # (no map, a step in flight: the call itself says so)
+            return 0
+        return n.value
+
+    def _knn(self, fn, head, n, k, neighbours):
+        k = int(k)
+        kk = k if 1 <= k <= 32 else 1  # (a refused k needs no buffers)
+        r = KnnResult()
+        kth = np.empty(max(n, 1), np.float64)
+        mean = np.empty(max(n, 1), np.float64)
+        ni = np.empty((max(n, 1), kk), np.uint32) if neighbours else None
+        nd = np.empty((max(n, 1), kk), np.float64) if neighbours else None
+        self._check(fn(self._h, *head, C.c_uint32(k & 0xFFFFFFFF), _p(ni) if neighbours else None, _p(nd) if neighbours else None, _p(kth), _p(mean),
+                       C.byref(r)))
+        out = {"n_points": int(r.n_points), "n_short": int(r.n_short), "k": k, "kth": kth[:n], "mean": mean[:n], "kth_stats": r.kth.as_dict(),
+               "mean_stats": r.mean.as_dict()}
+        if neighbours:
+            out["nbr_idx"] = ni[:n]
+            out["nbr_dist"] = nd[:n]
+        return out
+
+    def knn(self, cloud, k, neighbours=False):
+        """Every point's k nearest other points inside `cloud` (as for evaluate), 1 <= k <= 32, on the device (erasor_hip_knn_clouds):
+        float64 distances, neighbours ordered by (d2, index), self excluded by index.  Returns evalmap.knn's dict: n_points, n_short, k,
+        kth and mean (float64 per point; +inf where a point has fewer than k other points), kth_stats / mean_stats, and with
+        neighbours=True nbr_idx (n, k) uint32 / nbr_dist (n, k) float64, padded with KNN_NONE / +inf."""
+        kept = []
+        c = self._eval_cloud(cloud, kept)
+        return self._knn(lib().erasor_hip_knn_clouds, c, c[1].value, k, neighbours)
+
+    def knn_map(self, k, neighbours=False):
+        """knn of the handle's current map (the get_map view, never copied to the host; erasor_hip_knn_map)"""
+        return self._knn(lib().erasor_hip_knn_map, (), self._map_n(), k, neighbours)
+
+    def _radius_count(self, fn, head, n, r):
+        st = ScoreStats()
+        cnt = np.empty(max(n, 1), np.uint32)
+        self._check(fn(self._h, *head, C.c_double(r), _p(cnt), C.byref(st)))
+        return cnt[:n], st.as_dict()
+
+    def radius_count(self, cloud, r):
+        """(count, stats) as evalmap.radius_count: per point the number of other points of `cloud` within r (float64 d2 <= r*r), uint32,
+        and the counts' statistics (erasor_hip_radius_count_clouds)"""
+        kept = []
+        c = self._eval_cloud(cloud, kept)
+        return self._radius_count(lib().erasor_hip_radius_count_clouds, c, c[1].value, r)
+
+    def radius_count_map(self, r):
+        """radius_count of the handle's current map (erasor_hip_radius_count_map)"""
+        return self._radius_count(lib().erasor_hip_radius_count_map, (), self._map_n(), r)
+
+    def _density_filter(self, fn, head, n, score, k, radius, rule, thr, mul, min_neighbors, keep):
+        f = DensityFilter(DENSITY_SCORES.get(score, -1) if isinstance(score, str) else int(score),
+                          DENSITY_RULES.get(rule, -1) if isinstance(rule, str) else int(rule), int(k) & 0xFFFFFFFF, min(max(int(min_neighbors), 0), 0xFFFFFFFF),
+                          float(radius), float(thr), float(mul))
+        r = DensityResult()
+        mask = np.empty(max(n, 1), np.uint8)
+        kept = np.empty((max(n, 1), 4), np.float32) if keep else None
+        self._check(fn(self._h, *head, C.byref(f), _p(mask), _p(kept) if keep else None, C.c_size_t(n if keep else 0), C.byref(r)))
+        return mask[:n], (kept[: r.n_kept] if keep else None), r.as_dict()
+
+    def density_filter(self, cloud, score="mean", k=16, radius=0.5, rule="mad", thr=0.5, mul=2.0, min_neighbors=2, keep=True):
+        """`cloud` (as for evaluate) filtered by its density on the device (erasor_hip_density_filter_clouds).  score "kth" / "mean" (the
+        k-th neighbour's distance / the mean distance of the k nearest) with rule "abs" (keep iff score <= thr) or "mad" (thr = m + mul
+        * (1.4826 * mad) from the median and the median absolute deviation of the finite scores); score "count": keep iff at least
+        min_neighbors other points lie within radius.  score "mean" with "mad" is pcl::StatisticalOutlierRemoval's selection up to its
+        sigma rule, "count" is pcl::RadiusOutlierRemoval's.  Returns (mask, kept, result) as evalmap.density_filter does: uint8 per
+        point, the kept rows in the order given (None unless keep) and the result's dict."""
+        held = []
+        c = self._eval_cloud(cloud, held)
+        return self._density_filter(lib().erasor_hip_density_filter_clouds, c, c[1].value, score, k, radius, rule, thr, mul, min_neighbors, keep)
+
+    def density_filter_map(self, score="mean", k=16, radius=0.5, rule="mad", thr=0.5, mul=2.0, min_neighbors=2, keep=True):
+        """density_filter of the handle's current map, which stays as it is (erasor_hip_density_filter_map)"""
+        return self._density_filter(lib().erasor_hip_density_filter_map, (), self._map_n(), score, k, radius, rule, thr, mul, min_neighbors, keep)
 
     # -- maps without labels (fill_removert_intensity.cpp:24-59, compare_complement.cpp:43-75; on the host: evalmap.label_from /
     # evalmap.static_complement) --

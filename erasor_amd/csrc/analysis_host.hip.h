@@ -1,8 +1,8 @@
 // The offline analyses' host code: PR / RR evaluation (one estimate, many, by class), the overlap report, the frame check, the scans'
-// labels, the clustering, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
+// labels, the clustering, the k nearest neighbours and density filters, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
 // at its end -- one translation unit, like the kernel headers -- so it sees the handle, ensure / LAUNCH / HIPC, scan_u32, radix_sort,
 // map_to_device and voxelize_device from there; nothing of the step path depends on this file.  Kernels: evaluate.hip.h, nearest.hip.h,
-// align.hip.h, label_scans.hip.h, cluster.hip.h, render.hip.h.
+// align.hip.h, label_scans.hip.h, cluster.hip.h, knn.hip.h, render.hip.h.
 #pragma once
 
 extern "C" {
@@ -1027,6 +1027,307 @@ int erasor_hip_cluster_map(erasor_hip_handle *h, double tol, size_t min_size, si
     uint32_t n = 0;
     if ((rc = map_on_device(h, who, h->ev.map, &p, &n))) return rc;
     return cl_run(h, who, p, n, tol, min_size, max_size, ids, rows, cap_rows, kept_xyzi, cap_points, res);
+}
+
+// ---- k nearest neighbours, radius counts and the density filters on them (kernels: knn.hip.h) ----
+// Like ov_run and cl_run: the main stream, the evaluator's scratch, the tree's sort in bank 2, the grid the evaluator's at a cell edge a
+// little above the radius.  Round trips: the counters once per pass, and the host-driven select (8 passes) per score and for the MAD.
+static const double KN_NAN = std::numeric_limits<double>::quiet_NaN();
+
+static int kn_check_k(erasor_hip_handle *h, const char *who, uint32_t k) {
+    return (k < 1 || k > KN_MAX_K) ? invalid(h, who, "k must be within 1 .. 32") : ERASOR_OK;
+}
+static int kn_check_radius(erasor_hip_handle *h, const char *who, double radius) {
+    return (!(radius > 0) || !std::isfinite(radius)) ? invalid(h, who, "radius must be a finite number > 0") : ERASOR_OK;
+}
+static int kn_check_lists(erasor_hip_handle *h, const char *who, size_t n, uint32_t k, bool lists) {
+    return (lists && (uint64_t)n * k > (1ull << 30)) ? invalid(h, who, "neighbour lists need n * k <= 2^30") : ERASOR_OK;
+}
+static int kn_check_filter(erasor_hip_handle *h, const char *who, const erasor_density_filter *f, const void *res) {
+    if (!res) return invalid(h, who, "res is NULL");
+    if (!f) return invalid(h, who, "filter is NULL");
+    if (f->score != ERASOR_DENSITY_KTH && f->score != ERASOR_DENSITY_MEAN && f->score != ERASOR_DENSITY_COUNT)
+        return invalid(h, who, "unknown score (ERASOR_DENSITY_KTH, _MEAN or _COUNT)");
+    if (f->rule != ERASOR_DENSITY_ABS && f->rule != ERASOR_DENSITY_MAD) return invalid(h, who, "unknown rule (ERASOR_DENSITY_ABS or _MAD)");
+    if (f->score == ERASOR_DENSITY_COUNT) return kn_check_radius(h, who, f->radius);
+    int rc = kn_check_k(h, who, f->k);
+    if (rc) return rc;
+    if (f->rule == ERASOR_DENSITY_ABS && (!(f->thr >= 0) || !std::isfinite(f->thr))) return invalid(h, who, "thr must be a finite number >= 0");
+    if (f->rule == ERASOR_DENSITY_MAD && (!(f->mul >= 0) || !std::isfinite(f->mul))) return invalid(h, who, "mul must be a finite number >= 0");
+    return ERASOR_OK;
+}
+
+// the counters at their identities
+static int kn_reset(erasor_hip_handle *h) {
+    auto &E = h->ev;
+    if (ensure(h, E.kn_ctr, KN_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256)) return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.kn_ctr.p, 0, KN_NCTR * sizeof(unsigned long long), h->stream));
+    HIPC(h, hipMemsetAsync(E.kn_ctr.p + KN_C_KTH_MIN, 0xFF, sizeof(unsigned long long), h->stream));
+    HIPC(h, hipMemsetAsync(E.kn_ctr.p + KN_C_MEAN_MIN, 0xFF, sizeof(unsigned long long), h->stream));
+    return ERASOR_OK;
+}
+static int kn_counters(erasor_hip_handle *h, unsigned long long c[KN_NCTR]) {
+    return d2h(h, c, h->ev.kn_ctr.p, KN_NCTR * sizeof(unsigned long long));
+}
+
+// both knn scores of pts[0 .. n) (n > 0) into E.kn_kth / E.kn_mean, with `lists` the neighbour lists into E.kn_ni / E.kn_nd; the counters in c
+static int kn_search(erasor_hip_handle *h, const char *who, const float4 *pts, uint32_t n, uint32_t k, bool lists, unsigned long long c[KN_NCTR]) {
+    auto &E = h->ev;
+    uint32_t P = 1;
+    int rc = nn_pad(h, n, &P, who, "cloud");
+    if (rc || (rc = kn_reset(h))) return rc;
+    const size_t n1 = (size_t)n + 1;
+    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.kn_kth, n1) || ensure(h, E.kn_mean, n1) ||
+        (lists && (ensure(h, E.kn_ni, (size_t)n * k + 1) || ensure(h, E.kn_nd, (size_t)n * k + 1))))
+        return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if ((rc = nn_tree(h, pts, n, P, who, "point(s)"))) return rc;
+    uint32_t *ni = lists ? E.kn_ni.p : nullptr;
+    double *nd = lists ? E.kn_nd.p : nullptr;
+    const uint32_t g = cdiv(n, KN_QBLOCK);
+#define KN_QUERY(KC)                                                                                                                             \
+    LAUNCH(h, h->stream, "kn_query", k_kn_query<KC>, g, KN_QBLOCK, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, n, (const float4 *)E.nn_lo.p, \
+           (const float4 *)E.nn_hi.p, P, k, E.kn_kth.p, E.kn_mean.p, ni, nd, E.kn_ctr.p)
+    if (k <= 8) KN_QUERY(8);
+    else if (k <= 16) KN_QUERY(16);
+    else KN_QUERY(32);
+#undef KN_QUERY
+    return kn_counters(h, c);
+}
+
+// the radius counts of pts[0 .. n) (n > 0) into E.kn_cnt, and as float64 bit patterns into E.kn_kth; the counters in c
+static int kn_count(erasor_hip_handle *h, const char *who, const float4 *pts, uint32_t n, double radius, unsigned long long c[KN_NCTR]) {
+    auto &E = h->ev;
+    uint32_t nb = 1024;  // buckets: ev_run's (a power of two >= the cloud's size)
+    while (nb < n) nb <<= 1;
+    const size_t n1 = (size_t)n + 1;
+    int rc = kn_reset(h);
+    if (rc) return rc;
+    if (ensure(h, E.ctr, EV_NCTR) || ensure(h, E.cnt, (size_t)nb + 1) || ensure(h, E.pl, (size_t)nb + 1) || ensure(h, E.tops, nb / 1024 + 4) ||
+        ensure(h, E.bkt, n1) || ensure(h, E.pts, n1) || ensure(h, E.idx, n1) || ensure(h, E.kn_cnt, n1) || ensure(h, E.kn_kth, n1))
+        return ERASOR_E_NO_DEVICE;
+    const double cell = radius * CL_CELL_MARGIN, r2 = radius * radius;
+    const uint32_t g = cdiv(n, 256);
+    HIPC(h, hipMemsetAsync(E.ctr.p, 0, EV_NCTR * sizeof(unsigned long long), h->stream));
+    HIPC(h, hipMemsetAsync(E.cnt.p, 0, ((size_t)nb + 1) * sizeof(uint32_t), h->stream));
+    LAUNCH(h, h->stream, "kn_index", k_ev_hist, g, 256, pts, n, cell, nb - 1, E.bkt.p, E.cnt.p, E.ctr.p);
+    scan_u32(h, h->stream, E.cnt.p, E.pl.p, E.tops.p, nb + 1, nb + 1, nullptr, nullptr, "kn_index");
+    LAUNCH(h, h->stream, "kn_index", k_ev_offsets, cdiv(nb + 1, 256), 256, (const uint32_t *)E.pl.p, (const uint32_t *)E.tops.p, nb + 1, E.cnt.p, E.pl.p);
+    LAUNCH(h, h->stream, "kn_index", k_ev_scatter, g, 256, pts, n, (const uint32_t *)E.bkt.p, E.pl.p, E.pts.p, E.idx.p);
+    unsigned long long ec[EV_NCTR];
+    if ((rc = d2h(h, ec, E.ctr.p, sizeof(ec)))) return rc;
+    if (ec[EV_NON_FINITE]) return invalid(h, who, "non-finite coordinate (NaN / Inf) in " + std::to_string(ec[EV_NON_FINITE]) + " point(s)");
+    LAUNCH(h, h->stream, "kn_count", k_kn_count, g, 256, pts, n, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p, (const uint32_t *)E.cnt.p, nb - 1, cell, r2,
+           E.kn_cnt.p, E.kn_kth.p, E.kn_ctr.p);
+    return kn_counters(h, c);
+}
+
+static void kn_no_stats(erasor_score_stats *s) {
+    s->n_scored = 0;
+    s->min = s->median = s->p90 = s->p99 = s->max = KN_NAN;
+}
+// the statistics of the n_scored finite scores among bits[0 .. n): infinite scores lie above every rank
+static int kn_stats(erasor_hip_handle *h, const unsigned long long *bits, uint32_t n, uint64_t n_scored, unsigned long long min_bits,
+                    unsigned long long max_bits, erasor_score_stats *s) {
+    kn_no_stats(s);
+    if (!n_scored) return ERASOR_OK;
+    uint64_t rk[OV_SEL_MAX];
+    double v[OV_SEL_MAX] = {}, g90 = 0, g99 = 0;
+    ov_ranks(n_scored, rk, &g90, &g99);
+    const int rc = ov_select(h, bits, n, rk, v);
+    if (rc) return rc;
+    s->n_scored = n_scored;
+    memcpy(&s->min, &min_bits, sizeof(double));
+    memcpy(&s->max, &max_bits, sizeof(double));
+    s->median = (n_scored % 2) ? v[0] : (v[0] + v[1]) / 2.0;
+    s->p90 = ov_lerp(v[2], v[3], g90);
+    s->p99 = ov_lerp(v[4], v[5], g99);
+    return ERASOR_OK;
+}
+
+static int kn_run(erasor_hip_handle *h, const char *who, const float4 *pts, uint32_t n, uint32_t k, uint32_t *nbr_idx, double *nbr_dist, double *kth,
+                  double *mean, erasor_knn_result *res) {
+    auto &E = h->ev;
+    erasor_knn_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_points = n;
+    kn_no_stats(&r.kth);
+    kn_no_stats(&r.mean);
+    if (!n) {
+        *res = r;
+        return ERASOR_OK;
+    }
+    unsigned long long c[KN_NCTR];
+    int rc = kn_search(h, who, pts, n, k, nbr_idx || nbr_dist, c);
+    if (rc) return rc;
+    r.n_short = c[KN_C_SHORT];
+    const uint64_t n_scored = n - r.n_short;
+    if ((rc = kn_stats(h, E.kn_kth.p, n, n_scored, c[KN_C_KTH_MIN], c[KN_C_KTH_MAX], &r.kth)) ||
+        (rc = kn_stats(h, E.kn_mean.p, n, n_scored, c[KN_C_MEAN_MIN], c[KN_C_MEAN_MAX], &r.mean)))
+        return rc;
+    *res = r;
+    if (nbr_idx && (rc = d2h(h, nbr_idx, E.kn_ni.p, (size_t)n * k * sizeof(uint32_t)))) return rc;
+    if (nbr_dist && (rc = d2h(h, nbr_dist, E.kn_nd.p, (size_t)n * k * sizeof(double)))) return rc;
+    if (kth && (rc = d2h(h, kth, E.kn_kth.p, (size_t)n * sizeof(double)))) return rc;
+    if (mean && (rc = d2h(h, mean, E.kn_mean.p, (size_t)n * sizeof(double)))) return rc;
+    return ERASOR_OK;
+}
+
+static int rc_run(erasor_hip_handle *h, const char *who, const float4 *pts, uint32_t n, double radius, uint32_t *count, erasor_score_stats *res) {
+    kn_no_stats(res);
+    if (!n) return ERASOR_OK;
+    unsigned long long c[KN_NCTR];
+    int rc = kn_count(h, who, pts, n, radius, c);
+    if (rc || (rc = kn_stats(h, h->ev.kn_kth.p, n, n, c[KN_C_KTH_MIN], c[KN_C_KTH_MAX], res))) return rc;
+    return count ? d2h(h, count, h->ev.kn_cnt.p, (size_t)n * sizeof(uint32_t)) : ERASOR_OK;
+}
+
+static int df_run(erasor_hip_handle *h, const char *who, const float4 *pts, uint32_t n, const erasor_density_filter &f, uint8_t *keep_mask,
+                  float *kept_xyzi, size_t cap_points, erasor_density_result *res) {
+    auto &E = h->ev;
+    erasor_density_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_points = n;
+    r.m = r.mad = r.thr = r.min = r.median = r.p90 = r.p99 = r.max = KN_NAN;
+    const bool by_count = f.score == ERASOR_DENSITY_COUNT, mad = !by_count && f.rule == ERASOR_DENSITY_MAD;
+    if (by_count) r.thr = (double)f.min_neighbors;
+    else if (!mad) r.thr = f.thr;
+    if (!n) {
+        *res = r;
+        return ERASOR_OK;
+    }
+    unsigned long long c[KN_NCTR];
+    int rc = by_count ? kn_count(h, who, pts, n, f.radius, c) : kn_search(h, who, pts, n, f.k, false, c);
+    if (rc) return rc;
+    const bool use_mean = f.score == ERASOR_DENSITY_MEAN;
+    const unsigned long long *score = use_mean ? E.kn_mean.p : E.kn_kth.p;
+    r.n_short = by_count ? 0 : c[KN_C_SHORT];
+    erasor_score_stats st;
+    if ((rc = kn_stats(h, score, n, n - r.n_short, c[use_mean ? KN_C_MEAN_MIN : KN_C_KTH_MIN], c[use_mean ? KN_C_MEAN_MAX : KN_C_KTH_MAX], &st))) return rc;
+    r.n_scored = st.n_scored;
+    r.min = st.min, r.median = st.median, r.p90 = st.p90, r.p99 = st.p99, r.max = st.max;
+    const size_t n1 = (size_t)n + 1;
+    const uint32_t g = cdiv(n, 256);
+    if (mad && st.n_scored) {
+        // the median absolute deviation: |s - m| over the scored points, and a second select for its median
+        if (ensure(h, E.kn_dev, n1)) return ERASOR_E_NO_DEVICE;
+        r.m = st.median;
+        LAUNCH(h, h->stream, "kn_mad", k_kn_absdev, g, 256, score, n, r.m, E.kn_dev.p);
+        const uint64_t lo = (st.n_scored - 1) / 2, hi = st.n_scored / 2;
+        const uint64_t rk[OV_SEL_MAX] = {lo, hi, lo, hi, lo, hi};
+        double v[OV_SEL_MAX] = {};
+        if ((rc = ov_select(h, E.kn_dev.p, n, rk, v))) return rc;
+        r.mad = (st.n_scored % 2) ? v[0] : (v[0] + v[1]) / 2.0;
+        const double scaled = 1.4826 * r.mad;
+        r.thr = r.m + f.mul * scaled;
+    }
+    if (ensure(h, E.fm_flag, n1) || ensure(h, E.fm_pl, n1) || ensure(h, E.fm_tops, n / 1024 + 4) || ensure(h, E.kn_mask, n1)) return ERASOR_E_NO_DEVICE;
+    LAUNCH(h, h->stream, "kn_keep", k_kn_keep, g, 256, pts, n, score, (const uint32_t *)E.kn_cnt.p, by_count ? 1u : 0u, r.thr, f.min_neighbors, E.fm_flag.p,
+           E.kn_mask.p, E.kn_ctr.p);
+    if ((rc = kn_counters(h, c))) return rc;
+    r.n_kept = c[KN_C_KEPT];
+    r.n_removed = n - r.n_kept;
+    r.n_removed_dynamic = c[KN_C_REMOVED_DYNAMIC];
+    r.n_removed_static = c[KN_C_REMOVED_STATIC];
+    *res = r;
+    if (keep_mask && (rc = d2h(h, keep_mask, E.kn_mask.p, n))) return rc;
+    if (kept_xyzi && r.n_kept > cap_points) return ERASOR_E_CAPACITY;
+    if (kept_xyzi && r.n_kept) {
+        // the kept rows, as given: the stable compaction over the keep flags
+        if (ensure(h, E.fm_out, n1)) return ERASOR_E_NO_DEVICE;
+        scan_u32(h, h->stream, E.fm_flag.p, E.fm_pl.p, E.fm_tops.p, n, n, nullptr, nullptr, "kn_keep");
+        LAUNCH(h, h->stream, "kn_keep", k_f_compact, g, 256, pts, n, (const uint32_t *)E.fm_flag.p, (const uint32_t *)E.fm_pl.p, (const uint32_t *)E.fm_tops.p,
+               E.fm_out.p);
+        return d2h(h, kept_xyzi, E.fm_out.p, (size_t)r.n_kept * sizeof(float4));
+    }
+    return ERASOR_OK;
+}
+
+// the caller's cloud (checked, brought in through h->ev.gt) or the handle's map (h->ev.map) on the device
+static int kn_cloud(erasor_hip_handle *h, const char *who, const void *xyzi, size_t n, int is_device, const float4 **p) {
+    int rc = check_cloud(h, who, BAD_CLOUD, xyzi, n);
+    if (rc || !n) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    return ev_input(h, xyzi, n, is_device, h->ev.gt, p);
+}
+
+int erasor_hip_knn_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, uint32_t k, uint32_t *nbr_idx, double *nbr_dist, double *kth,
+                          double *mean, erasor_knn_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_knn_clouds";
+    if (!res) return invalid(h, who, "res is NULL");
+    const float4 *p = nullptr;
+    int rc = kn_check_k(h, who, k);
+    if (rc || (rc = check_cloud(h, who, BAD_CLOUD, xyzi, n)) || (rc = kn_check_lists(h, who, n, k, nbr_idx || nbr_dist)) ||
+        (rc = kn_cloud(h, who, xyzi, n, is_device, &p)))
+        return rc;
+    return kn_run(h, who, p, (uint32_t)n, k, nbr_idx, nbr_dist, kth, mean, res);
+}
+
+int erasor_hip_knn_map(erasor_hip_handle *h, uint32_t k, uint32_t *nbr_idx, double *nbr_dist, double *kth, double *mean, erasor_knn_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_knn_map";
+    if (!res) return invalid(h, who, "res is NULL");
+    int rc = kn_check_k(h, who, k);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    uint32_t n = 0;
+    if ((rc = map_on_device(h, who, h->ev.map, &p, &n)) || (rc = kn_check_lists(h, who, n, k, nbr_idx || nbr_dist))) return rc;
+    return kn_run(h, who, p, n, k, nbr_idx, nbr_dist, kth, mean, res);
+}
+
+int erasor_hip_radius_count_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, double radius, uint32_t *count,
+                                   erasor_score_stats *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_radius_count_clouds";
+    if (!res) return invalid(h, who, "res is NULL");
+    const float4 *p = nullptr;
+    int rc = kn_check_radius(h, who, radius);
+    if (rc || (rc = kn_cloud(h, who, xyzi, n, is_device, &p))) return rc;
+    return rc_run(h, who, p, (uint32_t)n, radius, count, res);
+}
+
+int erasor_hip_radius_count_map(erasor_hip_handle *h, double radius, uint32_t *count, erasor_score_stats *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_radius_count_map";
+    if (!res) return invalid(h, who, "res is NULL");
+    int rc = kn_check_radius(h, who, radius);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    uint32_t n = 0;
+    if ((rc = map_on_device(h, who, h->ev.map, &p, &n))) return rc;
+    return rc_run(h, who, p, n, radius, count, res);
+}
+
+int erasor_hip_density_filter_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, const erasor_density_filter *filter,
+                                     uint8_t *keep_mask, float *kept_xyzi, size_t cap_points, erasor_density_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_density_filter_clouds";
+    const float4 *p = nullptr;
+    int rc = kn_check_filter(h, who, filter, res);
+    if (rc || (rc = kn_cloud(h, who, xyzi, n, is_device, &p))) return rc;
+    return df_run(h, who, p, (uint32_t)n, *filter, keep_mask, kept_xyzi, cap_points, res);
+}
+
+int erasor_hip_density_filter_map(erasor_hip_handle *h, const erasor_density_filter *filter, uint8_t *keep_mask, float *kept_xyzi, size_t cap_points,
+                                  erasor_density_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_density_filter_map";
+    int rc = kn_check_filter(h, who, filter, res);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    uint32_t n = 0;
+    if ((rc = map_on_device(h, who, h->ev.map, &p, &n))) return rc;
+    return df_run(h, who, p, n, *filter, keep_mask, kept_xyzi, cap_points, res);
 }
 
 // ---- label_map (fill_removert_intensity.cpp:24-59, compare_map.cpp:77-110) and calc_complement (compare_complement.cpp:43-75): the

@@ -39,6 +39,7 @@
 #include "align.hip.h"
 #include "label_scans.hip.h"
 #include "cluster.hip.h"
+#include "knn.hip.h"
 #include "render.hip.h"
 
 using namespace ek;
@@ -373,6 +374,13 @@ struct erasor_hip_handle {
         // roots' ranks, the rows, the ids and the counters (the grid: cnt, pl, tops, bkt, pts, idx above; flags and kept cloud: fm_*)
         DBuf<uint32_t> cl_parent, cl_root, cl_tab, cl_rank, cl_rows, cl_ids;
         DBuf<unsigned long long> cl_ctr;
+        // k nearest neighbours, radius counts and the density filters (erasor_hip_knn_* / _radius_count_* / _density_filter_*): the two
+        // scores' bit patterns, the absolute deviations, the neighbour lists, the counts, the keep mask and the counters (the tree: nn_*
+        // above; the grid: cnt, pl, tops, bkt, pts, idx; flags and kept cloud: fm_*)
+        DBuf<unsigned long long> kn_kth, kn_mean, kn_dev, kn_ctr;
+        DBuf<uint32_t> kn_ni, kn_cnt;
+        DBuf<double> kn_nd;
+        DBuf<uint8_t> kn_mask;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
 #ifdef ERASOR_HIP_TEST_HOOKS
@@ -1132,6 +1140,8 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->ev.rd_bb); release(h->ev.rd_rec); release(h->ev.rd_srt); release(h->ev.rd_ctr); release(h->ev.rd_zb); release(h->ev.rd_img);
     release(h->ev.cl_parent); release(h->ev.cl_root); release(h->ev.cl_tab); release(h->ev.cl_rank); release(h->ev.cl_rows); release(h->ev.cl_ids);
     release(h->ev.cl_ctr);
+    release(h->ev.kn_kth); release(h->ev.kn_mean); release(h->ev.kn_dev); release(h->ev.kn_ctr); release(h->ev.kn_ni); release(h->ev.kn_cnt);
+    release(h->ev.kn_nd); release(h->ev.kn_mask);
     for (int k = 0; k < NSIDE; ++k) {
         if (h->q[k].ev_keys) (void)hipEventDestroy(h->q[k].ev_keys);
         if (h->q[k].ev_done) (void)hipEventDestroy(h->q[k].ev_done);

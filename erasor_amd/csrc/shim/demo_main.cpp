@@ -590,6 +590,85 @@ static int residue_mode(int argc, char **argv) {
     print_clusters(r, rows);
     return 0;
 }
+// ---- how dense a cloud is around each point, and the outlier filters on that (erasor_hip_knn_clouds, erasor_hip_density_filter_clouds) ----
+static void print_stats(const char *name, double mn, double median, double p90, double p99, double mx) {
+    printf("  %s: min=%.9g  median=%.9g  p90=%.9g  p99=%.9g  max=%.9g\n", name, mn, median, p90, p99, mx);
+}
+// --denoise <in.pcd> <out.pcd> sor <k> <mul> | ror <radius> <min_neighbors> | kth <k> <thr>: the cloud without its stragglers, saved as a
+// binary PCD.  sor: the mean distance to the k nearest neighbours against median + mul * 1.4826 * MAD (pcl::StatisticalOutlierRemoval's
+// selection, with a median and a MAD where PCL has a mean and a sigma); ror: at least min_neighbors other points within radius
+// (pcl::RadiusOutlierRemoval); kth: the k-th neighbour no farther than thr.
+static int denoise_mode(int argc, char **argv) {
+    if (argc != 7) return 2;
+    const std::string how = argv[4];
+    erasor_density_filter f;
+    memset(&f, 0, sizeof(f));
+    double a = 0, b = 0;
+    size_t cnt = 0;
+    if (how == "sor" || how == "kth") {
+        if (!parse_count(argv[5], &cnt) || cnt < 1 || cnt > 32 || !parse_number(argv[6], &b) || b < 0) return 2;
+        f.k = (uint32_t)cnt;
+        f.score = how == "sor" ? ERASOR_DENSITY_MEAN : ERASOR_DENSITY_KTH;
+        f.rule = how == "sor" ? ERASOR_DENSITY_MAD : ERASOR_DENSITY_ABS;
+        (how == "sor" ? f.mul : f.thr) = b;
+    } else if (how == "ror") {
+        if (!parse_number(argv[5], &a) || !(a > 0) || !parse_count(argv[6], &cnt)) return 2;
+        f.score = ERASOR_DENSITY_COUNT;
+        f.rule = ERASOR_DENSITY_ABS;
+        f.radius = a;
+        f.min_neighbors = (uint32_t)cnt;
+    } else {
+        return 2;
+    }
+    std::vector<float> cloud;
+    if (!load_cloud_xyzi(argv[2], cloud)) {
+        fprintf(stderr, "cannot read %s\n", argv[2]);
+        return 3;
+    }
+    erasor_hip_handle *h = render_handle();
+    if (!h) return 1;
+    const size_t n = cloud.size() / 4;
+    std::vector<float> kept(std::max<size_t>(n, 1) * 4, 0.f);
+    erasor_density_result r;
+    const int rc = erasor_hip_density_filter_clouds(h, cloud.data(), n, 0, &f, nullptr, kept.data(), n, &r);
+    if (rc) return render_fail(h, "density_filter", rc);
+    erasor_hip_destroy(h);
+    printf("denoise: n=%llu  kept=%llu  removed=%llu (dynamic %llu, static %llu)  short=%llu  scored=%llu\n", (unsigned long long)r.n_points,
+           (unsigned long long)r.n_kept, (unsigned long long)r.n_removed, (unsigned long long)r.n_removed_dynamic, (unsigned long long)r.n_removed_static,
+           (unsigned long long)r.n_short, (unsigned long long)r.n_scored);
+    print_stats(how == "sor" ? "mean" : (how == "ror" ? "count" : "kth"), r.min, r.median, r.p90, r.p99, r.max);
+    printf("  m=%.9g  mad=%.9g  thr=%.9g\n", r.m, r.mad, r.thr);
+    pcl::PointCloud<pcl::PointXYZI> out;
+    rows_to_cloud(kept, r.n_kept, out);
+    if (erasor_utils::save_pcd_binary(argv[3], out) != 0) {
+        fprintf(stderr, "cannot write %s\n", argv[3]);
+        return 1;
+    }
+    printf("saved %s\n", argv[3]);
+    return 0;
+}
+// --density <cloud.pcd> <k>: the statistics of the k-th neighbour's distance and of the mean distance to the k nearest, nothing written
+static int density_mode(int argc, char **argv) {
+    if (argc != 4) return 2;
+    size_t k = 0;
+    if (!parse_count(argv[3], &k) || k < 1 || k > 32) return 2;
+    std::vector<float> cloud;
+    if (!load_cloud_xyzi(argv[2], cloud)) {
+        fprintf(stderr, "cannot read %s\n", argv[2]);
+        return 3;
+    }
+    erasor_hip_handle *h = render_handle();
+    if (!h) return 1;
+    erasor_knn_result r;
+    const int rc = erasor_hip_knn_clouds(h, cloud.data(), cloud.size() / 4, 0, (uint32_t)k, nullptr, nullptr, nullptr, nullptr, &r);
+    if (rc) return render_fail(h, "knn", rc);
+    erasor_hip_destroy(h);
+    printf("density: n=%llu  k=%u  short=%llu  scored=%llu\n", (unsigned long long)r.n_points, (unsigned)k, (unsigned long long)r.n_short,
+           (unsigned long long)r.kth.n_scored);
+    print_stats("kth", r.kth.min, r.kth.median, r.kth.p90, r.kth.p99, r.kth.max);
+    print_stats("mean", r.mean.min, r.mean.median, r.mean.p90, r.mean.p99, r.mean.max);
+    return 0;
+}
 // --eval-many <voxelsize> <voxel_leaf> <gt> <est1> [<est2> ...]: --eval's row for every estimate against one ground truth, from ONE
 // erasor_hip_evaluate_many call (compare_map.cpp's use: several methods' maps against one GT)
 static int eval_many_mode(int argc, char **argv) {
@@ -1517,6 +1596,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && (std::string(argv[1]) == "--denoise" || std::string(argv[1]) == "--density")) {
+        try {
+            return std::string(argv[1]) == "--denoise" ? denoise_mode(argc, argv) : density_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--analyze") {
         try {
             return analyze_mode(argc, argv);
@@ -1559,8 +1646,10 @@ int main(int argc, char **argv) {
                 "       %s --eval-many <voxelsize> <voxel_leaf> <gt> <est1> [<est2> ...]\n"
                 "       %s --label-scans <rosparam.yaml> <static.pcd> <raw.pcd|-> <out_dir> [n_frames] [tau]\n"
                 "       %s --clusters <cloud.pcd> <tol> [min_size] [max_size] [kept_out.pcd]\n"
-                "       %s --residue <gt> <est> [tol] [voxelsize] [voxel_leaf]\n",
-                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                "       %s --residue <gt> <est> [tol] [voxelsize] [voxel_leaf]\n"
+                "       %s --denoise <in.pcd> <out.pcd> sor <k> <mul> | ror <radius> <min_neighbors> | kth <k> <thr>\n"
+                "       %s --density <cloud.pcd> <k>\n",
+                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

@@ -21,6 +21,9 @@ evaluate_by_class: the same decision per GT point, counted per semantic class an
 
 cluster / cluster_brute: Euclidean clustering of a cloud, the host restatement of Erasor.cluster (include/erasor_hip.h,
 erasor_cluster_row): connected components of "within tol", listed and filtered by size, with counts and boxes.
+
+knn / radius_count / density_filter (and knn_brute, radius_count_brute): every point's k nearest neighbours inside its own cloud, the
+points within a radius of it, and the outlier filters on both -- the host restatement of Erasor.knn / radius_count / density_filter.
 """
 import numpy as np
 from scipy.spatial import cKDTree
@@ -658,3 +661,220 @@ def cluster_brute(cloud, tol, min_size=1, max_size=0):
         ii.append(a + lo)
         jj.append(b)
     return _cluster_finish(c, _components(n, np.concatenate(ii), np.concatenate(jj)), min_size, max_size)
+
+
+# ---- k nearest neighbours, radius counts and the density filters (include/erasor_hip.h: erasor_hip_knn_* / _radius_count_* /
+# _density_filter_*; kernels: erasor_amd/csrc/knn.hip.h), on the host ---------------------------------------------------------------
+# The host restatement of the device's contract.  Distance: d2 = (ex*ex + ey*ey) + ez*ez in float64 with ex = float64(x_i) - float64(x_j),
+# d = sqrt(d2).  The neighbour order of point i: every j != i by (d2, j) ascending; self is excluded by index, so an identical point at
+# another index is a neighbour at distance 0.  A point with fewer than k other points gets KNN_NONE / +inf padding and infinite scores.
+KNN_NONE = 0xFFFFFFFF
+KNN_MAX_K = 32
+SCORE_STATS_FIELDS = ("n_scored", "min", "median", "p90", "p99", "max")
+DENSITY_SCORES = {"kth": 0, "mean": 1, "count": 2}  # ERASOR_DENSITY_KTH / _MEAN / _COUNT
+DENSITY_RULES = {"abs": 0, "mad": 1}                # ERASOR_DENSITY_ABS / _MAD
+DENSITY_RESULT_FIELDS = ("n_points", "n_kept", "n_removed", "n_removed_dynamic", "n_removed_static", "n_short", "n_scored", "m", "mad", "thr",
+                         "min", "median", "p90", "p99", "max")
+
+
+def _knn_cloud(cloud, who):
+    c = np.ascontiguousarray(np.asarray(cloud, np.float32).reshape(-1, 4))
+    if len(c) > 1 << 30:
+        raise ValueError(who + ": more than 2^30 points")
+    if not np.isfinite(c[:, :3]).all():
+        raise ValueError(who + ": non-finite coordinate")
+    return c
+
+
+def _check_k(k, who):
+    if not (isinstance(k, (int, np.integer)) and 1 <= k <= KNN_MAX_K):
+        raise ValueError(who + ": k must be within 1 .. 32")
+    return int(k)
+
+
+def _check_radius(r, who):
+    if not (np.isfinite(r) and r > 0):
+        raise ValueError(who + ": radius must be a finite number > 0")
+    return float(r)
+
+
+def pair_d2(a64, b64):
+    """the squared distance, operation by operation: float64 (..., 3) arrays that broadcast"""
+    e = a64 - b64
+    return (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
+
+
+def score_stats(score):
+    """min / median / p90 / p99 / max over the finite scores, as overlap() takes them; NaN when there are none"""
+    s = np.asarray(score, np.float64).reshape(-1)
+    f = s[np.isfinite(s)]
+    if len(f) == 0:
+        nan = float("nan")
+        return {"n_scored": 0, "min": nan, "median": nan, "p90": nan, "p99": nan, "max": nan}
+    return {"n_scored": int(len(f)), "min": float(f.min()), "median": float(np.median(f)), "p90": float(np.percentile(f, 90)),
+            "p99": float(np.percentile(f, 99)), "max": float(f.max())}
+
+
+def _knn_rows_brute(c64, rows, k):
+    """(idx, d2) of the first k neighbours of every point in `rows`, every pair by the predicate: (len(rows), k), padded"""
+    n = len(c64)
+    idx = np.full((len(rows), k), KNN_NONE, np.uint32)
+    d2o = np.full((len(rows), k), np.inf)
+    m = min(k, n - 1)
+    for lo in range(0, len(rows), 256):  # (row blocks: 256 x n distances at a time)
+        r = rows[lo:lo + 256]
+        d2 = pair_d2(c64[r, None, :], c64[None, :, :])
+        d2[np.arange(len(r)), r] = np.inf  # (self, by index: no real d2 is infinite, so it sorts last)
+        order = np.argsort(d2, axis=1, kind="stable")[:, :m]  # (stable: equal d2 in index order)
+        idx[lo:lo + len(r), :m] = order
+        d2o[lo:lo + len(r), :m] = np.take_along_axis(d2, order, 1)
+    return idx, d2o
+
+
+def _knn_finish(c, k, idx, d2, neighbours):
+    n = len(c)
+    d = np.sqrt(d2)
+    total = np.zeros(n)
+    for e in range(k):  # (((0.0 + d_0) + d_1) + ...): in list order
+        total = total + d[:, e]
+    short = n - 1 < k
+    kth = d[:, k - 1].copy() if n else np.zeros(0)
+    mean = total / np.float64(k)
+    out = {"n_points": int(n), "n_short": int(n if short else 0), "k": int(k), "kth": kth, "mean": mean, "kth_stats": score_stats(kth),
+           "mean_stats": score_stats(mean)}
+    if neighbours:
+        out["nbr_idx"] = idx
+        out["nbr_dist"] = d
+    return out
+
+
+def knn_brute(cloud, k, neighbours=False):
+    """knn() with every pair tested by the predicate in numpy (no tree): for a few thousand points"""
+    c = _knn_cloud(cloud, "knn")
+    k = _check_k(k, "knn")
+    idx, d2 = _knn_rows_brute(c[:, :3].astype(np.float64), np.arange(len(c)), k)
+    return _knn_finish(c, k, idx, d2, neighbours)
+
+
+def knn(cloud, k, neighbours=False):
+    """Every point's k nearest other points inside `cloud` (XYZI rows), 1 <= k <= 32.  cKDTree.query(k + 10) only proposes candidates;
+    they are re-ranked by (d2, j) with the float64 predicate, and a row whose last candidate is not strictly beyond its k-th neighbour
+    (ties, duplicates) is redone over every pair.  Returns a dict: n_points, n_short, k, kth and mean (float64 per point), kth_stats and
+    mean_stats (SCORE_STATS_FIELDS), and with neighbours=True nbr_idx (n, k) uint32 / nbr_dist (n, k) float64, padded with KNN_NONE /
+    +inf where a point has fewer than k other points."""
+    c = _knn_cloud(cloud, "knn")
+    k = _check_k(k, "knn")
+    n = len(c)
+    c64 = c[:, :3].astype(np.float64)
+    kk = min(k + 10, n)
+    if n - 1 <= k or kk == n:  # (every other point is a candidate anyway)
+        idx, d2 = _knn_rows_brute(c64, np.arange(n), k)
+        return _knn_finish(c, k, idx, d2, neighbours)
+    dist, cand = cKDTree(c64).query(c64, k=kk, workers=-1)
+    me = np.arange(n)[:, None]
+    d2 = pair_d2(c64[:, None, :], c64[cand])
+    d2[cand == me] = np.inf
+    cand = np.where(cand == me, KNN_NONE, cand).astype(np.int64)
+    by_j = np.argsort(cand, axis=1, kind="stable")
+    cand, d2 = np.take_along_axis(cand, by_j, 1), np.take_along_axis(d2, by_j, 1)
+    by_d = np.argsort(d2, axis=1, kind="stable")
+    cand, d2 = np.take_along_axis(cand, by_d, 1)[:, :k], np.take_along_axis(d2, by_d, 1)[:, :k]
+    # every point outside the candidates is at least as far as the tree's last one; its own float64 distances are a few ulps off the
+    # predicate's, 1e-9 relative is far above that
+    far = dist[:, -1] * dist[:, -1] * (1 - 1e-9)
+    redo = np.flatnonzero(~(d2[:, k - 1] < far))
+    idx = cand.astype(np.uint32)
+    if len(redo):
+        idx[redo], d2[redo] = _knn_rows_brute(c64, redo, k)
+    return _knn_finish(c, k, idx, d2, neighbours)
+
+
+def radius_count_brute(cloud, r):
+    """radius_count() with every pair tested by the predicate in numpy (no tree)"""
+    c = _knn_cloud(cloud, "radius_count")
+    r = _check_radius(r, "radius_count")
+    c64 = c[:, :3].astype(np.float64)
+    r2 = np.float64(r) * np.float64(r)
+    cnt = np.zeros(len(c), np.uint32)
+    for lo in range(0, len(c), 256):
+        within = pair_d2(c64[lo:lo + 256, None, :], c64[None, :, :]) <= r2
+        cnt[lo:lo + 256] = within.sum(1) - 1  # (self, by index: its d2 is 0)
+    return cnt, score_stats(cnt)
+
+
+def radius_count(cloud, r):
+    """(count, stats): per point the number of other points with d2 <= r*r (uint32), and the counts' SCORE_STATS_FIELDS.
+    cKDTree.query_pairs with a radius a hair above r only proposes the pairs; the float64 predicate decides."""
+    c = _knn_cloud(cloud, "radius_count")
+    r = _check_radius(r, "radius_count")
+    n = len(c)
+    if n == 0:
+        return np.zeros(0, np.uint32), score_stats([])
+    c64 = c[:, :3].astype(np.float64)
+    pairs = cKDTree(c64).query_pairs(r * (1 + 1e-9), output_type="ndarray")
+    ok = pair_d2(c64[pairs[:, 0]], c64[pairs[:, 1]]) <= np.float64(r) * np.float64(r)
+    cnt = (np.bincount(pairs[ok, 0], minlength=n) + np.bincount(pairs[ok, 1], minlength=n)).astype(np.uint32)
+    return cnt, score_stats(cnt)
+
+
+def density_threshold(score, rule, thr=None, mul=None):
+    """(keep, m, mad, thr) of the KTH / MEAN filters over `score` (float64, +inf where a point has no score).  "abs": keep iff score <=
+    thr.  "mad": m = the median of the finite scores, mad = the median of |score - m| over them, thr = m + mul * (1.4826 * mad).  An
+    infinite score is never kept and a NaN thr keeps nothing."""
+    s = np.asarray(score, np.float64).reshape(-1)
+    nan = np.float64("nan")
+    m = mad = nan
+    if rule == "abs":
+        if not (np.isfinite(thr) and thr >= 0):
+            raise ValueError("density_filter: thr must be a finite number >= 0")
+        t = np.float64(thr)
+    elif rule == "mad":
+        if not (np.isfinite(mul) and mul >= 0):
+            raise ValueError("density_filter: mul must be a finite number >= 0")
+        f = s[np.isfinite(s)]
+        t = nan
+        if len(f):
+            m = np.median(f)
+            mad = np.median(np.abs(f - m))
+            with np.errstate(over="ignore"):
+                t = m + np.float64(mul) * (np.float64(1.4826) * mad)
+    else:
+        raise ValueError("density_filter: unknown rule")
+    with np.errstate(invalid="ignore"):
+        keep = np.isfinite(s) & (s <= t)
+    return keep, float(m), float(mad), float(t)
+
+
+def density_filter(cloud, score="mean", k=16, radius=0.5, rule="mad", thr=0.5, mul=2.0, min_neighbors=2, keep=True):
+    """The cloud filtered by its density.  score "kth" / "mean" (of knn(cloud, k)) with rule "abs" (thr) or "mad" (mul), see
+    density_threshold; score "count" (of radius_count(cloud, radius)): keep iff count >= min_neighbors.  Returns (mask, kept, result):
+    uint8 per point, the kept rows in the order given (None unless keep), and a dict with DENSITY_RESULT_FIELDS."""
+    c = _knn_cloud(cloud, "density_filter")
+    if score not in DENSITY_SCORES:
+        raise ValueError("density_filter: unknown score")
+    if rule not in DENSITY_RULES:
+        raise ValueError("density_filter: unknown rule")
+    n = len(c)
+    nan = float("nan")
+    if score == "count":
+        r = _check_radius(radius, "density_filter")
+        cnt, st = radius_count(c, r)
+        ok = cnt >= np.uint64(min_neighbors)
+        m = mad = nan
+        t = float(min_neighbors)
+        n_short = 0
+    else:
+        k = _check_k(k, "density_filter")
+        if rule == "abs" and not (np.isfinite(thr) and thr >= 0):
+            raise ValueError("density_filter: thr must be a finite number >= 0")
+        if rule == "mad" and not (np.isfinite(mul) and mul >= 0):
+            raise ValueError("density_filter: mul must be a finite number >= 0")
+        q = knn(c, k)
+        st = q[score + "_stats"]
+        n_short = q["n_short"]
+        ok, m, mad, t = density_threshold(q[score], rule, thr, mul)
+    dyn = _decode(c[:, 3])[2]
+    res = {"n_points": int(n), "n_kept": int(ok.sum()), "n_removed": int(n - ok.sum()), "n_removed_dynamic": int((~ok & dyn).sum()),
+           "n_removed_static": int((~ok & ~dyn).sum()), "n_short": int(n_short), "n_scored": st["n_scored"], "m": m, "mad": mad, "thr": t,
+           "min": st["min"], "median": st["median"], "p90": st["p90"], "p99": st["p99"], "max": st["max"]}
+    return ok.astype(np.uint8), (c[ok].copy() if keep else None), res

@@ -585,6 +585,97 @@ int erasor_hip_cluster_map(erasor_hip_handle *h, double tol, size_t min_size, si
                            erasor_cluster_row *rows, size_t cap_rows, float *kept_xyzi, size_t cap_points,
                            erasor_cluster_result *res);
 
+/* ---- how dense the cloud is around each point: k nearest neighbours, radius counts, and the outlier filters on them ---------------
+ * replaces: what users of a cleaned map run on the host next -- pcl::StatisticalOutlierRemoval and pcl::RadiusOutlierRemoval, a
+ * KD-tree over the whole map -- to drop the single returns in the air, the thin shells dynamic removal leaves behind and the stray
+ * centroids at the rim of a reverted bin.  erasor_hip_cluster_* only drops disconnected fragments: it does not find a lone point one
+ * tolerance from a wall, and has no notion of "sparser than the rest of this map".  The contract, restated on the host by
+ * erasor_amd/evalmap.py (knn / knn_brute, radius_count / radius_count_brute, density_filter), which the device equals byte for byte:
+ *   - distance: ex = (double)x_i - (double)x_j and likewise ey, ez; d2 = (ex*ex + ey*ey) + ez*ez in float64, left to right, no fused
+ *     multiply-add; d = sqrt(d2), correctly rounded;
+ *   - the neighbour order of point i: every j != i by (d2, j) ascending, a total order under any number of ties and duplicates.  Self
+ *     is excluded by index, not by distance: an identical point at another index is a neighbour at distance 0;
+ *   - knn, 1 <= k <= 32: the first k entries of that order as nbr_idx[i*k + e] / nbr_dist[i*k + e]; kth[i] = nbr_dist[i*k + k-1];
+ *     mean[i] = (((0.0 + d_0) + d_1) + ... + d_{k-1}) / (double)k.  A point with fewer than k other points (n - 1 < k): the missing
+ *     entries are index 0xFFFFFFFF and distance +inf, kth and mean are +inf, and it is counted in n_short;
+ *   - radius count: count[i] = the number of j != i with d2 <= r*r, r*r formed once in float64;
+ *   - the statistics of a score are taken over the points whose score is finite (n_scored): min, median, p90, p99, max exactly as
+ *     erasor_hip_overlap_* takes its median and percentiles (the same ranks, the same interpolation, exact order statistics); NaN
+ *     when n_scored == 0.
+ * Not offered: PCL's mean + mul * sigma.  Sigma is a float sum and its value depends on the order of its terms; a median and a median
+ * absolute deviation do not.  Up to that rule and PCL's float32 metric, MEAN / MAD is StatisticalOutlierRemoval's selection and COUNT
+ * is RadiusOutlierRemoval's; PCL is not a dependency of this project and nothing is pinned against it. */
+typedef struct erasor_score_stats {
+    uint64_t n_scored;                  /* points whose score is finite */
+    double min, median, p90, p99, max;  /* over those; NaN when there are none */
+} erasor_score_stats;
+
+typedef struct erasor_knn_result {
+    uint64_t n_points;  /* points given */
+    uint64_t n_short;   /* points with fewer than k other points: padded lists, kth = mean = +inf */
+    erasor_score_stats kth, mean;
+} erasor_knn_result;
+
+enum { ERASOR_DENSITY_KTH = 0, ERASOR_DENSITY_MEAN = 1, ERASOR_DENSITY_COUNT = 2 };  /* erasor_density_filter.score */
+enum { ERASOR_DENSITY_ABS = 0, ERASOR_DENSITY_MAD = 1 };                             /* erasor_density_filter.rule */
+
+/* One filter.  score KTH / MEAN (the k-th neighbour's distance, the mean distance of the k nearest; both need k) with rule
+ *   ABS: keep iff score <= thr, thr given, finite and >= 0;
+ *   MAD: m = the median of the finite scores, dev_i = |score_i - m| in float64 over them, mad = the median of dev taken the same way,
+ *        thr = m + mul * (1.4826 * mad) evaluated on the host in that order, mul finite and >= 0; keep iff score <= thr.
+ * An infinite score is never kept and a NaN thr keeps nothing.  score COUNT (needs radius, finite and > 0): keep iff count >=
+ * min_neighbors; the rule must be a known one and is not used.  Fields a filter does not need are not read. */
+typedef struct erasor_density_filter {
+    int32_t score, rule;
+    uint32_t k, min_neighbors;
+    double radius, thr, mul;
+} erasor_density_filter;
+
+typedef struct erasor_density_result {
+    uint64_t n_points, n_kept, n_removed;
+    uint64_t n_removed_dynamic;  /* removed points whose uint32(intensity) & 0xFFFF is in 252..259 (decoded as erasor_hip_cluster_* does) */
+    uint64_t n_removed_static;   /* the other removed points: a labelled map shows at once whether the filter eats structure */
+    uint64_t n_short;            /* KTH / MEAN: points with fewer than k other points (their score is +inf); COUNT: 0 */
+    uint64_t n_scored;           /* points with a finite score */
+    double m, mad;               /* MAD: the median and the median absolute deviation; otherwise NaN */
+    double thr;                  /* the threshold applied: given (ABS), computed (MAD), (double)min_neighbors (COUNT) */
+    double min, median, p90, p99, max;  /* the score's statistics over the scored points; NaN when there are none */
+} erasor_density_result;
+
+/* The k nearest neighbours of every point of the cloud (XYZI rows, on the host or on the handle's device: is_device) inside that
+ * cloud.  All outputs are host buffers and optional: nbr_idx / nbr_dist (n * k entries each, row i = point i's list), kth / mean (n
+ * entries); NULL asks for the rest only.  n == 0: ERASOR_OK, counts zero and statistics NaN.  Works in the evaluator's own scratch:
+ * announced nodes, tickets and the last step's clouds stay as they are.  ERASOR_E_INVALID: a non-finite coordinate, k outside 1 .. 32,
+ * more than 2^30 points, res NULL, neighbour lists asked for with n * k > 2^30.  ERASOR_E_STATE: a step in flight.
+ * Identical points are searched exhaustively among themselves (every tie is visited): thousands of copies of one point are quadratic. */
+int erasor_hip_knn_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, uint32_t k, uint32_t *nbr_idx,
+                          double *nbr_dist, double *kth, double *mean, erasor_knn_result *res);
+/* the same over the handle's current map (the erasor_hip_get_map view, compacted on the device as erasor_hip_cluster_map does, never
+ * copied to the host).  ERASOR_E_STATE also: no map. */
+int erasor_hip_knn_map(erasor_hip_handle *h, uint32_t k, uint32_t *nbr_idx, double *nbr_dist, double *kth, double *mean,
+                       erasor_knn_result *res);
+
+/* count[i] (n entries, a host buffer, optional) = the number of other points within the radius of point i, and the counts' statistics
+ * (n_scored = n).  What pcl::RadiusOutlierRemoval counts on the host.  ERASOR_E_INVALID: a non-finite coordinate, radius not a finite
+ * number > 0, more than 2^30 points, res NULL.  ERASOR_E_STATE: a step in flight.  Voxelise a dense cloud first: the pass is quadratic
+ * in the points per radius-cell. */
+int erasor_hip_radius_count_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, double radius, uint32_t *count,
+                                   erasor_score_stats *res);
+/* the same over the handle's current map.  ERASOR_E_STATE also: no map. */
+int erasor_hip_radius_count_map(erasor_hip_handle *h, double radius, uint32_t *count, erasor_score_stats *res);
+
+/* The cloud filtered by `filter`: keep_mask (n bytes, 1 = kept) and kept_xyzi (cap_points rows: the kept rows in the order given, all
+ * four floats copied as bits), host buffers, optional; NULL asks for the counts only.  n rows always suffice; a kept buffer that
+ * does not hold the result gives ERASOR_E_CAPACITY, with res, and keep_mask if asked for, filled first.  What
+ * pcl::StatisticalOutlierRemoval (MEAN / MAD, up to its sigma rule) and pcl::RadiusOutlierRemoval (COUNT) do on the host.
+ * ERASOR_E_INVALID: a non-finite coordinate, an unknown score or rule, k outside 1 .. 32, radius not a finite number > 0, thr or mul
+ * not a finite number >= 0, more than 2^30 points, filter or res NULL.  ERASOR_E_STATE: a step in flight. */
+int erasor_hip_density_filter_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, const erasor_density_filter *filter,
+                                     uint8_t *keep_mask, float *kept_xyzi, size_t cap_points, erasor_density_result *res);
+/* the same over the handle's current map; the map itself stays as it is.  ERASOR_E_STATE also: no map. */
+int erasor_hip_density_filter_map(erasor_hip_handle *h, const erasor_density_filter *filter, uint8_t *keep_mask, float *kept_xyzi,
+                                  size_t cap_points, erasor_density_result *res);
+
 /* ---- maps without labels: label a third-party map from a dense labelled one, and the static points a method lost ----------------
  * Both search the overlap report's tree in FLANN's metric, as pcl::KdTreeFLANN (K = 1) does: float32 d^2 = ((0 + dx*dx) + dy*dy) + dz*dz
  * with dx = q.x - p.x in float, exact, the lowest index on ties.  Outputs are XYZI rows in caller HOST buffers; dst == NULL asks for
