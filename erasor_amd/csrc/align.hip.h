@@ -5,7 +5,7 @@
 // The cloud checked is the one the reference builds in every callback for RViz, ptr_query_viz = body2origin(tf_lidar2body · scan)
 // (OfflineMapUpdater.cpp:238-242, :441-449): the scan as given, T_lidar2body then the frame's T_body2origin, each with xform's
 // association (kernels.hip.h).  Each frame's row is the overlap report (nearest.hip.h) of those points against the map; the map's tree
-// is nn_tree's, built once.
+// is nn_build's, built once.
 //
 // k_al_query: one scan point per lane, all frames in one launch.  The frames are consecutive ranges of the concatenated scans (offsets);
 // the host gives every workgroup the frame of its first point and of the first point after it, so a lane binary-searches only the
@@ -42,12 +42,20 @@ struct AlRanks {
     unsigned long long pad;
 };
 
+// the largest frame in [a, z] whose first point is <= i: the frame holding point i (empty frames start where the next does)
+__device__ __forceinline__ uint32_t al_frame_of(const uint32_t *__restrict__ off, uint32_t i, uint32_t a, uint32_t z) {
+    while (a < z) {
+        const uint32_t m = (a + z + 1) / 2;
+        if (off[m] <= i) a = m;
+        else z = m - 1;
+    }
+    return a;
+}
+
 // (1) one scan point per lane.  off: [n_frames + 1] point offsets; wg: [grid + 1], wg[b] the frame of point b * NN_QBLOCK (wg[grid]:
-// the last frame); Tb: [n_frames] poses.  dbits: [n] distance bits; ctr: [n_frames][AL_NCTR], zeroed by the host.  n_map > 0.
+// the last frame); Tb: [n_frames] poses.  dbits: [n] distance bits; ctr: [n_frames][AL_NCTR], zeroed by the host.  T.n > 0.
 __global__ __launch_bounds__(NN_QBLOCK) void k_al_query(const float4 *__restrict__ scans, uint32_t n, const uint32_t *__restrict__ off,
-                                                         const uint32_t *__restrict__ wg, Xf Tl, const Xf *__restrict__ Tb,
-                                                         const float4 *__restrict__ pts, const uint32_t *__restrict__ idx, uint32_t n_map,
-                                                         const float4 *__restrict__ lo, const float4 *__restrict__ hi, uint32_t n_pad, double half,
+                                                         const uint32_t *__restrict__ wg, Xf Tl, const Xf *__restrict__ Tb, NnTree T, double half,
                                                          double one, double two, unsigned long long *__restrict__ dbits,
                                                          unsigned long long *__restrict__ ctr) {
     __shared__ uint32_t stack[NN_STACK * NN_QBLOCK];  // [depth][lane], as in k_nn_query
@@ -56,21 +64,14 @@ __global__ __launch_bounds__(NN_QBLOCK) void k_al_query(const float4 *__restrict
     uint32_t f = 0, flags = 0;  // flags: bit c set for counter c < AL_MAX_BITS, and bit AL_NON_FINITE
     unsigned long long bits = 0ull;
     if (valid) {
-        // the largest frame in [wg[b], wg[b + 1]] whose first point is <= i: the frame holding i (empty frames start where the next does)
-        uint32_t a = wg[blockIdx.x], z = wg[blockIdx.x + 1];
-        while (a < z) {
-            const uint32_t m = (a + z + 1) / 2;
-            if (off[m] <= i) a = m;
-            else z = m - 1;
-        }
-        f = a;
+        f = al_frame_of(off, i, wg[blockIdx.x], wg[blockIdx.x + 1]);  // (the frames its workgroup touches)
         const float4 q = xform(Tb[f], xform(Tl, scans[i]));
         if (!ev_finite(q)) {
             flags = 1u << AL_NON_FINITE;
             dbits[i] = AL_DROPPED;
         } else {
             uint32_t best_i;
-            const double d = sqrt(nn_search_f64((double)q.x, (double)q.y, (double)q.z, pts, idx, n_map, lo, hi, n_pad, stack, t, &best_i));
+            const double d = sqrt(nn_search_f64((double)q.x, (double)q.y, (double)q.z, T, stack, t, &best_i));
             flags = (d < half ? 1u << AL_BELOW_HALF : 0u) | (d < one ? 1u << AL_BELOW_ONE : 0u) | (d < two ? 1u << AL_BELOW_TWO : 0u);
             bits = __builtin_bit_cast(unsigned long long, d);
             dbits[i] = bits;

@@ -390,8 +390,12 @@ static double ov_lerp(double a, double b, double t) {
     return r;
 }
 
-// the leaf count of an n-point tree padded to a power of two (P); refused when its depth would not fit the traversal stack
-static int nn_pad(erasor_hip_handle *h, uint32_t n, uint32_t *P_out, const char *who, const char *cloud) {
+// The bounding-volume tree over pts[0 .. n) (nearest.hip.h) in E.nn_pts / nn_idx / nn_lo / nn_hi, and *T its view for the query kernels.
+// The leaf count is padded to a power of two (T->n_pad); a cloud whose tree would not fit the traversal stack is refused ("<who>: <cloud>
+// too large ..."), before anything else is done.  E.nn_ctr (OV_NCTR entries) is zeroed here; a non-finite point refuses the call
+// ("<who>: ... in <k> <noun>").  n == 0: T->n = 0, T->n_pad = 1, nothing is built and no search may start.
+static int nn_build(erasor_hip_handle *h, const float4 *pts, uint32_t n, const char *who, const char *cloud, const char *noun, NnTree *T) {
+    auto &E = h->ev;
     const uint32_t n_leaves = std::max(1u, cdiv(n, NN_LEAF));
     uint32_t P = 1, levels = 0;  // leaves padded to a power of two, levels below the root
     while (P < n_leaves) {
@@ -402,19 +406,15 @@ static int nn_pad(erasor_hip_handle *h, uint32_t n, uint32_t *P_out, const char 
         h->err = std::string(who) + ": " + cloud + " too large for the traversal stack";
         return ERASOR_E_INVALID;
     }
-    *P_out = P;
-    return ERASOR_OK;
-}
-
-// the bounding-volume tree over pts[0 .. n) (n > 0; nearest.hip.h) into E.nn_pts / nn_idx / nn_lo / nn_hi, P from nn_pad.  E.nn_ctr
-// (OV_NCTR entries) is zeroed by the caller; a non-finite point refuses the call ("<who>: ... in <k> <noun>").
-static int nn_tree(erasor_hip_handle *h, const float4 *pts, uint32_t n, uint32_t P, const char *who, const char *noun) {
-    auto &E = h->ev;
     const size_t n1 = (size_t)n + 1;
-    if (ensure(h, E.nn_bb, 8) || ensure(h, E.nn_key, n1) || ensure(h, E.nn_ka, n1) || ensure(h, E.nn_kb, n1) || ensure(h, E.nn_va, n1) ||
-        ensure(h, E.nn_vb, n1) || ensure(h, E.nn_idx, n1) || ensure(h, E.nn_pts, n1) || ensure(h, E.nn_lo, 2 * (size_t)P) ||
-        ensure(h, E.nn_hi, 2 * (size_t)P))
+    if (ensure(h, E.nn_ctr, OV_NCTR) ||
+        (n && (ensure(h, E.nn_bb, 8) || ensure(h, E.nn_key, n1) || ensure(h, E.nn_ka, n1) || ensure(h, E.nn_kb, n1) || ensure(h, E.nn_va, n1) ||
+               ensure(h, E.nn_vb, n1) || ensure(h, E.nn_idx, n1) || ensure(h, E.nn_pts, n1) || ensure(h, E.nn_lo, 2 * (size_t)P) ||
+               ensure(h, E.nn_hi, 2 * (size_t)P))))
         return ERASOR_E_NO_DEVICE;
+    *T = NnTree{E.nn_pts.p, E.nn_idx.p, E.nn_lo.p, E.nn_hi.p, n, P};
+    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
+    if (!n) return ERASOR_OK;
     // the box: k_bbox's fkey_ord min (3 x ~0u) / max (3 x 0)
     HIPC(h, hipMemsetAsync(E.nn_bb.p, 0xFF, 3 * sizeof(uint32_t), h->stream));
     HIPC(h, hipMemsetAsync(E.nn_bb.p + 3, 0, 3 * sizeof(uint32_t), h->stream));
@@ -515,20 +515,17 @@ static void ov_fill(uint64_t n, uint64_t below_half, uint64_t below_one, uint64_
 static int ov_run(erasor_hip_handle *h, const float4 *gt, uint32_t n_gt, const float4 *est, uint32_t n_est, double voxelsize, double *per_dist,
                   uint32_t *per_nearest, erasor_overlap_result *res) {
     auto &E = h->ev;
-    uint32_t P = 1;
-    int rc = nn_pad(h, n_gt, &P, "erasor_hip_overlap", "ground truth");
-    if (rc) return rc;
-    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256) ||
+    if (ensure(h, E.nn_hist, OV_SEL_MAX * 256) ||
         (n_est && (ensure(h, E.nn_dbits, (size_t)n_est + 1) || (per_nearest && ensure(h, E.nn_near, (size_t)n_est + 1)))))
         return ERASOR_E_NO_DEVICE;
     unsigned long long c[OV_NCTR];
-    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
-    if (n_gt && (rc = nn_tree(h, gt, n_gt, P, "erasor_hip_overlap", "ground-truth point(s)"))) return rc;
+    NnTree T;
+    int rc = nn_build(h, gt, n_gt, "erasor_hip_overlap", "ground truth", "ground-truth point(s)", &T);
+    if (rc) return rc;
     // the thresholds as overlap_report forms them: half = 0.5 * voxelsize, one = voxelsize, 2 * one
     const double half = 0.5 * voxelsize, one = voxelsize, two = 2 * one;
     if (n_est)
-        LAUNCH(h, h->stream, "ov_query", k_nn_query, cdiv(n_est, NN_QBLOCK), NN_QBLOCK, est, n_est, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p,
-               n_gt, (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, half, one, two, E.nn_dbits.p,
+        LAUNCH(h, h->stream, "ov_query", k_nn_query, cdiv(n_est, NN_QBLOCK), NN_QBLOCK, est, n_est, T, half, one, two, E.nn_dbits.p,
                per_nearest ? E.nn_near.p : (uint32_t *)nullptr, E.nn_ctr.p);
     HIPC(h, hipMemcpyAsync(c, E.nn_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
@@ -639,15 +636,13 @@ static int al_run(erasor_hip_handle *h, const char *who, const float4 *map, uint
         h->err = std::string(who) + ": empty map with a non-empty frame (no nearest point to measure against)";
         return ERASOR_E_INVALID;
     }
-    uint32_t P = 1;
-    int rc = nn_pad(h, n_map, &P, who, "map");
-    if (rc) return rc;
     const uint32_t grid = cdiv(n, NN_QBLOCK), nf = std::max(n_frames, 1u);
-    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256) || ensure(h, E.nn_dbits, (size_t)n + 1) ||
-        ensure(h, E.al_ctr, (size_t)nf * AL_NCTR) || ensure(h, E.al_rank, nf) || ensure(h, E.al_val, (size_t)nf * OV_SEL_MAX))
+    if (ensure(h, E.nn_hist, OV_SEL_MAX * 256) || ensure(h, E.nn_dbits, (size_t)n + 1) || ensure(h, E.al_ctr, (size_t)nf * AL_NCTR) ||
+        ensure(h, E.al_rank, nf) || ensure(h, E.al_val, (size_t)nf * OV_SEL_MAX))
         return ERASOR_E_NO_DEVICE;
-    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
-    if (n_map && (rc = nn_tree(h, map, n_map, P, who, "map point(s)"))) return rc;
+    NnTree T;
+    int rc = nn_build(h, map, n_map, who, "map", "map point(s)", &T);
+    if (rc) return rc;
     AlFrames F;
     if ((rc = al_put_frames(h, n, offsets, n_frames, T_body2origin, F))) return rc;
     const std::vector<uint32_t> &off = F.off;
@@ -656,8 +651,7 @@ static int al_run(erasor_hip_handle *h, const char *who, const float4 *map, uint
     const double half = 0.5 * voxelsize, one = voxelsize, two = 2 * one;
     if (n)
         LAUNCH(h, h->stream, "al_query", k_al_query, grid, NN_QBLOCK, scans, n, (const uint32_t *)E.al_off.p, (const uint32_t *)E.al_wg.p,
-               to_xf(T_lidar2body ? T_lidar2body : AL_IDENTITY), (const Xf *)E.al_xf.p, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, n_map,
-               (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, half, one, two, E.nn_dbits.p, E.al_ctr.p);
+               to_xf(T_lidar2body ? T_lidar2body : AL_IDENTITY), (const Xf *)E.al_xf.p, T, half, one, two, E.nn_dbits.p, E.al_ctr.p);
     std::vector<unsigned long long> c((size_t)nf * AL_NCTR);
     HIPC(h, hipMemcpyAsync(c.data(), E.al_ctr.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
@@ -779,13 +773,12 @@ static int ls_check_args(erasor_hip_handle *h, const char *who, const void *scan
 
 // the launch of one pass (list == nullptr: all n points; else the n_list left points)
 static int ls_pass(erasor_hip_handle *h, const float4 *scans, uint32_t n, const uint32_t *list, uint32_t n_list, uint32_t n_frames, const Xf &Tl,
-                   uint32_t n_map, uint32_t P, double T2, uint32_t code_hit, uint32_t code_miss, uint32_t count_miss, uint32_t *left) {
+                   const NnTree &T, double T2, uint32_t code_hit, uint32_t code_miss, uint32_t count_miss, uint32_t *left) {
     auto &E = h->ev;
     const uint32_t m = list ? n_list : n;
     if (!m) return ERASOR_OK;
     LAUNCH(h, h->stream, "ls_query", k_ls_query, cdiv(m, NN_QBLOCK), NN_QBLOCK, scans, n, list, n_list, (const uint32_t *)E.al_off.p, n_frames,
-           (const uint32_t *)E.al_wg.p, Tl, (const Xf *)E.al_xf.p, (const float4 *)E.nn_pts.p, n_map, (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P,
-           T2, code_hit, code_miss, count_miss, E.code.p, left, E.al_ctr.p);
+           (const uint32_t *)E.al_wg.p, Tl, (const Xf *)E.al_xf.p, T, T2, code_hit, code_miss, count_miss, E.code.p, left, E.al_ctr.p);
     return ERASOR_OK;
 }
 
@@ -795,24 +788,22 @@ static int ls_run(erasor_hip_handle *h, const char *who, const float4 *smap, uin
                   erasor_scan_label_row *summary) {
     auto &E = h->ev;
     const double T2 = ls_bound(tau);
-    uint32_t P = 1;
-    int rc = nn_pad(h, n_smap, &P, who, "static map");
-    if (rc) return rc;
     const uint32_t nf = std::max(n_frames, 1u);
     const bool scan = have_raw || sp.wanted();
-    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.al_ctr, (size_t)nf * LS_NCTR) || ensure(h, E.code, (size_t)n + 1) ||
+    if (ensure(h, E.al_ctr, (size_t)nf * LS_NCTR) || ensure(h, E.code, (size_t)n + 1) ||
         (scan && (ensure(h, E.fm_flag, (size_t)n + 1) || ensure(h, E.fm_pl, (size_t)n + 1) || ensure(h, E.fm_tops, n / 1024 + 4))) ||
         (have_raw && ensure(h, E.nn_near, (size_t)n + 1)) || (sp.xyzi && ensure(h, E.fm_out, (size_t)n + 1)))
         return ERASOR_E_NO_DEVICE;
-    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
-    if (n_smap && (rc = nn_tree(h, smap, n_smap, P, who, "static map point(s)"))) return rc;
+    NnTree T;
+    int rc = nn_build(h, smap, n_smap, who, "static map", "static map point(s)", &T);
+    if (rc) return rc;
     AlFrames F;
     if ((rc = al_put_frames(h, n, offsets, n_frames, T_body2origin, F))) return rc;
     const std::vector<uint32_t> &off = F.off;
     const Xf Tl = to_xf(T_lidar2body ? T_lidar2body : AL_IDENTITY);
     HIPC(h, hipMemsetAsync(E.al_ctr.p, 0, (size_t)nf * LS_NCTR * sizeof(unsigned long long), h->stream));
     // the static pass: code 0, or 1 for now
-    if ((rc = ls_pass(h, scans, n, nullptr, 0, n_frames, Tl, n_smap, P, T2, LS_STATIC, LS_DYNAMIC, have_raw ? 0u : 1u,
+    if ((rc = ls_pass(h, scans, n, nullptr, 0, n_frames, Tl, T, T2, LS_STATIC, LS_DYNAMIC, have_raw ? 0u : 1u,
                       have_raw ? E.fm_flag.p : (uint32_t *)nullptr)))
         return rc;
     std::vector<unsigned long long> c((size_t)nf * LS_NCTR, 0ull);
@@ -832,11 +823,10 @@ static int ls_run(erasor_hip_handle *h, const char *who, const float4 *smap, uin
                    (const uint32_t *)E.fm_tops.p, E.nn_near.p);
         }
         const float4 *rmap = nullptr;
-        uint32_t Pr = 1;
-        if ((rc = ev_input(h, raw_xyzi, n_raw, raw_is_device, E.gt, &rmap)) || (rc = nn_pad(h, n_raw, &Pr, who, "raw map"))) return rc;
-        HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
-        if (n_raw && (rc = nn_tree(h, rmap, n_raw, Pr, who, "raw map point(s)"))) return rc;
-        if ((rc = ls_pass(h, scans, n, E.nn_near.p, n_left, n_frames, Tl, n_raw, Pr, T2, LS_DYNAMIC, LS_UNKNOWN, 1u, nullptr))) return rc;
+        if ((rc = ev_input(h, raw_xyzi, n_raw, raw_is_device, E.gt, &rmap)) ||
+            (rc = nn_build(h, rmap, n_raw, who, "raw map", "raw map point(s)", &T)))
+            return rc;
+        if ((rc = ls_pass(h, scans, n, E.nn_near.p, n_left, n_frames, Tl, T, T2, LS_DYNAMIC, LS_UNKNOWN, 1u, nullptr))) return rc;
     }
     HIPC(h, hipMemcpyAsync(c.data(), E.al_ctr.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
@@ -1073,21 +1063,18 @@ static int kn_counters(erasor_hip_handle *h, unsigned long long c[KN_NCTR]) {
 // both knn scores of pts[0 .. n) (n > 0) into E.kn_kth / E.kn_mean, with `lists` the neighbour lists into E.kn_ni / E.kn_nd; the counters in c
 static int kn_search(erasor_hip_handle *h, const char *who, const float4 *pts, uint32_t n, uint32_t k, bool lists, unsigned long long c[KN_NCTR]) {
     auto &E = h->ev;
-    uint32_t P = 1;
-    int rc = nn_pad(h, n, &P, who, "cloud");
-    if (rc || (rc = kn_reset(h))) return rc;
+    int rc = kn_reset(h);
+    if (rc) return rc;
     const size_t n1 = (size_t)n + 1;
-    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.kn_kth, n1) || ensure(h, E.kn_mean, n1) ||
+    if (ensure(h, E.kn_kth, n1) || ensure(h, E.kn_mean, n1) ||
         (lists && (ensure(h, E.kn_ni, (size_t)n * k + 1) || ensure(h, E.kn_nd, (size_t)n * k + 1))))
         return ERASOR_E_NO_DEVICE;
-    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
-    if ((rc = nn_tree(h, pts, n, P, who, "point(s)"))) return rc;
+    NnTree T;
+    if ((rc = nn_build(h, pts, n, who, "cloud", "point(s)", &T))) return rc;
     uint32_t *ni = lists ? E.kn_ni.p : nullptr;
     double *nd = lists ? E.kn_nd.p : nullptr;
     const uint32_t g = cdiv(n, KN_QBLOCK);
-#define KN_QUERY(KC)                                                                                                                             \
-    LAUNCH(h, h->stream, "kn_query", k_kn_query<KC>, g, KN_QBLOCK, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, n, (const float4 *)E.nn_lo.p, \
-           (const float4 *)E.nn_hi.p, P, k, E.kn_kth.p, E.kn_mean.p, ni, nd, E.kn_ctr.p)
+#define KN_QUERY(KC) LAUNCH(h, h->stream, "kn_query", k_kn_query<KC>, g, KN_QBLOCK, T, k, E.kn_kth.p, E.kn_mean.p, ni, nd, E.kn_ctr.p)
     if (k <= 8) KN_QUERY(8);
     else if (k <= 16) KN_QUERY(16);
     else KN_QUERY(32);
@@ -1370,15 +1357,12 @@ int erasor_hip_label_map(erasor_hip_handle *h, const void *src_xyzi, size_t n_sr
     if ((rc = ev_voxelize(h, s, (uint32_t)n_src, leaf, E.est, &nq, &passthrough))) return rc;
     // 2. every centroid takes the intensity of its nearest medium point (KdTreeFLANN, K = 1)
     const uint32_t nm = (uint32_t)n_medium;
-    uint32_t P = 1;
-    if ((rc = nn_pad(h, nm, &P, "erasor_hip_label_map", "medium"))) return rc;
-    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.fm_ctr, FM_NCTR) || ensure(h, E.fm_out, (size_t)nq + 1)) return ERASOR_E_NO_DEVICE;
-    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
-    if ((rc = nn_tree(h, m, nm, P, "erasor_hip_label_map", "medium point(s)"))) return rc;
+    if (ensure(h, E.fm_ctr, FM_NCTR) || ensure(h, E.fm_out, (size_t)nq + 1)) return ERASOR_E_NO_DEVICE;
+    NnTree T;
+    if ((rc = nn_build(h, m, nm, "erasor_hip_label_map", "medium", "medium point(s)", &T))) return rc;
     HIPC(h, hipMemsetAsync(E.fm_ctr.p, 0, FM_NCTR * sizeof(unsigned long long), h->stream));
     if (nq)
-        LAUNCH(h, h->stream, "lm_query", k_lm_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, (const float4 *)E.est.p, nq, (const float4 *)E.nn_pts.p,
-               (const uint32_t *)E.nn_idx.p, nm, (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, E.fm_out.p, E.fm_ctr.p);
+        LAUNCH(h, h->stream, "lm_query", k_lm_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, (const float4 *)E.est.p, nq, T, E.fm_out.p, E.fm_ctr.p);
     unsigned long long c[FM_NCTR];
     HIPC(h, hipMemcpyAsync(c, E.fm_ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
@@ -1417,17 +1401,14 @@ int erasor_hip_static_complement(erasor_hip_handle *h, const void *est_xyzi, siz
     const float4 *e = nullptr, *g = nullptr;
     if ((rc = ev_input(h, est_xyzi, n_est, est_is_device, E.est, &e)) || (rc = ev_input(h, gt_xyzi, n_gt, gt_is_device, E.gt, &g))) return rc;
     const uint32_t ne = (uint32_t)n_est, ng = (uint32_t)n_gt;
-    uint32_t P = 1;
-    if ((rc = nn_pad(h, ne, &P, "erasor_hip_static_complement", "estimate"))) return rc;
-    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.fm_ctr, FM_NCTR) || ensure(h, E.fm_flag, (size_t)ng + 1) || ensure(h, E.fm_pl, (size_t)ng + 1) ||
+    if (ensure(h, E.fm_ctr, FM_NCTR) || ensure(h, E.fm_flag, (size_t)ng + 1) || ensure(h, E.fm_pl, (size_t)ng + 1) ||
         ensure(h, E.fm_tops, ng / 1024 + 4) || ensure(h, E.fm_out, (size_t)ng + 1))
         return ERASOR_E_NO_DEVICE;
-    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
-    if (ne && (rc = nn_tree(h, e, ne, P, "erasor_hip_static_complement", "estimated point(s)"))) return rc;
+    NnTree T;
+    if ((rc = nn_build(h, e, ne, "erasor_hip_static_complement", "estimate", "estimated point(s)", &T))) return rc;
     HIPC(h, hipMemsetAsync(E.fm_ctr.p, 0, FM_NCTR * sizeof(unsigned long long), h->stream));
     // the lost flags, then the lost points in ground-truth order: an exclusive scan of the flags and a scatter (no atomic decides a slot)
-    LAUNCH(h, h->stream, "cp_query", k_cp_query, cdiv(ng, NN_QBLOCK), NN_QBLOCK, g, ng, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, ne,
-           (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, 0.03, E.fm_flag.p, E.fm_ctr.p);
+    LAUNCH(h, h->stream, "cp_query", k_cp_query, cdiv(ng, NN_QBLOCK), NN_QBLOCK, g, ng, T, 0.03, E.fm_flag.p, E.fm_ctr.p);
     if (dst_xyzi) {
         scan_u32(h, h->stream, E.fm_flag.p, E.fm_pl.p, E.fm_tops.p, ng, ng, nullptr, nullptr, "cp_compact");
         LAUNCH(h, h->stream, "cp_compact", k_f_compact, cdiv(ng, 256), 256, g, ng, (const uint32_t *)E.fm_flag.p, (const uint32_t *)E.fm_pl.p,
@@ -1867,7 +1848,7 @@ int erasor_hip_debug_render_atomic(erasor_hip_handle *h, const void *xyzi, size_
 #endif
 
 #ifdef ERASOR_HIP_TEST_HOOKS
-// test hook: the bounding-volume tree of a cloud (x y z i rows, host or device) as nn_pad / nn_tree build it for overlap, align_frames,
+// test hook: the bounding-volume tree of a cloud (x y z i rows, host or device) as nn_build builds it for overlap, align_frames,
 // label_map and static_complement: P, the points in key order with their original indices, the sorted Morton keys, the boxes of all 2P
 // nodes (node 0 is never written: its rows come back as they lie in the scratch).  cap_nodes: the rows lo / hi hold.
 int erasor_hip_debug_nn_tree(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, uint32_t *P_out, float *pts, uint32_t *idx,
@@ -1879,16 +1860,13 @@ int erasor_hip_debug_nn_tree(erasor_hip_handle *h, const void *xyzi, size_t n, i
     const float4 *g = nullptr;
     int rc = ev_input(h, xyzi, n, is_device, E.gt, &g);
     if (rc) return rc;
-    uint32_t P = 1;
-    if ((rc = nn_pad(h, (uint32_t)n, &P, "erasor_hip_debug_nn_tree", "cloud"))) return rc;
-    if (ensure(h, E.nn_ctr, OV_NCTR)) return ERASOR_E_NO_DEVICE;
-    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
-    if ((rc = nn_tree(h, g, (uint32_t)n, P, "erasor_hip_debug_nn_tree", "point(s)"))) return rc;
-    *P_out = P;
-    if (2 * (size_t)P > cap_nodes) return ERASOR_E_CAPACITY;
-    if ((rc = d2h(h, pts, E.nn_pts.p, n * sizeof(float4))) || (rc = d2h(h, idx, E.nn_idx.p, n * sizeof(uint32_t))) ||
-        (rc = d2h(h, keys, E.dbg_skeys, n * sizeof(uint32_t))) || (rc = d2h(h, lo, E.nn_lo.p, 2 * (size_t)P * sizeof(float4))) ||
-        (rc = d2h(h, hi, E.nn_hi.p, 2 * (size_t)P * sizeof(float4))))
+    NnTree T;
+    if ((rc = nn_build(h, g, (uint32_t)n, "erasor_hip_debug_nn_tree", "cloud", "point(s)", &T))) return rc;
+    *P_out = T.n_pad;
+    if (2 * (size_t)T.n_pad > cap_nodes) return ERASOR_E_CAPACITY;
+    if ((rc = d2h(h, pts, T.pts, n * sizeof(float4))) || (rc = d2h(h, idx, T.idx, n * sizeof(uint32_t))) ||
+        (rc = d2h(h, keys, E.dbg_skeys, n * sizeof(uint32_t))) || (rc = d2h(h, lo, T.lo, 2 * (size_t)T.n_pad * sizeof(float4))) ||
+        (rc = d2h(h, hi, T.hi, 2 * (size_t)T.n_pad * sizeof(float4))))
         return rc;
     return ERASOR_OK;
 }
@@ -1908,24 +1886,20 @@ int erasor_hip_debug_nn_effort(erasor_hip_handle *h, const float *tree_xyzi, siz
     int rc;
     if ((rc = ev_input(h, tree_xyzi, n, 0, E.gt, &g)) || (rc = ev_input(h, query_xyzi, n_q, 0, E.est, &q))) return rc;
     const uint32_t nt = (uint32_t)n, nq = (uint32_t)n_q;
-    uint32_t P = 1;
-    if ((rc = nn_pad(h, nt, &P, "erasor_hip_debug_nn_effort", "cloud"))) return rc;
-    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.fm_ctr, FM_NCTR) || ensure(h, E.nn_dbits, n_q + 1) || ensure(h, E.nn_near, n_q + 1) ||
+    if (ensure(h, E.fm_ctr, FM_NCTR) || ensure(h, E.nn_dbits, n_q + 1) || ensure(h, E.nn_near, n_q + 1) ||
         ensure(h, E.fm_out, n_q + 1))
         return ERASOR_E_NO_DEVICE;
-    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
-    if ((rc = nn_tree(h, g, nt, P, "erasor_hip_debug_nn_effort", "point(s)"))) return rc;
+    NnTree T;
+    if ((rc = nn_build(h, g, nt, "erasor_hip_debug_nn_effort", "cloud", "point(s)", &T))) return rc;
     HIPC(h, hipMemsetAsync(E.fm_ctr.p, 0, FM_NCTR * sizeof(unsigned long long), h->stream));
     uint32_t *d_eff = nullptr;  // (the query grid's lanes past n_q never search: 2 * n_q entries are all that is written)
     HIPC(h, hipMalloc((void **)&d_eff, 2 * n_q * sizeof(uint32_t)));
     (void)hipMemsetAsync(d_eff, 0xFF, 2 * n_q * sizeof(uint32_t), h->stream);
     hipLaunchKernelGGL(k_nn_set_effort, dim3(1), dim3(1), 0, h->stream, d_eff);
     if (f32)
-        LAUNCH(h, h->stream, "lm_query", k_lm_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, q, nq, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, nt,
-               (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, E.fm_out.p, E.fm_ctr.p);
+        LAUNCH(h, h->stream, "lm_query", k_lm_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, q, nq, T, E.fm_out.p, E.fm_ctr.p);
     else
-        LAUNCH(h, h->stream, "ov_query", k_nn_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, q, nq, (const float4 *)E.nn_pts.p, (const uint32_t *)E.nn_idx.p, nt,
-               (const float4 *)E.nn_lo.p, (const float4 *)E.nn_hi.p, P, 0.5, 1.0, 2.0, E.nn_dbits.p, E.nn_near.p, E.nn_ctr.p);
+        LAUNCH(h, h->stream, "ov_query", k_nn_query, cdiv(nq, NN_QBLOCK), NN_QBLOCK, q, nq, T, 0.5, 1.0, 2.0, E.nn_dbits.p, E.nn_near.p, E.nn_ctr.p);
     hipLaunchKernelGGL(k_nn_set_effort, dim3(1), dim3(1), 0, h->stream, (uint32_t *)nullptr);
     unsigned long long c[FM_NCTR], co[OV_NCTR];
     rc = d2h(h, effort, d_eff, 2 * n_q * sizeof(uint32_t));
@@ -1957,13 +1931,11 @@ int erasor_hip_debug_ls_effort(erasor_hip_handle *h, const float *tree_xyzi, siz
     int rc;
     if ((rc = ev_input(h, tree_xyzi, n, 0, E.gt, &g)) || (rc = ev_input(h, query_xyzi, n_q, 0, E.est, &q))) return rc;
     const uint32_t nt = (uint32_t)n, nq = (uint32_t)n_q, grid = cdiv(nq, NN_QBLOCK);
-    uint32_t P = 1;
-    if ((rc = nn_pad(h, nt, &P, "erasor_hip_debug_ls_effort", "cloud"))) return rc;
-    if (ensure(h, E.nn_ctr, OV_NCTR) || ensure(h, E.al_off, 2) || ensure(h, E.al_wg, (size_t)grid + 1) || ensure(h, E.al_xf, 1) ||
+    if (ensure(h, E.al_off, 2) || ensure(h, E.al_wg, (size_t)grid + 1) || ensure(h, E.al_xf, 1) ||
         ensure(h, E.al_ctr, LS_NCTR) || ensure(h, E.code, n_q + 1))
         return ERASOR_E_NO_DEVICE;
-    HIPC(h, hipMemsetAsync(E.nn_ctr.p, 0, OV_NCTR * sizeof(unsigned long long), h->stream));
-    if ((rc = nn_tree(h, g, nt, P, "erasor_hip_debug_ls_effort", "point(s)"))) return rc;
+    NnTree T;
+    if ((rc = nn_build(h, g, nt, "erasor_hip_debug_ls_effort", "cloud", "point(s)", &T))) return rc;
     const uint32_t off[2] = {0, nq};
     const Xf one = to_xf(AL_IDENTITY);
     HIPC(h, hipMemcpyAsync(E.al_off.p, off, sizeof(off), hipMemcpyHostToDevice, h->stream));
@@ -1974,7 +1946,7 @@ int erasor_hip_debug_ls_effort(erasor_hip_handle *h, const float *tree_xyzi, siz
     HIPC(h, hipMalloc((void **)&d_eff, 2 * n_q * sizeof(uint32_t)));
     (void)hipMemsetAsync(d_eff, 0xFF, 2 * n_q * sizeof(uint32_t), h->stream);
     hipLaunchKernelGGL(k_nn_set_effort, dim3(1), dim3(1), 0, h->stream, d_eff);
-    rc = ls_pass(h, q, nq, nullptr, 0, 1, one, nt, P, ls_bound(tau), LS_STATIC, LS_DYNAMIC, 1u, nullptr);
+    rc = ls_pass(h, q, nq, nullptr, 0, 1, one, T, ls_bound(tau), LS_STATIC, LS_DYNAMIC, 1u, nullptr);
     hipLaunchKernelGGL(k_nn_set_effort, dim3(1), dim3(1), 0, h->stream, (uint32_t *)nullptr);
     if (!rc) rc = d2h(h, effort, d_eff, 2 * n_q * sizeof(uint32_t));
     (void)hipFree(d_eff);

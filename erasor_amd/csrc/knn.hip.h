@@ -22,16 +22,16 @@
 // selection and COUNT is RadiusOutlierRemoval's; PCL is not a dependency of this project and nothing is pinned against it.
 //
 // Search (k_kn_query).  The tree is nearest.hip.h's, built by its builders over the cloud itself.  One query per lane, taken in the
-// tree's sorted (Morton) order so that a wavefront walks neighbouring leaves; results go to the point's original index.  Depth first,
-// nearer child first, the pending siblings on a per-lane stack, as k_nn_query.  The lane keeps its k best (d2, j) sorted ascending; a
-// candidate enters when it is lexicographically below the list's last entry (or the list is not full), by insertion from the end.  A
-// node is pruned only when the list is FULL and the node's lower bound is STRICTLY greater than the list's last d2.
+// tree's sorted (Morton) order so that a wavefront walks neighbouring leaves; results go to the point's original index.  The traversal
+// is nearest.hip.h's nn_walk (depth first, nearer child first, the pending siblings on a per-lane stack), at the stride KN_QBLOCK; the
+// visitor KnList keeps the lane's k best (d2, j) sorted ascending; a candidate enters when it is lexicographically below the list's
+// last entry (or the list is not full), by insertion from the end.  Its bound is the list's last d2 once the list is FULL, so a node is
+// pruned only then, and only when the node's lower bound is STRICTLY greater.
 //
-// Why that is exact, with no epsilon (nearest.hip.h's argument, for k): the lower bound of a box is formed by the same monotone
-// operations as d2 -- per axis the gap to the box in float64, squared, summed left to right -- so lb <= d2(p) for every point p of the
-// box.  The list's last d2 only decreases.  A point that belongs to the final list has d2 <= the final last d2 <= the last d2 at any
-// moment, so a box pruned on lb > last d2 holds no such point; and because the prune is strict, every point AT the k-th d2 is visited,
-// so among equal d2 the index decides.  While the list is not full nothing is pruned: any point may still be needed.
+// Why that is exact, with no epsilon (nn_walk's argument, for k): the bound, the list's last d2, only decreases.  A point that belongs
+// to the final list has d2 <= the final last d2 <= the last d2 at any moment, so a box pruned on lb > last d2 holds no such point; and
+// because the prune is strict, every point AT the k-th d2 is visited, so among equal d2 the index decides.  While the list is not full
+// the bound is +inf and nothing is pruned: any point may still be needed.
 //
 // Where the list lives.  List and stack are indexed at run time; a per-thread array would go to scratch memory.  They are LDS arrays,
 // lane-minor ([entry][lane]: consecutive lanes in consecutive banks).  An entry is 12 B (d2 as float64, j as uint32), the stack
@@ -88,15 +88,61 @@ __device__ __forceinline__ void kn_commit_range(unsigned long long *ctr, uint32_
     }
 }
 
-// One query per lane, in the tree's sorted order: lane s asks for the k nearest other points of pts[s] (original index idx[s]).  pts /
-// idx / lo / hi / n_pad: the tree nearest.hip.h built over the cloud (n > 0, every point finite).  kth_bits / mean_bits: the two scores'
+// visitor: the k best (d2, j) of the query at sorted position s, ascending in the lane's column t of the LDS list ld / li
+// ([entry][KN_QBLOCK]).  The bound is the list's last d2 once the list is full and +inf before: nothing is pruned, everything enters.
+// (It carries no effort counters: no test hook reads this search's.)
+struct KnList {
+    typedef double real;
+    static constexpr bool FIXED = false;
+    double qx, qy, qz;
+    uint32_t s, k, t;
+    double *ld;
+    uint32_t *li;
+    uint32_t cnt = 0, worst_j = KN_NONE;
+    double worst = __builtin_huge_val();
+    __device__ __forceinline__ double lb(const float4 &l, const float4 &u) const { return nn_lb(l, u, qx, qy, qz); }
+    __device__ __forceinline__ double bound() const { return worst; }
+    // a leaf's points, except the query itself (by position, which is by index)
+    __device__ __forceinline__ bool leaf(const NnTree &T, uint32_t b, uint32_t e) {
+        for (uint32_t c = b; c < e; ++c) {
+            if (c == s) continue;
+            const float4 p = T.pts[c];
+            const double ex = qx - (double)p.x, ey = qy - (double)p.y, ez = qz - (double)p.z;
+            const double d2 = (ex * ex + ey * ey) + ez * ez;
+            if (!(d2 <= worst)) continue;
+            const uint32_t j = T.idx[c];
+            if (cnt == k && d2 == worst && j > worst_j) continue;
+            // insertion from the end: the entries above (d2, j) move up one place, the last one drops out when the list is full.  The
+            // loop walks the new entry's place in the lane's column (entry * KN_QBLOCK + t), not the entry number: with the number the
+            // compiler keeps apart the loop's two exits and the search is 4 % slower at k = 8 (MEASUREMENTS.md, Density)
+            uint32_t at = (cnt < k ? cnt : k - 1) * KN_QBLOCK + t;
+            while (at >= KN_QBLOCK) {
+                const double pd = ld[at - KN_QBLOCK];
+                const uint32_t pj = li[at - KN_QBLOCK];
+                if (pd < d2 || (pd == d2 && pj < j)) break;
+                ld[at] = pd;
+                li[at] = pj;
+                at -= KN_QBLOCK;
+            }
+            ld[at] = d2;
+            li[at] = j;
+            if (cnt < k) ++cnt;
+            if (cnt == k) {
+                worst = ld[(k - 1) * KN_QBLOCK + t];
+                worst_j = li[(k - 1) * KN_QBLOCK + t];
+            }
+        }
+        return false;
+    }
+};
+
+// One query per lane, in the tree's sorted order: lane s asks for the k nearest other points of T.pts[s] (original index T.idx[s]).  T:
+// the tree nearest.hip.h built over the cloud (T.n > 0, every point finite).  kth_bits / mean_bits: the two scores'
 // bit patterns at the point's original index; nbr_idx / nbr_dist ([n][k], optional): its neighbour lists.  KC: the list's capacity, k <= KC.
 template <uint32_t KC>
-__global__ __launch_bounds__(KN_QBLOCK) void k_kn_query(const float4 *__restrict__ pts, const uint32_t *__restrict__ idx, uint32_t n,
-                                                         const float4 *__restrict__ lo, const float4 *__restrict__ hi, uint32_t n_pad, uint32_t k,
-                                                         unsigned long long *__restrict__ kth_bits, unsigned long long *__restrict__ mean_bits,
-                                                         uint32_t *__restrict__ nbr_idx, double *__restrict__ nbr_dist,
-                                                         unsigned long long *__restrict__ ctr) {
+__global__ __launch_bounds__(KN_QBLOCK) void k_kn_query(NnTree T, uint32_t k, unsigned long long *__restrict__ kth_bits,
+                                                         unsigned long long *__restrict__ mean_bits, uint32_t *__restrict__ nbr_idx,
+                                                         double *__restrict__ nbr_dist, unsigned long long *__restrict__ ctr) {
     __shared__ uint32_t stack[NN_STACK * KN_QBLOCK];  // [depth][lane]
     __shared__ double ld[KC * KN_QBLOCK];              // [entry][lane]: the list's d2 ...
     __shared__ uint32_t li[KC * KN_QBLOCK];            // ... and original index
@@ -104,72 +150,12 @@ __global__ __launch_bounds__(KN_QBLOCK) void k_kn_query(const float4 *__restrict
     uint32_t is_short = 0;
     unsigned long long kb = 0ull, mb = 0ull;
     bool scored = false;
-    if (s < n) {
-        const float4 q = pts[s];
-        const double qx = (double)q.x, qy = (double)q.y, qz = (double)q.z;
-        const uint32_t self = idx[s];
-        uint32_t cnt = 0, worst_j = KN_NONE;
-        double worst = __builtin_huge_val();  // the list's last d2 once it is full; +inf before: nothing is pruned, everything enters
-        uint32_t node = 1, sp = 0;
-        for (;;) {
-            if (node >= n_pad) {  // a leaf: its points, except the query itself (by position, which is by index)
-                const uint32_t b = (node - n_pad) * NN_LEAF, e = b + NN_LEAF < n ? b + NN_LEAF : n;
-                for (uint32_t c = b; c < e; ++c) {
-                    if (c == s) continue;
-                    const float4 p = pts[c];
-                    const double ex = qx - (double)p.x, ey = qy - (double)p.y, ez = qz - (double)p.z;
-                    const double d2 = (ex * ex + ey * ey) + ez * ez;
-                    if (!(d2 <= worst)) continue;
-                    const uint32_t j = idx[c];
-                    if (cnt == k && d2 == worst && j > worst_j) continue;
-                    // insertion from the end: the entries above (d2, j) move up one place, the last one drops out when the list is full
-                    uint32_t pos = cnt < k ? cnt : k - 1;
-                    while (pos > 0) {
-                        const double pd = ld[(pos - 1) * KN_QBLOCK + t];
-                        const uint32_t pj = li[(pos - 1) * KN_QBLOCK + t];
-                        if (pd < d2 || (pd == d2 && pj < j)) break;
-                        ld[pos * KN_QBLOCK + t] = pd;
-                        li[pos * KN_QBLOCK + t] = pj;
-                        --pos;
-                    }
-                    ld[pos * KN_QBLOCK + t] = d2;
-                    li[pos * KN_QBLOCK + t] = j;
-                    if (cnt < k) ++cnt;
-                    if (cnt == k) {
-                        worst = ld[(k - 1) * KN_QBLOCK + t];
-                        worst_j = li[(k - 1) * KN_QBLOCK + t];
-                    }
-                }
-            } else {
-                const uint32_t c = 2 * node;
-                const float4 l0 = lo[c], u0 = hi[c], l1 = lo[c + 1], u1 = hi[c + 1];
-                const double d0 = l0.x <= u0.x ? nn_lb(l0, u0, qx, qy, qz) : __builtin_huge_val();  // (empty boxes: never entered)
-                const double d1 = l1.x <= u1.x ? nn_lb(l1, u1, qx, qy, qz) : __builtin_huge_val();
-                const bool v0 = l0.x <= u0.x && !(d0 > worst), v1 = l1.x <= u1.x && !(d1 > worst);
-                if (v0 && v1) {
-                    const uint32_t near = d1 < d0 ? c + 1 : c;
-                    stack[sp * KN_QBLOCK + t] = near ^ 1u;  // (sp < the tree's depth <= NN_STACK - 1: one entry per level above)
-                    ++sp;
-                    node = near;
-                    continue;
-                }
-                if (v0 || v1) {
-                    node = v0 ? c : c + 1;
-                    continue;
-                }
-            }
-            bool more = false;  // the next pending sibling that may still hold a point at or below the list's last d2
-            while (sp) {
-                --sp;
-                const uint32_t nk = stack[sp * KN_QBLOCK + t];
-                if (!(nn_lb(lo[nk], hi[nk], qx, qy, qz) > worst)) {
-                    node = nk;
-                    more = true;
-                    break;
-                }
-            }
-            if (!more) break;
-        }
+    if (s < T.n) {
+        const float4 q = T.pts[s];
+        const uint32_t self = T.idx[s];
+        KnList v{(double)q.x, (double)q.y, (double)q.z, s, k, t, ld, li};
+        nn_walk<KN_QBLOCK>(v, T, stack, t);
+        const uint32_t cnt = v.cnt;
         // the finishing pass over the sorted list: distances, the sequential sum, the padding
         double sum = 0.0, last = __builtin_huge_val();
         for (uint32_t e = 0; e < k; ++e) {

@@ -6,20 +6,22 @@
 // point is static (0) when the static map has a point at float64 distance d < tau from it; else dynamic (1) when no raw map was given
 // or the raw map has such a point; else unknown (2); a point with a non-finite coordinate after the transforms is dropped (255).
 //
-// The question is "is there a map point within tau", not "where is the nearest one": nn_exists_f64 walks nearest.hip.h's tree in
-// nn_search_f64's order (depth first, nearer child first, the pending siblings on the per-lane LDS stack) with the bound FIXED at T2,
+// The question is "is there a map point within tau", not "where is the nearest one": nn_exists_f64 runs nearest.hip.h's shared
+// traversal, nn_walk, (depth first, nearer child first, the pending siblings on the per-lane LDS stack) with the bound FIXED at T2,
 // the largest double whose correctly rounded sqrt is < tau (the host finds it with nextafter), and returns at the first leaf point
 // with d^2 <= T2.
 //
 // Why this equals the host's answer (evalmap.label_scans), with no epsilon: its d is sqrt(min d^2), d^2 = (ex*ex + ey*ey) + ez*ez in
 // float64 (what cKDTree returns; nearest.hip.h reproduces it bit for bit), and the correctly rounded sqrt is monotone, so d < tau <=>
-// min d^2 <= T2 <=> some map point has d^2 <= T2.  A box is pruned only when nn_lb, its exact lower bound (nearest.hip.h's header:
-// lb <= d^2(p) for every p of the box, formed by the same operations), is > T2: no point with d^2 <= T2 is ever skipped.
+// min d^2 <= T2 <=> some map point has d^2 <= T2.  The walker prunes a box only when nn_lb, its exact lower bound (nearest.hip.h's
+// header), is > T2, and a sibling that passed the fixed bound when it was pushed still passes it when it is popped: no point with
+// d^2 <= T2 is ever skipped.
 //
-// Why it never works harder than nn_search_f64 on the same tree: until the exact search meets its first point with d^2 <= T2 its bound
-// is > T2, so it enters every box this search enters (and more), in the same order -- where both children pass here both pass there and
-// the nearer is the same; where one passes here it is the one with the smaller bound, which the exact search takes first too.  At that
-// first point this search stops; the exact one goes on.  When no such point exists the exact search's bound stays > T2 throughout.
+// Why it never works harder than the exact search (nn_search_f64: the same walker, the bound its best d^2) on the same tree: until the
+// exact search meets its first point with d^2 <= T2 its bound is > T2, so it enters every box this search enters (and more), in the
+// same order -- where both children pass here both pass there and the nearer is the same; where one passes here it is the one with the
+// smaller bound, which the exact search takes first too.  At that first point this search stops; the exact one goes on.  When no such
+// point exists the exact search's bound stays > T2 throughout.
 //
 // k_ls_query: one scan point per lane.  The static pass runs over all points with k_al_query's frame lookup (the host gives every
 // workgroup the frames it touches).  With a raw map the points the static pass left are compacted into a list of their indices (a flag
@@ -44,79 +46,60 @@ enum : uint32_t {
 
 enum : uint8_t { LS_STATIC = 0, LS_DYNAMIC = 1, LS_UNKNOWN = 2, LS_DROPPED = 255 };
 
-// is there a tree point with float64 d^2 <= T2 from q (n_map > 0, q finite)?  stack: the workgroup's [NN_STACK][NN_QBLOCK] LDS array,
-// t: the lane's column; slot: the query's index for the test hook's effort counts.
-__device__ __forceinline__ bool nn_exists_f64(double qx, double qy, double qz, double T2, const float4 *__restrict__ pts, uint32_t n_map,
-                                             const float4 *__restrict__ lo, const float4 *__restrict__ hi, uint32_t n_pad, uint32_t *stack,
-                                             uint32_t t, uint32_t slot) {
-    uint32_t node = 1, sp = 0;
+// visitor: is there a tree point with float64 d^2 <= T2?  The bound is FIXED at T2 and the search ends at the first such point.
+struct NnExistsF64 {
+    typedef double real;
+    static constexpr bool FIXED = true;
+    double qx, qy, qz, T2;
     bool found = false;
 #ifdef ERASOR_HIP_TEST_HOOKS
-    uint32_t n_leaves = 0, n_points = 0;
+    uint32_t n_leaves = 0, n_points = 0;  // leaves opened, points tested up to and including the hit
 #endif
-    for (;;) {
-        if (node >= n_pad) {  // a leaf: its points, up to the first within the bound
-            const uint32_t b = (node - n_pad) * NN_LEAF, e = b + NN_LEAF < n_map ? b + NN_LEAF : n_map;
+    __device__ __forceinline__ double lb(const float4 &l, const float4 &u) const { return nn_lb(l, u, qx, qy, qz); }
+    __device__ __forceinline__ double bound() const { return T2; }
+    __device__ __forceinline__ bool leaf(const NnTree &T, uint32_t b, uint32_t e) {
 #ifdef ERASOR_HIP_TEST_HOOKS
-            ++n_leaves;
+        ++n_leaves;
 #endif
-            for (uint32_t s = b; s < e; ++s) {
-                const float4 p = pts[s];
-                const double ex = qx - (double)p.x, ey = qy - (double)p.y, ez = qz - (double)p.z;
-                const double d2 = (ex * ex + ey * ey) + ez * ez;
+        for (uint32_t s = b; s < e; ++s) {
+            const float4 p = T.pts[s];
+            const double ex = qx - (double)p.x, ey = qy - (double)p.y, ez = qz - (double)p.z;
+            const double d2 = (ex * ex + ey * ey) + ez * ez;
 #ifdef ERASOR_HIP_TEST_HOOKS
-                ++n_points;
+            ++n_points;
 #endif
-                if (d2 <= T2) {
-                    found = true;
-                    break;
-                }
-            }
-            if (found) break;
-        } else {
-            const uint32_t c = 2 * node;
-            const float4 l0 = lo[c], u0 = hi[c], l1 = lo[c + 1], u1 = hi[c + 1];
-            const double d0 = l0.x <= u0.x ? nn_lb(l0, u0, qx, qy, qz) : __builtin_huge_val();  // (empty boxes: never entered)
-            const double d1 = l1.x <= u1.x ? nn_lb(l1, u1, qx, qy, qz) : __builtin_huge_val();
-            const bool v0 = l0.x <= u0.x && !(d0 > T2), v1 = l1.x <= u1.x && !(d1 > T2);
-            if (v0 && v1) {
-                const uint32_t near = d1 < d0 ? c + 1 : c;
-                stack[sp * NN_QBLOCK + t] = near ^ 1u;  // (sp < the tree's depth <= NN_STACK - 1: one entry per level above)
-                ++sp;
-                node = near;
-                continue;
-            }
-            if (v0 || v1) {
-                node = v0 ? c : c + 1;
-                continue;
+            if (d2 <= T2) {
+                found = true;
+                break;
             }
         }
-        if (!sp) break;
-        --sp;
-        node = stack[sp * NN_QBLOCK + t];  // (a pending sibling passed the fixed bound when it was pushed: no second test)
+        return found;
     }
+};
+
+// is there a tree point with float64 d^2 <= T2 from q (T.n > 0, q finite)?  stack: the workgroup's [NN_STACK][NN_QBLOCK] LDS array,
+// t: the lane's column; slot: the query's index for the test hook's effort counts.
+__device__ __forceinline__ bool nn_exists_f64(double qx, double qy, double qz, double T2, const NnTree &T, uint32_t *stack, uint32_t t,
+                                             uint32_t slot) {
+    NnExistsF64 v{qx, qy, qz, T2};
+    nn_walk<NN_QBLOCK>(v, T, stack, t);
 #ifdef ERASOR_HIP_TEST_HOOKS
-    if (nn_effort) {
-        nn_effort[2 * (size_t)slot] = n_leaves;
-        nn_effort[2 * (size_t)slot + 1] = n_points;
-    }
+    nn_put_effort(v, (size_t)slot);
 #else
     (void)slot;
 #endif
-    return found;
+    return v.found;
 }
 
 // one pass of the labelling, one scan point per lane.  list == nullptr: the pass over all n points (wg: [grid + 1], the frame of every
 // workgroup's first point, as in k_al_query); else the pass over the n_list left points list[0 .. n_list), ascending.  off: [n_frames +
 // 1]; Tb: [n_frames].  A point with a tree point within the bound gets code_hit, the others code_miss; a dropped point LS_DROPPED (first
 // pass).  count_miss == 0: the missed points are not counted (a later pass decides them) and left[i] says whether point i is one (left:
-// [n], first pass with a raw map to come, else nullptr).  ctr: [n_frames][LS_NCTR], zeroed by the host.  n_map == 0: nothing is hit.
+// [n], first pass with a raw map to come, else nullptr).  ctr: [n_frames][LS_NCTR], zeroed by the host.  T.n == 0: nothing is hit; T.idx is not read.
 __global__ __launch_bounds__(NN_QBLOCK) void k_ls_query(const float4 *__restrict__ scans, uint32_t n, const uint32_t *__restrict__ list,
                                                          uint32_t n_list, const uint32_t *__restrict__ off, uint32_t n_frames,
-                                                         const uint32_t *__restrict__ wg, Xf Tl, const Xf *__restrict__ Tb,
-                                                         const float4 *__restrict__ pts, uint32_t n_map, const float4 *__restrict__ lo,
-                                                         const float4 *__restrict__ hi, uint32_t n_pad, double T2, uint32_t code_hit,
-                                                         uint32_t code_miss, uint32_t count_miss, uint8_t *__restrict__ codes,
+                                                         const uint32_t *__restrict__ wg, Xf Tl, const Xf *__restrict__ Tb, NnTree T,
+                                                         double T2, uint32_t code_hit, uint32_t code_miss, uint32_t count_miss, uint8_t *__restrict__ codes,
                                                          uint32_t *__restrict__ left, unsigned long long *__restrict__ ctr) {
     __shared__ uint32_t stack[NN_STACK * NN_QBLOCK];  // [depth][lane], as in k_nn_query
     const uint32_t t = threadIdx.x, j = blockIdx.x * NN_QBLOCK + t;
@@ -124,14 +107,7 @@ __global__ __launch_bounds__(NN_QBLOCK) void k_ls_query(const float4 *__restrict
     uint32_t f = 0, which = LS_NCTR, oor = 0;  // which: the counter this lane adds to (LS_NCTR: none)
     if (valid) {
         const uint32_t i = list ? list[j] : j;
-        // the largest frame in [a, z] whose first point is <= i: the frame holding i (empty frames start where the next does)
-        uint32_t a = list ? 0u : wg[blockIdx.x], z = list ? n_frames - 1 : wg[blockIdx.x + 1];
-        while (a < z) {
-            const uint32_t m = (a + z + 1) / 2;
-            if (off[m] <= i) a = m;
-            else z = m - 1;
-        }
-        f = a;
+        f = al_frame_of(off, i, list ? 0u : wg[blockIdx.x], list ? n_frames - 1 : wg[blockIdx.x + 1]);
         const float4 s = scans[i];
         const float4 q = xform(Tb[f], xform(Tl, s));
         if (!ev_finite(q)) {  // (first pass only: a left point is finite)
@@ -139,7 +115,7 @@ __global__ __launch_bounds__(NN_QBLOCK) void k_ls_query(const float4 *__restrict
             codes[i] = LS_DROPPED;
             if (left) left[i] = 0u;
         } else {
-            const bool hit = n_map && nn_exists_f64((double)q.x, (double)q.y, (double)q.z, T2, pts, n_map, lo, hi, n_pad, stack, t, j);
+            const bool hit = T.n && nn_exists_f64((double)q.x, (double)q.y, (double)q.z, T2, T, stack, t, j);
             const uint32_t gt = ev_is_dynamic(s.w, oor) ? 1u : 0u;
             codes[i] = (uint8_t)(hit ? code_hit : code_miss);
             if (left) left[i] = hit ? 0u : 1u;

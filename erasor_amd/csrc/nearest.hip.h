@@ -22,8 +22,8 @@
 // q < lo, q - (double)hi if q > hi, else 0, and lb = (gx*gx + gy*gy) + gz*gz.  For a point p of the box and q < lo: p.x - q >= lo - q
 // exactly, and rounding is monotone, so fl(p.x - q) >= fl(lo - q) = gx >= 0; fl(q - p.x) = -fl(p.x - q), so ex*ex = fl(p.x - q)^2 >=
 // gx*gx (the product of non-negative values is monotone after rounding too).  The same holds for q > hi, and gx = 0 <= |ex| inside.
-// Sums of non-negative terms are monotone in each term, so lb <= d^2(p) for every p in the box: pruning on lb > best never drops a point
-// with d^2 <= best.
+// Sums of non-negative terms are monotone in each term, so lb <= d^2(p) for every p in the box: what nn_walk, the one traversal every
+// search of the tree shares, needs of a lower bound (its own part of the argument is stated there, once).
 //
 // Order statistics: the distances' float64 bit patterns stay on the device (every d >= +0, so unsigned order is numeric order) and an
 // exact radix select finds the ranks the median and the two percentiles need: 8 passes of 8-bit digits from the top, all target ranks in
@@ -151,45 +151,55 @@ __device__ __forceinline__ double nn_lb(const float4 &l, const float4 &u, double
     return (gx * gx + gy * gy) + gz * gz;
 }
 
-// the exact float64 1-NN of q over the tree (n_gt > 0, q finite): the best d^2, and in *best_i the smallest original index at it.
-// stack: the workgroup's [NN_STACK][NN_QBLOCK] LDS array, t: the lane's column.  k_nn_query and k_al_query (align.hip.h) share it.
-__device__ __forceinline__ double nn_search_f64(double qx, double qy, double qz, const float4 *__restrict__ pts, const uint32_t *__restrict__ idx,
-                                               uint32_t n_gt, const float4 *__restrict__ lo, const float4 *__restrict__ hi, uint32_t n_pad,
-                                               uint32_t *stack, uint32_t t, uint32_t *best_i_out) {
-    double best = __builtin_huge_val();
-    uint32_t best_i = 0xFFFFFFFFu;
+// The tree as the searches see it, one value passed to every query kernel: pts / idx the points in key order and their original
+// indices ([n]), lo / hi the boxes of all 2 * n_pad nodes.  n == 0: n_pad = 1, nothing built, and no search may start.
+struct NnTree {
+    const float4 *pts;
+    const uint32_t *idx;
+    const float4 *lo, *hi;
+    uint32_t n, n_pad;
+};
+
+#ifdef ERASOR_HIP_TEST_HOOKS
+// a finished visitor's effort counts into nn_effort at the query's slot, when the hook is set
+template <class V>
+__device__ __forceinline__ void nn_put_effort(const V &v, size_t slot) {
+    if (nn_effort) {
+        nn_effort[2 * slot] = v.n_leaves;
+        nn_effort[2 * slot + 1] = v.n_points;
+    }
+}
+#endif
+
+// THE traversal, shared by every search of the tree (T.n > 0): depth first from the root, nearer child first, the pending siblings at
+// stack[depth * STRIDE + t] (the workgroup's [NN_STACK][STRIDE] LDS array, t: the lane's column).  The visitor V supplies what differs:
+//   real                 the arithmetic of its bounds (double or float);
+//   lb(l, u)             a lower bound of its d^2 from the query to every point of the box [l, u];
+//   bound()              the current bound: a box is pruned only when lb is STRICTLY greater;
+//   leaf(T, b, e)        the sorted points b .. e of a reached leaf (at least one); returns true to end the search at once;
+//   FIXED                the bound never changes, so a popped sibling, which passed it when it was pushed, is taken untested.
+// Why no search loses a point it needs: a box is skipped only on lb > bound, lb <= d^2(p) for every p of the box, and the bound never
+// grows, so a skipped box holds no point with d^2 <= the bound at that moment or later; because the prune is strict every point AT the
+// bound is visited, and the visitor's tie rule sees it.  Empty boxes (lo = +inf > hi) are never entered.  The order of visit -- the child
+// with the smaller lb first, the left one on equal lb -- decides only the effort, never the answer.
+template <uint32_t STRIDE, class V>
+__device__ __forceinline__ void nn_walk(V &v, const NnTree &T, uint32_t *stack, uint32_t t) {
+    typedef typename V::real real;
+    const real inf = (real)__builtin_huge_val();
     uint32_t node = 1, sp = 0;
-#ifdef ERASOR_HIP_TEST_HOOKS
-    uint32_t n_leaves = 0, n_points = 0;
-#endif
     for (;;) {
-        if (node >= n_pad) {  // a leaf: its points (a leaf that is reached holds at least one)
-            const uint32_t b = (node - n_pad) * NN_LEAF, e = b + NN_LEAF < n_gt ? b + NN_LEAF : n_gt;
-#ifdef ERASOR_HIP_TEST_HOOKS
-            ++n_leaves;
-            n_points += e - b;
-#endif
-            for (uint32_t s = b; s < e; ++s) {
-                const float4 p = pts[s];
-                const double ex = qx - (double)p.x, ey = qy - (double)p.y, ez = qz - (double)p.z;
-                const double d2 = (ex * ex + ey * ey) + ez * ez;
-                if (d2 <= best) {
-                    const uint32_t j = idx[s];
-                    if (d2 < best || j < best_i) {
-                        best = d2;
-                        best_i = j;
-                    }
-                }
-            }
+        if (node >= T.n_pad) {  // a leaf: its points (a leaf that is reached holds at least one)
+            const uint32_t b = (node - T.n_pad) * NN_LEAF, e = b + NN_LEAF < T.n ? b + NN_LEAF : T.n;
+            if (v.leaf(T, b, e)) return;
         } else {
             const uint32_t c = 2 * node;
-            const float4 l0 = lo[c], u0 = hi[c], l1 = lo[c + 1], u1 = hi[c + 1];
-            const double d0 = l0.x <= u0.x ? nn_lb(l0, u0, qx, qy, qz) : __builtin_huge_val();  // (empty boxes: never entered)
-            const double d1 = l1.x <= u1.x ? nn_lb(l1, u1, qx, qy, qz) : __builtin_huge_val();
-            const bool v0 = l0.x <= u0.x && !(d0 > best), v1 = l1.x <= u1.x && !(d1 > best);
+            const float4 l0 = T.lo[c], u0 = T.hi[c], l1 = T.lo[c + 1], u1 = T.hi[c + 1];
+            const real d0 = l0.x <= u0.x ? v.lb(l0, u0) : inf;  // (empty boxes: never entered)
+            const real d1 = l1.x <= u1.x ? v.lb(l1, u1) : inf;
+            const bool v0 = l0.x <= u0.x && !(d0 > v.bound()), v1 = l1.x <= u1.x && !(d1 > v.bound());
             if (v0 && v1) {
                 const uint32_t near = d1 < d0 ? c + 1 : c;
-                stack[sp * NN_QBLOCK + t] = near ^ 1u;  // (sp < the tree's depth <= NN_STACK - 1: one entry per level above)
+                stack[sp * STRIDE + t] = near ^ 1u;  // (sp < the tree's depth <= NN_STACK - 1: one entry per level above)
                 ++sp;
                 node = near;
                 continue;
@@ -199,33 +209,75 @@ __device__ __forceinline__ double nn_search_f64(double qx, double qy, double qz,
                 continue;
             }
         }
-        bool more = false;  // the next pending sibling that may still hold a point at d^2 <= best
-        while (sp) {
+        if constexpr (V::FIXED) {
+            if (!sp) return;
             --sp;
-            const uint32_t k = stack[sp * NN_QBLOCK + t];
-            if (!(nn_lb(lo[k], hi[k], qx, qy, qz) > best)) {
-                node = k;
-                more = true;
-                break;
+            node = stack[sp * STRIDE + t];
+        } else {
+            bool more = false;  // the next pending sibling that may still hold a point within the bound, which has shrunk since the push
+            while (sp) {
+                --sp;
+                const uint32_t k = stack[sp * STRIDE + t];
+                if (!(v.lb(T.lo[k], T.hi[k]) > v.bound())) {
+                    node = k;
+                    more = true;
+                    break;
+                }
+            }
+            if (!more) return;
+        }
+    }
+}
+
+// visitor: the exact float64 1-NN.  The bound is the best d^2 so far, so every point at the minimum is visited and ties go to the
+// smaller original index.
+struct NnBestF64 {
+    typedef double real;
+    static constexpr bool FIXED = false;
+    double qx, qy, qz;
+    double best = __builtin_huge_val();
+    uint32_t best_i = 0xFFFFFFFFu;
+#ifdef ERASOR_HIP_TEST_HOOKS
+    uint32_t n_leaves = 0, n_points = 0;  // leaves opened, and e - b of each
+#endif
+    __device__ __forceinline__ double lb(const float4 &l, const float4 &u) const { return nn_lb(l, u, qx, qy, qz); }
+    __device__ __forceinline__ double bound() const { return best; }
+    __device__ __forceinline__ bool leaf(const NnTree &T, uint32_t b, uint32_t e) {
+#ifdef ERASOR_HIP_TEST_HOOKS
+        ++n_leaves;
+        n_points += e - b;
+#endif
+        for (uint32_t s = b; s < e; ++s) {
+            const float4 p = T.pts[s];
+            const double ex = qx - (double)p.x, ey = qy - (double)p.y, ez = qz - (double)p.z;
+            const double d2 = (ex * ex + ey * ey) + ez * ez;
+            if (d2 <= best) {
+                const uint32_t j = T.idx[s];
+                if (d2 < best || j < best_i) {
+                    best = d2;
+                    best_i = j;
+                }
             }
         }
-        if (!more) break;
+        return false;
     }
+};
+
+// the exact float64 1-NN of q over the tree (T.n > 0, q finite): the best d^2, and in *best_i the smallest original index at it.
+// stack: the workgroup's [NN_STACK][NN_QBLOCK] LDS array, t: the lane's column.  k_nn_query and k_al_query (align.hip.h) share it.
+__device__ __forceinline__ double nn_search_f64(double qx, double qy, double qz, const NnTree &T, uint32_t *stack, uint32_t t, uint32_t *best_i) {
+    NnBestF64 v{qx, qy, qz};
+    nn_walk<NN_QBLOCK>(v, T, stack, t);
 #ifdef ERASOR_HIP_TEST_HOOKS
-    if (nn_effort) {
-        nn_effort[2 * (size_t)(blockIdx.x * NN_QBLOCK + t)] = n_leaves;
-        nn_effort[2 * (size_t)(blockIdx.x * NN_QBLOCK + t) + 1] = n_points;
-    }
+    nn_put_effort(v, (size_t)(blockIdx.x * NN_QBLOCK + t));
 #endif
-    *best_i_out = best_i;
-    return best;
+    *best_i = v.best_i;
+    return v.best;
 }
 
 // (5) one estimated point per lane: its nearest GT point (d^2, then the smaller original index), d = sqrt(d^2) as a bit pattern in
-// dbits, the original index in nearest (optional), the three threshold counters and the maximum.  n_gt > 0.
-__global__ __launch_bounds__(NN_QBLOCK) void k_nn_query(const float4 *__restrict__ est, uint32_t n_est, const float4 *__restrict__ pts,
-                                                         const uint32_t *__restrict__ idx, uint32_t n_gt, const float4 *__restrict__ lo,
-                                                         const float4 *__restrict__ hi, uint32_t n_pad, double half, double one, double two,
+// dbits, the original index in nearest (optional), the three threshold counters and the maximum.  T.n > 0.
+__global__ __launch_bounds__(NN_QBLOCK) void k_nn_query(const float4 *__restrict__ est, uint32_t n_est, NnTree T, double half, double one, double two,
                                                          unsigned long long *__restrict__ dbits, uint32_t *__restrict__ nearest,
                                                          unsigned long long *__restrict__ ctr) {
     __shared__ uint32_t stack[NN_STACK * NN_QBLOCK];  // [depth][lane]: consecutive lanes in consecutive banks
@@ -240,7 +292,7 @@ __global__ __launch_bounds__(NN_QBLOCK) void k_nn_query(const float4 *__restrict
             if (nearest) nearest[i] = 0xFFFFFFFFu;
         } else {
             uint32_t best_i;
-            const double best = nn_search_f64((double)q.x, (double)q.y, (double)q.z, pts, idx, n_gt, lo, hi, n_pad, stack, t, &best_i);
+            const double best = nn_search_f64((double)q.x, (double)q.y, (double)q.z, T, stack, t, &best_i);
             const double d = sqrt(best);
             bh = d < half ? 1u : 0u;
             b1 = d < one ? 1u : 0u;
@@ -264,14 +316,14 @@ __global__ __launch_bounds__(NN_QBLOCK) void k_nn_query(const float4 *__restrict
 // ---- the same tree searched in FLANN's metric: label_map (fill_removert_intensity.cpp:24-59, compare_map.cpp:77-110) and calc_complement
 // (compare_complement.cpp:43-75) query a pcl::KdTreeFLANN, K = 1, whose distance is L2_Simple in float32: r = 0; r += dx*dx; r += dy*dy;
 // r += dz*dz with dx = q.x - p.x in float (FLANN's L2_Simple; no fused multiply-add: -ffp-contract=off), and
-// whose ties go to the lowest index.  The traversal, the LDS stack and the strict pruning are k_nn_query's; only the arithmetic differs.
+// whose ties go to the lowest index.  The traversal, the LDS stack and the strict pruning are nn_walk's; only the visitor's arithmetic differs.
 //
 // Why the pruning stays exact in float: the lower bound is formed by the same float operations on the box gaps, gx = l.x - q.x if
 // q.x < l.x, q.x - u.x if q.x > u.x, else 0, and lb = ((0 + gx*gx) + gy*gy) + gz*gz.  For a point p of the box and q.x < l.x:
 // p.x - q.x >= l.x - q.x exactly, and rounding to nearest is monotone, so fl(p.x - q.x) >= fl(l.x - q.x) = gx >= 0; fl(q.x - p.x) =
 // -fl(p.x - q.x) (rounding to nearest is symmetric), so fl(dx*dx) >= fl(gx*gx).  The same holds for q.x > u.x, and gx = 0 <= |dx|
-// inside.  Sums of non-negative floats are monotone in each term after rounding, so lb <= d^2(p) for every p of the box, and pruning on
-// lb > best never drops a point with d^2 <= best.  Nothing here relies on gradual underflow, but the answer does: a difference of
+// inside.  Sums of non-negative floats are monotone in each term after rounding, so lb <= d^2(p) for every p of the box, as nn_walk
+// requires.  Nothing here relies on gradual underflow, but the answer does: a difference of
 // 1e-20 squares to a subnormal, which flushing would tie with an exact 0.  The library keeps f32 denormals (hipcc's default for
 // gfx950: the kernels' float denorm mode is "flush none"), as the host's float arithmetic does.
 //
@@ -300,95 +352,68 @@ __device__ __forceinline__ float nn_lb_f32(const float4 &l, const float4 &u, flo
     return r;
 }
 
-// the exact float32 1-NN of q over the tree (n > 0, q finite): best d^2, the smallest original index at it, that point's w bits, and
-// whether the points at the minimum carry more than one w bit pattern.  stack: the workgroup's [NN_STACK][NN_QBLOCK] LDS array.
+// visitor: the exact float32 1-NN in FLANN's metric: best d^2, the smallest original index at it, that point's w bits, and whether the
+// points at the minimum carry more than one w bit pattern.  The bound is the best d^2 so far.
 struct NnF32 {
     float d2;
     uint32_t idx, w;
     bool mixed;
 };
-__device__ __forceinline__ NnF32 nn_search_f32(float qx, float qy, float qz, const float4 *__restrict__ pts, const uint32_t *__restrict__ idx,
-                                               uint32_t n, const float4 *__restrict__ lo, const float4 *__restrict__ hi, uint32_t n_pad,
-                                               uint32_t *stack, uint32_t t) {
+struct NnBestF32 {
+    typedef float real;
+    static constexpr bool FIXED = false;
+    float qx, qy, qz;
     NnF32 b{__builtin_huge_valf(), 0xFFFFFFFFu, 0u, false};
-    uint32_t node = 1, sp = 0;
 #ifdef ERASOR_HIP_TEST_HOOKS
-    uint32_t n_leaves = 0, n_points = 0;
+    uint32_t n_leaves = 0, n_points = 0;  // leaves opened, and e - s0 of each
 #endif
-    for (;;) {
-        if (node >= n_pad) {  // a leaf: its points (a leaf that is reached holds at least one)
-            const uint32_t s0 = (node - n_pad) * NN_LEAF, e = s0 + NN_LEAF < n ? s0 + NN_LEAF : n;
+    __device__ __forceinline__ float lb(const float4 &l, const float4 &u) const { return nn_lb_f32(l, u, qx, qy, qz); }
+    __device__ __forceinline__ float bound() const { return b.d2; }
+    __device__ __forceinline__ bool leaf(const NnTree &T, uint32_t s0, uint32_t e) {
 #ifdef ERASOR_HIP_TEST_HOOKS
-            ++n_leaves;
-            n_points += e - s0;
+        ++n_leaves;
+        n_points += e - s0;
 #endif
-            for (uint32_t s = s0; s < e; ++s) {
-                const float4 p = pts[s];
-                const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-                float r = 0.0f;
-                r += dx * dx;
-                r += dy * dy;
-                r += dz * dz;
-                if (r <= b.d2) {
-                    const uint32_t j = idx[s], w = __float_as_uint(p.w);
-                    if (r < b.d2) {
-                        b.d2 = r;
+        for (uint32_t s = s0; s < e; ++s) {
+            const float4 p = T.pts[s];
+            const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
+            float r = 0.0f;
+            r += dx * dx;
+            r += dy * dy;
+            r += dz * dz;
+            if (r <= b.d2) {
+                const uint32_t j = T.idx[s], w = __float_as_uint(p.w);
+                if (r < b.d2) {
+                    b.d2 = r;
+                    b.idx = j;
+                    b.w = w;
+                    b.mixed = false;
+                } else {  // the same d^2: the smaller index is the answer, a second bit pattern makes the query tied
+                    // (idx == ~0u: no candidate yet -- a first point whose d^2 overflowed to +inf equals the seed, not a point)
+                    if (b.idx != 0xFFFFFFFFu && w != b.w) b.mixed = true;
+                    if (j < b.idx) {
                         b.idx = j;
                         b.w = w;
-                        b.mixed = false;
-                    } else {  // the same d^2: the smaller index is the answer, a second bit pattern makes the query tied
-                        // (idx == ~0u: no candidate yet -- a first point whose d^2 overflowed to +inf equals the seed, not a point)
-                        if (b.idx != 0xFFFFFFFFu && w != b.w) b.mixed = true;
-                        if (j < b.idx) {
-                            b.idx = j;
-                            b.w = w;
-                        }
                     }
                 }
             }
-        } else {
-            const uint32_t c = 2 * node;
-            const float4 l0 = lo[c], u0 = hi[c], l1 = lo[c + 1], u1 = hi[c + 1];
-            const float d0 = l0.x <= u0.x ? nn_lb_f32(l0, u0, qx, qy, qz) : __builtin_huge_valf();  // (empty boxes: never entered)
-            const float d1 = l1.x <= u1.x ? nn_lb_f32(l1, u1, qx, qy, qz) : __builtin_huge_valf();
-            const bool v0 = l0.x <= u0.x && !(d0 > b.d2), v1 = l1.x <= u1.x && !(d1 > b.d2);
-            if (v0 && v1) {
-                const uint32_t near = d1 < d0 ? c + 1 : c;
-                stack[sp * NN_QBLOCK + t] = near ^ 1u;  // (sp < the tree's depth <= NN_STACK - 1: one entry per level above)
-                ++sp;
-                node = near;
-                continue;
-            }
-            if (v0 || v1) {
-                node = v0 ? c : c + 1;
-                continue;
-            }
         }
-        bool more = false;  // the next pending sibling that may still hold a point at d^2 <= best
-        while (sp) {
-            --sp;
-            const uint32_t k = stack[sp * NN_QBLOCK + t];
-            if (!(nn_lb_f32(lo[k], hi[k], qx, qy, qz) > b.d2)) {
-                node = k;
-                more = true;
-                break;
-            }
-        }
-        if (!more) break;
+        return false;
     }
+};
+
+// the exact float32 1-NN of q over the tree (T.n > 0, q finite).  stack: the workgroup's [NN_STACK][NN_QBLOCK] LDS array.
+__device__ __forceinline__ NnF32 nn_search_f32(float qx, float qy, float qz, const NnTree &T, uint32_t *stack, uint32_t t) {
+    NnBestF32 v{qx, qy, qz};
+    nn_walk<NN_QBLOCK>(v, T, stack, t);
 #ifdef ERASOR_HIP_TEST_HOOKS
-    if (nn_effort) {
-        nn_effort[2 * (size_t)(blockIdx.x * NN_QBLOCK + t)] = n_leaves;
-        nn_effort[2 * (size_t)(blockIdx.x * NN_QBLOCK + t) + 1] = n_points;
-    }
+    nn_put_effort(v, (size_t)(blockIdx.x * NN_QBLOCK + t));
 #endif
-    return b;
+    return v.b;
 }
 
-// label_map: one centroid per lane; the row out[i] = (centroid x, y, z, w of its nearest medium point, copied as bits).  n_med > 0.
-__global__ __launch_bounds__(NN_QBLOCK) void k_lm_query(const float4 *__restrict__ cent, uint32_t n_q, const float4 *__restrict__ pts,
-                                                         const uint32_t *__restrict__ idx, uint32_t n_med, const float4 *__restrict__ lo,
-                                                         const float4 *__restrict__ hi, uint32_t n_pad, float4 *__restrict__ out,
+// label_map: one centroid per lane; the row out[i] = (centroid x, y, z, w of its nearest medium point, copied as bits).  T.n > 0.
+__global__ __launch_bounds__(NN_QBLOCK) void k_lm_query(const float4 *__restrict__ cent, uint32_t n_q, NnTree T, float4 *__restrict__ out,
                                                          unsigned long long *__restrict__ ctr) {
     __shared__ uint32_t stack[NN_STACK * NN_QBLOCK];
     const uint32_t t = threadIdx.x, i = blockIdx.x * NN_QBLOCK + t;
@@ -399,7 +424,7 @@ __global__ __launch_bounds__(NN_QBLOCK) void k_lm_query(const float4 *__restrict
             bad = 1;
             out[i] = q;
         } else {
-            const NnF32 b = nn_search_f32(q.x, q.y, q.z, pts, idx, n_med, lo, hi, n_pad, stack, t);
+            const NnF32 b = nn_search_f32(q.x, q.y, q.z, T, stack, t);
             out[i] = make_float4(q.x, q.y, q.z, __uint_as_float(b.w));
             tied = b.mixed ? 1u : 0u;
         }
@@ -409,11 +434,9 @@ __global__ __launch_bounds__(NN_QBLOCK) void k_lm_query(const float4 *__restrict
 }
 
 // static_complement: one ground-truth point per lane; lost[i] = 1 when the point is static and its nearest estimated point's float
-// d^2, widened to double, is > thr (calc_complement's `pointNKNSquaredDistance[0] > 0.03`: a float against a double literal).  n_est == 0:
+// d^2, widened to double, is > thr (calc_complement's `pointNKNSquaredDistance[0] > 0.03`: a float against a double literal).  T.n == 0:
 // every static point is lost (d^2 = +inf).
-__global__ __launch_bounds__(NN_QBLOCK) void k_cp_query(const float4 *__restrict__ gt, uint32_t n_gt, const float4 *__restrict__ pts,
-                                                         const uint32_t *__restrict__ idx, uint32_t n_est, const float4 *__restrict__ lo,
-                                                         const float4 *__restrict__ hi, uint32_t n_pad, double thr, uint32_t *__restrict__ lost,
+__global__ __launch_bounds__(NN_QBLOCK) void k_cp_query(const float4 *__restrict__ gt, uint32_t n_gt, NnTree T, double thr, uint32_t *__restrict__ lost,
                                                          unsigned long long *__restrict__ ctr) {
     __shared__ uint32_t stack[NN_STACK * NN_QBLOCK];
     const uint32_t t = threadIdx.x, i = blockIdx.x * NN_QBLOCK + t;
@@ -424,7 +447,7 @@ __global__ __launch_bounds__(NN_QBLOCK) void k_cp_query(const float4 *__restrict
             bad = 1;
         } else if (!ev_is_dynamic(q.w, oor)) {
             sta = 1;
-            const float d2 = n_est ? nn_search_f32(q.x, q.y, q.z, pts, idx, n_est, lo, hi, n_pad, stack, t).d2 : __builtin_huge_valf();
+            const float d2 = T.n ? nn_search_f32(q.x, q.y, q.z, T, stack, t).d2 : __builtin_huge_valf();
             ls = (double)d2 > thr ? 1u : 0u;
         }
         lost[i] = ls;

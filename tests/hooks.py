@@ -96,7 +96,7 @@ def debug_set_scan_one_max(g, n):
 
 
 def debug_nn_tree(g, cloud):
-    """the bounding-volume tree nn_pad / nn_tree build over `cloud` (N x 4 rows): P, the points in key order, their original indices,
+    """the bounding-volume tree nn_build builds over `cloud` (N x 4 rows): P, the points in key order, their original indices,
     the sorted Morton keys, lo / hi of the 2P nodes (node 0 is unused)"""
     cloud = np.ascontiguousarray(cloud, np.float32).reshape(-1, 4)
     n = len(cloud)

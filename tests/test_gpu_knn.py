@@ -2,7 +2,7 @@
 kernels in knn.hip.h) against their host restatement evalmap.knn / radius_count / density_filter (and the all-pairs knn_brute /
 radius_count_brute): byte for byte in neighbour lists, distances, scores, counts, mask, kept cloud and result.  Ties at the k-th place,
 one float32 step at the k-th place, at the radius and at the threshold, pairs a radius apart at every cell border, duplicates, short
-clouds, every size around the leaf, wavefront, workgroup and tree padding, degenerate boxes, the prefix property, the sequential mean,
+clouds, every size around the leaf, wavefront, workgroup and tree padding, k = 1 and the radius count on one padded tree, degenerate boxes, the prefix property, the sequential mean,
 every score with every rule, the buffers, the errors and the struct layout, the synthetic world, a 200 000-point cloud, the handle's
 map and a step after it.  tests/test_knn_on_cpu.py re-runs this file against the CPU stand-in."""
 import ctypes as C
@@ -283,6 +283,32 @@ def test_sizes_around_the_leaf_the_wavefront_the_workgroup_and_the_tree_padding(
 @pytest.mark.parametrize("k", [2, 7, 9, 16, 17, 31])
 def test_every_list_class_at_257_points(handle, k):
     check_knn(handle, blob(257, k), k, ref=evalmap.knn_brute, what="k classes")
+
+
+def test_the_nearest_other_point_and_the_radius_count_agree_on_a_padded_tree(handle):
+    """1025 points: 33 leaves under a tree padded to 64, so whole subtrees are empty boxes.  Among them 40 identical points (every one of
+    them ties with 39 others at distance 0) and, far outside, three points 0.5 apart on a line (the middle one ties between its two
+    neighbours).  knn(k = 1) is the float64 nearest OTHER point as the all-pairs restatement gives it, and radius_count(0.5) > 0 holds
+    exactly where that distance is <= 0.5 -- a distance the tail hits with equality."""
+    rng = np.random.default_rng(1025)
+    xyz = rng.uniform(-4, 4, (1025, 3)).astype(np.float32)
+    at = rng.permutation(1025)
+    dup, tail = at[:40], at[40:43]
+    xyz[dup] = [1.5, -2.25, 0.125]
+    xyz[tail] = [[20.0, 20.0, 20.0], [20.5, 20.0, 20.0], [21.0, 20.0, 20.0]]
+    cloud, r = xyzi(xyz), 0.5
+    want = evalmap.knn_brute(cloud, 1, True)
+    d, j = want["nbr_dist"][:, 0], want["nbr_idx"][:, 0]
+    near = d <= r
+    # the case itself, on the host alone: r is hit with equality, both sides of it occur, and the count's predicate (d2 <= r * r) says the same
+    assert (d[tail] == r).all() and j[tail[1]] == min(tail[0], tail[2]) and (d[dup] == 0).all() and 43 < near.sum() < 1025 - 43
+    assert all(j[i] == min(k for k in dup if k != i) for i in dup)
+    assert ((evalmap.radius_count_brute(cloud, r)[0] > 0) == near).all()
+    got = handle.knn(cloud, 1, True)
+    assert got["nbr_idx"][:, 0].tobytes() == j.tobytes(), np.flatnonzero(got["nbr_idx"][:, 0] != j)[:5]
+    assert got["nbr_dist"][:, 0].tobytes() == d.tobytes(), np.flatnonzero(got["nbr_dist"][:, 0] != d)[:5]
+    cnt = handle.radius_count(cloud, r)[0]
+    assert ((cnt > 0) == near).all(), np.flatnonzero((cnt > 0) != near)[:5]
 
 
 # ---- 6. degenerate boxes ----

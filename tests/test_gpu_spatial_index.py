@@ -1,4 +1,4 @@
-"""The two spatial indexes tested AS INDEXES: the bounding-volume tree of nearest.hip.h (nn_pad / nn_tree in erasor_hip.hip: Morton keys,
+"""The two spatial indexes tested AS INDEXES: the bounding-volume tree of nearest.hip.h (nn_build in analysis_host.hip.h: Morton keys,
 the 30-bit radix sort, leaves of 32 points, the per-lane depth-first search) behind overlap, align_frames, label_map and
 static_complement, and the hashed uniform grid of evaluate.hip.h (k_ev_hist / k_ev_offsets / k_ev_scatter, and evaluate_many's combined
 table) behind evaluate, evaluate_by_class and evaluate_many.
