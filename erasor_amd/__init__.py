@@ -78,6 +78,32 @@ class AlignRow(C.Structure):
         return d
 
 
+class RefineParams(C.Structure):
+    """erasor_refine_params (include/erasor_hip.h)"""
+    _fields_ = [("max_dist", C.c_double), ("eps_t", C.c_double), ("eps_r", C.c_double), ("max_iters", C.c_uint32), ("min_pairs", C.c_uint32)]
+
+
+class RefineRow(C.Structure):
+    """erasor_refine_row (include/erasor_hip.h): one frame of refine_poses"""
+    _fields_ = [("T", C.c_double * 16), ("status", C.c_uint32), ("iters", C.c_uint32)] + [(k, C.c_uint64) for k in (
+        "n_points", "n_non_finite", "n_pairs_first", "n_pairs_last")] + [(k, C.c_double) for k in ("rms_first", "rms_last", "moved_t", "moved_r")]
+
+    def as_dict(self):
+        """evalmap.refine_poses' row keys (the pose itself is returned beside the rows)"""
+        return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_ if k != "T"}
+
+
+class RefineSummary(C.Structure):
+    """erasor_refine_summary (include/erasor_hip.h)"""
+    _fields_ = [("n_frames", C.c_uint64), ("n_status", C.c_uint64 * 4), ("n_pairs_first", C.c_uint64), ("n_pairs_last", C.c_uint64),
+                ("sum_d2_first", C.c_double), ("sum_d2_last", C.c_double)]
+
+    def as_dict(self):
+        """evalmap.refine_poses' summary keys"""
+        return {"n_frames": int(self.n_frames), "n_status": [int(v) for v in self.n_status], "n_pairs_first": int(self.n_pairs_first),
+                "n_pairs_last": int(self.n_pairs_last), "sum_d2_first": float(self.sum_d2_first), "sum_d2_last": float(self.sum_d2_last)}
+
+
 class ScanLabelRow(C.Structure):
     """erasor_scan_label_row (include/erasor_hip.h): one frame of label_scans, or their sum"""
     _fields_ = [("n_points", C.c_uint64), ("n_non_finite", C.c_uint64), ("n_label_out_of_range", C.c_uint64), ("n", (C.c_uint64 * 3) * 2)]
@@ -323,7 +349,7 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "render.hip.h", "revert_bins.hip.h",
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "render.hip.h", "revert_bins.hip.h",
                                                  "exact_sort.hip.h", "exact_sort_core.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
@@ -875,6 +901,42 @@ class Erasor:
             m = self._eval_cloud(map, kept)
             self._check(lib().erasor_hip_align_frames_clouds(self._h, *m, *tail))
         return [rows[f].as_dict() for f in range(n_f)], summ.as_dict()
+
+    # -- every frame's pose refined against the map: point-to-point ICP (on the host: evalmap.refine_poses) --
+    def refine_poses(self, scans, T_body2origin, T_lidar2body=None, map=None, max_dist=1.0, eps_t=1e-4, eps_r=1e-5, max_iters=20, min_pairs=100):
+        """Every frame's T_body2origin refined against `map` (a cloud as for evaluate; None: the handle's current map) by point-to-point
+        ICP, all frames side by side (erasor_hip_refine_poses_clouds / _map): per iteration every scan point's exact nearest map point,
+        the pairs within max_dist, Horn's closed-form update, until the update is below eps_t (metres) and eps_r (radians) or max_iters
+        updates were made; a frame with fewer than min_pairs pairs keeps its pose.  scans, poses and T_lidar2body as for align_frames.
+        Returns (T_refined float64 [n, 4, 4], rows, summary) as evalmap.refine_poses does, bit for bit."""
+        kept = []
+        if isinstance(scans, tuple):
+            ptr, offsets = scans
+            offs = np.ascontiguousarray(offsets, np.uint64)
+            q = (C.c_void_p(ptr), C.c_size_t(int(offs[-1]) if len(offs) else 0), 1)
+        else:
+            a = [_f32(s).reshape(-1, 4) for s in scans]
+            offs = np.zeros(len(a) + 1, np.uint64)
+            offs[1:] = np.cumsum([len(s) for s in a], dtype=np.uint64)
+            cat = _f32(np.concatenate(a) if a else np.zeros((0, 4), np.float32))
+            kept.append(cat)
+            q = (_p(cat), C.c_size_t(len(cat)), 0)
+        n_f = len(offs) - 1
+        Tb = _f32(np.asarray(T_body2origin, np.float32).reshape(n_f, 16) if n_f else np.zeros((1, 16), np.float32))
+        if T_lidar2body is not None:
+            kept.append(_f32(T_lidar2body).reshape(16))
+        Tl = None if T_lidar2body is None else _p(kept[-1])
+        prm = RefineParams(float(max_dist), float(eps_t), float(eps_r), int(max_iters), int(min_pairs))
+        rows = (RefineRow * max(n_f, 1))()
+        summ = RefineSummary()
+        tail = (q[0], q[1], _p(offs), C.c_size_t(n_f), C.c_int(q[2]), Tl, _p(Tb), C.byref(prm), rows, C.byref(summ))
+        if map is None:
+            self._check(lib().erasor_hip_refine_poses_map(self._h, *tail))
+        else:
+            m = self._eval_cloud(map, kept)
+            self._check(lib().erasor_hip_refine_poses_clouds(self._h, *m, *tail))
+        T = np.array([list(rows[f].T) for f in range(n_f)], np.float64).reshape(n_f, 4, 4)
+        return T, [rows[f].as_dict() for f in range(n_f)], summ.as_dict()
 
     # -- every scan's points labelled static or moving from a cleaned map (on the host: evalmap.label_scans) --
     def label_scans(self, scans, T_body2origin, T_lidar2body=None, static_map=None, raw_map=None, tau=None, voxelsize=0.2, split=None):

@@ -733,6 +733,284 @@ int erasor_hip_align_frames_map(erasor_hip_handle *h, const void *scans_xyzi, si
     return al_run(h, who, m, n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, voxelsize, rows, summary);
 }
 
+// ---- every frame's pose refined against the map: point-to-point ICP, all frames side by side (kernels: refine.hip.h) ----
+// Like al_run: the main stream, the evaluator's scratch, the map's tree built once and sorted in bank 2.  Per iteration, for the live
+// frames together: the poses and live flags up, k_rf_query and k_rf_partials, the frames' sums and counters back, and the solve below
+// on the host -- a few dozen flops per frame, in + - * / and sqrt on doubles only (this file is compiled with -ffp-contract=off), so that
+// evalmap.refine_poses, in plain Python floats, restates it bit for bit.
+
+// cyclic Jacobi on the symmetric 4x4 A: pivots (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), until every element above the diagonal is exactly
+// zero before a sweep, or 32 sweeps.  A's diagonal: the eigenvalues; V's columns: the eigenvectors.
+static void rf_jacobi4(double A[4][4], double V[4][4]) {
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 32; ++sweep) {
+        if (A[0][1] == 0.0 && A[0][2] == 0.0 && A[0][3] == 0.0 && A[1][2] == 0.0 && A[1][3] == 0.0 && A[2][3] == 0.0) break;
+        for (int p = 0; p < 3; ++p)
+            for (int q = p + 1; q < 4; ++q) {
+                const double apq = A[p][q];
+                if (apq == 0.0) continue;
+                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+                const double at = theta < 0.0 ? -theta : theta;
+                double t = 1.0 / (at + sqrt(theta * theta + 1.0));
+                if (theta < 0.0) t = -t;
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < 4; ++k) {  // A <- A J
+                    const double akp = A[k][p], akq = A[k][q];
+                    A[k][p] = c * akp - s * akq;
+                    A[k][q] = s * akp + c * akq;
+                }
+                for (int k = 0; k < 4; ++k) {  // A <- Jt A
+                    const double apk = A[p][k], aqk = A[q][k];
+                    A[p][k] = c * apk - s * aqk;
+                    A[q][k] = s * apk + c * aqk;
+                }
+                A[p][q] = 0.0;
+                for (int i = 0; i < 4; ++i)
+                    for (int j = i + 1; j < 4; ++j) A[j][i] = A[i][j];
+                for (int k = 0; k < 4; ++k) {  // V <- V J
+                    const double vkp = V[k][p], vkq = V[k][q];
+                    V[k][p] = c * vkp - s * vkq;
+                    V[k][q] = s * vkp + c * vkq;
+                }
+            }
+    }
+}
+
+// one frame's update from its sums S (RF_NSUM) over n >= 1 pairs: Horn's quaternion from the centred cross-covariance, R <- dR R,
+// t <- t + delta.  *step_t: |delta|; *step_r: 2 |q_xyz| of the unit quaternion (w >= 0).
+static void rf_solve(const double *S, uint64_t n, RfPose &P, double *step_t, double *step_r) {
+    const double nn = (double)n;
+    double mq[3], mm[3], H[3][3];
+    for (int a = 0; a < 3; ++a) {
+        mq[a] = S[a] / nn;
+        mm[a] = S[3 + a] / nn;
+    }
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) H[a][b] = S[6 + 3 * a + b] - (S[a] * S[3 + b]) / nn;
+    double N[4][4], V[4][4];
+    N[0][0] = (H[0][0] + H[1][1]) + H[2][2];
+    N[0][1] = H[1][2] - H[2][1];
+    N[0][2] = H[2][0] - H[0][2];
+    N[0][3] = H[0][1] - H[1][0];
+    N[1][1] = (H[0][0] - H[1][1]) - H[2][2];
+    N[1][2] = H[0][1] + H[1][0];
+    N[1][3] = H[2][0] + H[0][2];
+    N[2][2] = (H[1][1] - H[0][0]) - H[2][2];
+    N[2][3] = H[1][2] + H[2][1];
+    N[3][3] = (H[2][2] - H[0][0]) - H[1][1];
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j) N[j][i] = N[i][j];
+    rf_jacobi4(N, V);
+    int k = 0;  // the largest eigenvalue, the first of equal ones
+    for (int i = 1; i < 4; ++i)
+        if (N[i][i] > N[k][k]) k = i;
+    double w = V[0][k], x = V[1][k], y = V[2][k], z = V[3][k];
+    if (w < 0.0) {
+        w = -w;
+        x = -x;
+        y = -y;
+        z = -z;
+    }
+    const double nrm = sqrt(((w * w + x * x) + y * y) + z * z);
+    w = w / nrm;
+    x = x / nrm;
+    y = y / nrm;
+    z = z / nrm;
+    const double xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
+    const double D[3][3] = {{1.0 - 2.0 * (yy + zz), 2.0 * (xy - wz), 2.0 * (xz + wy)},
+                            {2.0 * (xy + wz), 1.0 - 2.0 * (xx + zz), 2.0 * (yz - wx)},
+                            {2.0 * (xz - wy), 2.0 * (yz + wx), 1.0 - 2.0 * (xx + yy)}};
+    double d[3], R[9];
+    for (int a = 0; a < 3; ++a) d[a] = mm[a] - ((D[a][0] * mq[0] + D[a][1] * mq[1]) + D[a][2] * mq[2]);
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) R[3 * a + b] = (D[a][0] * P.R[b] + D[a][1] * P.R[3 + b]) + D[a][2] * P.R[6 + b];
+    for (int e = 0; e < 9; ++e) P.R[e] = R[e];
+    for (int a = 0; a < 3; ++a) P.t[a] = P.t[a] + d[a];
+    *step_t = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    *step_r = 2.0 * sqrt((xx + yy) + zz);
+}
+
+static int rf_check_args(erasor_hip_handle *h, const char *who, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets,
+                         size_t n_frames, const float *T_lidar2body, const float *T_body2origin, const erasor_refine_params *p) {
+    if (!p) return invalid(h, who, "params is NULL");
+    if (p->max_iters < 1 || p->max_iters > 64) return invalid(h, who, "max_iters must be 1 .. 64");
+    if (!(p->max_dist > 0) || !std::isfinite(p->max_dist)) return invalid(h, who, "max_dist must be a finite number > 0");
+    if (!(p->eps_t > 0) || !std::isfinite(p->eps_t)) return invalid(h, who, "eps_t must be a finite number > 0");
+    if (!(p->eps_r > 0) || !std::isfinite(p->eps_r)) return invalid(h, who, "eps_r must be a finite number > 0");
+    if (n_frames > 65536) return invalid(h, who, "more than 65536 frames");
+    if (!offsets) return invalid(h, who, "offsets is NULL (n_frames + 1 entries)");
+    if (n_frames && !T_body2origin) return invalid(h, who, "T_body2origin is NULL");
+    const int rc = check_scan_offsets(h, who, scans_xyzi, n_scan_points, offsets, n_frames);
+    if (rc) return rc;
+    if (T_lidar2body && !all_finite(T_lidar2body, 16)) return invalid(h, who, "non-finite entry in T_lidar2body");
+    return ERASOR_OK;
+}
+
+static int rf_run(erasor_hip_handle *h, const char *who, const float4 *map, uint32_t n_map, const float4 *scans, uint32_t n, const uint64_t *offsets,
+                  uint32_t n_frames, const float *T_lidar2body, const float *T_body2origin, const erasor_refine_params &prm, erasor_refine_row *rows,
+                  erasor_refine_summary *summary) {
+    auto &E = h->ev;
+    if (!n_map && n) {
+        h->err = std::string(who) + ": empty map with a non-empty frame (no nearest point to match)";
+        return ERASOR_E_INVALID;
+    }
+    const uint32_t nf = std::max(n_frames, 1u);
+    // the frames' chunks of RF_CHUNK points, counted from each frame's own first point
+    std::vector<uint32_t> off(n_frames + 1), cb(n_frames + 1, 0u);
+    for (uint32_t f = 0; f <= n_frames; ++f) off[f] = (uint32_t)offsets[f];
+    for (uint32_t f = 0; f < n_frames; ++f) cb[f + 1] = cb[f] + cdiv(off[f + 1] - off[f], RF_CHUNK);
+    const uint32_t grid = cb[n_frames];  // (<= n / 256 + n_frames)
+    std::vector<RfChunk> chunks(grid);
+    for (uint32_t f = 0; f < n_frames; ++f)
+        for (uint32_t b = cb[f]; b < cb[f + 1]; ++b) chunks[b] = RfChunk{f, b - cb[f]};
+    if (ensure(h, E.al_off, (size_t)nf + 1) || ensure(h, E.rf_cb, (size_t)nf + 1) || ensure(h, E.rf_chunk, (size_t)grid + 1) || ensure(h, E.rf_pose, nf) ||
+        ensure(h, E.rf_live, nf) || ensure(h, E.rf_part, ((size_t)grid + 1) * RF_NSUM) || ensure(h, E.rf_sums, (size_t)nf * RF_NSUM) ||
+        ensure(h, E.rf_ctr, (size_t)nf * RF_NCTR))
+        return ERASOR_E_NO_DEVICE;
+    NnTree T;
+    int rc = nn_build(h, map, n_map, who, "map", "map point(s)", &T);
+    if (rc) return rc;
+    HIPC(h, hipMemcpyAsync(E.al_off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(E.rf_cb.p, cb.data(), cb.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    if (grid) HIPC(h, hipMemcpyAsync(E.rf_chunk.p, chunks.data(), (size_t)grid * sizeof(RfChunk), hipMemcpyHostToDevice, h->stream));
+    const Xf Tl = to_xf(T_lidar2body ? T_lidar2body : AL_IDENTITY);
+    const double gate2 = prm.max_dist * prm.max_dist;
+    const uint64_t min_pairs = std::max(prm.min_pairs, 1u);
+
+    std::vector<RfPose> P(nf), P0(nf);
+    for (uint32_t f = 0; f < n_frames; ++f) {  // the float32 pose, widened
+        const float *Tf = T_body2origin + 16 * (size_t)f;
+        for (int a = 0; a < 3; ++a) {
+            for (int b = 0; b < 3; ++b) P[f].R[3 * a + b] = (double)Tf[4 * a + b];
+            P[f].t[a] = (double)Tf[4 * a + 3];
+        }
+        P0[f] = P[f];
+    }
+    std::vector<uint32_t> live(nf, 1u), status(nf, ERASOR_REFINE_MAX_ITERS), iters(nf, 0u);
+    std::vector<double> S((size_t)nf * RF_NSUM, 0.0), d2_first(nf, 0.0);
+    std::vector<unsigned long long> c((size_t)nf * RF_NCTR, 0ull), pairs_first(nf, 0ull), non_finite(nf, 0ull);
+    // the live frames' sums and counters under the poses P (into S and c; a frame that is not live keeps what it had)
+    auto evaluate = [&]() -> int {
+        if (!n_frames) return ERASOR_OK;
+        HIPC(h, hipMemcpyAsync(E.rf_pose.p, P.data(), (size_t)n_frames * sizeof(RfPose), hipMemcpyHostToDevice, h->stream));
+        HIPC(h, hipMemcpyAsync(E.rf_live.p, live.data(), (size_t)n_frames * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        HIPC(h, hipMemsetAsync(E.rf_ctr.p, 0, (size_t)n_frames * RF_NCTR * sizeof(unsigned long long), h->stream));
+        if (grid)
+            LAUNCH(h, h->stream, "rf_query", k_rf_query, grid, NN_QBLOCK, scans, (const uint32_t *)E.al_off.p, (const RfChunk *)E.rf_chunk.p, Tl,
+                   (const RfPose *)E.rf_pose.p, (const uint32_t *)E.rf_live.p, map, T, gate2, E.rf_part.p, E.rf_ctr.p);
+        LAUNCH(h, h->stream, "rf_partials", k_rf_partials, cdiv(n_frames * RF_NSUM, 256), 256, (const double *)E.rf_part.p, (const uint32_t *)E.rf_cb.p,
+               (const uint32_t *)E.rf_live.p, n_frames, E.rf_sums.p);
+        HIPC(h, hipMemcpyAsync(S.data(), E.rf_sums.p, (size_t)n_frames * RF_NSUM * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipMemcpyAsync(c.data(), E.rf_ctr.p, (size_t)n_frames * RF_NCTR * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
+        return ERASOR_OK;
+    };
+    uint32_t n_live = n_frames;
+    for (uint32_t it = 1; it <= prm.max_iters && n_live; ++it) {
+        if ((rc = evaluate())) return rc;
+        for (uint32_t f = 0; f < n_frames; ++f) {
+            if (!live[f]) continue;
+            const uint64_t np = c[(size_t)f * RF_NCTR + RF_PAIRS];
+            if (it == 1) {
+                pairs_first[f] = np;
+                d2_first[f] = S[(size_t)f * RF_NSUM + 15];
+                non_finite[f] = c[(size_t)f * RF_NCTR + RF_NON_FINITE];
+            }
+            if (np < min_pairs) {  // the frame keeps the pose it has
+                status[f] = (uint64_t)(off[f + 1] - off[f]) == non_finite[f] ? ERASOR_REFINE_NO_POINTS : ERASOR_REFINE_FEW_PAIRS;
+                live[f] = 0;
+                --n_live;
+                continue;
+            }
+            double st, sr;
+            rf_solve(&S[(size_t)f * RF_NSUM], np, P[f], &st, &sr);
+            iters[f] = it;
+            if (st <= prm.eps_t && sr <= prm.eps_r) {
+                status[f] = ERASOR_REFINE_CONVERGED;
+                live[f] = 0;
+                --n_live;
+            }
+        }
+    }
+    // the returned poses' pairs and distances: one more evaluation of every frame, nothing updated
+    std::fill(live.begin(), live.end(), 1u);
+    if ((rc = evaluate())) return rc;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    erasor_refine_summary sm;
+    memset(&sm, 0, sizeof(sm));
+    sm.n_frames = n_frames;
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const uint64_t np = c[(size_t)f * RF_NCTR + RF_PAIRS];
+        const double d2 = S[(size_t)f * RF_NSUM + 15];
+        sm.n_status[status[f]] += 1;
+        sm.n_pairs_first += pairs_first[f];
+        sm.n_pairs_last += np;
+        sm.sum_d2_first = sm.sum_d2_first + d2_first[f];
+        sm.sum_d2_last = sm.sum_d2_last + d2;
+        if (!rows) continue;
+        erasor_refine_row r;
+        memset(&r, 0, sizeof(r));
+        const RfPose &A = P[f], &B = P0[f];
+        for (int a = 0; a < 3; ++a) {
+            for (int b = 0; b < 3; ++b) r.T[4 * a + b] = A.R[3 * a + b];
+            r.T[4 * a + 3] = A.t[a];
+        }
+        r.T[15] = 1.0;
+        r.status = status[f];
+        r.iters = iters[f];
+        r.n_points = off[f + 1] - off[f];
+        r.n_non_finite = non_finite[f];
+        r.n_pairs_first = pairs_first[f];
+        r.n_pairs_last = np;
+        r.rms_first = pairs_first[f] ? sqrt(d2_first[f] / (double)pairs_first[f]) : nan;
+        r.rms_last = np ? sqrt(d2 / (double)np) : nan;
+        const double dx = A.t[0] - B.t[0], dy = A.t[1] - B.t[1], dz = A.t[2] - B.t[2];
+        r.moved_t = sqrt((dx * dx + dy * dy) + dz * dz);
+        double tr = 0.0;  // trace of R R0t: the rows' dot products, one after another
+        for (int a = 0; a < 3; ++a) tr = tr + ((A.R[3 * a] * B.R[3 * a] + A.R[3 * a + 1] * B.R[3 * a + 1]) + A.R[3 * a + 2] * B.R[3 * a + 2]);
+        double cs = (tr - 1.0) / 2.0;
+        if (cs > 1.0) cs = 1.0;
+        if (cs < -1.0) cs = -1.0;
+        r.moved_r = acos(cs);
+        rows[f] = r;
+    }
+    if (summary) *summary = sm;
+    return ERASOR_OK;
+}
+
+int erasor_hip_refine_poses_clouds(erasor_hip_handle *h, const void *map_xyzi, size_t n_map, int map_is_device, const void *scans_xyzi,
+                                   size_t n_scan_points, const uint64_t *offsets, size_t n_frames, int scans_are_device,
+                                   const float T_lidar2body[16], const float *T_body2origin, const erasor_refine_params *params,
+                                   erasor_refine_row *rows, erasor_refine_summary *summary) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_refine_poses_clouds";
+    int rc = rf_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, params);
+    if (rc || (rc = check_cloud(h, who, "NULL map or more than 2^30 map points", map_xyzi, n_map))) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr, *q = nullptr;
+    if ((rc = ev_input(h, map_xyzi, n_map, map_is_device, h->ev.gt, &m)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q)))
+        return rc;
+    return rf_run(h, who, m, (uint32_t)n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, *params, rows,
+                  summary);
+}
+
+int erasor_hip_refine_poses_map(erasor_hip_handle *h, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                                int scans_are_device, const float T_lidar2body[16], const float *T_body2origin, const erasor_refine_params *params,
+                                erasor_refine_row *rows, erasor_refine_summary *summary) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_refine_poses_map";
+    int rc = rf_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, params);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr, *q = nullptr;
+    uint32_t n_map = 0;
+    if ((rc = map_on_device(h, who, h->ev.map, &m, &n_map)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q))) return rc;
+    return rf_run(h, who, m, n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, *params, rows, summary);
+}
+
 // ---- every scan's points labelled static / dynamic / unknown from a cleaned map (kernels: label_scans.hip.h) ----
 // Like al_run: the main stream, the evaluator's scratch, the trees' sorts in bank 2.  One tree is resident at a time: the static map's,
 // then -- for the points the static pass left -- the raw map's in the same scratch; a host raw map is brought in only then, into the

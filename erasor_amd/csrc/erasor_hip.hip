@@ -37,6 +37,7 @@
 #include "evaluate.hip.h"
 #include "nearest.hip.h"
 #include "align.hip.h"
+#include "refine.hip.h"
 #include "label_scans.hip.h"
 #include "cluster.hip.h"
 #include "knn.hip.h"
@@ -352,6 +353,13 @@ struct erasor_hip_handle {
         DBuf<Xf> al_xf;
         DBuf<unsigned long long> al_ctr, al_val;
         DBuf<AlRanks> al_rank;
+        // every frame's pose refined against the map (erasor_hip_refine_poses_*): the same tree, the offsets in al_off; every workgroup's
+        // chunk, the frames' first chunks, poses and live flags, the chunk partials, the frames' sums and counters
+        DBuf<RfChunk> rf_chunk;
+        DBuf<RfPose> rf_pose;
+        DBuf<uint32_t> rf_cb, rf_live;
+        DBuf<double> rf_part, rf_sums;
+        DBuf<unsigned long long> rf_ctr;
         // K estimates against one ground truth (erasor_hip_evaluate_many): the estimates back to back, their table, counters per estimate
         // and one row for the ground truth (the combined bucket table and the bucketed points: cnt, pl, tops, bkt, pts, idx above)
         DBuf<float4> em_cat;
@@ -1135,6 +1143,8 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->ev.nn_ctr); release(h->ev.nn_dbits);
     release(h->ev.fm_out); release(h->ev.fm_flag); release(h->ev.fm_pl); release(h->ev.fm_tops); release(h->ev.fm_ctr);
     release(h->ev.al_off); release(h->ev.al_wg); release(h->ev.al_xf); release(h->ev.al_ctr); release(h->ev.al_val); release(h->ev.al_rank);
+    release(h->ev.rf_chunk); release(h->ev.rf_pose); release(h->ev.rf_cb); release(h->ev.rf_live); release(h->ev.rf_part); release(h->ev.rf_sums);
+    release(h->ev.rf_ctr);
     release(h->ev.em_cat); release(h->ev.em_tab); release(h->ev.em_ctr);
     release(h->ev.rd_pts); release(h->ev.rd_map); release(h->ev.rd_tile); release(h->ev.rd_cnt); release(h->ev.rd_pl); release(h->ev.rd_tops);
     release(h->ev.rd_bb); release(h->ev.rd_rec); release(h->ev.rd_srt); release(h->ev.rd_ctr); release(h->ev.rd_zb); release(h->ev.rd_img);

@@ -1085,6 +1085,173 @@ static int align_mode(int argc, char **argv) {
     return 0;
 }
 
+// --refine <rosparam.yaml> <poses_out> [n_frames] [max_dist = 1.0] [max_iters = 20]: what to do about the frames --align flags.  The same
+// files and poses as --align (data_dir, init_idx, poses_lidar2body.csv after callback_node's round trip, the initial map, tf/lidar2body);
+// every frame's T_body2origin is refined against the initial map by point-to-point ICP (erasor_hip_refine_poses_clouds).  One line per
+// frame: --align's "<0.5*v" percentage before and after (erasor_hip_align_frames_clouds, twice, voxelsize 0.2) and the frame's row; a frame
+// is flagged when it did not converge or moved more than max_dist.  Writes <poses_out> in poses_lidar2body.csv's own format -- the
+// file's lines as they are, x y z qx qy qz qw of the refined frames replaced (17 digits; a frame without enough pairs keeps its line) --
+// so that it can take the pose file's place in the run.
+static void rot_to_quat(const double *T, double q[4]) {  // (x y z w) of T's rotation (row-major 4x4): the largest of the four pivots
+    const double r00 = T[0], r01 = T[1], r02 = T[2], r10 = T[4], r11 = T[5], r12 = T[6], r20 = T[8], r21 = T[9], r22 = T[10];
+    const double tr = r00 + r11 + r22;
+    if (tr > 0) {
+        const double s = std::sqrt(tr + 1.0) * 2;
+        q[3] = 0.25 * s, q[0] = (r21 - r12) / s, q[1] = (r02 - r20) / s, q[2] = (r10 - r01) / s;
+    } else if (r00 > r11 && r00 > r22) {
+        const double s = std::sqrt(1.0 + r00 - r11 - r22) * 2;
+        q[3] = (r21 - r12) / s, q[0] = 0.25 * s, q[1] = (r01 + r10) / s, q[2] = (r02 + r20) / s;
+    } else if (r11 > r22) {
+        const double s = std::sqrt(1.0 + r11 - r00 - r22) * 2;
+        q[3] = (r02 - r20) / s, q[0] = (r01 + r10) / s, q[1] = 0.25 * s, q[2] = (r12 + r21) / s;
+    } else {
+        const double s = std::sqrt(1.0 + r22 - r00 - r11) * 2;
+        q[3] = (r10 - r01) / s, q[0] = (r02 + r20) / s, q[1] = (r12 + r21) / s, q[2] = 0.25 * s;
+    }
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int k = 0; k < 4; ++k) q[k] /= n;
+}
+static int refine_mode(int argc, char **argv) {
+    if (argc < 4) return 2;
+    const std::string out_path = argv[3];
+    const int max_frames = argc > 4 ? atoi(argv[4]) : 1 << 30;
+    erasor_refine_params prm = {argc > 5 ? atof(argv[5]) : 1.0, 1e-4, 1e-5, (uint32_t)(argc > 6 ? atoi(argv[6]) : 20), 100};
+    const double voxelsize = 0.2;
+    erasor::OfflineMapUpdater::Config cfg;
+    erasor_hip_params_default(&cfg.params);
+    erasor::DriverConfig drv;
+    if (!erasor::load_config_yaml(argv[2], cfg, &drv)) {
+        fprintf(stderr, "cannot read %s\n", argv[2]);
+        return 3;
+    }
+    if (cfg.initial_map_path.empty() || cfg.initial_map_path == "/") cfg.initial_map_path = drv.data_dir + "/dense_global_map.pcd";
+    const std::string pose_path = drv.data_dir + "/poses_lidar2body.csv";
+    std::vector<Eigen::Matrix4f> poses;
+    if (!erasor::load_all_poses(pose_path, poses)) {
+        fprintf(stderr, "cannot read %s\n", pose_path.c_str());
+        return 3;
+    }
+    std::vector<float> map, scans, Tb;
+    if (!load_cloud_xyzi(cfg.initial_map_path, map)) {
+        fprintf(stderr, "cannot read %s\n", cfg.initial_map_path.c_str());
+        return 3;
+    }
+    std::vector<uint64_t> offsets{0};
+    const int last = std::min((int)poses.size(), drv.init_idx + max_frames);
+    for (int i = drv.init_idx; i < last; ++i) {
+        char name[64];
+        snprintf(name, sizeof(name), "/pcds/%06d.pcd", i);
+        std::vector<float> scan;
+        if (!load_cloud_xyzi(drv.data_dir + name, scan)) {
+            fprintf(stderr, "cannot read %s%s\n", drv.data_dir.c_str(), name);
+            return 3;
+        }
+        scans.insert(scans.end(), scan.begin(), scan.end());
+        offsets.push_back(scans.size() / 4);
+        const Eigen::Matrix4f T = erasor_utils::geoPose2eigen(erasor_utils::eigen2geoPose(poses[i]));  // (callback_node's round trip)
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) Tb.push_back(T(r, c));
+    }
+    geometry_msgs::Pose l2b;
+    l2b.position.x = cfg.lidar2body[0];
+    l2b.position.y = cfg.lidar2body[1];
+    l2b.position.z = cfg.lidar2body[2];
+    l2b.orientation.x = cfg.lidar2body[3];
+    l2b.orientation.y = cfg.lidar2body[4];
+    l2b.orientation.z = cfg.lidar2body[5];
+    l2b.orientation.w = cfg.lidar2body[6];
+    const Eigen::Matrix4f TL = erasor_utils::geoPose2eigen(l2b);  // (OMU.cpp:100)
+    float Tl[16];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) Tl[4 * r + c] = TL(r, c);
+    erasor_params p;
+    erasor_hip_params_default(&p);
+    erasor_hip_handle *h = nullptr;
+    if (erasor_hip_create(&p, 0, &h) != ERASOR_OK) {
+        fprintf(stderr, "erasor_hip_create failed\n");
+        return 1;
+    }
+    const size_t n_frames = offsets.size() - 1;
+    std::vector<erasor_align_row> before(std::max<size_t>(n_frames, 1)), after(std::max<size_t>(n_frames, 1));
+    std::vector<erasor_refine_row> rows(std::max<size_t>(n_frames, 1));
+    erasor_refine_summary sum;
+    std::vector<float> Tr(Tb.size());
+    int rc = erasor_hip_align_frames_clouds(h, map.data(), map.size() / 4, 0, scans.data(), scans.size() / 4, offsets.data(), n_frames, 0, Tl, Tb.data(),
+                                            voxelsize, before.data(), nullptr);
+    if (!rc)
+        rc = erasor_hip_refine_poses_clouds(h, map.data(), map.size() / 4, 0, scans.data(), scans.size() / 4, offsets.data(), n_frames, 0, Tl, Tb.data(),
+                                            &prm, rows.data(), &sum);
+    if (!rc) {
+        for (size_t f = 0; f < n_frames; ++f)
+            for (int k = 0; k < 16; ++k) Tr[16 * f + k] = (float)rows[f].T[k];
+        rc = erasor_hip_align_frames_clouds(h, map.data(), map.size() / 4, 0, scans.data(), scans.size() / 4, offsets.data(), n_frames, 0, Tl, Tr.data(),
+                                            voxelsize, after.data(), nullptr);
+    }
+    if (rc) {
+        fprintf(stderr, "refine: %s (rc %d)\n", erasor_hip_last_error(h), rc);
+        erasor_hip_destroy(h);
+        return 1;
+    }
+    erasor_hip_destroy(h);
+    static const char *const STATUS[4] = {"converged", "iteration limit", "too few pairs", "no finite points"};
+    printf("%zu frames against %s (%zu points), max_dist %.3f m, at most %u iterations:\n", n_frames, cfg.initial_map_path.c_str(), map.size() / 4,
+           prm.max_dist, prm.max_iters);
+    for (size_t f = 0; f < n_frames; ++f) {
+        const erasor_refine_row &r = rows[f];
+        const bool flag = r.status != ERASOR_REFINE_CONVERGED || r.moved_t > prm.max_dist;
+        printf("%6d  n=%llu  <0.5*v %.2f%% -> %.2f%%  %s after %u  pairs %llu -> %llu  rms %.4fm -> %.4fm  moved %.4fm %.5frad%s\n",
+               drv.init_idx + (int)f, (unsigned long long)r.n_points, before[f].r.frac_half, after[f].r.frac_half, STATUS[r.status & 3u], r.iters,
+               (unsigned long long)r.n_pairs_first, (unsigned long long)r.n_pairs_last, r.rms_first, r.rms_last, r.moved_t, r.moved_r,
+               flag ? (r.status != ERASOR_REFINE_CONVERGED ? "  <- not converged: check this pose" : "  <- moved more than max_dist: check this pose") : "");
+    }
+    printf("summary: %llu converged, %llu at the iteration limit, %llu with too few pairs, %llu without finite points; pairs %llu -> %llu, "
+           "rms %.4fm -> %.4fm\n",
+           (unsigned long long)sum.n_status[0], (unsigned long long)sum.n_status[1], (unsigned long long)sum.n_status[2],
+           (unsigned long long)sum.n_status[3], (unsigned long long)sum.n_pairs_first, (unsigned long long)sum.n_pairs_last,
+           sum.n_pairs_first ? std::sqrt(sum.sum_d2_first / (double)sum.n_pairs_first) : 0.0,
+           sum.n_pairs_last ? std::sqrt(sum.sum_d2_last / (double)sum.n_pairs_last) : 0.0);
+    // the pose file again, line by line: the header and every pose outside the refined range as they are
+    std::ifstream in(pose_path);
+    std::ofstream out(out_path);
+    if (!in || !out) {
+        fprintf(stderr, "cannot write %s\n", out_path.c_str());
+        return 1;
+    }
+    std::string line;
+    int row = -1;  // the line's pose index (the header: -1), counted as load_all_poses counts
+    bool header = true;
+    while (std::getline(in, line)) {
+        if (header) {
+            header = false;
+            out << line << "\n";
+            continue;
+        }
+        size_t c1 = line.find(','), c2 = c1 == std::string::npos ? c1 : line.find(',', c1 + 1);
+        if (c2 == std::string::npos) {  // (a blank line: load_all_poses skips it too)
+            out << line << "\n";
+            continue;
+        }
+        ++row;
+        const int f = row - drv.init_idx;
+        if (f < 0 || f >= (int)n_frames || rows[f].status >= ERASOR_REFINE_FEW_PAIRS) {
+            out << line << "\n";
+            continue;
+        }
+        double q[4];
+        rot_to_quat(rows[f].T, q);
+        char buf[256];
+        snprintf(buf, sizeof(buf), "%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g", rows[f].T[3], rows[f].T[7], rows[f].T[11], q[0], q[1], q[2], q[3]);
+        out << line.substr(0, c2 + 1) << buf << "\n";
+    }
+    out.close();
+    if (!out) {
+        fprintf(stderr, "cannot write %s\n", out_path.c_str());
+        return 1;
+    }
+    printf("wrote %s\n", out_path.c_str());
+    return 0;
+}
+
 // --label-scans <rosparam.yaml> <static.pcd> <raw.pcd|-> <out_dir> [n_frames] [tau]: a cleaned map carried back to the scans
 // (erasor_hip_label_scans_clouds).  The same files and poses as --align (data_dir, init_idx, poses_lidar2body.csv after callback_node's
 // round trip, tf/lidar2body); every scan point is static (a point of <static.pcd> within tau), dynamic, or -- with a raw map -- unknown
@@ -1580,6 +1747,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && std::string(argv[1]) == "--refine") {
+        try {
+            return refine_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--label-scans") {
         try {
             return label_scans_mode(argc, argv);
@@ -1645,11 +1820,12 @@ int main(int argc, char **argv) {
                 "       %s --sweep <rosparam.yaml> <grid.yaml> <gt> [n_frames] [voxelsize] [concurrency]\n"
                 "       %s --eval-many <voxelsize> <voxel_leaf> <gt> <est1> [<est2> ...]\n"
                 "       %s --label-scans <rosparam.yaml> <static.pcd> <raw.pcd|-> <out_dir> [n_frames] [tau]\n"
+                "       %s --refine <rosparam.yaml> <poses_out> [n_frames] [max_dist] [max_iters]\n"
                 "       %s --clusters <cloud.pcd> <tol> [min_size] [max_size] [kept_out.pcd]\n"
                 "       %s --residue <gt> <est> [tol] [voxelsize] [voxel_leaf]\n"
                 "       %s --denoise <in.pcd> <out.pcd> sor <k> <mul> | ror <radius> <min_neighbors> | kth <k> <thr>\n"
                 "       %s --density <cloud.pcd> <k>\n",
-                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

@@ -14,6 +14,8 @@ reference's label_map (src/utils/fill_removert_intensity.cpp:24-59) and calc_com
 
 align_frames: overlap() of every frame's scan, put into the map frame by its pose, against the map (Erasor.align_frames).
 
+refine_poses: every frame's pose refined against the map by point-to-point ICP, every sum in one defined order (Erasor.refine_poses).
+
 label_scans / moving_iou: every scan's points labelled static / dynamic / unknown from a cleaned map, against the scan's own labels
 (Erasor.label_scans).
 
@@ -208,6 +210,252 @@ def moving_iou(summary):
         return float(a) / float(b) if b else float("nan")
 
     return {"TP": tp, "FP": fp, "FN": fn, "IoU": ratio(tp, tp + fp + fn), "precision": ratio(tp, tp + fp), "recall": ratio(tp, tp + fn)}
+
+
+# ---- refine_poses: every frame's pose refined against the map by point-to-point ICP (Erasor.refine_poses, refine.hip.h) ----
+REFINE_CONVERGED, REFINE_MAX_ITERS, REFINE_FEW_PAIRS, REFINE_NO_POINTS = 0, 1, 2, 3  # ERASOR_REFINE_*
+REFINE_CHUNK = 256   # RF_CHUNK: the sums' chunks, counted from each frame's own first point
+REFINE_NSUM = 16     # RF_NSUM: sum q' (3), sum m' (3), sum q' m't row-major (9), sum d2
+REFINE_ROW_FIELDS = ("status", "iters", "n_points", "n_non_finite", "n_pairs_first", "n_pairs_last", "rms_first", "rms_last", "moved_t", "moved_r")
+REFINE_SUMMARY_FIELDS = ("n_frames", "n_status", "n_pairs_first", "n_pairs_last", "sum_d2_first", "sum_d2_last")
+
+
+def _ieee_div(a, b):
+    """a / b on Python floats as IEEE 754 defines it where Python raises (b == 0)"""
+    import math
+    try:
+        return a / b
+    except ZeroDivisionError:
+        if a != a or a == 0.0:
+            return float("nan")
+        return math.copysign(float("inf"), a) * math.copysign(1.0, b)
+
+
+def nearest_f64(map64, tree, q):
+    """the exact float64 1-NN of every row of q (finite) in map64 (its cKDTree: `tree`): (d2, j) with d2 by pair_d2 and the lowest index
+    among the points at the minimum.  The tree only proposes candidates; a row whose last candidate is not strictly beyond its best is
+    redone over every map point."""
+    n, nm = len(q), len(map64)
+    if n == 0:
+        return np.zeros(0), np.zeros(0, np.int64)
+    kk = min(10, nm)
+    dist, cand = tree.query(q, k=kk, workers=-1)
+    dist, cand = dist.reshape(n, kk), cand.reshape(n, kk).astype(np.int64)
+    d2 = pair_d2(q[:, None, :], map64[cand])
+    by_j = np.argsort(cand, axis=1, kind="stable")
+    cand, d2 = np.take_along_axis(cand, by_j, 1), np.take_along_axis(d2, by_j, 1)
+    by_d = np.argsort(d2, axis=1, kind="stable")
+    best_j, best = np.take_along_axis(cand, by_d, 1)[:, 0].copy(), np.take_along_axis(d2, by_d, 1)[:, 0].copy()
+    if kk < nm:  # (the tree's own distances are a few ulps off the predicate's: 1e-9 relative is far above that)
+        redo = np.flatnonzero(~(best < dist[:, -1] * dist[:, -1] * (1 - 1e-9)))
+        for lo in range(0, len(redo), 256):
+            r = redo[lo:lo + 256]
+            full = pair_d2(q[r, None, :], map64[None, :, :])
+            j = np.argmin(full, axis=1)  # (the first of equal minima: the lowest index)
+            best_j[r], best[r] = j, full[np.arange(len(r)), j]
+    return best, best_j
+
+
+def refine_tree_sum(v):
+    """the defined sum of one frame's per-point rows v (n, k), in scan order: chunks of 256 from the frame's first point, padded with +0.0;
+    inside a chunk the halving tree v[i] += v[i + s] for s = 128 .. 1; the chunks' partials one after another from 0.0.  Returns (k,)"""
+    n, k = v.shape
+    nc = -(-n // REFINE_CHUNK)
+    pad = np.zeros((nc * REFINE_CHUNK, k))
+    pad[:n] = v
+    c = pad.reshape(nc, REFINE_CHUNK, k)
+    s = REFINE_CHUNK // 2
+    while s >= 1:
+        c = c[:, :s] + c[:, s:2 * s]
+        s //= 2
+    total = np.zeros(k)
+    for b in range(nc):
+        total = total + c[b, 0]
+    return total
+
+
+def _jacobi4(A):
+    """cyclic Jacobi on the symmetric 4x4 A (lists of Python floats, changed in place): pivots (0,1) (0,2) (0,3) (1,2) (1,3) (2,3),
+    until every element above the diagonal is exactly zero before a sweep, or 32 sweeps.  Returns V (columns: eigenvectors)"""
+    from math import sqrt
+    V = [[1.0 if i == j else 0.0 for j in range(4)] for i in range(4)]
+    for _ in range(32):
+        if A[0][1] == 0.0 and A[0][2] == 0.0 and A[0][3] == 0.0 and A[1][2] == 0.0 and A[1][3] == 0.0 and A[2][3] == 0.0:
+            break
+        for p in range(3):
+            for q in range(p + 1, 4):
+                apq = A[p][q]
+                if apq == 0.0:
+                    continue
+                theta = _ieee_div(A[q][q] - A[p][p], 2.0 * apq)
+                at = -theta if theta < 0.0 else theta
+                t = _ieee_div(1.0, at + sqrt(theta * theta + 1.0))
+                if theta < 0.0:
+                    t = -t
+                c = _ieee_div(1.0, sqrt(t * t + 1.0))
+                s = t * c
+                for k in range(4):
+                    akp, akq = A[k][p], A[k][q]
+                    A[k][p] = c * akp - s * akq
+                    A[k][q] = s * akp + c * akq
+                for k in range(4):
+                    apk, aqk = A[p][k], A[q][k]
+                    A[p][k] = c * apk - s * aqk
+                    A[q][k] = s * apk + c * aqk
+                A[p][q] = 0.0
+                for i in range(4):
+                    for j in range(i + 1, 4):
+                        A[j][i] = A[i][j]
+                for k in range(4):
+                    vkp, vkq = V[k][p], V[k][q]
+                    V[k][p] = c * vkp - s * vkq
+                    V[k][q] = s * vkp + c * vkq
+    return V
+
+
+def refine_solve(S, n, R, t):
+    """one frame's update from its sums S (16 Python floats) over n >= 1 pairs: Horn's quaternion from the centred cross-covariance by
+    _jacobi4, R <- dR R, t <- t + delta.  R: 9 floats row-major, t: 3.  Returns (R, t, |delta|, 2 |q_xyz|)"""
+    from math import sqrt
+    nn = float(n)
+    mq = [S[a] / nn for a in range(3)]
+    mm = [S[3 + a] / nn for a in range(3)]
+    H = [[S[6 + 3 * a + b] - (S[a] * S[3 + b]) / nn for b in range(3)] for a in range(3)]
+    N = [[0.0] * 4 for _ in range(4)]
+    N[0][0] = (H[0][0] + H[1][1]) + H[2][2]
+    N[0][1] = H[1][2] - H[2][1]
+    N[0][2] = H[2][0] - H[0][2]
+    N[0][3] = H[0][1] - H[1][0]
+    N[1][1] = (H[0][0] - H[1][1]) - H[2][2]
+    N[1][2] = H[0][1] + H[1][0]
+    N[1][3] = H[2][0] + H[0][2]
+    N[2][2] = (H[1][1] - H[0][0]) - H[2][2]
+    N[2][3] = H[1][2] + H[2][1]
+    N[3][3] = (H[2][2] - H[0][0]) - H[1][1]
+    for i in range(4):
+        for j in range(i + 1, 4):
+            N[j][i] = N[i][j]
+    V = _jacobi4(N)
+    k = 0
+    for i in range(1, 4):
+        if N[i][i] > N[k][k]:
+            k = i
+    w, x, y, z = V[0][k], V[1][k], V[2][k], V[3][k]
+    if w < 0.0:
+        w, x, y, z = -w, -x, -y, -z
+    nrm = sqrt(((w * w + x * x) + y * y) + z * z)
+    w, x, y, z = _ieee_div(w, nrm), _ieee_div(x, nrm), _ieee_div(y, nrm), _ieee_div(z, nrm)
+    xx, yy, zz, xy, xz, yz, wx, wy, wz = x * x, y * y, z * z, x * y, x * z, y * z, w * x, w * y, w * z
+    D = [[1.0 - 2.0 * (yy + zz), 2.0 * (xy - wz), 2.0 * (xz + wy)],
+         [2.0 * (xy + wz), 1.0 - 2.0 * (xx + zz), 2.0 * (yz - wx)],
+         [2.0 * (xz - wy), 2.0 * (yz + wx), 1.0 - 2.0 * (xx + yy)]]
+    d = [mm[a] - ((D[a][0] * mq[0] + D[a][1] * mq[1]) + D[a][2] * mq[2]) for a in range(3)]
+    Rn = [(D[a][0] * R[b] + D[a][1] * R[3 + b]) + D[a][2] * R[6 + b] for a in range(3) for b in range(3)]
+    tn = [t[a] + d[a] for a in range(3)]
+    return Rn, tn, sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]), 2.0 * sqrt((xx + yy) + zz)
+
+
+def refine_frame_sums(map64, tree, p32, R, t, gate2, nearest=nearest_f64):
+    """one frame's sums under the pose (R, t): p32 the body points (float32, T_lidar2body applied).  Returns (S (16,), pairs, points
+    without a query).  q' = R p and q = q' + t in float64, rows as ((a*x + b*y) + c*z); the pairs: d2 <= gate2; m' = map[j] - t"""
+    n = len(p32)
+    p = p32.astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        r = np.stack([(R[3 * a] * p[:, 0] + R[3 * a + 1] * p[:, 1]) + R[3 * a + 2] * p[:, 2] for a in range(3)], 1)
+        q = r + np.asarray(t, np.float64)[None, :]
+    ok = np.isfinite(p32).all(1) & np.isfinite(q).all(1)
+    v = np.zeros((n, REFINE_NSUM))
+    pairs = 0
+    if ok.any():
+        d2, j = nearest(map64, tree, q[ok])
+        inl = d2 <= gate2
+        rows = np.flatnonzero(ok)[inl]
+        rr = r[rows]
+        m = map64[j[inl]] - np.asarray(t, np.float64)[None, :]
+        v[rows, 0:3] = rr
+        v[rows, 3:6] = m
+        for a in range(3):
+            for b in range(3):
+                v[rows, 6 + 3 * a + b] = rr[:, a] * m[:, b]
+        v[rows, 15] = d2[inl]
+        pairs = int(inl.sum())
+    return refine_tree_sum(v), pairs, int((~ok).sum())
+
+
+def refine_poses(map_xyz, scans, T_body2origin, T_lidar2body=None, max_dist=1.0, eps_t=1e-4, eps_r=1e-5, max_iters=20, min_pairs=100,
+                 nearest=nearest_f64):
+    """Every frame's T_body2origin refined against the map by point-to-point ICP with a fixed gate: the host restatement of
+    Erasor.refine_poses (include/erasor_hip.h, erasor_refine_row), operation for operation.  Per frame: p = T_lidar2body · scan row in
+    float32 (the identity when None, still applied); the pose (R, t) in float64 from the float32 T_body2origin[f]; per iteration
+    refine_frame_sums and refine_solve, until the update is <= eps_t and <= eps_r (status 0) or max_iters updates (1); a frame with fewer
+    than max(min_pairs, 1) pairs keeps its pose (2; 3 when no point has finite coordinates under the input pose).  Returns
+    (T float64 [n, 4, 4], rows, summary): REFINE_ROW_FIELDS per frame, REFINE_SUMMARY_FIELDS."""
+    import math
+    if not (1 <= int(max_iters) <= 64):
+        raise ValueError("refine_poses: max_iters must be 1 .. 64")
+    for name, val in (("max_dist", max_dist), ("eps_t", eps_t), ("eps_r", eps_r)):
+        if not (np.isfinite(val) and val > 0):
+            raise ValueError("refine_poses: %s must be a finite number > 0" % name)
+    map32 = np.asarray(map_xyz, np.float32).reshape(-1, 3)
+    map64 = map32.astype(np.float64)
+    tree = cKDTree(map64) if len(map64) else None
+    if tree is None and any(len(s) for s in scans):
+        raise ValueError("refine_poses: empty map with a non-empty frame (no nearest point to match)")
+    Tl = np.eye(4, dtype=np.float32) if T_lidar2body is None else T_lidar2body
+    gate2 = float(max_dist) * float(max_dist)
+    need = max(int(min_pairs), 1)
+    nan = float("nan")
+    n_f = len(scans)
+    T_out = np.zeros((n_f, 4, 4))
+    rows = []
+    summary = {"n_frames": n_f, "n_status": [0, 0, 0, 0], "n_pairs_first": 0, "n_pairs_last": 0, "sum_d2_first": 0.0, "sum_d2_last": 0.0}
+    for f, scan in enumerate(scans):  # (the frames do not interact: one after the other here, side by side on the device)
+        xyz = np.asarray(scan, np.float32).reshape(len(scan), 4)[:, :3]
+        with np.errstate(over="ignore", invalid="ignore"):
+            p32 = _xform(Tl, xyz)
+        T0 = np.asarray(T_body2origin[f], np.float32).reshape(4, 4)
+        R0 = [float(T0[a, b]) for a in range(3) for b in range(3)]
+        t0 = [float(T0[a, 3]) for a in range(3)]
+        R, t = list(R0), list(t0)
+        status, iters = REFINE_MAX_ITERS, 0
+        pairs_first, d2_first, bad_first = 0, 0.0, 0
+        for it in range(1, int(max_iters) + 1):
+            S, pairs, bad = refine_frame_sums(map64, tree, p32, R, t, gate2, nearest)
+            if it == 1:
+                pairs_first, d2_first, bad_first = pairs, float(S[15]), bad
+            if pairs < need:
+                status = REFINE_NO_POINTS if bad_first == len(xyz) else REFINE_FEW_PAIRS
+                break
+            R, t, st, sr = refine_solve([float(s) for s in S], pairs, R, t)
+            iters = it
+            if st <= eps_t and sr <= eps_r:
+                status = REFINE_CONVERGED
+                break
+        S, pairs_last, _ = refine_frame_sums(map64, tree, p32, R, t, gate2, nearest)
+        d2_last = float(S[15])
+        for a in range(3):
+            T_out[f, a, :3] = R[3 * a:3 * a + 3]
+            T_out[f, a, 3] = t[a]
+        T_out[f, 3, 3] = 1.0
+        dx, dy, dz = t[0] - t0[0], t[1] - t0[1], t[2] - t0[2]
+        tr = 0.0
+        for a in range(3):
+            tr = tr + ((R[3 * a] * R0[3 * a] + R[3 * a + 1] * R0[3 * a + 1]) + R[3 * a + 2] * R0[3 * a + 2])
+        cs = (tr - 1.0) / 2.0
+        if cs > 1.0:
+            cs = 1.0
+        if cs < -1.0:
+            cs = -1.0
+        rows.append({"status": status, "iters": iters, "n_points": int(len(xyz)), "n_non_finite": bad_first, "n_pairs_first": pairs_first,
+                     "n_pairs_last": pairs_last, "rms_first": math.sqrt(d2_first / float(pairs_first)) if pairs_first else nan,
+                     "rms_last": math.sqrt(d2_last / float(pairs_last)) if pairs_last else nan,
+                     "moved_t": math.sqrt((dx * dx + dy * dy) + dz * dz), "moved_r": math.acos(cs)})
+        summary["n_status"][status] += 1
+        summary["n_pairs_first"] += pairs_first
+        summary["n_pairs_last"] += pairs_last
+        summary["sum_d2_first"] = summary["sum_d2_first"] + d2_first
+        summary["sum_d2_last"] = summary["sum_d2_last"] + d2_last
+    return T_out, rows, summary
 
 
 def _l2_simple(q, p):

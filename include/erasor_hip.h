@@ -492,6 +492,68 @@ int erasor_hip_align_frames_map(erasor_hip_handle *h, const void *scans_xyzi, si
                                 int scans_are_device, const float T_lidar2body[16], const float *T_body2origin, double voxelsize,
                                 erasor_align_row *rows, erasor_overlap_result *summary);
 
+/* ---- every frame's pose refined against the map: point-to-point ICP, all frames side by side -----------------------------------
+ * replaces: "fix the poses in your SLAM and come back" -- the reference README's first pitfall (pose_i · pcds/00000<i>.pcd must
+ * overlay on dense_global_map.pcd) names the fault, erasor_hip_align_frames_* finds the frames, and this moves them.  Frame f is the
+ * scans' points [offsets[f], offsets[f + 1]) put into the map frame as the reference puts a scan there (OfflineMapUpdater.cpp:238-242,
+ * 441-449): p = T_lidar2body · row in float32 (NULL: the identity, still applied), then q = R·p + t with the frame's pose in float64,
+ * which starts as the float32 T_body2origin[f] widened.  Per iteration: every q's exact nearest map point (ties to the lowest index),
+ * the pairs with d^2 <= max_dist * max_dist, Horn's closed-form rigid update from their sums, until the update's translation is
+ * <= eps_t and its rotation angle (2 |q_xyz| of the unit quaternion) <= eps_r, or max_iters updates.  Every sum is taken in one
+ * defined order, so the result is the host restatement's (evalmap.refine_poses) bit for bit.  No re-orthonormalisation:
+ * max_iters <= 64 keeps R's drift at rounding level. */
+typedef struct erasor_refine_params {
+    double max_dist;     /* the correspondence gate, > 0 */
+    double eps_t;        /* stop: |translation update| <= eps_t ... */
+    double eps_r;        /* ... and rotation update <= eps_r (radians) */
+    uint32_t max_iters;  /* 1 .. 64 */
+    uint32_t min_pairs;  /* a frame with fewer pairs keeps the pose it has and ends (0 counts as 1) */
+} erasor_refine_params;
+
+#define ERASOR_REFINE_CONVERGED  0  /* the last update was below eps_t and eps_r */
+#define ERASOR_REFINE_MAX_ITERS  1  /* max_iters updates made */
+#define ERASOR_REFINE_FEW_PAIRS  2  /* fewer than min_pairs pairs: the pose of the iteration before (first iteration: the input, bit for bit) */
+#define ERASOR_REFINE_NO_POINTS  3  /* no point with finite coordinates under the input pose (an empty frame too) */
+
+typedef struct erasor_refine_row {
+    double T[16];            /* the refined T_body2origin, row-major: R, t, and 0 0 0 1 */
+    uint32_t status;         /* ERASOR_REFINE_* */
+    uint32_t iters;          /* updates applied */
+    uint64_t n_points;       /* points of the frame as given */
+    uint64_t n_non_finite;   /* without a query under the input pose: a non-finite coordinate after T_lidar2body or after the pose */
+    uint64_t n_pairs_first;  /* pairs within the gate under the input pose ... */
+    uint64_t n_pairs_last;   /* ... and under T */
+    double rms_first;        /* sqrt(sum of the pairs' d^2 / pairs) under the input pose; NaN without a pair ... */
+    double rms_last;         /* ... and under T */
+    double moved_t;          /* |t - t_input| */
+    double moved_r;          /* the angle of R · R_inputᵀ from its trace: acos of (trace - 1) / 2 clamped to [-1, 1] */
+} erasor_refine_row;
+
+typedef struct erasor_refine_summary {
+    uint64_t n_frames;
+    uint64_t n_status[4];    /* frames by ERASOR_REFINE_* */
+    uint64_t n_pairs_first;  /* the rows' totals, added in frame order */
+    uint64_t n_pairs_last;
+    double sum_d2_first;
+    double sum_d2_last;
+} erasor_refine_summary;
+
+/* Map, scans, offsets, T_lidar2body and T_body2origin as erasor_hip_align_frames_clouds takes them, except that a non-finite entry of
+ * T_body2origin is not refused: that frame's points have no query and it ends with ERASOR_REFINE_NO_POINTS.  rows: n_frames entries or
+ * NULL; summary: optional.  Works in the evaluator's own scratch, like erasor_hip_align_frames_clouds; the map's tree is built once.
+ * ERASOR_E_INVALID: params NULL, max_iters outside 1 .. 64, max_dist / eps_t / eps_r not a finite number > 0, the offsets' and sizes'
+ * errors of erasor_hip_align_frames_clouds, a non-finite map point or T_lidar2body entry, an empty map with a non-empty frame.
+ * ERASOR_E_STATE: a step in flight. */
+int erasor_hip_refine_poses_clouds(erasor_hip_handle *h, const void *map_xyzi, size_t n_map, int map_is_device,
+                                   const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                                   int scans_are_device, const float T_lidar2body[16], const float *T_body2origin,
+                                   const erasor_refine_params *params, erasor_refine_row *rows, erasor_refine_summary *summary);
+/* the same against the handle's current map (compacted on the device as erasor_hip_align_frames_map does, never copied to the host).
+ * ERASOR_E_STATE also: no map. */
+int erasor_hip_refine_poses_map(erasor_hip_handle *h, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                                int scans_are_device, const float T_lidar2body[16], const float *T_body2origin,
+                                const erasor_refine_params *params, erasor_refine_row *rows, erasor_refine_summary *summary);
+
 /* ---- every scan's points labelled static or moving from a cleaned map ---------------------------------------------------------
  * replaces: what users of a cleaned map do on the host afterwards -- a KD-tree over the cleaned map, a radius test per scan point, the
  * scan's moving points dropped (automatic moving-object-segmentation labels, cleaned scans for re-mapping); the reference itself stops
