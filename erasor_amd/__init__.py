@@ -32,6 +32,13 @@ class Params(C.Structure):
     ]
 
 
+class StepLogEntry(C.Structure):
+    """erasor_step_log_entry (include/erasor_hip.h)"""
+    _fields_ = [("step", C.c_uint64), ("period_us", C.c_double), ("n_alloc", C.c_uint32), ("n_free", C.c_uint32), ("n_create", C.c_uint32),
+                ("reserved", C.c_uint8), ("use_ov", C.c_uint8), ("deep", C.c_uint8), ("sampled", C.c_uint8), ("ova_mode", C.c_uint8),
+                ("ova_block", C.c_uint8), ("ova_skip", C.c_uint8), ("grown", C.c_uint8)]
+
+
 class StepResult(C.Structure):
     """erasor_step_result (include/erasor_hip.h)"""
     _fields_ = [(k, C.c_uint64) for k in (
@@ -350,7 +357,7 @@ class ErasorError(RuntimeError):
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "render.hip.h", "revert_bins.hip.h",
-                                                 "exact_sort.hip.h", "exact_sort_core.h")]
+                                                 "exact_sort.hip.h", "exact_sort_core.h", "overlap_auto.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _SRC_DIR, "-s"])
@@ -1209,6 +1216,15 @@ class Erasor:
         m, a, b = C.c_int(0), C.c_double(0), C.c_double(0)
         self._check(lib().erasor_hip_overlap_auto(self._h, C.byref(m), C.byref(a), C.byref(b)))
         return m.value, a.value, b.value
+
+    def step_log(self):
+        """the last collected steps (up to 256), oldest first, as dicts: step, period_us (0: not consecutive), n_alloc / n_free / n_create
+        (allocations, frees, stream or event creations inside the step's calls and the announcements before it), reserved, use_ov, deep,
+        sampled, grown (1: map scratch enlarged, 2: outskirts rebuilt), and the overlap decision's mode / block / skip before the step's sample (erasor_hip_step_log)"""
+        buf = (StepLogEntry * 256)()
+        n = C.c_size_t(0)
+        self._check(lib().erasor_hip_step_log(self._h, buf, C.c_size_t(256), C.byref(n)))
+        return [{f: getattr(buf[k], f) for f, _ in StepLogEntry._fields_} for k in range(n.value)]
 
     def chain_batch(self, n_scans, lead=3):
         """the query chains of `n_scans` announced nodes share one set of launches (erasor_hip_chain_batch); 1: every chain on its own"""

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/erasor_hip.h"
+#include "overlap_auto.h"
 #ifndef ERASOR_REV_GRID
 #define ERASOR_REV_GRID 128u  // workgroups of the per-bin launch (one reverted bin each; more bins than workgroups: a grid-stride loop)
 #endif
@@ -243,21 +244,18 @@ struct erasor_hip_handle {
     unsigned long long tm_last_open = 0;
     uint64_t tm_n = 0, tm_ngap = 0, tm_nper = 0;
     // ERASOR_HIP_OVERLAP unset: the handle decides by measurement whether consecutive steps overlap (round 5 had a threshold fitted to the
-    // five bench workloads here).  The period of a step -- end to end on the device's own clock, consecutive steps only -- is sampled in
-    // blocks: plain, overlapped, overlapped, plain (OVA_W samples each; a sequence drifts -- its first steps revert more bins --, and
-    // this order cancels a linear drift; the first OVA_SKIP samples after a change of mode are not counted), and the mode with the
-    // shorter mean period runs on (plain has to lose by 2 %).  Measured again every OVA_AGAIN steps.  Results never depend on it.
-    struct OvAuto {
-        int mode = 0;            // 1: overlapped, 0: plain -- what the next step uses
-        int block = 0;           // 0..3: the block being sampled (modes 0 1 1 0); 4: decided
-        int skip = 4;            // samples still to be ignored (start-up, a change of mode)
-        int n = 0;               // samples of the current block
-        double sum[2] = {0, 0};
-        double mx[2] = {0, 0};   // the largest sample of each mode: left out of its mean (one hiccup in eight samples must not decide 600 steps)
-        int cnt[2] = {0, 0};
-        double est[2] = {0, 0};  // the last decision's mean periods (0: not measured)
-        unsigned long long since_decision = 0;
-    } ova;
+    // five bench workloads here): overlap_auto.h.  Results never depend on it.
+    OvAuto ova;
+    // the last STEP_LOG_N collected steps (erasor_hip_step_log), and what is counted into the next record where it is made: device and
+    // pinned allocations, frees, stream / event creations (ensure, early_stream, copy_stream, get_evt -- the worker thread's launches
+    // take events too --, stage_host_scan)
+    static constexpr unsigned STEP_LOG_N = 256;
+    erasor_step_log_entry slog[STEP_LOG_N];
+    unsigned long long slog_n = 0;
+    std::atomic<uint32_t> n_alloc{0}, n_free{0}, n_create{0};
+    std::atomic<int> log_scope{0};  // > 0 inside a step's calls and an announcement (LogScope): only then are they counted -- a getter's scratch is not a step's cost
+    uint8_t grown_now = 0;  // 1: grow_map_scratch, 2: rebuild_outskirts ran since the last collected step
+    bool ov_ready = false;  // the early stream was created at the first deep step (step_plan_reserve), ahead of the first overlapped step
     unsigned long long tm_last_end = 0, tm_last_seq = 0;
     unsigned long long step_seq = 0;  // steps issued so far (k_step_end echoes it into the pinned block)
     // a step that has been enqueued (erasor_hip_step_async) and not collected yet (erasor_hip_step_wait)
@@ -275,6 +273,7 @@ struct erasor_hip_handle {
         uint32_t nchunks = 0;     // chunk count of the step's own VoI pass (grid hint of a split launched ahead later)
         bool spec_launched = false;
         bool reserved = false;    // the write-back uses the reserved layout (round 5)
+        bool use_ov = false;      // the step took the passes launched ahead of it (the record, erasor_hip_step_log)
         bool deep = false;        // the caller had announced at least batch_lead nodes beyond this step (OvAuto samples only such steps)
     } fly;
     HostOut *pin = nullptr;         // pinned host block k_step_end reports into
@@ -429,6 +428,19 @@ struct erasor_hip_handle {
 
 namespace {
 
+// the calls whose allocations and creations go into the per-step record: a step's two halves and the announcements
+struct LogScope {
+    erasor_hip_handle *h;
+    explicit LogScope(erasor_hip_handle *h_) : h(h_) {
+        if (h) ++h->log_scope;
+    }
+    ~LogScope() {
+        if (h) --h->log_scope;
+    }
+    LogScope(const LogScope &) = delete;
+    LogScope &operator=(const LogScope &) = delete;
+};
+
 const bool g_debug_sync = getenv("ERASOR_HIP_DEBUG_SYNC") != nullptr;  // bring-up aid: sync + log every launch
 
 #define HIPC(h, call)                                                                         \
@@ -446,11 +458,13 @@ int ensure(erasor_hip_handle *h, DBuf<T> &b, size_t n, bool keep = false) {
     T *np = nullptr;
     size_t ncap = n + n / 8 + 64;
     HIPC(h, hipMalloc((void **)&np, ncap * sizeof(T)));
+    h->n_alloc += h->log_scope > 0;
     if (keep && b.p) HIPC(h, hipMemcpyAsync(np, b.p, b.cap * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
     if (b.p) {
         HIPC(h, hipStreamSynchronize(h->stream));
         if (h->bstream) HIPC(h, hipStreamSynchronize(h->bstream));  // (passes launched ahead of the next step may be writing the old block)
         (void)hipFree(b.p);
+        h->n_free += h->log_scope > 0;
     }
     b.p = np;
     b.cap = ncap;
@@ -471,6 +485,7 @@ hipEvent_t get_evt(erasor_hip_handle *h) {
     }
     hipEvent_t e;
     (void)hipEventCreate(&e);
+    h->n_create += h->log_scope > 0;
     return e;
 }
 int prof_id(erasor_hip_handle *h, const char *name) {
@@ -672,6 +687,7 @@ int grow_map_scratch(erasor_hip_handle *h, uint64_t need) {
         return ERASOR_E_CAPACITY;
     }
     ++h->n_grow;
+    h->grown_now |= 1;
     h->capMap = (uint32_t)capMap;
     h->capV = h->capMap;
     const uint32_t V = h->capV;
@@ -773,6 +789,7 @@ int copy_F_dense(erasor_hip_handle *h, float4 *dst) {
 // rebuild the outskirts region without tombstones at the end of the buffer (stable)
 int rebuild_outskirts(erasor_hip_handle *h, uint32_t min_front_room) {
     ++h->store_epoch;
+    h->grown_now |= 2;
     if (getenv("ERASOR_HIP_CHAIN_STAMPS"))
         fprintf(stderr, "[rebuild_outskirts] o_begin %u, capO %u, o_valid %llu, nF %u (points %u), front room wanted %u\n", h->o_begin, h->capO,
                 (unsigned long long)h->o_valid, h->nF, h->nFv, min_front_room);
@@ -1032,11 +1049,19 @@ static bool early_stream(erasor_hip_handle *h) {
         return false;
     }
     h->bstream_own = true;
+    h->n_create += h->log_scope > 0;
+    // (a marker: whatever the runtime sets up at a stream's first command is set up here too, not beside the first early write-back;
+    // ev_early is only ever waited for, and waiting for a marker that has passed is no wait)
+    (void)hipEventRecord(h->ev_early, h->bstream);
     return true;
 }
 // the copy stream (host scans announced ahead, read-backs of a collected step): created on first use
 static hipStream_t copy_stream(erasor_hip_handle *h) {
-    if (!h->cstream && hipStreamCreateWithFlags(&h->cstream, hipStreamNonBlocking) != hipSuccess) h->cstream = nullptr;
+    if (!h->cstream) {
+        if (hipStreamCreateWithFlags(&h->cstream, hipStreamNonBlocking) != hipSuccess) h->cstream = nullptr;
+        else
+            h->n_create += h->log_scope > 0;
+    }
     return h->cstream ? h->cstream : h->stream;
 }
 
@@ -1356,15 +1381,22 @@ static uint64_t staged_fingerprint(QSide &q, size_t n) {
 static int stage_host_scan(erasor_hip_handle *h, QSide &q, const void *scan_src, uint32_t ns, hipStream_t stream, RowFmt fmt, uint64_t *fp_out) {
     if (q.h2d_pending) HIPC(h, hipEventSynchronize(q.ev_h2d));  // (an announcement that was dropped: its copy may still read the staging buffer)
     if (scan_src != (const void *)q.stage && q.stage_cap < ns) {
-        if (q.stage) (void)hipHostFree(q.stage);
+        if (q.stage) {
+            (void)hipHostFree(q.stage);
+            h->n_free += h->log_scope > 0;
+        }
         q.stage = nullptr;
         q.stage_cap = (size_t)ns + ns / 4 + 1024;
         HIPC(h, hipHostMalloc((void **)&q.stage, q.stage_cap * sizeof(float4), hipHostMallocDefault));
+        h->n_alloc += h->log_scope > 0;
         for (int k = 0; k < NSIDE; ++k) {  // (round 6: the sides that have never staged anything get their pinned buffers now, see alloc_scan)
             QSide &o = h->q[k];
             if (o.stage || &o == &q) continue;
-            if (hipHostMalloc((void **)&o.stage, q.stage_cap * sizeof(float4), hipHostMallocDefault) == hipSuccess) o.stage_cap = q.stage_cap;
-            else o.stage = nullptr;
+            if (hipHostMalloc((void **)&o.stage, q.stage_cap * sizeof(float4), hipHostMallocDefault) == hipSuccess) {
+                o.stage_cap = q.stage_cap;
+                h->n_alloc += h->log_scope > 0;
+            } else
+                o.stage = nullptr;
         }
     }
     const unsigned char *p = static_cast<const unsigned char *>(scan_src);
@@ -1738,7 +1770,9 @@ static int enqueue_query_chain(erasor_hip_handle *h, int side, const void *scan_
     if (rc) return rc;
     const uint32_t B = h->B, nq = ns;
     if (B + 1 <= QB_NB_MAX) {
-        if (ensure(h, q.qb_hist, (size_t)(B + 1) * std::max(1u, cdiv(nq, QB_TILE)) + 8)) return ERASOR_E_NO_DEVICE;
+        // (rows for the side's CAPACITY, not for this scan: the table then grows with the side's arrays in alloc_scan and not, one side
+        // at a time, whenever a scan is a tile longer than the last -- the per-step record showed those as single allocations mid-sequence)
+        if (ensure(h, q.qb_hist, (size_t)(B + 1) * std::max(1u, cdiv(std::max(nq, q.capS), QB_TILE)) + 8)) return ERASOR_E_NO_DEVICE;
     } else {
         const uint32_t nb_q = 256u * std::max(1u, cdiv(nq, RTILE));
         if (ensure(h, h->hist, nb_q) || ensure(h, h->hist_l, nb_q) || ensure(h, h->hist_t, cdiv(nb_q, 1024) + 2)) return ERASOR_E_NO_DEVICE;
@@ -2034,8 +2068,6 @@ static inline void cpu_relax() {
     __asm__ __volatile__("yield");
 #endif
 }
-// ERASOR_HIP_OVERLAP unset: does overlapping consecutive steps pay on this handle's workload?  See the definition of OvAuto.
-static void overlap_auto_sample(erasor_hip_handle *h, double period_us);
 static int step_collect(erasor_hip_handle *h, erasor_step_result *res);
 
 // ERASOR_HIP_HOST_TIMING: the host's time stamps along step_enqueue (carried in the plan)
@@ -2298,8 +2330,14 @@ static int step_plan_reserve(erasor_hip_handle *h, StepPlan &pl) {
     pl.fold = B <= 1024 * SRT_KPT && n_voi > 0;
     pl.srt_in_revert = pl.st1_ahead && h->prof != 1;
     const int announced_beyond = h->npend + (h->ann.valid ? 1 : 0);  // nodes announced behind this step's own
-    const bool overlap_pays = overlap_wanted(h, announced_beyond);
     h->fly.deep = announced_beyond >= h->batch_lead;
+    // A deep caller's handle will try the overlapped mode (OvAuto): what that mode needs and a plain step does not is made NOW, at the first
+    // deep step -- among the first step's few hundred allocations --, not at the first step that writes the reserved layout.  Measured
+    // (MEASUREMENTS.md, "cold start"): that step made no allocation -- the scratch is sized by the store's extent, which has the
+    // reserved layout's room from the first step on -- but created the early stream, and its period was 0.55-10.8 ms against
+    // 0.15-0.45 ms of its neighbours.  A handle that never sees a deep caller, or has one query stream, creates what it did before.
+    if (!h->ov_ready && h->fly.deep && h->nqs >= 2 && overlap_env() != 0) h->ov_ready = early_stream(h);
+    const bool overlap_pays = overlap_wanted(h, announced_beyond);
     pl.reserved = pl.srt_in_revert && pl.fold && pl.mb_count && !flags && overlap_pays && early_stream(h);
     pl.nbk = B + 1;
     pl.bits = key_bits(B + 1);
@@ -2694,6 +2732,7 @@ static int step_end_and_ahead(erasor_hip_handle *h, StepPlan &pl) {
 static void step_publish(erasor_hip_handle *h, StepPlan &pl) {
     h->fly.active = true;
     h->fly.reserved = pl.reserved;
+    h->fly.use_ov = pl.use_ov;
     h->fly.seq = h->step_seq;
     h->fly.n_map_in = pl.n_map_in;
     h->fly.ns = pl.ns;
@@ -2720,6 +2759,7 @@ static void step_publish(erasor_hip_handle *h, StepPlan &pl) {
 static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_scan, bool src_is_device, const float T_l2b[16],
                         const float T_b2o[16], const float T_o2b[16], int flags = 0, RowFmt fmt = RowFmt(), uint64_t ticket = 0) {
     if (!h) return ERASOR_E_INVALID;
+    LogScope in_step(h);
     StepPlan pl{scan_src, n_scan, src_is_device, T_l2b, T_b2o, T_o2b, flags, fmt, ticket};
     int rc = step_admit(h, pl);
     if (!rc) rc = step_plan_reserve(h, pl);
@@ -2738,56 +2778,11 @@ static int step_enqueue(erasor_hip_handle *h, const void *scan_src, size_t n_sca
     return ERASOR_OK;
 }
 
-// (see erasor_hip_handle::OvAuto)
-static constexpr int OVA_W = 4, OVA_SKIP = 3;
-static constexpr unsigned long long OVA_AGAIN = 600;
-static void overlap_auto_sample(erasor_hip_handle *h, double period_us) {
-    auto &a = h->ova;
-    static const int block_mode[4] = {0, 1, 1, 0};
-    if (a.block >= 4) {  // decided: measure again after a while
-        if (++a.since_decision >= OVA_AGAIN) {
-            a.block = 0;
-            a.n = 0;
-            a.sum[0] = a.sum[1] = 0;
-            a.mx[0] = a.mx[1] = 0;
-            a.cnt[0] = a.cnt[1] = 0;
-            if (a.mode != block_mode[0]) {
-                a.mode = block_mode[0];
-                a.skip = OVA_SKIP;
-            }
-        }
-        return;
-    }
-    if (a.skip > 0) {
-        --a.skip;
-        return;
-    }
-    a.sum[a.mode] += period_us;
-    a.mx[a.mode] = std::max(a.mx[a.mode], period_us);
-    ++a.cnt[a.mode];
-    if (++a.n < OVA_W) return;
-    a.n = 0;
-    ++a.block;
-    if (a.block < 4) {
-        if (block_mode[a.block] != a.mode) {
-            a.mode = block_mode[a.block];
-            a.skip = OVA_SKIP;
-        }
-        return;
-    }
-    // (means without each mode's largest sample: a page fault or a late host thread in one of eight steps is not the mode's doing)
-    a.est[0] = a.cnt[0] > 1 ? (a.sum[0] - a.mx[0]) / (a.cnt[0] - 1) : a.sum[0] / a.cnt[0];
-    a.est[1] = a.cnt[1] > 1 ? (a.sum[1] - a.mx[1]) / (a.cnt[1] - 1) : a.sum[1] / a.cnt[1];
-    const int m = (a.est[1] * 1.02 < a.est[0]) ? 1 : 0;
-    if (m != a.mode) a.skip = OVA_SKIP;
-    a.mode = m;
-    a.since_decision = 0;
-}
-
 // Second half: wait for the step's results (k_step_end's last store into the pinned block is the step's number), commit the host
 // mirror of the map store, report.  A VoxelGrid pass-through flip re-runs the step here, synchronously.
 static int step_collect(erasor_hip_handle *h, erasor_step_result *res) {
     if (!h) return ERASOR_E_INVALID;
+    LogScope in_step(h);
     if (!h->fly.active) {
         h->err = "erasor_hip_step_wait without a step in flight";
         return ERASOR_E_STATE;
@@ -2820,6 +2815,20 @@ static int step_collect(erasor_hip_handle *h, erasor_step_result *res) {
     {   // measurement (erasor_hip_chain_timing): the main chain's span on the device's own clock, and how long the stream sat between the
         // previous step's end and this step's chunk scan
         const unsigned long long t_open = h->st.t_open, t_end = h->pin->t_end;
+        erasor_step_log_entry &le = h->slog[h->slog_n++ % erasor_hip_handle::STEP_LOG_N];
+        le = erasor_step_log_entry();
+        le.step = step_seq;
+        le.n_alloc = h->n_alloc.exchange(0);
+        le.n_free = h->n_free.exchange(0);
+        le.n_create = h->n_create.exchange(0);
+        le.reserved = h->fly.reserved;
+        le.use_ov = h->fly.use_ov;
+        le.deep = h->fly.deep;
+        le.ova_mode = (uint8_t)h->ova.mode;
+        le.ova_block = (uint8_t)h->ova.block;
+        le.ova_skip = (uint8_t)h->ova.skip;
+        le.grown = h->grown_now;
+        h->grown_now = 0;
         if (t_end > t_open) {
             h->tm_span += (double)(t_end - t_open) * 0.01;
             if (h->tm_last_end && h->tm_last_seq + 1 == step_seq) {
@@ -2831,7 +2840,11 @@ static int step_collect(erasor_hip_handle *h, erasor_step_result *res) {
                     const double per = (double)(t_end - h->tm_last_end) * 0.01;  // end of a step to the end of the next: the period
                     h->tm_period += per;
                     ++h->tm_nper;
-                    if (h->fly.deep) overlap_auto_sample(h, per);
+                    le.period_us = per;
+                    if (h->fly.deep) {
+                        le.sampled = h->ova.block < 4 && h->ova.skip == 0;
+                        overlap_auto_sample(h->ova, per);
+                    }
                 }
             }
             ++h->tm_n;
@@ -3021,6 +3034,7 @@ static int prefetch_common(erasor_hip_handle *h, const void *scan_xyzi, size_t n
     // host then stages the next node's cloud while the GPU is busy with the current one; see the end of this function)
     if (!h || !T_l2b || (!scan_xyzi && n) || n > 0x3FFFFFFFull) return ERASOR_E_INVALID;
     if ((src_is_device && (fmt.stride != 16 || fmt.ioff != 12)) || fmt.stride < 16 || fmt.ioff < 12 || fmt.ioff + 4 > fmt.stride) return ERASOR_E_INVALID;
+    LogScope in_announcement(h);
     HIPC(h, hipSetDevice(h->device));
     if (h->ann.valid && h->npend >= MAX_AHEAD) {
         h->err = "erasor_hip_prefetch_scan: as many scans as there are query sides to hold them are already announced";
@@ -3909,6 +3923,14 @@ int erasor_hip_overlap_auto(erasor_hip_handle *h, int *mode, double *plain_perio
     if (mode) *mode = h->ova.mode;
     if (plain_period_us) *plain_period_us = h->ova.est[0];
     if (overlapped_period_us) *overlapped_period_us = h->ova.est[1];
+    return ERASOR_OK;
+}
+int erasor_hip_step_log(erasor_hip_handle *h, erasor_step_log_entry *out, size_t cap, size_t *n) {
+    if (!h || (!out && cap)) return ERASOR_E_INVALID;
+    const unsigned long long have = std::min<unsigned long long>(h->slog_n, erasor_hip_handle::STEP_LOG_N);
+    const size_t cnt = (size_t)std::min<unsigned long long>(have, cap);
+    for (size_t k = 0; k < cnt; ++k) out[k] = h->slog[(h->slog_n - cnt + k) % erasor_hip_handle::STEP_LOG_N];  // (the newest `cnt`, oldest first)
+    if (n) *n = cnt;
     return ERASOR_OK;
 }
 int erasor_hip_chain_batch(erasor_hip_handle *h, int n_scans, int lead) {

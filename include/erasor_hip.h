@@ -847,10 +847,32 @@ int erasor_hip_ahead_split_counts(erasor_hip_handle *h, uint64_t *launched, uint
 int erasor_hip_announce_origin2body(erasor_hip_handle *h, const float T_origin2body[16]);
 /* steps whose early passes were launched ahead like that / steps that took them */
 int erasor_hip_overlap_counts(erasor_hip_handle *h, uint64_t *launched, uint64_t *used);
-/* ERASOR_HIP_OVERLAP unset: the handle decides by measurement (period of a step on the device's clock, a few steps in either mode, again
- * every 600 steps) whether consecutive steps overlap.  *mode: 1 overlapped, 0 plain -- what the next step will use; the two periods the
- * last decision compared, in microseconds (0: not measured yet). */
+/* ERASOR_HIP_OVERLAP unset: the handle decides by measurement whether consecutive steps overlap: the period of a step on the device's
+ * clock, four samples plain, then four overlapped.  If the two means (each without its largest sample) differ by more than a margin the
+ * decision is taken there, after a fresh handle's 16th step; otherwise a second overlapped and a second
+ * plain block follow and the shorter mean wins (plain has to lose by 2 %; after the 27th step).  Measured again every 600 steps.  *mode: 1 overlapped,
+ * 0 plain -- what the next step will use; the two periods the last decision compared, in microseconds (0: not measured yet). */
 int erasor_hip_overlap_auto(erasor_hip_handle *h, int *mode, double *plain_period_us, double *overlapped_period_us);
+/* What a handle's steps cost beside their kernels: one record per COLLECTED step, the last 256 are kept. */
+typedef struct erasor_step_log_entry {
+    uint64_t step;        /* the step's number (1: the handle's first) */
+    double period_us;     /* end of the previous step to the end of this one on the device's clock -- the value the overlap decision
+                             samples --, 0 when the two were not consecutive */
+    uint32_t n_alloc;     /* device (and pinned host) allocations, frees, stream / event creations made inside this step's calls and */
+    uint32_t n_free;      /* in the announcements since the previous step was collected */
+    uint32_t n_create;
+    uint8_t reserved;     /* the step wrote the reserved layout (an overlapped step) */
+    uint8_t use_ov;       /* it took the passes launched ahead of it beside the previous step's per-bin launch */
+    uint8_t deep;         /* the caller had announced deep enough for the overlap decision to sample it */
+    uint8_t sampled;      /* the period was counted by the overlap decision (not skipped, not between two measurements) */
+    uint8_t ova_mode;     /* the overlap decision's state BEFORE this step's sample: the mode in force, */
+    uint8_t ova_block;    /* the block being sampled (0..3: plain, overlapped, overlapped, plain; 4: decided) */
+    uint8_t ova_skip;     /* and the samples still to be ignored */
+    uint8_t grown;        /* growth the map's own growth forced inside the step: 1 the map-sized scratch was enlarged, 2 the outskirts were
+                             rebuilt (a pass over the store), 3 both */
+} erasor_step_log_entry;
+/* the last records, oldest first: up to `cap` of them into out[], *n = how many were written */
+int erasor_hip_step_log(erasor_hip_handle *h, erasor_step_log_entry *out, size_t cap, size_t *n);
 /* Round 6 -- the query chains of SEVERAL announced nodes as one set of launches.  A node's query chain (voxelize_preserving_labels of
  * its scan, OfflineMapUpdater.cpp:237-241; lidar->body, R-POD keys, per-bin statistics, erasor.cpp:100-115) does not depend on the map,
  * and every launch of it is bound by latency, not by work: a launch that serves the same stage of n_scans scans costs what it costs for
