@@ -172,6 +172,11 @@ class DensityResult(C.Structure):
         return {k: (int if t is C.c_uint64 else float)(getattr(self, k)) for k, t in self._fields_}
 
 
+class NormalsResult(C.Structure):
+    """erasor_normals_result (include/erasor_hip.h)"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_short", "n_degenerate", "n_ambiguous", "n_flipped")] + [("curvature", ScoreStats)]
+
+
 DENSITY_SCORES = {"kth": 0, "mean": 1, "count": 2}  # ERASOR_DENSITY_KTH / _MEAN / _COUNT
 DENSITY_RULES = {"abs": 0, "mad": 1}                # ERASOR_DENSITY_ABS / _MAD
 KNN_NONE = 0xFFFFFFFF  # the padding of a neighbour list
@@ -356,7 +361,7 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "render.hip.h", "revert_bins.hip.h",
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "normals.hip.h", "render.hip.h", "revert_bins.hip.h",
                                                  "exact_sort.hip.h", "exact_sort_core.h", "overlap_auto.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
@@ -1119,6 +1124,32 @@ class Erasor:
     def density_filter_map(self, score="mean", k=16, radius=0.5, rule="mad", thr=0.5, mul=2.0, min_neighbors=2, keep=True):
         """density_filter of the handle's current map, which stays as it is (erasor_hip_density_filter_map)"""
         return self._density_filter(lib().erasor_hip_density_filter_map, (), self._map_n(), score, k, radius, rule, thr, mul, min_neighbors, keep)
+
+    # -- the surface a point lies on: normals, curvature, covariance eigenvalues (on the host: evalmap.normals) --
+    def _normals(self, fn, head, n, k, viewpoint, eigenvalues):
+        r = NormalsResult()
+        v = None if viewpoint is None else (C.c_double * 3)(*[float(x) for x in np.asarray(viewpoint, np.float64).reshape(3)])
+        nrm = np.empty((max(n, 1), 3), np.float32)
+        curv = np.empty(max(n, 1), np.float64)
+        eig = np.empty((max(n, 1), 3), np.float64) if eigenvalues else None
+        self._check(fn(self._h, *head, C.c_uint32(int(k) & 0xFFFFFFFF), v, _p(nrm), _p(curv), _p(eig) if eigenvalues else None, C.byref(r)))
+        res = {**{f: int(getattr(r, f)) for f in ("n_points", "n_short", "n_degenerate", "n_ambiguous", "n_flipped")}, "k": int(k),
+               "curvature_stats": r.curvature.as_dict()}
+        return nrm[:n], curv[:n], (eig[:n] if eigenvalues else None), res
+
+    def normals(self, cloud, k=16, viewpoint=None, eigenvalues=False):
+        """Every point's surface normal and curvature from itself and its k nearest other points inside `cloud` (as for evaluate),
+        2 <= k <= 32, on the device (erasor_hip_normals_clouds): the covariance's smallest eigenvector by a Jacobi solve in float64,
+        turned towards `viewpoint` (three numbers) or upwards (None); pcl::NormalEstimation's job.  Returns (normals (n, 3) float32,
+        curvature (n,) float64, eigenvalues (n, 3) float64 ascending or None, result) as evalmap.normals does; points with fewer
+        than k other points and neighbourhoods without extent are NaN and counted in the result."""
+        kept = []
+        c = self._eval_cloud(cloud, kept)
+        return self._normals(lib().erasor_hip_normals_clouds, c, c[1].value, k, viewpoint, eigenvalues)
+
+    def normals_map(self, k=16, viewpoint=None, eigenvalues=False):
+        """normals of the handle's current map (the get_map view, never copied to the host; erasor_hip_normals_map)"""
+        return self._normals(lib().erasor_hip_normals_map, (), self._map_n(), k, viewpoint, eigenvalues)
 
     # -- maps without labels (fill_removert_intensity.cpp:24-59, compare_complement.cpp:43-75; on the host: evalmap.label_from /
     # evalmap.static_complement) --

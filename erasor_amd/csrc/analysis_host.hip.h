@@ -1,8 +1,8 @@
 // The offline analyses' host code: PR / RR evaluation (one estimate, many, by class), the overlap report, the frame check, the scans'
-// labels, the clustering, the k nearest neighbours and density filters, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
+// labels, the clustering, the k nearest neighbours and density filters, the normals, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
 // at its end -- one translation unit, like the kernel headers -- so it sees the handle, ensure / LAUNCH / HIPC, scan_u32, radix_sort,
 // map_to_device and voxelize_device from there; nothing of the step path depends on this file.  Kernels: evaluate.hip.h, nearest.hip.h,
-// align.hip.h, label_scans.hip.h, cluster.hip.h, knn.hip.h, render.hip.h.
+// align.hip.h, label_scans.hip.h, cluster.hip.h, knn.hip.h, normals.hip.h, render.hip.h.
 #pragma once
 
 extern "C" {
@@ -1593,6 +1593,86 @@ int erasor_hip_density_filter_map(erasor_hip_handle *h, const erasor_density_fil
     uint32_t n = 0;
     if ((rc = map_on_device(h, who, h->ev.map, &p, &n))) return rc;
     return df_run(h, who, p, n, *filter, keep_mask, kept_xyzi, cap_points, res);
+}
+
+// ---- every point's surface normal, curvature and eigenvalues from its k nearest neighbours (kernel: normals.hip.h) ----
+// Like kn_run: the main stream, the evaluator's scratch, the tree's sort in bank 2.  Round trips: the counters once, and the host-driven
+// select (8 passes) for the curvature's statistics.
+static int nm_check_args(erasor_hip_handle *h, const char *who, uint32_t k, const double *viewpoint, const void *res) {
+    if (!res) return invalid(h, who, "res is NULL");
+    if (k < NM_MIN_K || k > KN_MAX_K) return invalid(h, who, "k must be within 2 .. 32");
+    if (viewpoint && !(std::isfinite(viewpoint[0]) && std::isfinite(viewpoint[1]) && std::isfinite(viewpoint[2])))
+        return invalid(h, who, "viewpoint must be three finite numbers");
+    return ERASOR_OK;
+}
+
+static int nm_run(erasor_hip_handle *h, const char *who, const float4 *pts, uint32_t n, uint32_t k, const double *viewpoint, float *normals,
+                  double *curvature, double *eigenvalues, erasor_normals_result *res) {
+    auto &E = h->ev;
+    erasor_normals_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_points = n;
+    kn_no_stats(&r.curvature);
+    if (!n) {
+        *res = r;
+        return ERASOR_OK;
+    }
+    const size_t n1 = (size_t)n + 1;
+    if (ensure(h, E.nm_ctr, NM_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256) || ensure(h, E.nm_curv, n1) || (normals && ensure(h, E.nm_nrm, 3 * n1)) ||
+        (eigenvalues && ensure(h, E.nm_eig, 3 * n1)))
+        return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nm_ctr.p, 0, NM_NCTR * sizeof(unsigned long long), h->stream));
+    HIPC(h, hipMemsetAsync(E.nm_ctr.p + NM_C_CURV_MIN, 0xFF, sizeof(unsigned long long), h->stream));
+    NnTree T;
+    int rc = nn_build(h, pts, n, who, "cloud", "point(s)", &T);
+    if (rc) return rc;
+    float *nrm = normals ? E.nm_nrm.p : nullptr;
+    double *eig = eigenvalues ? E.nm_eig.p : nullptr;
+    const uint32_t view = viewpoint ? 1u : 0u;
+    const double vx = viewpoint ? viewpoint[0] : 0.0, vy = viewpoint ? viewpoint[1] : 0.0, vz = viewpoint ? viewpoint[2] : 0.0;
+    const uint32_t g = cdiv(n, KN_QBLOCK);
+#define NM_QUERY(KC) LAUNCH(h, h->stream, "nm_query", k_nm_query<KC>, g, KN_QBLOCK, T, pts, k, view, vx, vy, vz, nrm, E.nm_curv.p, eig, E.nm_ctr.p)
+    if (k <= 8) NM_QUERY(8);
+    else if (k <= 16) NM_QUERY(16);
+    else NM_QUERY(32);
+#undef NM_QUERY
+    unsigned long long c[NM_NCTR];
+    if ((rc = d2h(h, c, E.nm_ctr.p, NM_NCTR * sizeof(unsigned long long)))) return rc;
+    r.n_short = c[NM_C_SHORT];
+    r.n_degenerate = c[NM_C_DEGENERATE];
+    r.n_ambiguous = c[NM_C_AMBIGUOUS];
+    r.n_flipped = c[NM_C_FLIPPED];
+    if ((rc = kn_stats(h, E.nm_curv.p, n, n - r.n_short - r.n_degenerate, c[NM_C_CURV_MIN], c[NM_C_CURV_MAX], &r.curvature))) return rc;
+    *res = r;
+    if (normals && (rc = d2h(h, normals, E.nm_nrm.p, (size_t)n * 3 * sizeof(float)))) return rc;
+    if (curvature && (rc = d2h(h, curvature, E.nm_curv.p, (size_t)n * sizeof(double)))) return rc;
+    if (eigenvalues && (rc = d2h(h, eigenvalues, E.nm_eig.p, (size_t)n * 3 * sizeof(double)))) return rc;
+    return ERASOR_OK;
+}
+
+int erasor_hip_normals_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, uint32_t k, const double *viewpoint, float *normals,
+                              double *curvature, double *eigenvalues, erasor_normals_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_normals_clouds";
+    const float4 *p = nullptr;
+    int rc = nm_check_args(h, who, k, viewpoint, res);
+    if (rc || (rc = kn_cloud(h, who, xyzi, n, is_device, &p))) return rc;
+    return nm_run(h, who, p, (uint32_t)n, k, viewpoint, normals, curvature, eigenvalues, res);
+}
+
+int erasor_hip_normals_map(erasor_hip_handle *h, uint32_t k, const double *viewpoint, float *normals, double *curvature, double *eigenvalues,
+                           erasor_normals_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_normals_map";
+    int rc = nm_check_args(h, who, k, viewpoint, res);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    uint32_t n = 0;
+    if ((rc = map_on_device(h, who, h->ev.map, &p, &n))) return rc;
+    return nm_run(h, who, p, n, k, viewpoint, normals, curvature, eigenvalues, res);
 }
 
 // ---- label_map (fill_removert_intensity.cpp:24-59, compare_map.cpp:77-110) and calc_complement (compare_complement.cpp:43-75): the

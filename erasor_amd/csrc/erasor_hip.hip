@@ -42,6 +42,7 @@
 #include "label_scans.hip.h"
 #include "cluster.hip.h"
 #include "knn.hip.h"
+#include "normals.hip.h"
 #include "render.hip.h"
 
 using namespace ek;
@@ -388,6 +389,11 @@ struct erasor_hip_handle {
         DBuf<uint32_t> kn_ni, kn_cnt;
         DBuf<double> kn_nd;
         DBuf<uint8_t> kn_mask;
+        // normals, curvature and eigenvalues (erasor_hip_normals_*): the curvatures' bit patterns, the normals, the eigenvalues and the
+        // counters (the tree: nn_* above)
+        DBuf<unsigned long long> nm_curv, nm_ctr;
+        DBuf<float> nm_nrm;
+        DBuf<double> nm_eig;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
 #ifdef ERASOR_HIP_TEST_HOOKS
@@ -1177,6 +1183,7 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->ev.cl_ctr);
     release(h->ev.kn_kth); release(h->ev.kn_mean); release(h->ev.kn_dev); release(h->ev.kn_ctr); release(h->ev.kn_ni); release(h->ev.kn_cnt);
     release(h->ev.kn_nd); release(h->ev.kn_mask);
+    release(h->ev.nm_curv); release(h->ev.nm_ctr); release(h->ev.nm_nrm); release(h->ev.nm_eig);
     for (int k = 0; k < NSIDE; ++k) {
         if (h->q[k].ev_keys) (void)hipEventDestroy(h->q[k].ev_keys);
         if (h->q[k].ev_done) (void)hipEventDestroy(h->q[k].ev_done);

@@ -669,6 +669,43 @@ static int density_mode(int argc, char **argv) {
     print_stats("mean", r.mean.min, r.mean.median, r.mean.p90, r.mean.p99, r.mean.max);
     return 0;
 }
+// --normals <in.pcd> <out.pcd> <k> [vx vy vz]: every point's surface normal and curvature from its k nearest neighbours
+// (erasor_hip_normals_clouds; pcl::NormalEstimation's job), turned towards the viewpoint or, without one, upwards; the counts, the
+// curvature's statistics, and the cloud saved as a binary PCD with the fields x y z intensity normal_x normal_y normal_z curvature
+static int normals_mode(int argc, char **argv) {
+    if (argc != 5 && argc != 8) return 2;
+    size_t k = 0;
+    if (!parse_count(argv[4], &k) || k < 2 || k > 32) return 2;
+    double view[3] = {0, 0, 0};
+    if (argc == 8)
+        for (int a = 0; a < 3; ++a)
+            if (!parse_number(argv[5 + a], &view[a]) || !std::isfinite(view[a])) return 2;
+    std::vector<float> cloud;
+    if (!load_cloud_xyzi(argv[2], cloud)) {
+        fprintf(stderr, "cannot read %s\n", argv[2]);
+        return 3;
+    }
+    erasor_hip_handle *h = render_handle();
+    if (!h) return 1;
+    const size_t n = cloud.size() / 4;
+    std::vector<float> nrm(std::max<size_t>(n, 1) * 3, 0.f);
+    std::vector<double> curv(std::max<size_t>(n, 1), 0.0);
+    erasor_normals_result r;
+    const int rc = erasor_hip_normals_clouds(h, cloud.data(), n, 0, (uint32_t)k, argc == 8 ? view : nullptr, nrm.data(), curv.data(), nullptr, &r);
+    if (rc) return render_fail(h, "normals", rc);
+    erasor_hip_destroy(h);
+    printf("normals: n=%llu  k=%u  short=%llu  degenerate=%llu  ambiguous=%llu  flipped=%llu  scored=%llu\n", (unsigned long long)r.n_points, (unsigned)k,
+           (unsigned long long)r.n_short, (unsigned long long)r.n_degenerate, (unsigned long long)r.n_ambiguous, (unsigned long long)r.n_flipped,
+           (unsigned long long)r.curvature.n_scored);
+    print_stats("curvature", r.curvature.min, r.curvature.median, r.curvature.p90, r.curvature.p99, r.curvature.max);
+    std::vector<float> curv32(curv.begin(), curv.end());
+    if (erasor_utils::save_pcd_normals_binary(argv[3], cloud.data(), nrm.data(), curv32.data(), n) != 0) {
+        fprintf(stderr, "cannot write %s\n", argv[3]);
+        return 1;
+    }
+    printf("saved %s\n", argv[3]);
+    return 0;
+}
 // --eval-many <voxelsize> <voxel_leaf> <gt> <est1> [<est2> ...]: --eval's row for every estimate against one ground truth, from ONE
 // erasor_hip_evaluate_many call (compare_map.cpp's use: several methods' maps against one GT)
 static int eval_many_mode(int argc, char **argv) {
@@ -1779,6 +1816,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && std::string(argv[1]) == "--normals") {
+        try {
+            return normals_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--analyze") {
         try {
             return analyze_mode(argc, argv);
@@ -1824,8 +1869,9 @@ int main(int argc, char **argv) {
                 "       %s --clusters <cloud.pcd> <tol> [min_size] [max_size] [kept_out.pcd]\n"
                 "       %s --residue <gt> <est> [tol] [voxelsize] [voxel_leaf]\n"
                 "       %s --denoise <in.pcd> <out.pcd> sor <k> <mul> | ror <radius> <min_neighbors> | kth <k> <thr>\n"
-                "       %s --density <cloud.pcd> <k>\n",
-                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                "       %s --density <cloud.pcd> <k>\n"
+                "       %s --normals <in.pcd> <out.pcd> <k> [vx vy vz]\n",
+                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

@@ -360,6 +360,22 @@ int save_pcd_binary(const std::string &pcd_name, const Cloud &src) {
     }
     return fclose(fp) == 0 ? 0 : -1;
 }
+
+int save_pcd_normals_binary(const std::string &pcd_name, const float *xyzi, const float *normals, const float *curvature, size_t n) {
+    FILE *fp = fopen(pcd_name.c_str(), "wb");
+    if (!fp) return -1;
+    fprintf(fp, "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity normal_x normal_y normal_z curvature\n"
+                "SIZE 4 4 4 4 4 4 4 4\nTYPE F F F F F F F F\nCOUNT 1 1 1 1 1 1 1 1\n");
+    fprintf(fp, "WIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %zu\nDATA binary\n", n, n);
+    for (size_t i = 0; i < n; ++i) {
+        const float v[8] = {xyzi[4 * i], xyzi[4 * i + 1], xyzi[4 * i + 2], xyzi[4 * i + 3], normals[3 * i], normals[3 * i + 1], normals[3 * i + 2], curvature[i]};
+        if (fwrite(v, 4, 8, fp) != 8) {
+            fclose(fp);
+            return -1;
+        }
+    }
+    return fclose(fp) == 0 ? 0 : -1;
+}
 }  // namespace erasor_utils
 
 namespace erasor {

@@ -40,6 +40,9 @@ int load_pcd(const std::string &pcd_name, Cloud &dst);
 // pcl::io::savePCDFileASCII as used at OMU.cpp:193 (PCL's default: 8 significant digits), and the lossless binary form
 int save_pcd_ascii(const std::string &pcd_name, const Cloud &src);
 int save_pcd_binary(const std::string &pcd_name, const Cloud &src);
+// a cloud with its normals (erasor_hip_normals_*): binary, fields x y z intensity normal_x normal_y normal_z curvature, all float32 -- the
+// layout of pcl::PointXYZINormal's fields.  xyzi: n rows of 4, normals: n rows of 3, curvature: n
+int save_pcd_normals_binary(const std::string &pcd_name, const float *xyzi, const float *normals, const float *curvature, size_t n);
 // utils.cpp:80-114, same signature as utils.hpp:103 (called at OMU.cpp:186,238, erasor.cpp:528, mapgen.hpp:239,252,295):
 // PCL VoxelGrid + exact 1-NN label, on the GPU (erasor_hip_voxelize_preserving_labels).  The free function has no
 // object to hang a device handle on: it uses one process-wide handle on device `voxelize_device()` (default 0).

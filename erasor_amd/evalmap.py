@@ -26,6 +26,9 @@ erasor_cluster_row): connected components of "within tol", listed and filtered b
 
 knn / radius_count / density_filter (and knn_brute, radius_count_brute): every point's k nearest neighbours inside its own cloud, the
 points within a radius of it, and the outlier filters on both -- the host restatement of Erasor.knn / radius_count / density_filter.
+
+normals / normals_brute: every point's surface normal, curvature and covariance eigenvalues from its k nearest neighbours -- the host
+restatement of Erasor.normals.
 """
 import numpy as np
 from scipy.spatial import cKDTree
@@ -1126,3 +1129,198 @@ def density_filter(cloud, score="mean", k=16, radius=0.5, rule="mad", thr=0.5, m
            "n_removed_static": int((~ok & ~dyn).sum()), "n_short": int(n_short), "n_scored": st["n_scored"], "m": m, "mad": mad, "thr": t,
            "min": st["min"], "median": st["median"], "p90": st["p90"], "p99": st["p99"], "max": st["max"]}
     return ok.astype(np.uint8), (c[ok].copy() if keep else None), res
+
+
+# ---- surface normals, curvature and eigenvalues (include/erasor_hip.h: erasor_hip_normals_*; kernel: erasor_amd/csrc/normals.hip.h),
+# on the host ----------------------------------------------------------------------------------------------------------------------
+# The host restatement of the device's contract; include/erasor_hip.h states it in full.  Float64 on the float32 coordinates, one IEEE
+# operation at a time: the neighbourhood is the point itself and then its k nearest others in knn's order; the centroid and the six
+# covariance entries are summed in that order and divided by m = k + 1; _jacobi3 solves; the eigenvalues ascend by (value, column).
+NORMALS_MIN_K = 2
+NORMALS_RESULT_FIELDS = ("n_points", "n_short", "n_degenerate", "n_ambiguous", "n_flipped")
+
+
+def _check_normals_args(k, viewpoint, who):
+    if not (isinstance(k, (int, np.integer)) and NORMALS_MIN_K <= k <= KNN_MAX_K):
+        raise ValueError(who + ": k must be within 2 .. 32")
+    if viewpoint is None:
+        return int(k), None
+    v = np.asarray(viewpoint, np.float64).reshape(-1)
+    if len(v) != 3 or not np.isfinite(v).all():
+        raise ValueError(who + ": viewpoint must be three finite numbers")
+    return int(k), (float(v[0]), float(v[1]), float(v[2]))
+
+
+def _jacobi3(A):
+    """cyclic Jacobi on the symmetric 3x3 A (lists of Python floats, changed in place): pivots (0,1) (0,2) (1,2) with _jacobi4's rotation,
+    a pivot that is exactly zero skipped, until every element above the diagonal is exactly zero before a sweep, or 32 sweeps.  Returns
+    V (columns: eigenvectors); the eigenvalues are A's diagonal"""
+    from math import sqrt
+    V = [[1.0 if i == j else 0.0 for j in range(3)] for i in range(3)]
+    for _ in range(32):
+        if A[0][1] == 0.0 and A[0][2] == 0.0 and A[1][2] == 0.0:
+            break
+        for p in range(2):
+            for q in range(p + 1, 3):
+                apq = A[p][q]
+                if apq == 0.0:
+                    continue
+                theta = _ieee_div(A[q][q] - A[p][p], 2.0 * apq)
+                at = -theta if theta < 0.0 else theta
+                t = _ieee_div(1.0, at + sqrt(theta * theta + 1.0))
+                if theta < 0.0:
+                    t = -t
+                c = _ieee_div(1.0, sqrt(t * t + 1.0))
+                s = t * c
+                for k in range(3):
+                    akp, akq = A[k][p], A[k][q]
+                    A[k][p] = c * akp - s * akq
+                    A[k][q] = s * akp + c * akq
+                for k in range(3):
+                    apk, aqk = A[p][k], A[q][k]
+                    A[p][k] = c * apk - s * aqk
+                    A[q][k] = s * apk + c * aqk
+                A[p][q] = 0.0
+                for i in range(3):
+                    for j in range(i + 1, 3):
+                        A[j][i] = A[i][j]
+                for k in range(3):
+                    vkp, vkq = V[k][p], V[k][q]
+                    V[k][p] = c * vkp - s * vkq
+                    V[k][q] = s * vkp + c * vkq
+    return V
+
+
+def _normals_result(n, k, n_short, n_degenerate, n_ambiguous, n_flipped, curvature):
+    return {"n_points": int(n), "n_short": int(n_short), "n_degenerate": int(n_degenerate), "n_ambiguous": int(n_ambiguous),
+            "n_flipped": int(n_flipped), "k": int(k), "curvature_stats": score_stats(curvature)}
+
+
+def normals_brute(cloud, k, viewpoint=None):
+    """normals() in pure Python floats, one point at a time, over all-pairs neighbour lists: for a few hundred points"""
+    c = _knn_cloud(cloud, "normals")
+    k, view = _check_normals_args(k, viewpoint, "normals")
+    n, m = len(c), float(k + 1)
+    nan = float("nan")
+    nrm, curv, eig = np.full((n, 3), nan), np.full(n, nan), np.full((n, 3), nan)
+    c64 = c[:, :3].astype(np.float64)
+    n_deg = n_amb = n_flip = 0
+    if n - 1 < k:
+        return nrm.astype(np.float32), curv, eig, _normals_result(n, k, n, 0, 0, 0, curv)
+    idx, _ = _knn_rows_brute(c64, np.arange(n), k)
+    P = c64.tolist()
+    for i in range(n):
+        hood = [P[i]] + [P[j] for j in idx[i].tolist()]
+        sx = sy = sz = 0.0
+        for p in hood:
+            sx, sy, sz = sx + p[0], sy + p[1], sz + p[2]
+        cx, cy, cz = sx / m, sy / m, sz / m
+        xx = xy = xz = yy = yz = zz = 0.0
+        for p in hood:
+            ex, ey, ez = p[0] - cx, p[1] - cy, p[2] - cz
+            xx, xy, xz, yy, yz, zz = xx + ex * ex, xy + ex * ey, xz + ex * ez, yy + ey * ey, yz + ey * ez, zz + ez * ez
+        xx, xy, xz, yy, yz, zz = xx / m, xy / m, xz / m, yy / m, yz / m, zz / m
+        tr = (xx + yy) + zz
+        if not tr > 0:
+            n_deg += 1
+            continue
+        A = [[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]]
+        V = _jacobi3(A)
+        col = sorted(range(3), key=lambda j: (A[j][j], j))
+        l0, l1, l2 = (A[j][j] for j in col)
+        nx, ny, nz = V[0][col[0]], V[1][col[0]], V[2][col[0]]
+        n_amb += l0 == l1
+        if view is None:
+            flip = nz < 0 or (nz == 0 and (ny < 0 or (ny == 0 and nx < 0)))
+        else:
+            flip = ((view[0] - P[i][0]) * nx + (view[1] - P[i][1]) * ny) + (view[2] - P[i][2]) * nz < 0
+        if flip:
+            nx, ny, nz = -nx, -ny, -nz
+            n_flip += 1
+        nrm[i], curv[i], eig[i] = (nx, ny, nz), abs(l0) / tr, (l0, l1, l2)
+    return nrm.astype(np.float32), curv, eig, _normals_result(n, k, 0, n_deg, n_amb, n_flip, curv)
+
+
+def _jacobi3_rows(a, live):
+    """_jacobi3 on every row at once: a = [a00, a01, a02, a11, a12, a22] (float64 arrays, changed in place), only where `live`.  The same
+    operations element by element; a row whose pivot is exactly zero, or whose off-diagonals all were before the sweep, keeps its
+    values.  Returns the nine entries of V, row-major"""
+    n = len(a[0])
+    v = [np.ones(n) if j in (0, 4, 8) else np.zeros(n) for j in range(9)]
+    # per pivot: (app, aqq, apq, apr, aqr) in a, and the columns p and q of V
+    pivots = (((0, 3, 1, 2, 4), (0, 1)), ((0, 5, 2, 1, 4), (0, 2)), ((3, 5, 4, 1, 2), (1, 2)))
+    with np.errstate(all="ignore"):
+        for _ in range(32):
+            active = live & ~((a[1] == 0.0) & (a[2] == 0.0) & (a[4] == 0.0))
+            if not active.any():
+                break
+            for (pp, qq, pq, pr, qr), (p, q) in pivots:
+                app, aqq, apq, apr, aqr = a[pp], a[qq], a[pq], a[pr], a[qr]
+                do = active & (apq != 0.0)
+                theta = (aqq - app) / (2.0 * apq)
+                at = np.where(theta < 0.0, -theta, theta)
+                t = 1.0 / (at + np.sqrt(theta * theta + 1.0))
+                t = np.where(theta < 0.0, -t, t)
+                c = 1.0 / np.sqrt(t * t + 1.0)
+                s = t * c
+                bpp, bpq = c * app - s * apq, s * app + c * apq  # A <- A J
+                bqp, bqq = c * apq - s * aqq, s * apq + c * aqq
+                a[pp] = np.where(do, c * bpp - s * bqp, app)     # A <- Jt A
+                a[qq] = np.where(do, s * bpq + c * bqq, aqq)
+                a[pq] = np.where(do, 0.0, apq)
+                a[pr] = np.where(do, c * apr - s * aqr, apr)
+                a[qr] = np.where(do, s * apr + c * aqr, aqr)
+                for row in range(3):                             # V <- V J
+                    vp, vq = v[3 * row + p], v[3 * row + q]
+                    v[3 * row + p] = np.where(do, c * vp - s * vq, vp)
+                    v[3 * row + q] = np.where(do, s * vp + c * vq, vq)
+    return v
+
+
+def normals(cloud, k, viewpoint=None):
+    """Every point's surface normal, curvature and covariance eigenvalues from itself and its k nearest other points inside `cloud` (XYZI
+    rows), 2 <= k <= 32; viewpoint: three finite numbers the normals are turned towards, or None for "up".  knn() gives the neighbour
+    lists; the arithmetic is element-wise numpy float64 over all points at once, sequential over the neighbour index.  Returns (normals
+    (n, 3) float32, curvature (n,) float64, eigenvalues (n, 3) float64 ascending, result): result has NORMALS_RESULT_FIELDS, k and
+    curvature_stats (SCORE_STATS_FIELDS over the finite curvatures).  Short and degenerate points are NaN."""
+    c = _knn_cloud(cloud, "normals")
+    k, view = _check_normals_args(k, viewpoint, "normals")
+    n, m = len(c), np.float64(k + 1)
+    if n - 1 < k:
+        curv = np.full(n, np.nan)
+        return np.full((n, 3), np.nan, np.float32), curv, np.full((n, 3), np.nan), _normals_result(n, k, n, 0, 0, 0, curv)
+    nb = knn(c, k, True)["nbr_idx"].astype(np.int64)
+    c64 = c[:, :3].astype(np.float64)
+    hood = [c64] + [c64[nb[:, e]] for e in range(k)]  # the point itself, then the list in its order
+    s = np.zeros((n, 3))
+    for p in hood:
+        s = s + p
+    cen = s / m
+    a = [np.zeros(n) for _ in range(6)]  # xx, xy, xz, yy, yz, zz
+    for p in hood:
+        e = p - cen
+        ex, ey, ez = e[:, 0], e[:, 1], e[:, 2]
+        for j, term in enumerate((ex * ex, ex * ey, ex * ez, ey * ey, ey * ez, ez * ez)):
+            a[j] = a[j] + term
+    a = [x / m for x in a]
+    tr = (a[0] + a[3]) + a[5]
+    ok = tr > 0
+    v = _jacobi3_rows(a, ok)
+    d0, d1, d2 = a[0], a[3], a[5]
+    r0 = (d1 < d0).astype(np.int64) + (d2 < d0)
+    r1 = (d0 <= d1).astype(np.int64) + (d2 < d1)
+    pick = lambda r, x0, x1, x2: np.where(r0 == r, x0, np.where(r1 == r, x1, x2))
+    l0, l1, l2 = pick(0, d0, d1, d2), pick(1, d0, d1, d2), pick(2, d0, d1, d2)
+    nx, ny, nz = pick(0, v[0], v[1], v[2]), pick(0, v[3], v[4], v[5]), pick(0, v[6], v[7], v[8])
+    with np.errstate(all="ignore"):
+        curv = np.where(ok, np.abs(l0) / tr, np.nan)
+    if view is None:
+        flip = (nz < 0) | ((nz == 0) & ((ny < 0) | ((ny == 0) & (nx < 0))))
+    else:
+        flip = ((view[0] - c64[:, 0]) * nx + (view[1] - c64[:, 1]) * ny) + (view[2] - c64[:, 2]) * nz < 0
+    flip = flip & ok
+    nrm = np.stack([np.where(flip, -x, x) for x in (nx, ny, nz)], 1)
+    nrm[~ok] = np.nan
+    eig = np.stack([l0, l1, l2], 1)
+    eig[~ok] = np.nan
+    return nrm.astype(np.float32), curv, eig, _normals_result(n, k, 0, (~ok).sum(), (ok & (l0 == l1)).sum(), flip.sum(), curv)

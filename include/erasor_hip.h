@@ -738,6 +738,54 @@ int erasor_hip_density_filter_clouds(erasor_hip_handle *h, const void *xyzi, siz
 int erasor_hip_density_filter_map(erasor_hip_handle *h, const erasor_density_filter *filter, uint8_t *keep_mask, float *kept_xyzi,
                                   size_t cap_points, erasor_density_result *res);
 
+/* ---- the surface a point lies on: every point's normal, curvature and covariance eigenvalues from its k nearest neighbours ---------
+ * replaces: what users of a cleaned map compute on the host next -- pcl::NormalEstimation over a KD-tree of the whole map -- and what
+ * a point-to-plane registration, a shaded rendering and telling a wall from scatter start from.  The contract, restated on the host by
+ * erasor_amd/evalmap.py (normals / normals_brute), which the device equals byte for byte.  Everything is float64 on the float32
+ * coordinates, every operation a separate IEEE operation in the order written:
+ *   - the neighbourhood of point i: the point itself first, then its k nearest other points in erasor_hip_knn_*'s order, (d2, j)
+ *     ascending, self excluded by index: m = k + 1 points, 2 <= k <= 32.  A point with fewer than k other points is short: its normal,
+ *     curvature and eigenvalues are NaN, and it is counted in n_short;
+ *   - centroid, per axis: s = ((0.0 + p_self) + p_n0) + ... in list order, c = s / (double)m;
+ *   - covariance: for each neighbourhood point in the same order e = p - c and cxx = cxx + ex*ex (likewise cxy, cxz, cyy, cyz, czz),
+ *     each from 0.0; after the loop each entry divided by (double)m, PCL's scale; tr = (cxx + cyy) + czz, taken before the solve;
+ *   - a point is degenerate if !(tr > 0) -- all m points identical: NaN outputs, counted in n_degenerate;
+ *   - the eigen-solve: cyclic Jacobi on the symmetric 3x3, pivots (0,1), (0,2), (1,2), the rotation of erasor_hip_refine_poses' 4x4
+ *     solve, a pivot that is exactly 0 skipped; it stops when all three off-diagonals are exactly 0 before a sweep, or after 32 sweeps.
+ *     The eigenvalues are the diagonal, ascending by (value, column index); the normal is the column of V of the first, not
+ *     renormalised.  n_ambiguous counts the points whose two smallest eigenvalues are exactly equal (an exactly collinear
+ *     neighbourhood: a direction that is defined by these rules, but arbitrary) -- counted, not hidden;
+ *   - curvature = fabs(l0) / tr, PCL's definition;
+ *   - orientation: with a viewpoint v, s = ((vx-px)*nx + (vy-py)*ny) + (vz-pz)*nz and all three components are negated iff s < 0;
+ *     without one ("up") iff nz < 0, or nz == 0 and ny < 0, or nz == 0 and ny == 0 and nx < 0.  n_flipped counts the negations;
+ *   - the curvature's statistics are taken over the finite curvatures, as erasor_score_stats says.
+ * Not offered: a radius neighbourhood, whose point count is unbounded (the list has no fixed size on the device and the sums no
+ * bounded order), and MLS smoothing -- the reason erasor_hip_knn_* gives for sigma: sums whose value depends on the order of their
+ * terms.  PCL is not a dependency of this project and nothing is pinned against it. */
+typedef struct erasor_normals_result {
+    uint64_t n_points;      /* points given */
+    uint64_t n_short;       /* points with fewer than k other points: NaN outputs */
+    uint64_t n_degenerate;  /* points whose neighbourhood has no extent (!(tr > 0)): NaN outputs */
+    uint64_t n_ambiguous;   /* points whose two smallest eigenvalues are exactly equal */
+    uint64_t n_flipped;     /* normals negated by the orientation rule */
+    erasor_score_stats curvature;  /* over the finite curvatures (n_points - n_short - n_degenerate of them) */
+} erasor_normals_result;
+
+/* The normals of every point of the cloud (XYZI rows, on the host or on the handle's device: is_device) from its neighbourhood inside
+ * that cloud -- pcl::NormalEstimation with setKSearch(k) and setViewPoint on the host.  viewpoint: three float64, or NULL for "up".
+ * All outputs are host buffers and optional: normals (n * 3 float32), curvature (n float64), eigenvalues (n * 3 float64, ascending);
+ * NULL asks for the rest only.  n == 0: ERASOR_OK, counts zero and statistics NaN.  Works in the evaluator's own scratch: announced
+ * nodes, tickets and the last step's clouds stay as they are.  ERASOR_E_INVALID: a non-finite coordinate, k outside 2 .. 32, a
+ * non-finite viewpoint, more than 2^30 points, res NULL.  ERASOR_E_STATE: a step in flight.  The search is erasor_hip_knn_*'s:
+ * thousands of copies of one point are quadratic. */
+int erasor_hip_normals_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, uint32_t k,
+                              const double *viewpoint /* NULL: up */, float *normals, double *curvature, double *eigenvalues,
+                              erasor_normals_result *res);
+/* the same over the handle's current map (the erasor_hip_get_map view, compacted on the device as erasor_hip_knn_map does, never
+ * copied to the host) -- pcl::NormalEstimation over the map.  ERASOR_E_STATE also: no map. */
+int erasor_hip_normals_map(erasor_hip_handle *h, uint32_t k, const double *viewpoint /* NULL: up */, float *normals, double *curvature,
+                           double *eigenvalues, erasor_normals_result *res);
+
 /* ---- maps without labels: label a third-party map from a dense labelled one, and the static points a method lost ----------------
  * Both search the overlap report's tree in FLANN's metric, as pcl::KdTreeFLANN (K = 1) does: float32 d^2 = ((0 + dx*dx) + dy*dy) + dz*dz
  * with dx = q.x - p.x in float, exact, the lowest index on ties.  Outputs are XYZI rows in caller HOST buffers; dst == NULL asks for
