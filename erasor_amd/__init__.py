@@ -362,7 +362,7 @@ class ErasorError(RuntimeError):
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "normals.hip.h", "render.hip.h", "revert_bins.hip.h",
-                                                 "exact_sort.hip.h", "exact_sort_core.h", "overlap_auto.h")]
+                                                 "exact_sort.hip.h", "exact_sort_core.h", "overlap_auto.h", "stream_place.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _SRC_DIR, "-s"])
@@ -1247,6 +1247,14 @@ class Erasor:
         m, a, b = C.c_int(0), C.c_double(0), C.c_double(0)
         self._check(lib().erasor_hip_overlap_auto(self._h, C.byref(m), C.byref(a), C.byref(b)))
         return m.value, a.value, b.value
+
+    def stream_pipes(self):
+        """where the handle's streams landed (erasor_hip_stream_pipes): {"pipes": [main, q0, q1, early] as me * 4 + pipe, -1 unknown or
+        not created, "n_pads": idle pad streams kept, "distinct_seen": different pipes the rehearsal saw}"""
+        p = (C.c_int * 4)()
+        a, b = C.c_int(0), C.c_int(0)
+        self._check(lib().erasor_hip_stream_pipes(self._h, p, C.byref(a), C.byref(b)))
+        return {"pipes": [int(v) for v in p], "n_pads": a.value, "distinct_seen": b.value}
 
     def step_log(self):
         """the last collected steps (up to 256), oldest first, as dicts: step, period_us (0: not consecutive), n_alloc / n_free / n_create

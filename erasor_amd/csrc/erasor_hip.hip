@@ -28,6 +28,7 @@
 
 #include "../../include/erasor_hip.h"
 #include "overlap_auto.h"
+#include "stream_place.h"
 #ifndef ERASOR_REV_GRID
 #define ERASOR_REV_GRID 128u  // workgroups of the per-bin launch (one reverted bin each; more bins than workgroups: a grid-stride loop)
 #endif
@@ -177,6 +178,13 @@ struct erasor_hip_handle {
     // k_voi_split / k_chunk_scan_* / k_voi_gather in overlap mode), and the events the two streams meet at
     hipStream_t bstream = nullptr;
     bool bstream_own = false;
+    // where the streams landed (stream_place.h): the rehearsal at handle creation steers the early stream, created later, onto a compute
+    // pipe of its own; the pads are idle streams that keep the runtime from handing out a taken queue again
+    StreamPlace place;
+    hipStream_t pads[SP_TRIES] = {nullptr, nullptr, nullptr, nullptr};
+    hipStream_t place_hold = nullptr;  // the candidate that found a free pipe: holds the place until early_stream() takes it
+    uint32_t *pipe_word = nullptr;  // pinned: k_stream_pipe's answer
+    bool early_shares_pipe = false;  // the early stream was seen on the pipe of main / q0 / q1 after all
     hipEvent_t ev_stats = nullptr, ev_srt4 = nullptr, ev_asm = nullptr, ev_early = nullptr, ev_scan = nullptr;
     unsigned n_chain = 0;
     // round 6: chains of announced scans are held back until `batch_n` of them can share one set of launches -- unless fewer than
@@ -1047,15 +1055,73 @@ static bool create_sides(erasor_hip_handle *h, int prio, int nqs_force) {
     h->cstream = nullptr;
     return true;
 }
+static int overlap_env();
+// ERASOR_HIP_NO_PLACEMENT=1: no rehearsal, no pads, no probe of the early stream (A/B switch)
+static bool placement_off() {
+    static const bool off = getenv("ERASOR_HIP_NO_PLACEMENT") != nullptr && atoi(getenv("ERASOR_HIP_NO_PLACEMENT")) != 0;
+    return off;
+}
+// the compute pipe `stream` is on right now, as me * 4 + pipe; -1: unknown.  One launch of one thread, and a wait for that stream.
+static int stream_pipe(erasor_hip_handle *h, hipStream_t stream) {
+    if (!h->pipe_word) return -1;
+    *h->pipe_word = STREAM_PIPE_UNKNOWN;
+    hipLaunchKernelGGL(k_stream_pipe, dim3(1), dim3(1), 0, stream, h->pipe_word);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return -1;
+    return sp_pipe_of_hw_id(*h->pipe_word);
+}
+// Handle creation, two query streams, the overlap not switched off: see where main, q0 and q1 landed, then create candidates until one lands
+// on a pipe none of them has (stream_place.h).  Outside any step or announcement: the step record counts none of it.
+static void place_rehearsal(erasor_hip_handle *h) {
+    if (hipHostMalloc((void **)&h->pipe_word, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
+        h->pipe_word = nullptr;
+        return;
+    }
+    const int pm = stream_pipe(h, h->stream), p0 = stream_pipe(h, h->qstream[0]), p1 = stream_pipe(h, h->qstream[1]);
+    if (!sp_begin(h->place, pm, p0, p1)) return;
+    hipStream_t cand[SP_TRIES] = {nullptr, nullptr, nullptr, nullptr};
+    int n = 0;
+    SpAction act = SP_GIVE_UP;
+    while (n < SP_TRIES) {
+        if (hipStreamCreateWithFlags(&cand[n], hipStreamNonBlocking) != hipSuccess) {
+            cand[n] = nullptr;
+            act = SP_GIVE_UP;
+            h->place.n_pads = 0;
+            h->place.done = true;
+            break;
+        }
+        act = sp_candidate(h->place, stream_pipe(h, cand[n]));
+        ++n;
+        if (act != SP_PAD) break;
+    }
+    if (act == SP_FREE) {
+        // The last candidate found the place (idle: its probe waited for it); the others stay as pads.  It is destroyed in early_stream(),
+        // right in front of the creation that is to land there, not here: a caller with host scans creates the copy stream at its first
+        // announcement, BEFORE the first deep step, and that stream would take the place.
+        h->place_hold = cand[n - 1];
+        for (int k = 0; k < n - 1; ++k) h->pads[k] = cand[k];
+    } else {
+        for (int k = 0; k < n; ++k)
+            if (cand[k]) (void)hipStreamDestroy(cand[k]);
+    }
+    if (getenv("ERASOR_HIP_PLACEMENT_LOG"))
+        fprintf(stderr, "[erasor_hip] placement: main %d q0 %d q1 %d, candidates %d %d %d %d -> %s, %d pad(s)\n", pm, p0, p1, h->place.cand[0],
+                h->place.cand[1], h->place.cand[2], h->place.cand[3], act == SP_FREE ? "a free pipe" : "none free", h->place.n_pads);
+}
 // the early stream of overlapped steps (one of the query streams when there are three; else created on first use)
 static bool early_stream(erasor_hip_handle *h) {
     if (h->bstream) return true;
+    if (h->place_hold) {  // (the runtime hands a new stream to the least-used queue: the one this leaves)
+        (void)hipStreamDestroy(h->place_hold);
+        h->place_hold = nullptr;
+    }
     if (hipStreamCreateWithFlags(&h->bstream, hipStreamNonBlocking) != hipSuccess) {
         h->bstream = nullptr;
         return false;
     }
     h->bstream_own = true;
     h->n_create += h->log_scope > 0;
+    // (one probe, no second try: a second creation inside a step would show in the step record)
+    if (h->pipe_word && h->place.fixed[0] >= 0) h->early_shares_pipe = sp_early(h->place, stream_pipe(h, h->bstream));
     // (a marker: whatever the runtime sets up at a stream's first command is set up here too, not beside the first early write-back;
     // ev_early is only ever waited for, and waiting for a marker that has passed is no wait)
     (void)hipEventRecord(h->ev_early, h->bstream);
@@ -1078,13 +1144,17 @@ static hipStream_t copy_stream(erasor_hip_handle *h) {
 // depending on where its streams landed).  The variable is read when the HIP runtime starts, so it is the PROCESS's business -- the
 // environment's, which may cap it: rounds 2-3 set it from a load-time constructor of this library, which changed the environment of
 // whoever loaded it.  Now: ONE warning when a process creates its second handle with few queues.
+// Under a cap of four queues a handle with two query streams does what it can by itself: it looks where main, q0 and q1 landed and steers
+// its early stream onto a compute pipe none of them has (place_rehearsal, stream_place.h).  What it still cannot do: the third query stream
+// of plain steps stays tied to GPU_MAX_HW_QUEUES >= 8 (create_sides), and the handle does not set the variable.
 static std::atomic<int> g_handles_created{0};
 static void warn_hw_queues_once() {
     static std::atomic<bool> warned{false};
     const char *e = getenv("GPU_MAX_HW_QUEUES");
     if ((e && atoi(e) >= 8) || warned.exchange(true)) return;
     fprintf(stderr, "[erasor_hip] several handles in one process and GPU_MAX_HW_QUEUES is %s: their streams share %s hardware queues and "
-                    "look-ahead chains of one handle may run one after the other\n",
+                    "look-ahead chains of one handle may run one after the other (a handle steers only its early stream onto a free compute "
+                    "pipe, erasor_hip_stream_pipes; a third query stream needs GPU_MAX_HW_QUEUES >= 8)\n",
             e ? e : "unset", e ? e : "HIP's default number of");
 }
 
@@ -1123,6 +1193,8 @@ static int create_handle(const erasor_params *p, int device, int nqs_force, eras
         return ERASOR_E_NO_DEVICE;
     }
     if (g_handles_created.fetch_add(1) >= 1) warn_hw_queues_once();
+    // (not for a handle with one query stream -- it overlaps only when forced to -- or three: the early stream is the third query stream there)
+    if (h->nqs == 2 && nqs_force <= 0 && overlap_env() != 0 && !placement_off()) place_rehearsal(h);
     worker_start(h);
     *out = h;
     return ERASOR_OK;
@@ -1161,6 +1233,10 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     for (hipEvent_t e : {h->ev_stats, h->ev_srt4, h->ev_asm, h->ev_early, h->ev_scan})
         if (e) (void)hipEventDestroy(e);
     if (h->bstream && h->bstream_own) (void)hipStreamDestroy(h->bstream);
+    for (hipStream_t &s : h->pads)
+        if (s) (void)hipStreamDestroy(s);
+    if (h->place_hold) (void)hipStreamDestroy(h->place_hold);
+    if (h->pipe_word) (void)hipHostFree(h->pipe_word);
     release(h->nvox); release(h->ng); release(h->out_off); release(h->ground_off); release(h->rej_off); release(h->crej_off);
     release(h->plane_n); release(h->plane_d);
     release(h->st1); release(h->status); release(h->action);
@@ -3930,6 +4006,16 @@ int erasor_hip_overlap_auto(erasor_hip_handle *h, int *mode, double *plain_perio
     if (mode) *mode = h->ova.mode;
     if (plain_period_us) *plain_period_us = h->ova.est[0];
     if (overlapped_period_us) *overlapped_period_us = h->ova.est[1];
+    return ERASOR_OK;
+}
+int erasor_hip_stream_pipes(erasor_hip_handle *h, int pipes[4], int *n_pads, int *distinct_seen) {
+    if (!h) return ERASOR_E_INVALID;
+    if (pipes) {
+        for (int k = 0; k < SP_FIXED; ++k) pipes[k] = h->place.fixed[k];
+        pipes[3] = h->place.early;
+    }
+    if (n_pads) *n_pads = h->place.n_pads;
+    if (distinct_seen) *distinct_seen = sp_distinct_seen(h->place);
     return ERASOR_OK;
 }
 int erasor_hip_step_log(erasor_hip_handle *h, erasor_step_log_entry *out, size_t cap, size_t *n) {

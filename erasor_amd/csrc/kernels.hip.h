@@ -4421,6 +4421,19 @@ __global__ void k_pad(unsigned long long ticks) {
     const unsigned long long t0 = wall_clock64();
     while (wall_clock64() - t0 < ticks) {}
 }
+// Where the stream this is launched on has landed: the wave's HW_ID (gfx9: [7:6] pipe, [26:24] queue, [31:30] me; tools/queue_probe.hip)
+// into a pinned word.  One thread.  STREAM_PIPE_UNKNOWN where there is no such register (the CPU stand-in): nothing is steered then.
+static constexpr uint32_t STREAM_PIPE_UNKNOWN = 0xFFFFFFFFu;
+__global__ void k_stream_pipe(uint32_t *out) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t id;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(id));
+    // (me is 1 or 2 for a compute queue: the word is never all ones)
+    *out = id;
+#else
+    *out = STREAM_PIPE_UNKNOWN;
+#endif
+}
 
 // start of a scan's query chain (its own stream): counters, bounding box, bucket totals, voxel count of this query side
 __device__ __forceinline__ void query_begin_body(Counters *qctr, uint32_t *bb, uint32_t *qb_tot, uint32_t qb_n, uint32_t *nvox, uint32_t nvox_init) {

@@ -921,6 +921,14 @@ typedef struct erasor_step_log_entry {
 } erasor_step_log_entry;
 /* the last records, oldest first: up to `cap` of them into out[], *n = how many were written */
 int erasor_hip_step_log(erasor_hip_handle *h, erasor_step_log_entry *out, size_t cap, size_t *n);
+/* Where the handle's streams landed.  A handle with two query streams sees, when it is created, which compute pipe its main stream and
+ * its two query streams run on, and steers the early stream of overlapped steps -- created at the first deep step -- onto a pipe none
+ * of them has: candidate streams are created one at a time (four at most); one that shares a pipe stays alive as an idle pad, the first
+ * one on a free pipe holds the place and is destroyed right in front of the early stream's creation, which lands where it was.  pipes[]: main, q0, q1, early, each me * 4 + pipe of the
+ * hardware's HW_ID, -1 for unknown or not created; *n_pads: pads kept; *distinct_seen: different pipes seen in all (the three streams'
+ * and every candidate's).  Handles with one or three query streams, ERASOR_HIP_OVERLAP=0 and ERASOR_HIP_NO_PLACEMENT=1: nothing is
+ * probed, every pipe is -1.  Results never depend on any of it. */
+int erasor_hip_stream_pipes(erasor_hip_handle *h, int pipes[4], int *n_pads, int *distinct_seen);
 /* Round 6 -- the query chains of SEVERAL announced nodes as one set of launches.  A node's query chain (voxelize_preserving_labels of
  * its scan, OfflineMapUpdater.cpp:237-241; lidar->body, R-POD keys, per-bin statistics, erasor.cpp:100-115) does not depend on the map,
  * and every launch of it is bound by latency, not by work: a launch that serves the same stage of n_scans scans costs what it costs for

@@ -90,6 +90,8 @@ def main(argv=None):
         return
     print("# %s: %d warm-up + %d steps on a fresh handle; decision now: %s (plain %.1f us, overlapped %.1f us)"
           % (a.workload, a.warmup, a.steps, "overlapped" if mode else "plain", p_plain, p_ov))
+    sp = seq.g.stream_pipes()
+    print("# streams (me * 4 + pipe; main, q0, q1, early): %s; %d pad(s) kept, %d different pipe(s) seen" % (sp["pipes"], sp["n_pads"], sp["distinct_seen"]))
     print("| step | period us | layout | took ahead | deep | alloc | free | create | grown | decision: mode block skip | sampled |")
     print("|---:|---:|---|---|---|---:|---:|---:|---|---|---|")
     for e in log:
