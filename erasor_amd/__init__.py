@@ -111,6 +111,34 @@ class RefineSummary(C.Structure):
                 "n_pairs_last": int(self.n_pairs_last), "sum_d2_first": float(self.sum_d2_first), "sum_d2_last": float(self.sum_d2_last)}
 
 
+class RefinePlaneParams(C.Structure):
+    """erasor_refine_plane_params (include/erasor_hip.h)"""
+    _fields_ = [("max_dist", C.c_double), ("eps_t", C.c_double), ("eps_r", C.c_double), ("max_iters", C.c_uint32), ("min_pairs", C.c_uint32),
+                ("normals_k", C.c_uint32), ("max_curvature", C.c_double), ("rank_tol", C.c_double)]
+
+
+class RefinePlaneRow(C.Structure):
+    """erasor_refine_plane_row (include/erasor_hip.h): one frame of refine_poses_plane"""
+    _fields_ = RefineRow._fields_ + [("rank", C.c_uint32), ("lambda_ratio", C.c_double), ("n_unusable_first", C.c_uint64),
+                                     ("n_unusable_last", C.c_uint64), ("rms_plane_first", C.c_double), ("rms_plane_last", C.c_double)]
+
+    def as_dict(self):
+        """evalmap.refine_poses_plane's row keys (the pose itself is returned beside the rows)"""
+        return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_ if k != "T"}
+
+
+class RefinePlaneSummary(C.Structure):
+    """erasor_refine_plane_summary (include/erasor_hip.h)"""
+    _fields_ = [("n_frames", C.c_uint64), ("n_status", C.c_uint64 * 5), ("n_pairs_first", C.c_uint64), ("n_pairs_last", C.c_uint64),
+                ("sum_d2_first", C.c_double), ("sum_d2_last", C.c_double), ("sum_r2_first", C.c_double), ("sum_r2_last", C.c_double),
+                ("n_map_no_normal", C.c_uint64)]
+
+    def as_dict(self):
+        """evalmap.refine_poses_plane's summary keys"""
+        return {k: ([int(v) for v in self.n_status] if k == "n_status" else float(getattr(self, k)) if t is C.c_double else int(getattr(self, k)))
+                for k, t in self._fields_}
+
+
 class ScanLabelRow(C.Structure):
     """erasor_scan_label_row (include/erasor_hip.h): one frame of label_scans, or their sum"""
     _fields_ = [("n_points", C.c_uint64), ("n_non_finite", C.c_uint64), ("n_label_out_of_range", C.c_uint64), ("n", (C.c_uint64 * 3) * 2)]
@@ -361,7 +389,7 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "normals.hip.h", "render.hip.h", "revert_bins.hip.h",
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "normals.hip.h", "refine_plane.hip.h", "render.hip.h", "revert_bins.hip.h",
                                                  "exact_sort.hip.h", "exact_sort_core.h", "overlap_auto.h", "stream_place.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
@@ -947,6 +975,45 @@ class Erasor:
         else:
             m = self._eval_cloud(map, kept)
             self._check(lib().erasor_hip_refine_poses_clouds(self._h, *m, *tail))
+        T = np.array([list(rows[f].T) for f in range(n_f)], np.float64).reshape(n_f, 4, 4)
+        return T, [rows[f].as_dict() for f in range(n_f)], summ.as_dict()
+
+    # -- every frame's pose refined point-to-plane against the map's normals (on the host: evalmap.refine_poses_plane) --
+    def refine_poses_plane(self, scans, T_body2origin, T_lidar2body=None, map=None, k=16, max_dist=1.0, max_curvature=1.0, rank_tol=1e-9,
+                           eps_t=1e-4, eps_r=1e-5, max_iters=20, min_pairs=100):
+        """refine_poses with the residual taken along the map's surface normals (erasor_hip_refine_poses_plane_clouds / _map): the map's
+        normals and curvature from its k nearest neighbours are computed once on the device; a scan point within max_dist of a map point
+        with a finite normal and a curvature <= max_curvature is a pair; the 6x6 normal equations are solved on the host over the
+        directions whose eigenvalue is above rank_tol times the largest.  A row's rank tells how many of the pose's six directions the
+        frame's pairs constrain; lambda_ratio how well the weakest one.  scans, poses, T_lidar2body and map as for refine_poses.
+        Returns (T_refined float64 [n, 4, 4], rows, summary) as evalmap.refine_poses_plane does, bit for bit."""
+        kept = []
+        if isinstance(scans, tuple):
+            ptr, offsets = scans
+            offs = np.ascontiguousarray(offsets, np.uint64)
+            q = (C.c_void_p(ptr), C.c_size_t(int(offs[-1]) if len(offs) else 0), 1)
+        else:
+            a = [_f32(s).reshape(-1, 4) for s in scans]
+            offs = np.zeros(len(a) + 1, np.uint64)
+            offs[1:] = np.cumsum([len(s) for s in a], dtype=np.uint64)
+            cat = _f32(np.concatenate(a) if a else np.zeros((0, 4), np.float32))
+            kept.append(cat)
+            q = (_p(cat), C.c_size_t(len(cat)), 0)
+        n_f = len(offs) - 1
+        Tb = _f32(np.asarray(T_body2origin, np.float32).reshape(n_f, 16) if n_f else np.zeros((1, 16), np.float32))
+        if T_lidar2body is not None:
+            kept.append(_f32(T_lidar2body).reshape(16))
+        Tl = None if T_lidar2body is None else _p(kept[-1])
+        prm = RefinePlaneParams(float(max_dist), float(eps_t), float(eps_r), int(max_iters), int(min_pairs), int(k), float(max_curvature),
+                                float(rank_tol))
+        rows = (RefinePlaneRow * max(n_f, 1))()
+        summ = RefinePlaneSummary()
+        tail = (q[0], q[1], _p(offs), C.c_size_t(n_f), C.c_int(q[2]), Tl, _p(Tb), C.byref(prm), rows, C.byref(summ))
+        if map is None:
+            self._check(lib().erasor_hip_refine_poses_plane_map(self._h, *tail))
+        else:
+            m = self._eval_cloud(map, kept)
+            self._check(lib().erasor_hip_refine_poses_plane_clouds(self._h, *m, *tail))
         T = np.array([list(rows[f].T) for f in range(n_f)], np.float64).reshape(n_f, 4, 4)
         return T, [rows[f].as_dict() for f in range(n_f)], summ.as_dict()
 

@@ -1,8 +1,8 @@
 // The offline analyses' host code: PR / RR evaluation (one estimate, many, by class), the overlap report, the frame check, the scans'
-// labels, the clustering, the k nearest neighbours and density filters, the normals, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
+// labels, the clustering, the k nearest neighbours and density filters, the normals, the point-to-plane refinement, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
 // at its end -- one translation unit, like the kernel headers -- so it sees the handle, ensure / LAUNCH / HIPC, scan_u32, radix_sort,
 // map_to_device and voxelize_device from there; nothing of the step path depends on this file.  Kernels: evaluate.hip.h, nearest.hip.h,
-// align.hip.h, label_scans.hip.h, cluster.hip.h, knn.hip.h, normals.hip.h, render.hip.h.
+// align.hip.h, label_scans.hip.h, cluster.hip.h, knn.hip.h, normals.hip.h, refine_plane.hip.h, render.hip.h.
 #pragma once
 
 extern "C" {
@@ -899,7 +899,7 @@ static int rf_run(erasor_hip_handle *h, const char *who, const float4 *map, uint
         if (grid)
             LAUNCH(h, h->stream, "rf_query", k_rf_query, grid, NN_QBLOCK, scans, (const uint32_t *)E.al_off.p, (const RfChunk *)E.rf_chunk.p, Tl,
                    (const RfPose *)E.rf_pose.p, (const uint32_t *)E.rf_live.p, map, T, gate2, E.rf_part.p, E.rf_ctr.p);
-        LAUNCH(h, h->stream, "rf_partials", k_rf_partials, cdiv(n_frames * RF_NSUM, 256), 256, (const double *)E.rf_part.p, (const uint32_t *)E.rf_cb.p,
+        LAUNCH(h, h->stream, "rf_partials", k_rf_partials<RF_NSUM>, cdiv(n_frames * RF_NSUM, 256), 256, (const double *)E.rf_part.p, (const uint32_t *)E.rf_cb.p,
                (const uint32_t *)E.rf_live.p, n_frames, E.rf_sums.p);
         HIPC(h, hipMemcpyAsync(S.data(), E.rf_sums.p, (size_t)n_frames * RF_NSUM * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPC(h, hipMemcpyAsync(c.data(), E.rf_ctr.p, (size_t)n_frames * RF_NCTR * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
@@ -1606,6 +1606,29 @@ static int nm_check_args(erasor_hip_handle *h, const char *who, uint32_t k, cons
     return ERASOR_OK;
 }
 
+// the device part: the normals and curvature of pts[0 .. n) (n > 0, T their tree) into E.nm_nrm (if want_nrm), E.nm_curv and E.nm_eig (if
+// want_eig), the counters into E.nm_ctr.  Nothing is copied out; erasor_hip_refine_poses_plane_* reads the two arrays where they lie.
+static int nm_device(erasor_hip_handle *h, const float4 *pts, uint32_t n, const NnTree &T, uint32_t k, const double *viewpoint, bool want_nrm,
+                     bool want_eig) {
+    auto &E = h->ev;
+    const size_t n1 = (size_t)n + 1;
+    if (ensure(h, E.nm_ctr, NM_NCTR) || ensure(h, E.nm_curv, n1) || (want_nrm && ensure(h, E.nm_nrm, 3 * n1)) || (want_eig && ensure(h, E.nm_eig, 3 * n1)))
+        return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.nm_ctr.p, 0, NM_NCTR * sizeof(unsigned long long), h->stream));
+    HIPC(h, hipMemsetAsync(E.nm_ctr.p + NM_C_CURV_MIN, 0xFF, sizeof(unsigned long long), h->stream));
+    float *nrm = want_nrm ? E.nm_nrm.p : nullptr;
+    double *eig = want_eig ? E.nm_eig.p : nullptr;
+    const uint32_t view = viewpoint ? 1u : 0u;
+    const double vx = viewpoint ? viewpoint[0] : 0.0, vy = viewpoint ? viewpoint[1] : 0.0, vz = viewpoint ? viewpoint[2] : 0.0;
+    const uint32_t g = cdiv(n, KN_QBLOCK);
+#define NM_QUERY(KC) LAUNCH(h, h->stream, "nm_query", k_nm_query<KC>, g, KN_QBLOCK, T, pts, k, view, vx, vy, vz, nrm, E.nm_curv.p, eig, E.nm_ctr.p)
+    if (k <= 8) NM_QUERY(8);
+    else if (k <= 16) NM_QUERY(16);
+    else NM_QUERY(32);
+#undef NM_QUERY
+    return ERASOR_OK;
+}
+
 static int nm_run(erasor_hip_handle *h, const char *who, const float4 *pts, uint32_t n, uint32_t k, const double *viewpoint, float *normals,
                   double *curvature, double *eigenvalues, erasor_normals_result *res) {
     auto &E = h->ev;
@@ -1617,25 +1640,10 @@ static int nm_run(erasor_hip_handle *h, const char *who, const float4 *pts, uint
         *res = r;
         return ERASOR_OK;
     }
-    const size_t n1 = (size_t)n + 1;
-    if (ensure(h, E.nm_ctr, NM_NCTR) || ensure(h, E.nn_hist, OV_SEL_MAX * 256) || ensure(h, E.nm_curv, n1) || (normals && ensure(h, E.nm_nrm, 3 * n1)) ||
-        (eigenvalues && ensure(h, E.nm_eig, 3 * n1)))
-        return ERASOR_E_NO_DEVICE;
-    HIPC(h, hipMemsetAsync(E.nm_ctr.p, 0, NM_NCTR * sizeof(unsigned long long), h->stream));
-    HIPC(h, hipMemsetAsync(E.nm_ctr.p + NM_C_CURV_MIN, 0xFF, sizeof(unsigned long long), h->stream));
+    if (ensure(h, E.nn_hist, OV_SEL_MAX * 256)) return ERASOR_E_NO_DEVICE;
     NnTree T;
     int rc = nn_build(h, pts, n, who, "cloud", "point(s)", &T);
-    if (rc) return rc;
-    float *nrm = normals ? E.nm_nrm.p : nullptr;
-    double *eig = eigenvalues ? E.nm_eig.p : nullptr;
-    const uint32_t view = viewpoint ? 1u : 0u;
-    const double vx = viewpoint ? viewpoint[0] : 0.0, vy = viewpoint ? viewpoint[1] : 0.0, vz = viewpoint ? viewpoint[2] : 0.0;
-    const uint32_t g = cdiv(n, KN_QBLOCK);
-#define NM_QUERY(KC) LAUNCH(h, h->stream, "nm_query", k_nm_query<KC>, g, KN_QBLOCK, T, pts, k, view, vx, vy, vz, nrm, E.nm_curv.p, eig, E.nm_ctr.p)
-    if (k <= 8) NM_QUERY(8);
-    else if (k <= 16) NM_QUERY(16);
-    else NM_QUERY(32);
-#undef NM_QUERY
+    if (rc || (rc = nm_device(h, pts, n, T, k, viewpoint, normals != nullptr, eigenvalues != nullptr))) return rc;
     unsigned long long c[NM_NCTR];
     if ((rc = d2h(h, c, E.nm_ctr.p, NM_NCTR * sizeof(unsigned long long)))) return rc;
     r.n_short = c[NM_C_SHORT];
@@ -1673,6 +1681,298 @@ int erasor_hip_normals_map(erasor_hip_handle *h, uint32_t k, const double *viewp
     uint32_t n = 0;
     if ((rc = map_on_device(h, who, h->ev.map, &p, &n))) return rc;
     return nm_run(h, who, p, n, k, viewpoint, normals, curvature, eigenvalues, res);
+}
+
+// ---- every frame's pose refined point-to-plane against the map's normals, all frames side by side (kernel: refine_plane.hip.h) ----
+// rf_run's shape, with the map's normals computed first by nm_device over the same tree and left on the device; per iteration the poses
+// and live flags up, k_rfp_query and k_rf_partials, the frames' 29 sums and three counters back, and the 6x6 solve below on the host,
+// restated in plain Python floats by evalmap._jacobi6 / refine_plane_solve.
+
+// rf_jacobi4 on a symmetric 6x6: pivots (p, q), p < q, row-major
+static void rfp_jacobi6(double A[6][6], double V[6][6]) {
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 32; ++sweep) {
+        bool diagonal = true;
+        for (int i = 0; i < 5; ++i)
+            for (int j = i + 1; j < 6; ++j) diagonal = diagonal && A[i][j] == 0.0;
+        if (diagonal) break;
+        for (int p = 0; p < 5; ++p)
+            for (int q = p + 1; q < 6; ++q) {
+                const double apq = A[p][q];
+                if (apq == 0.0) continue;
+                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+                const double at = theta < 0.0 ? -theta : theta;
+                double t = 1.0 / (at + sqrt(theta * theta + 1.0));
+                if (theta < 0.0) t = -t;
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < 6; ++k) {  // A <- A J
+                    const double akp = A[k][p], akq = A[k][q];
+                    A[k][p] = c * akp - s * akq;
+                    A[k][q] = s * akp + c * akq;
+                }
+                for (int k = 0; k < 6; ++k) {  // A <- Jt A
+                    const double apk = A[p][k], aqk = A[q][k];
+                    A[p][k] = c * apk - s * aqk;
+                    A[q][k] = s * apk + c * aqk;
+                }
+                A[p][q] = 0.0;
+                for (int i = 0; i < 6; ++i)
+                    for (int j = i + 1; j < 6; ++j) A[j][i] = A[i][j];
+                for (int k = 0; k < 6; ++k) {  // V <- V J
+                    const double vkp = V[k][p], vkq = V[k][q];
+                    V[k][p] = c * vkp - s * vkq;
+                    V[k][q] = s * vkp + c * vkq;
+                }
+            }
+    }
+}
+
+// one frame's update from its sums S (RFP_NSUM): the pseudo-inverse of the normal equations over the eigen-directions above rank_tol,
+// in index order; the rotation from the half vector, R <- D R, t <- t + x[3..5].  Returns the rank; 0: P is untouched.  *ratio:
+// lambda_min / lambda_max, NaN when lambda_max is not > 0.
+static uint32_t rfp_solve(const double *S, double rank_tol, RfPose &P, double *step_t, double *step_r, double *ratio) {
+    double A[6][6], V[6][6], b[6], x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int k = 0;
+    for (int a = 0; a < 6; ++a)
+        for (int c = a; c < 6; ++c, ++k) A[a][c] = A[c][a] = S[k];
+    for (int a = 0; a < 6; ++a) b[a] = -S[21 + a];
+    rfp_jacobi6(A, V);
+    double lmax = A[0][0], lmin = A[0][0];
+    for (int i = 1; i < 6; ++i) {
+        if (A[i][i] > lmax) lmax = A[i][i];
+        if (A[i][i] < lmin) lmin = A[i][i];
+    }
+    *ratio = lmax > 0 ? lmin / lmax : std::numeric_limits<double>::quiet_NaN();
+    uint32_t rank = 0;
+    for (int i = 0; i < 6; ++i) {
+        if (!(lmax > 0 && A[i][i] > rank_tol * lmax)) continue;
+        ++rank;
+        const double g = (((((V[0][i] * b[0] + V[1][i] * b[1]) + V[2][i] * b[2]) + V[3][i] * b[3]) + V[4][i] * b[4]) + V[5][i] * b[5]) / A[i][i];
+        for (int a = 0; a < 6; ++a) x[a] = x[a] + V[a][i] * g;
+    }
+    *step_t = 0.0;
+    *step_r = 0.0;
+    if (!rank) return 0;
+    const double hx = 0.5 * x[0], hy = 0.5 * x[1], hz = 0.5 * x[2];
+    const double w = 1.0 / sqrt(1.0 + ((hx * hx + hy * hy) + hz * hz));
+    const double qx = hx * w, qy = hy * w, qz = hz * w;
+    const double xx = qx * qx, yy = qy * qy, zz = qz * qz, xy = qx * qy, xz = qx * qz, yz = qy * qz, wx = w * qx, wy = w * qy, wz = w * qz;
+    const double D[3][3] = {{1.0 - 2.0 * (yy + zz), 2.0 * (xy - wz), 2.0 * (xz + wy)},
+                            {2.0 * (xy + wz), 1.0 - 2.0 * (xx + zz), 2.0 * (yz - wx)},
+                            {2.0 * (xz - wy), 2.0 * (yz + wx), 1.0 - 2.0 * (xx + yy)}};
+    double R[9];
+    for (int a = 0; a < 3; ++a)
+        for (int c = 0; c < 3; ++c) R[3 * a + c] = (D[a][0] * P.R[c] + D[a][1] * P.R[3 + c]) + D[a][2] * P.R[6 + c];
+    for (int e = 0; e < 9; ++e) P.R[e] = R[e];
+    for (int a = 0; a < 3; ++a) P.t[a] = P.t[a] + x[3 + a];
+    *step_t = sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]);
+    *step_r = 2.0 * sqrt((xx + yy) + zz);
+    return rank;
+}
+
+static int rfp_check_args(erasor_hip_handle *h, const char *who, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets,
+                          size_t n_frames, const float *T_lidar2body, const float *T_body2origin, const erasor_refine_plane_params *p) {
+    if (!p) return invalid(h, who, "params is NULL");
+    if (p->normals_k < NM_MIN_K || p->normals_k > KN_MAX_K) return invalid(h, who, "normals_k must be within 2 .. 32");
+    if (!(p->max_curvature > 0) || !std::isfinite(p->max_curvature)) return invalid(h, who, "max_curvature must be a finite number > 0");
+    if (!(p->rank_tol >= 0 && p->rank_tol < 1)) return invalid(h, who, "rank_tol must be a finite number within [0, 1)");
+    const erasor_refine_params base = {p->max_dist, p->eps_t, p->eps_r, p->max_iters, p->min_pairs};
+    return rf_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, &base);
+}
+
+static int rfp_run(erasor_hip_handle *h, const char *who, const float4 *map, uint32_t n_map, const float4 *scans, uint32_t n, const uint64_t *offsets,
+                   uint32_t n_frames, const float *T_lidar2body, const float *T_body2origin, const erasor_refine_plane_params &prm,
+                   erasor_refine_plane_row *rows, erasor_refine_plane_summary *summary) {
+    auto &E = h->ev;
+    if (!n_map && n) {
+        h->err = std::string(who) + ": empty map with a non-empty frame (no nearest point to match)";
+        return ERASOR_E_INVALID;
+    }
+    const uint32_t nf = std::max(n_frames, 1u);
+    // the frames' chunks of RF_CHUNK points, counted from each frame's own first point (as rf_run)
+    std::vector<uint32_t> off(n_frames + 1), cb(n_frames + 1, 0u);
+    for (uint32_t f = 0; f <= n_frames; ++f) off[f] = (uint32_t)offsets[f];
+    for (uint32_t f = 0; f < n_frames; ++f) cb[f + 1] = cb[f] + cdiv(off[f + 1] - off[f], RF_CHUNK);
+    const uint32_t grid = cb[n_frames];
+    std::vector<RfChunk> chunks(grid);
+    for (uint32_t f = 0; f < n_frames; ++f)
+        for (uint32_t b = cb[f]; b < cb[f + 1]; ++b) chunks[b] = RfChunk{f, b - cb[f]};
+    if (ensure(h, E.al_off, (size_t)nf + 1) || ensure(h, E.rf_cb, (size_t)nf + 1) || ensure(h, E.rf_chunk, (size_t)grid + 1) || ensure(h, E.rf_pose, nf) ||
+        ensure(h, E.rf_live, nf) || ensure(h, E.rf_part, ((size_t)grid + 1) * RFP_NSUM) || ensure(h, E.rf_sums, (size_t)nf * RFP_NSUM) ||
+        ensure(h, E.rf_ctr, (size_t)nf * RFP_NCTR))
+        return ERASOR_E_NO_DEVICE;
+    // one tree for the map's normals and for every iteration; the normals and the curvature stay in E.nm_nrm / E.nm_curv
+    NnTree T;
+    int rc = nn_build(h, map, n_map, who, "map", "map point(s)", &T);
+    if (rc) return rc;
+    uint64_t n_no_normal = 0;
+    if (n_map) {
+        if ((rc = nm_device(h, map, n_map, T, prm.normals_k, nullptr, true, false))) return rc;
+        unsigned long long nc[NM_NCTR];
+        if ((rc = d2h(h, nc, E.nm_ctr.p, NM_NCTR * sizeof(unsigned long long)))) return rc;
+        n_no_normal = nc[NM_C_SHORT] + nc[NM_C_DEGENERATE];
+    }
+    HIPC(h, hipMemcpyAsync(E.al_off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(E.rf_cb.p, cb.data(), cb.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    if (grid) HIPC(h, hipMemcpyAsync(E.rf_chunk.p, chunks.data(), (size_t)grid * sizeof(RfChunk), hipMemcpyHostToDevice, h->stream));
+    const Xf Tl = to_xf(T_lidar2body ? T_lidar2body : AL_IDENTITY);
+    const double gate2 = prm.max_dist * prm.max_dist;
+    const uint64_t min_pairs = std::max(prm.min_pairs, 1u);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+
+    std::vector<RfPose> P(nf), P0(nf);
+    for (uint32_t f = 0; f < n_frames; ++f) {  // the float32 pose, widened
+        const float *Tf = T_body2origin + 16 * (size_t)f;
+        for (int a = 0; a < 3; ++a) {
+            for (int b = 0; b < 3; ++b) P[f].R[3 * a + b] = (double)Tf[4 * a + b];
+            P[f].t[a] = (double)Tf[4 * a + 3];
+        }
+        P0[f] = P[f];
+    }
+    std::vector<uint32_t> live(nf, 1u), status(nf, ERASOR_REFINE_MAX_ITERS), iters(nf, 0u), rank(nf, 0u);
+    std::vector<double> S((size_t)nf * RFP_NSUM, 0.0), d2_first(nf, 0.0), r2_first(nf, 0.0), ratio(nf, nan);
+    std::vector<unsigned long long> c((size_t)nf * RFP_NCTR, 0ull), pairs_first(nf, 0ull), non_finite(nf, 0ull), unusable_first(nf, 0ull);
+    // the live frames' sums and counters under the poses P (into S and c; a frame that is not live keeps what it had)
+    auto evaluate = [&]() -> int {
+        if (!n_frames) return ERASOR_OK;
+        HIPC(h, hipMemcpyAsync(E.rf_pose.p, P.data(), (size_t)n_frames * sizeof(RfPose), hipMemcpyHostToDevice, h->stream));
+        HIPC(h, hipMemcpyAsync(E.rf_live.p, live.data(), (size_t)n_frames * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        HIPC(h, hipMemsetAsync(E.rf_ctr.p, 0, (size_t)n_frames * RFP_NCTR * sizeof(unsigned long long), h->stream));
+        if (grid)
+            LAUNCH(h, h->stream, "rfp_query", k_rfp_query, grid, NN_QBLOCK, scans, (const uint32_t *)E.al_off.p, (const RfChunk *)E.rf_chunk.p, Tl,
+                   (const RfPose *)E.rf_pose.p, (const uint32_t *)E.rf_live.p, map, (const float *)E.nm_nrm.p,
+                   (const unsigned long long *)E.nm_curv.p, T, gate2, prm.max_curvature, E.rf_part.p, E.rf_ctr.p);
+        LAUNCH(h, h->stream, "rfp_partials", k_rf_partials<RFP_NSUM>, cdiv(n_frames * RFP_NSUM, 256), 256, (const double *)E.rf_part.p,
+               (const uint32_t *)E.rf_cb.p, (const uint32_t *)E.rf_live.p, n_frames, E.rf_sums.p);
+        HIPC(h, hipMemcpyAsync(S.data(), E.rf_sums.p, (size_t)n_frames * RFP_NSUM * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipMemcpyAsync(c.data(), E.rf_ctr.p, (size_t)n_frames * RFP_NCTR * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
+        return ERASOR_OK;
+    };
+    uint32_t n_live = n_frames;
+    for (uint32_t it = 1; it <= prm.max_iters && n_live; ++it) {
+        if ((rc = evaluate())) return rc;
+        for (uint32_t f = 0; f < n_frames; ++f) {
+            if (!live[f]) continue;
+            const double *Sf = &S[(size_t)f * RFP_NSUM];
+            const uint64_t np = c[(size_t)f * RFP_NCTR + RFP_PAIRS];
+            if (it == 1) {
+                pairs_first[f] = np;
+                d2_first[f] = Sf[28];
+                r2_first[f] = Sf[27];
+                non_finite[f] = c[(size_t)f * RFP_NCTR + RFP_NON_FINITE];
+                unusable_first[f] = c[(size_t)f * RFP_NCTR + RFP_UNUSABLE];
+            }
+            bool ended = false;
+            if (np < min_pairs) {  // the frame keeps the pose it has
+                status[f] = (uint64_t)(off[f + 1] - off[f]) == non_finite[f] ? ERASOR_REFINE_NO_POINTS : ERASOR_REFINE_FEW_PAIRS;
+                ended = true;
+            } else {
+                double st, sr;
+                rank[f] = rfp_solve(Sf, prm.rank_tol, P[f], &st, &sr, &ratio[f]);
+                if (!rank[f]) {  // nothing to solve for: the pose is kept
+                    status[f] = ERASOR_REFINE_DEGENERATE;
+                    ended = true;
+                } else {
+                    iters[f] = it;
+                    if (st <= prm.eps_t && sr <= prm.eps_r) {
+                        status[f] = ERASOR_REFINE_CONVERGED;
+                        ended = true;
+                    }
+                }
+            }
+            if (ended) {
+                live[f] = 0;
+                --n_live;
+            }
+        }
+    }
+    // the returned poses' pairs, distances and residuals: one more evaluation of every frame, nothing updated
+    std::fill(live.begin(), live.end(), 1u);
+    if ((rc = evaluate())) return rc;
+    erasor_refine_plane_summary sm;
+    memset(&sm, 0, sizeof(sm));
+    sm.n_frames = n_frames;
+    sm.n_map_no_normal = n_no_normal;
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const uint64_t np = c[(size_t)f * RFP_NCTR + RFP_PAIRS];
+        const double d2 = S[(size_t)f * RFP_NSUM + 28], r2 = S[(size_t)f * RFP_NSUM + 27];
+        sm.n_status[status[f]] += 1;
+        sm.n_pairs_first += pairs_first[f];
+        sm.n_pairs_last += np;
+        sm.sum_d2_first = sm.sum_d2_first + d2_first[f];
+        sm.sum_d2_last = sm.sum_d2_last + d2;
+        sm.sum_r2_first = sm.sum_r2_first + r2_first[f];
+        sm.sum_r2_last = sm.sum_r2_last + r2;
+        if (!rows) continue;
+        erasor_refine_plane_row r;
+        memset(&r, 0, sizeof(r));
+        const RfPose &A = P[f], &B = P0[f];
+        for (int a = 0; a < 3; ++a) {
+            for (int b = 0; b < 3; ++b) r.T[4 * a + b] = A.R[3 * a + b];
+            r.T[4 * a + 3] = A.t[a];
+        }
+        r.T[15] = 1.0;
+        r.status = status[f];
+        r.iters = iters[f];
+        r.n_points = off[f + 1] - off[f];
+        r.n_non_finite = non_finite[f];
+        r.n_pairs_first = pairs_first[f];
+        r.n_pairs_last = np;
+        r.rms_first = pairs_first[f] ? sqrt(d2_first[f] / (double)pairs_first[f]) : nan;
+        r.rms_last = np ? sqrt(d2 / (double)np) : nan;
+        const double dx = A.t[0] - B.t[0], dy = A.t[1] - B.t[1], dz = A.t[2] - B.t[2];
+        r.moved_t = sqrt((dx * dx + dy * dy) + dz * dz);
+        double tr = 0.0;  // trace of R R0t: the rows' dot products, one after another
+        for (int a = 0; a < 3; ++a) tr = tr + ((A.R[3 * a] * B.R[3 * a] + A.R[3 * a + 1] * B.R[3 * a + 1]) + A.R[3 * a + 2] * B.R[3 * a + 2]);
+        double cs = (tr - 1.0) / 2.0;
+        if (cs > 1.0) cs = 1.0;
+        if (cs < -1.0) cs = -1.0;
+        r.moved_r = acos(cs);
+        r.rank = rank[f];
+        r.lambda_ratio = ratio[f];
+        r.n_unusable_first = unusable_first[f];
+        r.n_unusable_last = c[(size_t)f * RFP_NCTR + RFP_UNUSABLE];
+        r.rms_plane_first = pairs_first[f] ? sqrt(r2_first[f] / (double)pairs_first[f]) : nan;
+        r.rms_plane_last = np ? sqrt(r2 / (double)np) : nan;
+        rows[f] = r;
+    }
+    if (summary) *summary = sm;
+    return ERASOR_OK;
+}
+
+int erasor_hip_refine_poses_plane_clouds(erasor_hip_handle *h, const void *map_xyzi, size_t n_map, int map_is_device, const void *scans_xyzi,
+                                         size_t n_scan_points, const uint64_t *offsets, size_t n_frames, int scans_are_device,
+                                         const float T_lidar2body[16], const float *T_body2origin, const erasor_refine_plane_params *params,
+                                         erasor_refine_plane_row *rows, erasor_refine_plane_summary *summary) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_refine_poses_plane_clouds";
+    int rc = rfp_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, params);
+    if (rc || (rc = check_cloud(h, who, "NULL map or more than 2^30 map points", map_xyzi, n_map))) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr, *q = nullptr;
+    if ((rc = ev_input(h, map_xyzi, n_map, map_is_device, h->ev.gt, &m)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q)))
+        return rc;
+    return rfp_run(h, who, m, (uint32_t)n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, *params, rows,
+                   summary);
+}
+
+int erasor_hip_refine_poses_plane_map(erasor_hip_handle *h, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                                      int scans_are_device, const float T_lidar2body[16], const float *T_body2origin,
+                                      const erasor_refine_plane_params *params, erasor_refine_plane_row *rows,
+                                      erasor_refine_plane_summary *summary) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_refine_poses_plane_map";
+    int rc = rfp_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, params);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr, *q = nullptr;
+    uint32_t n_map = 0;
+    if ((rc = map_on_device(h, who, h->ev.map, &m, &n_map)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q))) return rc;
+    return rfp_run(h, who, m, n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, *params, rows, summary);
 }
 
 // ---- label_map (fill_removert_intensity.cpp:24-59, compare_map.cpp:77-110) and calc_complement (compare_complement.cpp:43-75): the

@@ -44,6 +44,7 @@
 #include "cluster.hip.h"
 #include "knn.hip.h"
 #include "normals.hip.h"
+#include "refine_plane.hip.h"
 #include "render.hip.h"
 
 using namespace ek;

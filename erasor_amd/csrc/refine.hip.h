@@ -13,7 +13,8 @@
 // writes, al_put_frames' per-workgroup table in its place); lanes without a pair hold +0.0; inside a chunk the halving tree
 // v[i] += v[i + s], s = 128, 64 through LDS and s = 32 .. 1 by shuffles inside wavefront 0.  k_rf_partials then adds a frame's chunk
 // partials one after another in chunk order from 0.0, one lane per (frame, component).  No float atomics; the counts are integer
-// atomics, one per wavefront.
+// atomics, one per wavefront.  The chunk's tree is rf_reduce and the second launch takes its component count as a template parameter:
+// refine_plane.hip.h adds its 29 sums by the same rule.
 //
 // LDS: the walk's [NN_STACK][NN_QBLOCK] stack (26 KB) is dead once every lane has its neighbour, and the tree over the wavefronts
 // reuses it, RF_GROUP components at a time ([RF_GROUP][256] doubles = 16 KB).  A frame that has ended is frozen: its workgroups return
@@ -45,6 +46,54 @@ struct RfPose {
 struct RfChunk {
     uint32_t frame, chunk;
 };
+
+// The chunk's defined sum of every lane's NSUM values v, stored by lane 0 to out[0 .. NSUM): the halving tree v[i] += v[i + s].  Every lane
+// of the workgroup (RF_CHUNK lanes) calls it with the walk over; red: the workgroup's LDS, [GROUP][RF_CHUNK] doubles.  GROUP components
+// cross the wavefronts together (the last group may be short); which ones travel together does not change a sum.
+template <uint32_t NSUM, uint32_t GROUP>
+__device__ __forceinline__ void rf_reduce(double (&v)[NSUM], double *red, uint32_t t, double *__restrict__ out) {
+    static_assert(GROUP * RF_CHUNK * sizeof(double) <= NN_STACK * NN_QBLOCK * sizeof(uint32_t), "the tree fits the walk's stack");
+    // s = 128, 64: lanes [s, 2s) hand their values to lanes [0, s), a group of components at a time
+    __syncthreads();  // (every lane's walk is over: the stack is free)
+#pragma unroll
+    for (uint32_t g = 0; g < NSUM; g += GROUP) {
+        if (t >= 128) {
+#pragma unroll
+            for (uint32_t c = 0; c < GROUP; ++c)
+                if (g + c < NSUM) red[c * RF_CHUNK + t] = v[g + c];
+        }
+        __syncthreads();
+        if (t < 128) {
+#pragma unroll
+            for (uint32_t c = 0; c < GROUP; ++c)
+                if (g + c < NSUM) v[g + c] += red[c * RF_CHUNK + t + 128];
+            if (t >= 64) {
+#pragma unroll
+                for (uint32_t c = 0; c < GROUP; ++c)
+                    if (g + c < NSUM) red[c * RF_CHUNK + t] = v[g + c];
+            }
+        }
+        __syncthreads();
+        if (t < 64) {
+#pragma unroll
+            for (uint32_t c = 0; c < GROUP; ++c)
+                if (g + c < NSUM) v[g + c] += red[c * RF_CHUNK + t + 64];
+        }
+        // (the next group writes rows [128, 256) first, which nobody reads after the barrier above, and rows [64, 128) only after
+        // its own first barrier, behind wavefront 0's reads here)
+    }
+    if (t >= 64) return;
+    // s = 32 .. 1 inside wavefront 0: lane i < s takes lane i + s (the other lanes' values are not used again)
+#pragma unroll
+    for (uint32_t s = 32; s >= 1; s >>= 1) {
+#pragma unroll
+        for (uint32_t c = 0; c < NSUM; ++c) v[c] += __shfl_down(v[c], s);
+    }
+    if (t == 0) {
+#pragma unroll
+        for (uint32_t c = 0; c < NSUM; ++c) out[c] = v[c];
+    }
+}
 
 // (1) one scan point per lane, one chunk per workgroup.  off: [n_frames + 1]; chunks: [grid]; pose, live: [n_frames]; map: the points
 // the tree was built over, in their own order.  part: [grid][RF_NSUM]; ctr: [n_frames][RF_NCTR], zeroed by the host.  T.n > 0.
@@ -92,54 +141,20 @@ __global__ __launch_bounds__(NN_QBLOCK) void k_rf_query(const float4 *__restrict
     }
     ev_commit(ctr + (size_t)f * RF_NCTR, RF_PAIRS, pair);
     ev_commit(ctr + (size_t)f * RF_NCTR, RF_NON_FINITE, bad);
-    // s = 128, 64: lanes [s, 2s) hand their values to lanes [0, s), a group of components at a time
-    __syncthreads();  // (every lane's walk is over: the stack is free)
-#pragma unroll
-    for (uint32_t g = 0; g < RF_NSUM; g += RF_GROUP) {
-        if (t >= 128) {
-#pragma unroll
-            for (uint32_t c = 0; c < RF_GROUP; ++c) red[c * RF_CHUNK + t] = v[g + c];
-        }
-        __syncthreads();
-        if (t < 128) {
-#pragma unroll
-            for (uint32_t c = 0; c < RF_GROUP; ++c) v[g + c] += red[c * RF_CHUNK + t + 128];
-            if (t >= 64) {
-#pragma unroll
-                for (uint32_t c = 0; c < RF_GROUP; ++c) red[c * RF_CHUNK + t] = v[g + c];
-            }
-        }
-        __syncthreads();
-        if (t < 64) {
-#pragma unroll
-            for (uint32_t c = 0; c < RF_GROUP; ++c) v[g + c] += red[c * RF_CHUNK + t + 64];
-        }
-        // (the next group writes rows [128, 256) first, which nobody reads after the barrier above, and rows [64, 128) only after
-        // its own first barrier, behind wavefront 0's reads here)
-    }
-    if (t >= 64) return;
-    // s = 32 .. 1 inside wavefront 0: lane i < s takes lane i + s (the other lanes' values are not used again)
-#pragma unroll
-    for (uint32_t s = 32; s >= 1; s >>= 1) {
-#pragma unroll
-        for (uint32_t c = 0; c < RF_NSUM; ++c) v[c] += __shfl_down(v[c], s);
-    }
-    if (t == 0) {
-#pragma unroll
-        for (uint32_t c = 0; c < RF_NSUM; ++c) part[(size_t)blockIdx.x * RF_NSUM + c] = v[c];
-    }
+    rf_reduce<RF_NSUM, RF_GROUP>(v, red, t, part + (size_t)blockIdx.x * RF_NSUM);
 }
 
 // (2) one lane per (frame, component): the frame's chunk partials, one after another in chunk order, from 0.0.  cb: [n_frames + 1],
-// cb[f] the frame's first chunk; sums: [n_frames][RF_NSUM], written for live frames only.
+// cb[f] the frame's first chunk; part: [chunks][NSUM]; sums: [n_frames][NSUM], written for live frames only.
+template <uint32_t NSUM>
 __global__ __launch_bounds__(256) void k_rf_partials(const double *__restrict__ part, const uint32_t *__restrict__ cb,
                                                       const uint32_t *__restrict__ live, uint32_t n_frames, double *__restrict__ sums) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_frames * RF_NSUM) return;
-    const uint32_t f = k / RF_NSUM, c = k % RF_NSUM;
+    if (k >= n_frames * NSUM) return;
+    const uint32_t f = k / NSUM, c = k % NSUM;
     if (!live[f]) return;
     double s = 0.0;
-    for (uint32_t b = cb[f]; b < cb[f + 1]; ++b) s += part[(size_t)b * RF_NSUM + c];
+    for (uint32_t b = cb[f]; b < cb[f + 1]; ++b) s += part[(size_t)b * NSUM + c];
     sums[k] = s;
 }
 

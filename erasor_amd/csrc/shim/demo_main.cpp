@@ -1129,6 +1129,10 @@ static int align_mode(int argc, char **argv) {
 // is flagged when it did not converge or moved more than max_dist.  Writes <poses_out> in poses_lidar2body.csv's own format -- the
 // file's lines as they are, x y z qx qy qz qw of the refined frames replaced (17 digits; a frame without enough pairs keeps its line) --
 // so that it can take the pose file's place in the run.
+// --refine-plane <rosparam.yaml> <poses_out> [n_frames] [max_dist = 1.0] [max_iters = 20] [k = 16]: the same mode with the residual taken
+// along the map's surface normals (erasor_hip_refine_poses_plane_clouds; k: the normals' neighbourhood).  Each row also prints the rank of
+// the frame's normal equations, lambda_ratio and the plane rms; a frame whose pairs constrain fewer than the pose's six directions is
+// flagged -- the directions left out were not moved.
 static void rot_to_quat(const double *T, double q[4]) {  // (x y z w) of T's rotation (row-major 4x4): the largest of the four pivots
     const double r00 = T[0], r01 = T[1], r02 = T[2], r10 = T[4], r11 = T[5], r12 = T[6], r20 = T[8], r21 = T[9], r22 = T[10];
     const double tr = r00 + r11 + r22;
@@ -1148,7 +1152,7 @@ static void rot_to_quat(const double *T, double q[4]) {  // (x y z w) of T's rot
     const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     for (int k = 0; k < 4; ++k) q[k] /= n;
 }
-static int refine_mode(int argc, char **argv) {
+static int refine_mode(int argc, char **argv, bool plane) {
     if (argc < 4) return 2;
     const std::string out_path = argv[3];
     const int max_frames = argc > 4 ? atoi(argv[4]) : 1 << 30;
@@ -1210,14 +1214,31 @@ static int refine_mode(int argc, char **argv) {
     }
     const size_t n_frames = offsets.size() - 1;
     std::vector<erasor_align_row> before(std::max<size_t>(n_frames, 1)), after(std::max<size_t>(n_frames, 1));
-    std::vector<erasor_refine_row> rows(std::max<size_t>(n_frames, 1));
-    erasor_refine_summary sum;
+    std::vector<erasor_refine_plane_row> rows(std::max<size_t>(n_frames, 1));  // (--refine fills the fields the two rows share)
+    erasor_refine_plane_summary sum;
+    memset(&sum, 0, sizeof(sum));
+    const erasor_refine_plane_params pprm = {prm.max_dist, prm.eps_t, prm.eps_r, prm.max_iters, prm.min_pairs, (uint32_t)(argc > 7 ? atoi(argv[7]) : 16), 1.0, 1e-9};
     std::vector<float> Tr(Tb.size());
     int rc = erasor_hip_align_frames_clouds(h, map.data(), map.size() / 4, 0, scans.data(), scans.size() / 4, offsets.data(), n_frames, 0, Tl, Tb.data(),
                                             voxelsize, before.data(), nullptr);
-    if (!rc)
+    if (!rc && plane)
+        rc = erasor_hip_refine_poses_plane_clouds(h, map.data(), map.size() / 4, 0, scans.data(), scans.size() / 4, offsets.data(), n_frames, 0, Tl,
+                                                  Tb.data(), &pprm, rows.data(), &sum);
+    if (!rc && !plane) {
+        std::vector<erasor_refine_row> r0(rows.size());
+        erasor_refine_summary s0;
         rc = erasor_hip_refine_poses_clouds(h, map.data(), map.size() / 4, 0, scans.data(), scans.size() / 4, offsets.data(), n_frames, 0, Tl, Tb.data(),
-                                            &prm, rows.data(), &sum);
+                                            &prm, r0.data(), &s0);
+        for (size_t f = 0; f < n_frames && !rc; ++f) {
+            erasor_refine_plane_row &r = rows[f];
+            memcpy(r.T, r0[f].T, sizeof(r.T));
+            r.status = r0[f].status, r.iters = r0[f].iters, r.n_points = r0[f].n_points, r.n_non_finite = r0[f].n_non_finite;
+            r.n_pairs_first = r0[f].n_pairs_first, r.n_pairs_last = r0[f].n_pairs_last, r.rms_first = r0[f].rms_first, r.rms_last = r0[f].rms_last;
+            r.moved_t = r0[f].moved_t, r.moved_r = r0[f].moved_r;
+        }
+        for (int k = 0; k < 4; ++k) sum.n_status[k] = s0.n_status[k];
+        sum.n_pairs_first = s0.n_pairs_first, sum.n_pairs_last = s0.n_pairs_last, sum.sum_d2_first = s0.sum_d2_first, sum.sum_d2_last = s0.sum_d2_last;
+    }
     if (!rc) {
         for (size_t f = 0; f < n_frames; ++f)
             for (int k = 0; k < 16; ++k) Tr[16 * f + k] = (float)rows[f].T[k];
@@ -1225,28 +1246,37 @@ static int refine_mode(int argc, char **argv) {
                                             voxelsize, after.data(), nullptr);
     }
     if (rc) {
-        fprintf(stderr, "refine: %s (rc %d)\n", erasor_hip_last_error(h), rc);
+        fprintf(stderr, "%s: %s (rc %d)\n", plane ? "refine-plane" : "refine", erasor_hip_last_error(h), rc);
         erasor_hip_destroy(h);
         return 1;
     }
     erasor_hip_destroy(h);
-    static const char *const STATUS[4] = {"converged", "iteration limit", "too few pairs", "no finite points"};
-    printf("%zu frames against %s (%zu points), max_dist %.3f m, at most %u iterations:\n", n_frames, cfg.initial_map_path.c_str(), map.size() / 4,
+    static const char *const STATUS[5] = {"converged", "iteration limit", "too few pairs", "no finite points", "degenerate"};
+    printf("%zu frames against %s (%zu points), max_dist %.3f m, at most %u iterations", n_frames, cfg.initial_map_path.c_str(), map.size() / 4,
            prm.max_dist, prm.max_iters);
+    if (plane) printf(", point-to-plane with normals from %u neighbours (%llu map points without one)", pprm.normals_k, (unsigned long long)sum.n_map_no_normal);
+    printf(":\n");
     for (size_t f = 0; f < n_frames; ++f) {
-        const erasor_refine_row &r = rows[f];
+        const erasor_refine_plane_row &r = rows[f];
         const bool flag = r.status != ERASOR_REFINE_CONVERGED || r.moved_t > prm.max_dist;
-        printf("%6d  n=%llu  <0.5*v %.2f%% -> %.2f%%  %s after %u  pairs %llu -> %llu  rms %.4fm -> %.4fm  moved %.4fm %.5frad%s\n",
-               drv.init_idx + (int)f, (unsigned long long)r.n_points, before[f].r.frac_half, after[f].r.frac_half, STATUS[r.status & 3u], r.iters,
-               (unsigned long long)r.n_pairs_first, (unsigned long long)r.n_pairs_last, r.rms_first, r.rms_last, r.moved_t, r.moved_r,
-               flag ? (r.status != ERASOR_REFINE_CONVERGED ? "  <- not converged: check this pose" : "  <- moved more than max_dist: check this pose") : "");
+        printf("%6d  n=%llu  <0.5*v %.2f%% -> %.2f%%  %s after %u  pairs %llu -> %llu  rms %.4fm -> %.4fm  moved %.4fm %.5frad",
+               drv.init_idx + (int)f, (unsigned long long)r.n_points, before[f].r.frac_half, after[f].r.frac_half, STATUS[r.status < 5 ? r.status : 4],
+               r.iters, (unsigned long long)r.n_pairs_first, (unsigned long long)r.n_pairs_last, r.rms_first, r.rms_last, r.moved_t, r.moved_r);
+        if (plane) printf("  rank %u  lambda_ratio %.3g  plane rms %.4fm -> %.4fm", r.rank, r.lambda_ratio, r.rms_plane_first, r.rms_plane_last);
+        printf("%s", flag ? (r.status != ERASOR_REFINE_CONVERGED ? "  <- not converged: check this pose" : "  <- moved more than max_dist: check this pose") : "");
+        if (plane && r.status <= ERASOR_REFINE_MAX_ITERS && r.rank < 6) printf("  <- only %u of 6 directions constrained", r.rank);
+        printf("\n");
     }
-    printf("summary: %llu converged, %llu at the iteration limit, %llu with too few pairs, %llu without finite points; pairs %llu -> %llu, "
-           "rms %.4fm -> %.4fm\n",
-           (unsigned long long)sum.n_status[0], (unsigned long long)sum.n_status[1], (unsigned long long)sum.n_status[2],
-           (unsigned long long)sum.n_status[3], (unsigned long long)sum.n_pairs_first, (unsigned long long)sum.n_pairs_last,
+    printf("summary: %llu converged, %llu at the iteration limit, %llu with too few pairs, %llu without finite points", (unsigned long long)sum.n_status[0],
+           (unsigned long long)sum.n_status[1], (unsigned long long)sum.n_status[2], (unsigned long long)sum.n_status[3]);
+    if (plane) printf(", %llu degenerate", (unsigned long long)sum.n_status[4]);
+    printf("; pairs %llu -> %llu, rms %.4fm -> %.4fm", (unsigned long long)sum.n_pairs_first, (unsigned long long)sum.n_pairs_last,
            sum.n_pairs_first ? std::sqrt(sum.sum_d2_first / (double)sum.n_pairs_first) : 0.0,
            sum.n_pairs_last ? std::sqrt(sum.sum_d2_last / (double)sum.n_pairs_last) : 0.0);
+    if (plane)
+        printf(", plane rms %.4fm -> %.4fm", sum.n_pairs_first ? std::sqrt(sum.sum_r2_first / (double)sum.n_pairs_first) : 0.0,
+               sum.n_pairs_last ? std::sqrt(sum.sum_r2_last / (double)sum.n_pairs_last) : 0.0);
+    printf("\n");
     // the pose file again, line by line: the header and every pose outside the refined range as they are
     std::ifstream in(pose_path);
     std::ofstream out(out_path);
@@ -1784,9 +1814,9 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
-    if (argc >= 2 && std::string(argv[1]) == "--refine") {
+    if (argc >= 2 && (std::string(argv[1]) == "--refine" || std::string(argv[1]) == "--refine-plane")) {
         try {
-            return refine_mode(argc, argv);
+            return refine_mode(argc, argv, std::string(argv[1]) == "--refine-plane");
         } catch (const std::exception &e) {
             fprintf(stderr, "error: %s\n", e.what());
             return 1;
@@ -1866,12 +1896,14 @@ int main(int argc, char **argv) {
                 "       %s --eval-many <voxelsize> <voxel_leaf> <gt> <est1> [<est2> ...]\n"
                 "       %s --label-scans <rosparam.yaml> <static.pcd> <raw.pcd|-> <out_dir> [n_frames] [tau]\n"
                 "       %s --refine <rosparam.yaml> <poses_out> [n_frames] [max_dist] [max_iters]\n"
+                "       %s --refine-plane <rosparam.yaml> <poses_out> [n_frames] [max_dist] [max_iters] [k]\n"
                 "       %s --clusters <cloud.pcd> <tol> [min_size] [max_size] [kept_out.pcd]\n"
                 "       %s --residue <gt> <est> [tol] [voxelsize] [voxel_leaf]\n"
                 "       %s --denoise <in.pcd> <out.pcd> sor <k> <mul> | ror <radius> <min_neighbors> | kth <k> <thr>\n"
                 "       %s --density <cloud.pcd> <k>\n"
                 "       %s --normals <in.pcd> <out.pcd> <k> [vx vy vz]\n",
-                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0],
+                argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

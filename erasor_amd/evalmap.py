@@ -461,6 +461,238 @@ def refine_poses(map_xyz, scans, T_body2origin, T_lidar2body=None, max_dist=1.0,
     return T_out, rows, summary
 
 
+# ---- refine_poses_plane: every frame's pose refined point-to-plane against the map's normals (Erasor.refine_poses_plane,
+# refine_plane.hip.h).  The map's normals and curvature are normals(map, k) with no viewpoint; a scan point within the gate of a map point
+# with a finite normal and a curvature <= max_curvature is a pair with the residual r = n . (q - m) and the row J = (q' x n, n); the 29
+# sums are refine_tree_sum's; the 6x6 normal equations are solved by _jacobi6 and a pseudo-inverse over the directions above rank_tol.
+REFINE_DEGENERATE = 4  # ERASOR_REFINE_DEGENERATE: no direction of the normal equations above rank_tol (the pose is kept)
+REFINE_PLANE_NSUM = 29  # RFP_NSUM: J[a]*J[b] for a <= b row-major (0..20), J[a]*r (21..26), r*r (27), d2 (28)
+REFINE_PLANE_ROW_FIELDS = REFINE_ROW_FIELDS + ("rank", "lambda_ratio", "n_unusable_first", "n_unusable_last", "rms_plane_first", "rms_plane_last")
+REFINE_PLANE_SUMMARY_FIELDS = REFINE_SUMMARY_FIELDS + ("sum_r2_first", "sum_r2_last", "n_map_no_normal")
+
+
+def _jacobi6(A):
+    """_jacobi4 on a symmetric 6x6 (lists of Python floats, changed in place): the pivots (p, q), p < q, row-major, the same rotation, a
+    pivot that is exactly zero skipped, until every element above the diagonal is exactly zero before a sweep, or 32 sweeps.  Returns V
+    (columns: eigenvectors); the eigenvalues are A's diagonal"""
+    from math import sqrt
+    V = [[1.0 if i == j else 0.0 for j in range(6)] for i in range(6)]
+    for _ in range(32):
+        if all(A[i][j] == 0.0 for i in range(5) for j in range(i + 1, 6)):
+            break
+        for p in range(5):
+            for q in range(p + 1, 6):
+                apq = A[p][q]
+                if apq == 0.0:
+                    continue
+                theta = _ieee_div(A[q][q] - A[p][p], 2.0 * apq)
+                at = -theta if theta < 0.0 else theta
+                t = _ieee_div(1.0, at + sqrt(theta * theta + 1.0))
+                if theta < 0.0:
+                    t = -t
+                c = _ieee_div(1.0, sqrt(t * t + 1.0))
+                s = t * c
+                for k in range(6):
+                    akp, akq = A[k][p], A[k][q]
+                    A[k][p] = c * akp - s * akq
+                    A[k][q] = s * akp + c * akq
+                for k in range(6):
+                    apk, aqk = A[p][k], A[q][k]
+                    A[p][k] = c * apk - s * aqk
+                    A[q][k] = s * apk + c * aqk
+                A[p][q] = 0.0
+                for i in range(6):
+                    for j in range(i + 1, 6):
+                        A[j][i] = A[i][j]
+                for k in range(6):
+                    vkp, vkq = V[k][p], V[k][q]
+                    V[k][p] = c * vkp - s * vkq
+                    V[k][q] = s * vkp + c * vkq
+    return V
+
+
+def refine_plane_solve(S, R, t, rank_tol):
+    """one frame's update from its sums S (29 Python floats): A from S[0..20], b = -S[21..26], _jacobi6, the pseudo-inverse over the
+    directions i with lambda_i > rank_tol * lambda_max (lambda_max > 0) in index order, the rotation from the half vector without
+    trigonometry, R <- D R, t <- t + x[3..5].  rank 0: (R, t) as given and steps of 0.0.  Returns (R, t, |x[3..5]|, 2 |q_xyz|, rank,
+    lambda_ratio)"""
+    from math import sqrt
+    A = [[0.0] * 6 for _ in range(6)]
+    k = 0
+    for a in range(6):
+        for b in range(a, 6):
+            A[a][b] = A[b][a] = S[k]
+            k += 1
+    bb = [-S[21 + a] for a in range(6)]
+    V = _jacobi6(A)
+    lam = [A[i][i] for i in range(6)]
+    lmax = lmin = lam[0]
+    for i in range(1, 6):
+        if lam[i] > lmax:
+            lmax = lam[i]
+        if lam[i] < lmin:
+            lmin = lam[i]
+    ratio = lmin / lmax if lmax > 0 else float("nan")
+    x = [0.0] * 6
+    rank = 0
+    for i in range(6):
+        if not (lmax > 0 and lam[i] > rank_tol * lmax):
+            continue
+        rank += 1
+        g = (((((V[0][i] * bb[0] + V[1][i] * bb[1]) + V[2][i] * bb[2]) + V[3][i] * bb[3]) + V[4][i] * bb[4]) + V[5][i] * bb[5]) / lam[i]
+        for a in range(6):
+            x[a] = x[a] + V[a][i] * g
+    if rank == 0:
+        return list(R), list(t), 0.0, 0.0, 0, ratio
+    hx, hy, hz = 0.5 * x[0], 0.5 * x[1], 0.5 * x[2]
+    w = 1.0 / sqrt(1.0 + ((hx * hx + hy * hy) + hz * hz))
+    qx, qy, qz = hx * w, hy * w, hz * w
+    xx, yy, zz, xy, xz, yz, wx, wy, wz = qx * qx, qy * qy, qz * qz, qx * qy, qx * qz, qy * qz, w * qx, w * qy, w * qz
+    D = [[1.0 - 2.0 * (yy + zz), 2.0 * (xy - wz), 2.0 * (xz + wy)],
+         [2.0 * (xy + wz), 1.0 - 2.0 * (xx + zz), 2.0 * (yz - wx)],
+         [2.0 * (xz - wy), 2.0 * (yz + wx), 1.0 - 2.0 * (xx + yy)]]
+    Rn = [(D[a][0] * R[b] + D[a][1] * R[3 + b]) + D[a][2] * R[6 + b] for a in range(3) for b in range(3)]
+    tn = [t[a] + x[3 + a] for a in range(3)]
+    return Rn, tn, sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]), 2.0 * sqrt((xx + yy) + zz), rank, ratio
+
+
+def refine_plane_frame_sums(map64, tree, nrm32, curv, p32, R, t, gate2, max_curvature, nearest=nearest_f64):
+    """one frame's sums under the pose (R, t): p32 the body points (float32, T_lidar2body applied), nrm32 / curv the map's normals and
+    curvature.  Returns (S (29,), pairs, points without a query, unusable candidates).  A candidate: d2 <= gate2; a pair: a candidate
+    whose map point has three finite normal components and a curvature <= max_curvature"""
+    n = len(p32)
+    p = p32.astype(np.float64)
+    tt = np.asarray(t, np.float64)[None, :]
+    with np.errstate(over="ignore", invalid="ignore"):
+        qr = np.stack([(R[3 * a] * p[:, 0] + R[3 * a + 1] * p[:, 1]) + R[3 * a + 2] * p[:, 2] for a in range(3)], 1)
+        q = qr + tt
+    ok = np.isfinite(p32).all(1) & np.isfinite(q).all(1)
+    v = np.zeros((n, REFINE_PLANE_NSUM))
+    pairs = unusable = 0
+    if ok.any():
+        d2, j = nearest(map64, tree, q[ok])
+        cand = d2 <= gate2
+        with np.errstate(invalid="ignore"):
+            use = cand & np.isfinite(nrm32[j]).all(1) & (curv[j] <= max_curvature)
+        rows = np.flatnonzero(ok)[use]
+        ju = j[use]
+        nn = nrm32[ju].astype(np.float64)
+        e = q[rows] - map64[ju]
+        qq = qr[rows]
+        r = (e[:, 0] * nn[:, 0] + e[:, 1] * nn[:, 1]) + e[:, 2] * nn[:, 2]
+        J = [qq[:, 1] * nn[:, 2] - qq[:, 2] * nn[:, 1], qq[:, 2] * nn[:, 0] - qq[:, 0] * nn[:, 2], qq[:, 0] * nn[:, 1] - qq[:, 1] * nn[:, 0],
+             nn[:, 0], nn[:, 1], nn[:, 2]]
+        k = 0
+        for a in range(6):
+            for b in range(a, 6):
+                v[rows, k] = J[a] * J[b]
+                k += 1
+        for a in range(6):
+            v[rows, 21 + a] = J[a] * r
+        v[rows, 27] = r * r
+        v[rows, 28] = d2[use]
+        pairs = int(use.sum())
+        unusable = int(cand.sum()) - pairs
+    return refine_tree_sum(v), pairs, int((~ok).sum()), unusable
+
+
+def refine_poses_plane(map_xyz, scans, T_body2origin, T_lidar2body=None, k=16, max_dist=1.0, max_curvature=1.0, rank_tol=1e-9, eps_t=1e-4,
+                       eps_r=1e-5, max_iters=20, min_pairs=100, nearest=nearest_f64, normals_hook=None):
+    """Every frame's T_body2origin refined point-to-plane against the map's normals: the host restatement of Erasor.refine_poses_plane
+    (include/erasor_hip.h, erasor_refine_plane_row), operation for operation.  The map's normals and curvature: normals(map, k), "up";
+    normals_hook(nrm32, curv) -> nrm32, if given, replaces the normals (the orientation test's way in).  Per frame as refine_poses, with
+    refine_plane_frame_sums and refine_plane_solve; min_pairs applies to the pairs; a solve of rank 0 keeps the pose and ends the frame
+    with status 4.  Returns (T float64 [n, 4, 4], rows, summary): REFINE_PLANE_ROW_FIELDS per frame, REFINE_PLANE_SUMMARY_FIELDS."""
+    import math
+    who = "refine_poses_plane"
+    if not (1 <= int(max_iters) <= 64):
+        raise ValueError(who + ": max_iters must be 1 .. 64")
+    for name, val in (("max_dist", max_dist), ("eps_t", eps_t), ("eps_r", eps_r), ("max_curvature", max_curvature)):
+        if not (np.isfinite(val) and val > 0):
+            raise ValueError(who + ": %s must be a finite number > 0" % name)
+    if not (np.isfinite(rank_tol) and 0 <= rank_tol < 1):
+        raise ValueError(who + ": rank_tol must be within [0, 1)")
+    if not (isinstance(k, (int, np.integer)) and NORMALS_MIN_K <= k <= KNN_MAX_K):
+        raise ValueError(who + ": normals_k must be within 2 .. 32")
+    map32 = np.asarray(map_xyz, np.float32).reshape(-1, 3)
+    map64 = map32.astype(np.float64)
+    tree = cKDTree(map64) if len(map64) else None
+    if tree is None and any(len(s) for s in scans):
+        raise ValueError(who + ": empty map with a non-empty frame (no nearest point to match)")
+    if len(map32):
+        nrm32, curv, _, _ = normals(np.concatenate([map32, np.zeros((len(map32), 1), np.float32)], 1), int(k))
+    else:
+        nrm32, curv = np.zeros((0, 3), np.float32), np.zeros(0)
+    if normals_hook is not None:
+        nrm32 = np.asarray(normals_hook(nrm32, curv), np.float32).reshape(len(map32), 3)
+    Tl = np.eye(4, dtype=np.float32) if T_lidar2body is None else T_lidar2body
+    gate2 = float(max_dist) * float(max_dist)
+    need = max(int(min_pairs), 1)
+    max_curvature, rank_tol = float(max_curvature), float(rank_tol)
+    nan = float("nan")
+    n_f = len(scans)
+    T_out = np.zeros((n_f, 4, 4))
+    rows = []
+    summary = {"n_frames": n_f, "n_status": [0, 0, 0, 0, 0], "n_pairs_first": 0, "n_pairs_last": 0, "sum_d2_first": 0.0, "sum_d2_last": 0.0,
+               "sum_r2_first": 0.0, "sum_r2_last": 0.0, "n_map_no_normal": int(np.isnan(nrm32).any(1).sum())}
+    for f, scan in enumerate(scans):
+        xyz = np.asarray(scan, np.float32).reshape(len(scan), 4)[:, :3]
+        with np.errstate(over="ignore", invalid="ignore"):
+            p32 = _xform(Tl, xyz)
+        T0 = np.asarray(T_body2origin[f], np.float32).reshape(4, 4)
+        R0 = [float(T0[a, b]) for a in range(3) for b in range(3)]
+        t0 = [float(T0[a, 3]) for a in range(3)]
+        R, t = list(R0), list(t0)
+        status, iters, rank, ratio = REFINE_MAX_ITERS, 0, 0, nan
+        first = None
+        for it in range(1, int(max_iters) + 1):
+            S, pairs, bad, unusable = refine_plane_frame_sums(map64, tree, nrm32, curv, p32, R, t, gate2, max_curvature, nearest)
+            if it == 1:
+                first = (pairs, float(S[28]), float(S[27]), bad, unusable)
+            if pairs < need:
+                status = REFINE_NO_POINTS if first[3] == len(xyz) else REFINE_FEW_PAIRS
+                break
+            R, t, st, sr, rank, ratio = refine_plane_solve([float(s) for s in S], R, t, rank_tol)
+            if rank == 0:
+                status = REFINE_DEGENERATE
+                break
+            iters = it
+            if st <= eps_t and sr <= eps_r:
+                status = REFINE_CONVERGED
+                break
+        pairs_first, d2_first, r2_first, bad_first, unusable_first = first
+        S, pairs_last, _, unusable_last = refine_plane_frame_sums(map64, tree, nrm32, curv, p32, R, t, gate2, max_curvature, nearest)
+        d2_last, r2_last = float(S[28]), float(S[27])
+        for a in range(3):
+            T_out[f, a, :3] = R[3 * a:3 * a + 3]
+            T_out[f, a, 3] = t[a]
+        T_out[f, 3, 3] = 1.0
+        dx, dy, dz = t[0] - t0[0], t[1] - t0[1], t[2] - t0[2]
+        tr = 0.0
+        for a in range(3):
+            tr = tr + ((R[3 * a] * R0[3 * a] + R[3 * a + 1] * R0[3 * a + 1]) + R[3 * a + 2] * R0[3 * a + 2])
+        cs = (tr - 1.0) / 2.0
+        if cs > 1.0:
+            cs = 1.0
+        if cs < -1.0:
+            cs = -1.0
+        rows.append({"status": status, "iters": iters, "n_points": int(len(xyz)), "n_non_finite": bad_first, "n_pairs_first": pairs_first,
+                     "n_pairs_last": pairs_last, "rms_first": math.sqrt(d2_first / float(pairs_first)) if pairs_first else nan,
+                     "rms_last": math.sqrt(d2_last / float(pairs_last)) if pairs_last else nan,
+                     "moved_t": math.sqrt((dx * dx + dy * dy) + dz * dz), "moved_r": math.acos(cs), "rank": rank, "lambda_ratio": ratio,
+                     "n_unusable_first": unusable_first, "n_unusable_last": unusable_last,
+                     "rms_plane_first": math.sqrt(r2_first / float(pairs_first)) if pairs_first else nan,
+                     "rms_plane_last": math.sqrt(r2_last / float(pairs_last)) if pairs_last else nan})
+        summary["n_status"][status] += 1
+        summary["n_pairs_first"] += pairs_first
+        summary["n_pairs_last"] += pairs_last
+        summary["sum_d2_first"] = summary["sum_d2_first"] + d2_first
+        summary["sum_d2_last"] = summary["sum_d2_last"] + d2_last
+        summary["sum_r2_first"] = summary["sum_r2_first"] + r2_first
+        summary["sum_r2_last"] = summary["sum_r2_last"] + r2_last
+    return T_out, rows, summary
+
+
 def _l2_simple(q, p):
     """FLANN's L2_Simple in float32, operation by operation: r = 0; r += dx*dx; r += dy*dy; r += dz*dz with dx = q.x - p.x"""
     r = np.zeros(len(q), np.float32)

@@ -554,6 +554,82 @@ int erasor_hip_refine_poses_map(erasor_hip_handle *h, const void *scans_xyzi, si
                                 int scans_are_device, const float T_lidar2body[16], const float *T_body2origin,
                                 const erasor_refine_params *params, erasor_refine_row *rows, erasor_refine_summary *summary);
 
+/* ---- every frame's pose refined point-to-plane against the map's own normals, all frames side by side --------------------------
+ * erasor_hip_refine_poses_* with the residual taken along the map's surface normal: a scan never samples the map's own points, so
+ * point-to-point stops a fraction of the sampling step off and creeps along surfaces; point-to-plane lets a frame slide along a
+ * surface and converges in a few iterations.  Once per call the map's normals and curvature are computed on the device as
+ * erasor_hip_normals_* computes them (k = normals_k, no viewpoint; the orientation cannot matter, every summed product holds two
+ * factors of the normal) and stay there.  Per iteration, frames and points as for erasor_hip_refine_poses_*: q' = R·p, q = q' + t,
+ * q's exact nearest map point j (ties to the lowest index); a CANDIDATE has d^2 <= max_dist * max_dist; a PAIR is a candidate whose
+ * normal n_j is finite and whose curvature is <= max_curvature; any other candidate is counted as unusable.  A pair's residual is
+ * r = n·(q - m_j) and its row J = (q' x n, n); the frame's 29 sums (J[a]J[b] for a <= b, J[a]r, r^2, d^2) are taken in the defined
+ * order of erasor_hip_refine_poses_*.  The host then solves the 6x6 normal equations (A = sum J^T J, b = -sum J^T r) by cyclic Jacobi
+ * (the rotation of the 4x4 solve, pivots row-major, 32 sweeps at most) and applies the pseudo-inverse over the eigen-directions with
+ * lambda_i > rank_tol * lambda_max: x = sum over the kept i of v_i (v_i·b) / lambda_i; the rotation is the unit quaternion of the half
+ * vector h = x[0..2] / 2, w = 1 / sqrt(1 + |h|^2), (x, y, z) = h w; R <- D·R, t <- t + x[3..5].  rank is the number of kept
+ * directions: a frame that sees one plane has rank 3, two perpendicular planes 5, and only a rank of 6 constrains the whole pose --
+ * the directions left out are not moved.  The eigenvalues mix radians and metres, so rank_tol is a parameter and lambda_ratio
+ * (lambda_min / lambda_max) is reported; a null direction held only by noise in the normals passes rank_tol and shows in
+ * lambda_ratio alone.  Stopping, min_pairs (applied to the pairs), frozen frames and the final evaluation are
+ * erasor_hip_refine_poses_*'s.  The result is the host restatement's (evalmap.refine_poses_plane) bit for bit. */
+typedef struct erasor_refine_plane_params {
+    double max_dist;       /* the correspondence gate, > 0 */
+    double eps_t;          /* stop: |translation update| <= eps_t ... */
+    double eps_r;          /* ... and rotation update <= eps_r (radians) */
+    uint32_t max_iters;    /* 1 .. 64 */
+    uint32_t min_pairs;    /* a frame with fewer pairs keeps the pose it has and ends (0 counts as 1) */
+    uint32_t normals_k;    /* the neighbourhood of the map's normals, 2 .. 32 */
+    double max_curvature;  /* a map point with a larger curvature gives no pair; finite, > 0 (curvature is <= 1/3: 1.0 gates nothing) */
+    double rank_tol;       /* a direction counts when lambda_i > rank_tol * lambda_max; finite, within [0, 1) */
+} erasor_refine_plane_params;
+
+#define ERASOR_REFINE_DEGENERATE 4  /* a solve with no direction above rank_tol (lambda_max is not > 0): the pose is kept */
+
+typedef struct erasor_refine_plane_row {
+    double T[16];            /* as erasor_refine_row, field for field, down to moved_r */
+    uint32_t status;         /* ERASOR_REFINE_*, ERASOR_REFINE_DEGENERATE included */
+    uint32_t iters;
+    uint64_t n_points;
+    uint64_t n_non_finite;
+    uint64_t n_pairs_first;
+    uint64_t n_pairs_last;
+    double rms_first;        /* the pairs' point distances, as in erasor_refine_row */
+    double rms_last;
+    double moved_t;
+    double moved_r;
+    uint32_t rank;             /* directions kept by the last solve made; 0 when none was made */
+    double lambda_ratio;       /* lambda_min / lambda_max of that solve; NaN when lambda_max is not > 0 or no solve was made */
+    uint64_t n_unusable_first; /* candidates without a usable normal under the input pose ... */
+    uint64_t n_unusable_last;  /* ... and under T */
+    double rms_plane_first;    /* sqrt(sum of the pairs' r^2 / pairs) under the input pose; NaN without a pair ... */
+    double rms_plane_last;     /* ... and under T */
+} erasor_refine_plane_row;
+
+typedef struct erasor_refine_plane_summary {
+    uint64_t n_frames;
+    uint64_t n_status[5];    /* frames by ERASOR_REFINE_* */
+    uint64_t n_pairs_first;  /* the rows' totals, added in frame order */
+    uint64_t n_pairs_last;
+    double sum_d2_first;
+    double sum_d2_last;
+    double sum_r2_first;
+    double sum_r2_last;
+    uint64_t n_map_no_normal;  /* map points whose normal is NaN: fewer than normals_k other points, or a neighbourhood of identical points */
+} erasor_refine_plane_summary;
+
+/* Arguments and errors as erasor_hip_refine_poses_clouds.  ERASOR_E_INVALID also: normals_k outside 2 .. 32, max_curvature not a
+ * finite number > 0, rank_tol not a finite number within [0, 1); each message names the parameter. */
+int erasor_hip_refine_poses_plane_clouds(erasor_hip_handle *h, const void *map_xyzi, size_t n_map, int map_is_device,
+                                         const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                                         int scans_are_device, const float T_lidar2body[16], const float *T_body2origin,
+                                         const erasor_refine_plane_params *params, erasor_refine_plane_row *rows,
+                                         erasor_refine_plane_summary *summary);
+/* the same against the handle's current map, as erasor_hip_refine_poses_map */
+int erasor_hip_refine_poses_plane_map(erasor_hip_handle *h, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets,
+                                      size_t n_frames, int scans_are_device, const float T_lidar2body[16], const float *T_body2origin,
+                                      const erasor_refine_plane_params *params, erasor_refine_plane_row *rows,
+                                      erasor_refine_plane_summary *summary);
+
 /* ---- every scan's points labelled static or moving from a cleaned map ---------------------------------------------------------
  * replaces: what users of a cleaned map do on the host afterwards -- a KD-tree over the cleaned map, a radius test per scan point, the
  * scan's moving points dropped (automatic moving-object-segmentation labels, cleaned scans for re-mapping); the reference itself stops

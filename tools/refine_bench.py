@@ -3,7 +3,7 @@
 put wrong by a known amount, refined against the sampled map.
 
   python tools/refine_bench.py [--spacing 0.2] [--length 400] [--frames 12] [--az 2000] [--iters 8] [--runs 3] [--host-frames 2] [--no-host]
-                               [--out FILE.json]
+                               [--plane] [--out FILE.json]
 
 On the one input:
   (a) Erasor.refine_poses with its defaults: median wall time of --runs calls after a warm-up call (scans and map on the host: the copies
@@ -15,7 +15,11 @@ On the one input:
       what one align_frames searches);
   (c) evalmap.refine_poses, the host restatement, on the first --host-frames frames: wall time, and the device result on those frames
       compared with it byte for byte.
---no-host skips (c) (for a run under a profiler)."""
+--no-host skips (c) (for a run under a profiler).
+  (d) with --plane, Erasor.refine_poses_plane on the same input in the same run, beside the rows above: the wall time at its defaults, the
+      iterations, ranks and statuses, the translation errors and frac_half after it; the call held to exactly --iters and to 1 iteration
+      and the cost of one iteration from their difference; rfp_query per launch, rfp_partials and the one-off normals pass (nm_query) from
+      the event brackets.  Its host restatement is not run here: evalmap.normals over the whole map is minutes of numpy."""
 import argparse
 import json
 import os
@@ -71,6 +75,7 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--host-frames", type=int, default=2)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--plane", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     erasor_amd.build()
@@ -143,6 +148,37 @@ def main():
         row["c_host_wall_ms"] = (time.perf_counter() - t0) * 1e3
         row["c_device_wall_ms_same_frames"] = median_ms(lambda: g.refine_poses([scans[f] for f in sub], [T_given[f] for f in sub], Tl), a.runs)
         row["c_equal_to_host"] = same(dev[0], ref[0]) and str(dev[1]) == str(ref[1]) and str(dev[2]) == str(ref[2])
+    # (d) point-to-plane on the same input
+    if a.plane:
+        row["d_plane_wall_ms"] = median_ms(lambda: out.__setitem__("p", g.refine_poses_plane(scans, T_given, Tl)), a.runs)
+        Tp, prows, psumm = out["p"]
+        row["d_summary"] = psumm
+        row["d_iters"] = [r["iters"] for r in prows]
+        row["d_rank"] = [r["rank"] for r in prows]
+        row["d_lambda_ratio_min"] = float(np.min([r["lambda_ratio"] for r in prows]))
+        row["d_rms_plane_last_median"] = float(np.median([r["rms_plane_last"] for r in prows]))
+        err2 = [float(np.linalg.norm(Tp[f][:3, 3] - np.asarray(T_true[f], np.float64).reshape(4, 4)[:3, 3])) for f in range(a.frames)]
+        row["d_translation_error_m_refined_median_max"] = [float(np.median(err2)), float(np.max(err2))]
+        after_p, _ = g.align_frames(scans, Tp.astype(np.float32), Tl)
+        row["d_frac_half_after_min_median"] = [float(np.min([r["frac_half"] for r in after_p])), float(np.median([r["frac_half"] for r in after_p]))]
+        p_n = median_ms(lambda: out.__setitem__("pn", g.refine_poses_plane(scans, T_given, Tl, max_iters=a.iters, **tiny)), a.runs)
+        p_1 = median_ms(lambda: g.refine_poses_plane(scans, T_given, Tl, max_iters=1, **tiny), a.runs)
+        assert all(r["iters"] == a.iters for r in out["pn"][1] if r["status"] == 1)
+        row["d_plane_%d_iters_wall_ms" % a.iters] = p_n
+        row["d_plane_1_iter_wall_ms"] = p_1
+        row["d_ms_per_iteration"] = (p_n[0] - p_1[0]) / max(a.iters - 1, 1)
+        row["d_iteration_over_point_to_point"] = row["d_ms_per_iteration"] / row["b_ms_per_iteration"]
+        row["d_wall_over_point_to_point"] = row["d_plane_wall_ms"][0] / row["a_refine_wall_ms"][0]
+        g.profiling(1)
+        g.profile_reset()
+        g.refine_poses_plane(scans, T_given, Tl, max_iters=a.iters, **tiny)
+        prof_p = {k: v[0] for k, v in g.profile_get().items()}
+        g.profiling(0)
+        row["d_rfp_query_device_ms_per_launch"] = prof_p.get("rfp_query", 0.0) / (a.iters + 1)
+        row["d_rfp_partials_device_ms_per_launch"] = prof_p.get("rfp_partials", 0.0) / (a.iters + 1)
+        row["d_nm_query_device_ms"] = prof_p.get("nm_query", 0.0)
+        row["d_rfp_query_over_rf_query"] = row["d_rfp_query_device_ms_per_launch"] / max(row["b_rf_query_device_ms_per_launch"], 1e-9)
+        row["d_plane_device_ms_per_kernel"] = prof_p
     print(json.dumps(row), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
