@@ -205,6 +205,40 @@ class NormalsResult(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_short", "n_degenerate", "n_ambiguous", "n_flipped")] + [("curvature", ScoreStats)]
 
 
+class Visibility(C.Structure):
+    """erasor_visibility"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("col_tan", C.POINTER(C.c_double)), ("row_tan", C.POINTER(C.c_double)),
+                ("min_range", C.c_double), ("max_range", C.c_double), ("margin_abs", C.c_double), ("margin_rel", C.c_double),
+                ("window", C.c_uint32), ("k", C.c_uint32), ("min_cos", C.c_double), ("min_through", C.c_uint32), ("reserved", C.c_uint32),
+                ("hit_weight", C.c_double), ("image_budget_bytes", C.c_uint64)]
+
+
+class VisibilityRow(C.Structure):
+    """erasor_visibility_row"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_non_finite", "n_on_axis", "n_out_of_range", "n_out_of_view", "n_pixels", "n_map_in_view",
+                                          "n_hit", "n_occluded", "n_no_return", "n_through", "n_grazing")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class VisibilityResult(C.Structure):
+    """erasor_visibility_result"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_never_in_view", "n_kept", "n_removed", "n_removed_dynamic", "n_removed_static",
+                                          "n_map_no_normal", "n_in_view", "n_hit", "n_occluded", "n_no_return", "n_through", "n_grazing")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+VISIBILITY_IMAGE_BUDGET = 256 << 20  # ERASOR_VISIBILITY_IMAGE_BUDGET
+
+
+def visibility_grid(width, height, el_bottom_deg, el_top_deg):
+    """evalmap.visibility_grid, re-exported: the edge tables of a uniform width x height grid between two elevations, for Erasor.visibility"""
+    from . import evalmap
+    return evalmap.visibility_grid(width, height, el_bottom_deg, el_top_deg)
+
 DENSITY_SCORES = {"kth": 0, "mean": 1, "count": 2}  # ERASOR_DENSITY_KTH / _MEAN / _COUNT
 DENSITY_RULES = {"abs": 0, "mad": 1}                # ERASOR_DENSITY_ABS / _MAD
 KNN_NONE = 0xFFFFFFFF  # the padding of a neighbour list
@@ -389,7 +423,7 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "normals.hip.h", "refine_plane.hip.h", "render.hip.h", "revert_bins.hip.h",
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "normals.hip.h", "refine_plane.hip.h", "visibility.hip.h", "render.hip.h", "revert_bins.hip.h",
                                                  "exact_sort.hip.h", "exact_sort_core.h", "overlap_auto.h", "stream_place.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
@@ -1016,6 +1050,63 @@ class Erasor:
             self._check(lib().erasor_hip_refine_poses_plane_clouds(self._h, *m, *tail))
         T = np.array([list(rows[f].T) for f in range(n_f)], np.float64).reshape(n_f, 4, 4)
         return T, [rows[f].as_dict() for f in range(n_f)], summ.as_dict()
+
+    # -- the see-through check: every scan's range image votes on every map point (on the host: evalmap.visibility) --
+    def visibility(self, scans, T_body2origin, T_lidar2body=None, map=None, grid=None, min_range=0.5, max_range=80.0, margin_abs=0.2, margin_rel=0.01,
+                   window=1, k=0, min_cos=0.25, min_through=2, hit_weight=1.0, keep=True, image_budget_bytes=0):
+        """Every map point voted on by every scan's range image (erasor_hip_visibility_clouds / _map): a point that scans look straight
+        through was not static.  scans, poses and T_lidar2body as for align_frames; `map` a cloud as for evaluate, or None for the
+        handle's current map (which stays as it is); `grid` from visibility_grid(), or a dict with a sensor's own width, height, col_tan
+        and row_tan.  A map point in view of a frame is a hit, occluded, without return or seen through within margin_abs + margin_rel *
+        range over a (2 window + 1)^2 pixel window; with k > 0 a see-through at an incidence below min_cos against the point's normal
+        (k neighbours) is not counted.  A point is removed iff through >= min_through and through > hit_weight * hit.  The frames are
+        handled in batches whose images fit image_budget_bytes (0: VISIBILITY_IMAGE_BUDGET).  Returns (votes (n, 4) uint16: in_view,
+        hit, through, occluded; mask uint8, 1 = kept; the kept rows in the order given, or None unless keep; a row per frame; the
+        result) as evalmap.visibility does, byte for byte.  A min_through outside 0 .. 2^32 - 1 is a ValueError, as it is there."""
+        kept = []
+        if isinstance(scans, tuple):
+            ptr, offsets = scans
+            offs = np.ascontiguousarray(offsets, np.uint64)
+            q = (C.c_void_p(ptr), C.c_size_t(int(offs[-1]) if len(offs) else 0), 1)
+        else:
+            a = [_f32(s).reshape(-1, 4) for s in scans]
+            offs = np.zeros(len(a) + 1, np.uint64)
+            offs[1:] = np.cumsum([len(s) for s in a], dtype=np.uint64)
+            cat = _f32(np.concatenate(a) if a else np.zeros((0, 4), np.float32))
+            kept.append(cat)
+            q = (_p(cat), C.c_size_t(len(cat)), 0)
+        n_f = len(offs) - 1
+        Tb = _f32(np.asarray(T_body2origin, np.float32).reshape(n_f, 16) if n_f else np.zeros((1, 16), np.float32))
+        if T_lidar2body is not None:
+            kept.append(_f32(T_lidar2body).reshape(16))
+        Tl = None if T_lidar2body is None else _p(kept[-1])
+        if grid is None:
+            raise ValueError("visibility: a grid is needed (visibility_grid)")
+        if not 0 <= int(min_through) <= 0xFFFFFFFF:
+            raise ValueError("visibility: min_through must fit 32 bits")
+        col = np.ascontiguousarray(grid["col_tan"], np.float64).reshape(-1)
+        row = np.ascontiguousarray(grid["row_tan"], np.float64).reshape(-1)
+        W, H = int(grid["width"]), int(grid["height"])
+        if 8 <= W <= 4096 and 1 <= H <= 256 and (len(col) != W // 8 - 1 or len(row) != H + 1):
+            raise ValueError("visibility: col_tan has width / 8 - 1 entries and row_tan height + 1")
+        prm = Visibility(W & 0xFFFFFFFF, H & 0xFFFFFFFF, col.ctypes.data_as(C.POINTER(C.c_double)), row.ctypes.data_as(C.POINTER(C.c_double)),
+                         float(min_range), float(max_range), float(margin_abs), float(margin_rel), int(window) & 0xFFFFFFFF, int(k) & 0xFFFFFFFF,
+                         float(min_cos), int(min_through), 0, float(hit_weight), int(image_budget_bytes))
+        if map is None:
+            head, n = (), self._map_n()
+            fn = lib().erasor_hip_visibility_map
+        else:
+            head = self._eval_cloud(map, kept)
+            n = head[1].value
+            fn = lib().erasor_hip_visibility_clouds
+        votes = np.empty((max(n, 1), 4), np.uint16)
+        mask = np.empty(max(n, 1), np.uint8)
+        out = np.empty((max(n, 1), 4), np.float32) if keep else None
+        rows = (VisibilityRow * max(n_f, 1))()
+        r = VisibilityResult()
+        self._check(fn(self._h, *head, q[0], q[1], _p(offs), C.c_size_t(n_f), C.c_int(q[2]), Tl, _p(Tb), C.byref(prm),
+                       _p(votes), _p(mask), _p(out) if keep else None, C.c_size_t(n if keep else 0), rows, C.byref(r)))
+        return votes[:n], mask[:n], (out[: r.n_kept] if keep else None), [rows[f].as_dict() for f in range(n_f)], r.as_dict()
 
     # -- every scan's points labelled static or moving from a cleaned map (on the host: evalmap.label_scans) --
     def label_scans(self, scans, T_body2origin, T_lidar2body=None, static_map=None, raw_map=None, tau=None, voxelsize=0.2, split=None):

@@ -1,8 +1,8 @@
 // The offline analyses' host code: PR / RR evaluation (one estimate, many, by class), the overlap report, the frame check, the scans'
-// labels, the clustering, the k nearest neighbours and density filters, the normals, the point-to-plane refinement, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
+// labels, the clustering, the k nearest neighbours and density filters, the normals, the point-to-plane refinement, the see-through check, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
 // at its end -- one translation unit, like the kernel headers -- so it sees the handle, ensure / LAUNCH / HIPC, scan_u32, radix_sort,
 // map_to_device and voxelize_device from there; nothing of the step path depends on this file.  Kernels: evaluate.hip.h, nearest.hip.h,
-// align.hip.h, label_scans.hip.h, cluster.hip.h, knn.hip.h, normals.hip.h, refine_plane.hip.h, render.hip.h.
+// align.hip.h, label_scans.hip.h, cluster.hip.h, knn.hip.h, normals.hip.h, refine_plane.hip.h, visibility.hip.h, render.hip.h.
 #pragma once
 
 extern "C" {
@@ -1973,6 +1973,212 @@ int erasor_hip_refine_poses_plane_map(erasor_hip_handle *h, const void *scans_xy
     uint32_t n_map = 0;
     if ((rc = map_on_device(h, who, h->ev.map, &m, &n_map)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q))) return rc;
     return rfp_run(h, who, m, n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, *params, rows, summary);
+}
+
+// ---- the see-through check: every scan's range image votes on every map point (kernels: visibility.hip.h) ----
+// Like al_run: the main stream, the evaluator's scratch; with k > 0 the map's tree (bank 2) and normals as rfp_run takes them, once a
+// call.  The frames are cut into batches whose images fit the budget; per batch one memset, one k_vis_image over the batch's scan points
+// and one k_vis_vote over the map.  Round trips: the normals' counters (k > 0), and at the end the per-frame counters, the decision's
+// counters and the outputs asked for.
+
+static int vs_check_args(erasor_hip_handle *h, const char *who, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets,
+                         size_t n_frames, const float *T_lidar2body, const float *T_body2origin, const erasor_visibility *p) {
+    if (!p) return invalid(h, who, "params is NULL");
+    if (p->width % 8 || p->width < 8 || p->width > VIS_MAX_W) return invalid(h, who, "width must be a multiple of 8 within 8 .. 4096");
+    if (p->height < 1 || p->height > VIS_MAX_H) return invalid(h, who, "height must be within 1 .. 256");
+    const uint32_t nc = p->width / 8 - 1, nr = p->height + 1;
+    if ((nc && !p->col_tan) || !p->row_tan) return invalid(h, who, "col_tan or row_tan is NULL");
+    for (uint32_t j = 0; j < nc; ++j)
+        if (!(p->col_tan[j] > 0 && p->col_tan[j] < 1) || (j && !(p->col_tan[j] > p->col_tan[j - 1])))
+            return invalid(h, who, "col_tan must be strictly increasing within (0, 1)");
+    for (uint32_t j = 0; j < nr; ++j)
+        if (!std::isfinite(p->row_tan[j]) || (j && !(p->row_tan[j] > p->row_tan[j - 1])))
+            return invalid(h, who, "row_tan must be finite and strictly increasing");
+    if (!std::isfinite(p->min_range) || !std::isfinite(p->max_range) || !(p->min_range >= 0) || !(p->min_range < p->max_range))
+        return invalid(h, who, "0 <= min_range < max_range, both finite");
+    if (!std::isfinite(p->margin_abs) || !std::isfinite(p->margin_rel) || !(p->margin_abs >= 0) || !(p->margin_rel >= 0))
+        return invalid(h, who, "the margins must be finite numbers >= 0");
+    if (p->window > 2) return invalid(h, who, "window must be 0, 1 or 2");
+    if (p->k && (p->k < NM_MIN_K || p->k > KN_MAX_K)) return invalid(h, who, "k must be 0 or within 2 .. 32");
+    if (!std::isfinite(p->min_cos) || !std::isfinite(p->hit_weight) || !(p->hit_weight >= 0))
+        return invalid(h, who, "min_cos must be finite and hit_weight a finite number >= 0");
+    if (n_frames > ERASOR_VISIBILITY_MAX_FRAMES) return invalid(h, who, "more than 65535 frames");
+    if (!offsets) return invalid(h, who, "offsets is NULL (n_frames + 1 entries)");
+    if (n_frames && !T_body2origin) return invalid(h, who, "T_body2origin is NULL");
+    const int rc = check_scan_offsets(h, who, scans_xyzi, n_scan_points, offsets, n_frames);
+    if (rc) return rc;
+    if (T_lidar2body && !all_finite(T_lidar2body, 16)) return invalid(h, who, "non-finite entry in T_lidar2body");
+    if (!all_finite(T_body2origin, n_frames * 16)) return invalid(h, who, "non-finite entry in T_body2origin");
+    return ERASOR_OK;
+}
+
+// a frame's map-to-lidar transform and origin: evalmap.visibility_transforms, the same function in the same order; false: not finite
+static bool vs_frame(const float *A, const float *B, VisFrame *F) {
+    double M[3][4];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 4; ++j) {
+            const double v = ((double)A[4 * i + 0] * (double)B[0 + j] + (double)A[4 * i + 1] * (double)B[4 + j]) + (double)A[4 * i + 2] * (double)B[8 + j];
+            M[i][j] = j == 3 ? v + (double)A[4 * i + 3] : v;
+        }
+    bool ok = true;
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) F->m[4 * i + j] = M[j][i];
+        F->m[4 * i + 3] = -((M[0][i] * M[0][3] + M[1][i] * M[1][3]) + M[2][i] * M[2][3]);
+        F->o[i] = M[i][3];
+    }
+    F->pad = 0.0;
+    for (int k = 0; k < 12; ++k) ok = ok && std::isfinite(F->m[k]);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 4; ++j) ok = ok && std::isfinite(M[i][j]);
+    return ok;
+}
+
+static int vs_run(erasor_hip_handle *h, const char *who, const float4 *map, uint32_t n_map, const float4 *scans, uint32_t n, const uint64_t *offsets,
+                  uint32_t n_frames, const float *T_lidar2body, const float *T_body2origin, const erasor_visibility &prm, uint16_t *votes,
+                  uint8_t *keep_mask, float *kept_xyzi, size_t cap_points, erasor_visibility_row *rows, erasor_visibility_result *res) {
+    auto &E = h->ev;
+    const uint32_t W = prm.width, H = prm.height, M = W / 8, nf = std::max(n_frames, 1u);
+    const VisParams P{W, H, M, prm.window, prm.min_range, prm.max_range, prm.margin_abs, prm.margin_rel, prm.min_cos};
+    // the frames: transforms (refused before anything runs), offsets, every image workgroup's first frame
+    std::vector<VisFrame> fr(nf);
+    const float *Tl = T_lidar2body ? T_lidar2body : AL_IDENTITY;
+    for (uint32_t f = 0; f < n_frames; ++f)
+        if (!vs_frame(T_body2origin + 16 * (size_t)f, Tl, &fr[f])) return invalid(h, who, "non-finite transform of frame " + std::to_string(f));
+    const uint32_t grid_all = cdiv(n, 256);
+    std::vector<uint32_t> off(n_frames + 1), wg(grid_all + 1);
+    for (uint32_t f = 0; f <= n_frames; ++f) off[f] = (uint32_t)offsets[f];
+    for (uint32_t b = 0, f = 0; b < grid_all; ++b) {  // the largest f < n_frames with off[f] <= b * 256 (as al_put_frames)
+        while (f + 1 < n_frames && off[f + 1] <= b * 256u) ++f;
+        wg[b] = f;
+    }
+    wg[grid_all] = n_frames ? n_frames - 1 : 0;
+    // the batches: as many whole images as fit the budget, at least one
+    const uint64_t image_bytes = (uint64_t)H * W * sizeof(uint32_t);
+    const uint64_t budget = prm.image_budget_bytes ? prm.image_budget_bytes : ERASOR_VISIBILITY_IMAGE_BUDGET;
+    const uint32_t batch = (uint32_t)std::min<uint64_t>(nf, std::max<uint64_t>(1, budget / image_bytes));
+    const size_t n1 = (size_t)n_map + 1, ntab = (size_t)(M - 1) + (H + 1);
+    if (ensure(h, E.al_off, (size_t)nf + 1) || ensure(h, E.al_wg, (size_t)grid_all + 1) || ensure(h, E.vs_frames, nf) || ensure(h, E.vs_tab, ntab) ||
+        ensure(h, E.vs_img, (size_t)batch * H * W) || ensure(h, E.vs_votes, n1) || ensure(h, E.vs_ctr, (size_t)nf * VIS_NCTR + VD_NCTR) ||
+        ensure(h, E.fm_flag, n1) || ensure(h, E.fm_pl, n1) || ensure(h, E.fm_tops, n_map / 1024 + 4) || ensure(h, E.kn_mask, n1))
+        return ERASOR_E_NO_DEVICE;
+    // the map's normals, once a call (rfp_run's): they stay in E.nm_nrm
+    uint64_t n_no_normal = 0;
+    int rc;
+    if (prm.k && n_map) {
+        NnTree T;
+        if ((rc = nn_build(h, map, n_map, who, "map", "map point(s)", &T)) || (rc = nm_device(h, map, n_map, T, prm.k, nullptr, true, false))) return rc;
+        unsigned long long nc[NM_NCTR];
+        if ((rc = d2h(h, nc, E.nm_ctr.p, NM_NCTR * sizeof(unsigned long long)))) return rc;
+        n_no_normal = nc[NM_C_SHORT] + nc[NM_C_DEGENERATE];
+    }
+    std::vector<double> tabs(ntab);
+    for (uint32_t j = 0; j + 1 < M; ++j) tabs[j] = prm.col_tan[j];
+    for (uint32_t j = 0; j <= H; ++j) tabs[(M - 1) + j] = prm.row_tan[j];
+    unsigned long long *const dctr = E.vs_ctr.p + (size_t)nf * VIS_NCTR;  // the decision's counters, behind the frames'
+    HIPC(h, hipMemcpyAsync(E.al_off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(E.al_wg.p, wg.data(), wg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(E.vs_frames.p, fr.data(), (size_t)nf * sizeof(VisFrame), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(E.vs_tab.p, tabs.data(), ntab * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemsetAsync(E.vs_ctr.p, 0, ((size_t)nf * VIS_NCTR + VD_NCTR) * sizeof(unsigned long long), h->stream));
+    HIPC(h, hipMemsetAsync(E.vs_votes.p, 0, n1 * sizeof(VisVote), h->stream));
+    const uint32_t gm = cdiv(n_map, 256);
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += batch) {
+        const uint32_t f1 = std::min(n_frames, f0 + batch), lo = off[f0], hi = off[f1];
+        HIPC(h, hipMemsetAsync(E.vs_img.p, 0xFF, (size_t)(f1 - f0) * image_bytes, h->stream));
+        if (hi > lo) {
+            const uint32_t b0 = lo / 256u, b1 = cdiv(hi, 256);
+            LAUNCH(h, h->stream, "vis_image", k_vis_image, b1 - b0, 256, scans, lo, hi, b0, (const uint32_t *)E.al_off.p, (const uint32_t *)E.al_wg.p, f0, f1, P,
+                   (const double *)E.vs_tab.p, E.vs_img.p, E.vs_ctr.p);
+        }
+        if (n_map)
+            LAUNCH(h, h->stream, "vis_vote", k_vis_vote, gm, 256, map, n_map, prm.k ? (const float *)E.nm_nrm.p : (const float *)nullptr,
+                   (const VisFrame *)E.vs_frames.p, f0, f1, P, (const double *)E.vs_tab.p, (const uint32_t *)E.vs_img.p, E.vs_votes.p, E.vs_ctr.p);
+    }
+    if (n_map)
+        LAUNCH(h, h->stream, "vis_decide", k_vis_decide, gm, 256, map, n_map, (const VisVote *)E.vs_votes.p, prm.min_through, prm.hit_weight, E.fm_flag.p,
+               E.kn_mask.p, dctr);
+    std::vector<unsigned long long> c((size_t)nf * VIS_NCTR + VD_NCTR);
+    if ((rc = d2h(h, c.data(), E.vs_ctr.p, c.size() * sizeof(unsigned long long)))) return rc;
+    erasor_visibility_result r;
+    memset(&r, 0, sizeof(r));
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const unsigned long long *cf = &c[(size_t)f * VIS_NCTR];
+        erasor_visibility_row row;
+        row.n_points = off[f + 1] - off[f];
+        row.n_non_finite = cf[VIS_C_NON_FINITE];
+        row.n_on_axis = cf[VIS_C_AXIS];
+        row.n_out_of_range = cf[VIS_C_RANGE];
+        row.n_out_of_view = cf[VIS_C_VIEW];
+        row.n_pixels = cf[VIS_C_PIXELS];
+        row.n_map_in_view = cf[VIS_C_IN_VIEW];
+        row.n_hit = cf[VIS_C_VERDICT + VIS_HIT];
+        row.n_occluded = cf[VIS_C_VERDICT + VIS_OCCLUDED];
+        row.n_no_return = cf[VIS_C_VERDICT + VIS_NO_RETURN];
+        row.n_through = cf[VIS_C_VERDICT + VIS_THROUGH];
+        row.n_grazing = cf[VIS_C_VERDICT + VIS_GRAZING];
+        if (rows) rows[f] = row;
+        r.n_in_view += row.n_map_in_view;
+        r.n_hit += row.n_hit;
+        r.n_occluded += row.n_occluded;
+        r.n_no_return += row.n_no_return;
+        r.n_through += row.n_through;
+        r.n_grazing += row.n_grazing;
+    }
+    const unsigned long long *cd = &c[(size_t)nf * VIS_NCTR];
+    r.n_points = n_map;
+    r.n_never_in_view = n_map - cd[VD_C_SEEN];
+    r.n_removed_dynamic = cd[VD_C_REMOVED_DYNAMIC];
+    r.n_removed_static = cd[VD_C_REMOVED_STATIC];
+    r.n_removed = r.n_removed_dynamic + r.n_removed_static;
+    r.n_kept = n_map - r.n_removed;
+    r.n_map_no_normal = n_no_normal;
+    if (res) *res = r;
+    if (votes && (rc = d2h(h, votes, E.vs_votes.p, (size_t)n_map * sizeof(VisVote)))) return rc;
+    if (keep_mask && (rc = d2h(h, keep_mask, E.kn_mask.p, n_map))) return rc;
+    if (kept_xyzi && r.n_kept > cap_points) return ERASOR_E_CAPACITY;
+    if (kept_xyzi && r.n_kept) {
+        // the kept rows, as given: the stable compaction over the keep flags (df_run's)
+        if (ensure(h, E.fm_out, n1)) return ERASOR_E_NO_DEVICE;
+        scan_u32(h, h->stream, E.fm_flag.p, E.fm_pl.p, E.fm_tops.p, n_map, n_map, nullptr, nullptr, "vis_keep");
+        LAUNCH(h, h->stream, "vis_keep", k_f_compact, gm, 256, map, n_map, (const uint32_t *)E.fm_flag.p, (const uint32_t *)E.fm_pl.p,
+               (const uint32_t *)E.fm_tops.p, E.fm_out.p);
+        return d2h(h, kept_xyzi, E.fm_out.p, (size_t)r.n_kept * sizeof(float4));
+    }
+    return ERASOR_OK;
+}
+
+int erasor_hip_visibility_clouds(erasor_hip_handle *h, const void *map_xyzi, size_t n_map, int map_is_device, const void *scans_xyzi,
+                                 size_t n_scan_points, const uint64_t *offsets, size_t n_frames, int scans_are_device, const float T_lidar2body[16],
+                                 const float *T_body2origin, const erasor_visibility *params, uint16_t *votes, uint8_t *keep_mask, float *kept_xyzi,
+                                 size_t cap_points, erasor_visibility_row *rows, erasor_visibility_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_visibility_clouds";
+    int rc = vs_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, params);
+    if (rc || (rc = check_cloud(h, who, "NULL map or more than 2^30 map points", map_xyzi, n_map))) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr, *q = nullptr;
+    if ((rc = ev_input(h, map_xyzi, n_map, map_is_device, h->ev.gt, &m)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q)))
+        return rc;
+    return vs_run(h, who, m, (uint32_t)n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, *params, votes, keep_mask,
+                  kept_xyzi, cap_points, rows, res);
+}
+
+int erasor_hip_visibility_map(erasor_hip_handle *h, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                              int scans_are_device, const float T_lidar2body[16], const float *T_body2origin, const erasor_visibility *params,
+                              uint16_t *votes, uint8_t *keep_mask, float *kept_xyzi, size_t cap_points, erasor_visibility_row *rows,
+                              erasor_visibility_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_visibility_map";
+    int rc = vs_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, params);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr, *q = nullptr;
+    uint32_t n_map = 0;
+    if ((rc = map_on_device(h, who, h->ev.map, &m, &n_map)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q))) return rc;
+    return vs_run(h, who, m, n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, *params, votes, keep_mask, kept_xyzi,
+                  cap_points, rows, res);
 }
 
 // ---- label_map (fill_removert_intensity.cpp:24-59, compare_map.cpp:77-110) and calc_complement (compare_complement.cpp:43-75): the

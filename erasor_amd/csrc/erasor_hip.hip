@@ -45,6 +45,7 @@
 #include "knn.hip.h"
 #include "normals.hip.h"
 #include "refine_plane.hip.h"
+#include "visibility.hip.h"
 #include "render.hip.h"
 
 using namespace ek;
@@ -403,6 +404,14 @@ struct erasor_hip_handle {
         DBuf<unsigned long long> nm_curv, nm_ctr;
         DBuf<float> nm_nrm;
         DBuf<double> nm_eig;
+        // the see-through check (erasor_hip_visibility_*): the frames' transforms, the two edge tables, a batch's range images, the map
+        // points' votes, the per-frame counters with the decision's behind them (offsets and workgroup frames: al_off, al_wg; the
+        // normals: nm_nrm; flags, mask and kept cloud: fm_*, kn_mask)
+        DBuf<VisFrame> vs_frames;
+        DBuf<double> vs_tab;
+        DBuf<uint32_t> vs_img;
+        DBuf<VisVote> vs_votes;
+        DBuf<unsigned long long> vs_ctr;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
 #ifdef ERASOR_HIP_TEST_HOOKS
@@ -1261,6 +1270,7 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->ev.kn_kth); release(h->ev.kn_mean); release(h->ev.kn_dev); release(h->ev.kn_ctr); release(h->ev.kn_ni); release(h->ev.kn_cnt);
     release(h->ev.kn_nd); release(h->ev.kn_mask);
     release(h->ev.nm_curv); release(h->ev.nm_ctr); release(h->ev.nm_nrm); release(h->ev.nm_eig);
+    release(h->ev.vs_frames); release(h->ev.vs_tab); release(h->ev.vs_img); release(h->ev.vs_votes); release(h->ev.vs_ctr);
     for (int k = 0; k < NSIDE; ++k) {
         if (h->q[k].ev_keys) (void)hipEventDestroy(h->q[k].ev_keys);
         if (h->q[k].ev_done) (void)hipEventDestroy(h->q[k].ev_done);

@@ -1122,6 +1122,114 @@ static int align_mode(int argc, char **argv) {
     return 0;
 }
 
+// --visibility <rosparam.yaml> <map.pcd|-> <out.pcd> [n_frames] [W H el_bottom el_top] [window] [k]: the see-through check
+// (erasor_hip_visibility_clouds): every scan becomes a W x H range image between the two elevations (degrees; 1024 x 64 between -24.8 and
+// 2.0, an HDL-64E's, by default), every map point is voted on by every image, and the points that scans look straight through leave.
+// The same files and poses as --align (data_dir, init_idx, poses_lidar2body.csv after callback_node's round trip, tf/lidar2body); the
+// map is <map.pcd>, or with "-" the configured initial map.  The two edge tables are evalmap.visibility_grid's expressions with C's tan.
+// window (1) and k (0: no incidence gate) as erasor_visibility says; the other parameters are the documented defaults (0.5 .. 80 m,
+// margins 0.2 m + 1 %, min_cos 0.25, min_through 2, hit_weight 1).  One line per frame, the result, and the kept cloud as a binary PCD --
+// which --eval scores against a ground truth like any other map.
+static int visibility_mode(int argc, char **argv) {
+    if (argc < 5 || (argc > 6 && argc < 10)) return 2;
+    const int max_frames = argc > 5 ? atoi(argv[5]) : 1 << 30;
+    size_t W = 1024, H = 64, window = 1, k = 0;
+    double el0 = -24.8, el1 = 2.0;
+    if (argc > 9 && (!parse_count(argv[6], &W) || !parse_count(argv[7], &H) || !parse_number(argv[8], &el0) || !parse_number(argv[9], &el1))) return 2;
+    if ((argc > 10 && !parse_count(argv[10], &window)) || (argc > 11 && !parse_count(argv[11], &k)) || argc > 12) return 2;
+    if (W % 8 || W < 8 || W > 4096 || H < 1 || H > 256 || !(el0 < el1) || !(el0 > -90.0) || !(el1 < 90.0) || window > 2 || k == 1 || k > 32) return 2;
+    erasor::OfflineMapUpdater::Config cfg;
+    erasor_hip_params_default(&cfg.params);
+    erasor::DriverConfig drv;
+    if (!erasor::load_config_yaml(argv[2], cfg, &drv)) {
+        fprintf(stderr, "cannot read %s\n", argv[2]);
+        return 3;
+    }
+    if (cfg.initial_map_path.empty() || cfg.initial_map_path == "/") cfg.initial_map_path = drv.data_dir + "/dense_global_map.pcd";
+    const std::string map_path = std::string(argv[3]) == "-" ? cfg.initial_map_path : std::string(argv[3]);
+    std::vector<Eigen::Matrix4f> poses;
+    if (!erasor::load_all_poses(drv.data_dir + "/poses_lidar2body.csv", poses)) {
+        fprintf(stderr, "cannot read %s/poses_lidar2body.csv\n", drv.data_dir.c_str());
+        return 3;
+    }
+    std::vector<float> map, scans, Tb;
+    if (!load_cloud_xyzi(map_path, map)) {
+        fprintf(stderr, "cannot read %s\n", map_path.c_str());
+        return 3;
+    }
+    std::vector<uint64_t> offsets{0};
+    const int last = std::min((int)poses.size(), drv.init_idx + max_frames);
+    for (int i = drv.init_idx; i < last; ++i) {
+        char name[64];
+        snprintf(name, sizeof(name), "/pcds/%06d.pcd", i);
+        std::vector<float> scan;
+        if (!load_cloud_xyzi(drv.data_dir + name, scan)) {
+            fprintf(stderr, "cannot read %s%s\n", drv.data_dir.c_str(), name);
+            return 3;
+        }
+        scans.insert(scans.end(), scan.begin(), scan.end());
+        offsets.push_back(scans.size() / 4);
+        const Eigen::Matrix4f T = erasor_utils::geoPose2eigen(erasor_utils::eigen2geoPose(poses[i]));  // (callback_node's round trip)
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) Tb.push_back(T(r, c));
+    }
+    geometry_msgs::Pose l2b;
+    l2b.position.x = cfg.lidar2body[0];
+    l2b.position.y = cfg.lidar2body[1];
+    l2b.position.z = cfg.lidar2body[2];
+    l2b.orientation.x = cfg.lidar2body[3];
+    l2b.orientation.y = cfg.lidar2body[4];
+    l2b.orientation.z = cfg.lidar2body[5];
+    l2b.orientation.w = cfg.lidar2body[6];
+    const Eigen::Matrix4f TL = erasor_utils::geoPose2eigen(l2b);  // (OMU.cpp:100)
+    float Tl[16];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) Tl[4 * r + c] = TL(r, c);
+    // the edge tables: evalmap.visibility_grid's expressions
+    const size_t M = W / 8;
+    const double pi = 3.141592653589793;
+    std::vector<double> col_tan, row_tan;
+    for (size_t j = 1; j < M; ++j) col_tan.push_back(tan(((pi / 4.0) * (double)j) / (double)M));
+    for (size_t i = 0; i <= H; ++i) row_tan.push_back(tan((((el1 - el0) * (double)i) / (double)H + el0) * (pi / 180.0)));
+    erasor_visibility prm;
+    memset(&prm, 0, sizeof(prm));
+    prm.width = (uint32_t)W, prm.height = (uint32_t)H, prm.col_tan = col_tan.data(), prm.row_tan = row_tan.data();
+    prm.min_range = 0.5, prm.max_range = 80.0, prm.margin_abs = 0.2, prm.margin_rel = 0.01;
+    prm.window = (uint32_t)window, prm.k = (uint32_t)k, prm.min_cos = 0.25, prm.min_through = 2, prm.hit_weight = 1.0;
+    erasor_hip_handle *h = render_handle();
+    if (!h) return 1;
+    const size_t n = map.size() / 4, n_frames = offsets.size() - 1;
+    std::vector<float> kept(std::max<size_t>(n, 1) * 4, 0.f);
+    std::vector<erasor_visibility_row> rows(std::max<size_t>(n_frames, 1));
+    erasor_visibility_result r;
+    const int rc = erasor_hip_visibility_clouds(h, map.data(), n, 0, scans.data(), scans.size() / 4, offsets.data(), n_frames, 0, Tl, Tb.data(), &prm, nullptr,
+                                                nullptr, kept.data(), n, rows.data(), &r);
+    if (rc) return render_fail(h, "visibility", rc);
+    erasor_hip_destroy(h);
+    typedef unsigned long long ull;
+    printf("%zu frames against %s (%zu points), %zu x %zu pixels between %.9g and %.9g degrees, window %zu, k %zu:\n", n_frames, map_path.c_str(), n, W, H,
+           el0, el1, window, k);
+    for (size_t f = 0; f < n_frames; ++f) {
+        const erasor_visibility_row &w = rows[f];
+        printf("%6d  n=%llu  dropped %llu non-finite, %llu on the axis, %llu out of range, %llu out of view  pixels %llu  map in view %llu: hit %llu, "
+               "occluded %llu, no return %llu, through %llu, grazing %llu\n",
+               drv.init_idx + (int)f, (ull)w.n_points, (ull)w.n_non_finite, (ull)w.n_on_axis, (ull)w.n_out_of_range, (ull)w.n_out_of_view, (ull)w.n_pixels,
+               (ull)w.n_map_in_view, (ull)w.n_hit, (ull)w.n_occluded, (ull)w.n_no_return, (ull)w.n_through, (ull)w.n_grazing);
+    }
+    printf("visibility: n=%llu  never in view=%llu  kept=%llu  removed=%llu (dynamic %llu, static %llu)  without a normal=%llu\n", (ull)r.n_points,
+           (ull)r.n_never_in_view, (ull)r.n_kept, (ull)r.n_removed, (ull)r.n_removed_dynamic, (ull)r.n_removed_static, (ull)r.n_map_no_normal);
+    printf("  verdicts: in view %llu  hit %llu  occluded %llu  no return %llu  through %llu  grazing %llu\n", (ull)r.n_in_view, (ull)r.n_hit, (ull)r.n_occluded,
+           (ull)r.n_no_return, (ull)r.n_through, (ull)r.n_grazing);
+    pcl::PointCloud<pcl::PointXYZI> out;
+    rows_to_cloud(kept, r.n_kept, out);
+    if (erasor_utils::save_pcd_binary(argv[4], out) != 0) {
+        fprintf(stderr, "cannot write %s\n", argv[4]);
+        return 1;
+    }
+    printf("saved %s\n", argv[4]);
+    return 0;
+}
+
 // --refine <rosparam.yaml> <poses_out> [n_frames] [max_dist = 1.0] [max_iters = 20]: what to do about the frames --align flags.  The same
 // files and poses as --align (data_dir, init_idx, poses_lidar2body.csv after callback_node's round trip, the initial map, tf/lidar2body);
 // every frame's T_body2origin is refined against the initial map by point-to-point ICP (erasor_hip_refine_poses_clouds).  One line per
@@ -1822,6 +1930,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && std::string(argv[1]) == "--visibility") {
+        try {
+            return visibility_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--label-scans") {
         try {
             return label_scans_mode(argc, argv);
@@ -1901,8 +2017,9 @@ int main(int argc, char **argv) {
                 "       %s --residue <gt> <est> [tol] [voxelsize] [voxel_leaf]\n"
                 "       %s --denoise <in.pcd> <out.pcd> sor <k> <mul> | ror <radius> <min_neighbors> | kth <k> <thr>\n"
                 "       %s --density <cloud.pcd> <k>\n"
-                "       %s --normals <in.pcd> <out.pcd> <k> [vx vy vz]\n",
-                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0],
+                "       %s --normals <in.pcd> <out.pcd> <k> [vx vy vz]\n"
+                "       %s --visibility <rosparam.yaml> <map.pcd|-> <out.pcd> [n_frames] [W H el_bottom el_top] [window] [k]\n",
+                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0],
                 argv[0]);
         return 2;
     }

@@ -29,6 +29,9 @@ points within a radius of it, and the outlier filters on both -- the host restat
 
 normals / normals_brute: every point's surface normal, curvature and covariance eigenvalues from its k nearest neighbours -- the host
 restatement of Erasor.normals.
+
+visibility / visibility_brute (and visibility_grid, visibility_column, visibility_transforms, visibility_decide): the see-through check,
+map points voted out by every scan's range image -- the normative text of Erasor.visibility.
 """
 import numpy as np
 from scipy.spatial import cKDTree
@@ -1556,3 +1559,345 @@ def normals(cloud, k, viewpoint=None):
     eig = np.stack([l0, l1, l2], 1)
     eig[~ok] = np.nan
     return nrm.astype(np.float32), curv, eig, _normals_result(n, k, 0, (~ok).sum(), (ok & (l0 == l1)).sum(), flip.sum(), curv)
+
+
+# ---- the see-through check: map points voted out by every scan's range image (include/erasor_hip.h: erasor_hip_visibility_*; kernels:
+# erasor_amd/csrc/visibility.hip.h), on the host ----------------------------------------------------------------------------------
+# The normative text of the contract; the device equals it byte for byte.  Float64 on the float32 coordinates, one IEEE operation at a
+# time, and nothing but + - * /, sqrt and comparisons: the pixel grid is DATA, two tables of tangents made once by the caller
+# (visibility_grid, or a sensor's own beam edges), so no pixel needs atan2 and its last-bit trouble at sector boundaries.
+#
+# The pixel of a point (x, y, z) in the lidar frame, W columns (M = W / 8 per octant) and H rows:
+#   a = |x|, b = |y|; a == b == 0: ON THE AXIS, no pixel.  t = min(a, b) / max(a, b) in [0, 1]; j = the number of col_tan entries <= t
+#   (col_tan: M - 1 strictly increasing tangents in (0, 1), the inner column edges of an octant; 0 <= j <= M - 1).
+#   quadrant q: 0 (x >= 0, y >= 0), 1 (x < 0, y >= 0), 2 (x < 0, y < 0), 3 (x >= 0, y < 0) -- a zero of either sign is >= 0;
+#   octant o = 2 q + odd with odd = (a < b) in quadrants 0 and 2, and odd = !(a < b) in quadrants 1 and 3: the octants 0 .. 7 counted
+#   counter-clockwise from +x.  An even octant runs outward from an axis, t grows with the angle: column o M + j.  An odd octant runs
+#   towards an axis, t falls with the angle, it is mirrored: column o M + (M - 1) - j.  So the columns 0 .. W - 1 follow each other
+#   once round the circle, and a direction on an edge belongs to exactly one of them.
+#   s = z / sqrt(x*x + y*y); row = (the number of row_tan entries <= s) - 1 (row_tan: H + 1 strictly increasing finite tangents, the row
+#   edges from the bottom); a row outside 0 .. H - 1 is OUT OF VIEW.
+#   range rho = sqrt((x*x + y*y) + z*z).
+# The gates, in this order: non-finite coordinate, on the axis, rho outside [min_range, max_range], out of view.
+VISIBILITY_EMPTY = 0xFFFFFFFF
+VISIBILITY_MAX_FRAMES = 65535
+VISIBILITY_ROW_FIELDS = ("n_points", "n_non_finite", "n_on_axis", "n_out_of_range", "n_out_of_view", "n_pixels", "n_map_in_view", "n_hit",
+                         "n_occluded", "n_no_return", "n_through", "n_grazing")
+VISIBILITY_RESULT_FIELDS = ("n_points", "n_never_in_view", "n_kept", "n_removed", "n_removed_dynamic", "n_removed_static", "n_map_no_normal",
+                            "n_in_view", "n_hit", "n_occluded", "n_no_return", "n_through", "n_grazing")
+VISIBILITY_DEFAULTS = {"min_range": 0.5, "max_range": 80.0, "margin_abs": 0.2, "margin_rel": 0.01, "window": 1, "k": 0, "min_cos": 0.25,
+                       "min_through": 2, "hit_weight": 1.0}
+VIS_HIT, VIS_OCCLUDED, VIS_NO_RETURN, VIS_THROUGH, VIS_GRAZING, VIS_NOT_IN_VIEW = 0, 1, 2, 3, 4, 5
+_VIS_OK, _VIS_NON_FINITE, _VIS_AXIS, _VIS_RANGE, _VIS_VIEW = 0, 1, 2, 3, 4
+
+
+def visibility_grid(width, height, el_bottom_deg, el_top_deg):
+    """The two edge tables of a uniform grid: `width` columns of equal azimuth (a multiple of 8), `height` rows of equal elevation between
+    el_bottom_deg and el_top_deg.  col_tan[k - 1] = tan(((pi / 4) * k) / M) for k = 1 .. M - 1, M = width / 8; row_tan[i] =
+    tan((((top - bottom) * i) / H + bottom) * (pi / 180)) for i = 0 .. H -- the driver forms them by the same expressions with C's tan."""
+    import math
+    W, H = int(width), int(height)
+    if W % 8 or not 8 <= W <= 4096 or not 1 <= H <= 256:
+        raise ValueError("visibility_grid: width must be a multiple of 8 within 8 .. 4096, height within 1 .. 256")
+    M = W // 8
+    col = np.array([math.tan(((math.pi / 4.0) * k) / M) for k in range(1, M)], np.float64)
+    row = np.array([math.tan((((float(el_top_deg) - float(el_bottom_deg)) * i) / H + float(el_bottom_deg)) * (math.pi / 180.0)) for i in range(H + 1)],
+                   np.float64)
+    return check_visibility_grid({"width": W, "height": H, "col_tan": col, "row_tan": row})
+
+
+def check_visibility_grid(grid):
+    W, H = int(grid["width"]), int(grid["height"])
+    col = np.ascontiguousarray(grid["col_tan"], np.float64).reshape(-1)
+    row = np.ascontiguousarray(grid["row_tan"], np.float64).reshape(-1)
+    if W % 8 or not 8 <= W <= 4096:
+        raise ValueError("visibility: width must be a multiple of 8 within 8 .. 4096")
+    if not 1 <= H <= 256:
+        raise ValueError("visibility: height must be within 1 .. 256")
+    if len(col) != W // 8 - 1 or len(row) != H + 1:
+        raise ValueError("visibility: col_tan has width / 8 - 1 entries and row_tan height + 1")
+    if not ((col > 0) & (col < 1)).all() or not (np.diff(col) > 0).all():
+        raise ValueError("visibility: col_tan must be strictly increasing within (0, 1)")
+    if not np.isfinite(row).all() or not (np.diff(row) > 0).all():
+        raise ValueError("visibility: row_tan must be finite and strictly increasing")
+    return {"width": W, "height": H, "col_tan": col, "row_tan": row}
+
+
+def visibility_column(x, y, col_tan, width):
+    """the column of the direction (x, y), or -1 on the axis: THE pixel mapping, written down once (float64 arrays)"""
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    M = int(width) // 8
+    a, b = np.abs(x), np.abs(y)
+    swap = a < b
+    lo, hi = np.where(swap, a, b), np.where(swap, b, a)
+    axis = hi == 0
+    with np.errstate(all="ignore"):
+        t = lo / np.where(axis, 1.0, hi)
+    j = np.searchsorted(col_tan, t, side="right").astype(np.int64)  # the number of entries <= t
+    sx, sy = x < 0, y < 0
+    q = np.where(sx, np.where(sy, 2, 1), np.where(sy, 3, 0))
+    odd = np.where((q & 1) == 1, ~swap, swap).astype(np.int64)
+    o = 2 * q + odd
+    return np.where(axis, -1, np.where(odd == 1, o * M + (M - 1) - j, o * M + j))
+
+
+def _vis_pixels(x, y, z, finite, grid, min_range, max_range):
+    """(gate, rho, column, row) of points in a lidar frame (float64 arrays): gate is _VIS_OK or the first gate that rejects"""
+    W, H = grid["width"], grid["height"]
+    with np.errstate(all="ignore"):
+        x, y, z = (np.where(finite, v, 1.0) for v in (x, y, z))
+        col = visibility_column(x, y, grid["col_tan"], W)
+        xy = x * x + y * y
+        rho = np.sqrt(xy + z * z)
+        s = z / np.sqrt(np.where(col < 0, 1.0, xy))
+    row = np.searchsorted(grid["row_tan"], s, side="right").astype(np.int64) - 1
+    gate = np.full(len(x), _VIS_OK, np.int64)
+    gate[(row < 0) | (row >= H)] = _VIS_VIEW
+    gate[~((rho >= min_range) & (rho <= max_range))] = _VIS_RANGE
+    gate[col < 0] = _VIS_AXIS
+    gate[~finite] = _VIS_NON_FINITE
+    return gate, rho, col, row
+
+
+def visibility_transforms(T_body2origin, T_lidar2body=None):
+    """Every frame's map-to-lidar transform in float64, the rigid inverse of T_body2origin[f] . T_lidar2body (their upper three rows, the
+    float32 entries widened), every sum in index order: M[i][j] = (A[i][0] B[0][j] + A[i][1] B[1][j]) + A[i][2] B[2][j], and + A[i][3] in
+    column 3; the inverse's rotation is M's transposed and its translation -((M[0][i] M[0][3] + M[1][i] M[1][3]) + M[2][i] M[2][3]).
+    Returns (m [n, 12]: per row r0, r1, r2, t; origin [n, 3]: the lidar's origin in the map frame).  ValueError on a non-finite entry."""
+    A = np.asarray(T_body2origin, np.float32).reshape(-1, 4, 4).astype(np.float64)
+    B = (np.eye(4, dtype=np.float32) if T_lidar2body is None else np.asarray(T_lidar2body, np.float32).reshape(4, 4)).astype(np.float64)
+    n = len(A)
+    M = np.zeros((n, 3, 4))
+    with np.errstate(all="ignore"):
+        for i in range(3):
+            for j in range(4):
+                v = (A[:, i, 0] * B[0, j] + A[:, i, 1] * B[1, j]) + A[:, i, 2] * B[2, j]
+                M[:, i, j] = v + A[:, i, 3] if j == 3 else v
+        m = np.zeros((n, 12))
+        for i in range(3):
+            for j in range(3):
+                m[:, 4 * i + j] = M[:, j, i]
+            m[:, 4 * i + 3] = -((M[:, 0, i] * M[:, 0, 3] + M[:, 1, i] * M[:, 1, 3]) + M[:, 2, i] * M[:, 2, 3])
+    if not (np.isfinite(m).all() and np.isfinite(M).all()):
+        raise ValueError("visibility: non-finite frame transform")
+    return m, M[:, :, 3].copy()
+
+
+def visibility_decide(votes, min_through, hit_weight):
+    """the points removed (bool): through >= min_through and (double)through > hit_weight * (double)hit"""
+    v = np.asarray(votes).reshape(-1, 4)
+    th, hit = v[:, 2].astype(np.float64), v[:, 1].astype(np.float64)
+    return (v[:, 2].astype(np.int64) >= int(min_through)) & (th > np.float64(hit_weight) * hit)
+
+
+def _vis_args(map_xyzi, scans, grid, min_range, max_range, margin_abs, margin_rel, window, k, min_cos, min_through, hit_weight):
+    if grid is None:
+        raise ValueError("visibility: a grid is needed (visibility_grid)")
+    g = check_visibility_grid(grid)
+    if not (np.isfinite(min_range) and np.isfinite(max_range) and 0 <= min_range < max_range):
+        raise ValueError("visibility: 0 <= min_range < max_range, both finite")
+    if not (np.isfinite(margin_abs) and np.isfinite(margin_rel) and margin_abs >= 0 and margin_rel >= 0):
+        raise ValueError("visibility: the margins must be finite numbers >= 0")
+    if window not in (0, 1, 2):
+        raise ValueError("visibility: window must be 0, 1 or 2")
+    if not (k == 0 or NORMALS_MIN_K <= k <= KNN_MAX_K):
+        raise ValueError("visibility: k must be 0 or within 2 .. 32")
+    if not (np.isfinite(min_cos) and np.isfinite(hit_weight) and hit_weight >= 0):
+        raise ValueError("visibility: min_cos must be finite and hit_weight a finite number >= 0")
+    if not 0 <= int(min_through) <= 0xFFFFFFFF:
+        raise ValueError("visibility: min_through must fit 32 bits")
+    if len(scans) > VISIBILITY_MAX_FRAMES:
+        raise ValueError("visibility: more than 65535 frames")
+    c = np.ascontiguousarray(np.asarray(map_xyzi, np.float32).reshape(-1, 4))
+    if k and not np.isfinite(c[:, :3]).all():
+        raise ValueError("visibility: non-finite coordinate in the map (the normals need a finite cloud)")
+    return g, c
+
+
+def _vis_finish(c, votes, rows, n_no_normal, min_through, hit_weight, keep):
+    rem = visibility_decide(votes, min_through, hit_weight)
+    dyn = _decode(c[:, 3])[2]
+    res = {"n_points": int(len(c)), "n_never_in_view": int((votes[:, 0] == 0).sum()), "n_kept": int((~rem).sum()), "n_removed": int(rem.sum()),
+           "n_removed_dynamic": int((rem & dyn).sum()), "n_removed_static": int((rem & ~dyn).sum()), "n_map_no_normal": int(n_no_normal)}
+    for key, src in (("n_in_view", "n_map_in_view"), ("n_hit", "n_hit"), ("n_occluded", "n_occluded"), ("n_no_return", "n_no_return"),
+                     ("n_through", "n_through"), ("n_grazing", "n_grazing")):
+        res[key] = int(sum(r[src] for r in rows))
+    return votes, (~rem).astype(np.uint8), (c[~rem].copy() if keep else None), rows, res
+
+
+def visibility_verdicts(map_xyzi, scans, T_body2origin, T_lidar2body=None, grid=None, min_range=0.5, max_range=80.0, margin_abs=0.2, margin_rel=0.01,
+                        window=1, k=0, min_cos=0.25, min_through=2, hit_weight=1.0):
+    """the verdict of every (frame, map point) pair, VIS_* codes as uint8 [n_frames, n_map], and every frame's range image [n_frames, H, W]
+    uint32: what visibility() counts, for the tests and for looking at one frame"""
+    g, c = _vis_args(map_xyzi, scans, grid, min_range, max_range, margin_abs, margin_rel, window, k, min_cos, min_through, hit_weight)
+    W, H, w = g["width"], g["height"], int(window)
+    m, org = visibility_transforms(np.zeros((0, 4, 4), np.float32) if len(scans) == 0 else T_body2origin, T_lidar2body)
+    if len(m) != len(scans):
+        raise ValueError("visibility: one T_body2origin per frame")
+    nrm = normals(c, int(k))[0].astype(np.float64) if k else None
+    p = c[:, :3].astype(np.float64)
+    pfin = np.isfinite(c[:, :3]).all(1)
+    verd = np.full((len(scans), len(c)), VIS_NOT_IN_VIEW, np.uint8)
+    imgs = np.full((len(scans), H, W), VISIBILITY_EMPTY, np.uint32)
+    drops = np.zeros((len(scans), 5), np.int64)
+    for f, scan in enumerate(scans):
+        s = np.asarray(scan, np.float32).reshape(-1, 4)[:, :3]
+        s64 = s.astype(np.float64)
+        gate, rho, col, row = _vis_pixels(s64[:, 0], s64[:, 1], s64[:, 2], np.isfinite(s).all(1), g, min_range, max_range)
+        ok = gate == _VIS_OK
+        drops[f] = [len(s)] + [int((gate == code).sum()) for code in (_VIS_NON_FINITE, _VIS_AXIS, _VIS_RANGE, _VIS_VIEW)]
+        with np.errstate(over="ignore"):
+            bits = rho[ok].astype(np.float32).view(np.uint32)
+        np.minimum.at(imgs[f].reshape(-1), row[ok] * W + col[ok], bits)  # (non-negative floats order as their bits)
+        # the map in this frame
+        with np.errstate(all="ignore"):
+            px, py, pz = (np.where(pfin, p[:, a], 0.0) for a in range(3))
+            q = [((m[f, 4 * r] * px + m[f, 4 * r + 1] * py) + m[f, 4 * r + 2] * pz) + m[f, 4 * r + 3] for r in range(3)]
+        gate, rho, col, row = _vis_pixels(q[0], q[1], q[2], pfin, g, min_range, max_range)
+        iv = np.flatnonzero(gate == _VIS_OK)
+        rho, col, row = rho[iv], col[iv], row[iv]
+        mg = margin_abs + margin_rel * rho
+        lo, hi = rho - mg, rho + mg
+        hit = np.zeros(len(iv), bool)
+        occ = np.zeros(len(iv), bool)
+        some = np.zeros(len(iv), bool)
+        for dr in range(-w, w + 1):
+            rr = row + dr
+            inr = (rr >= 0) & (rr < H)
+            for dc in range(-w, w + 1):
+                cc = (col + dc) % W
+                b = imgs[f][np.where(inr, rr, 0), cc]
+                full = inr & (b != VISIBILITY_EMPTY)
+                r = b.view(np.float32).astype(np.float64)
+                with np.errstate(invalid="ignore"):
+                    hit |= full & (lo <= r) & (r <= hi)
+                    occ |= full & (r < lo)
+                some |= full
+        v = np.where(hit, VIS_HIT, np.where(occ, VIS_OCCLUDED, np.where(~some, VIS_NO_RETURN, VIS_THROUGH))).astype(np.uint8)
+        if k:
+            d = p[iv] - org[f]
+            n = nrm[iv]
+            with np.errstate(invalid="ignore"):
+                dot = (n[:, 0] * d[:, 0] + n[:, 1] * d[:, 1]) + n[:, 2] * d[:, 2]
+                vv = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+                graze = (v == VIS_THROUGH) & ~np.isnan(n[:, 0]) & (np.abs(dot) < min_cos * np.sqrt(vv))
+            v[graze] = VIS_GRAZING
+        verd[f, iv] = v
+    return verd, imgs, drops, (int(np.isnan(nrm[:, 0]).sum()) if k else 0), c
+
+
+def _vis_rows(verd, imgs, drops):
+    return [dict(zip(VISIBILITY_ROW_FIELDS, [int(x) for x in drops[f]] + [int((imgs[f] != VISIBILITY_EMPTY).sum()), int((verd[f] != VIS_NOT_IN_VIEW).sum())] +
+                     [int((verd[f] == code).sum()) for code in (VIS_HIT, VIS_OCCLUDED, VIS_NO_RETURN, VIS_THROUGH, VIS_GRAZING)])) for f in range(len(verd))]
+
+
+def visibility(map_xyzi, scans, T_body2origin, T_lidar2body=None, grid=None, min_range=0.5, max_range=80.0, margin_abs=0.2, margin_rel=0.01,
+               window=1, k=0, min_cos=0.25, min_through=2, hit_weight=1.0, keep=True):
+    """The see-through check (Erasor.visibility): a map point that later scans look straight through was not static.  Every scan (XYZI
+    rows in the lidar frame, taken as given) becomes an H x W range image: per pixel the smallest float32 range of the points that pass
+    the gates.  Every map point is put into every frame by visibility_transforms; where it passes the gates it is IN VIEW, and with m =
+    margin_abs + margin_rel * rho the non-empty pixels r (as float64) of the (2 window + 1)^2 pixels around its own -- columns wrap, rows
+    clip -- give its verdict, in this priority: HIT (some rho - m <= r <= rho + m), OCCLUDED (some r < rho - m), NO RETURN (all empty:
+    no evidence), THROUGH (every r > rho + m).  With k > 0 a THROUGH is demoted to GRAZING (no evidence) when |n . v| < min_cos *
+    sqrt(v . v), v = p - the lidar's origin in the map frame and n the point's float32 normal from normals(map, k); a NaN normal gates
+    nothing.  A point is removed iff through >= min_through and through > hit_weight * hit.
+    Returns (votes [n, 4] uint16: in_view, hit, through, occluded; mask uint8, 1 = kept; the kept rows in the order given or None;
+    a row per frame with VISIBILITY_ROW_FIELDS; a dict with VISIBILITY_RESULT_FIELDS)."""
+    verd, imgs, drops, n_no_normal, c = visibility_verdicts(map_xyzi, scans, T_body2origin, T_lidar2body, grid, min_range, max_range, margin_abs,
+                                                            margin_rel, window, k, min_cos, min_through, hit_weight)
+    votes = np.stack([(verd != VIS_NOT_IN_VIEW).sum(0), (verd == VIS_HIT).sum(0), (verd == VIS_THROUGH).sum(0), (verd == VIS_OCCLUDED).sum(0)],
+                     1).astype(np.uint16).reshape(-1, 4)
+    return _vis_finish(c, votes, _vis_rows(verd, imgs, drops), n_no_normal, min_through, hit_weight, keep)
+
+
+def visibility_brute(map_xyzi, scans, T_body2origin, T_lidar2body=None, grid=None, min_range=0.5, max_range=80.0, margin_abs=0.2, margin_rel=0.01,
+                     window=1, k=0, min_cos=0.25, min_through=2, hit_weight=1.0, keep=True):
+    """visibility() point by point in plain Python floats (math.sqrt, bisect), for small inputs: the check of the vectorised text"""
+    import bisect
+    import math
+    g, c = _vis_args(map_xyzi, scans, grid, min_range, max_range, margin_abs, margin_rel, window, k, min_cos, min_through, hit_weight)
+    W, H, w, M = g["width"], g["height"], int(window), g["width"] // 8
+    ct, rt = [float(v) for v in g["col_tan"]], [float(v) for v in g["row_tan"]]
+    m, org = visibility_transforms(np.zeros((0, 4, 4), np.float32) if len(scans) == 0 else T_body2origin, T_lidar2body)
+    nrm = normals_brute(c, int(k))[0] if k else None
+
+    def pixel(x, y, z):
+        if not (math.isfinite(x) and math.isfinite(y) and math.isfinite(z)):
+            return _VIS_NON_FINITE, 0.0, 0, 0
+        a, b = abs(x), abs(y)
+        if a == 0 and b == 0:
+            return _VIS_AXIS, 0.0, 0, 0
+        xy = x * x + y * y
+        rho = math.sqrt(xy + z * z)
+        if not (min_range <= rho <= max_range):
+            return _VIS_RANGE, rho, 0, 0
+        swap = a < b
+        t = (a / b) if swap else (b / a)
+        j = bisect.bisect_right(ct, t)
+        q = (2 if y < 0 else 1) if x < 0 else (3 if y < 0 else 0)
+        odd = (not swap) if q & 1 else swap
+        o = 2 * q + (1 if odd else 0)
+        col = o * M + (M - 1) - j if odd else o * M + j
+        row = bisect.bisect_right(rt, z / math.sqrt(xy)) - 1
+        if row < 0 or row >= H:
+            return _VIS_VIEW, rho, col, row
+        return _VIS_OK, rho, col, row
+
+    votes = np.zeros((len(c), 4), np.uint16)
+    rows = []
+    for f, scan in enumerate(scans):
+        s = np.asarray(scan, np.float32).reshape(-1, 4)
+        img = [VISIBILITY_EMPTY] * (H * W)
+        cnt = [0] * 5
+        for x, y, z, _ in s.astype(np.float64).tolist():
+            gate, rho, col, row = pixel(x, y, z)
+            cnt[gate] += 1
+            if gate == _VIS_OK:
+                with np.errstate(over="ignore"):
+                    bits = int(np.float32(rho).view(np.uint32))
+                img[row * W + col] = min(img[row * W + col], bits)
+        tally = [0] * 6
+        mf, of = [float(v) for v in m[f]], [float(v) for v in org[f]]
+        for i, (x32, y32, z32, _) in enumerate(c.astype(np.float64).tolist()):
+            if not (math.isfinite(x32) and math.isfinite(y32) and math.isfinite(z32)):
+                continue
+            q = [((mf[4 * r] * x32 + mf[4 * r + 1] * y32) + mf[4 * r + 2] * z32) + mf[4 * r + 3] for r in range(3)]
+            gate, rho, col, row = pixel(q[0], q[1], q[2])
+            if gate != _VIS_OK:
+                continue
+            mg = margin_abs + margin_rel * rho
+            lo, hi = rho - mg, rho + mg
+            hit = occ = some = False
+            for dr in range(-w, w + 1):
+                if not 0 <= row + dr < H:
+                    continue
+                for dc in range(-w, w + 1):
+                    b = img[(row + dr) * W + (col + dc) % W]
+                    if b == VISIBILITY_EMPTY:
+                        continue
+                    r = float(np.uint32(b).view(np.float32))
+                    some = True
+                    hit = hit or lo <= r <= hi
+                    occ = occ or r < lo
+            v = VIS_HIT if hit else VIS_OCCLUDED if occ else VIS_NO_RETURN if not some else VIS_THROUGH
+            if v == VIS_THROUGH and k:
+                n = [float(t) for t in nrm[i]]
+                if not math.isnan(n[0]):
+                    d = [x32 - of[0], y32 - of[1], z32 - of[2]]
+                    dot = (n[0] * d[0] + n[1] * d[1]) + n[2] * d[2]
+                    if abs(dot) < min_cos * math.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]):
+                        v = VIS_GRAZING
+            tally[5] += 1
+            tally[v] += 1
+            votes[i, 0] += 1
+            if v == VIS_HIT:
+                votes[i, 1] += 1
+            elif v == VIS_THROUGH:
+                votes[i, 2] += 1
+            elif v == VIS_OCCLUDED:
+                votes[i, 3] += 1
+        rows.append(dict(zip(VISIBILITY_ROW_FIELDS, [len(s), cnt[_VIS_NON_FINITE], cnt[_VIS_AXIS], cnt[_VIS_RANGE], cnt[_VIS_VIEW],
+                                                     sum(1 for b in img if b != VISIBILITY_EMPTY), tally[5], tally[VIS_HIT], tally[VIS_OCCLUDED],
+                                                     tally[VIS_NO_RETURN], tally[VIS_THROUGH], tally[VIS_GRAZING]])))
+    n_no_normal = int(np.isnan(nrm[:, 0]).sum()) if k else 0
+    return _vis_finish(c, votes, rows, n_no_normal, min_through, hit_weight, keep)

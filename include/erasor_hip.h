@@ -630,6 +630,94 @@ int erasor_hip_refine_poses_plane_map(erasor_hip_handle *h, const void *scans_xy
                                       const erasor_refine_plane_params *params, erasor_refine_plane_row *rows,
                                       erasor_refine_plane_summary *summary);
 
+/* ---- the see-through check: map points voted out by every scan's range image ----------------------------------------------------
+ * stands in for: nothing the reference runs.  ERASOR rejects by its bin-wise height test alone; the reference only COMPARES its result
+ * against the visibility-based methods' maps (README.md:214, roslaunch erasor compare_results.launch, and the OctoMap / PeopleRemover /
+ * Removert panels of img/<seq>/README.md), and erasor_hip_label_map exists so that such maps can be scored here.  This call produces
+ * that second opinion: a map point that later scans look straight through was not static.
+ * The contract; the normative text is erasor_amd/evalmap.py (visibility / visibility_brute), which the device equals byte for byte.
+ * Float64 on the float32 coordinates, every operation a separate IEEE operation in the order written, nothing but + - * /, sqrt and
+ * comparisons -- the pixel grid is data, two tables of tangents, so that no pixel needs atan2:
+ *   - the pixel of (x, y, z) in a lidar frame, W columns (M = W / 8 per octant) and H rows: a = |x|, b = |y|; a == b == 0 is ON THE
+ *     AXIS.  t = min(a, b) / max(a, b), j = the number of col_tan entries <= t.  The quadrant q is 0 (x >= 0, y >= 0), 1 (x < 0,
+ *     y >= 0), 2 (x < 0, y < 0), 3 (x >= 0, y < 0), a zero of either sign being >= 0; the octant o = 2 q + odd, odd = (a < b) in
+ *     quadrants 0 and 2 and !(a < b) in 1 and 3 (octants counted counter-clockwise from +x).  The column is o M + j in an even octant
+ *     and o M + (M - 1) - j, mirrored, in an odd one.  s = z / sqrt(x*x + y*y), row = (the number of row_tan entries <= s) - 1; a row
+ *     outside 0 .. H - 1 is OUT OF VIEW.  rho = sqrt((x*x + y*y) + z*z);
+ *   - the gates, in this order: a non-finite coordinate, on the axis, rho outside [min_range, max_range], out of view;
+ *   - range images: per frame H x W uint32.  A scan point, as given in the lidar frame with no transform, that passes the gates puts the
+ *     bits of (float)rho into its pixel by an integer minimum; an empty pixel is 0xFFFFFFFF.  The others are counted per frame and gate;
+ *   - every frame's map-to-lidar transform is the rigid inverse of T_body2origin[f] . T_lidar2body (upper three rows, widened), in
+ *     float64 on the host: M[i][j] = (A[i][0] B[0][j] + A[i][1] B[1][j]) + A[i][2] B[2][j], + A[i][3] in column 3; the inverse's
+ *     rotation is M's transposed, its translation -((M[0][i] M[0][3] + M[1][i] M[1][3]) + M[2][i] M[2][3]); the lidar's origin in the
+ *     map frame is M's column 3.  A map point p goes into frame f as q = ((r0 x + r1 y) + r2 z) + t per row; it is IN VIEW of f when it
+ *     passes the gates;
+ *   - the verdict of a point in view, with m = margin_abs + margin_rel * rho, over the non-empty pixels r (as float64) of the
+ *     (2 window + 1)^2 pixels around its own, columns wrapping mod W and rows clipped, in this priority: HIT (some rho - m <= r <=
+ *     rho + m), OCCLUDED (some r < rho - m), NO RETURN (every pixel empty: no evidence), THROUGH (every r > rho + m);
+ *   - with k > 0 a THROUGH is demoted to GRAZING (no evidence) when |n . v| < min_cos * sqrt(v . v), v = p - the frame's origin and n
+ *     the point's float32 normal of erasor_hip_normals_* with k neighbours ("up"), computed once a call on the device and never copied
+ *     out; a NaN normal gates nothing (isolated fragments are what should stay removable);
+ *   - a point is removed iff through >= min_through and (double)through > hit_weight * (double)hit. */
+typedef struct erasor_visibility {
+    uint32_t width;               /* W: columns, a multiple of 8 within 8 .. 4096 */
+    uint32_t height;              /* H: rows, 1 .. 256 */
+    const double *col_tan;        /* [W / 8 - 1] strictly increasing, within (0, 1): the inner column edges of an octant (host) */
+    const double *row_tan;        /* [H + 1] strictly increasing, finite: the row edges from the bottom (host) */
+    double min_range, max_range;  /* finite, 0 <= min_range < max_range */
+    double margin_abs, margin_rel;/* finite, >= 0 */
+    uint32_t window;              /* w: 0, 1 or 2 */
+    uint32_t k;                   /* 0: no incidence gate; 2 .. 32: the normals' neighbourhood */
+    double min_cos;               /* finite */
+    uint32_t min_through;
+    uint32_t reserved;            /* 0 */
+    double hit_weight;            /* finite, >= 0 */
+    uint64_t image_budget_bytes;  /* the frames are cut into batches whose images fit this; 0: ERASOR_VISIBILITY_IMAGE_BUDGET; at least one image */
+} erasor_visibility;
+#define ERASOR_VISIBILITY_IMAGE_BUDGET (256ull << 20)
+#define ERASOR_VISIBILITY_MAX_FRAMES 65535
+
+typedef struct erasor_visibility_row {  /* one frame */
+    uint64_t n_points;        /* scan points given */
+    uint64_t n_non_finite;    /* ... dropped: a non-finite coordinate */
+    uint64_t n_on_axis;       /* ... x == y == 0 */
+    uint64_t n_out_of_range;  /* ... rho outside [min_range, max_range] */
+    uint64_t n_out_of_view;   /* ... a row outside 0 .. H - 1 */
+    uint64_t n_pixels;        /* pixels filled */
+    uint64_t n_map_in_view;   /* map points in view, and their verdicts: */
+    uint64_t n_hit, n_occluded, n_no_return, n_through, n_grazing;
+} erasor_visibility_row;
+
+typedef struct erasor_visibility_result {
+    uint64_t n_points;           /* map points */
+    uint64_t n_never_in_view;    /* ... in view of no frame */
+    uint64_t n_kept, n_removed;
+    uint64_t n_removed_dynamic;  /* removed points by label, as erasor_density_result counts them */
+    uint64_t n_removed_static;
+    uint64_t n_map_no_normal;    /* k > 0: map points whose normal is NaN (not gated) */
+    uint64_t n_in_view, n_hit, n_occluded, n_no_return, n_through, n_grazing;  /* over all frames */
+} erasor_visibility_result;
+
+/* Map, scans, offsets, T_lidar2body and T_body2origin as erasor_hip_align_frames_clouds takes them.  Every output is a host buffer and
+ * may be NULL: votes (n_map x 4 uint16: in_view, hit, through, occluded), keep_mask (n_map uint8, 1 = kept), kept_xyzi (the kept rows in
+ * the order given, erasor_hip_density_filter_*'s stable compaction; cap_points rows, ERASOR_E_CAPACITY after res is filled if they do
+ * not fit), rows (n_frames), res.  Works in the evaluator's own scratch.  ERASOR_E_INVALID: params NULL, a bad width or height, tables
+ * that are NULL or not increasing, min_range >= max_range or a negative or non-finite range or margin, window above 2, k = 1 or above
+ * 32, a non-finite min_cos or hit_weight, more than 65535 frames, offsets that are not monotone, a non-finite pose entry or frame
+ * transform, more than 2^30 points, and with k > 0 a non-finite map coordinate (the normals' refusal).  ERASOR_E_STATE: a step in
+ * flight. */
+int erasor_hip_visibility_clouds(erasor_hip_handle *h, const void *map_xyzi, size_t n_map, int map_is_device, const void *scans_xyzi,
+                                 size_t n_scan_points, const uint64_t *offsets, size_t n_frames, int scans_are_device,
+                                 const float T_lidar2body[16] /* NULL: identity */, const float *T_body2origin,
+                                 const erasor_visibility *params, uint16_t *votes, uint8_t *keep_mask, float *kept_xyzi, size_t cap_points,
+                                 erasor_visibility_row *rows, erasor_visibility_result *res);
+/* the same for the handle's current map (compacted on the device as erasor_hip_normals_map does, never copied to the host and not
+ * modified).  ERASOR_E_STATE also: no map. */
+int erasor_hip_visibility_map(erasor_hip_handle *h, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                              int scans_are_device, const float T_lidar2body[16], const float *T_body2origin,
+                              const erasor_visibility *params, uint16_t *votes, uint8_t *keep_mask, float *kept_xyzi, size_t cap_points,
+                              erasor_visibility_row *rows, erasor_visibility_result *res);
+
 /* ---- every scan's points labelled static or moving from a cleaned map ---------------------------------------------------------
  * replaces: what users of a cleaned map do on the host afterwards -- a KD-tree over the cleaned map, a radius test per scan point, the
  * scan's moving points dropped (automatic moving-object-segmentation labels, cleaned scans for re-mapping); the reference itself stops
