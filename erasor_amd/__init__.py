@@ -239,6 +239,39 @@ def visibility_grid(width, height, el_bottom_deg, el_top_deg):
     from . import evalmap
     return evalmap.visibility_grid(width, height, el_bottom_deg, el_top_deg)
 
+class Carve(C.Structure):
+    """erasor_carve"""
+    _fields_ = [("voxel", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double), ("l_init", C.c_float), ("l_hit", C.c_float),
+                ("l_miss", C.c_float), ("l_min", C.c_float), ("l_max", C.c_float), ("l_thr", C.c_float), ("stop_short", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class CarveRow(C.Structure):
+    """erasor_carve_row"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_non_finite", "n_out_of_range", "n_rays", "n_steps", "n_end_in_map", "n_voxels_hit",
+                                          "n_voxels_free")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class CarveResult(C.Structure):
+    """erasor_carve_result"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_map_non_finite", "n_voxels", "n_blocks", "n_voxels_touched", "n_kept", "n_removed",
+                                          "n_removed_dynamic", "n_removed_static", "n_scan_points", "n_non_finite", "n_out_of_range", "n_rays",
+                                          "n_steps", "n_end_in_map", "n_voxels_hit", "n_voxels_free")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def carve_logodds(p_hit=0.7, p_miss=0.4, p_min=0.12, p_max=0.97, p_thr=0.5):
+    """evalmap.carve_logodds, re-exported: OctoMap's log-odds from its probabilities (float32(log(p / (1 - p))), l_init = 0), for
+    Erasor.carve"""
+    from . import evalmap
+    return evalmap.carve_logodds(p_hit, p_miss, p_min, p_max, p_thr)
+
+
 DENSITY_SCORES = {"kth": 0, "mean": 1, "count": 2}  # ERASOR_DENSITY_KTH / _MEAN / _COUNT
 DENSITY_RULES = {"abs": 0, "mad": 1}                # ERASOR_DENSITY_ABS / _MAD
 KNN_NONE = 0xFFFFFFFF  # the padding of a neighbour list
@@ -423,7 +456,7 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "normals.hip.h", "refine_plane.hip.h", "visibility.hip.h", "render.hip.h", "revert_bins.hip.h",
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "normals.hip.h", "refine_plane.hip.h", "visibility.hip.h", "carve.hip.h", "render.hip.h", "revert_bins.hip.h",
                                                  "exact_sort.hip.h", "exact_sort_core.h", "overlap_auto.h", "stream_place.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
@@ -1107,6 +1140,55 @@ class Erasor:
         self._check(fn(self._h, *head, q[0], q[1], _p(offs), C.c_size_t(n_f), C.c_int(q[2]), Tl, _p(Tb), C.byref(prm),
                        _p(votes), _p(mask), _p(out) if keep else None, C.c_size_t(n if keep else 0), rows, C.byref(r)))
         return votes[:n], mask[:n], (out[: r.n_kept] if keep else None), [rows[f].as_dict() for f in range(n_f)], r.as_dict()
+
+    # -- carving free space: every scan's rays walked through the map's voxels (on the host: evalmap.carve) --
+    def carve(self, scans, T_body2origin, T_lidar2body=None, map=None, voxel=0.2, min_range=0.5, max_range=80.0, stop_short=0, logodds=None, keep=True):
+        """Free space carved out of a map, OctoMap's way (erasor_hip_carve_clouds / _map): the map goes into voxels of `voxel` metres, every
+        ray of every scan is walked through them from the lidar's origin to its return; a voxel that rays pass through is free in that
+        frame, one that rays end in is hit (hits first), and the frames are integrated in order as clamped float32 log-odds (`logodds`: a
+        dict with l_init, l_hit, l_miss, l_min, l_max, l_thr; None: carve_logodds()).  A point is removed iff its voxel's log-odds end
+        below l_thr.  The last stop_short voxels before a ray's end give no free evidence.  scans, poses and T_lidar2body as for
+        visibility; `map` a cloud as for evaluate, or None for the handle's current map (which stays as it is).  Returns (votes (n, 2)
+        uint16: the hits and misses of the point's voxel; logodds (n,) float32; mask uint8, 1 = kept; the kept rows in the order given,
+        or None unless keep; a row per frame; the result) as evalmap.carve does, byte for byte."""
+        from . import evalmap
+        kept = []
+        if isinstance(scans, tuple):
+            ptr, offsets = scans
+            offs = np.ascontiguousarray(offsets, np.uint64)
+            q = (C.c_void_p(ptr), C.c_size_t(int(offs[-1]) if len(offs) else 0), 1)
+        else:
+            a = [_f32(s).reshape(-1, 4) for s in scans]
+            offs = np.zeros(len(a) + 1, np.uint64)
+            offs[1:] = np.cumsum([len(s) for s in a], dtype=np.uint64)
+            cat = _f32(np.concatenate(a) if a else np.zeros((0, 4), np.float32))
+            kept.append(cat)
+            q = (_p(cat), C.c_size_t(len(cat)), 0)
+        n_f = len(offs) - 1
+        Tb = _f32(np.asarray(T_body2origin, np.float32).reshape(n_f, 16) if n_f else np.zeros((1, 16), np.float32))
+        if T_lidar2body is not None:
+            kept.append(_f32(T_lidar2body).reshape(16))
+        Tl = None if T_lidar2body is None else _p(kept[-1])
+        lg = evalmap.carve_logodds() if logodds is None else logodds
+        if not 0 <= int(stop_short) <= 0xFFFFFFFF:
+            raise ValueError("carve: stop_short must fit 32 bits")
+        prm = Carve(float(voxel), float(min_range), float(max_range), *[float(lg[k]) for k in evalmap.CARVE_LOGODDS_FIELDS], int(stop_short), 0)
+        if map is None:
+            head, n = (), self._map_n()
+            fn = lib().erasor_hip_carve_map
+        else:
+            head = self._eval_cloud(map, kept)
+            n = head[1].value
+            fn = lib().erasor_hip_carve_clouds
+        votes = np.empty((max(n, 1), 2), np.uint16)
+        lo = np.empty(max(n, 1), np.float32)
+        mask = np.empty(max(n, 1), np.uint8)
+        out = np.empty((max(n, 1), 4), np.float32) if keep else None
+        rows = (CarveRow * max(n_f, 1))()
+        r = CarveResult()
+        self._check(fn(self._h, *head, q[0], q[1], _p(offs), C.c_size_t(n_f), C.c_int(q[2]), Tl, _p(Tb), C.byref(prm),
+                       _p(votes), _p(lo), _p(mask), _p(out) if keep else None, C.c_size_t(n if keep else 0), rows, C.byref(r)))
+        return votes[:n], lo[:n], mask[:n], (out[: r.n_kept] if keep else None), [rows[f].as_dict() for f in range(n_f)], r.as_dict()
 
     # -- every scan's points labelled static or moving from a cleaned map (on the host: evalmap.label_scans) --
     def label_scans(self, scans, T_body2origin, T_lidar2body=None, static_map=None, raw_map=None, tau=None, voxelsize=0.2, split=None):

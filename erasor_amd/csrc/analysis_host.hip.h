@@ -1,8 +1,8 @@
 // The offline analyses' host code: PR / RR evaluation (one estimate, many, by class), the overlap report, the frame check, the scans'
-// labels, the clustering, the k nearest neighbours and density filters, the normals, the point-to-plane refinement, the see-through check, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
+// labels, the clustering, the k nearest neighbours and density filters, the normals, the point-to-plane refinement, the see-through check, the carving of free space, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
 // at its end -- one translation unit, like the kernel headers -- so it sees the handle, ensure / LAUNCH / HIPC, scan_u32, radix_sort,
 // map_to_device and voxelize_device from there; nothing of the step path depends on this file.  Kernels: evaluate.hip.h, nearest.hip.h,
-// align.hip.h, label_scans.hip.h, cluster.hip.h, knn.hip.h, normals.hip.h, refine_plane.hip.h, visibility.hip.h, render.hip.h.
+// align.hip.h, label_scans.hip.h, cluster.hip.h, knn.hip.h, normals.hip.h, refine_plane.hip.h, visibility.hip.h, carve.hip.h, render.hip.h.
 #pragma once
 
 extern "C" {
@@ -2179,6 +2179,206 @@ int erasor_hip_visibility_map(erasor_hip_handle *h, const void *scans_xyzi, size
     if ((rc = map_on_device(h, who, h->ev.map, &m, &n_map)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q))) return rc;
     return vs_run(h, who, m, n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, *params, votes, keep_mask, kept_xyzi,
                   cap_points, rows, res);
+}
+
+// ---- carving free space: every scan's rays walked through the map's voxels (kernels: carve.hip.h) ----
+// Like vs_run: the main stream, the evaluator's scratch.  The block table is built once a call (claim, slots, scan, base) and its
+// counters read (the refusal of a map point out of the cell range comes before any ray is walked); then the frames go in batches of at
+// most CV_BATCH in index order, one k_cv_walk over the batch's scan points and one k_cv_integrate over the voxels each; at the end
+// k_cv_gather, one round trip for the counters, and the outputs asked for.
+
+static int cv_check_args(erasor_hip_handle *h, const char *who, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                         const float *T_lidar2body, const float *T_body2origin, const erasor_carve *p) {
+    if (!p) return invalid(h, who, "params is NULL");
+    if (!std::isfinite(p->voxel) || !(p->voxel > 0)) return invalid(h, who, "voxel must be a finite number > 0");
+    if (!std::isfinite(p->min_range) || !std::isfinite(p->max_range) || !(p->min_range >= 0) || !(p->min_range < p->max_range))
+        return invalid(h, who, "0 <= min_range < max_range, both finite");
+    if (p->max_range / p->voxel > (double)ERASOR_CARVE_MAX_CELLS) return invalid(h, who, "max_range / voxel must not exceed 4096");
+    const float lg[6] = {p->l_init, p->l_hit, p->l_miss, p->l_min, p->l_max, p->l_thr};
+    if (!all_finite(lg, 6) || !(p->l_hit >= 0) || !(p->l_miss <= 0) || !(p->l_min <= p->l_init) || !(p->l_init <= p->l_max))
+        return invalid(h, who, "the log-odds must be finite, l_hit >= 0, l_miss <= 0 and l_min <= l_init <= l_max");
+    if (p->stop_short > ERASOR_CARVE_MAX_STOP_SHORT) return invalid(h, who, "stop_short must be within 0 .. 64");
+    if (n_frames > ERASOR_CARVE_MAX_FRAMES) return invalid(h, who, "more than 65535 frames");
+    if (!offsets) return invalid(h, who, "offsets is NULL (n_frames + 1 entries)");
+    if (n_frames && !T_body2origin) return invalid(h, who, "T_body2origin is NULL");
+    const int rc = check_scan_offsets(h, who, scans_xyzi, n_scan_points, offsets, n_frames);
+    if (rc) return rc;
+    if (T_lidar2body && !all_finite(T_lidar2body, 16)) return invalid(h, who, "non-finite entry in T_lidar2body");
+    if (!all_finite(T_body2origin, n_frames * 16)) return invalid(h, who, "non-finite entry in T_body2origin");
+    return ERASOR_OK;
+}
+
+// a frame's forward matrix and the cell of its origin: evalmap._carve_frames, the same operations in the same order.  0: fine; 1: not
+// finite; 2: the origin's cell reaches 2^28
+static int cv_frame(const float *A, const float *B, double voxel, CvFrame *F) {
+    VisFrame V;
+    if (!vs_frame(A, B, &V)) return 1;  // (M and its inverse, as evalmap.visibility_transforms refuses them)
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 4; ++j) {
+            const double v = ((double)A[4 * i + 0] * (double)B[0 + j] + (double)A[4 * i + 1] * (double)B[4 + j]) + (double)A[4 * i + 2] * (double)B[8 + j];
+            F->m[4 * i + j] = j == 3 ? v + (double)A[4 * i + 3] : v;
+        }
+        const double c = floor(F->m[4 * i + 3] / voxel);
+        if (!(fabs(c) < CV_CELL_LIMIT)) return 2;
+        F->c0[i] = (int32_t)c;
+    }
+    F->pad = 0;
+    return 0;
+}
+
+static int cv_run(erasor_hip_handle *h, const char *who, const float4 *map, uint32_t n_map, const float4 *scans, uint32_t n, const uint64_t *offsets,
+                  uint32_t n_frames, const float *T_lidar2body, const float *T_body2origin, const erasor_carve &prm, uint16_t *votes, float *logodds,
+                  uint8_t *keep_mask, float *kept_xyzi, size_t cap_points, erasor_carve_row *rows, erasor_carve_result *res) {
+    auto &E = h->ev;
+    const uint32_t nf = std::max(n_frames, 1u);
+    const CvParams P{prm.voxel, prm.min_range, prm.max_range, prm.l_init, prm.l_hit, prm.l_miss, prm.l_min, prm.l_max, prm.l_thr, prm.stop_short, 0u};
+    // the frames: matrices and origin cells (refused before anything runs), offsets, every walk workgroup's first frame
+    std::vector<CvFrame> fr(nf);
+    const float *Tl = T_lidar2body ? T_lidar2body : AL_IDENTITY;
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const int bad = cv_frame(T_body2origin + 16 * (size_t)f, Tl, prm.voxel, &fr[f]);
+        if (bad == 1) return invalid(h, who, "non-finite transform of frame " + std::to_string(f));
+        if (bad) return invalid(h, who, "the origin of frame " + std::to_string(f) + " lies in a cell whose coordinate reaches 2^28");
+    }
+    const uint32_t grid_all = cdiv(n, 256);
+    std::vector<uint32_t> off(n_frames + 1), wg(grid_all + 1);
+    for (uint32_t f = 0; f <= n_frames; ++f) off[f] = (uint32_t)offsets[f];
+    for (uint32_t b = 0, f = 0; b < grid_all; ++b) {  // the largest f < n_frames with off[f] <= b * 256 (as vs_run)
+        while (f + 1 < n_frames && off[f + 1] <= b * 256u) ++f;
+        wg[b] = f;
+    }
+    wg[grid_all] = n_frames ? n_frames - 1 : 0;
+    // the table: a power of two of at least twice the point count
+    uint64_t cap = 64;
+    while (cap < 2 * (uint64_t)n_map) cap <<= 1;
+    const uint32_t capmask = (uint32_t)(cap - 1);
+    const size_t n1 = (size_t)n_map + 1, nctr = (size_t)nf * CV_NCTR + CG_NCTR;
+    if (ensure(h, E.al_off, (size_t)nf + 1) || ensure(h, E.al_wg, (size_t)grid_all + 1) || ensure(h, E.cv_frames, nf) || ensure(h, E.cv_tab, cap) ||
+        ensure(h, E.cv_cnt, cap + 1) || ensure(h, E.cv_pl, cap + 1) || ensure(h, E.cv_tops, cap / 1024 + 4) || ensure(h, E.cv_slot, n1) ||
+        ensure(h, E.cv_hm, n1) || ensure(h, E.cv_wfree, n1) || ensure(h, E.cv_whit, n1) || ensure(h, E.cv_votes, n1) || ensure(h, E.cv_L, n1) ||
+        ensure(h, E.cv_lo, n1) || ensure(h, E.cv_ctr, nctr + 1) || ensure(h, E.fm_flag, n1) || ensure(h, E.fm_pl, n1) ||
+        ensure(h, E.fm_tops, n_map / 1024 + 4) || ensure(h, E.kn_mask, n1))
+        return ERASOR_E_NO_DEVICE;
+    unsigned long long *const gctr = E.cv_ctr.p + (size_t)nf * CV_NCTR;  // the call's counters, behind the frames'
+    uint32_t *const d_nvox = (uint32_t *)(E.cv_ctr.p + nctr);           // the number of map voxels (the scan's total)
+    HIPC(h, hipMemcpyAsync(E.al_off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(E.al_wg.p, wg.data(), wg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(E.cv_frames.p, fr.data(), (size_t)nf * sizeof(CvFrame), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemsetAsync(E.cv_ctr.p, 0, (nctr + 1) * sizeof(unsigned long long), h->stream));
+    HIPC(h, hipMemsetAsync(E.cv_tab.p, 0, cap * sizeof(CvBlock), h->stream));
+    HIPC(h, hipMemsetAsync(E.cv_hm.p, 0, n1 * sizeof(uint32_t), h->stream));
+    HIPC(h, hipMemsetAsync(E.cv_wfree.p, 0, n1 * sizeof(uint32_t), h->stream));
+    HIPC(h, hipMemsetAsync(E.cv_whit.p, 0, n1 * sizeof(uint32_t), h->stream));
+    const uint32_t gm = cdiv(n_map, 256), gc = cdiv(cap, 256);
+    if (n_map) {
+        LAUNCH(h, h->stream, "cv_claim", k_cv_claim, gm, 256, map, n_map, prm.voxel, E.cv_tab.p, capmask, E.cv_slot.p, gctr);
+        LAUNCH(h, h->stream, "cv_slots", k_cv_slots, std::min(gc, CV_SLOTS_GRID), 256, map, prm.voxel, E.cv_tab.p, capmask, E.cv_cnt.p, gctr);
+        scan_u32(h, h->stream, E.cv_cnt.p, E.cv_pl.p, E.cv_tops.p, (uint32_t)cap, (uint32_t)cap, nullptr, d_nvox, "cv_scan");
+        LAUNCH(h, h->stream, "cv_base", k_cv_base, gc, 256, E.cv_tab.p, capmask, (const uint32_t *)E.cv_pl.p, (const uint32_t *)E.cv_tops.p);
+        LAUNCH(h, h->stream, "cv_fill", k_cv_fill, gm, 256, E.cv_L.p, n_map, prm.l_init);
+    }
+    int rc;
+    unsigned long long g0[CG_NCTR + 1];
+    if ((rc = d2h(h, g0, gctr, sizeof(g0)))) return rc;
+    if (g0[CG_C_BAD_CELL]) return invalid(h, who, std::to_string(g0[CG_C_BAD_CELL]) + " map point(s) lie in a cell whose coordinate reaches 2^28");
+    const uint32_t n_voxels = (uint32_t)(g0[CG_NCTR] & 0xFFFFFFFFull);  // (the low word of the last counter: d_nvox)
+    const uint32_t gv = cdiv(n_voxels, 256);
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += CV_BATCH) {
+        const uint32_t f1 = std::min(n_frames, f0 + CV_BATCH), lo = off[f0], hi = off[f1];
+        if (hi > lo) {
+            const uint32_t b0 = lo / 256u, b1 = cdiv(hi, 256);
+            LAUNCH(h, h->stream, "cv_walk", k_cv_walk, b1 - b0, 256, scans, lo, hi, b0, (const uint32_t *)E.al_off.p, (const uint32_t *)E.al_wg.p, f0, f1, P,
+                   (const CvFrame *)E.cv_frames.p, (const CvBlock *)E.cv_tab.p, capmask, E.cv_wfree.p, E.cv_whit.p, E.cv_ctr.p);
+            if (n_voxels)
+                LAUNCH(h, h->stream, "cv_integrate", k_cv_integrate, gv, 256, n_voxels, f0, f1 - f0, P, E.cv_L.p, E.cv_hm.p, E.cv_wfree.p, E.cv_whit.p, E.cv_ctr.p,
+                       gctr);
+        }
+    }
+    if (n_map)
+        LAUNCH(h, h->stream, "cv_gather", k_cv_gather, gm, 256, map, n_map, (const uint32_t *)E.cv_slot.p, (const CvBlock *)E.cv_tab.p, P, (const float *)E.cv_L.p,
+               (const uint32_t *)E.cv_hm.p, E.cv_votes.p, E.cv_lo.p, E.fm_flag.p, E.kn_mask.p, gctr);
+    std::vector<unsigned long long> c(nctr);
+    if ((rc = d2h(h, c.data(), E.cv_ctr.p, c.size() * sizeof(unsigned long long)))) return rc;
+    erasor_carve_result r;
+    memset(&r, 0, sizeof(r));
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const unsigned long long *cf = &c[(size_t)f * CV_NCTR];
+        erasor_carve_row row;
+        row.n_points = off[f + 1] - off[f];
+        row.n_non_finite = cf[CV_C_NON_FINITE];
+        row.n_out_of_range = cf[CV_C_RANGE];
+        row.n_rays = cf[CV_C_RAYS];
+        row.n_steps = cf[CV_C_STEPS];
+        row.n_end_in_map = cf[CV_C_END];
+        row.n_voxels_hit = cf[CV_C_VHIT];
+        row.n_voxels_free = cf[CV_C_VFREE];
+        if (rows) rows[f] = row;
+        r.n_scan_points += row.n_points;
+        r.n_non_finite += row.n_non_finite;
+        r.n_out_of_range += row.n_out_of_range;
+        r.n_rays += row.n_rays;
+        r.n_steps += row.n_steps;
+        r.n_end_in_map += row.n_end_in_map;
+        r.n_voxels_hit += row.n_voxels_hit;
+        r.n_voxels_free += row.n_voxels_free;
+    }
+    const unsigned long long *cg = &c[(size_t)nf * CV_NCTR];
+    r.n_points = n_map;
+    r.n_map_non_finite = cg[CG_C_NON_FINITE];
+    r.n_voxels = n_voxels;
+    r.n_blocks = cg[CG_C_BLOCKS];
+    r.n_voxels_touched = cg[CG_C_TOUCHED];
+    r.n_removed_dynamic = cg[CG_C_REMOVED_DYNAMIC];
+    r.n_removed_static = cg[CG_C_REMOVED_STATIC];
+    r.n_removed = r.n_removed_dynamic + r.n_removed_static;
+    r.n_kept = n_map - r.n_removed;
+    if (res) *res = r;
+    if (votes && (rc = d2h(h, votes, E.cv_votes.p, (size_t)n_map * sizeof(uint32_t)))) return rc;
+    if (logodds && (rc = d2h(h, logodds, E.cv_lo.p, (size_t)n_map * sizeof(float)))) return rc;
+    if (keep_mask && (rc = d2h(h, keep_mask, E.kn_mask.p, n_map))) return rc;
+    if (kept_xyzi && r.n_kept > cap_points) return ERASOR_E_CAPACITY;
+    if (kept_xyzi && r.n_kept) {
+        // the kept rows, as given: the stable compaction over the keep flags (vs_run's)
+        if (ensure(h, E.fm_out, n1)) return ERASOR_E_NO_DEVICE;
+        scan_u32(h, h->stream, E.fm_flag.p, E.fm_pl.p, E.fm_tops.p, n_map, n_map, nullptr, nullptr, "cv_keep");
+        LAUNCH(h, h->stream, "cv_keep", k_f_compact, gm, 256, map, n_map, (const uint32_t *)E.fm_flag.p, (const uint32_t *)E.fm_pl.p,
+               (const uint32_t *)E.fm_tops.p, E.fm_out.p);
+        return d2h(h, kept_xyzi, E.fm_out.p, (size_t)r.n_kept * sizeof(float4));
+    }
+    return ERASOR_OK;
+}
+
+int erasor_hip_carve_clouds(erasor_hip_handle *h, const void *map_xyzi, size_t n_map, int map_is_device, const void *scans_xyzi, size_t n_scan_points,
+                            const uint64_t *offsets, size_t n_frames, int scans_are_device, const float T_lidar2body[16], const float *T_body2origin,
+                            const erasor_carve *params, uint16_t *votes, float *logodds, uint8_t *keep_mask, float *kept_xyzi, size_t cap_points,
+                            erasor_carve_row *rows, erasor_carve_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_carve_clouds";
+    int rc = cv_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, params);
+    if (rc || (rc = check_cloud(h, who, "NULL map or more than 2^30 map points", map_xyzi, n_map))) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr, *q = nullptr;
+    if ((rc = ev_input(h, map_xyzi, n_map, map_is_device, h->ev.gt, &m)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q)))
+        return rc;
+    return cv_run(h, who, m, (uint32_t)n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, *params, votes, logodds,
+                  keep_mask, kept_xyzi, cap_points, rows, res);
+}
+
+int erasor_hip_carve_map(erasor_hip_handle *h, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames, int scans_are_device,
+                         const float T_lidar2body[16], const float *T_body2origin, const erasor_carve *params, uint16_t *votes, float *logodds,
+                         uint8_t *keep_mask, float *kept_xyzi, size_t cap_points, erasor_carve_row *rows, erasor_carve_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_carve_map";
+    int rc = cv_check_args(h, who, scans_xyzi, n_scan_points, offsets, n_frames, T_lidar2body, T_body2origin, params);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr, *q = nullptr;
+    uint32_t n_map = 0;
+    if ((rc = map_on_device(h, who, h->ev.map, &m, &n_map)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q))) return rc;
+    return cv_run(h, who, m, n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, *params, votes, logodds, keep_mask,
+                  kept_xyzi, cap_points, rows, res);
 }
 
 // ---- label_map (fill_removert_intensity.cpp:24-59, compare_map.cpp:77-110) and calc_complement (compare_complement.cpp:43-75): the

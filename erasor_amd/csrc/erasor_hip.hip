@@ -46,6 +46,7 @@
 #include "normals.hip.h"
 #include "refine_plane.hip.h"
 #include "visibility.hip.h"
+#include "carve.hip.h"
 #include "render.hip.h"
 
 using namespace ek;
@@ -412,6 +413,14 @@ struct erasor_hip_handle {
         DBuf<uint32_t> vs_img;
         DBuf<VisVote> vs_votes;
         DBuf<unsigned long long> vs_ctr;
+        // carving free space (erasor_hip_carve_*): the frames, the block table with its counts and their scan, every map point's slot,
+        // the voxels' log-odds, votes and two words of frame bits, the points' votes and log-odds, the per-frame counters with the
+        // call's behind them (offsets and workgroup frames: al_off, al_wg; flags, mask and kept cloud: fm_*, kn_mask)
+        DBuf<CvFrame> cv_frames;
+        DBuf<CvBlock> cv_tab;
+        DBuf<uint32_t> cv_cnt, cv_pl, cv_tops, cv_slot, cv_hm, cv_wfree, cv_whit, cv_votes;
+        DBuf<float> cv_L, cv_lo;
+        DBuf<unsigned long long> cv_ctr;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
 #ifdef ERASOR_HIP_TEST_HOOKS
@@ -1271,6 +1280,9 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->ev.kn_nd); release(h->ev.kn_mask);
     release(h->ev.nm_curv); release(h->ev.nm_ctr); release(h->ev.nm_nrm); release(h->ev.nm_eig);
     release(h->ev.vs_frames); release(h->ev.vs_tab); release(h->ev.vs_img); release(h->ev.vs_votes); release(h->ev.vs_ctr);
+    release(h->ev.cv_frames); release(h->ev.cv_tab); release(h->ev.cv_cnt); release(h->ev.cv_pl); release(h->ev.cv_tops); release(h->ev.cv_slot);
+    release(h->ev.cv_hm); release(h->ev.cv_wfree); release(h->ev.cv_whit); release(h->ev.cv_votes); release(h->ev.cv_L); release(h->ev.cv_lo);
+    release(h->ev.cv_ctr);
     for (int k = 0; k < NSIDE; ++k) {
         if (h->q[k].ev_keys) (void)hipEventDestroy(h->q[k].ev_keys);
         if (h->q[k].ev_done) (void)hipEventDestroy(h->q[k].ev_done);

@@ -1230,6 +1230,111 @@ static int visibility_mode(int argc, char **argv) {
     return 0;
 }
 
+// --carve <rosparam.yaml> <map.pcd|-> <out.pcd> [n_frames] [voxel] [max_range] [stop_short]: free space carved out of a map, OctoMap's
+// way (erasor_hip_carve_clouds): the map goes into voxels of `voxel` metres (0.2), every ray of every scan is walked through them up to
+// max_range (80 m; from 0.5 m), a voxel that rays pass through is free and one that rays end in is occupied, the frames are integrated as
+// clamped log-odds, and the points of the voxels that end below the threshold leave.  The same files and poses as --visibility.  The
+// log-odds are OctoMap's defaults, evalmap.carve_logodds' expression with C's log: (float)log(p / (1 - p)) of 0.7 (hit), 0.4 (miss),
+// 0.12 and 0.97 (the clamps) and 0.5 (the threshold), from 0.  One line per frame, the result, and the kept cloud as a binary PCD -- which
+// --eval scores against a ground truth like any other map.
+static int carve_mode(int argc, char **argv) {
+    if (argc < 5 || argc > 9) return 2;
+    size_t max_frames = (size_t)1 << 30, stop_short = 0;
+    double voxel = 0.2, max_range = 80.0;
+    const double min_range = 0.5;
+    if ((argc > 5 && !parse_count(argv[5], &max_frames)) || (argc > 6 && !parse_number(argv[6], &voxel)) || (argc > 7 && !parse_number(argv[7], &max_range)) ||
+        (argc > 8 && !parse_count(argv[8], &stop_short)))
+        return 2;
+    if (!(voxel > 0) || !std::isfinite(voxel) || !(max_range > min_range) || !std::isfinite(max_range) || max_range / voxel > (double)ERASOR_CARVE_MAX_CELLS ||
+        stop_short > ERASOR_CARVE_MAX_STOP_SHORT)
+        return 2;
+    erasor::OfflineMapUpdater::Config cfg;
+    erasor_hip_params_default(&cfg.params);
+    erasor::DriverConfig drv;
+    if (!erasor::load_config_yaml(argv[2], cfg, &drv)) {
+        fprintf(stderr, "cannot read %s\n", argv[2]);
+        return 3;
+    }
+    if (cfg.initial_map_path.empty() || cfg.initial_map_path == "/") cfg.initial_map_path = drv.data_dir + "/dense_global_map.pcd";
+    const std::string map_path = std::string(argv[3]) == "-" ? cfg.initial_map_path : std::string(argv[3]);
+    std::vector<Eigen::Matrix4f> poses;
+    if (!erasor::load_all_poses(drv.data_dir + "/poses_lidar2body.csv", poses)) {
+        fprintf(stderr, "cannot read %s/poses_lidar2body.csv\n", drv.data_dir.c_str());
+        return 3;
+    }
+    std::vector<float> map, scans, Tb;
+    if (!load_cloud_xyzi(map_path, map)) {
+        fprintf(stderr, "cannot read %s\n", map_path.c_str());
+        return 3;
+    }
+    std::vector<uint64_t> offsets{0};
+    const int last = (int)std::min<size_t>(poses.size(), (size_t)drv.init_idx + max_frames);
+    for (int i = drv.init_idx; i < last; ++i) {
+        char name[64];
+        snprintf(name, sizeof(name), "/pcds/%06d.pcd", i);
+        std::vector<float> scan;
+        if (!load_cloud_xyzi(drv.data_dir + name, scan)) {
+            fprintf(stderr, "cannot read %s%s\n", drv.data_dir.c_str(), name);
+            return 3;
+        }
+        scans.insert(scans.end(), scan.begin(), scan.end());
+        offsets.push_back(scans.size() / 4);
+        const Eigen::Matrix4f T = erasor_utils::geoPose2eigen(erasor_utils::eigen2geoPose(poses[i]));  // (callback_node's round trip)
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) Tb.push_back(T(r, c));
+    }
+    geometry_msgs::Pose l2b;
+    l2b.position.x = cfg.lidar2body[0];
+    l2b.position.y = cfg.lidar2body[1];
+    l2b.position.z = cfg.lidar2body[2];
+    l2b.orientation.x = cfg.lidar2body[3];
+    l2b.orientation.y = cfg.lidar2body[4];
+    l2b.orientation.z = cfg.lidar2body[5];
+    l2b.orientation.w = cfg.lidar2body[6];
+    const Eigen::Matrix4f TL = erasor_utils::geoPose2eigen(l2b);  // (OMU.cpp:100)
+    float Tl[16];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) Tl[4 * r + c] = TL(r, c);
+    auto logodds = [](double p) { return (float)log(p / (1.0 - p)); };  // evalmap.carve_logodds' expression
+    erasor_carve prm;
+    memset(&prm, 0, sizeof(prm));
+    prm.voxel = voxel, prm.min_range = min_range, prm.max_range = max_range, prm.stop_short = (uint32_t)stop_short;
+    prm.l_init = 0.f, prm.l_hit = logodds(0.7), prm.l_miss = logodds(0.4), prm.l_min = logodds(0.12), prm.l_max = logodds(0.97), prm.l_thr = logodds(0.5);
+    erasor_hip_handle *h = render_handle();
+    if (!h) return 1;
+    const size_t n = map.size() / 4, n_frames = offsets.size() - 1;
+    std::vector<float> kept(std::max<size_t>(n, 1) * 4, 0.f);
+    std::vector<erasor_carve_row> rows(std::max<size_t>(n_frames, 1));
+    erasor_carve_result r;
+    const int rc = erasor_hip_carve_clouds(h, map.data(), n, 0, scans.data(), scans.size() / 4, offsets.data(), n_frames, 0, Tl, Tb.data(), &prm, nullptr, nullptr,
+                                           nullptr, kept.data(), n, rows.data(), &r);
+    if (rc) return render_fail(h, "carve", rc);
+    erasor_hip_destroy(h);
+    typedef unsigned long long ull;
+    printf("%zu frames against %s (%zu points), voxel %.9g, range %.9g .. %.9g, stop_short %zu:\n", n_frames, map_path.c_str(), n, voxel, min_range, max_range,
+           stop_short);
+    for (size_t f = 0; f < n_frames; ++f) {
+        const erasor_carve_row &w = rows[f];
+        printf("%6d  n=%llu  dropped %llu non-finite, %llu out of range  rays %llu  steps %llu  ends in the map %llu  voxels hit %llu, free %llu\n",
+               drv.init_idx + (int)f, (ull)w.n_points, (ull)w.n_non_finite, (ull)w.n_out_of_range, (ull)w.n_rays, (ull)w.n_steps, (ull)w.n_end_in_map,
+               (ull)w.n_voxels_hit, (ull)w.n_voxels_free);
+    }
+    printf("carve: n=%llu  non-finite=%llu  voxels=%llu in %llu blocks, touched %llu  kept=%llu  removed=%llu (dynamic %llu, static %llu)\n", (ull)r.n_points,
+           (ull)r.n_map_non_finite, (ull)r.n_voxels, (ull)r.n_blocks, (ull)r.n_voxels_touched, (ull)r.n_kept, (ull)r.n_removed, (ull)r.n_removed_dynamic,
+           (ull)r.n_removed_static);
+    printf("  rays: %llu of %llu points (dropped %llu non-finite, %llu out of range)  steps %llu  ends in the map %llu  voxel hits %llu, misses %llu\n",
+           (ull)r.n_rays, (ull)r.n_scan_points, (ull)r.n_non_finite, (ull)r.n_out_of_range, (ull)r.n_steps, (ull)r.n_end_in_map, (ull)r.n_voxels_hit,
+           (ull)r.n_voxels_free);
+    pcl::PointCloud<pcl::PointXYZI> out;
+    rows_to_cloud(kept, r.n_kept, out);
+    if (erasor_utils::save_pcd_binary(argv[4], out) != 0) {
+        fprintf(stderr, "cannot write %s\n", argv[4]);
+        return 1;
+    }
+    printf("saved %s\n", argv[4]);
+    return 0;
+}
+
 // --refine <rosparam.yaml> <poses_out> [n_frames] [max_dist = 1.0] [max_iters = 20]: what to do about the frames --align flags.  The same
 // files and poses as --align (data_dir, init_idx, poses_lidar2body.csv after callback_node's round trip, the initial map, tf/lidar2body);
 // every frame's T_body2origin is refined against the initial map by point-to-point ICP (erasor_hip_refine_poses_clouds).  One line per
@@ -1938,6 +2043,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && std::string(argv[1]) == "--carve") {
+        try {
+            return carve_mode(argc, argv);
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--label-scans") {
         try {
             return label_scans_mode(argc, argv);
@@ -2018,9 +2131,10 @@ int main(int argc, char **argv) {
                 "       %s --denoise <in.pcd> <out.pcd> sor <k> <mul> | ror <radius> <min_neighbors> | kth <k> <thr>\n"
                 "       %s --density <cloud.pcd> <k>\n"
                 "       %s --normals <in.pcd> <out.pcd> <k> [vx vy vz]\n"
-                "       %s --visibility <rosparam.yaml> <map.pcd|-> <out.pcd> [n_frames] [W H el_bottom el_top] [window] [k]\n",
+                "       %s --visibility <rosparam.yaml> <map.pcd|-> <out.pcd> [n_frames] [W H el_bottom el_top] [window] [k]\n"
+                "       %s --carve <rosparam.yaml> <map.pcd|-> <out.pcd> [n_frames] [voxel] [max_range] [stop_short]\n",
                 argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0],
-                argv[0]);
+                argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

@@ -32,6 +32,9 @@ restatement of Erasor.normals.
 
 visibility / visibility_brute (and visibility_grid, visibility_column, visibility_transforms, visibility_decide): the see-through check,
 map points voted out by every scan's range image -- the normative text of Erasor.visibility.
+
+carve / carve_brute (and carve_walk, carve_logodds): free space carved out of a map, every scan's rays walked through the map's voxels and
+the voxels' clamped log-odds integrated, OctoMap's way -- the normative text of Erasor.carve.
 """
 import numpy as np
 from scipy.spatial import cKDTree
@@ -1901,3 +1904,331 @@ def visibility_brute(map_xyzi, scans, T_body2origin, T_lidar2body=None, grid=Non
                                                      tally[VIS_NO_RETURN], tally[VIS_THROUGH], tally[VIS_GRAZING]])))
     n_no_normal = int(np.isnan(nrm[:, 0]).sum()) if k else 0
     return _vis_finish(c, votes, rows, n_no_normal, min_through, hit_weight, keep)
+
+
+# ---- carving free space: every scan's rays walked through the map's voxels, the voxels' log-odds integrated (include/erasor_hip.h:
+# erasor_hip_carve_*; kernels: erasor_amd/csrc/carve.hip.h), on the host ----------------------------------------------------------
+# The normative text of the contract; the device equals it byte for byte.  OctoMap's and Peopleremover's argument (the reference's
+# compare_results.launch, compare_map.cpp, analysis_octomap.py): the map goes into a voxel grid, every ray of every scan is walked
+# through it, a voxel that rays pass through is free, one that rays end in is occupied, and the two are integrated as clamped log-odds.
+#
+# Coordinates are float64 on the float32 inputs.  Every operation is a separate IEEE operation in the order written.  Only + - * /,
+# sqrt, floor and comparisons are used.  The log-odds are float32.
+#
+# Voxels.
+#   - A finite point lies in cell c = floor(x / voxel) per axis.
+#   - A map point with a non-finite coordinate lies in no voxel.  It is kept, gets zero votes and log-odds l_init, and is counted as
+#     n_map_non_finite.
+#   - The map voxels are the cells that hold at least one finite map point.  Only they carry state.
+# Rays.
+#   - The forward matrix of frame f is the M of visibility_transforms: T_body2origin[f] . T_lidar2body, upper three rows, float32
+#     entries widened.
+#   - The ray's origin o is M's column 3.
+#   - A scan point (x, y, z) in the lidar frame has rho = sqrt((x x + y y) + z z).
+#   - The gates, in this order: a non-finite coordinate, then rho outside [min_range, max_range].  Both are dropped and counted per
+#     frame.
+#   - The end point is e_i = ((M[i][0] x + M[i][1] y) + M[i][2] z) + M[i][3].
+#   - Under a rigid M the end lies within max_range of the origin, so at most 4097 cells away per axis.  A ray whose end cell is not
+#     within 4098 cells of the origin's cell on every axis (a matrix that stretches, or an end that is not finite) is dropped and
+#     counted as out of range: this keeps every walk below 3 * 4098 steps whatever the matrix.
+# Traversal.
+#   - c0 = cell(o), c1 = cell(e), n_a = |c1_a - c0_a|, step_a = +-1, N = n_x + n_y + n_z.
+#   - For an axis with n_a > 0: d_a = e_a - o_a; tMax_a = ((c0_a + (step_a > 0 ? 1 : 0)) * voxel - o_a) / d_a; tDelta_a = voxel / |d_a|.
+#   - An axis with no steps left never moves.
+#   - Each of the N steps moves the axis with the smallest tMax among the axes that still have steps left.  Ties go to x before y
+#     before z.
+#   - After the move, c_a += step_a, the steps left on that axis drop by one, and tMax_a += tDelta_a.
+#   - So the walk visits V_0 = c0 ... V_N = c1, and always ends in c1 whatever the rounding.
+#   - Free evidence: V_i for 0 <= i <= N - 1 - stop_short.
+#   - Hit evidence: V_N.
+#   - n_steps of a ray is max(0, N - stop_short).
+# One update per voxel and scan, hits first (OctoMap's insertPointCloud rule).
+#   - In frame f a map voxel is hit if any ray of f ends in it.
+#   - Otherwise it is free if any ray of f has it as free evidence.
+#   - Otherwise it is untouched.
+# Integration, per map voxel, frames in index order.
+#   - L starts at l_init.
+#   - A hit frame: L = min(L + l_hit, l_max), and hits += 1.
+#   - A free frame: L = max(L + l_miss, l_min), and misses += 1.
+#   - Everything is float32.
+#   - The log-odds are parameters.  No kernel calls log.
+# Decision.  A map point is removed iff its voxel's L < l_thr.  Every point of a voxel shares its voxel's fate.
+CARVE_MAX_FRAMES = 65535
+CARVE_MAX_CELLS = 4096      # max_range / voxel
+CARVE_MAX_REACH = 4098      # cells between a ray's origin and its end, per axis
+CARVE_MAX_STOP_SHORT = 64
+CARVE_CELL_LIMIT = 1 << 28  # a finite map point's or a frame origin's cell coordinate stays inside +- this
+CARVE_ROW_FIELDS = ("n_points", "n_non_finite", "n_out_of_range", "n_rays", "n_steps", "n_end_in_map", "n_voxels_hit", "n_voxels_free")
+CARVE_RESULT_FIELDS = ("n_points", "n_map_non_finite", "n_voxels", "n_blocks", "n_voxels_touched", "n_kept", "n_removed", "n_removed_dynamic",
+                       "n_removed_static", "n_scan_points", "n_non_finite", "n_out_of_range", "n_rays", "n_steps", "n_end_in_map", "n_voxels_hit",
+                       "n_voxels_free")
+CARVE_LOGODDS_FIELDS = ("l_init", "l_hit", "l_miss", "l_min", "l_max", "l_thr")
+
+
+def carve_logodds(p_hit=0.7, p_miss=0.4, p_min=0.12, p_max=0.97, p_thr=0.5):
+    """OctoMap's log-odds from its probabilities, float32(log(p / (1 - p))) each, and l_init = 0 (its prior of one half): the defaults
+    are OctoMap's own.  The driver forms them by the same expression with C's log."""
+    import math
+    lo = lambda p: float(np.float32(math.log(float(p) / (1.0 - float(p)))))
+    return {"l_init": 0.0, "l_hit": lo(p_hit), "l_miss": lo(p_miss), "l_min": lo(p_min), "l_max": lo(p_max), "l_thr": lo(p_thr)}
+
+
+def _carve_args(map_xyzi, scans, voxel, min_range, max_range, stop_short, logodds):
+    lg = carve_logodds() if logodds is None else {k: float(np.float32(logodds[k])) for k in CARVE_LOGODDS_FIELDS}
+    voxel, min_range, max_range = float(voxel), float(min_range), float(max_range)
+    if not (np.isfinite(voxel) and voxel > 0):
+        raise ValueError("carve: voxel must be a finite number > 0")
+    if not (np.isfinite(min_range) and np.isfinite(max_range) and 0 <= min_range < max_range):
+        raise ValueError("carve: 0 <= min_range < max_range, both finite")
+    if max_range / voxel > CARVE_MAX_CELLS:
+        raise ValueError("carve: max_range / voxel must not exceed 4096")
+    if not (all(np.isfinite(lg[k]) for k in CARVE_LOGODDS_FIELDS) and lg["l_hit"] >= 0 and lg["l_miss"] <= 0 and lg["l_min"] <= lg["l_init"] <= lg["l_max"]):
+        raise ValueError("carve: the log-odds must be finite, l_hit >= 0, l_miss <= 0 and l_min <= l_init <= l_max")
+    if not 0 <= int(stop_short) <= CARVE_MAX_STOP_SHORT:
+        raise ValueError("carve: stop_short must be within 0 .. 64")
+    if len(scans) > CARVE_MAX_FRAMES:
+        raise ValueError("carve: more than 65535 frames")
+    c = np.ascontiguousarray(np.asarray(map_xyzi, np.float32).reshape(-1, 4))
+    return c, voxel, min_range, max_range, int(stop_short), {k: np.float32(v) for k, v in lg.items()}
+
+
+def _carve_frames(scans, T_body2origin, T_lidar2body, voxel):
+    """every frame's forward matrix M [n, 3, 4] in float64 (visibility_transforms' M) and its origin's cell"""
+    n = len(scans)
+    A = (np.zeros((0, 4, 4), np.float32) if n == 0 else np.asarray(T_body2origin, np.float32).reshape(-1, 4, 4)).astype(np.float64)
+    if len(A) != n:
+        raise ValueError("carve: one T_body2origin per frame")
+    visibility_transforms(A.astype(np.float32), T_lidar2body)  # (the refusal of a non-finite frame matrix)
+    B = (np.eye(4, dtype=np.float32) if T_lidar2body is None else np.asarray(T_lidar2body, np.float32).reshape(4, 4)).astype(np.float64)
+    M = np.zeros((n, 3, 4))
+    for i in range(3):
+        for j in range(4):
+            v = (A[:, i, 0] * B[0, j] + A[:, i, 1] * B[1, j]) + A[:, i, 2] * B[2, j]
+            M[:, i, j] = v + A[:, i, 3] if j == 3 else v
+    c0 = np.floor(M[:, :, 3] / voxel)
+    if not (np.abs(c0) < CARVE_CELL_LIMIT).all():
+        raise ValueError("carve: a frame origin's cell coordinate reaches 2^28")
+    return M, c0.astype(np.int64)
+
+
+def _carve_map_cells(c, voxel):
+    """(finite [n] bool, cells [n, 3] int64 with zeros where not finite)"""
+    fin = np.isfinite(c[:, :3]).all(1)
+    cells = np.zeros((len(c), 3), np.int64)
+    f = np.floor(c[fin, :3].astype(np.float64) / voxel)
+    if not (np.abs(f) < CARVE_CELL_LIMIT).all():
+        raise ValueError("carve: a map point's cell coordinate reaches 2^28")
+    cells[fin] = f.astype(np.int64)
+    return fin, cells
+
+
+def _carve_rays(scan, M, voxel, min_range, max_range, c0):
+    """the rays of one frame that pass the gates: (n_points, n_non_finite, n_out_of_range, o [3], e [k, 3], c1 [k, 3] int64)"""
+    s = np.asarray(scan, np.float32).reshape(-1, 4)[:, :3]
+    fin = np.isfinite(s).all(1)
+    p = s[fin].astype(np.float64)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    rho = np.sqrt((x * x + y * y) + z * z)
+    ok = (rho >= min_range) & (rho <= max_range)
+    with np.errstate(all="ignore"):
+        e = np.stack([((M[i, 0] * x + M[i, 1] * y) + M[i, 2] * z) + M[i, 3] for i in range(3)], 1)
+        fe = np.floor(e / voxel)
+        ok &= (np.abs(fe - c0.astype(np.float64)) <= CARVE_MAX_REACH).all(1)  # (False for NaN)
+    return len(s), int((~fin).sum()), int((~ok).sum()), M[:, 3].copy(), e[ok], fe[ok].astype(np.int64)
+
+
+class _CarveGrid:
+    """the map voxels: the distinct cells in lexicographic order, looked up through compressed coordinates (no key overflows)"""
+
+    def __init__(self, cells):
+        self.U = np.unique(cells.reshape(-1, 3), axis=0) if len(cells) else np.zeros((0, 3), np.int64)
+        self.n = len(self.U)
+        if self.n:
+            self.ax = [np.unique(self.U[:, a]) for a in range(3)]
+            i = [np.searchsorted(self.ax[a], self.U[:, a]) for a in range(3)]
+            kxy = i[0] * len(self.ax[1]) + i[1]
+            self.uxy = np.unique(kxy)
+            self.keys = np.searchsorted(self.uxy, kxy) * len(self.ax[2]) + i[2]  # (increasing: U is in lexicographic order)
+
+    def find(self, q):
+        """the voxel index of every cell of q [k, 3], or -1"""
+        q = np.asarray(q, np.int64).reshape(-1, 3)
+        if not self.n or not len(q):
+            return np.full(len(q), -1, np.int64)
+        ok = np.ones(len(q), bool)
+        i = []
+        for a in range(3):
+            j = np.minimum(np.searchsorted(self.ax[a], q[:, a]), len(self.ax[a]) - 1)
+            ok &= self.ax[a][j] == q[:, a]
+            i.append(j)
+        kxy = i[0] * len(self.ax[1]) + i[1]
+        j = np.minimum(np.searchsorted(self.uxy, kxy), len(self.uxy) - 1)
+        ok &= self.uxy[j] == kxy
+        key = j * len(self.ax[2]) + i[2]
+        v = np.minimum(np.searchsorted(self.keys, key), self.n - 1)
+        ok &= self.keys[v] == key
+        return np.where(ok, v, -1)
+
+
+def _carve_walk_setup(o, e, c0, c1, voxel):
+    """(step, left, tmax, tdelta) of rays [k]: o [3] or [k, 3], e [k, 3], c0 [3] or [k, 3], c1 [k, 3]"""
+    o = np.broadcast_to(np.asarray(o, np.float64), e.shape)
+    c0 = np.broadcast_to(np.asarray(c0, np.int64), c1.shape)
+    left = np.abs(c1 - c0)
+    step = np.where(c1 > c0, 1, -1).astype(np.int64)
+    with np.errstate(all="ignore"):
+        d = e - o
+        tmax = ((c0 + (step > 0)).astype(np.float64) * voxel - o) / d
+        tdelta = voxel / np.abs(d)
+    return step, left, tmax, tdelta
+
+
+def carve_walk(origin, end, voxel):
+    """One ray's voxel list [N + 1, 3] int64, V_0 = cell(origin) ... V_N = cell(end), by the traversal of the contract (float64 origin
+    and end, as given): for the tests and for looking at one ray."""
+    import math
+    voxel = float(voxel)
+    o, e = [float(v) for v in origin], [float(v) for v in end]
+    c = [int(math.floor(o[a] / voxel)) for a in range(3)]
+    c1 = [int(math.floor(e[a] / voxel)) for a in range(3)]
+    left = [abs(c1[a] - c[a]) for a in range(3)]
+    step = [1 if c1[a] > c[a] else -1 for a in range(3)]
+    tmax, tdelta = [0.0] * 3, [0.0] * 3
+    for a in range(3):
+        if left[a]:
+            d = e[a] - o[a]
+            tmax[a] = (float(c[a] + (1 if step[a] > 0 else 0)) * voxel - o[a]) / d
+            tdelta[a] = voxel / abs(d)
+    out = [tuple(c)]
+    for _ in range(sum(left)):
+        a = -1
+        for b in range(3):
+            if left[b] and (a < 0 or tmax[b] < tmax[a]):
+                a = b
+        c[a] += step[a]
+        left[a] -= 1
+        tmax[a] += tdelta[a]
+        out.append(tuple(c))
+    assert list(out[-1]) == c1
+    return np.array(out, np.int64).reshape(-1, 3)
+
+
+def _carve_finish(c, fin, vox_of, L, hits, misses, n_blocks, rows, lg, keep):
+    n = len(c)
+    votes = np.zeros((n, 2), np.uint16)
+    lo = np.full(n, lg["l_init"], np.float32)
+    votes[fin, 0], votes[fin, 1], lo[fin] = hits[vox_of[fin]], misses[vox_of[fin]], L[vox_of[fin]]
+    rem = fin & (lo < lg["l_thr"])
+    dyn = _decode(c[:, 3])[2]
+    res = {"n_points": n, "n_map_non_finite": int((~fin).sum()), "n_voxels": int(len(L)), "n_blocks": int(n_blocks),
+           "n_voxels_touched": int(((hits.astype(np.int64) + misses) > 0).sum()), "n_kept": int((~rem).sum()), "n_removed": int(rem.sum()),
+           "n_removed_dynamic": int((rem & dyn).sum()), "n_removed_static": int((rem & ~dyn).sum())}
+    for key, src in (("n_scan_points", "n_points"),) + tuple((k, k) for k in CARVE_ROW_FIELDS[1:]):
+        res[key] = int(sum(r[src] for r in rows))
+    return votes, lo, (~rem).astype(np.uint8), (c[~rem].copy() if keep else None), rows, res
+
+
+def carve(map_xyzi, scans, T_body2origin, T_lidar2body=None, voxel=0.2, min_range=0.5, max_range=80.0, stop_short=0, logodds=None, keep=True):
+    """Free space carved out of a map (Erasor.carve): the contract above.  scans: XYZI rows per frame in the lidar frame; logodds: a dict
+    with CARVE_LOGODDS_FIELDS (None: carve_logodds()).  Returns (votes [n, 2] uint16: hits, misses of the point's voxel; logodds [n]
+    float32; mask uint8, 1 = kept; the kept rows in the order given or None; a row per frame with CARVE_ROW_FIELDS; a dict with
+    CARVE_RESULT_FIELDS)."""
+    c, voxel, min_range, max_range, ss, lg = _carve_args(map_xyzi, scans, voxel, min_range, max_range, stop_short, logodds)
+    M, c0s = _carve_frames(scans, T_body2origin, T_lidar2body, voxel)
+    fin, cells = _carve_map_cells(c, voxel)
+    G = _CarveGrid(cells[fin])
+    vox_of = np.zeros(len(c), np.int64)
+    vox_of[fin] = G.find(cells[fin])
+    n_blocks = len(np.unique(G.U >> 2, axis=0)) if G.n else 0
+    L = np.full(G.n, lg["l_init"], np.float32)
+    hits, misses = np.zeros(G.n, np.uint16), np.zeros(G.n, np.uint16)
+    rows = []
+    for f, scan in enumerate(scans):
+        n_pts, n_nf, n_oor, o, e, c1 = _carve_rays(scan, M[f], voxel, min_range, max_range, c0s[f])
+        step, left, tmax, tdelta = _carve_walk_setup(o, e, c0s[f], c1, voxel)
+        N = left.sum(1)
+        vh = G.find(c1)
+        hit = np.zeros(G.n, bool)
+        hit[vh[vh >= 0]] = True
+        free = np.zeros(G.n, bool)
+        last = N - 1 - ss  # the index of a ray's last free voxel
+        cur = np.broadcast_to(c0s[f], c1.shape).copy()
+        live = np.flatnonzero(last >= 0)
+        left, tmax = left.copy(), tmax.copy()
+        i = 0
+        while len(live):
+            v = G.find(cur[live])
+            free[v[v >= 0]] = True
+            live = live[last[live] > i]  # (those still have a step before their next free voxel)
+            tm = np.where(left[live] > 0, tmax[live], np.inf)
+            a = np.argmin(tm, 1)  # (the first of equal minima: x before y before z)
+            cur[live, a] += step[live, a]
+            left[live, a] -= 1
+            tmax[live, a] += tdelta[live, a]
+            i += 1
+        free &= ~hit
+        L[hit] = np.minimum(L[hit] + lg["l_hit"], lg["l_max"])
+        L[free] = np.maximum(L[free] + lg["l_miss"], lg["l_min"])
+        hits[hit] += 1
+        misses[free] += 1
+        rows.append(dict(zip(CARVE_ROW_FIELDS, [n_pts, n_nf, n_oor, len(e), int(np.maximum(N - ss, 0).sum()), int((vh >= 0).sum()), int(hit.sum()),
+                                                int(free.sum())])))
+    return _carve_finish(c, fin, vox_of, L, hits, misses, n_blocks, rows, lg, keep)
+
+
+def carve_brute(map_xyzi, scans, T_body2origin, T_lidar2body=None, voxel=0.2, min_range=0.5, max_range=80.0, stop_short=0, logodds=None, keep=True):
+    """carve() ray by ray in plain Python floats (math.sqrt, math.floor) with dicts for the voxels, for small inputs: the check of the
+    vectorised text"""
+    import math
+    c, voxel, min_range, max_range, ss, lg = _carve_args(map_xyzi, scans, voxel, min_range, max_range, stop_short, logodds)
+    M, c0s = _carve_frames(scans, T_body2origin, T_lidar2body, voxel)
+    fin, cells = _carve_map_cells(c, voxel)
+    vox = {}  # cell -> [L, hits, misses]
+    for i, row in enumerate(c.astype(np.float64).tolist()):
+        if all(math.isfinite(v) for v in row[:3]):
+            vox.setdefault(tuple(int(math.floor(v / voxel)) for v in row[:3]), [lg["l_init"], 0, 0])
+    rows = []
+    for f, scan in enumerate(scans):
+        s = np.asarray(scan, np.float32).reshape(-1, 4)
+        m = [[float(v) for v in r] for r in M[f]]
+        o = [m[i][3] for i in range(3)]
+        c0 = tuple(int(v) for v in c0s[f])
+        n_nf = n_oor = n_rays = n_steps = n_end = 0
+        hit, free = set(), set()
+        for x, y, z, _ in s.astype(np.float64).tolist():
+            if not (math.isfinite(x) and math.isfinite(y) and math.isfinite(z)):
+                n_nf += 1
+                continue
+            rho = math.sqrt((x * x + y * y) + z * z)
+            if not (min_range <= rho <= max_range):
+                n_oor += 1
+                continue
+            e = [((m[i][0] * x + m[i][1] * y) + m[i][2] * z) + m[i][3] for i in range(3)]
+            if not all(math.isfinite(v) and abs(math.floor(v / voxel) - c0[a]) <= CARVE_MAX_REACH for a, v in enumerate(e)):
+                n_oor += 1
+                continue
+            walk = [tuple(int(v) for v in w) for w in carve_walk(o, e, voxel)]
+            N = len(walk) - 1
+            n_rays += 1
+            n_steps += max(0, N - ss)
+            for w in walk[: max(0, N - ss)]:
+                if w in vox:
+                    free.add(w)
+            if walk[N] in vox:
+                hit.add(walk[N])
+                n_end += 1
+        free -= hit
+        for w in hit:
+            st = vox[w]
+            st[0], st[1] = min(np.float32(st[0] + lg["l_hit"]), lg["l_max"]), st[1] + 1
+        for w in free:
+            st = vox[w]
+            st[0], st[2] = max(np.float32(st[0] + lg["l_miss"]), lg["l_min"]), st[2] + 1
+        rows.append(dict(zip(CARVE_ROW_FIELDS, [len(s), n_nf, n_oor, n_rays, n_steps, n_end, len(hit), len(free)])))
+    order = sorted(vox)
+    index = {w: j for j, w in enumerate(order)}
+    vox_of = np.array([index[tuple(int(v) for v in cells[i])] if fin[i] else 0 for i in range(len(c))], np.int64).reshape(-1)
+    L = np.array([vox[w][0] for w in order], np.float32).reshape(-1)
+    hits = np.array([vox[w][1] for w in order], np.uint16).reshape(-1)
+    misses = np.array([vox[w][2] for w in order], np.uint16).reshape(-1)
+    return _carve_finish(c, fin, vox_of, L, hits, misses, len({tuple(v >> 2 for v in w) for w in order}), rows, lg, keep)

@@ -718,6 +718,109 @@ int erasor_hip_visibility_map(erasor_hip_handle *h, const void *scans_xyzi, size
                               const erasor_visibility *params, uint16_t *votes, uint8_t *keep_mask, float *kept_xyzi, size_t cap_points,
                               erasor_visibility_row *rows, erasor_visibility_result *res);
 
+/* ---- carving free space: every scan's rays cast through the map's voxels ------------------------------------------------------------
+ * stands in for: nothing the reference runs.  The reference only COMPARES ERASOR's map with those of OctoMap and Peopleremover
+ * (roslaunch erasor compare_results.launch, src/utils/compare_map.cpp, the panels of img/<seq>/README.md,
+ * scripts/semantickitti2bag/analysis_octomap.py), the two methods that put the map into a voxel grid and walk every ray of every scan
+ * through it.  These calls produce OctoMap's side of that comparison: a voxel that rays pass through is free, a voxel that rays end in
+ * is occupied, and the two are integrated as clamped log-odds.  Unlike the range-image vote of erasor_hip_visibility_* this separates
+ * an occluder from what stands behind it in the same pixel, and depends on a voxel size, not on the sensor's beam layout.
+ * The contract; the normative text is erasor_amd/evalmap.py (carve / carve_brute), which the device equals byte for byte.
+ * Coordinates are float64 on the float32 inputs.  Every operation is a separate IEEE operation in the order written.  Only + - * /,
+ * sqrt, floor and comparisons are used.  The log-odds are float32.
+ * Voxels.
+ *   - A finite point lies in cell c = floor(x / voxel) per axis.
+ *   - A map point with a non-finite coordinate lies in no voxel.  It is kept, gets zero votes and log-odds l_init, and is counted as
+ *     n_map_non_finite.
+ *   - The map voxels are the cells that hold at least one finite map point.  Only they carry state.
+ * Rays.
+ *   - The forward matrix of frame f is the M of visibility_transforms: T_body2origin[f] . T_lidar2body, upper three rows, float32
+ *     entries widened.
+ *   - The ray's origin o is M's column 3.
+ *   - A scan point (x, y, z) in the lidar frame has rho = sqrt((x x + y y) + z z).
+ *   - The gates, in this order: a non-finite coordinate, then rho outside [min_range, max_range].  Both are dropped and counted per
+ *     frame.
+ *   - The end point is e_i = ((M[i][0] x + M[i][1] y) + M[i][2] z) + M[i][3].
+ *   - Under a rigid M the end lies within max_range of the origin, so at most 4097 cells away per axis.  A ray whose end cell is not
+ *     within 4098 cells of the origin's cell on every axis (a matrix that stretches, or an end that is not finite) is dropped and
+ *     counted as out of range: this keeps every walk below 3 * 4098 steps whatever the matrix.
+ * Traversal.
+ *   - c0 = cell(o), c1 = cell(e), n_a = |c1_a - c0_a|, step_a = +-1, N = n_x + n_y + n_z.
+ *   - For an axis with n_a > 0: d_a = e_a - o_a; tMax_a = ((c0_a + (step_a > 0 ? 1 : 0)) * voxel - o_a) / d_a; tDelta_a = voxel / |d_a|.
+ *   - An axis with no steps left never moves.
+ *   - Each of the N steps moves the axis with the smallest tMax among the axes that still have steps left.  Ties go to x before y
+ *     before z.
+ *   - After the move, c_a += step_a, the steps left on that axis drop by one, and tMax_a += tDelta_a.
+ *   - So the walk visits V_0 = c0 ... V_N = c1, and always ends in c1 whatever the rounding.
+ *   - Free evidence: V_i for 0 <= i <= N - 1 - stop_short.
+ *   - Hit evidence: V_N.
+ *   - n_steps of a ray is max(0, N - stop_short).
+ * One update per voxel and scan, hits first (OctoMap's insertPointCloud rule).
+ *   - In frame f a map voxel is hit if any ray of f ends in it.
+ *   - Otherwise it is free if any ray of f has it as free evidence.
+ *   - Otherwise it is untouched.
+ * Integration, per map voxel, frames in index order.
+ *   - L starts at l_init.
+ *   - A hit frame: L = min(L + l_hit, l_max), and hits += 1.
+ *   - A free frame: L = max(L + l_miss, l_min), and misses += 1.
+ *   - Everything is float32.
+ *   - The log-odds are parameters.  No kernel calls log.
+ * Decision.  A map point is removed iff its voxel's L < l_thr.  Every point of a voxel shares its voxel's fate. */
+typedef struct erasor_carve {
+    double voxel;                 /* finite, > 0 */
+    double min_range, max_range;  /* finite, 0 <= min_range < max_range, max_range / voxel <= 4096 */
+    float l_init, l_hit, l_miss;  /* finite; l_hit >= 0, l_miss <= 0 (erasor_amd.carve_logodds forms OctoMap's defaults) */
+    float l_min, l_max, l_thr;    /* finite; l_min <= l_init <= l_max */
+    uint32_t stop_short;          /* 0 .. 64: the last stop_short voxels before a ray's end give no free evidence */
+    uint32_t reserved;            /* 0 */
+} erasor_carve;
+#define ERASOR_CARVE_MAX_FRAMES 65535
+#define ERASOR_CARVE_MAX_CELLS 4096
+#define ERASOR_CARVE_MAX_STOP_SHORT 64
+
+typedef struct erasor_carve_row {  /* one frame */
+    uint64_t n_points;        /* scan points given */
+    uint64_t n_non_finite;    /* ... dropped: a non-finite coordinate */
+    uint64_t n_out_of_range;  /* ... rho outside [min_range, max_range] (or an end out of reach) */
+    uint64_t n_rays;          /* rays walked */
+    uint64_t n_steps;         /* the sum of their max(0, N - stop_short) */
+    uint64_t n_end_in_map;    /* rays whose end voxel is a map voxel */
+    uint64_t n_voxels_hit;    /* distinct map voxels hit by this frame */
+    uint64_t n_voxels_free;   /* distinct map voxels free in this frame (and not hit) */
+} erasor_carve_row;
+
+typedef struct erasor_carve_result {
+    uint64_t n_points;           /* map points */
+    uint64_t n_map_non_finite;   /* ... with a non-finite coordinate: in no voxel, kept */
+    uint64_t n_voxels;           /* map voxels */
+    uint64_t n_blocks;           /* 4 x 4 x 4 blocks that hold one */
+    uint64_t n_voxels_touched;   /* map voxels with at least one hit or miss */
+    uint64_t n_kept, n_removed;
+    uint64_t n_removed_dynamic;  /* removed points by label, as erasor_density_result counts them */
+    uint64_t n_removed_static;
+    uint64_t n_scan_points, n_non_finite, n_out_of_range, n_rays, n_steps, n_end_in_map, n_voxels_hit, n_voxels_free;  /* the rows' sums */
+} erasor_carve_result;
+
+/* Map, scans, offsets, T_lidar2body and T_body2origin as erasor_hip_visibility_clouds takes them.  Every output is a host buffer and
+ * may be NULL: votes (n_map x 2 uint16: the hits and misses of the point's voxel), logodds (n_map float32), keep_mask (n_map uint8,
+ * 1 = kept), kept_xyzi (the kept rows in the order given, the stable compaction; cap_points rows, ERASOR_E_CAPACITY after res is
+ * filled if they do not fit), rows (n_frames), res.  Works in the evaluator's own scratch.
+ * ERASOR_E_INVALID: params NULL; voxel not finite or not > 0; 0 <= min_range < max_range does not hold; max_range / voxel > 4096; a
+ * non-finite log-odds parameter, l_hit < 0, l_miss > 0, or not l_min <= l_init <= l_max; stop_short > 64; more than 65535 frames (the
+ * uint16 votes cannot wrap); offsets that are not monotone; a non-finite pose entry or frame matrix; more than 2^30 points; a finite map
+ * point or a frame origin whose cell coordinate reaches +-2^28.  ERASOR_E_STATE: a step in flight. */
+int erasor_hip_carve_clouds(erasor_hip_handle *h, const void *map_xyzi, size_t n_map, int map_is_device, const void *scans_xyzi,
+                            size_t n_scan_points, const uint64_t *offsets, size_t n_frames, int scans_are_device,
+                            const float T_lidar2body[16] /* NULL: identity */, const float *T_body2origin, const erasor_carve *params,
+                            uint16_t *votes, float *logodds, uint8_t *keep_mask, float *kept_xyzi, size_t cap_points, erasor_carve_row *rows,
+                            erasor_carve_result *res);
+/* the same for the handle's current map (compacted on the device as erasor_hip_visibility_map does, never copied to the host and not
+ * modified).  ERASOR_E_STATE also: no map. */
+int erasor_hip_carve_map(erasor_hip_handle *h, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                         int scans_are_device, const float T_lidar2body[16], const float *T_body2origin, const erasor_carve *params,
+                         uint16_t *votes, float *logodds, uint8_t *keep_mask, float *kept_xyzi, size_t cap_points, erasor_carve_row *rows,
+                         erasor_carve_result *res);
+
 /* ---- every scan's points labelled static or moving from a cleaned map ---------------------------------------------------------
  * replaces: what users of a cleaned map do on the host afterwards -- a KD-tree over the cleaned map, a radius test per scan point, the
  * scan's moving points dropped (automatic moving-object-segmentation labels, cleaned scans for re-mapping); the reference itself stops
