@@ -272,6 +272,51 @@ def carve_logodds(p_hit=0.7, p_miss=0.4, p_min=0.12, p_max=0.97, p_thr=0.5):
     return evalmap.carve_logodds(p_hit, p_miss, p_min, p_max, p_thr)
 
 
+class Ground(C.Structure):
+    """erasor_ground"""
+    _fields_ = [("n_rings", C.c_uint32), ("n_sectors", C.c_uint32), ("ring_edge", C.POINTER(C.c_double)), ("col_tan", C.POINTER(C.c_double)),
+                ("elevation", C.POINTER(C.c_double)), ("flatness", C.POINTER(C.c_double)), ("num_lpr", C.c_uint32), ("iters", C.c_uint32),
+                ("min_points", C.c_uint32), ("min_votes", C.c_uint32), ("th_seeds", C.c_double), ("th_dist", C.c_double), ("min_z", C.c_double),
+                ("uprightness", C.c_double), ("ratio", C.c_double), ("keep", C.c_uint32), ("reserved", C.c_uint32),
+                ("work_budget_bytes", C.c_uint64)]
+
+
+class GroundRow(C.Structure):
+    """erasor_ground_row"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_non_finite", "n_out_of_range", "n_judged", "n_ground", "n_ground_dynamic", "n_patches",
+                                          "n_sparse", "n_degenerate", "n_rejected_upright", "n_rejected_elevation", "n_gathered")]
+
+    def as_dict(self, gathered=False):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if gathered or k != "n_gathered"}
+
+
+class GroundPatch(C.Structure):
+    """erasor_ground_patch (evalmap.GROUND_PATCH_DTYPE)"""
+    _fields_ = [("status", C.c_uint32), ("n_points", C.c_uint32), ("n_ground", C.c_uint32), ("reserved", C.c_uint32), ("normal", C.c_double * 3),
+                ("d", C.c_double), ("mean_z", C.c_double), ("eig", C.c_double * 3)]
+
+
+class GroundResult(C.Structure):
+    """erasor_ground_result"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_frames", "n_points", "n_non_finite", "n_out_of_range", "n_judged", "n_ground", "n_ground_dynamic",
+                                          "n_patches", "n_sparse", "n_degenerate", "n_rejected_upright", "n_rejected_elevation", "n_map_points",
+                                          "n_map_ground", "n_map_ground_dynamic", "n_map_ground_static", "n_map_unseen", "n_kept")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# the fit's size classes and the default work budget (include/erasor_hip.h)
+GROUND_WAVE_POINTS, GROUND_SMALL_POINTS, GROUND_LDS_POINTS = 64, 1024, 4096
+GROUND_WORK_BUDGET = 256 << 20
+
+
+def ground_grid(n_rings=20, n_sectors=64, min_range=0.5, max_range=80.0):
+    """evalmap.ground_grid, re-exported: a uniform patch grid (n_sectors, col_tan, ring_edge) for Erasor.ground_scans / ground_votes"""
+    from . import evalmap
+    return evalmap.ground_grid(n_rings, n_sectors, min_range, max_range)
+
+
 DENSITY_SCORES = {"kth": 0, "mean": 1, "count": 2}  # ERASOR_DENSITY_KTH / _MEAN / _COUNT
 DENSITY_RULES = {"abs": 0, "mad": 1}                # ERASOR_DENSITY_ABS / _MAD
 KNN_NONE = 0xFFFFFFFF  # the padding of a neighbour list
@@ -456,7 +501,7 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "normals.hip.h", "refine_plane.hip.h", "visibility.hip.h", "carve.hip.h", "render.hip.h", "revert_bins.hip.h",
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "normals.hip.h", "refine_plane.hip.h", "visibility.hip.h", "carve.hip.h", "ground.hip.h", "render.hip.h", "revert_bins.hip.h",
                                                  "exact_sort.hip.h", "exact_sort_core.h", "overlap_auto.h", "stream_place.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
@@ -1189,6 +1234,101 @@ class Erasor:
         self._check(fn(self._h, *head, q[0], q[1], _p(offs), C.c_size_t(n_f), C.c_int(q[2]), Tl, _p(Tb), C.byref(prm),
                        _p(votes), _p(lo), _p(mask), _p(out) if keep else None, C.c_size_t(n if keep else 0), rows, C.byref(r)))
         return votes[:n], lo[:n], mask[:n], (out[: r.n_kept] if keep else None), [rows[f].as_dict() for f in range(n_f)], r.as_dict()
+
+    # -- every scan's ground, and the map's ground points by vote (on the host: evalmap.ground_scans / ground_votes) --
+    def _ground_params(self, grid, num_lpr, th_seeds, th_dist, iters, min_points, min_z, uprightness, elevation, flatness, kept, min_votes=1,
+                       ratio=0.5, keep=1, work_budget_bytes=0):
+        """erasor_ground from the arguments (its tables are appended to `kept`, which must outlive the call)"""
+        from . import evalmap
+        g = evalmap.ground_grid() if grid is None else grid
+        S = int(g["n_sectors"])
+        col = np.ascontiguousarray(g["col_tan"], np.float64).reshape(-1)
+        edge = np.ascontiguousarray(g["ring_edge"], np.float64).reshape(-1)
+        R = len(edge) - 1
+        if 8 <= S <= 512 and len(col) != S // 8 - 1:
+            raise ValueError("ground: col_tan has n_sectors / 8 - 1 entries")
+        for v in (num_lpr, iters, min_points, min_votes):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError("ground: num_lpr, iters, min_points and min_votes must fit 32 bits")
+        tabs = []
+        for t in (elevation, flatness):
+            a = None if t is None else np.ascontiguousarray(t, np.float64).reshape(-1)
+            if a is not None and len(a) != max(R, 0):
+                raise ValueError("ground: elevation and flatness have n_rings entries")
+            tabs.append(a)
+        kept += [col, edge] + tabs
+        dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+        return Ground(max(R, 0) & 0xFFFFFFFF, S & 0xFFFFFFFF, dp(edge), dp(col), dp(tabs[0]), dp(tabs[1]), int(num_lpr), int(iters), int(min_points),
+                      int(min_votes), float(th_seeds), float(th_dist), float(min_z), float(uprightness), float(ratio), 1 if keep else 0, 0,
+                      int(work_budget_bytes)), max(R, 1), S
+
+    def ground_scans(self, scans, grid=None, num_lpr=10, th_seeds=0.5, th_dist=0.15, iters=3, min_points=10, min_z=-3.03, uprightness=0.707,
+                     elevation=None, flatness=None, patches=False):
+        """Every scan's ground (erasor_hip_ground_scans): R-GPF (erasor.cpp:183-294) on every polar patch of every scan, all frames in one
+        call.  scans: a list of XYZI arrays in the lidar frame, or (device_ptr, offsets); grid: ground_grid() or a dict with n_sectors,
+        col_tan and ring_edge (None: ground_grid()); elevation, flatness: tables of n_rings entries (None: both gates off).  A point's code:
+        1 ground, 0 judged and not ground, 2 not judged (out of range, a sparse or degenerate patch), 255 non-finite.  Returns (codes uint8,
+        all frames one after another; a row per frame; their sums; with `patches` the table [n_frames, n_rings, n_sectors] of
+        evalmap.GROUND_PATCH_DTYPE, else None) as evalmap.ground_scans does, byte for byte."""
+        from . import evalmap
+        kept = []
+        if isinstance(scans, tuple):
+            ptr, offsets = scans
+            offs = np.ascontiguousarray(offsets, np.uint64)
+            q = (C.c_void_p(ptr), C.c_size_t(int(offs[-1]) if len(offs) else 0), 1)
+        else:
+            a = [_f32(s).reshape(-1, 4) for s in scans]
+            offs = np.zeros(len(a) + 1, np.uint64)
+            offs[1:] = np.cumsum([len(s) for s in a], dtype=np.uint64)
+            cat = _f32(np.concatenate(a) if a else np.zeros((0, 4), np.float32))
+            kept.append(cat)
+            q = (_p(cat), C.c_size_t(len(cat)), 0)
+        n_f, n = len(offs) - 1, q[1].value
+        prm, R, S = self._ground_params(grid, num_lpr, th_seeds, th_dist, iters, min_points, min_z, uprightness, elevation, flatness, kept)
+        codes = np.empty(max(n, 1), np.uint8)
+        rows = (GroundRow * max(n_f, 1))()
+        tab = np.zeros((n_f, R, S), evalmap.GROUND_PATCH_DTYPE) if patches else None
+        r = GroundResult()
+        self._check(lib().erasor_hip_ground_scans(self._h, q[0], q[1], _p(offs), C.c_size_t(n_f), C.c_int(q[2]), C.byref(prm), _p(codes), rows,
+                                                  tab.ctypes.data_as(C.c_void_p) if patches and tab.size else None, C.byref(r)))
+        res = {k: v for k, v in r.as_dict().items() if not k.startswith("n_map_") and k != "n_kept"}
+        return codes[:n], [rows[f].as_dict() for f in range(n_f)], res, tab
+
+    def ground_votes(self, T_body2origin, T_lidar2body=None, map=None, grid=None, num_lpr=10, th_seeds=0.5, th_dist=0.15, iters=3, min_points=10,
+                     min_z=-3.03, uprightness=0.707, elevation=None, flatness=None, min_votes=1, ratio=0.5, keep=1, work_budget_bytes=0):
+        """The map's ground points by vote (erasor_hip_ground_votes_clouds / _map): what every frame sees of the map is segmented exactly
+        as a scan (ground_scans), and a map point is ground iff ground >= min_votes and ground > ratio * seen over the frames that judged
+        it.  Poses and T_lidar2body as for visibility; `map` a cloud as for evaluate, or None for the handle's current map (which stays as
+        it is).  The frames go in batches of work_budget_bytes / (n_map * 16) frames (0: GROUND_WORK_BUDGET); the result does not depend on
+        it.  Returns (votes (n, 2) uint16: seen, ground; mask uint8, 1 = ground; the ground rows (keep = 1) or the rest (keep = 0) in map
+        order; a row per frame; the result) as evalmap.ground_votes does, byte for byte."""
+        kept = []
+        Tb = _f32(np.asarray(T_body2origin, np.float32).reshape(-1, 16))
+        n_f = len(Tb)
+        if not n_f:
+            Tb = np.zeros((1, 16), np.float32)
+        if T_lidar2body is not None:
+            kept.append(_f32(T_lidar2body).reshape(16))
+        Tl = None if T_lidar2body is None else _p(kept[-1])
+        prm, _, _ = self._ground_params(grid, num_lpr, th_seeds, th_dist, iters, min_points, min_z, uprightness, elevation, flatness, kept, min_votes,
+                                        ratio, keep, work_budget_bytes)
+        if map is None:
+            head, n = (), self._map_n()
+            fn = lib().erasor_hip_ground_votes_map
+        else:
+            head = self._eval_cloud(map, kept)
+            n = head[1].value
+            fn = lib().erasor_hip_ground_votes_clouds
+        votes = np.empty((max(n, 1), 2), np.uint16)
+        mask = np.empty(max(n, 1), np.uint8)
+        out = np.empty((max(n, 1), 4), np.float32)
+        rows = (GroundRow * max(n_f, 1))()
+        r = GroundResult()
+        self._check(fn(self._h, *head, Tl, _p(Tb), C.c_size_t(n_f), C.byref(prm), _p(votes), _p(mask), _p(out), C.c_size_t(n), rows, C.byref(r)))
+        res = {"n_points": int(r.n_map_points), "n_ground": int(r.n_map_ground), "n_ground_dynamic": int(r.n_map_ground_dynamic),
+               "n_ground_static": int(r.n_map_ground_static), "n_unseen": int(r.n_map_unseen), "n_kept": int(r.n_kept),
+               "n_gathered": int(r.n_points), "n_judged": int(r.n_judged)}
+        return votes[:n], mask[:n], out[: r.n_kept], [rows[f].as_dict(gathered=True) for f in range(n_f)], res
 
     # -- every scan's points labelled static or moving from a cleaned map (on the host: evalmap.label_scans) --
     def label_scans(self, scans, T_body2origin, T_lidar2body=None, static_map=None, raw_map=None, tau=None, voxelsize=0.2, split=None):

@@ -1,8 +1,8 @@
 // The offline analyses' host code: PR / RR evaluation (one estimate, many, by class), the overlap report, the frame check, the scans'
-// labels, the clustering, the k nearest neighbours and density filters, the normals, the point-to-plane refinement, the see-through check, the carving of free space, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
+// labels, the clustering, the k nearest neighbours and density filters, the normals, the point-to-plane refinement, the see-through check, the carving of free space, the ground, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
 // at its end -- one translation unit, like the kernel headers -- so it sees the handle, ensure / LAUNCH / HIPC, scan_u32, radix_sort,
 // map_to_device and voxelize_device from there; nothing of the step path depends on this file.  Kernels: evaluate.hip.h, nearest.hip.h,
-// align.hip.h, label_scans.hip.h, cluster.hip.h, knn.hip.h, normals.hip.h, refine_plane.hip.h, visibility.hip.h, carve.hip.h, render.hip.h.
+// align.hip.h, label_scans.hip.h, cluster.hip.h, knn.hip.h, normals.hip.h, refine_plane.hip.h, visibility.hip.h, carve.hip.h, ground.hip.h, render.hip.h.
 #pragma once
 
 extern "C" {
@@ -2379,6 +2379,290 @@ int erasor_hip_carve_map(erasor_hip_handle *h, const void *scans_xyzi, size_t n_
     if ((rc = map_on_device(h, who, h->ev.map, &m, &n_map)) || (rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q))) return rc;
     return cv_run(h, who, m, n_map, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, T_lidar2body, T_body2origin, *params, votes, logodds, keep_mask,
                   kept_xyzi, cap_points, rows, res);
+}
+
+// ---- the ground: R-GPF on every polar patch of every scan, and the map's ground points by vote (kernels: ground.hip.h) ----
+// Like cv_run: the main stream, the evaluator's scratch, the sort in histogram bank 2.  The frames go in batches in index order (the
+// scans: as many as keep a batch's patch table within GR_MAX_PATCHES; the map form: also within the work budget); per batch one
+// k_gr_key, the counts' scan, the keys' stable radix sort and the three k_gr_fit launches; the map form gathers in front and votes
+// behind.  Round trips: a batch's patch rows where they are asked for, and at the end the counters and the outputs asked for.
+
+static int gr_check_params(erasor_hip_handle *h, const char *who, const erasor_ground *p, size_t n_frames) {
+    if (!p) return invalid(h, who, "params is NULL");
+    if (p->n_rings < 1 || p->n_rings > ERASOR_GROUND_MAX_RINGS) return invalid(h, who, "n_rings must be within 1 .. 64");
+    if (p->n_sectors % 8 || p->n_sectors < 8 || p->n_sectors > ERASOR_GROUND_MAX_SECTORS)
+        return invalid(h, who, "n_sectors must be a multiple of 8 within 8 .. 512");
+    const uint32_t nc = p->n_sectors / 8 - 1;
+    if (!p->ring_edge || (nc && !p->col_tan)) return invalid(h, who, "ring_edge or col_tan is NULL");
+    for (uint32_t j = 0; j <= p->n_rings; ++j)
+        if (!std::isfinite(p->ring_edge[j]) || (j ? !(p->ring_edge[j] > p->ring_edge[j - 1]) : !(p->ring_edge[0] >= 0)))
+            return invalid(h, who, "ring_edge must be finite, strictly increasing and start at >= 0");
+    for (uint32_t j = 0; j < nc; ++j)
+        if (!(p->col_tan[j] > 0 && p->col_tan[j] < 1) || (j && !(p->col_tan[j] > p->col_tan[j - 1])))
+            return invalid(h, who, "col_tan must be strictly increasing within (0, 1)");
+    for (uint32_t j = 0; j < p->n_rings; ++j)
+        if ((p->elevation && std::isnan(p->elevation[j])) || (p->flatness && std::isnan(p->flatness[j])))
+            return invalid(h, who, "elevation and flatness must not hold a NaN");
+    if (p->num_lpr < 1 || p->num_lpr > ERASOR_GROUND_MAX_LPR) return invalid(h, who, "num_lpr must be within 1 .. 64");
+    if (p->iters < 1 || p->iters > ERASOR_GROUND_MAX_ITERS) return invalid(h, who, "iters must be within 1 .. 16");
+    if (p->min_points < 3) return invalid(h, who, "min_points must be at least 3");
+    if (!std::isfinite(p->th_seeds) || !std::isfinite(p->th_dist) || !std::isfinite(p->min_z) || !std::isfinite(p->uprightness))
+        return invalid(h, who, "th_seeds, th_dist, min_z and uprightness must be finite");
+    if (!std::isfinite(p->ratio)) return invalid(h, who, "ratio must be finite");
+    if (n_frames > ERASOR_GROUND_MAX_FRAMES) return invalid(h, who, "more than 65535 frames");
+    return ERASOR_OK;
+}
+
+// the tables on the device (ring_edge, col_tan, elevation, flatness) and the kernels' parameters
+static int gr_put_tables(erasor_hip_handle *h, const erasor_ground &prm, GrParams *P) {
+    auto &E = h->ev;
+    const uint32_t R = prm.n_rings, S = prm.n_sectors, M = S / 8;
+    *P = GrParams{R, S, M, prm.num_lpr, prm.iters, prm.min_points, prm.th_seeds, prm.th_dist, prm.min_z, prm.uprightness};
+    std::vector<double> tabs;
+    tabs.insert(tabs.end(), prm.ring_edge, prm.ring_edge + R + 1);
+    if (M > 1) tabs.insert(tabs.end(), prm.col_tan, prm.col_tan + (M - 1));
+    for (uint32_t j = 0; j < R; ++j) tabs.push_back(prm.elevation ? prm.elevation[j] : (double)INFINITY);
+    for (uint32_t j = 0; j < R; ++j) tabs.push_back(prm.flatness ? prm.flatness[j] : 0.0);
+    if (ensure(h, E.gr_tab, tabs.size())) return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemcpyAsync(E.gr_tab.p, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));  // (tabs leaves scope)
+    return ERASOR_OK;
+}
+
+// One batch: nb frames with the device offsets d_off[0 .. nb] (absolute indices into pts), their points lo + k, k < n (n = *n_dev when
+// given, n_ub its bound).  codes: by absolute index; patches: the batch's nb R S rows, zeroed, or NULL; ctr: the batch's first frame's.
+static int gr_segment(erasor_hip_handle *h, const float4 *pts, uint32_t lo, uint32_t n_ub, const uint32_t *n_dev, const uint32_t *d_off, uint32_t nb,
+                      const GrParams &P, uint8_t *codes, erasor_ground_patch *patches, unsigned long long *ctr) {
+    auto &E = h->ev;
+    if (!n_ub || !nb) return ERASOR_OK;
+    const uint32_t np = nb * P.R * P.S;  // (<= GR_MAX_PATCHES)
+    const size_t n1 = (size_t)n_ub + 1;
+    if (ensure(h, E.gr_key, n1) || ensure(h, E.gr_ka, n1) || ensure(h, E.gr_kb, n1) || ensure(h, E.gr_va, n1) || ensure(h, E.gr_vb, n1) ||
+        ensure(h, E.gr_cnt, (size_t)np + 2) || ensure(h, E.gr_pl, (size_t)np + 2) || ensure(h, E.gr_tops, np / 1024 + 4))
+        return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemsetAsync(E.gr_cnt.p, 0, ((size_t)np + 1) * sizeof(uint32_t), h->stream));
+    LAUNCH(h, h->stream, "gr_key", k_gr_key, cdiv(n_ub, 256), 256, pts, lo, n_ub, n_dev, d_off, nb, P, (const double *)E.gr_tab.p, E.gr_key.p, E.gr_cnt.p, codes,
+           ctr);
+    scan_u32(h, h->stream, E.gr_cnt.p, E.gr_pl.p, E.gr_tops.p, np + 1, np + 1, nullptr, nullptr, "gr_scan");
+    const uint32_t *skeys = nullptr, *sperm = nullptr;
+    const int rc = radix_sort(h, h->stream, 2, E.gr_key.p, n_ub, n_dev, key_bits(np + 1), E.gr_ka.p, E.gr_kb.p, E.gr_va.p, E.gr_vb.p, &skeys, &sperm, "gr_sort");
+    if (rc) return rc;
+    // The three size classes, each over the whole table.  One launch per class, not one launch that dispatches by class: a launch has one
+    // workgroup size, one static LDS allotment and one register budget, and the classes differ in all three (64 lanes, 768 B and 146
+    // VGPRs for the wavefront class; 256 lanes with 21 KiB or 57 KiB and about 100 VGPRs for the other two), so a single kernel would
+    // give every patch of 20 points the large class's 57 KiB and two workgroups per CU.  What a single launch would cost or save was
+    // not measured (EXPERIMENTS "Ground").
+    LAUNCH(h, h->stream, "gr_fit_wave", (k_gr_fit<64, GR_WAVE_POINTS, 0>), std::min(np, 16384u), 64, pts, lo, sperm, (const uint32_t *)E.gr_cnt.p,
+           (const uint32_t *)E.gr_pl.p, (const uint32_t *)E.gr_tops.p, np, P, (const double *)E.gr_tab.p, codes, patches, ctr);
+    LAUNCH(h, h->stream, "gr_fit_small", (k_gr_fit<256, GR_SMALL_POINTS, 1>), std::min(np, 4096u), 256, pts, lo, sperm, (const uint32_t *)E.gr_cnt.p,
+           (const uint32_t *)E.gr_pl.p, (const uint32_t *)E.gr_tops.p, np, P, (const double *)E.gr_tab.p, codes, patches, ctr);
+    LAUNCH(h, h->stream, "gr_fit_large", (k_gr_fit<256, GR_LDS_POINTS, 2>), std::min(np, 1024u), 256, pts, lo, sperm, (const uint32_t *)E.gr_cnt.p,
+           (const uint32_t *)E.gr_pl.p, (const uint32_t *)E.gr_tops.p, np, P, (const double *)E.gr_tab.p, codes, patches, ctr);
+    return ERASOR_OK;
+}
+
+// a frame's row from its counters (n_points: the scan's, or the gathered count in the map form), added into the result
+static erasor_ground_row gr_row(const unsigned long long *cf, uint64_t n_points, uint64_t n_gathered, erasor_ground_result *r) {
+    erasor_ground_row row;
+    row.n_points = n_points;
+    row.n_non_finite = cf[GR_C_NON_FINITE];
+    row.n_out_of_range = cf[GR_C_RANGE];
+    row.n_judged = cf[GR_C_JUDGED];
+    row.n_ground = cf[GR_C_GROUND];
+    row.n_ground_dynamic = cf[GR_C_GROUND_DYNAMIC];
+    row.n_patches = cf[GR_C_PATCHES];
+    row.n_sparse = cf[GR_C_STATUS + (uint32_t)ERASOR_GROUND_SPARSE];
+    row.n_degenerate = cf[GR_C_STATUS + (uint32_t)ERASOR_GROUND_DEGENERATE];
+    row.n_rejected_upright = cf[GR_C_STATUS + (uint32_t)ERASOR_GROUND_REJECTED_UPRIGHT];
+    row.n_rejected_elevation = cf[GR_C_STATUS + (uint32_t)ERASOR_GROUND_REJECTED_ELEVATION];
+    row.n_gathered = n_gathered;
+    r->n_points += row.n_points;
+    r->n_non_finite += row.n_non_finite;
+    r->n_out_of_range += row.n_out_of_range;
+    r->n_judged += row.n_judged;
+    r->n_ground += row.n_ground;
+    r->n_ground_dynamic += row.n_ground_dynamic;
+    r->n_patches += row.n_patches;
+    r->n_sparse += row.n_sparse;
+    r->n_degenerate += row.n_degenerate;
+    r->n_rejected_upright += row.n_rejected_upright;
+    r->n_rejected_elevation += row.n_rejected_elevation;
+    return row;
+}
+
+static int gr_run_scans(erasor_hip_handle *h, const float4 *scans, uint32_t n, const uint64_t *offsets, uint32_t n_frames, const erasor_ground &prm,
+                        uint8_t *codes, erasor_ground_row *rows, erasor_ground_patch *patches, erasor_ground_result *res) {
+    auto &E = h->ev;
+    GrParams P;
+    int rc;
+    if ((rc = gr_put_tables(h, prm, &P))) return rc;
+    const uint32_t nf = std::max(n_frames, 1u), RS = P.R * P.S, nbmax = std::max(1u, GR_MAX_PATCHES / RS);
+    std::vector<uint32_t> off(n_frames + 1);
+    for (uint32_t f = 0; f <= n_frames; ++f) off[f] = (uint32_t)offsets[f];
+    if (ensure(h, E.al_off, (size_t)nf + 1) || ensure(h, E.gr_codes, (size_t)n + 1) || ensure(h, E.gr_ctr, (size_t)nf * GR_NCTR) ||
+        (patches && ensure(h, E.gr_patch, (size_t)std::min(nbmax, nf) * RS)))
+        return ERASOR_E_NO_DEVICE;
+    HIPC(h, hipMemcpyAsync(E.al_off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemsetAsync(E.gr_ctr.p, 0, (size_t)nf * GR_NCTR * sizeof(unsigned long long), h->stream));
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += nbmax) {
+        const uint32_t f1 = std::min(n_frames, f0 + nbmax), nb = f1 - f0, lo = off[f0], hi = off[f1];
+        erasor_ground_patch *const hp = patches ? patches + (size_t)f0 * RS : nullptr;
+        if (hi == lo) {
+            if (hp) memset(hp, 0, (size_t)nb * RS * sizeof(erasor_ground_patch));
+            continue;
+        }
+        if (hp) HIPC(h, hipMemsetAsync(E.gr_patch.p, 0, (size_t)nb * RS * sizeof(erasor_ground_patch), h->stream));
+        if ((rc = gr_segment(h, scans, lo, hi - lo, nullptr, (const uint32_t *)E.al_off.p + f0, nb, P, E.gr_codes.p, hp ? E.gr_patch.p : nullptr,
+                             E.gr_ctr.p + (size_t)f0 * GR_NCTR)))
+            return rc;
+        if (hp && (rc = d2h(h, hp, E.gr_patch.p, (size_t)nb * RS * sizeof(erasor_ground_patch)))) return rc;
+    }
+    std::vector<unsigned long long> c((size_t)nf * GR_NCTR);
+    if ((rc = d2h(h, c.data(), E.gr_ctr.p, c.size() * sizeof(unsigned long long)))) return rc;
+    erasor_ground_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_frames = n_frames;
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const erasor_ground_row row = gr_row(&c[(size_t)f * GR_NCTR], off[f + 1] - off[f], 0, &r);
+        if (rows) rows[f] = row;
+    }
+    if (res) *res = r;
+    if (codes && n) return d2h(h, codes, E.gr_codes.p, n);
+    return ERASOR_OK;
+}
+
+static int gr_run_votes(erasor_hip_handle *h, const char *who, const float4 *map, uint32_t n_map, const float *T_lidar2body, const float *T_body2origin,
+                        uint32_t n_frames, const erasor_ground &prm, uint16_t *votes, uint8_t *ground_mask, float *kept_xyzi, size_t cap_points,
+                        erasor_ground_row *rows, erasor_ground_result *res) {
+    auto &E = h->ev;
+    const uint32_t nf = std::max(n_frames, 1u);
+    std::vector<VisFrame> fr(nf);
+    const float *Tl = T_lidar2body ? T_lidar2body : AL_IDENTITY;
+    for (uint32_t f = 0; f < n_frames; ++f)
+        if (!vs_frame(T_body2origin + 16 * (size_t)f, Tl, &fr[f])) return invalid(h, who, "non-finite transform of frame " + std::to_string(f));
+    GrParams P;
+    int rc;
+    if ((rc = gr_put_tables(h, prm, &P))) return rc;
+    // the batches: whole frames of n_map * 16 bytes each within the budget, at least one; the patch table and the pairs' index bound them too
+    const uint32_t RS = P.R * P.S;
+    const uint64_t budget = prm.work_budget_bytes ? prm.work_budget_bytes : ERASOR_GROUND_WORK_BUDGET;
+    uint64_t nbmax = n_map ? budget / ((uint64_t)n_map * sizeof(float4)) : nf;
+    nbmax = std::min<uint64_t>(nbmax, GR_MAX_PATCHES / RS);
+    if (n_map) nbmax = std::min<uint64_t>(nbmax, (1ull << 30) / n_map);
+    nbmax = std::max<uint64_t>(1, std::min<uint64_t>(nbmax, nf));
+    const size_t n1 = (size_t)n_map + 1, npair = (size_t)nbmax * n_map, nctr = (size_t)nf * GR_NCTR + GD_NCTR;
+    if (ensure(h, E.gr_frames, nf) || ensure(h, E.gr_flag, npair + 1) || ensure(h, E.gr_fpl, npair + 1) || ensure(h, E.gr_ftops, npair / 1024 + 4) ||
+        ensure(h, E.gr_cloud, npair + 1) || ensure(h, E.gr_midx, npair + 1) || ensure(h, E.gr_off, (size_t)nbmax + 2) || ensure(h, E.gr_votes, n1) ||
+        ensure(h, E.gr_codes, npair + 1) || ensure(h, E.gr_ctr, nctr) || ensure(h, E.fm_flag, n1) || ensure(h, E.fm_pl, n1) ||
+        ensure(h, E.fm_tops, n_map / 1024 + 4) || ensure(h, E.kn_mask, n1))
+        return ERASOR_E_NO_DEVICE;
+    unsigned long long *const dctr = E.gr_ctr.p + (size_t)nf * GR_NCTR;  // the decision's counters, behind the frames'
+    HIPC(h, hipMemcpyAsync(E.gr_frames.p, fr.data(), (size_t)nf * sizeof(VisFrame), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemsetAsync(E.gr_ctr.p, 0, nctr * sizeof(unsigned long long), h->stream));
+    HIPC(h, hipMemsetAsync(E.gr_votes.p, 0, n1 * sizeof(uint32_t), h->stream));
+    const uint32_t gm = cdiv(n_map, 256);
+    for (uint32_t f0 = 0; n_map && f0 < n_frames; f0 += (uint32_t)nbmax) {
+        const uint32_t f1 = (uint32_t)std::min<uint64_t>(n_frames, f0 + nbmax), nb = f1 - f0, tot = nb * n_map;
+        unsigned long long *const cf = E.gr_ctr.p + (size_t)f0 * GR_NCTR;
+        uint32_t *const d_n = E.gr_off.p + nb;  // the batch's gathered total: the last offset
+        LAUNCH(h, h->stream, "gr_gather", k_gr_gather_flag, dim3(gm, nb), 256, map, n_map, (const VisFrame *)E.gr_frames.p + f0, P, (const double *)E.gr_tab.p,
+               E.gr_flag.p);
+        scan_u32(h, h->stream, E.gr_flag.p, E.gr_fpl.p, E.gr_ftops.p, tot, tot, nullptr, d_n, "gr_gather");
+        LAUNCH(h, h->stream, "gr_gather", k_gr_gather_put, dim3(gm, nb), 256, map, n_map, (const VisFrame *)E.gr_frames.p + f0, (const uint32_t *)E.gr_flag.p, (const uint32_t *)E.gr_fpl.p, (const uint32_t *)E.gr_ftops.p, E.gr_cloud.p, E.gr_midx.p, E.gr_off.p);
+        LAUNCH(h, h->stream, "gr_gather", k_gr_count_frames, cdiv(nb, 256), 256, (const uint32_t *)E.gr_off.p, nb, cf);
+        if ((rc = gr_segment(h, E.gr_cloud.p, 0, tot, d_n, (const uint32_t *)E.gr_off.p, nb, P, E.gr_codes.p, nullptr, cf))) return rc;
+        LAUNCH(h, h->stream, "gr_vote", k_gr_vote, cdiv(tot, 256), 256, (const uint8_t *)E.gr_codes.p, (const uint32_t *)E.gr_midx.p, (const uint32_t *)d_n,
+               E.gr_votes.p);
+    }
+    if (n_map)
+        LAUNCH(h, h->stream, "gr_decide", k_gr_decide, gm, 256, map, n_map, (const uint32_t *)E.gr_votes.p, prm.min_votes, prm.ratio, prm.keep, E.fm_flag.p,
+               E.kn_mask.p, dctr);
+    std::vector<unsigned long long> c(nctr);
+    if ((rc = d2h(h, c.data(), E.gr_ctr.p, c.size() * sizeof(unsigned long long)))) return rc;
+    erasor_ground_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_frames = n_frames;
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const unsigned long long *cf = &c[(size_t)f * GR_NCTR];
+        const erasor_ground_row row = gr_row(cf, cf[GR_C_POINTS], cf[GR_C_POINTS], &r);
+        if (rows) rows[f] = row;
+    }
+    const unsigned long long *cd = &c[(size_t)nf * GR_NCTR];
+    r.n_map_points = n_map;
+    r.n_map_ground_dynamic = cd[GD_C_GROUND_DYNAMIC];
+    r.n_map_ground_static = cd[GD_C_GROUND_STATIC];
+    r.n_map_ground = r.n_map_ground_dynamic + r.n_map_ground_static;
+    r.n_map_unseen = cd[GD_C_UNSEEN];
+    r.n_kept = prm.keep ? r.n_map_ground : n_map - r.n_map_ground;
+    if (res) *res = r;
+    if (votes && n_map && (rc = d2h(h, votes, E.gr_votes.p, (size_t)n_map * sizeof(uint32_t)))) return rc;
+    if (ground_mask && n_map && (rc = d2h(h, ground_mask, E.kn_mask.p, n_map))) return rc;
+    if (kept_xyzi && r.n_kept > cap_points) return ERASOR_E_CAPACITY;
+    if (kept_xyzi && r.n_kept) {
+        // the rows asked for, as given: the stable compaction over the flags (cv_run's)
+        if (ensure(h, E.fm_out, n1)) return ERASOR_E_NO_DEVICE;
+        scan_u32(h, h->stream, E.fm_flag.p, E.fm_pl.p, E.fm_tops.p, n_map, n_map, nullptr, nullptr, "gr_keep");
+        LAUNCH(h, h->stream, "gr_keep", k_f_compact, gm, 256, map, n_map, (const uint32_t *)E.fm_flag.p, (const uint32_t *)E.fm_pl.p,
+               (const uint32_t *)E.fm_tops.p, E.fm_out.p);
+        return d2h(h, kept_xyzi, E.fm_out.p, (size_t)r.n_kept * sizeof(float4));
+    }
+    return ERASOR_OK;
+}
+
+int erasor_hip_ground_scans(erasor_hip_handle *h, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                            int scans_are_device, const erasor_ground *params, uint8_t *codes, erasor_ground_row *rows, erasor_ground_patch *patches,
+                            erasor_ground_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_ground_scans";
+    int rc = gr_check_params(h, who, params, n_frames);
+    if (rc) return rc;
+    if (!offsets) return invalid(h, who, "offsets is NULL (n_frames + 1 entries)");
+    if ((rc = check_scan_offsets(h, who, scans_xyzi, n_scan_points, offsets, n_frames))) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *q = nullptr;
+    if ((rc = ev_input(h, scans_xyzi, n_scan_points, scans_are_device, h->ev.est, &q))) return rc;
+    return gr_run_scans(h, q, (uint32_t)n_scan_points, offsets, (uint32_t)n_frames, *params, codes, rows, patches, res);
+}
+
+static int gr_check_votes_args(erasor_hip_handle *h, const char *who, const float *T_lidar2body, const float *T_body2origin, size_t n_frames,
+                               const erasor_ground *params) {
+    const int rc = gr_check_params(h, who, params, n_frames);
+    if (rc) return rc;
+    if (n_frames && !T_body2origin) return invalid(h, who, "T_body2origin is NULL");
+    if (T_lidar2body && !all_finite(T_lidar2body, 16)) return invalid(h, who, "non-finite entry in T_lidar2body");
+    if (!all_finite(T_body2origin, n_frames * 16)) return invalid(h, who, "non-finite entry in T_body2origin");
+    return ERASOR_OK;
+}
+
+int erasor_hip_ground_votes_clouds(erasor_hip_handle *h, const void *map_xyzi, size_t n_map, int map_is_device, const float T_lidar2body[16],
+                                   const float *T_body2origin, size_t n_frames, const erasor_ground *params, uint16_t *votes, uint8_t *ground_mask,
+                                   float *kept_xyzi, size_t cap_points, erasor_ground_row *rows, erasor_ground_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_ground_votes_clouds";
+    int rc = gr_check_votes_args(h, who, T_lidar2body, T_body2origin, n_frames, params);
+    if (rc || (rc = check_cloud(h, who, "NULL map or more than 2^30 map points", map_xyzi, n_map))) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr;
+    if ((rc = ev_input(h, map_xyzi, n_map, map_is_device, h->ev.gt, &m))) return rc;
+    return gr_run_votes(h, who, m, (uint32_t)n_map, T_lidar2body, T_body2origin, (uint32_t)n_frames, *params, votes, ground_mask, kept_xyzi, cap_points, rows,
+                        res);
+}
+
+int erasor_hip_ground_votes_map(erasor_hip_handle *h, const float T_lidar2body[16], const float *T_body2origin, size_t n_frames,
+                                const erasor_ground *params, uint16_t *votes, uint8_t *ground_mask, float *kept_xyzi, size_t cap_points,
+                                erasor_ground_row *rows, erasor_ground_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_ground_votes_map";
+    int rc = gr_check_votes_args(h, who, T_lidar2body, T_body2origin, n_frames, params);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *m = nullptr;
+    uint32_t n_map = 0;
+    if ((rc = map_on_device(h, who, h->ev.map, &m, &n_map))) return rc;
+    return gr_run_votes(h, who, m, n_map, T_lidar2body, T_body2origin, (uint32_t)n_frames, *params, votes, ground_mask, kept_xyzi, cap_points, rows, res);
 }
 
 // ---- label_map (fill_removert_intensity.cpp:24-59, compare_map.cpp:77-110) and calc_complement (compare_complement.cpp:43-75): the

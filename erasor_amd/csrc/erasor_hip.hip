@@ -47,6 +47,7 @@
 #include "refine_plane.hip.h"
 #include "visibility.hip.h"
 #include "carve.hip.h"
+#include "ground.hip.h"
 #include "render.hip.h"
 
 using namespace ek;
@@ -421,6 +422,17 @@ struct erasor_hip_handle {
         DBuf<uint32_t> cv_cnt, cv_pl, cv_tops, cv_slot, cv_hm, cv_wfree, cv_whit, cv_votes;
         DBuf<float> cv_L, cv_lo;
         DBuf<unsigned long long> cv_ctr;
+        // the ground (erasor_hip_ground_*): the tables, a batch's patch keys, the sort's two key and two value arrays, the patches' counts
+        // and their scan, the patch rows, the codes, the per-frame counters with the decision's behind them; the map form: the frames'
+        // transforms, the gather's flags and their scan, a batch's clouds with their map indices and offsets, the votes (offsets of the
+        // scans: al_off; flags, mask and kept cloud: fm_*, kn_mask)
+        DBuf<double> gr_tab;
+        DBuf<uint32_t> gr_key, gr_ka, gr_kb, gr_va, gr_vb, gr_cnt, gr_pl, gr_tops, gr_flag, gr_fpl, gr_ftops, gr_midx, gr_off, gr_votes;
+        DBuf<erasor_ground_patch> gr_patch;
+        DBuf<uint8_t> gr_codes;
+        DBuf<unsigned long long> gr_ctr;
+        DBuf<VisFrame> gr_frames;
+        DBuf<float4> gr_cloud;
     } ev;
     DBuf<unsigned long long> dbg_stamps;  // optional cycle stamps of the first finished segment (ERASOR_HIP_SORT_STAMPS)
 #ifdef ERASOR_HIP_TEST_HOOKS
@@ -1283,6 +1295,10 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->ev.cv_frames); release(h->ev.cv_tab); release(h->ev.cv_cnt); release(h->ev.cv_pl); release(h->ev.cv_tops); release(h->ev.cv_slot);
     release(h->ev.cv_hm); release(h->ev.cv_wfree); release(h->ev.cv_whit); release(h->ev.cv_votes); release(h->ev.cv_L); release(h->ev.cv_lo);
     release(h->ev.cv_ctr);
+    release(h->ev.gr_tab); release(h->ev.gr_key); release(h->ev.gr_ka); release(h->ev.gr_kb); release(h->ev.gr_va); release(h->ev.gr_vb);
+    release(h->ev.gr_cnt); release(h->ev.gr_pl); release(h->ev.gr_tops); release(h->ev.gr_flag); release(h->ev.gr_fpl); release(h->ev.gr_ftops);
+    release(h->ev.gr_midx); release(h->ev.gr_off); release(h->ev.gr_votes); release(h->ev.gr_patch); release(h->ev.gr_codes); release(h->ev.gr_ctr);
+    release(h->ev.gr_frames); release(h->ev.gr_cloud);
     for (int k = 0; k < NSIDE; ++k) {
         if (h->q[k].ev_keys) (void)hipEventDestroy(h->q[k].ev_keys);
         if (h->q[k].ev_done) (void)hipEventDestroy(h->q[k].ev_done);

@@ -1658,6 +1658,196 @@ static int label_scans_mode(int argc, char **argv) {
     return 0;
 }
 
+// What --ground and --ground-map read: the rosparam file, the poses (after callback_node's round trip), tf/lidar2body and the first
+// max_frames scans from init_idx on.  0, or the status to leave with (3: a file cannot be read).
+static int ground_load(const char *yaml, size_t max_frames, bool want_scans, erasor::OfflineMapUpdater::Config &cfg, erasor::DriverConfig &drv,
+                       std::vector<float> &scans, std::vector<uint64_t> &offsets, std::vector<float> &Tb, float Tl[16]) {
+    erasor_hip_params_default(&cfg.params);
+    if (!erasor::load_config_yaml(yaml, cfg, &drv)) {
+        fprintf(stderr, "cannot read %s\n", yaml);
+        return 3;
+    }
+    if (cfg.initial_map_path.empty() || cfg.initial_map_path == "/") cfg.initial_map_path = drv.data_dir + "/dense_global_map.pcd";
+    std::vector<Eigen::Matrix4f> poses;
+    if (!erasor::load_all_poses(drv.data_dir + "/poses_lidar2body.csv", poses)) {
+        fprintf(stderr, "cannot read %s/poses_lidar2body.csv\n", drv.data_dir.c_str());
+        return 3;
+    }
+    offsets.assign(1, 0);
+    const int last = (int)std::min<size_t>(poses.size(), (size_t)drv.init_idx + max_frames);
+    for (int i = drv.init_idx; i < last; ++i) {
+        if (want_scans) {
+            char name[64];
+            snprintf(name, sizeof(name), "/pcds/%06d.pcd", i);
+            std::vector<float> scan;
+            if (!load_cloud_xyzi(drv.data_dir + name, scan)) {
+                fprintf(stderr, "cannot read %s%s\n", drv.data_dir.c_str(), name);
+                return 3;
+            }
+            scans.insert(scans.end(), scan.begin(), scan.end());
+        }
+        offsets.push_back(scans.size() / 4);
+        const Eigen::Matrix4f T = erasor_utils::geoPose2eigen(erasor_utils::eigen2geoPose(poses[i]));  // (callback_node's round trip)
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) Tb.push_back(T(r, c));
+    }
+    geometry_msgs::Pose l2b;
+    l2b.position.x = cfg.lidar2body[0];
+    l2b.position.y = cfg.lidar2body[1];
+    l2b.position.z = cfg.lidar2body[2];
+    l2b.orientation.x = cfg.lidar2body[3];
+    l2b.orientation.y = cfg.lidar2body[4];
+    l2b.orientation.z = cfg.lidar2body[5];
+    l2b.orientation.w = cfg.lidar2body[6];
+    const Eigen::Matrix4f TL = erasor_utils::geoPose2eigen(l2b);  // (OMU.cpp:100)
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) Tl[4 * r + c] = TL(r, c);
+    return 0;
+}
+
+// erasor_ground with the reference's parameters (config/seq_05.yaml; min_z: its min_h in the lidar frame) over a uniform grid:
+// evalmap.ground_grid's expressions with C's tan
+static void ground_params(size_t R, size_t S, double min_range, double max_range, std::vector<double> &ring_edge, std::vector<double> &col_tan,
+                          erasor_ground *prm) {
+    const size_t M = S / 8;
+    const double pi = 3.141592653589793;
+    for (size_t j = 1; j < M; ++j) col_tan.push_back(tan(((pi / 4.0) * (double)j) / (double)M));
+    for (size_t i = 0; i <= R; ++i) ring_edge.push_back(min_range + ((max_range - min_range) * (double)i) / (double)R);
+    memset(prm, 0, sizeof(*prm));
+    prm->n_rings = (uint32_t)R, prm->n_sectors = (uint32_t)S, prm->ring_edge = ring_edge.data(), prm->col_tan = col_tan.data();
+    prm->num_lpr = 10, prm->iters = 3, prm->min_points = 10, prm->min_votes = 1;
+    prm->th_seeds = 0.5, prm->th_dist = 0.15, prm->min_z = -3.03, prm->uprightness = 0.707, prm->ratio = 0.5, prm->keep = 1;
+}
+
+static void ground_print_row(int frame, const erasor_ground_row &w, bool map_form) {
+    typedef unsigned long long ull;
+    printf("%6d  n=%llu  dropped %llu non-finite, %llu out of range  judged %llu  ground %llu (dynamic %llu)  patches %llu: sparse %llu, degenerate %llu, "
+           "not upright %llu, elevated %llu",
+           frame, (ull)w.n_points, (ull)w.n_non_finite, (ull)w.n_out_of_range, (ull)w.n_judged, (ull)w.n_ground, (ull)w.n_ground_dynamic, (ull)w.n_patches,
+           (ull)w.n_sparse, (ull)w.n_degenerate, (ull)w.n_rejected_upright, (ull)w.n_rejected_elevation);
+    if (map_form) printf("  gathered %llu", (ull)w.n_gathered);
+    printf("\n");
+}
+
+// --ground <rosparam.yaml> <out_dir> [n_frames] [n_rings n_sectors max_range]: every scan's ground (erasor_hip_ground_scans): R-GPF with
+// the reference's parameters on every patch of a uniform polar grid (20 rings x 64 sectors between 0.5 and 80 m by default), the scans
+// taken as given in the lidar frame.  One line per frame and the sums.  Writes <out_dir>/%06d.ground, one byte per point in scan order
+// (1 ground, 0 not ground, 2 not judged, 255 non-finite), and <out_dir>/%06d.pcd (binary) with the frame's points that are not ground.
+static int ground_mode(int argc, char **argv) {
+    if (argc != 4 && argc != 5 && argc != 8) return 2;
+    size_t max_frames = (size_t)1 << 30, R = 20, S = 64;
+    double max_range = 80.0;
+    const double min_range = 0.5;
+    if (argc > 4 && !parse_count(argv[4], &max_frames)) return 2;
+    if (argc > 7 && (!parse_count(argv[5], &R) || !parse_count(argv[6], &S) || !parse_number(argv[7], &max_range))) return 2;
+    if (R < 1 || R > ERASOR_GROUND_MAX_RINGS || S % 8 || S < 8 || S > ERASOR_GROUND_MAX_SECTORS || !(max_range > min_range) || !std::isfinite(max_range)) return 2;
+    const std::string out_dir = argv[3];
+    erasor::OfflineMapUpdater::Config cfg;
+    erasor::DriverConfig drv;
+    std::vector<float> scans, Tb;
+    std::vector<uint64_t> offsets;
+    float Tl[16];
+    const int st = ground_load(argv[2], max_frames, true, cfg, drv, scans, offsets, Tb, Tl);
+    if (st) return st;
+    std::vector<double> ring_edge, col_tan;
+    erasor_ground prm;
+    ground_params(R, S, min_range, max_range, ring_edge, col_tan, &prm);
+    erasor_hip_handle *h = render_handle();
+    if (!h) return 1;
+    const size_t n_frames = offsets.size() - 1, n_pts = scans.size() / 4;
+    std::vector<uint8_t> codes(std::max<size_t>(n_pts, 1));
+    std::vector<erasor_ground_row> rows(std::max<size_t>(n_frames, 1));
+    erasor_ground_result r;
+    const int rc = erasor_hip_ground_scans(h, scans.data(), n_pts, offsets.data(), n_frames, 0, &prm, codes.data(), rows.data(), nullptr, &r);
+    if (rc) return render_fail(h, "ground", rc);
+    erasor_hip_destroy(h);
+    typedef unsigned long long ull;
+    printf("%zu frames, %zu rings x %zu sectors between %.9g and %.9g m:\n", n_frames, R, S, min_range, max_range);
+    for (size_t f = 0; f < n_frames; ++f) {
+        ground_print_row(drv.init_idx + (int)f, rows[f], false);
+        char name[64];
+        snprintf(name, sizeof(name), "/%06d.ground", drv.init_idx + (int)f);
+        FILE *fp = fopen((out_dir + name).c_str(), "wb");
+        if (!fp) {
+            fprintf(stderr, "cannot write %s%s\n", out_dir.c_str(), name);
+            return 1;
+        }
+        const size_t m = (size_t)(offsets[f + 1] - offsets[f]);
+        if (fwrite(codes.data() + offsets[f], 1, m, fp) != m || fclose(fp) != 0) return 1;
+        std::vector<float> rest;
+        for (uint64_t i = offsets[f]; i < offsets[f + 1]; ++i)
+            if (codes[i] != ERASOR_GROUND_CODE_GROUND) rest.insert(rest.end(), scans.begin() + 4 * i, scans.begin() + 4 * i + 4);
+        pcl::PointCloud<pcl::PointXYZI> out;
+        rows_to_cloud(rest, rest.size() / 4, out);
+        snprintf(name, sizeof(name), "/%06d.pcd", drv.init_idx + (int)f);
+        if (erasor_utils::save_pcd_binary(out_dir + name, out) != 0) {
+            fprintf(stderr, "cannot write %s%s\n", out_dir.c_str(), name);
+            return 1;
+        }
+    }
+    printf("ground: frames=%llu  n=%llu  non-finite=%llu  out of range=%llu  judged=%llu  ground=%llu (dynamic %llu)  patches=%llu: sparse %llu, degenerate %llu, "
+           "not upright %llu, elevated %llu\n",
+           (ull)r.n_frames, (ull)r.n_points, (ull)r.n_non_finite, (ull)r.n_out_of_range, (ull)r.n_judged, (ull)r.n_ground, (ull)r.n_ground_dynamic, (ull)r.n_patches,
+           (ull)r.n_sparse, (ull)r.n_degenerate, (ull)r.n_rejected_upright, (ull)r.n_rejected_elevation);
+    return 0;
+}
+
+// --ground-map <rosparam.yaml> <map.pcd|-> <ground_out.pcd> <rest_out.pcd> [n_frames] [min_votes] [ratio]: the map's ground points by
+// vote (erasor_hip_ground_votes_clouds): what every frame sees of the map is segmented as a scan over the default grid, and a map point is
+// ground iff it has at least min_votes (1) ground votes and more than ratio (0.5) times the frames that judged it.  The same files and
+// poses as --carve; the map is <map.pcd>, or with "-" the configured initial map.  One line per frame, the result, and two binary PCDs:
+// the ground points and the rest, both in map order.
+static int ground_map_mode(int argc, char **argv) {
+    if (argc < 6 || argc > 9) return 2;
+    size_t max_frames = (size_t)1 << 30, min_votes = 1;
+    double ratio = 0.5;
+    if ((argc > 6 && !parse_count(argv[6], &max_frames)) || (argc > 7 && !parse_count(argv[7], &min_votes)) || (argc > 8 && !parse_number(argv[8], &ratio)))
+        return 2;
+    if (!std::isfinite(ratio) || min_votes > 0xFFFFFFFFull) return 2;
+    erasor::OfflineMapUpdater::Config cfg;
+    erasor::DriverConfig drv;
+    std::vector<float> scans, Tb, map;
+    std::vector<uint64_t> offsets;
+    float Tl[16];
+    const int st = ground_load(argv[2], max_frames, false, cfg, drv, scans, offsets, Tb, Tl);
+    if (st) return st;
+    const std::string map_path = std::string(argv[3]) == "-" ? cfg.initial_map_path : std::string(argv[3]);
+    if (!load_cloud_xyzi(map_path, map)) {
+        fprintf(stderr, "cannot read %s\n", map_path.c_str());
+        return 3;
+    }
+    std::vector<double> ring_edge, col_tan;
+    erasor_ground prm;
+    ground_params(20, 64, 0.5, 80.0, ring_edge, col_tan, &prm);
+    prm.min_votes = (uint32_t)min_votes, prm.ratio = ratio;
+    erasor_hip_handle *h = render_handle();
+    if (!h) return 1;
+    const size_t n = map.size() / 4, n_frames = offsets.size() - 1;
+    std::vector<uint8_t> mask(std::max<size_t>(n, 1));
+    std::vector<erasor_ground_row> rows(std::max<size_t>(n_frames, 1));
+    erasor_ground_result r;
+    const int rc = erasor_hip_ground_votes_clouds(h, map.data(), n, 0, Tl, Tb.data(), n_frames, &prm, nullptr, mask.data(), nullptr, 0, rows.data(), &r);
+    if (rc) return render_fail(h, "ground-map", rc);
+    erasor_hip_destroy(h);
+    typedef unsigned long long ull;
+    printf("%zu frames against %s (%zu points), min_votes %zu, ratio %.9g:\n", n_frames, map_path.c_str(), n, min_votes, ratio);
+    for (size_t f = 0; f < n_frames; ++f) ground_print_row(drv.init_idx + (int)f, rows[f], true);
+    printf("ground-map: n=%llu  ground=%llu (dynamic %llu, static %llu)  unseen=%llu  gathered=%llu  judged=%llu\n", (ull)r.n_map_points, (ull)r.n_map_ground,
+           (ull)r.n_map_ground_dynamic, (ull)r.n_map_ground_static, (ull)r.n_map_unseen, (ull)r.n_points, (ull)r.n_judged);
+    std::vector<float> part[2];
+    for (size_t i = 0; i < n; ++i) part[mask[i] ? 0 : 1].insert(part[mask[i] ? 0 : 1].end(), map.begin() + 4 * i, map.begin() + 4 * i + 4);
+    for (int k = 0; k < 2; ++k) {
+        pcl::PointCloud<pcl::PointXYZI> out;
+        rows_to_cloud(part[k], part[k].size() / 4, out);
+        if (erasor_utils::save_pcd_binary(argv[4 + k], out) != 0) {
+            fprintf(stderr, "cannot write %s\n", argv[4 + k]);
+            return 1;
+        }
+        printf("saved %s\n", argv[4 + k]);
+    }
+    return 0;
+}
+
 // --queue <n_workers> <max_frames> <a.yaml> <b.yaml> ...: independent sequences (one rosparam file each) over n_workers devices
 // (worker w drives device w mod the visible devices): every worker is a thread with its own updater per job, and takes the NEXT sequence
 // of the list whenever it is idle (erasor::WorkQueue) -- BASELINE config 3 on a node with fewer GPUs than sequences.
@@ -2051,6 +2241,19 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && (std::string(argv[1]) == "--ground" || std::string(argv[1]) == "--ground-map")) {
+        try {
+            const int st = std::string(argv[1]) == "--ground" ? ground_mode(argc, argv) : ground_map_mode(argc, argv);
+            if (st == 2)
+                fprintf(stderr, "usage: %s --ground <rosparam.yaml> <out_dir> [n_frames] [n_rings n_sectors max_range]\n"
+                                "       %s --ground-map <rosparam.yaml> <map.pcd|-> <ground_out.pcd> <rest_out.pcd> [n_frames] [min_votes] [ratio]\n",
+                        argv[0], argv[0]);
+            return st;
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && std::string(argv[1]) == "--label-scans") {
         try {
             return label_scans_mode(argc, argv);
@@ -2132,9 +2335,11 @@ int main(int argc, char **argv) {
                 "       %s --density <cloud.pcd> <k>\n"
                 "       %s --normals <in.pcd> <out.pcd> <k> [vx vy vz]\n"
                 "       %s --visibility <rosparam.yaml> <map.pcd|-> <out.pcd> [n_frames] [W H el_bottom el_top] [window] [k]\n"
-                "       %s --carve <rosparam.yaml> <map.pcd|-> <out.pcd> [n_frames] [voxel] [max_range] [stop_short]\n",
+                "       %s --carve <rosparam.yaml> <map.pcd|-> <out.pcd> [n_frames] [voxel] [max_range] [stop_short]\n"
+                "       %s --ground <rosparam.yaml> <out_dir> [n_frames] [n_rings n_sectors max_range]\n"
+                "       %s --ground-map <rosparam.yaml> <map.pcd|-> <ground_out.pcd> <rest_out.pcd> [n_frames] [min_votes] [ratio]\n",
                 argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0],
-                argv[0], argv[0]);
+                argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

@@ -2232,3 +2232,349 @@ def carve_brute(map_xyzi, scans, T_body2origin, T_lidar2body=None, voxel=0.2, mi
     hits = np.array([vox[w][1] for w in order], np.uint16).reshape(-1)
     misses = np.array([vox[w][2] for w in order], np.uint16).reshape(-1)
     return _carve_finish(c, fin, vox_of, L, hits, misses, len({tuple(v >> 2 for v in w) for w in order}), rows, lg, keep)
+
+
+# ---- the ground of every scan, and the map's ground points by vote (Erasor.ground_scans / ground_votes; kernels: ground.hip.h) ----
+# R-GPF (erasor.cpp:183-294: extract_initial_seeds_, estimate_plane_, the loop of extract_ground) run on every polar patch of every scan,
+# as the author's follow-up (Patchwork) runs it, with every order fixed.  The reference fits in float32 with Eigen's JacobiSVD over an
+# unordered cloud and sorts the seeds' candidates with std::sort; here everything is float64 on the float32 coordinates, every operation a
+# separate IEEE operation in the order written, and only + - * /, sqrt and comparisons:
+#   * the patch grid is data: n_sectors (a multiple of 8) columns of visibility_column over col_tan, and n_rings rings between the
+#     ring_edge radii; r = sqrt(x*x + y*y), ring = (the number of ring_edge entries <= r) - 1.  The gates, in this order: a non-finite
+#     coordinate (code 255); on the axis, or a ring outside 0 .. n_rings - 1 (OUT OF RANGE, code 2).  A patch is (frame, ring, sector);
+#     its points are kept in scan order, j = 0 .. m - 1;
+#   * a patch of fewer than min_points points is SPARSE (its points: code 2);
+#   * seeds: the candidates are the points with z >= min_z ordered by (z, j) (-0.0 equals +0.0); lpr = (((0.0 + z_0) + z_1) + ...) / k over
+#     the first k = min(num_lpr, candidates); no candidate: DEGENERATE.  The seeds: z >= min_z and z < lpr + th_seeds;
+#   * `iters` times over the current member set: the count n and the nine raw moments x y z xx xy xz yy yz zz summed over ALL the patch's
+#     points in patch order by refine_tree_sum's rule (a non-member holds +0.0); n < 3: DEGENERATE; mean = S / n; cov_ab = S_ab / n -
+#     mean_a * mean_b; tr = (cxx + cyy) + czz, taken before the solve; not tr > 0: DEGENERATE (zero, or below it by rounding);
+#     _jacobi3; the eigenvalues ascend by (value, column); the normal is the first one's column, negated iff its z < 0; d = -((nx mx +
+#     ny my) + nz mz); the new members are the patch's points with ((nx x + ny y) + nz z) + d < th_dist (one-sided, as the reference);
+#   * after the last iteration: nz < uprightness: REJECTED_UPRIGHT; else mean_z > elevation[ring] and not (l0 / tr <= flatness[ring]):
+#     REJECTED_ELEVATION (mean_z, l0, tr: the last iteration's); else OK;
+#   * codes: 1 a member of an OK patch; 0 judged and not a member, or any point of a REJECTED patch; 2 not judged (out of range, SPARSE,
+#     DEGENERATE); 255 non-finite.  The patch table's rows of SPARSE and DEGENERATE patches carry zeros behind n_points.
+GROUND_EMPTY, GROUND_OK, GROUND_SPARSE, GROUND_DEGENERATE, GROUND_REJECTED_UPRIGHT, GROUND_REJECTED_ELEVATION = 0, 1, 2, 3, 4, 5
+GROUND_CODE_NOT, GROUND_CODE_GROUND, GROUND_CODE_NOT_JUDGED, GROUND_CODE_NON_FINITE = 0, 1, 2, 255
+GROUND_MAX_FRAMES = 65535
+GROUND_MAX_RINGS, GROUND_MAX_SECTORS, GROUND_MAX_LPR, GROUND_MAX_ITERS = 64, 512, 64, 16
+GROUND_WAVE_POINTS = 64     # ERASOR_GROUND_WAVE_POINTS: a patch of at most this many points is fitted by one wavefront
+GROUND_SMALL_POINTS = 1024  # ERASOR_GROUND_SMALL_POINTS: ... by a workgroup with the small LDS allotment; beyond, the large one
+GROUND_LDS_POINTS = 4096    # ERASOR_GROUND_LDS_POINTS: a patch beyond this streams from memory in every iteration
+GROUND_WORK_BUDGET = 256 << 20
+GROUND_ROW_FIELDS = ("n_points", "n_non_finite", "n_out_of_range", "n_judged", "n_ground", "n_ground_dynamic", "n_patches", "n_sparse",
+                     "n_degenerate", "n_rejected_upright", "n_rejected_elevation")
+GROUND_VOTES_ROW_FIELDS = GROUND_ROW_FIELDS + ("n_gathered",)
+GROUND_VOTES_RESULT_FIELDS = ("n_points", "n_ground", "n_ground_dynamic", "n_ground_static", "n_unseen", "n_kept", "n_gathered", "n_judged")
+GROUND_DEFAULTS = {"num_lpr": 10, "th_seeds": 0.5, "th_dist": 0.15, "iters": 3, "min_points": 10, "min_z": -3.03, "uprightness": 0.707}
+GROUND_PATCH_DTYPE = np.dtype([("status", np.uint32), ("n_points", np.uint32), ("n_ground", np.uint32), ("reserved", np.uint32),
+                               ("normal", np.float64, 3), ("d", np.float64), ("mean_z", np.float64), ("eig", np.float64, 3)])  # erasor_ground_patch
+
+
+def ground_grid(n_rings=20, n_sectors=64, min_range=0.5, max_range=80.0):
+    """A uniform patch grid: n_sectors columns of equal azimuth (visibility_grid's column table for that width) and n_rings rings of equal
+    width, ring_edge[i] = min_range + ((max_range - min_range) * i) / n_rings -- the driver forms both by the same expressions"""
+    import math
+    R, S = int(n_rings), int(n_sectors)
+    if S % 8 or not 8 <= S <= GROUND_MAX_SECTORS or not 1 <= R <= GROUND_MAX_RINGS:
+        raise ValueError("ground_grid: n_sectors must be a multiple of 8 within 8 .. 512, n_rings within 1 .. 64")
+    M = S // 8
+    col = np.array([math.tan(((math.pi / 4.0) * k) / M) for k in range(1, M)], np.float64)
+    edge = np.array([float(min_range) + ((float(max_range) - float(min_range)) * i) / R for i in range(R + 1)], np.float64)
+    return check_ground_grid({"n_sectors": S, "col_tan": col, "ring_edge": edge})
+
+
+def check_ground_grid(grid):
+    S = int(grid["n_sectors"])
+    col = np.ascontiguousarray(grid["col_tan"], np.float64).reshape(-1)
+    edge = np.ascontiguousarray(grid["ring_edge"], np.float64).reshape(-1)
+    if S % 8 or not 8 <= S <= GROUND_MAX_SECTORS:
+        raise ValueError("ground: n_sectors must be a multiple of 8 within 8 .. 512")
+    if not 2 <= len(edge) <= GROUND_MAX_RINGS + 1:
+        raise ValueError("ground: ring_edge has n_rings + 1 entries, n_rings within 1 .. 64")
+    if len(col) != S // 8 - 1:
+        raise ValueError("ground: col_tan has n_sectors / 8 - 1 entries")
+    if not ((col > 0) & (col < 1)).all() or not (np.diff(col) > 0).all():
+        raise ValueError("ground: col_tan must be strictly increasing within (0, 1)")
+    if not np.isfinite(edge).all() or not (np.diff(edge) > 0).all() or not edge[0] >= 0:
+        raise ValueError("ground: ring_edge must be finite, strictly increasing and start at >= 0")
+    return {"n_sectors": S, "col_tan": col, "ring_edge": edge}
+
+
+def _ground_args(grid, num_lpr, th_seeds, th_dist, iters, min_points, min_z, uprightness, elevation, flatness, n_frames):
+    g = check_ground_grid(ground_grid() if grid is None else grid)
+    R = len(g["ring_edge"]) - 1
+    if not (isinstance(num_lpr, (int, np.integer)) and 1 <= num_lpr <= GROUND_MAX_LPR):
+        raise ValueError("ground: num_lpr must be within 1 .. 64")
+    if not (isinstance(iters, (int, np.integer)) and 1 <= iters <= GROUND_MAX_ITERS):
+        raise ValueError("ground: iters must be within 1 .. 16")
+    if not (isinstance(min_points, (int, np.integer)) and 3 <= min_points <= 0xFFFFFFFF):
+        raise ValueError("ground: min_points must be at least 3")
+    if not all(np.isfinite(v) for v in (th_seeds, th_dist, min_z, uprightness)):
+        raise ValueError("ground: th_seeds, th_dist, min_z and uprightness must be finite")
+    el = np.full(R, np.inf) if elevation is None else np.ascontiguousarray(elevation, np.float64).reshape(-1)
+    fl = np.zeros(R) if flatness is None else np.ascontiguousarray(flatness, np.float64).reshape(-1)
+    if len(el) != R or len(fl) != R or np.isnan(el).any() or np.isnan(fl).any():
+        raise ValueError("ground: elevation and flatness have n_rings entries, none of them NaN")
+    if n_frames > GROUND_MAX_FRAMES:
+        raise ValueError("ground: more than 65535 frames")
+    prm = {"num_lpr": int(num_lpr), "th_seeds": float(th_seeds), "th_dist": float(th_dist), "iters": int(iters), "min_points": int(min_points),
+           "min_z": float(min_z), "uprightness": float(uprightness), "elevation": el, "flatness": fl}
+    return g, R, prm
+
+
+def ground_patch_of(x, y, grid):
+    """(ring, sector) of points in a lidar frame (float64 arrays of finite values), ring = -1 where the point is out of range: THE patch
+    mapping, written down once"""
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    edge = grid["ring_edge"]
+    sec = visibility_column(x, y, grid["col_tan"], grid["n_sectors"])
+    r = np.sqrt(x * x + y * y)
+    ring = np.searchsorted(edge, r, side="right").astype(np.int64) - 1
+    ring[(sec < 0) | (ring < 0) | (ring >= len(edge) - 1)] = -1
+    return ring, sec
+
+
+def _ground_plane(S, n):
+    """mean, covariance, trace and (when the trace is positive) the sorted eigen-solve of nine raw moments S over n members, in Python floats"""
+    nn = float(n)
+    mx, my, mz = float(S[0]) / nn, float(S[1]) / nn, float(S[2]) / nn
+    cxx, cxy, cxz = float(S[3]) / nn - mx * mx, float(S[4]) / nn - mx * my, float(S[5]) / nn - mx * mz
+    cyy, cyz, czz = float(S[6]) / nn - my * my, float(S[7]) / nn - my * mz, float(S[8]) / nn - mz * mz
+    tr = (cxx + cyy) + czz
+    if not tr > 0:
+        return None
+    A = [[cxx, cxy, cxz], [cxy, cyy, cyz], [cxz, cyz, czz]]
+    V = _jacobi3(A)
+    col = sorted(range(3), key=lambda j: (A[j][j], j))
+    l = [A[j][j] for j in col]
+    nx, ny, nz = V[0][col[0]], V[1][col[0]], V[2][col[0]]
+    if nz < 0:
+        nx, ny, nz = -nx, -ny, -nz
+    d = -((nx * mx + ny * my) + nz * mz)
+    return (nx, ny, nz), d, mz, l, tr
+
+
+def _ground_gates(nz, mean_z, l0, tr, ring, prm):
+    if nz < prm["uprightness"]:
+        return GROUND_REJECTED_UPRIGHT
+    if mean_z > prm["elevation"][ring] and not (l0 / tr <= prm["flatness"][ring]):
+        return GROUND_REJECTED_ELEVATION
+    return GROUND_OK
+
+
+def ground_fit(p64, ring, prm):
+    """R-GPF on one patch: p64 its points (m, 3) float64 in patch order, m >= min_points.  Returns (status, members (bool), plane or None),
+    plane = ((nx, ny, nz), d, mean_z, [l0, l1, l2], trace) of the last iteration"""
+    x, y, z = p64[:, 0], p64[:, 1], p64[:, 2]
+    m = len(z)
+    none = np.zeros(m, bool)
+    cand = np.flatnonzero(z >= prm["min_z"])
+    if len(cand) == 0:
+        return GROUND_DEGENERATE, none, None
+    lowest = cand[np.argsort(z[cand], kind="stable")][: prm["num_lpr"]]  # (a stable sort of z: ascending by (z, j))
+    s = 0.0
+    for v in z[lowest].tolist():
+        s = s + v
+    lpr = s / float(len(lowest))
+    mem = (z >= prm["min_z"]) & (z < lpr + prm["th_seeds"])
+    rows = np.stack([x, y, z, x * x, x * y, x * z, y * y, y * z, z * z], 1)
+    plane = None
+    for _ in range(prm["iters"]):
+        n = int(mem.sum())
+        if n < 3:
+            return GROUND_DEGENERATE, none, None
+        plane = _ground_plane(refine_tree_sum(np.where(mem[:, None], rows, 0.0)), n)
+        if plane is None:
+            return GROUND_DEGENERATE, none, None
+        (nx, ny, nz), d = plane[0], plane[1]
+        with np.errstate(all="ignore"):
+            mem = ((nx * x + ny * y) + nz * z) + d < prm["th_dist"]
+    return _ground_gates(plane[0][2], plane[2], plane[3][0], plane[4], ring, prm), mem, plane
+
+
+def _tree_sum_brute(vals):
+    """refine_tree_sum of one column, in Python floats"""
+    total = 0.0
+    for b in range(0, len(vals), REFINE_CHUNK):
+        c = vals[b:b + REFINE_CHUNK] + [0.0] * (REFINE_CHUNK - len(vals[b:b + REFINE_CHUNK]))
+        s = REFINE_CHUNK // 2
+        while s >= 1:
+            c = [c[i] + c[i + s] for i in range(s)]
+            s //= 2
+        total = total + c[0]
+    return total
+
+
+def ground_fit_brute(p64, ring, prm):
+    """ground_fit point by point in Python floats"""
+    P = [[float(v) for v in r] for r in np.asarray(p64, np.float64).reshape(-1, 3).tolist()]
+    m = len(P)
+    none = np.zeros(m, bool)
+    cand = sorted((P[j][2] + 0.0, j) for j in range(m) if P[j][2] >= prm["min_z"])  # (-0.0 + 0.0 = +0.0: tuples compare z, then j)
+    if not cand:
+        return GROUND_DEGENERATE, none, None
+    k = min(prm["num_lpr"], len(cand))
+    s = 0.0
+    for zj, _ in cand[:k]:
+        s = s + zj
+    lpr = s / float(k)
+    mem = [p[2] >= prm["min_z"] and p[2] < lpr + prm["th_seeds"] for p in P]
+    plane = None
+    for _ in range(prm["iters"]):
+        n = sum(mem)
+        if n < 3:
+            return GROUND_DEGENERATE, none, None
+        cols = []
+        for a, b in ((0, None), (1, None), (2, None), (0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)):
+            cols.append(_tree_sum_brute([(p[a] if b is None else p[a] * p[b]) if g else 0.0 for p, g in zip(P, mem)]))
+        plane = _ground_plane(cols, n)
+        if plane is None:
+            return GROUND_DEGENERATE, none, None
+        (nx, ny, nz), d = plane[0], plane[1]
+        mem = [((nx * p[0] + ny * p[1]) + nz * p[2]) + d < prm["th_dist"] for p in P]
+    return _ground_gates(plane[0][2], plane[2], plane[3][0], plane[4], ring, prm), np.array(mem, bool).reshape(-1), plane
+
+
+def _ground_scans(scans, grid, num_lpr, th_seeds, th_dist, iters, min_points, min_z, uprightness, elevation, flatness, patches, fit):
+    g, R, prm = _ground_args(grid, num_lpr, th_seeds, th_dist, iters, min_points, min_z, uprightness, elevation, flatness, len(scans))
+    S = g["n_sectors"]
+    table = np.zeros((len(scans), R, S), GROUND_PATCH_DTYPE)
+    codes, rows = [], []
+    for f, scan in enumerate(scans):
+        s = np.ascontiguousarray(np.asarray(scan, np.float32).reshape(-1, 4))
+        fin = np.isfinite(s[:, :3]).all(1)
+        p64 = np.where(fin[:, None], s[:, :3], np.float32(1)).astype(np.float64)
+        ring, sec = ground_patch_of(p64[:, 0], p64[:, 1], g)
+        ring[~fin] = -1
+        code = np.full(len(s), GROUND_CODE_NOT_JUDGED, np.uint8)
+        code[~fin] = GROUND_CODE_NON_FINITE
+        inr = np.flatnonzero(ring >= 0)
+        key = ring[inr] * S + sec[inr]
+        order = inr[np.argsort(key, kind="stable")]  # (patch by patch, each in scan order)
+        cnt = {st: 0 for st in (GROUND_SPARSE, GROUND_DEGENERATE, GROUND_REJECTED_UPRIGHT, GROUND_REJECTED_ELEVATION)}
+        n_judged = 0
+        pos = 0
+        for k, m in zip(*np.unique(key, return_counts=True)):
+            idx = order[pos:pos + m]
+            pos += m
+            rg, sc = int(k) // S, int(k) % S
+            row = table[f, rg, sc]
+            row["n_points"] = m
+            if int(m) < prm["min_points"]:
+                row["status"] = GROUND_SPARSE
+                cnt[GROUND_SPARSE] += 1
+                continue
+            status, mem, plane = fit(p64[idx], rg, prm)
+            row["status"] = status
+            if status == GROUND_DEGENERATE:
+                cnt[status] += 1
+                continue
+            n_judged += int(m)
+            row["normal"], row["d"], row["mean_z"], row["eig"] = plane[0], plane[1], plane[2], plane[3]
+            code[idx] = GROUND_CODE_NOT
+            if status == GROUND_OK:
+                code[idx[mem]] = GROUND_CODE_GROUND
+                row["n_ground"] = int(mem.sum())
+            else:
+                cnt[status] += 1
+        gr = code == GROUND_CODE_GROUND
+        rows.append(dict(zip(GROUND_ROW_FIELDS, [len(s), int((~fin).sum()), int((fin & (ring < 0)).sum()), n_judged, int(gr.sum()),
+                                                 int((gr & _decode(s[:, 3])[2]).sum()), len(np.unique(key)), cnt[GROUND_SPARSE],
+                                                 cnt[GROUND_DEGENERATE], cnt[GROUND_REJECTED_UPRIGHT], cnt[GROUND_REJECTED_ELEVATION]])))
+        codes.append(code)
+    res = {"n_frames": len(scans)}
+    for k in GROUND_ROW_FIELDS:
+        res[k] = int(sum(r[k] for r in rows))
+    return (np.concatenate(codes) if codes else np.zeros(0, np.uint8)), rows, res, (table if patches else None)
+
+
+def ground_scans(scans, grid=None, num_lpr=10, th_seeds=0.5, th_dist=0.15, iters=3, min_points=10, min_z=-3.03, uprightness=0.707,
+                 elevation=None, flatness=None, patches=False):
+    """Every scan's ground (Erasor.ground_scans): the contract above.  scans: XYZI rows per frame in the lidar frame; grid: ground_grid()
+    or a dict with n_sectors, col_tan and ring_edge (None: ground_grid()); elevation, flatness: float64 tables of n_rings entries (None:
+    +inf and 0, both gates off).  Returns (codes uint8, all frames one after another; a row per frame with GROUND_ROW_FIELDS, where
+    n_ground_dynamic counts the ground points labelled 252 .. 259; their sums with n_frames; with `patches` the table [n_frames, n_rings,
+    n_sectors] of GROUND_PATCH_DTYPE, else None)."""
+    return _ground_scans(scans, grid, num_lpr, th_seeds, th_dist, iters, min_points, min_z, uprightness, elevation, flatness, patches, ground_fit)
+
+
+def ground_scans_brute(scans, grid=None, num_lpr=10, th_seeds=0.5, th_dist=0.15, iters=3, min_points=10, min_z=-3.03, uprightness=0.707,
+                       elevation=None, flatness=None, patches=False):
+    """ground_scans() with every patch fitted point by point in plain Python floats, for small inputs: the check of the vectorised text"""
+    return _ground_scans(scans, grid, num_lpr, th_seeds, th_dist, iters, min_points, min_z, uprightness, elevation, flatness, patches,
+                         ground_fit_brute)
+
+
+def ground_gather(map_xyzi, T_body2origin, T_lidar2body=None, grid=None):
+    """What every frame sees of the map, as ground_votes segments it: every finite map point put into the frame's lidar frame by
+    visibility_transforms' row in float64, q = ((r0 x + r1 y) + r2 z) + t, and rounded to float32; the points whose rounded coordinates
+    are finite and whose ring is in range are kept in map order with the map point's intensity.  Returns (clouds, indices): per frame the
+    (k, 4) float32 cloud and the map indices of its rows."""
+    g = check_ground_grid(ground_grid() if grid is None else grid)
+    c = np.ascontiguousarray(np.asarray(map_xyzi, np.float32).reshape(-1, 4))
+    n_f = len(np.asarray(T_body2origin, np.float32).reshape(-1, 16))
+    m, _ = visibility_transforms(np.zeros((0, 4, 4), np.float32) if n_f == 0 else T_body2origin, T_lidar2body)
+    pfin = np.isfinite(c[:, :3]).all(1)
+    p = np.where(pfin[:, None], c[:, :3], np.float32(0)).astype(np.float64)
+    clouds, indices = [], []
+    for f in range(n_f):
+        with np.errstate(all="ignore"):
+            q = np.stack([((m[f, 4 * r] * p[:, 0] + m[f, 4 * r + 1] * p[:, 1]) + m[f, 4 * r + 2] * p[:, 2]) + m[f, 4 * r + 3] for r in range(3)],
+                         1).astype(np.float32)
+        ok = pfin & np.isfinite(q).all(1)
+        q64 = np.where(ok[:, None], q, np.float32(1)).astype(np.float64)
+        ring, _ = ground_patch_of(q64[:, 0], q64[:, 1], g)
+        idx = np.flatnonzero(ok & (ring >= 0))
+        clouds.append(np.concatenate([q[idx], c[idx, 3:4]], 1).astype(np.float32).reshape(-1, 4))
+        indices.append(idx)
+    return clouds, indices
+
+
+def ground_decide(votes, min_votes, ratio):
+    """the map's ground points (bool): ground >= min_votes and (double)ground > ratio * (double)seen"""
+    v = np.asarray(votes).reshape(-1, 2)
+    return (v[:, 1].astype(np.int64) >= int(min_votes)) & (v[:, 1].astype(np.float64) > np.float64(ratio) * v[:, 0].astype(np.float64))
+
+
+def _ground_votes(scans_fn, map_xyzi, T_body2origin, T_lidar2body, grid, kw, min_votes, ratio, keep):
+    if not 0 <= int(min_votes) <= 0xFFFFFFFF or not np.isfinite(ratio):
+        raise ValueError("ground: min_votes must fit 32 bits and ratio be finite")
+    c = np.ascontiguousarray(np.asarray(map_xyzi, np.float32).reshape(-1, 4))
+    clouds, indices = ground_gather(c, T_body2origin, T_lidar2body, grid)
+    codes, rows, res, _ = scans_fn(clouds, grid, **kw)
+    votes = np.zeros((len(c), 2), np.uint16)
+    pos = 0
+    for f, idx in enumerate(indices):
+        cf = codes[pos:pos + len(idx)]
+        pos += len(idx)
+        votes[idx[cf <= GROUND_CODE_GROUND], 0] += 1
+        votes[idx[cf == GROUND_CODE_GROUND], 1] += 1
+        rows[f]["n_gathered"] = len(idx)
+    gr = ground_decide(votes, min_votes, ratio)
+    dyn = _decode(c[:, 3])[2]
+    kept = gr if keep else ~gr
+    out = {"n_points": len(c), "n_ground": int(gr.sum()), "n_ground_dynamic": int((gr & dyn).sum()), "n_ground_static": int((gr & ~dyn).sum()),
+           "n_unseen": int((votes[:, 0] == 0).sum()), "n_kept": int(kept.sum()), "n_gathered": res["n_points"], "n_judged": res["n_judged"]}
+    return votes, gr.astype(np.uint8), c[kept].copy(), rows, out
+
+
+def ground_votes(map_xyzi, T_body2origin, T_lidar2body=None, grid=None, num_lpr=10, th_seeds=0.5, th_dist=0.15, iters=3, min_points=10,
+                 min_z=-3.03, uprightness=0.707, elevation=None, flatness=None, min_votes=1, ratio=0.5, keep=1, work_budget_bytes=0):
+    """The map's ground points by vote (Erasor.ground_votes): ground_gather's cloud of every frame is segmented exactly as a scan
+    (ground_scans); a map point gets seen += 1 where it was judged (code 0 or 1) and ground += 1 where its code was 1; it is ground iff
+    ground >= min_votes and (double)ground > ratio * (double)seen.  work_budget_bytes only sizes the device's batches: the result does not
+    depend on it.  Returns (votes [n, 2] uint16: seen, ground; mask uint8, 1 = ground; the ground rows (keep = 1) or the rest (keep = 0)
+    in map order; a row per frame with GROUND_VOTES_ROW_FIELDS; a dict with GROUND_VOTES_RESULT_FIELDS)."""
+    kw = dict(num_lpr=num_lpr, th_seeds=th_seeds, th_dist=th_dist, iters=iters, min_points=min_points, min_z=min_z, uprightness=uprightness,
+              elevation=elevation, flatness=flatness)
+    return _ground_votes(ground_scans, map_xyzi, T_body2origin, T_lidar2body, grid, kw, min_votes, ratio, keep)
+
+
+def ground_votes_brute(map_xyzi, T_body2origin, T_lidar2body=None, grid=None, num_lpr=10, th_seeds=0.5, th_dist=0.15, iters=3, min_points=10,
+                       min_z=-3.03, uprightness=0.707, elevation=None, flatness=None, min_votes=1, ratio=0.5, keep=1, work_budget_bytes=0):
+    """ground_votes() over ground_scans_brute, for small inputs"""
+    kw = dict(num_lpr=num_lpr, th_seeds=th_seeds, th_dist=th_dist, iters=iters, min_points=min_points, min_z=min_z, uprightness=uprightness,
+              elevation=elevation, flatness=flatness)
+    return _ground_votes(ground_scans_brute, map_xyzi, T_body2origin, T_lidar2body, grid, kw, min_votes, ratio, keep)

@@ -821,6 +821,133 @@ int erasor_hip_carve_map(erasor_hip_handle *h, const void *scans_xyzi, size_t n_
                          uint16_t *votes, float *logodds, uint8_t *keep_mask, float *kept_xyzi, size_t cap_points, erasor_carve_row *rows,
                          erasor_carve_result *res);
 
+/* ---- every scan's ground, patch by patch; the map's ground points by vote -------------------------------------------------------
+ * restates: R-GPF, erasor.cpp:183-294 (extract_initial_seeds_, estimate_plane_, the loop of extract_ground), which the reference runs
+ * per bin, inside a step, for the bins the Scan Ratio Test reverts.  Here it runs on every polar patch of every scan, as the author's
+ * follow-up (Patchwork) runs it, so that "which of these points are ground?" has an answer outside a step.
+ * Where the contract departs from the reference:
+ *   - the orders are defined: a patch's points in scan order, the seeds' candidates by (z, index), the moments by the summing rule of
+ *     erasor_hip_refine_poses_* (chunks of 256, a halving tree, chunks in sequence); the reference leaves them to std::sort and PCL;
+ *   - float64 on the float32 coordinates with a cyclic Jacobi solve (erasor_hip_normals_*'s); the reference fits in float32 with
+ *     Eigen's JacobiSVD; the covariance is taken from raw moments over n, where PCL centres first and divides by n - 1 -- the
+ *     eigenvectors are the same in exact arithmetic;
+ *   - the gates: uprightness (erasor.cpp:286 carries it commented out), and elevation / flatness per ring (Patchwork's); min_z is
+ *     the reference's min_h in the lidar frame.
+ * The contract; the normative text is erasor_amd/evalmap.py (ground_scans / ground_votes and their *_brute twins), which the device
+ * equals byte for byte.  Every operation is a separate IEEE operation in the order written.
+ * Patch.
+ *   - The sector of (x, y) is erasor_visibility's column over col_tan with n_sectors for the width.
+ *   - r = sqrt(x x + y y); ring = (the number of ring_edge entries <= r) - 1.
+ *   - The gates, in this order: a non-finite coordinate (code 255); on the axis or a ring outside 0 .. n_rings - 1 (out of range).
+ *   - A patch is (frame, ring, sector).  Its points are kept in scan order.
+ * Fit, per patch.
+ *   - Fewer than min_points points: SPARSE.
+ *   - The candidates are the points with z >= min_z, ascending by (z, index), -0.0 equal to +0.0.
+ *   - lpr = (((0.0 + z_0) + z_1) + ...) / k over the first k = min(num_lpr, candidates).  No candidate: DEGENERATE.
+ *   - The seeds: z >= min_z and z < lpr + th_seeds.
+ *   - iters times: n members and the nine raw moments x y z xx xy xz yy yz zz over all the patch's points (a non-member holds +0.0);
+ *     n < 3: DEGENERATE; mean = S / n; cov_ab = S_ab / n - mean_a mean_b; tr = (cxx + cyy) + czz; not tr > 0: DEGENERATE; the
+ *     eigenvalues ascending by (value, column); the normal is the first one's column, negated iff nz < 0;
+ *     d = -((nx mx + ny my) + nz mz); the new members: ((nx x + ny y) + nz z) + d < th_dist (one-sided, as the reference).
+ *   - Then nz < uprightness: REJECTED_UPRIGHT; else mean_z > elevation[ring] and not (l0 / tr <= flatness[ring]): REJECTED_ELEVATION.
+ * Codes, one uint8 per point: 1 a member of an OK patch; 0 judged and not a member, or any point of a REJECTED patch; 2 not judged
+ * (out of range, SPARSE, DEGENERATE); 255 non-finite. */
+typedef struct erasor_ground {
+    uint32_t n_rings;          /* 1 .. 64 */
+    uint32_t n_sectors;        /* a multiple of 8 within 8 .. 512 */
+    const double *ring_edge;   /* n_rings + 1 finite, strictly increasing radii, the first >= 0 */
+    const double *col_tan;     /* n_sectors / 8 - 1 tangents, strictly increasing within (0, 1) (erasor_visibility's) */
+    const double *elevation;   /* n_rings entries, none NaN; NULL: +inf, the gate is off */
+    const double *flatness;    /* n_rings entries, none NaN; NULL: 0 */
+    uint32_t num_lpr;          /* 1 .. 64 */
+    uint32_t iters;            /* 1 .. 16 */
+    uint32_t min_points;       /* >= 3 */
+    uint32_t min_votes;        /* the map form: a ground point has at least this many ground votes ... */
+    double th_seeds, th_dist, min_z, uprightness;  /* finite */
+    double ratio;              /* ... and (double)ground > ratio * (double)seen; finite */
+    uint32_t keep;             /* the map form's kept_xyzi: 1 the ground rows, 0 the rest */
+    uint32_t reserved;         /* 0 */
+    uint64_t work_budget_bytes;  /* the map form: frames go in batches of n_map * 16 bytes each within this; 0: ERASOR_GROUND_WORK_BUDGET */
+} erasor_ground;
+#define ERASOR_GROUND_MAX_FRAMES 65535
+#define ERASOR_GROUND_MAX_RINGS 64
+#define ERASOR_GROUND_MAX_SECTORS 512
+#define ERASOR_GROUND_MAX_LPR 64
+#define ERASOR_GROUND_MAX_ITERS 16
+#define ERASOR_GROUND_WORK_BUDGET (256ull << 20)
+/* the fit's size classes: a patch of at most WAVE_POINTS points is fitted by one wavefront, a larger one by a workgroup whose LDS holds
+ * SMALL_POINTS or LDS_POINTS coordinates; a patch beyond LDS_POINTS streams from memory in every pass (the same bytes) */
+#define ERASOR_GROUND_WAVE_POINTS 64u
+#define ERASOR_GROUND_SMALL_POINTS 1024u
+#define ERASOR_GROUND_LDS_POINTS 4096u
+enum { ERASOR_GROUND_EMPTY = 0, ERASOR_GROUND_OK = 1, ERASOR_GROUND_SPARSE = 2, ERASOR_GROUND_DEGENERATE = 3,
+       ERASOR_GROUND_REJECTED_UPRIGHT = 4, ERASOR_GROUND_REJECTED_ELEVATION = 5 };
+enum { ERASOR_GROUND_CODE_NOT = 0, ERASOR_GROUND_CODE_GROUND = 1, ERASOR_GROUND_CODE_NOT_JUDGED = 2, ERASOR_GROUND_CODE_NON_FINITE = 255 };
+
+typedef struct erasor_ground_row {  /* one frame */
+    uint64_t n_points;              /* points given (the map form: gathered) */
+    uint64_t n_non_finite;          /* ... with a non-finite coordinate */
+    uint64_t n_out_of_range;        /* ... on the axis or in no ring */
+    uint64_t n_judged;              /* ... of OK and REJECTED patches: code 0 or 1 */
+    uint64_t n_ground;              /* ... code 1 */
+    uint64_t n_ground_dynamic;      /* ... of those labelled 252 .. 259 */
+    uint64_t n_patches;             /* non-empty patches */
+    uint64_t n_sparse, n_degenerate, n_rejected_upright, n_rejected_elevation;  /* ... by status */
+    uint64_t n_gathered;            /* the map form: map points gathered into this frame; erasor_hip_ground_scans: 0 */
+} erasor_ground_row;
+
+typedef struct erasor_ground_patch {  /* one (frame, ring, sector) */
+    uint32_t status;     /* ERASOR_GROUND_EMPTY .. REJECTED_ELEVATION */
+    uint32_t n_points;
+    uint32_t n_ground;   /* OK: the members */
+    uint32_t reserved;
+    double normal[3], d, mean_z, eig[3];  /* OK and REJECTED: the last iteration's plane, its members' mean z, the eigenvalues ascending; else 0 */
+} erasor_ground_patch;
+
+typedef struct erasor_ground_result {
+    uint64_t n_frames;
+    uint64_t n_points, n_non_finite, n_out_of_range, n_judged, n_ground, n_ground_dynamic, n_patches, n_sparse, n_degenerate,
+        n_rejected_upright, n_rejected_elevation;  /* the rows' sums */
+    /* the map form; erasor_hip_ground_scans: 0 */
+    uint64_t n_map_points;
+    uint64_t n_map_ground;          /* map points decided ground */
+    uint64_t n_map_ground_dynamic;  /* ... by label, as erasor_density_result counts them */
+    uint64_t n_map_ground_static;
+    uint64_t n_map_unseen;          /* map points no frame judged */
+    uint64_t n_kept;                /* rows of kept_xyzi: n_map_ground (keep = 1) or the rest (keep = 0) */
+} erasor_ground_result;
+
+/* Every scan's ground (R-GPF, erasor.cpp:183-294, per polar patch; the departures -- defined orders, float64, the gates -- above).
+ * Scans and offsets as erasor_hip_carve_clouds takes them, taken as given in the lidar frame.  Every output is a host buffer and may be
+ * NULL: codes (n_scan_points uint8), rows (n_frames), patches (n_frames x n_rings x n_sectors, empty patches EMPTY and zeros), res.
+ * n_frames == 0 and n_scan_points == 0 are fine.  Works in the evaluator's own scratch.
+ * ERASOR_E_INVALID, the message naming the argument: params NULL; n_rings outside 1 .. 64; n_sectors not a multiple of 8 within
+ * 8 .. 512; ring_edge or col_tan NULL, not finite, not strictly increasing, ring_edge[0] < 0, col_tan outside (0, 1); a NaN in elevation
+ * or flatness; num_lpr outside 1 .. 64; iters outside 1 .. 16; min_points < 3; th_seeds, th_dist, min_z, uprightness or ratio not finite;
+ * more than 65535 frames; offsets NULL or not monotone; NULL scans; more than 2^30 points.  ERASOR_E_STATE: a step in flight. */
+int erasor_hip_ground_scans(erasor_hip_handle *h, const void *scans_xyzi, size_t n_scan_points, const uint64_t *offsets, size_t n_frames,
+                            int scans_are_device, const erasor_ground *params, uint8_t *codes, erasor_ground_row *rows,
+                            erasor_ground_patch *patches, erasor_ground_result *res);
+/* The map's ground points by vote (the same R-GPF restatement of erasor.cpp:183-294 and the same departures).  For every frame, every
+ * finite map point goes into the frame's lidar frame by erasor_hip_visibility_clouds' transform, q = ((r0 x + r1 y) + r2 z) + t in
+ * float64 rounded to float32; the points whose rounded coordinates are finite and have a patch are kept in map order (a stable
+ * compaction) and that cloud is segmented exactly as a scan.  A map point gets seen += 1 where it was judged and ground += 1 where its
+ * code was 1; it is ground iff ground >= min_votes and (double)ground > ratio * (double)seen.  Frames go in index order, in batches of
+ * work_budget_bytes / (n_map * 16) frames, at least one: the result does not depend on the budget.
+ * Outputs, host buffers that may be NULL: votes (n_map x 2 uint16: seen, ground), ground_mask (n_map uint8, 1 = ground), kept_xyzi (the
+ * ground rows or the rest by params->keep, in map order; cap_points rows, ERASOR_E_CAPACITY after res is filled if they do not fit),
+ * rows (n_frames), res.  ERASOR_E_INVALID as erasor_hip_ground_scans, and: T_body2origin NULL with frames, a non-finite pose entry or
+ * frame transform (the message names the frame), a NULL map with points. */
+int erasor_hip_ground_votes_clouds(erasor_hip_handle *h, const void *map_xyzi, size_t n_map, int map_is_device,
+                                   const float T_lidar2body[16] /* NULL: identity */, const float *T_body2origin, size_t n_frames,
+                                   const erasor_ground *params, uint16_t *votes, uint8_t *ground_mask, float *kept_xyzi, size_t cap_points,
+                                   erasor_ground_row *rows, erasor_ground_result *res);
+/* the same for the handle's current map (compacted on the device as erasor_hip_carve_map does, never copied to the host and not
+ * modified).  ERASOR_E_STATE also: no map. */
+int erasor_hip_ground_votes_map(erasor_hip_handle *h, const float T_lidar2body[16], const float *T_body2origin, size_t n_frames,
+                                const erasor_ground *params, uint16_t *votes, uint8_t *ground_mask, float *kept_xyzi, size_t cap_points,
+                                erasor_ground_row *rows, erasor_ground_result *res);
+
 /* ---- every scan's points labelled static or moving from a cleaned map ---------------------------------------------------------
  * replaces: what users of a cleaned map do on the host afterwards -- a KD-tree over the cleaned map, a radius test per scan point, the
  * scan's moving points dropped (automatic moving-object-segmentation labels, cleaned scans for re-mapping); the reference itself stops
