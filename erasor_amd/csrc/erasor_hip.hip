@@ -4040,6 +4040,11 @@ int erasor_hip_drop_announced(erasor_hip_handle *h) {
     q_drain(h);
     return ERASOR_OK;
 }
+int erasor_hip_announced_count(const erasor_hip_handle *h, int *n) {
+    if (!h || !n) return ERASOR_E_INVALID;
+    *n = h->npend + (h->ann.valid ? 1 : 0);  // (host state only: allowed while a step is in flight)
+    return ERASOR_OK;
+}
 int erasor_hip_overlap_auto(erasor_hip_handle *h, int *mode, double *plain_period_us, double *overlapped_period_us) {
     if (!h) return ERASOR_E_INVALID;
     if (mode) *mode = h->ova.mode;

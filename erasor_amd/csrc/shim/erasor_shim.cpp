@@ -370,32 +370,51 @@ void OfflineMapUpdater::announce_next_deferred(int seq, const Cloud &lidar, cons
     def_cloud_ = &lidar;
     def_odom_ = odom;
     def_seq_ = seq;
+    announce_status_ = PENDING;
 }
-// the deferred announcement, made now -- inside a callback_node (stack_count_ counts that callback already), while its step runs on the GPU.
-// It is about the node behind the last one announced (with one node ahead: the next callback)
+// The capacity test of an announcement, made BEFORE the gate is looked at: max_ahead_ nodes announced beyond the callback in front
+// (upcoming_cb; its own announcement does not count: announce_next(k + 1) in front of callback_node(k) is one node ahead), or as many in
+// all as the library holds beside a step in flight.  A GATED node is refused as well while outstanding() >= lookahead(): a caller that
+// retries on `0 && outstanding() >= lookahead()` must never retry a node the updater has moved past.
+bool OfflineMapUpdater::full(int upcoming_cb, bool gated) const {
+    const int total = (int)ahead_.size();
+    const int beyond = total - ((total && ahead_.front().cb_no <= upcoming_cb) ? 1 : 0);
+    return beyond >= max_ahead_ || total >= 7 || (gated && total >= max_ahead_);
+}
+void OfflineMapUpdater::forget_announced() {
+    n_dropped_ += ahead_.size();
+    ahead_.clear();
+}
+// the deferred announcement, made now -- inside a callback_node (stack_count_ counts that callback already, and its own announcement is
+// taken), while its step runs on the GPU.  It is about the node behind the last one announced or gated (with nothing ahead: the next callback)
 void OfflineMapUpdater::stage_deferred() {
     if (!def_cloud_) return;
     const Cloud &lidar = *def_cloud_;
     def_cloud_ = nullptr;
     const int cb_no = std::max(ahead_upto_, stack_count_) + 1;
-    if (cb_no % cfg_.params.removal_interval != 0) {  // gated out (OMU.cpp:206-209)
-        ahead_upto_ = cb_no;
+    const bool gated = cb_no % cfg_.params.removal_interval != 0;  // (OMU.cpp:206-209)
+    if (full(stack_count_, gated)) {  // nothing moves: the caller hands the node over again
+        announce_status_ = FULL;
         return;
     }
-    if (n_ahead_ >= max_ahead_) return;  // as many ahead as the updater takes
+    if (gated) {
+        ahead_upto_ = cb_no;
+        announce_status_ = GATED;
+        return;
+    }
     float Tl[16], Tb[16];
     mat16(tf_lidar2body_, Tl);
     mat16(erasor_utils::geoPose2eigen(def_odom_), Tb);
     uint64_t t = 0;
     check(h_, erasor_hip_prefetch_node_rows(h_, lidar.points.data(), lidar.size(), kRowStride, kRowIntensity, Tl, Tb, &t), "erasor_hip_prefetch_node_rows");
+    ahead_.push_back(Ahead{cb_no, t, def_seq_, true});  // (the library holds it from here on, whatever the next call does)
+    ahead_upto_ = cb_no;
+    announce_status_ = ANNOUNCED;
     {
         float To[16];
         mat16(erasor_utils::inverse(erasor_utils::geoPose2eigen(def_odom_)), To);
         check(h_, erasor_hip_announce_origin2body(h_, To), "erasor_hip_announce_origin2body");
     }
-    ++n_ahead_;
-    ahead_upto_ = cb_no;
-    auto_tickets_.emplace_back(def_seq_, t);
 }
 void OfflineMapUpdater::callback_node(int seq, const geometry_msgs::Pose &odom, const Cloud &lidar, uint64_t ticket) {
     // the deferred announcement points at a caller local: whatever way this callback ends, it does not outlive it
@@ -404,12 +423,12 @@ void OfflineMapUpdater::callback_node(int seq, const geometry_msgs::Pose &odom, 
         ~ClearDeferred() { p = nullptr; }
     } clear_deferred{def_cloud_};
     stack_count_++;
-    for (auto it = auto_tickets_.begin(); it != auto_tickets_.end(); ++it)  // announced through announce_next_deferred
-        if (it->first == seq) {
-            if (!ticket) ticket = it->second;
-            auto_tickets_.erase(it);
-            break;
-        }
+    // is the oldest announcement this callback's own?  (Announcements are made in node order and never for a gated callback.)  Then a
+    // node handed over through announce_next_deferred takes its ticket by itself; and a ticket the updater does not hold for THIS
+    // callback -- of a node it had to drop, or handed in twice -- is no ticket: the cloud is looked at
+    const bool own = !ahead_.empty() && ahead_.front().cb_no == stack_count_;
+    if (own && ahead_.front().by_seq && !ticket) ticket = ahead_.front().ticket;
+    if (ticket && !(own && ahead_.front().ticket == ticket)) ticket = 0;
     if (stack_count_ % cfg_.params.removal_interval != 0) {  // OMU.cpp:206-209,327-329 "PASS!"
         if (cfg_.verbose) printf(" PASS! \n");
         stage_deferred();
@@ -427,7 +446,8 @@ void OfflineMapUpdater::callback_node(int seq, const geometry_msgs::Pose &odom, 
         if (ticket) {
             // (in two halves: a deferred announcement of the node behind this one is staged while this step runs on the GPU)
             check(h_, erasor_hip_step_ticket_async(h_, ticket, Tb, To), "erasor_hip_step_ticket_async");
-            if (n_ahead_ > 0) --n_ahead_;
+            ahead_.pop_front();
+            ++n_ticket_steps_;
             try {
                 stage_deferred();
             } catch (...) {
@@ -437,16 +457,27 @@ void OfflineMapUpdater::callback_node(int seq, const geometry_msgs::Pose &odom, 
             }
             check(h_, erasor_hip_step_wait(h_, &last), "erasor_hip_step_wait");
         } else {
-            // (deep announcements are consumed by ticket: a cloud that comes without one is a fresh scan, and the library drops every
-            // announcement when it meets one -- erasor_hip_step_rows recognises at most the OLDEST by content; with one node ahead that is
-            // the old behaviour)
+            // (erasor_hip_step_rows recognises at most the OLDEST announcement by content and consumes it; a cloud it does not recognise is
+            // a fresh scan: the library then drops every announcement whose chain has started and keeps the one that has not -- the next
+            // scan, announced in front of this callback)
             check(h_, erasor_hip_step_rows(h_, lidar.points.data(), lidar.size(), kRowStride, kRowIntensity, Tl, Tb, To, &last), "erasor_hip_step_rows");
-            if (n_ahead_ > 1) {  // the step consumed the oldest or dropped all: make it "all" (a standalone call drops what is left)
-                check(h_, erasor_hip_drop_announced(h_), "erasor_hip_drop_announced");
+            if (!ahead_.empty()) {  // which of the three it was: the library says how many it still holds (always the latest ones)
+                int left = 0;
+                check(h_, erasor_hip_announced_count(h_, &left), "erasor_hip_announced_count");
+                const size_t held = ahead_.size(), now = (size_t)std::max(left, 0);
+                if (own && now + 1 == held) {
+                    ahead_.pop_front();  // this node's announcement, recognised: consumed, not dropped
+                } else if (now < held) {
+                    n_dropped_ += held - now;
+                    ahead_.erase(ahead_.begin(), ahead_.begin() + (long)(held - now));
+                }
+                // this node's own announcement, not recognised (another buffer) and kept because its chain had not started: nobody can
+                // take it any more, and it would stand in front of every later ticket
+                if (!ahead_.empty() && ahead_.front().cb_no <= stack_count_) {
+                    check(h_, erasor_hip_drop_announced(h_), "erasor_hip_drop_announced");
+                    forget_announced();
+                }
             }
-            n_ahead_ = 0;  // (whatever was announced has been consumed or dropped by this step)
-            ahead_upto_ = stack_count_;
-            auto_tickets_.clear();
             stage_deferred();
         }
         if (last.n_ambiguous)  // (never seen on transformed clouds; said aloud because bin equality is only PROVABLE when it is zero)
@@ -469,26 +500,38 @@ uint64_t OfflineMapUpdater::announce_upcoming(const Cloud &lidar, const geometry
 uint64_t OfflineMapUpdater::announce(const Cloud &lidar, const geometry_msgs::Pose *odom, bool upcoming) {
     // called BEFORE callback_node(current) with the cloud of the node after it: current is callback number stack_count_ + 1
     // (round 6: up to max_ahead_ nodes, in node order: this call is about the node behind the last one announced or gated)
-    if (upcoming && (n_ahead_ > 0 || ahead_upto_ > stack_count_)) return 0;  // (only in front of everything else)
-    const int cb_no = upcoming ? stack_count_ + 1 : std::max(ahead_upto_, stack_count_ + 1) + 1;
-    if (cb_no % cfg_.params.removal_interval != 0) {  // that node will be gated out (OMU.cpp:206-209): nothing to announce
-        ahead_upto_ = cb_no;
+    if (upcoming && (!ahead_.empty() || ahead_upto_ > stack_count_)) {  // (only in front of everything else)
+        announce_status_ = NOT_FIRST;
         return 0;
     }
-    if (n_ahead_ >= max_ahead_) return 0;  // as many nodes ahead as callback_node can honour (one unless set_lookahead said more)
+    const int cb_no = upcoming ? stack_count_ + 1 : std::max(ahead_upto_, stack_count_ + 1) + 1;
+    const bool gated = cb_no % cfg_.params.removal_interval != 0;  // that node will be gated out (OMU.cpp:206-209)
+    // capacity FIRST, and a refusal for capacity moves nothing: the caller makes this very call again, and it must then still be about
+    // this node (the gate used to come first and moved ahead_upto_ even when the caller went on to retry: the retried cloud was staged
+    // under the next node's callback number)
+    if (!upcoming && full(stack_count_ + 1, gated)) {
+        announce_status_ = FULL;
+        return 0;
+    }
+    if (gated) {  // nothing to announce
+        ahead_upto_ = cb_no;
+        announce_status_ = GATED;
+        return 0;
+    }
     float Tl[16], Tb[16];
     mat16(tf_lidar2body_, Tl);
     if (odom) mat16(erasor_utils::geoPose2eigen(*odom), Tb);  // OMU.cpp:219: the whole node is known, the next fetch_VoI pass goes ahead too
     uint64_t ticket = 0;
     check(h_, erasor_hip_prefetch_node_rows(h_, lidar.points.data(), lidar.size(), kRowStride, kRowIntensity, Tl, odom ? Tb : nullptr, &ticket),
           "erasor_hip_prefetch_node_rows");
+    ahead_.push_back(Ahead{cb_no, ticket, 0, false});  // (the library holds it from here on, whatever the next call does)
+    ahead_upto_ = cb_no;
+    announce_status_ = ANNOUNCED;
     if (odom) {  // (round 5: ... and the inverse callback_node will compute, OMU.cpp:436: that step may then overlap the one in front)
         float To[16];
         mat16(erasor_utils::inverse(erasor_utils::geoPose2eigen(*odom)), To);
         check(h_, erasor_hip_announce_origin2body(h_, To), "erasor_hip_announce_origin2body");
     }
-    ++n_ahead_;
-    ahead_upto_ = cb_no;
     return ticket;
 }
 void OfflineMapUpdater::set_lookahead(int n) { max_ahead_ = std::max(1, std::min(n, 7)); }
@@ -506,6 +549,7 @@ void OfflineMapUpdater::save_static_map(float voxel_size) {
     std::vector<float> out(v.size() + 4);
     size_t n = 0;
     check(h_, erasor_hip_voxelize_preserving_labels(h_, v.data(), src.size(), voxel_size, out.data(), src.size(), &n), "voxelize_preserving_labels");
+    forget_announced();  // (the voxelisation borrows the query sides: the library has dropped what was announced)
     Cloud map_to_be_saved;
     from_xyzi(out, n, map_to_be_saved);
     const std::string target = cfg_.save_path + "/" + cfg_.data_name + "_result.pcd";  // OMU.cpp:191-193

@@ -162,28 +162,58 @@ public:
     uint64_t announce_next(const pcl::PointCloud<pcl::PointXYZI> &lidar, const geometry_msgs::Pose &odom);
     // Round 6 -- DEEP look-ahead for drivers that know their nodes ahead (main_in_your_env.cpp:92-123 reads them from disk): after
     // set_lookahead(n), n = 1 .. 7, announce_next may be called for up to n nodes beyond the upcoming callback, IN NODE ORDER (each call is
-    // about the node behind the last one announced); it returns 0 -- and announces nothing -- for a node the removal_interval gate skips
-    // and when n nodes are outstanding (call again before a later callback).  With three or more nodes ahead the library lets consecutive
-    // steps overlap and the announced nodes' query chains share their launches (erasor_hip_chain_batch): the offline rate of the C ABI
-    // through the reference's own class.  Deep announcements are consumed BY TICKET: a callback without one drops them all.
+    // about the node behind the last one announced or gated; with nothing announced beyond it: the node behind the upcoming callback's).
+    // With three or more nodes ahead the library lets consecutive steps overlap and the announced nodes' query chains share their launches
+    // (erasor_hip_chain_batch): the offline rate of the C ABI through the reference's own class.
+    //
+    // THE CONTRACT OF AN ANNOUNCEMENT (announce_next, announce_upcoming, announce_next_deferred) -- last_announce() says which it was:
+    //   ANNOUNCED  the node is staged; announce_next / announce_upcoming returned its ticket (never 0).
+    //   FULL       nothing was taken and NOTHING MOVED: n nodes are announced beyond the upcoming callback, or 7 in all (the library's
+    //              query sides).  The call is still about the same node: make it again before a later callback, while the node is still
+    //              beyond the upcoming callback (a node whose own callback is the upcoming one is past announcing; it simply comes
+    //              without a ticket).  The capacity test comes FIRST: a node the removal_interval gate will skip is answered FULL as well
+    //              while outstanding() >= lookahead(), and GATED once there is room -- so `returned 0 && outstanding() >= lookahead()`
+    //              is the same test as last_announce() == FULL, and a caller that retries on either never retries a node the updater
+    //              has moved past.
+    //   GATED      the removal_interval gate skips that node (OMU.cpp:206-209): nothing to announce, the updater has moved past it; the
+    //              next call is about the node behind it.
+    //   NOT_FIRST  announce_upcoming while something is announced already: nothing moved.
+    //   PENDING    announce_next_deferred has been called and the upcoming callback has not run yet; after that callback it is one of
+    //              ANNOUNCED / GATED / FULL like any other (FULL: the cloud was NOT taken -- hand the node over again).
+    // A callback takes its node's announcement by the TICKET it is handed, or by itself when the node came through
+    // announce_next_deferred.  A callback without a ticket hands its cloud to the library, which compares it with the oldest announced
+    // copy (pointer, size, every record): the same cloud consumes that announcement and the nodes behind it stay announced; any other
+    // cloud is the fresh scan it is, and every announcement in front of which it arrived is dropped (their nodes then come as fresh scans
+    // too: a ticket the updater no longer holds -- dropped, consumed, or never given out -- counts as no ticket; announcing goes on with
+    // the node behind the last one handed over).  Only an announcement that has not started yet (the latest, with no step since) survives
+    // a foreign cloud: announce_next(k + 1) in front of an unannounced callback_node(k), the first node of a sequence.
+    // save_static_map drops what is announced (its voxelisation borrows the query sides).
+    enum AnnounceStatus { ANNOUNCED = 0, GATED = 1, FULL = 2, NOT_FIRST = 3, PENDING = 4 };
     void set_lookahead(int n);
-    // ... and the node the UPCOMING callback itself brings, while nothing is announced yet (the first node of a sequence: a callback
-    // without a ticket in front of announced nodes would drop them); 0 if something is announced already or the gate skips the node
+    // ... and the node the UPCOMING callback itself brings, while nothing is announced yet (the first node of a sequence); 0 if something
+    // is announced already (NOT_FIRST) or the gate skips the node (GATED)
     uint64_t announce_upcoming(const pcl::PointCloud<pcl::PointXYZI> &lidar, const geometry_msgs::Pose &odom);
     int lookahead() const { return max_ahead_; }
-    int outstanding() const { return n_ahead_; }  // nodes announced and not yet stepped
-    // the callback of an announced node, by ticket (0: like the three-argument form)
+    int outstanding() const { return (int)ahead_.size(); }  // nodes announced and not yet stepped or dropped, the upcoming callback's own included
+    AnnounceStatus last_announce() const { return announce_status_; }
+    // the callback of an announced node, by ticket (0, or a ticket the updater does not hold for this node: like the three-argument form)
     void callback_node(int seq, const geometry_msgs::Pose &odom, const pcl::PointCloud<pcl::PointXYZI> &lidar, uint64_t ticket);
     // The same announcement WITHOUT the copy on the caller's time: the cloud is staged by the UPCOMING callback_node while that node's
-    // own step runs on the GPU (0.1 ms of host work per 125 k-point cloud that no longer precedes the step).  `lidar` must stay alive
-    // and unchanged until that callback has returned; the callback of node `seq` then finds its ticket by itself.
+    // own step runs on the GPU (0.1 ms of host work per 125 k-point cloud that no longer precedes the step) -- AFTER that callback has
+    // taken its own announcement, so the hand-over finds room where announce_next in front of the callback would not.  `lidar` must stay
+    // alive and unchanged until that callback has returned (the updater does not look at it afterwards, taken or not); the callback of
+    // that node then finds its ticket by itself.  `seq` is what staged() answers to; WHICH node it is follows from the order of the calls.
     void announce_next_deferred(int seq, const pcl::PointCloud<pcl::PointXYZI> &lidar, const geometry_msgs::Pose &odom);
     // is node `seq` staged (its callback will not look at the cloud it is handed)?
     bool staged(int seq) const {
-        for (const auto &a : auto_tickets_)
-            if (a.first == seq) return true;
+        for (const auto &a : ahead_)
+            if (a.by_seq && a.seq == seq) return true;
         return false;
     }
+    // read-only counters for tests and drivers: callbacks stepped by a ticket (handed in or found), and announcements the updater or the
+    // library dropped unstepped (a foreign cloud without a ticket in front of them, save_static_map)
+    size_t stepped_by_ticket() const { return n_ticket_steps_; }
+    size_t announcements_dropped() const { return n_dropped_; }
     void save_static_map(float voxel_size);                    // OMU.cpp:174-196
     void get_map(pcl::PointCloud<pcl::PointXYZI> &dst);        // *map_arranged_
     erasor_hip_handle *handle() { return h_; }                 // for adapters that read more of the last step (ros1_adapter.cpp)
@@ -197,15 +227,25 @@ private:
     erasor_hip_handle *h_ = nullptr;
     Eigen::Matrix4f tf_lidar2body_, tf_body2origin_;
     int stack_count_ = 0;
-    // nodes announced and not yet consumed; round 6: up to max_ahead_ of them (set_lookahead), in node order.  ahead_upto_: callback
-    // number (stack_count_ counts callbacks, gated ones too) of the last node an announcement was made -- or skipped by the gate -- for
-    int n_ahead_ = 0, max_ahead_ = 1, ahead_upto_ = 0;
+    // nodes announced and not yet stepped, oldest first (node order): the callback number each one belongs to (stack_count_ counts
+    // callbacks, gated ones too), its ticket, and for announce_next_deferred the caller's sequence number (that callback takes the ticket by
+    // itself).  Up to max_ahead_ beyond the upcoming callback (set_lookahead).  ahead_upto_: callback number of the last node an
+    // announcement was made -- or skipped by the gate -- for; a refusal for capacity leaves it alone
+    struct Ahead {
+        int cb_no;
+        uint64_t ticket;
+        int seq;
+        bool by_seq;
+    };
+    std::deque<Ahead> ahead_;
+    int max_ahead_ = 1, ahead_upto_ = 0;
+    AnnounceStatus announce_status_ = ANNOUNCED;
+    size_t n_ticket_steps_ = 0, n_dropped_ = 0;
     const pcl::PointCloud<pcl::PointXYZI> *def_cloud_ = nullptr;  // announce_next_deferred: staged by the upcoming callback
     geometry_msgs::Pose def_odom_;
     int def_seq_ = 0;
-    // tickets of the nodes announced that way, by sequence number (their callbacks take them by themselves); round 6: several, since with
-    // set_lookahead(n) the deferred announcement is about the node behind the last announced one, not about the next callback
-    std::deque<std::pair<int, uint64_t>> auto_tickets_;
+    bool full(int upcoming_cb, bool gated) const;  // the capacity test of an announcement (upcoming_cb: the callback in front of it)
+    void forget_announced();                       // the library has dropped what was announced: the books follow
     void stage_deferred();
     uint64_t announce(const pcl::PointCloud<pcl::PointXYZI> &lidar, const geometry_msgs::Pose *odom, bool upcoming = false);
 };

@@ -1337,6 +1337,11 @@ int erasor_hip_chain_batch(erasor_hip_handle *h, int n_scans, int lead);
  * caller that lost track of its announcements (the shim's OfflineMapUpdater: a callback without a ticket while several nodes are
  * announced by ticket, OfflineMapUpdater.cpp:203 has no notion of either). */
 int erasor_hip_drop_announced(erasor_hip_handle *h);
+/* How many nodes are announced and not yet stepped or dropped.  A step WITHOUT a ticket may consume the oldest announcement (its scan,
+ * recognised by pointer, size and content), keep the one announcement that has not started (another scan: the next one) or drop them all:
+ * a caller that keeps books of its tickets asks here which of the three it was.  Reads host state only; any time, also with a step in
+ * flight. */
+int erasor_hip_announced_count(const erasor_hip_handle *h, int *n);
 /* sets of shared launches made so far / chains that went into them */
 int erasor_hip_chain_batch_counts(erasor_hip_handle *h, uint64_t *sets, uint64_t *chains);
 /* The main stream's dependency chain on the device's own clock (no events, no extra launches: the chunk scan and the step's end stamp
