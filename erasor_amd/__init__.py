@@ -170,6 +170,52 @@ class ClusterResult(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class ObjectVoteParams(C.Structure):
+    """erasor_object_vote_params (include/erasor_hip.h)"""
+    _fields_ = [(k, C.c_double) for k in ("tol", "max_extent", "remove_ratio", "revert_ratio")] + [
+        (k, C.c_uint64) for k in ("min_size", "max_size", "min_voted")] + [("vote_thr", C.c_uint32), ("ground_keep", C.c_uint32)]
+
+
+class ObjectRow(C.Structure):
+    """erasor_object_row (include/erasor_hip.h): one touched cluster"""
+    _fields_ = [(k, C.c_uint32) for k in ("first", "n_points", "n_voted", "n_dynamic", "n_voted_dynamic", "n_label_out_of_range")] + [
+        ("min_xyz", C.c_float * 3), ("max_xyz", C.c_float * 3), ("decision", C.c_uint32)]
+
+
+# the rows as numpy records (ObjectRow's layout; evalmap.OBJECT_ROW_DTYPE), the decision codes and the id of a point without a row
+OBJECT_ROW_DTYPE = np.dtype([(k, np.uint32) for k in ("first", "n_points", "n_voted", "n_dynamic", "n_voted_dynamic", "n_label_out_of_range")] + [
+    ("min_xyz", np.float32, 3), ("max_xyz", np.float32, 3), ("decision", np.uint32)])
+OBJECT_UNCHANGED, OBJECT_REMOVED, OBJECT_REVERTED, OBJECT_NOT_OBJECT = 0, 1, 2, 3
+OBJECT_NONE = 0xFFFFFFFF
+
+
+class ObjectVoteResult(C.Structure):
+    """erasor_object_vote_result (include/erasor_hip.h)"""
+    _fields_ = [(k, C.c_uint64) for k in (
+        "n_points", "n_ground", "n_clusters", "n_touched", "n_removed_clusters", "n_reverted_clusters", "n_not_object", "n_voted", "n_removed",
+        "n_grown", "n_grown_dynamic", "n_reverted", "n_reverted_dynamic", "n_ground_reverted", "n_ground_reverted_dynamic", "largest")]
+
+    def as_dict(self):
+        """evalmap.object_vote's result keys"""
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def votes_from_masks(*kept_masks):
+    """the saturating uint8 count, per point, of the masks that say 0 (removed): the 1 = kept masks of visibility, carve and a step go
+    straight in, and object_vote(vote_thr=2) of three of them is their majority"""
+    if not kept_masks:
+        raise ValueError("votes_from_masks: no mask")
+    n = len(np.asarray(kept_masks[0]).reshape(-1))
+    votes = np.zeros(n, np.uint16)
+    for m in kept_masks:
+        m = np.asarray(m).reshape(-1)
+        if len(m) != n:
+            raise ValueError("votes_from_masks: the masks differ in length")
+        votes += (m == 0)
+        np.minimum(votes, 255, out=votes)
+    return votes.astype(np.uint8)
+
+
 class ScoreStats(C.Structure):
     """erasor_score_stats (include/erasor_hip.h): a score's statistics over the points where it is finite"""
     _fields_ = [("n_scored", C.c_uint64)] + [(k, C.c_double) for k in ("min", "median", "p90", "p99", "max")]
@@ -501,7 +547,7 @@ class ErasorError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 … -shared -> erasor_amd/liberasor_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "knn.hip.h", "normals.hip.h", "refine_plane.hip.h", "visibility.hip.h", "carve.hip.h", "ground.hip.h", "render.hip.h", "revert_bins.hip.h",
+    srcs = [os.path.join(_SRC_DIR, f) for f in ("erasor_hip.hip", "analysis_host.hip.h", "kernels.hip.h", "evaluate.hip.h", "nearest.hip.h", "align.hip.h", "refine.hip.h", "label_scans.hip.h", "cluster.hip.h", "objects.hip.h", "knn.hip.h", "normals.hip.h", "refine_plane.hip.h", "visibility.hip.h", "carve.hip.h", "ground.hip.h", "render.hip.h", "revert_bins.hip.h",
                                                  "exact_sort.hip.h", "exact_sort_core.h", "overlap_auto.h", "stream_place.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "erasor_hip.h"))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
@@ -1409,6 +1455,61 @@ class Erasor:
         if lib().erasor_hip_map_size(self._h, C.byref(n)) != 0:  # (no map, a step in flight: the call itself says so)
             n = C.c_size_t(0)
         return self._cluster(lib().erasor_hip_cluster_map, (), n.value, tol, min_size, max_size, ids, keep)
+
+    # -- the decision per object: a method's per-point votes spread over clusters, fragments reverted (on the host: evalmap.object_vote) --
+    def _object_vote(self, fn, head, tail_n, n, votes, ground, prm, ids, keep):
+        v = np.ascontiguousarray(np.asarray(votes, np.uint8).reshape(-1))
+        g = None if ground is None else np.ascontiguousarray(np.asarray(ground, np.uint8).reshape(-1))
+        if len(v) != n or (g is not None and len(g) != n):
+            raise ErasorError(-1, "object_vote: votes and ground must have one entry per point")
+        if not (0 <= prm["vote_thr"] < 1 << 32 and prm["min_size"] >= 0 and prm["max_size"] >= 0 and prm["min_voted"] >= 0):
+            raise ErasorError(-1, "object_vote: vote_thr must be within 1 .. 255 and the size limits not negative")
+        P = ObjectVoteParams(tol=prm["tol"], max_extent=prm["max_extent"], remove_ratio=prm["remove_ratio"], revert_ratio=prm["revert_ratio"],
+                             min_size=min(int(prm["min_size"]), 2 ** 64 - 1), max_size=min(int(prm["max_size"]), 2 ** 64 - 1),
+                             min_voted=min(int(prm["min_voted"]), 2 ** 64 - 1), vote_thr=int(prm["vote_thr"]), ground_keep=int(bool(prm["ground_keep"])))
+        r = ObjectVoteResult()
+        v = v if n else np.zeros(1, np.uint8)
+        mask = np.empty(max(n, 1), np.uint8)
+        id_buf = np.empty(max(n, 1), np.uint32) if ids else None
+        rows = np.zeros(max(min(n, 1 << 16), 1), OBJECT_ROW_DTYPE)
+        kept = np.empty((max(n, 1), 4), np.float32) if keep else None
+        for attempt in range(2):  # (a second call only when the rows did not fit: then with their exact count; mask and ids came with the first)
+            rc = fn(self._h, *head, _p(v), None if g is None else _p(g), *tail_n, C.byref(P), None if attempt else _p(mask),
+                    _p(id_buf) if ids and not attempt else None, _p(rows), C.c_size_t(len(rows)), _p(kept) if keep else None,
+                    C.c_size_t(len(kept) if keep else 0), C.byref(r))
+            if rc != E_CAPACITY or attempt:
+                break
+            rows = np.zeros(max(int(r.n_touched), 1), OBJECT_ROW_DTYPE)
+        self._check(rc)
+        return (mask[:n], rows[: r.n_touched], id_buf[:n] if ids else None, kept[: r.n_points - r.n_removed] if keep else None, r.as_dict())
+
+    def object_vote(self, cloud, votes, ground=None, tol=0.5, vote_thr=1, min_size=1, max_size=0, max_extent=0.0, remove_ratio=0.5,
+                    revert_ratio=0.0, min_voted=1, ground_keep=True, ids=True, keep=True):
+        """A removal method's per-point votes decided per object, on the device (erasor_hip_object_vote_clouds).  `cloud` as for
+        evaluate; `votes`: uint8 per point, voted iff >= vote_thr (votes_from_masks turns the 1 = kept masks of visibility, carve and a
+        step into them; their sum with vote_thr=2 of three is the majority); `ground`: uint8 per point (ground_votes' mask, 1 = ground)
+        or None.  Ground points are cut out of the graph -- the ground connects everything -- and kept if ground_keep.  Every cluster
+        of the other points at `tol` is removed whole when at least min_voted and the share remove_ratio of its points are voted, kept
+        whole when at most the share revert_ratio is, and left to its per-point votes otherwise, or when it is no object: fewer than
+        min_size or more than max_size points, a box side above max_extent.  revert_ratio is 0 by default, so nothing is reverted:
+        with an incomplete ground mask one huge cluster holds every object and its tiny vote share would wipe the votes out -- set
+        max_size or max_extent before using revert_ratio.  Returns (mask, rows, ids, kept, result) as evalmap.object_vote does: uint8
+        per point, 1 = kept; OBJECT_ROW_DTYPE records of the touched clusters in increasing `first`; per point its row or OBJECT_NONE
+        (None unless ids); the rows with mask 1 in the order given (None unless keep: pass it to set_map); the counts as a dict."""
+        hold = []
+        c = self._eval_cloud(cloud, hold)
+        prm = dict(tol=tol, vote_thr=vote_thr, min_size=min_size, max_size=max_size, max_extent=max_extent, remove_ratio=remove_ratio,
+                   revert_ratio=revert_ratio, min_voted=min_voted, ground_keep=ground_keep)
+        return self._object_vote(lib().erasor_hip_object_vote_clouds, c, (), c[1].value, votes, ground, prm, ids, keep)
+
+    def object_vote_map(self, votes, ground=None, tol=0.5, vote_thr=1, min_size=1, max_size=0, max_extent=0.0, remove_ratio=0.5,
+                        revert_ratio=0.0, min_voted=1, ground_keep=True, ids=True, keep=True):
+        """object_vote over the handle's current map (the get_map view, never copied to the host; erasor_hip_object_vote_map): votes and
+        ground index that view, as the masks of visibility, carve and ground_votes with map=None do"""
+        n = len(np.asarray(votes).reshape(-1))
+        prm = dict(tol=tol, vote_thr=vote_thr, min_size=min_size, max_size=max_size, max_extent=max_extent, remove_ratio=remove_ratio,
+                   revert_ratio=revert_ratio, min_voted=min_voted, ground_keep=ground_keep)
+        return self._object_vote(lib().erasor_hip_object_vote_map, (), (C.c_size_t(n),), n, votes, ground, prm, ids, keep)
 
     def residue(self, gt, est, tol=0.5, voxelsize=0.2, voxel_leaf=0.0, min_size=1):
         """The ghost objects a method left: the dynamic points of the labelled ground truth `gt` that evaluate(gt, est, voxelsize) found

@@ -2,8 +2,11 @@
 // labels, the clustering, the k nearest neighbours and density filters, the normals, the point-to-plane refinement, the see-through check, the carving of free space, the ground, label_map and static_complement, the bird's-eye renderer, their test hooks and the parameter sweep.  Included by erasor_hip.hip
 // at its end -- one translation unit, like the kernel headers -- so it sees the handle, ensure / LAUNCH / HIPC, scan_u32, radix_sort,
 // map_to_device and voxelize_device from there; nothing of the step path depends on this file.  Kernels: evaluate.hip.h, nearest.hip.h,
-// align.hip.h, label_scans.hip.h, cluster.hip.h, knn.hip.h, normals.hip.h, refine_plane.hip.h, visibility.hip.h, carve.hip.h, ground.hip.h, render.hip.h.
+// align.hip.h, label_scans.hip.h, cluster.hip.h, knn.hip.h, normals.hip.h, refine_plane.hip.h, visibility.hip.h, carve.hip.h, ground.hip.h, render.hip.h,
+// and objects.hip.h (the decision per object), which this file includes itself.
 #pragma once
+
+#include "objects.hip.h"
 
 extern "C" {
 
@@ -1295,6 +1298,166 @@ int erasor_hip_cluster_map(erasor_hip_handle *h, double tol, size_t min_size, si
     uint32_t n = 0;
     if ((rc = map_on_device(h, who, h->ev.map, &p, &n))) return rc;
     return cl_run(h, who, p, n, tol, min_size, max_size, ids, rows, cap_rows, kept_xyzi, cap_points, res);
+}
+
+// ---- the decision per object: per-point votes spread over the clusters they fall on, fragments reverted (kernels: objects.hip.h) ----
+// Like cl_run: the main stream, the evaluator's scratch, the evaluator's grid at a cell edge a little above tol -- over the non-ground
+// rows, compacted stably so that a cluster's lowest compacted index is its lowest given index.  The host counts the ground bytes it was
+// given (they size the compacted cloud's launches); one round trip for the counters (they size the rows), then the copies.
+static int obj_check_args(erasor_hip_handle *h, const char *who, const uint8_t *votes, const erasor_object_vote_params *p, const void *res) {
+    if (!res) return invalid(h, who, "res is NULL");
+    if (!p) return invalid(h, who, "params is NULL");
+    if (!votes) return invalid(h, who, "votes is NULL");
+    if (!(p->tol > 0) || !std::isfinite(p->tol)) return invalid(h, who, "tol must be a finite number > 0");
+    if (p->vote_thr < 1 || p->vote_thr > 255) return invalid(h, who, "vote_thr must be within 1 .. 255");
+    if (!(p->max_extent >= 0) || !std::isfinite(p->max_extent)) return invalid(h, who, "max_extent must be 0 or a finite number > 0");
+    if (!(p->remove_ratio > 0 && p->remove_ratio <= 1)) return invalid(h, who, "remove_ratio must be within (0, 1]");
+    if (!(p->revert_ratio >= 0 && p->revert_ratio < 1) || !(p->revert_ratio < p->remove_ratio))
+        return invalid(h, who, "revert_ratio must be within [0, 1) and below remove_ratio");
+    return ERASOR_OK;
+}
+
+static int obj_run(erasor_hip_handle *h, const char *who, const float4 *pts, uint32_t n, const uint8_t *votes, const uint8_t *ground,
+                   const erasor_object_vote_params &P, uint8_t *mask, uint32_t *ids, erasor_object_row *rows, size_t cap_rows, float *kept_xyzi,
+                   size_t cap_points, erasor_object_vote_result *res) {
+    static_assert(sizeof(erasor_object_row) == OB_ROW * sizeof(uint32_t), "the device writes erasor_object_row word by word");
+    auto &E = h->ev;
+    erasor_object_vote_result r;
+    memset(&r, 0, sizeof(r));
+    r.n_points = n;
+    if (!n) {
+        *res = r;
+        return ERASOR_OK;
+    }
+    ObDecide D;
+    D.min_size = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(P.min_size, 1), 0xFFFFFFFFull);
+    D.max_size = (uint32_t)std::min<uint64_t>(P.max_size, 0xFFFFFFFFull);  // (0: no upper limit)
+    D.min_voted = (uint32_t)std::min<uint64_t>(P.min_voted, 0xFFFFFFFFull);
+    D.max_extent = P.max_extent, D.remove_ratio = P.remove_ratio, D.revert_ratio = P.revert_ratio;
+    uint32_t m = n;  // the points in the graph
+    if (ground)
+        for (uint32_t i = 0; i < n; ++i) m -= ground[i] != 0 ? 1u : 0u;
+    uint32_t nb = 1024;  // buckets: ev_run's (a power of two >= the compacted cloud's size)
+    while (nb < m) nb <<= 1;
+    const size_t n1 = (size_t)n + 1;
+    if (ensure(h, E.ctr, EV_NCTR) || ensure(h, E.ob_ctr, OB_NCTR) || ensure(h, E.cnt, (size_t)nb + 1) || ensure(h, E.pl, (size_t)nb + 1) ||
+        ensure(h, E.tops, nb / 1024 + 4) || ensure(h, E.bkt, n1) || ensure(h, E.pts, n1) || ensure(h, E.idx, n1) || ensure(h, E.cl_parent, n1) ||
+        ensure(h, E.cl_root, n1) || ensure(h, E.ob_tab, n1 * OB_TROW) || ensure(h, E.ob_code, n1) || ensure(h, E.ob_touched, n1) ||
+        ensure(h, E.ob_keep, n1) || ensure(h, E.ob_ids, n1) || ensure(h, E.ob_mask, n1) || ensure(h, E.ob_cls, n1) || ensure(h, E.ob_votes, n1) ||
+        ensure(h, E.fm_pl, n1) || ensure(h, E.fm_tops, n / 1024 + 4))
+        return ERASOR_E_NO_DEVICE;
+    if (ground && (ensure(h, E.ob_ground, n1) || ensure(h, E.ob_ng, n1) || ensure(h, E.ob_gpl, n1) || ensure(h, E.ob_gtops, n / 1024 + 4) ||
+                   ensure(h, E.ob_pts, n1) || ensure(h, E.ob_src, n1)))
+        return ERASOR_E_NO_DEVICE;
+    const double cell = P.tol * CL_CELL_MARGIN, tol2 = P.tol * P.tol;
+    const uint32_t g = cdiv(n, 256), gm = cdiv(m, 256);
+    HIPC(h, hipMemcpyAsync(E.ob_votes.p, votes, n, hipMemcpyHostToDevice, h->stream));
+    if (ground) HIPC(h, hipMemcpyAsync(E.ob_ground.p, ground, n, hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemsetAsync(E.ctr.p, 0, EV_NCTR * sizeof(unsigned long long), h->stream));
+    HIPC(h, hipMemsetAsync(E.ob_ctr.p, 0, OB_NCTR * sizeof(unsigned long long), h->stream));
+    LAUNCH(h, h->stream, "obj_flags", k_obj_flags, g, 256, pts, n, (const uint8_t *)E.ob_votes.p, ground ? (const uint8_t *)E.ob_ground.p : nullptr, P.vote_thr,
+           E.ob_cls.p, ground ? E.ob_ng.p : nullptr, E.ob_ctr.p);
+    // the graph's points: the rows given, or the non-ground ones of them in the order given with their source indices
+    const float4 *cp = pts;
+    const uint32_t *src = nullptr, *gpl = nullptr, *gtops = nullptr;
+    if (ground) {
+        scan_u32(h, h->stream, E.ob_ng.p, E.ob_gpl.p, E.ob_gtops.p, n, n, nullptr, nullptr, "obj_flags");
+        LAUNCH(h, h->stream, "obj_flags", k_obj_compact, g, 256, pts, n, (const uint32_t *)E.ob_ng.p, (const uint32_t *)E.ob_gpl.p, (const uint32_t *)E.ob_gtops.p,
+               E.ob_pts.p, E.ob_src.p);
+        cp = E.ob_pts.p, src = E.ob_src.p, gpl = E.ob_gpl.p, gtops = E.ob_gtops.p;
+    }
+    if (m) {
+        HIPC(h, hipMemsetAsync(E.cnt.p, 0, ((size_t)nb + 1) * sizeof(uint32_t), h->stream));
+        LAUNCH(h, h->stream, "obj_index", k_ev_hist, gm, 256, cp, m, cell, nb - 1, E.bkt.p, E.cnt.p, E.ctr.p);
+        scan_u32(h, h->stream, E.cnt.p, E.pl.p, E.tops.p, nb + 1, nb + 1, nullptr, nullptr, "obj_index");
+        LAUNCH(h, h->stream, "obj_index", k_ev_offsets, cdiv(nb + 1, 256), 256, (const uint32_t *)E.pl.p, (const uint32_t *)E.tops.p, nb + 1, E.cnt.p, E.pl.p);
+        LAUNCH(h, h->stream, "obj_index", k_ev_scatter, gm, 256, cp, m, (const uint32_t *)E.bkt.p, E.pl.p, E.pts.p, E.idx.p);
+        LAUNCH(h, h->stream, "obj_index", k_obj_init, gm, 256, m, E.cl_parent.p, E.ob_tab.p);
+        LAUNCH(h, h->stream, "obj_unite", k_cl_unite, gm, 256, cp, m, (const float4 *)E.pts.p, (const uint32_t *)E.idx.p, (const uint32_t *)E.cnt.p, nb - 1, cell,
+               tol2, E.cl_parent.p);
+        LAUNCH(h, h->stream, "obj_table", k_obj_table, gm, 256, cp, m, (const uint32_t *)E.cl_parent.p, (const uint8_t *)E.ob_cls.p, src, E.cl_root.p, E.ob_tab.p);
+        LAUNCH(h, h->stream, "obj_decide", k_obj_decide, gm, 256, m, (const uint32_t *)E.cl_root.p, (const uint32_t *)E.ob_tab.p, D, E.ob_code.p, E.ob_touched.p,
+               E.ob_ctr.p);
+        // the touched roots ranked in compacted-index order (= `first` order)
+        scan_u32(h, h->stream, E.ob_touched.p, E.fm_pl.p, E.fm_tops.p, m, m, nullptr, nullptr, "obj_decide");
+    }
+    LAUNCH(h, h->stream, "obj_apply", k_obj_apply, g, 256, pts, n, (const uint8_t *)E.ob_cls.p, gpl, gtops, (const uint32_t *)E.cl_root.p,
+           (const uint32_t *)E.ob_code.p, (const uint32_t *)E.ob_touched.p, (const uint32_t *)E.fm_pl.p, (const uint32_t *)E.fm_tops.p, P.ground_keep,
+           E.ob_mask.p, E.ob_ids.p, E.ob_keep.p, E.ob_ctr.p);
+    // (k_ev_hist's own counters in E.ctr cover the compacted rows only and stay on the device: a ground point's coordinates count too)
+    unsigned long long oc[OB_NCTR];
+    HIPC(h, hipMemcpyAsync(oc, E.ob_ctr.p, sizeof(oc), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (oc[OB_C_NON_FINITE])
+        return invalid(h, who, "non-finite coordinate (NaN / Inf) in " + std::to_string(oc[OB_C_NON_FINITE]) + " point(s)");
+    r.n_ground = oc[OB_C_GROUND];
+    r.n_clusters = oc[OB_C_CLUSTERS];
+    r.n_touched = oc[OB_C_TOUCHED];
+    r.n_removed_clusters = oc[OB_C_REMOVED_CL];
+    r.n_reverted_clusters = oc[OB_C_REVERTED_CL];
+    r.n_not_object = oc[OB_C_NOT_OBJECT];
+    r.n_voted = oc[OB_C_VOTED];
+    r.n_removed = oc[OB_C_REMOVED];
+    r.n_grown = oc[OB_C_GROWN];
+    r.n_grown_dynamic = oc[OB_C_GROWN_DYN];
+    r.n_reverted = oc[OB_C_REVERTED];
+    r.n_reverted_dynamic = oc[OB_C_REVERTED_DYN];
+    r.n_ground_reverted = oc[OB_C_GROUND_REV];
+    r.n_ground_reverted_dynamic = oc[OB_C_GROUND_REV_DYN];
+    r.largest = oc[OB_C_LARGEST];
+    *res = r;
+    int rc;
+    if (mask && (rc = d2h(h, mask, E.ob_mask.p, n))) return rc;
+    if (ids && (rc = d2h(h, ids, E.ob_ids.p, (size_t)n * sizeof(uint32_t)))) return rc;
+    const uint64_t n_kept = r.n_points - r.n_removed;
+    if ((rows && r.n_touched > cap_rows) || (kept_xyzi && n_kept > cap_points)) return ERASOR_E_CAPACITY;
+    if (rows && r.n_touched) {
+        if (ensure(h, E.ob_rows, (size_t)r.n_touched * OB_ROW + 1)) return ERASOR_E_NO_DEVICE;
+        LAUNCH(h, h->stream, "obj_rows", k_obj_rows, gm, 256, m, (const uint32_t *)E.ob_touched.p, (const uint32_t *)E.fm_pl.p, (const uint32_t *)E.fm_tops.p,
+               (const uint32_t *)E.ob_tab.p, (const uint32_t *)E.ob_code.p, src, E.ob_rows.p);
+        if ((rc = d2h(h, rows, E.ob_rows.p, (size_t)r.n_touched * sizeof(erasor_object_row)))) return rc;
+    }
+    if (kept_xyzi && n_kept) {
+        // the rows with mask 1, as given: the stable compaction over the keep flags (the touched flags' scan is spent by now)
+        if (ensure(h, E.fm_out, n1)) return ERASOR_E_NO_DEVICE;
+        scan_u32(h, h->stream, E.ob_keep.p, E.fm_pl.p, E.fm_tops.p, n, n, nullptr, nullptr, "obj_keep");
+        LAUNCH(h, h->stream, "obj_keep", k_f_compact, g, 256, pts, n, (const uint32_t *)E.ob_keep.p, (const uint32_t *)E.fm_pl.p, (const uint32_t *)E.fm_tops.p,
+               E.fm_out.p);
+        return d2h(h, kept_xyzi, E.fm_out.p, (size_t)n_kept * sizeof(float4));
+    }
+    return ERASOR_OK;
+}
+
+int erasor_hip_object_vote_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, const uint8_t *votes, const uint8_t *ground,
+                                  const erasor_object_vote_params *params, uint8_t *mask, uint32_t *ids, erasor_object_row *rows, size_t cap_rows,
+                                  float *kept_xyzi, size_t cap_points, erasor_object_vote_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_object_vote_clouds";
+    int rc = obj_check_args(h, who, votes, params, res);
+    if (rc || (rc = check_cloud(h, who, BAD_CLOUD, xyzi, n))) return rc;
+    const float4 *p = nullptr;
+    if (n) {
+        HIPC(h, hipSetDevice(h->device));
+        if ((rc = ev_input(h, xyzi, n, is_device, h->ev.gt, &p))) return rc;
+    }
+    return obj_run(h, who, p, (uint32_t)n, votes, ground, *params, mask, ids, rows, cap_rows, kept_xyzi, cap_points, res);
+}
+
+int erasor_hip_object_vote_map(erasor_hip_handle *h, const uint8_t *votes, const uint8_t *ground, size_t n, const erasor_object_vote_params *params,
+                               uint8_t *mask, uint32_t *ids, erasor_object_row *rows, size_t cap_rows, float *kept_xyzi, size_t cap_points,
+                               erasor_object_vote_result *res) {
+    NOFLY(h);
+    if (!h) return ERASOR_E_INVALID;
+    const char *who = "erasor_hip_object_vote_map";
+    int rc = obj_check_args(h, who, votes, params, res);
+    if (rc) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    const float4 *p = nullptr;
+    uint32_t n_map = 0;
+    if ((rc = map_on_device(h, who, h->ev.map, &p, &n_map))) return rc;
+    if (n != (size_t)n_map) return invalid(h, who, "n is not the map's size (erasor_hip_map_size)");
+    return obj_run(h, who, p, n_map, votes, ground, *params, mask, ids, rows, cap_rows, kept_xyzi, cap_points, res);
 }
 
 // ---- k nearest neighbours, radius counts and the density filters on them (kernels: knn.hip.h) ----

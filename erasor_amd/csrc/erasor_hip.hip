@@ -394,6 +394,14 @@ struct erasor_hip_handle {
         // roots' ranks, the rows, the ids and the counters (the grid: cnt, pl, tops, bkt, pts, idx above; flags and kept cloud: fm_*)
         DBuf<uint32_t> cl_parent, cl_root, cl_tab, cl_rank, cl_rows, cl_ids;
         DBuf<unsigned long long> cl_ctr;
+        // the decision per object (erasor_hip_object_vote_*): the votes and the ground mask on the device, the class bytes, the non-ground
+        // flags with their scan, the compacted cloud and its index map, the table per root, the decisions, the touched flags, the keep
+        // flags, the rows, the ids, the mask and the counters (the forest and the roots: cl_parent, cl_root; the grid: cnt, pl, tops,
+        // bkt, pts, idx above; the touched flags' scan, then the kept cloud's: fm_*)
+        DBuf<uint8_t> ob_votes, ob_ground, ob_cls, ob_mask;
+        DBuf<uint32_t> ob_ng, ob_gpl, ob_gtops, ob_src, ob_tab, ob_code, ob_touched, ob_keep, ob_rows, ob_ids;
+        DBuf<float4> ob_pts;
+        DBuf<unsigned long long> ob_ctr;
         // k nearest neighbours, radius counts and the density filters (erasor_hip_knn_* / _radius_count_* / _density_filter_*): the two
         // scores' bit patterns, the absolute deviations, the neighbour lists, the counts, the keep mask and the counters (the tree: nn_*
         // above; the grid: cnt, pl, tops, bkt, pts, idx; flags and kept cloud: fm_*)
@@ -1288,6 +1296,9 @@ void erasor_hip_destroy(erasor_hip_handle *h) {
     release(h->ev.rd_bb); release(h->ev.rd_rec); release(h->ev.rd_srt); release(h->ev.rd_ctr); release(h->ev.rd_zb); release(h->ev.rd_img);
     release(h->ev.cl_parent); release(h->ev.cl_root); release(h->ev.cl_tab); release(h->ev.cl_rank); release(h->ev.cl_rows); release(h->ev.cl_ids);
     release(h->ev.cl_ctr);
+    release(h->ev.ob_votes); release(h->ev.ob_ground); release(h->ev.ob_cls); release(h->ev.ob_mask); release(h->ev.ob_ng); release(h->ev.ob_gpl);
+    release(h->ev.ob_gtops); release(h->ev.ob_src); release(h->ev.ob_tab); release(h->ev.ob_code); release(h->ev.ob_touched); release(h->ev.ob_keep);
+    release(h->ev.ob_rows); release(h->ev.ob_ids); release(h->ev.ob_pts); release(h->ev.ob_ctr);
     release(h->ev.kn_kth); release(h->ev.kn_mean); release(h->ev.kn_dev); release(h->ev.kn_ctr); release(h->ev.kn_ni); release(h->ev.kn_cnt);
     release(h->ev.kn_nd); release(h->ev.kn_mask);
     release(h->ev.nm_curv); release(h->ev.nm_ctr); release(h->ev.nm_nrm); release(h->ev.nm_eig);

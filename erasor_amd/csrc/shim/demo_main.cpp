@@ -590,6 +590,110 @@ static int residue_mode(int argc, char **argv) {
     print_clusters(r, rows);
     return 0;
 }
+// ---- the decision per object (erasor_hip_object_vote_clouds) ----
+// near[i] = the cloud `ref` has a point within tau of raw point i: erasor_hip_label_scans_clouds with `ref` as the static map and the raw
+// map as one frame under identity poses -- code 0 (static) is "within tau", code 1 (dynamic) is not.  An empty `ref` (a method that
+// removed everything) is near nothing: every raw point is voted by it.  On failure the error is printed and the handle destroyed
+// (render_fail): the caller returns at once.
+static int near_cloud(erasor_hip_handle *h, const std::vector<float> &ref, const std::vector<float> &raw, double tau, std::vector<uint8_t> *near) {
+    const size_t n = raw.size() / 4;
+    const uint64_t offsets[2] = {0, (uint64_t)n};
+    const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    erasor_scan_label_row row;
+    std::vector<uint8_t> codes(std::max<size_t>(n, 1));
+    const int rc = erasor_hip_label_scans_clouds(h, ref.data(), ref.size() / 4, 0, nullptr, 0, 0, 0, raw.data(), n, offsets, 1, 0, nullptr, I, tau, codes.data(), 0,
+                                                 nullptr, 0, nullptr, &row, nullptr);
+    if (rc) return render_fail(h, "label_scans", rc);
+    near->resize(n);
+    for (size_t i = 0; i < n; ++i) (*near)[i] = codes[i] == 0 ? 1 : 0;
+    return 0;
+}
+// --objects <raw.pcd> <ground.pcd|-> <out.pcd> <tol> <vote_thr> <remove_ratio> <revert_ratio> <max_size> <kept1.pcd> [<kept2.pcd> ...]
+// [--tau t]: the votes of one or more removal methods decided per object.  A raw point is voted by kept_j iff kept_j has no point within
+// tau of it (default 0.2 * sqrt(3) / 2, the evaluator's threshold), so kept clouds that are subsets of the raw map (--visibility, --carve)
+// and a voxelised ERASOR map both work; it is ground iff <ground.pcd> (what --ground-map writes; "-": no ground mask) has a point within
+// tau.  Prints the result, the twenty largest touched clusters and one line per decision, and saves the kept cloud as a binary PCD.
+static int objects_mode(int argc, char **argv) {
+    double tau = 0.2 * sqrt(3.0) / 2.0;
+    if (argc >= 4 && std::string(argv[argc - 2]) == "--tau") {
+        if (!parse_number(argv[argc - 1], &tau) || !(tau > 0)) return 2;
+        argc -= 2;
+    }
+    if (argc < 11) return 2;
+    erasor_object_vote_params P;
+    memset(&P, 0, sizeof(P));
+    size_t thr = 0, max_size = 0;
+    if (!parse_number(argv[5], &P.tol) || !(P.tol > 0) || !parse_count(argv[6], &thr) || thr < 1 || thr > 255 || !parse_number(argv[7], &P.remove_ratio) ||
+        !(P.remove_ratio > 0 && P.remove_ratio <= 1) || !parse_number(argv[8], &P.revert_ratio) ||
+        !(P.revert_ratio >= 0 && P.revert_ratio < 1 && P.revert_ratio < P.remove_ratio) || !parse_count(argv[9], &max_size))
+        return 2;
+    P.vote_thr = (uint32_t)thr, P.max_size = max_size, P.min_size = 1, P.min_voted = 1, P.ground_keep = 1;
+    const bool have_ground = std::string(argv[3]) != "-";
+    std::vector<float> raw, gnd;
+    std::vector<std::vector<float>> kept_in(argc - 10);
+    if (!load_cloud_xyzi(argv[2], raw)) {
+        fprintf(stderr, "cannot read %s\n", argv[2]);
+        return 3;
+    }
+    if (have_ground && !load_cloud_xyzi(argv[3], gnd)) {
+        fprintf(stderr, "cannot read %s\n", argv[3]);
+        return 3;
+    }
+    for (int k = 10; k < argc; ++k)
+        if (!load_cloud_xyzi(argv[k], kept_in[k - 10])) {
+            fprintf(stderr, "cannot read %s\n", argv[k]);
+            return 3;
+        }
+    erasor_hip_handle *h = render_handle();
+    if (!h) return 1;
+    const size_t n = raw.size() / 4;
+    std::vector<uint8_t> votes(std::max<size_t>(n, 1), 0), ground, near;
+    for (const std::vector<float> &k : kept_in) {
+        if (near_cloud(h, k, raw, tau, &near)) return 1;
+        for (size_t i = 0; i < n; ++i)
+            if (!near[i] && votes[i] < 255) ++votes[i];
+    }
+    if (have_ground && near_cloud(h, gnd, raw, tau, &ground)) return 1;
+    if (have_ground && !n) ground.assign(1, 0);
+    std::vector<uint8_t> mask(std::max<size_t>(n, 1));
+    std::vector<erasor_object_row> rows(std::max<size_t>(n, 1));
+    std::vector<float> kept(std::max<size_t>(n, 1) * 4);
+    erasor_object_vote_result r;
+    const int rc = erasor_hip_object_vote_clouds(h, raw.data(), n, 0, votes.data(), have_ground ? ground.data() : nullptr, &P, mask.data(), nullptr, rows.data(),
+                                                 rows.size(), kept.data(), n, &r);
+    if (rc) return render_fail(h, "object_vote", rc);
+    erasor_hip_destroy(h);  // (the handle's last use: nothing below needs it, a failed write included)
+    rows.resize(r.n_touched);
+    typedef unsigned long long ull;
+    printf("objects: n=%llu  ground=%llu  clusters=%llu  touched=%llu  removed=%llu  reverted=%llu  not objects=%llu  largest=%llu\n", (ull)r.n_points,
+           (ull)r.n_ground, (ull)r.n_clusters, (ull)r.n_touched, (ull)r.n_removed_clusters, (ull)r.n_reverted_clusters, (ull)r.n_not_object, (ull)r.largest);
+    printf("points: voted=%llu  removed=%llu  grown=%llu (dynamic %llu)  reverted=%llu (dynamic %llu)  ground reverted=%llu (dynamic %llu)\n", (ull)r.n_voted,
+           (ull)r.n_removed, (ull)r.n_grown, (ull)r.n_grown_dynamic, (ull)r.n_reverted, (ull)r.n_reverted_dynamic, (ull)r.n_ground_reverted,
+           (ull)r.n_ground_reverted_dynamic);
+    static const char *const NAMES[4] = {"unchanged", "removed", "reverted", "not an object"};
+    ull n_cl[4] = {0, 0, 0, 0}, n_pt[4] = {0, 0, 0, 0}, n_dyn[4] = {0, 0, 0, 0};
+    for (const erasor_object_row &c : rows) {
+        const uint32_t d = c.decision & 3u;
+        ++n_cl[d], n_pt[d] += c.n_points, n_dyn[d] += c.n_dynamic;
+    }
+    std::stable_sort(rows.begin(), rows.end(), [](const erasor_object_row &a, const erasor_object_row &b) { return a.n_points > b.n_points; });
+    for (size_t k = 0; k < rows.size() && k < 20; ++k) {
+        const erasor_object_row &c = rows[k];
+        printf("  first=%u  n=%u  voted=%u  dynamic=%u (%.1f%%)  %s  box=[%.3f %.3f %.3f]..[%.3f %.3f %.3f]\n", c.first, c.n_points, c.n_voted, c.n_dynamic,
+               100.0 * (double)c.n_dynamic / (double)c.n_points, NAMES[c.decision & 3u], c.min_xyz[0], c.min_xyz[1], c.min_xyz[2], c.max_xyz[0], c.max_xyz[1],
+               c.max_xyz[2]);
+    }
+    for (int d = 0; d < 4; ++d)
+        printf("%s: clusters=%llu  points=%llu  dynamic=%llu (%.1f%%)\n", NAMES[d], n_cl[d], n_pt[d], n_dyn[d], n_pt[d] ? 100.0 * (double)n_dyn[d] / (double)n_pt[d] : 0.0);
+    pcl::PointCloud<pcl::PointXYZI> out;
+    rows_to_cloud(kept, r.n_points - r.n_removed, out);
+    if (erasor_utils::save_pcd_binary(argv[4], out) != 0) {
+        fprintf(stderr, "cannot write %s\n", argv[4]);
+        return 1;
+    }
+    printf("saved %s\n", argv[4]);
+    return 0;
+}
 // ---- how dense a cloud is around each point, and the outlier filters on that (erasor_hip_knn_clouds, erasor_hip_density_filter_clouds) ----
 static void print_stats(const char *name, double mn, double median, double p90, double p99, double mx) {
     printf("  %s: min=%.9g  median=%.9g  p90=%.9g  p99=%.9g  max=%.9g\n", name, mn, median, p90, p99, mx);
@@ -2270,6 +2374,18 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (argc >= 2 && std::string(argv[1]) == "--objects") {
+        try {
+            const int st = objects_mode(argc, argv);
+            if (st == 2)
+                fprintf(stderr, "usage: %s --objects <raw.pcd> <ground.pcd|-> <out.pcd> <tol> <vote_thr> <remove_ratio> <revert_ratio> <max_size> <kept1.pcd> "
+                                "[<kept2.pcd> ...] [--tau t]\n", argv[0]);
+            return st;
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+    }
     if (argc >= 2 && (std::string(argv[1]) == "--denoise" || std::string(argv[1]) == "--density")) {
         try {
             return std::string(argv[1]) == "--denoise" ? denoise_mode(argc, argv) : density_mode(argc, argv);
@@ -2337,9 +2453,10 @@ int main(int argc, char **argv) {
                 "       %s --visibility <rosparam.yaml> <map.pcd|-> <out.pcd> [n_frames] [W H el_bottom el_top] [window] [k]\n"
                 "       %s --carve <rosparam.yaml> <map.pcd|-> <out.pcd> [n_frames] [voxel] [max_range] [stop_short]\n"
                 "       %s --ground <rosparam.yaml> <out_dir> [n_frames] [n_rings n_sectors max_range]\n"
-                "       %s --ground-map <rosparam.yaml> <map.pcd|-> <ground_out.pcd> <rest_out.pcd> [n_frames] [min_votes] [ratio]\n",
+                "       %s --ground-map <rosparam.yaml> <map.pcd|-> <ground_out.pcd> <rest_out.pcd> [n_frames] [min_votes] [ratio]\n"
+                "       %s --objects <raw.pcd> <ground.pcd|-> <out.pcd> <tol> <vote_thr> <remove_ratio> <revert_ratio> <max_size> <kept1.pcd> [<kept2.pcd> ...] [--tau t]\n",
                 argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0],
-                argv[0], argv[0], argv[0], argv[0]);
+                argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string dir = argv[1];

@@ -1152,6 +1152,155 @@ def cluster_brute(cloud, tol, min_size=1, max_size=0):
     return _cluster_finish(c, _components(n, np.concatenate(ii), np.concatenate(jj)), min_size, max_size)
 
 
+# ---- the decision per object (include/erasor_hip.h: erasor_hip_object_vote_*; kernels: erasor_amd/csrc/objects.hip.h), on the host -----
+# The host restatement of the device's contract.  Point i is voted iff votes[i] >= vote_thr and ground iff ground[i] != 0.  Ground points
+# are outside the graph: adjacent to nothing, in no cluster; over the others adjacency is cluster's, a cluster is a connected component
+# and its `first` the lowest index it contains in the GIVEN cloud's indexing.  Per cluster, in this order: OBJECT_NOT_OBJECT when n_points <
+# max(min_size, 1), or max_size != 0 and n_points > max_size, or max_extent > 0 and float64(max) - float64(min) > max_extent on some axis
+# (per-point votes stand); OBJECT_REMOVED when n_voted >= min_voted and float64(n_voted) >= remove_ratio * float64(n_points) (every
+# point goes); OBJECT_REVERTED when n_voted > 0 and float64(n_voted) <= revert_ratio * float64(n_points) (every point stays);
+# OBJECT_UNCHANGED otherwise (per-point votes stand).  A ground point is kept if ground_keep, otherwise removed iff voted.  One row per
+# touched cluster (n_voted > 0) in increasing `first`.  Counts, boxes and one float64 product per cluster: no float sum anywhere.
+OBJECT_UNCHANGED, OBJECT_REMOVED, OBJECT_REVERTED, OBJECT_NOT_OBJECT = 0, 1, 2, 3
+OBJECT_NONE = 0xFFFFFFFF
+OBJECT_ROW_DTYPE = np.dtype([(k, np.uint32) for k in ("first", "n_points", "n_voted", "n_dynamic", "n_voted_dynamic", "n_label_out_of_range")] +
+                            [("min_xyz", np.float32, 3), ("max_xyz", np.float32, 3), ("decision", np.uint32)])
+OBJECT_RESULT_FIELDS = ("n_points", "n_ground", "n_clusters", "n_touched", "n_removed_clusters", "n_reverted_clusters", "n_not_object", "n_voted",
+                        "n_removed", "n_grown", "n_grown_dynamic", "n_reverted", "n_reverted_dynamic", "n_ground_reverted",
+                        "n_ground_reverted_dynamic", "largest")
+
+
+def _object_args(cloud, votes, ground, tol, vote_thr, min_size, max_size, max_extent, remove_ratio, revert_ratio, min_voted):
+    c = np.ascontiguousarray(np.asarray(cloud, np.float32).reshape(-1, 4))
+    v = np.ascontiguousarray(np.asarray(votes, np.uint8).reshape(-1))
+    g = np.zeros(len(c), np.uint8) if ground is None else np.ascontiguousarray(np.asarray(ground, np.uint8).reshape(-1))
+    if len(v) != len(c) or len(g) != len(c):
+        raise ValueError("object_vote: votes and ground must have one entry per point")
+    if len(c) > 1 << 30:
+        raise ValueError("object_vote: more than 2^30 points")
+    if not (np.isfinite(tol) and tol > 0):
+        raise ValueError("object_vote: tol must be a finite number > 0")
+    if not 1 <= int(vote_thr) <= 255:
+        raise ValueError("object_vote: vote_thr must be within 1 .. 255")
+    if not (np.isfinite(max_extent) and max_extent >= 0):
+        raise ValueError("object_vote: max_extent must be 0 or a finite number > 0")
+    if not (0 < remove_ratio <= 1):
+        raise ValueError("object_vote: remove_ratio must be within (0, 1]")
+    if not (0 <= revert_ratio < 1) or revert_ratio >= remove_ratio:
+        raise ValueError("object_vote: revert_ratio must be within [0, 1) and below remove_ratio")
+    if min_size < 0 or max_size < 0 or min_voted < 0:
+        raise ValueError("object_vote: negative size limit")
+    if not np.isfinite(c[:, :3]).all():
+        raise ValueError("object_vote: non-finite coordinate")
+    return c, v, g != 0
+
+
+def object_decide(n_points, n_voted, min_xyz, max_xyz, min_size=1, max_size=0, max_extent=0.0, remove_ratio=0.5, revert_ratio=0.0, min_voted=1):
+    """the decision code of every cluster (arrays, one entry per cluster; the boxes float32 (k, 3)), tested in the contract's order"""
+    n = np.asarray(n_points, np.int64)
+    nv = np.asarray(n_voted, np.int64)
+    ext = np.asarray(max_xyz, np.float32).astype(np.float64) - np.asarray(min_xyz, np.float32).astype(np.float64)
+    gate = (n < max(int(min_size), 1)) | ((int(max_size) != 0) & (n > int(max_size)))
+    if max_extent > 0:
+        gate = gate | (ext > np.float64(max_extent)).any(axis=1)
+    nd, vd = n.astype(np.float64), nv.astype(np.float64)
+    removed = (nv >= int(min_voted)) & (vd >= np.float64(remove_ratio) * nd)
+    reverted = (nv > 0) & (vd <= np.float64(revert_ratio) * nd)
+    return np.where(gate, OBJECT_NOT_OBJECT, np.where(removed, OBJECT_REMOVED, np.where(reverted, OBJECT_REVERTED, OBJECT_UNCHANGED))).astype(np.uint32)
+
+
+def _object_finish(c, voted, is_ground, comp_any, min_size, max_size, max_extent, remove_ratio, revert_ratio, min_voted, ground_keep):
+    """mask, rows, ids, kept cloud and result from any labelling of the non-ground points' components (comp_any: an integer per non-ground
+    point, in the order of their indices)"""
+    n = len(c)
+    res = dict.fromkeys(OBJECT_RESULT_FIELDS, 0)
+    res["n_points"] = int(n)
+    ids = np.full(n, OBJECT_NONE, np.uint32)
+    if n == 0:
+        return np.zeros(0, np.uint8), np.zeros(0, OBJECT_ROW_DTYPE), ids, c.copy(), res
+    _, _, dyn = _decode(c[:, 3])
+    src = np.flatnonzero(~is_ground)  # (ascending: a cluster's lowest compacted index is its lowest given index)
+    removed = voted & ~(is_ground & bool(ground_keep))  # (the per-point votes; the clusters' decisions change them below)
+    rows = np.zeros(0, OBJECT_ROW_DTYPE)
+    if len(src):
+        rows_cl, comp, _, r_cl = _cluster_finish(np.ascontiguousarray(c[src]), comp_any, 1, 0)
+        k = len(rows_cl)
+        comp = comp.astype(np.int64)
+        n_voted = np.bincount(comp, voted[src], minlength=k).astype(np.int64)
+        code = object_decide(rows_cl["n_points"], n_voted, rows_cl["min_xyz"], rows_cl["max_xyz"], min_size, max_size, max_extent, remove_ratio,
+                             revert_ratio, min_voted)
+        touched = n_voted > 0
+        rows = np.zeros(int(touched.sum()), OBJECT_ROW_DTYPE)
+        rows["first"] = src[rows_cl["first"][touched]]
+        for f in ("n_points", "n_dynamic", "n_label_out_of_range", "min_xyz", "max_xyz"):
+            rows[f] = rows_cl[f][touched]
+        rows["n_voted"] = n_voted[touched]
+        rows["n_voted_dynamic"] = np.bincount(comp, voted[src] & dyn[src], minlength=k)[touched]
+        rows["decision"] = code[touched]
+        rank = np.full(k, OBJECT_NONE, np.uint32)
+        rank[touched] = np.arange(len(rows), dtype=np.uint32)
+        ids[src] = rank[comp]
+        pc = code[comp]
+        removed[src] = np.where(pc == OBJECT_REMOVED, True, np.where(pc == OBJECT_REVERTED, False, voted[src]))
+        res.update(n_clusters=int(k), n_touched=len(rows), n_removed_clusters=int((code[touched] == OBJECT_REMOVED).sum()),
+                   n_reverted_clusters=int((code[touched] == OBJECT_REVERTED).sum()), n_not_object=int((code[touched] == OBJECT_NOT_OBJECT).sum()),
+                   largest=r_cl["largest"])
+    grown, rev, grev = ~voted & removed, voted & ~is_ground & ~removed, voted & is_ground & ~removed
+    res.update(n_ground=int(is_ground.sum()), n_voted=int(voted.sum()), n_removed=int(removed.sum()), n_grown=int(grown.sum()),
+               n_grown_dynamic=int((grown & dyn).sum()), n_reverted=int(rev.sum()), n_reverted_dynamic=int((rev & dyn).sum()),
+               n_ground_reverted=int(grev.sum()), n_ground_reverted_dynamic=int((grev & dyn).sum()))
+    mask = (~removed).astype(np.uint8)
+    return mask, rows, ids, c[mask != 0].copy(), res
+
+
+def object_vote(cloud, votes, ground=None, tol=0.5, vote_thr=1, min_size=1, max_size=0, max_extent=0.0, remove_ratio=0.5, revert_ratio=0.0,
+                min_voted=1, ground_keep=True):
+    """A removal method's per-point votes decided per object.  `cloud`: XYZI rows; `votes`: uint8 per point (voted iff >= vote_thr: a sum
+    of several methods' votes with vote_thr=2 of three is their majority); `ground`: uint8 per point or None -- ground points are cut out
+    of the graph, which is what lets the objects standing on them fall apart into clusters.  Every cluster of the other points (cluster's
+    adjacency at `tol`) is removed whole when at least min_voted and the share remove_ratio of its points are voted, kept whole when at
+    most the share revert_ratio is, and left to its per-point votes otherwise or when it is no object (fewer than min_size or more than
+    max_size points, a box side above max_extent).  revert_ratio is 0 by default and nothing is reverted: where the ground mask is
+    incomplete one huge cluster holds every object through the ground, and its tiny vote share must not wipe the votes out -- set
+    max_size or max_extent before using revert_ratio.  Returns (mask, rows, ids, kept, result): uint8 per point, 1 = kept;
+    OBJECT_ROW_DTYPE records of the touched clusters (n_voted > 0) in increasing `first`; per point its row index or OBJECT_NONE (ground
+    points, points of untouched clusters); the rows with mask 1 in the order given; a dict with OBJECT_RESULT_FIELDS.  cKDTree only
+    proposes the pairs, as in cluster."""
+    c, v, g = _object_args(cloud, votes, ground, tol, vote_thr, min_size, max_size, max_extent, remove_ratio, revert_ratio, min_voted)
+    voted = v >= int(vote_thr)
+    src = np.flatnonzero(~g)
+    comp = None
+    if len(src):
+        c64 = c[src, :3].astype(np.float64)
+        pairs = cKDTree(c64).query_pairs(float(tol) * (1 + 1e-9), output_type="ndarray")
+        ok = cluster_adjacent(c[src[pairs[:, 0]], :3], c[src[pairs[:, 1]], :3], tol)
+        comp = _components(len(src), pairs[ok, 0], pairs[ok, 1])
+    return _object_finish(c, voted, g, comp, min_size, max_size, max_extent, remove_ratio, revert_ratio, min_voted, ground_keep)
+
+
+def object_vote_brute(cloud, votes, ground=None, tol=0.5, vote_thr=1, min_size=1, max_size=0, max_extent=0.0, remove_ratio=0.5, revert_ratio=0.0,
+                      min_voted=1, ground_keep=True):
+    """object_vote() with no tree: a plain flood fill from every non-ground point not yet reached, each step testing the predicate against
+    all non-ground points -- for a few thousand points"""
+    c, v, g = _object_args(cloud, votes, ground, tol, vote_thr, min_size, max_size, max_extent, remove_ratio, revert_ratio, min_voted)
+    voted = v >= int(vote_thr)
+    src = np.flatnonzero(~g)
+    c64 = c[src, :3].astype(np.float64)
+    t2 = np.float64(tol) * np.float64(tol)
+    comp = np.full(len(src), -1, np.int64)
+    for seed in range(len(src)):
+        if comp[seed] >= 0:
+            continue
+        comp[seed] = seed
+        stack = [seed]
+        while stack:
+            d = c64[stack.pop()][None, :] - c64
+            near = np.flatnonzero(((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2] <= t2) & (comp < 0))
+            comp[near] = seed
+            stack.extend(near.tolist())
+    return _object_finish(c, voted, g, comp if len(src) else None, min_size, max_size, max_extent, remove_ratio, revert_ratio, min_voted, ground_keep)
+
+
 # ---- k nearest neighbours, radius counts and the density filters (include/erasor_hip.h: erasor_hip_knn_* / _radius_count_* /
 # _density_filter_*; kernels: erasor_amd/csrc/knn.hip.h), on the host ---------------------------------------------------------------
 # The host restatement of the device's contract.  Distance: d2 = (ex*ex + ey*ey) + ez*ez in float64 with ex = float64(x_i) - float64(x_j),

@@ -1041,6 +1041,97 @@ int erasor_hip_cluster_map(erasor_hip_handle *h, double tol, size_t min_size, si
                            erasor_cluster_row *rows, size_t cap_rows, float *kept_xyzi, size_t cap_points,
                            erasor_cluster_result *res);
 
+/* ---- the decision per object: a removal method's votes spread over clusters, fragments reverted ------------------------------------
+ * replaces: nothing in the reference, which decides bin by bin and stops there; ERASOR2 decides per instance and Removert has a
+ * "revert" stage for the two failures this repairs -- half of a moving object left standing because no vote reached its lower part,
+ * and static structure chewed by stray votes.  Every removal method here decides one point at a time (a step by bin, the see-through
+ * check by pixel vote, the carving by voxel log-odds); this call takes such per-point votes, finds the objects they fall on and
+ * decides per object.  The contract, restated on the host by erasor_amd/evalmap.py (object_vote, object_vote_brute), which the device
+ * equals byte for byte; every definition is free of order:
+ *   - point i is VOTED iff votes[i] >= vote_thr (1 <= vote_thr <= 255; votes may be a sum over several methods: vote_thr 2 of three
+ *     is their majority) and GROUND iff ground[i] != 0 (ground NULL: no point is);
+ *   - ground points are outside the graph: adjacent to nothing, members of no cluster.  A ground point comes out kept if ground_keep,
+ *     otherwise removed iff voted.  The ground is what connects everything (a voxelised map is a handful of clusters at tol 0.5):
+ *     the mask is what cuts the objects loose;
+ *   - over the other points adjacency is erasor_hip_cluster_*'s: ((dx*dx + dy*dy) + dz*dz) <= tol*tol in float64 on the float32
+ *     coordinates, left to right, no fused multiply-add.  A cluster is a connected component; its `first` is the lowest index it
+ *     contains in the GIVEN cloud's indexing;
+ *   - a cluster's decision, tested in this order:
+ *       ERASOR_OBJECT_NOT_OBJECT (3)  n_points < max(min_size, 1), or max_size != 0 and n_points > max_size, or max_extent > 0 and
+ *                                     (double)max - (double)min > max_extent on some axis: per-point votes stand;
+ *       ERASOR_OBJECT_REMOVED (1)     n_voted >= min_voted and (double)n_voted >= remove_ratio * (double)n_points (one float64
+ *                                     multiply): every point of the cluster is removed;
+ *       ERASOR_OBJECT_REVERTED (2)    n_voted > 0 and (double)n_voted <= revert_ratio * (double)n_points: every point is kept;
+ *       ERASOR_OBJECT_UNCHANGED (0)   per-point votes stand;
+ *   - one row per TOUCHED cluster (n_voted > 0), in increasing `first`; untouched clusters are counted, not listed.
+ * With revert_ratio 0 (the default of every wrapper) nothing is ever reverted, on purpose: where the ground mask is incomplete one
+ * huge cluster holds every car through the ground, and its tiny vote share must not wipe the votes out.  Set max_size or max_extent
+ * before using revert_ratio.  As for the clusters there is no centroid and no float sum: counts, boxes and one float64 product per
+ * cluster, none of which depends on how the device scheduled its work. */
+enum { ERASOR_OBJECT_UNCHANGED = 0, ERASOR_OBJECT_REMOVED = 1, ERASOR_OBJECT_REVERTED = 2, ERASOR_OBJECT_NOT_OBJECT = 3 };
+
+typedef struct erasor_object_vote_params {
+    double tol;           /* finite, > 0 */
+    double max_extent;    /* 0: no limit; otherwise finite, > 0: the longest box side of an object */
+    double remove_ratio;  /* within (0, 1] */
+    double revert_ratio;  /* within [0, 1) and below remove_ratio; 0: nothing is reverted */
+    uint64_t min_size;    /* 0 is taken as 1 */
+    uint64_t max_size;    /* 0: no limit */
+    uint64_t min_voted;
+    uint32_t vote_thr;    /* 1 .. 255 */
+    uint32_t ground_keep; /* != 0: every ground point is kept; 0: a ground point is removed iff voted */
+} erasor_object_vote_params;
+
+typedef struct erasor_object_row {
+    uint32_t first;                 /* the lowest index of the cluster, in the given cloud's indexing */
+    uint32_t n_points;
+    uint32_t n_voted;
+    uint32_t n_dynamic;             /* points whose uint32(intensity) & 0xFFFF is in 252..259, decoded as erasor_hip_cluster_* does */
+    uint32_t n_voted_dynamic;
+    uint32_t n_label_out_of_range;
+    float min_xyz[3], max_xyz[3];   /* the box, per coordinate in float32's total order, copied as bits */
+    uint32_t decision;              /* ERASOR_OBJECT_* */
+} erasor_object_row;
+
+typedef struct erasor_object_vote_result {
+    uint64_t n_points;             /* points given */
+    uint64_t n_ground;
+    uint64_t n_clusters;           /* all clusters of the non-ground points, touched or not */
+    uint64_t n_touched;            /* rows */
+    uint64_t n_removed_clusters;
+    uint64_t n_reverted_clusters;
+    uint64_t n_not_object;         /* touched clusters with ERASOR_OBJECT_NOT_OBJECT */
+    uint64_t n_voted;              /* voted points, ground points included */
+    uint64_t n_removed;            /* points with mask 0: n_points - n_removed is the kept cloud's rows */
+    uint64_t n_grown;              /* unvoted points that come out removed ... */
+    uint64_t n_grown_dynamic;      /* ... and how many of them carry a dynamic label: whether the growth eats structure */
+    uint64_t n_reverted;           /* voted non-ground points that come out kept */
+    uint64_t n_reverted_dynamic;
+    uint64_t n_ground_reverted;    /* voted ground points that come out kept */
+    uint64_t n_ground_reverted_dynamic;
+    uint64_t largest;              /* the largest n_points of any cluster */
+} erasor_object_vote_result;
+
+/* The cloud (XYZI rows, on the host or on the handle's device: is_device) with one vote byte and, unless ground is NULL, one ground
+ * byte per point (host arrays of n bytes).  All outputs are host buffers and optional: mask (n bytes, 1 = kept, as the see-through
+ * check and the carving return it), ids (n entries: the point's row index, or 0xFFFFFFFF for ground points and points of untouched
+ * clusters), rows (cap_rows entries), kept_xyzi (cap_points rows: the rows with mask 1 in the order given, all four floats copied as
+ * bits).  n rows always suffice for either; a buffer that does not hold the result gives ERASOR_E_CAPACITY, with res, and mask and
+ * ids if asked for, filled first.  n == 0: ERASOR_OK and a zero result.  Works in the evaluator's own scratch: announced nodes,
+ * tickets and the last step's clouds stay as they are.  ERASOR_E_INVALID: a non-finite coordinate (of any point, ground or not), tol
+ * not a finite number > 0, remove_ratio outside (0, 1], revert_ratio outside [0, 1) or not below remove_ratio, vote_thr outside
+ * 1 .. 255, max_extent negative or not finite, more than 2^30 points, params, votes or res NULL.  ERASOR_E_STATE: a step in flight. */
+int erasor_hip_object_vote_clouds(erasor_hip_handle *h, const void *xyzi, size_t n, int is_device, const uint8_t *votes,
+                                  const uint8_t *ground, const erasor_object_vote_params *params, uint8_t *mask, uint32_t *ids,
+                                  erasor_object_row *rows, size_t cap_rows, float *kept_xyzi, size_t cap_points,
+                                  erasor_object_vote_result *res);
+/* the same over the handle's current map (the erasor_hip_get_map view, compacted on the device as erasor_hip_cluster_map does, never
+ * copied to the host); votes and ground index that view.  ERASOR_E_INVALID also: n is not erasor_hip_map_size.  ERASOR_E_STATE
+ * also: no map. */
+int erasor_hip_object_vote_map(erasor_hip_handle *h, const uint8_t *votes, const uint8_t *ground, size_t n,
+                               const erasor_object_vote_params *params, uint8_t *mask, uint32_t *ids, erasor_object_row *rows,
+                               size_t cap_rows, float *kept_xyzi, size_t cap_points, erasor_object_vote_result *res);
+
 /* ---- how dense the cloud is around each point: k nearest neighbours, radius counts, and the outlier filters on them ---------------
  * replaces: what users of a cleaned map run on the host next -- pcl::StatisticalOutlierRemoval and pcl::RadiusOutlierRemoval, a
  * KD-tree over the whole map -- to drop the single returns in the air, the thin shells dynamic removal leaves behind and the stray
